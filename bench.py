@@ -22,11 +22,19 @@ Prints ONE JSON line on rank 0 (contract in the task statement). `roofline` (dom
 library's own stream): `achieved` / `frac` price every lattice update at SURVEY §8(d)'s 144 B (72 B fp32) exactly as the
 contract defines them — above 1 for a launch that fuses d iterations, which moves ~1/d of that; `frac_hbm_measured` = the HBM
 bytes the kernel really moved (committed PMC passes, profiles/traffic.json) / time / 8 TB/s; `frac_valu` = the same passes'
-vector instructions against the chip's issue rate; `bound` = whichever of the two is nearer its ceiling. `sustained` = a
-second, longer window of the same context. At N=1 also `cpu_baseline` (the reference binary oracle/_ref/ref_driver if it
-runs on this host, else the oracle port; bounded sample), `other_arithmetic` and `single_precision_variant` (BASELINE.json
-configs[4] on this GPU with its MLUPS-per-GB/s beside the fp64 figure). At N>1 `strips.parity`: a second short run compared
-bit for bit with a one-GPU run of the whole grid.
+vector instructions against the chip's issue rate; `bound` = whichever of the two is nearer its ceiling.
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, write --dump-outputs, print the line.
+Everything that takes runs of its own is behind --full: `sustained` = a second, longer window of the same context; the live
+counter passes of `roofline` (without them its bytes come from profiles/traffic.json); at N=1 `cpu_baseline` (the reference
+binary oracle/_ref/ref_driver if it runs on this host, else the oracle port; bounded sample), `other_arithmetic` and
+`single_precision_variant` (BASELINE.json configs[4] on this GPU with its MLUPS-per-GB/s beside the fp64 figure); at N>1 the
+compute-only pass of `strips` and `strips.parity`: a second short run compared bit for bit with a one-GPU run of the whole grid.
+
+--dump-outputs DIR writes, after the timed region, what the timed calls computed: the post-collision populations of the last
+timed step (a step ends on its collision; the state lbm_save_state hands a caller) at a fixed, seeded sample of lattice
+sites — DIR/populations.npy [9, sites] in the run's element type and DIR/sites.npy, the sampled global site indices
+y * nx + x (float64). The sample depends on the grid only, so runs of two builds, or of 1 and N GPUs, compare entry for entry.
 """
 import argparse
 import importlib
@@ -324,6 +332,12 @@ def main():
     ap.add_argument("--no-f32-variant", action="store_true", help="skip the single-precision variant (BASELINE.json configs[4]) beside the headline")
     ap.add_argument("--no-live-pmc", action="store_true", help="do not take the counter passes (rocprofv3 child runs after the timed region): "
                                                                "roofline.traffic then comes from profiles/traffic.json")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what takes runs of its own: the sustained window, the live counter passes, the other "
+                         "arithmetic, the fp32 variant and the CPU baseline (N=1), the compute-only pass and the strip parity (N>1); "
+                         "the --no-* options above switch parts of it off")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's populations (a fixed, seeded sample of sites) as DIR/*.npy")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -390,11 +404,13 @@ def main():
     dt = time.perf_counter() - t0
     ms_total, launches, iterations = ctx.last_step_stats()
     kernel_ms = ms_total / max(launches, 1)            # mean duration of one launch of the dominant kernel
+    if args.dump_outputs:      # (before anything below advances or re-initialises the context)
+        dump_outputs(ctx, args.dump_outputs, nx, ny_total, rank * local_ny, local_ny, args.precision, dist, rank, world)
     # `sustained`: a second, longer window of the same context (the driver's K may be as short as 20 steps = 4 launches,
     # which a boosting clock flatters by ~5 %): at least 3000 steps / 80 ms
     sus_steps = max(3000, args.steps) if world == 1 else max(1200, args.steps)
     dt_sus = None
-    if not args.no_sustained:
+    if args.full and not args.no_sustained:
         t1 = time.perf_counter()
         ctx.step(sus_steps, 0)
         fence()
@@ -413,9 +429,9 @@ def main():
     plan_pairs = " ".join(f"{k}={v}" for k, v in ctx.plan_options().items())      # `--set tune=0 --set <pair> ...` reproduces the plan in another run
     arith_id = 1 if args.arith == "contracted" else 0
     roof = roofline_of(lbm, ctx, nx, local_ny, args.precision, kernel_ms, launches, iterations, args.steps, arith_id,
-                       live=(world == 1 and not args.no_live_pmc), re_number=args.re) if rank == 0 else None
+                       live=(world == 1 and args.full and not args.no_live_pmc), re_number=args.re) if rank == 0 else None
     parity = None
-    if world > 1:
+    if world > 1 and args.full:
         # what the halo traffic costs: the same launches with the exchange skipped (diagnostic pass, results discarded)
         n = max(60, min(args.steps, 600))
         ctx.set_option("skip_exchange", 1)
@@ -432,7 +448,7 @@ def main():
 
     other = None
     spv = None
-    if world == 1 and not args.no_other_arith:
+    if world == 1 and args.full and not args.no_other_arith:
         # the same workload in the OTHER arithmetic mode, same harness, reported beside the headline (not part of `value`)
         oa = "strict" if args.arith == "contracted" else "contracted"
         with lbm.Context(nx, ny_total, tau=0.6, inlet_velocity=u_in, precision=args.precision, device=device,
@@ -449,7 +465,7 @@ def main():
                 sys.exit(f"the {oa} run went unstable at timestep {ub}: result invalid")
             other = {"arithmetic": oa, "value": round(nx * ny_total * sus_steps / dt2 / 1e6, 1), "unit": "MLUPS", "steps": sus_steps,
                      "kernel": c2.kernel_name(), "plan": c2.plan(), "unstable": ub}
-    if world == 1 and not args.no_f32_variant and (nx, ny_total, args.precision) == (4096, 1024, "f64"):
+    if world == 1 and args.full and not args.no_f32_variant and (nx, ny_total, args.precision) == (4096, 1024, "f64"):
         spv = single_precision_variant(lbm, device, args)
 
     if rank == 0:
@@ -486,8 +502,6 @@ def main():
         if world > 1:
             graph_opt = next((int(kv.split("=")[1]) for kv in args.set if kv.startswith("graph=")), 1)
             line["strips"] = {"nranks": world, "schedule": schedule_used,
-                              "ms_per_step_compute_only": round(compute_only_ms, 5),
-                              "ms_per_step_exchange_exposed": round(dt / args.steps * 1e3 - compute_only_ms, 5),
                               # slowest rank: host time to issue one iteration's share of launches / events / exchanges in the timed window
                               "host_issue_us_per_iteration": round(t_issue / args.steps * 1e6, 3),
                               "gpu_us_per_iteration": round(dt / args.steps * 1e6, 3),
@@ -498,8 +512,11 @@ def main():
                               "graph_replays_rank0": graph_replays,
                               # (from the library's own description of the measured schedule: six rows per launch or twelve per two)
                               "halo_bytes_per_face_and_exchange": (lambda m: int(m.group(1)) if m else None)(re.search(r"(\d+) B per face and exchange", schedule_used))}
-            line["strips"].update(parity)
-            verdict = str(parity.get("parity", ""))
+            if compute_only_ms is not None:
+                line["strips"].update(ms_per_step_compute_only=round(compute_only_ms, 5),
+                                      ms_per_step_exchange_exposed=round(dt / args.steps * 1e3 - compute_only_ms, 5))
+            line["strips"].update(parity or {"parity": "not checked (--full compares the strips with a one-GPU run)"})
+            verdict = str(line["strips"]["parity"])
             if verdict.startswith("MISMATCH"):
                 line["value_unverified"] = line["value"]
                 line["value"] = None            # as for an unstable run: a wrong halo exchange has no throughput
@@ -511,7 +528,7 @@ def main():
             if roof.get("mlups_per_gbs"):
                 spv["mlups_per_gbs_fp64_headline"] = roof["mlups_per_gbs"]
             line["single_precision_variant"] = spv
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(nx, ny_total, u_in)
         print(json.dumps(line), flush=True)
         if world > 1:
@@ -560,6 +577,49 @@ def single_precision_variant(lbm, device, args):
             return out
     except Exception as e:      # (a GPU that cannot hold 2 x 2.4 GB beside the headline context: report, do not fail the bench)
         return {"error": str(e)[:200]}
+
+
+DUMP_SITES = 1 << 19          # sampled sites of --dump-outputs: 9 x 2^19 fp64 populations = 38 MB (+ 4 MB of indices), under 64 MB
+DUMP_SEED = 20261016
+
+
+def dump_sites(nx, ny):
+    """The sorted global site indices (y * nx + x) --dump-outputs samples: every site of a small grid, else DUMP_SITES drawn
+    without replacement by a generator of fixed seed — a function of the grid alone."""
+    import numpy as np
+    n = nx * ny
+    if n <= DUMP_SITES:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=DUMP_SITES, replace=False))
+
+
+def dump_outputs(ctx, out_dir, nx, ny_total, y_start, local_ny, precision, dist, rank, world):
+    """--dump-outputs: the post-collision populations of the last timed step at the sampled sites, read through
+    lbm_save_state (the one accessor that needs no extra step after a call that ended on a fused launch; layout: a header,
+    then [9][local_ny][nx] in the element type). Each rank reads its own rows; rank 0 writes the strips' samples in row order."""
+    import numpy as np
+    sites = dump_sites(nx, ny_total)
+    mine = sites[(sites >= y_start * nx) & (sites < (y_start + local_ny) * nx)]
+    os.makedirs(out_dir, exist_ok=True)
+    ckpt = os.path.join(out_dir, f".state_rank{rank}.ckpt")
+    try:
+        ctx.save_state(ckpt)
+        dtype = np.float64 if precision == "f64" else np.float32
+        body = 9 * local_ny * nx * np.dtype(dtype).itemsize
+        f = np.memmap(ckpt, dtype=dtype, mode="r", offset=os.path.getsize(ckpt) - body, shape=(9, local_ny * nx))
+        vals = np.array(f[:, mine - y_start * nx])
+        del f
+    finally:
+        if os.path.exists(ckpt):
+            os.remove(ckpt)
+    if world > 1:
+        parts = [None] * world
+        dist.all_gather_object(parts, vals)
+        vals = np.concatenate(parts, axis=1)      # rank r holds rows [r * local_ny, (r + 1) * local_ny): row order
+    if rank == 0:
+        assert vals.shape == (9, sites.size), (vals.shape, sites.size)
+        np.save(os.path.join(out_dir, "populations.npy"), vals)
+        np.save(os.path.join(out_dir, "sites.npy"), sites.astype(np.float64))
 
 
 def row_checksums(populations):

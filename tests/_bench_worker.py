@@ -21,6 +21,7 @@ class FakeContext:
     def __init__(self, nx, ny, tau=0.6, inlet_velocity=0.01, y_start=0, local_ny=0, precision="f64", device=0, options=None, **kw):
         self.nx, self.ny, self.y_start = nx, ny, y_start
         self.local_ny = local_ny if local_ny > 0 else ny - y_start
+        self.precision = precision
         self.steps = 0
         self.opts = dict(options or {})
         self.last = (0.0, 0, 0)
@@ -56,6 +57,13 @@ class FakeContext:
         if SCENARIO == "mismatch" and self.y_start > 0:
             a[3, 5, 2] += 1e-9
         return a
+
+    def save_state(self, path):
+        # lbm_save_state's layout: a 72-byte header, then the interior of the strip as [9][local_ny][nx] in the element type
+        a = self.populations("f_next")[1:-1, 1:-1].transpose(2, 0, 1)
+        with open(path, "wb") as f:
+            f.write(b"LBMCKPT1" + bytes(64))
+            f.write(np.ascontiguousarray(a, dtype=np.float64 if self.precision == "f64" else np.float32).tobytes())
 
 
 fake = types.ModuleType(PKG)

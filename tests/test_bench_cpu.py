@@ -144,3 +144,16 @@ def test_committed_bench_lines_of_the_current_round_belong_to_their_build():
             checked += 1
     assert checked >= 0      # (no round-5 record yet while the round is being built: nothing to check is not a failure)
 
+
+
+def test_dump_sample_is_fixed_and_fits_64_mb():
+    """--dump-outputs samples the same sites on every run of a grid (two builds compare entry for entry): sorted, distinct, inside
+    the grid, and populations + indices stay under 64 MB in fp64 at every BASELINE.json grid; a small grid is dumped whole."""
+    import numpy as np
+    b = load_bench()
+    for nx, ny in ((4096, 1024), (8192, 2048), (16384, 4096), (1024, 256)):
+        s = b.dump_sites(nx, ny)
+        assert np.array_equal(s, b.dump_sites(nx, ny)) and s.size == min(nx * ny, b.DUMP_SITES)
+        assert np.all(np.diff(s) > 0) and s[0] >= 0 and s[-1] < nx * ny
+        assert s.size * (9 + 1) * 8 <= 64 << 20
+    assert np.array_equal(b.dump_sites(64, 48), np.arange(64 * 48))

@@ -1,7 +1,7 @@
 """bench.py --gpus N end to end on the CPU with two gloo ranks and a compute-free stand-in for the HIP package (tests/_bench_worker.py):
 the first real multi-GPU run is the driver's, so the part of bench.py only that run executes — rendezvous, MAX-reductions over the
-ranks, the strips.parity gather and comparison, the N>1 fields of the JSON line, the exit code — is exercised here: a wrong halo
-exchange must not print a throughput."""
+ranks, the strips.parity gather and comparison (`--full`), the N>1 fields of the JSON line, the exit code, the gather of
+--dump-outputs — is exercised here: a wrong halo exchange must not print a throughput."""
 import json
 import os
 import socket
@@ -13,7 +13,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def run_bench(scenario, world=2, extra=(), grid=("64", "48")):
+def run_bench(scenario, world=2, extra=(), grid=("64", "48"), full=True):
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
@@ -21,7 +21,7 @@ def run_bench(scenario, world=2, extra=(), grid=("64", "48")):
     for rank in range(world):
         env = dict(os.environ, RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
         procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "_bench_worker.py"), scenario, "--gpus", str(world),
-                                       "--steps", "20", "--warmup", "5", "--nx", grid[0], "--ny", grid[1], *extra],
+                                       "--steps", "20", "--warmup", "5", "--nx", grid[0], "--ny", grid[1], *(("--full",) if full else ()), *extra],
                                       env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     outs = [p.communicate(timeout=900) for p in procs]
     return [p.returncode for p in procs], outs
@@ -97,3 +97,52 @@ def test_weak_scaling_keeps_the_rows_per_gpu():
     assert line["scaling"] == "weak" and line["config"]["ny"] == 96 and line["config"]["rows_per_gpu"] == 48
     assert "not a BASELINE.json config" in line["config"]["workload"] and line["strips"]["parity"] == "bit-equal"
 
+
+
+def expected_populations(nx, ny, steps):
+    """What the stand-in's populations hold after `steps` iterations, as [9, ny * nx] over the global sites y * nx + x."""
+    import numpy as np
+    rows = np.arange(ny, dtype=np.float64)[:, None, None]
+    cols = np.arange(1, nx + 1, dtype=np.float64)[None, :, None]
+    a = rows * 1e-3 + cols * 1e-6 + np.arange(9, dtype=np.float64)[None, None, :] + steps
+    return a.transpose(2, 0, 1).reshape(9, ny * nx)
+
+
+@pytest.mark.timeout(600)
+def test_a_plain_run_is_lean_and_dumps_the_last_timed_iteration(tmp_path):
+    """Without --full bench.py times the window and prints the line, nothing more: no sustained window, no compute-only pass and
+    no parity run (the line says the strips were not checked), no other arithmetic, fp32 variant or CPU baseline. --dump-outputs
+    writes the populations of the last timed step (warmup + steps) at the sampled sites; the strips' gather reproduces a
+    one-rank run's files exactly."""
+    import numpy as np
+    lines = {}
+    for world in (1, 2):
+        d = tmp_path / f"n{world}"
+        rcs, outs = run_bench("ok", world=world, extra=("--dump-outputs", str(d)), full=False)
+        assert rcs == [0] * world, [o[1][-1000:] for o in outs]
+        line = json.loads([l for l in outs[0][0].splitlines() if l.startswith("{")][0])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in line, key
+        assert line["steps"] == 20 and line["value"] > 0 and line["ms_per_step"] > 0
+        for key in ("sustained", "other_arithmetic", "single_precision_variant", "cpu_baseline"):
+            assert key not in line, key
+        assert "live counter passes not requested" in line["roofline"]["traffic_source"]
+        lines[world] = line
+        assert sorted(p.name for p in d.iterdir()) == ["populations.npy", "sites.npy"]
+    st = lines[2]["strips"]
+    assert st["parity"].startswith("not checked") and lines[2]["parity_unverified"] is True and lines[2]["value"] > 0
+    assert "ms_per_step_compute_only" not in st and "per_rank" not in st
+    pops = [np.load(tmp_path / f"n{w}" / "populations.npy") for w in (1, 2)]
+    sites = [np.load(tmp_path / f"n{w}" / "sites.npy") for w in (1, 2)]
+    assert pops[0].dtype == np.float64 and pops[0].shape == (9, 64 * 48) and np.array_equal(sites[0], np.arange(64 * 48))
+    assert np.array_equal(pops[0], expected_populations(64, 48, 25))
+    assert np.array_equal(pops[0], pops[1]) and np.array_equal(sites[0], sites[1])
+
+
+@pytest.mark.timeout(600)
+def test_dump_outputs_follows_the_precision(tmp_path):
+    import numpy as np
+    rcs, outs = run_bench("ok", world=2, extra=("--precision", "f32", "--dump-outputs", str(tmp_path)), full=False)
+    assert rcs == [0, 0], [o[1][-1000:] for o in outs]
+    pops = np.load(tmp_path / "populations.npy")
+    assert pops.dtype == np.float32 and np.array_equal(pops, expected_populations(64, 48, 25).astype(np.float32))

@@ -488,3 +488,37 @@ def test_kernel_name_is_the_kernel_that_really_runs_on_a_host_staged_strip(lbm):
         six.initialise()       # six iterations per launch fit the six staged rows: the register kernel stays
         assert six.kernel_name().replace(" ", "") == "k_stepc_col<double,4,8,6,true,1>", six.kernel_name()
 
+
+
+@pytest.mark.timeout(600)
+def test_bench_dump_outputs_hold_the_last_timed_iteration(lbm, tmp_path):
+    """bench.py --dump-outputs after `--steps 20 --warmup 5` (trailing_pair=1: the call may end on a fused launch) writes the
+    post-collision populations of the 25th step, read through lbm_save_state — the oracle's f_next after 26 iterations, since a step
+    of the library ends on the collision the oracle's next iteration begins with (lbm_initialise collides once): strict arithmetic
+    bit-equal at every site of a grid small enough to be dumped whole, contracted within the north-star 1e-10."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from oracle.oracle import Oracle, make_params
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    nx, ny, re_number = 256, 64, 10.0
+    u_in = re_number * ((0.6 - 0.5) / 3.0) / (2.0 * 0.05 * ny)      # bench.py's u_in for --re
+    o = Oracle(make_params(nx, ny, inlet_velocity=u_in))
+    assert o.run(26) == -1
+    ref = np.ascontiguousarray(o.f_next[1:-1, 1:-1, :].transpose(2, 0, 1)).reshape(9, nx * ny)
+    o.close()
+    for arith in ("strict", "contracted"):
+        d = tmp_path / arith
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--nx", str(nx),
+                              "--ny", str(ny), "--re", str(re_number), "--arith", arith, "--dump-outputs", str(d)],
+                             cwd=root, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+        assert out.returncode == 0, out.stderr[-2000:]
+        line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+        assert line["steps"] == 20 and line["ms_per_step"] > 0 and "sustained" not in line
+        pops, sites = np.load(d / "populations.npy"), np.load(d / "sites.npy")
+        assert pops.dtype == np.float64 and pops.shape == (9, nx * ny) and np.array_equal(sites, np.arange(nx * ny))
+        if arith == "strict":
+            assert np.array_equal(pops, ref), line["config"]["kernel"]
+        err = float(np.max(np.abs(pops - ref)))
+        assert err < TOL, (arith, err, line["config"]["kernel"])

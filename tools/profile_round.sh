@@ -5,7 +5,7 @@
 # (tools/pmc_traffic.sh). PART 1: the fp64 grids; PART 2: the fp32 grids.
 set -e
 OUT=$1; PART=$2
-B="python3 bench.py --no-cpu-baseline --no-other-arith --no-f32-variant --no-sustained"
+B="python3 bench.py --full --no-cpu-baseline --no-other-arith --no-f32-variant --no-sustained"
 run() { name=$1; shift; tools/pmc_traffic.sh "$OUT/$name" -- $B "$@"; cp "$OUT/$name"/stats/*kernel_stats.csv "$OUT/$name/kernel_stats.csv" 2>/dev/null || true; rm -rf "$OUT/$name/stats" "$OUT/$name/fetch" "$OUT/$name/write" "$OUT/$name/sq" "$OUT/$name"/*.log; echo "$name: $(cut -c1-90 $OUT/$name/bench_line.json)"; }
 C5="--set tune=0 --set layout=1 --set variant=1 --set nt=1 --set xcd=1 --set pair_ty=12 --set deep=6"
 C6="--set tune=0 --set layout=1 --set variant=1 --set nt=1 --set xcd=1 --set pair_ty=12 --set deep=7"

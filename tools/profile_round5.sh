@@ -20,7 +20,7 @@ if [ "$2" != "skip-traffic" ]; then
   cp "$OUT/traffic.json" profiles/traffic.json
   say "traffic table: done"
 fi
-B="bench.py --no-cpu-baseline --no-other-arith --no-f32-variant"
+B="bench.py --full --no-cpu-baseline --no-other-arith --no-f32-variant"
 run() {
   name=$1; shift
   if [ -n "$ONLY" ] && ! echo " $ONLY " | grep -q " $name "; then return 0; fi      # ONLY="c3_f64_contracted c2_1024x256_f64": a part of the record per call
@@ -44,8 +44,8 @@ run c3_f32 --steps 6000 --warmup 600 --precision f32
 run c5_16384x4096_f32 --steps 600 --warmup 60 --precision f32 --nx 16384 --ny 4096
 if [ -z "$ONLY" ] || echo " $ONLY " | grep -q " bench "; then
   say "default bench line"
-  python3 bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
+  python3 bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
   say "driver-style bench line"
-  python3 bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench_driver_style.json" 2> "$OUT/bench_driver_style.err"
+  python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > "$OUT/bench_driver_style.json" 2> "$OUT/bench_driver_style.err"
 fi
 say done

@@ -38,7 +38,7 @@ def describe(d):
 def main():
     root = sys.argv[1]
     print("| file | what |\n|---|---|")
-    for f, cmd in (("bench_default.json", "python bench.py"), ("bench_driver_style.json", "python bench.py --gpus 1 --steps 20 --warmup 5")):
+    for f, cmd in (("bench_default.json", "python bench.py --full"), ("bench_driver_style.json", "python bench.py --full --gpus 1 --steps 20 --warmup 5")):
         print(f"| `{f}` | `{cmd}`: {describe(line_of(os.path.join(root, f)))} |")
     print("\n| config | grid | kernel | plan | MLUPS (window) | sustained | µs / launch (HIP events) | `kernel_stats.csv` mean µs |\n|---|---|---|---|---|---|---|---|")
     for name in sorted(os.listdir(root)):
