@@ -56,6 +56,10 @@ def lib():
         L.lbm_get_populations.argtypes = [vp, C.c_int, dp]
         L.lbm_set_f_current.argtypes = [vp, dp]
         L.lbm_get_solid.argtypes = [vp, C.POINTER(C.c_ubyte)]
+        L.lbm_set_solid_mask.argtypes = [vp, C.POINTER(C.c_ubyte), C.c_int, C.c_int]
+        ip = C.POINTER(C.c_int)
+        L.lbm_debug_geometry.argtypes = [C.POINTER(C.c_ubyte), C.c_int, C.c_int, C.c_int, C.c_int, ip, C.POINTER(C.c_ulonglong), C.c_long,
+                                         ip, C.c_long, ip, C.c_int, ip]
         L.lbm_comm_unique_id.argtypes = [vp]
         L.lbm_comm_init.argtypes = [vp, C.c_int, C.c_int, vp]
         L.lbm_comm_allreduce.argtypes = [vp, dp, C.c_int, C.c_int]
@@ -108,16 +112,52 @@ def build_id():
     return lib().lbm_build_id().decode()
 
 
+def _mask_bytes(solid, nx, ny):
+    """A bool / integer (ny, nx) array as the contiguous uint8 0/1 array lbm_set_solid_mask reads."""
+    m = np.asarray(solid)
+    if m.shape != (ny, nx):
+        raise ValueError(f"solid mask has shape {m.shape}, the domain is (ny, nx) = {(ny, nx)}")
+    if not (m.dtype == np.bool_ or np.issubdtype(m.dtype, np.integer)):
+        raise TypeError(f"solid mask must be bool or uint8, not {m.dtype}")
+    return np.ascontiguousarray(m != 0, dtype=np.uint8)
+
+
+def debug_geometry(solid, y_start=0, local_ny=0, boxes=()):
+    """lbm_debug_geometry (no device): the packing lbm_set_solid_mask makes for one strip of a global (ny, nx) mask.
+    Returns (dims, bits [rows, words] uint64, sat [nby+1, nbx+1] int32, near [len(boxes)]) with dims = {y0, rows, words, nbx, nby,
+    bx0, bx1, by0, by1}; boxes = [(x0, x1, y0, y1)] global inclusive, near[k] = the kernels' near-solid query for box k."""
+    L = lib()
+    ny, nx = np.shape(solid)
+    m = _mask_bytes(solid, nx, ny)
+    local_ny = local_ny if local_ny > 0 else ny - y_start
+    dims = (C.c_int * 9)()
+    ub = C.POINTER(C.c_ubyte)
+    if L.lbm_debug_geometry(m.ctypes.data_as(ub), nx, ny, y_start, local_ny, dims, None, 0, None, 0, None, 0, None) < 0:
+        raise LbmError(L.lbm_last_error().decode())
+    d = dict(zip(("y0", "rows", "words", "nbx", "nby", "bx0", "bx1", "by0", "by1"), list(dims)))
+    bits = np.zeros((d["rows"], d["words"]), dtype=np.uint64)
+    sat = np.zeros((d["nby"] + 1, d["nbx"] + 1), dtype=np.int32)
+    b = np.ascontiguousarray(np.asarray(boxes, dtype=np.int32).reshape(-1, 4))
+    near = np.zeros(len(b), dtype=np.int32)
+    ip = C.POINTER(C.c_int)
+    rc = L.lbm_debug_geometry(m.ctypes.data_as(ub), nx, ny, y_start, local_ny, dims, bits.ctypes.data_as(C.POINTER(C.c_ulonglong)), bits.size,
+                              sat.ctypes.data_as(ip), sat.size, b.ctypes.data_as(ip), len(b), near.ctypes.data_as(ip))
+    if rc < 0:
+        raise LbmError(L.lbm_last_error().decode())
+    return d, bits, sat, near
+
+
 def _dp(a):
     return a.ctypes.data_as(C.POINTER(C.c_double)) if a is not None else None
 
 
 class Context:
-    """One strip of the lattice on one GPU (struct lbm_ctx)."""
+    """One strip of the lattice on one GPU (struct lbm_ctx). solid: optional bool / uint8 (ny, nx) array of the WHOLE domain, row
+    y = 0 first, nonzero = solid (lbm_set_solid_mask): the obstacle geometry in place of the cylinder_* disc."""
 
     def __init__(self, nx, ny, tau=0.6, inlet_velocity=0.01333, cylinder_x=0.2, cylinder_y=0.5,
                  cylinder_radius=0.05, y_start=0, local_ny=0, precision="f64", device=0, force_log_capacity=0,
-                 options=None):
+                 options=None, solid=None):
         self.L = lib()
         self.params = Params(tau, inlet_velocity, nx, ny, cylinder_x, cylinder_y, cylinder_radius, y_start,
                              local_ny, {"f64": 0, "f32": 1}[precision], force_log_capacity)
@@ -129,6 +169,8 @@ class Context:
         self.solid_count = None
         for k, v in (options or {}).items():
             self.set_option(k, v)
+        if solid is not None:
+            self.set_solid_mask(solid)
 
     def _chk(self, rc):
         if rc < 0:
@@ -154,6 +196,11 @@ class Context:
 
     def set_option(self, key, value):
         self._chk(self.L.lbm_set_option(self.h, key.encode(), int(value)))
+
+    def set_solid_mask(self, solid):
+        """lbm_set_solid_mask: the global (ny, nx) mask; before initialise()."""
+        m = _mask_bytes(solid, self.nx, self.ny)
+        self._chk(self.L.lbm_set_solid_mask(self.h, m.ctypes.data_as(C.POINTER(C.c_ubyte)), self.nx, self.ny))
 
     def initialise(self):
         n = C.c_int()
@@ -280,15 +327,16 @@ class Context:
 
 class Group:
     """n strips of one lattice driven in lockstep by this process (lbm_group_*): one Context per strip, bottom to top.
-    transport: "peer" (device copies / hipMemcpyPeerAsync) or "rccl" (ncclCommInitAll; distinct devices)."""
+    transport: "peer" (device copies / hipMemcpyPeerAsync) or "rccl" (ncclCommInitAll; distinct devices).
+    solid: optional global (ny, nx) obstacle mask, given to every member (Context)."""
 
-    def __init__(self, nx, ny, bounds, devices=None, transport="peer", options=None, **kw):
+    def __init__(self, nx, ny, bounds, devices=None, transport="peer", options=None, solid=None, **kw):
         from .strips import partition_rows
         if isinstance(bounds, int):
             bounds = partition_rows(ny, bounds)
         devices = devices or [0] * len(bounds)
         self.nx, self.ny = nx, ny
-        self.ctxs = [Context(nx, ny, y_start=y0, local_ny=n, device=d, options=options, **kw)
+        self.ctxs = [Context(nx, ny, y_start=y0, local_ny=n, device=d, options=options, solid=solid, **kw)
                      for (y0, n), d in zip(bounds, devices)]
         self.L = lib()
         self._arr = (C.c_void_p * len(self.ctxs))(*[c.h for c in self.ctxs])

@@ -239,6 +239,13 @@ struct lbm_ctx {
     bool initialised = false;
     double feq_in[Q];
     int cyl_x = 0, cyl_y = 0, cyl_r = 0;
+    // user-defined geometry (lbm_set_solid_mask): the strip's window of the mask, packed on the host (lbm_geom.hpp), and its device
+    // copy (read-only: uploaded once, never written by a kernel). has_mask false: the disc of cyl_* is the geometry.
+    bool has_mask = false;
+    HostMask hmask;
+    MaskView mview;                  // device pointers of hmask's bitmap and coarse table
+    double* d_fpart = nullptr;       // k_forces: partial sums of the chunks of a large force box (masked contexts only)
+    int fpart_chunks = 0;
     // options
     int alternate = 1;   // walk the rows bottom-up / top-down on alternate steps (Infinity Cache reuse)
     int use_nt = 0;      // non-temporal stores in the step kernel

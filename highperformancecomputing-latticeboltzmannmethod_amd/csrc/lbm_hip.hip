@@ -3,6 +3,7 @@
 #include "lbm_kernels.hpp"
 #include "lbm_col_api.hpp"
 #include "lbm_plan.hpp"
+#include "lbm_geom.hpp"
 #include "../../include/lbm_hip.h"
 
 #include <rccl/rccl.h>
@@ -54,6 +55,8 @@ int allreduce_doubles(lbm_ctx* c, double* vals, int n, int op) {
 // File: header {magic "LBMCKPT1", nx, ny, y_start, local_ny, precision, steps_done, tau, inlet_velocity, cylinder_*}
 // followed by the post-collision populations P_{steps_done} of the strip's interior, [9][local_ny][nx] in the
 // element type. The state is complete: ghost cells and solid cells are reconstructed by lbm_initialise.
+// A context with a user-defined geometry (lbm_set_solid_mask) writes magic "LBMCKPT2" and the mask's 64-bit digest between the
+// header and the populations; it loads only such a file with the same digest, and an unmasked context only "LBMCKPT1" files.
 namespace {
 struct CkptHeader {
     char magic[8];
@@ -229,7 +232,7 @@ void lbm_destroy(lbm_ctx* c) {
     if (c->comm) { lbm_trace("destroy", "ctx %p ncclCommDestroy", (void*)c); ncclCommDestroy(c->comm); }
     c->pool.reset();
     void* ptrs[] = {c->buf[0], c->buf[1], c->scratch, c->d_macro, c->d_maxbits, c->d_unstable, c->d_tbase, c->d_solid_count, c->d_feq,
-                    c->d_force_now, c->d_force_log, c->d_halo, c->d_red};
+                    c->d_force_now, c->d_force_log, c->d_halo, c->d_red, (void*)c->mview.bits, (void*)c->mview.sat, c->d_fpart};
     for (void* q : ptrs)
         if (q) (void)hipFree(q);
     hipEvent_t evs[] = {c->ev_edge, c->ev_comm, c->ev_main, c->ev_t0, c->ev_t1, c->gev_main, c->gev_edge, c->gev_comm};
@@ -384,12 +387,46 @@ int lbm_set_f_current(lbm_ctx* c, const double* aos) {
 
 int lbm_get_solid(lbm_ctx* c, unsigned char* mask) {
     if (!c || !mask) return fail(LBM_ERR_ARG, "null argument");
+    if (c->has_mask) {
+        const MaskView m = c->hmask.view();
+        for (int y = 0; y < c->nyl; ++y)
+            for (int x = 0; x < c->nx; ++x) mask[(size_t)y * c->nx + x] = mask_cell(m, x, c->p.y_start + y) ? 1 : 0;
+        return LBM_OK;
+    }
     const double r2 = (double)(c->cyl_r * c->cyl_r);
     for (int y = 0; y < c->nyl; ++y)
         for (int x = 0; x < c->nx; ++x) {
             const double dx = x - c->cyl_x, dy = (c->p.y_start + y) - c->cyl_y;
             mask[(size_t)y * c->nx + x] = (dx * dx + dy * dy <= r2) ? 1 : 0;
         }
+    return LBM_OK;
+}
+
+int lbm_set_solid_mask(lbm_ctx* c, const unsigned char* mask, int nx, int ny) {
+    if (!c || !mask) return fail(LBM_ERR_ARG, "lbm_set_solid_mask: null argument");
+    if (c->initialised) return fail(LBM_ERR_ARG, "lbm_set_solid_mask must be called before lbm_initialise");
+    if (nx != c->nx || ny != c->p.ny) return fail(LBM_ERR_ARG, "lbm_set_solid_mask: mask is %dx%d, the domain %dx%d", nx, ny, c->nx, c->p.ny);
+    HostMask h = pack_mask(mask, nx, ny, c->p.y_start, c->nyl);
+    HIPCHK(hipSetDevice(c->device));
+    if (c->mview.bits) { HIPCHK(hipFree((void*)c->mview.bits)); c->mview.bits = nullptr; }
+    if (c->mview.sat) { HIPCHK(hipFree((void*)c->mview.sat)); c->mview.sat = nullptr; }
+    if (c->d_fpart) { HIPCHK(hipFree(c->d_fpart)); c->d_fpart = nullptr; }
+    c->has_mask = false;
+    // device copies of the bitmap and the coarse table (owned by the context from the moment they exist: lbm_destroy frees them)
+    c->mview = h.view();
+    c->mview.bits = nullptr; c->mview.sat = nullptr;
+    unsigned long long* dbits = nullptr;
+    int* dsat = nullptr;
+    HIPCHK(hipMalloc(&dbits, std::max<size_t>(1, h.bits.size()) * sizeof(unsigned long long)));
+    c->mview.bits = dbits;
+    HIPCHK(hipMalloc(&dsat, h.sat.size() * sizeof(int)));
+    c->mview.sat = dsat;
+    HIPCHK(hipMemcpy(dbits, h.bits.data(), h.bits.size() * sizeof(unsigned long long), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dsat, h.sat.data(), h.sat.size() * sizeof(int), hipMemcpyHostToDevice));
+    c->fpart_chunks = (int)(((long)c->nx * c->nyl + FORCE_CHUNK - 1) / FORCE_CHUNK);
+    HIPCHK(hipMalloc(&c->d_fpart, 2 * sizeof(double) * (size_t)std::max(1, c->fpart_chunks)));
+    c->hmask = std::move(h);
+    c->has_mask = true;
     return LBM_OK;
 }
 
@@ -571,11 +608,12 @@ int lbm_save_state(lbm_ctx* c, const char* path) {
     FILE* fp = fopen(path, "wb");
     if (!fp) return fail(LBM_ERR_ARG, "cannot open %s for writing", path);
     CkptHeader h{};
-    memcpy(h.magic, "LBMCKPT1", 8);
+    memcpy(h.magic, c->has_mask ? "LBMCKPT2" : "LBMCKPT1", 8);
     h.nx = c->nx; h.ny = c->p.ny; h.y_start = c->p.y_start; h.local_ny = c->nyl; h.precision = c->p.precision;
     h.steps_done = c->steps_done; h.tau = c->p.tau; h.inlet_velocity = c->p.inlet_velocity;
     h.cylinder_x = c->p.cylinder_x; h.cylinder_y = c->p.cylinder_y; h.cylinder_radius = c->p.cylinder_radius;
     int rc = fwrite(&h, sizeof(h), 1, fp) == 1 ? LBM_OK : fail(LBM_ERR_ARG, "short write");
+    if (!rc && c->has_mask && fwrite(&c->hmask.digest, sizeof(c->hmask.digest), 1, fp) != 1) rc = fail(LBM_ERR_ARG, "short write");
     if (!rc) rc = DISPATCH(c, do_save<double>(c, fp), do_save<float>(c, fp));
     fclose(fp);
     return rc;
@@ -598,7 +636,13 @@ int lbm_load_state(lbm_ctx* c, const char* path) {
     if (!fp) return fail(LBM_ERR_ARG, "cannot open %s", path);
     CkptHeader h{};
     int rc = LBM_OK;
-    if (fread(&h, sizeof(h), 1, fp) != 1 || memcmp(h.magic, "LBMCKPT1", 8) != 0) rc = fail(LBM_ERR_ARG, "%s is not a checkpoint", path);
+    unsigned long long digest = 0;
+    const bool v1 = fread(&h, sizeof(h), 1, fp) == 1 && memcmp(h.magic, "LBMCKPT1", 8) == 0;
+    const bool v2 = !v1 && memcmp(h.magic, "LBMCKPT2", 8) == 0 && fread(&digest, sizeof(digest), 1, fp) == 1;
+    if (!v1 && !v2) rc = fail(LBM_ERR_ARG, "%s is not a checkpoint", path);
+    else if (v1 && c->has_mask) rc = fail(LBM_ERR_ARG, "checkpoint %s was written without an obstacle mask; this context has one", path);
+    else if (v2 && !c->has_mask) rc = fail(LBM_ERR_ARG, "checkpoint %s was written with an obstacle mask; this context has none", path);
+    else if (v2 && digest != c->hmask.digest) rc = fail(LBM_ERR_ARG, "checkpoint %s was written for a different obstacle mask", path);
     else if (h.nx != c->nx || h.ny != c->p.ny || h.y_start != c->p.y_start || h.local_ny != c->nyl ||
              h.precision != c->p.precision || h.tau != c->p.tau || h.inlet_velocity != c->p.inlet_velocity ||
              h.cylinder_x != c->p.cylinder_x || h.cylinder_y != c->p.cylinder_y || h.cylinder_radius != c->p.cylinder_radius)
@@ -693,6 +737,28 @@ const char* lbm_kernel_name(const lbm_ctx* c) {
     const int deep = usable ? c->deep : 0, fuse = usable || !c->deep ? c->fuse : std::min(c->fuse, 3);
     snprintf(name, sizeof(name), "%s", plan_kernel_name(fuse, deep, c->pair_ty, c->use_nt, c->arith, (int)c->esize).c_str());
     return name;
+}
+
+/* TEST HOOK (no device needed): the host-side packing of lbm_set_solid_mask for the strip [y_start, y_start + local_ny) (csrc/lbm_geom.hpp)
+ * and the kernels' block-uniform near-solid query over it (lbm_kernels.hpp mask_box_any, the same function the device runs). */
+int lbm_debug_geometry(const unsigned char* mask, int nx, int ny, int y_start, int local_ny, int* dims9, unsigned long long* bits, long bits_cap,
+                       int* sat, long sat_cap, const int* boxes4, int nbox, int* near_out) {
+    if (!mask || !dims9 || nx < 1 || ny < 1 || y_start < 0 || local_ny < 1 || y_start + local_ny > ny || nbox < 0 || (nbox > 0 && (!boxes4 || !near_out)))
+        return fail(LBM_ERR_ARG, "bad argument");
+    const HostMask h = pack_mask(mask, nx, ny, y_start, local_ny);
+    const int d[9] = {h.y0, h.rows, h.words, h.nbx, h.nby, h.bx0, h.bx1, h.by0, h.by1};
+    memcpy(dims9, d, sizeof(d));
+    if (bits) {
+        if (bits_cap < (long)h.bits.size()) return fail(LBM_ERR_ARG, "bits: %zu words needed", h.bits.size());
+        memcpy(bits, h.bits.data(), h.bits.size() * sizeof(unsigned long long));
+    }
+    if (sat) {
+        if (sat_cap < (long)h.sat.size()) return fail(LBM_ERR_ARG, "sat: %zu entries needed", h.sat.size());
+        memcpy(sat, h.sat.data(), h.sat.size() * sizeof(int));
+    }
+    const MaskView m = h.view();
+    for (int k = 0; k < nbox; ++k) near_out[k] = mask_box_any(m, boxes4[4 * k], boxes4[4 * k + 1], boxes4[4 * k + 2], boxes4[4 * k + 3]) ? 1 : 0;
+    return LBM_OK;
 }
 
 /* TEST HOOK (no device needed): the candidates lbm_initialise would time for a whole-domain context of this grid, one per line:

@@ -108,7 +108,7 @@ __global__ void __launch_bounds__(NW * 64, (col_waves_per_simd<NW>())) k_stepc_c
     const int Xo = bx * OW;
     const int X0 = Xo - HW, Yr = Yo - HW;                  // region origin
     const int ry0 = w * R;                                 // this wave's first region row
-    const bool near_cyl = tile_near_cylinder(a, Xo, Yo, OW, OH, HW);
+    const bool near_cyl = tile_near_solid(a, Xo, Yo, OW, OH, HW);
     auto outside_value = [&](bool row_in, bool col_in, int i) -> T { return (row_in && !col_in) ? T(0) : e.feq_in[i]; };
     const int yg0 = a.y_start + Yo;
     // LEAN (block-uniform): every cell of the region is a plain fluid cell strictly inside the domain and the tile is full
@@ -119,9 +119,7 @@ __global__ void __launch_bounds__(NW * 64, (col_waves_per_simd<NW>())) k_stepc_c
     const __amdgpu_buffer_rsrc_t rsrc = buf_desc(reinterpret_cast<const char*>(a.src) - KB), rdst = buf_desc(a.dst);
     const int x = X0 + lane;
     // one general cell: BCs, stability, collision (solid cells keep w_i); `count` = the cell's instability is reported
-    auto update = [&](T (&f)[Q], int yg, bool count, bool& bad) {
-        bool solid = false;
-        if (near_cyl) solid = is_solid_cell(x, yg, a.cyl_x, a.cyl_y, a.cyl_r2);   // block-uniform branch
+    auto update = [&](T (&f)[Q], int yg, bool solid, bool count, bool& bad) {
         T rho_bc, u_out;
         if (!solid) apply_bcs(f, yg == 0, yg == a.ny_glob - 1, x == 0, x == a.nx - 1, a.u_in, rho_bc, u_out);
         bad |= unstable_if(f, count);
@@ -135,6 +133,16 @@ __global__ void __launch_bounds__(NW * 64, (col_waves_per_simd<NW>())) k_stepc_c
         T g[R][Q];
         bool bad = false;
         const bool col_in = (x >= 0 && x < a.nx);
+        // bit j: the thread's cell of row j is solid. The thread <-> cell map is fixed for all D levels, so the geometry is looked
+        // up once, here, and serves every level and the store predicate (block-uniform branch: only tiles near a solid cell)
+        unsigned sbits = 0;
+        if (!LEAN && near_cyl && col_in) {
+#pragma unroll
+            for (int j = 0; j < R; ++j) {
+                const int yg = a.y_start + Yr + ry0 + j;
+                if (yg >= 0 && yg < a.ny_glob && solid_at(a, x, yg)) sbits |= 1u << j;
+            }
+        }
         LBM_PROF_IDS(b, NW, w);
         LBM_PROF(b, NW, w, 0);
         // ---- level 1: iteration t on the whole region, from HBM
@@ -166,7 +174,7 @@ __global__ void __launch_bounds__(NW * 64, (col_waves_per_simd<NW>())) k_stepc_c
                     const long c = (long)(y + GR) * a.pitch + a.xoff + x;
 #pragma unroll
                     for (int i = 0; i < Q; ++i) g[j][i] = a.src[(long)i * a.plane + c - (long)cy(i) * a.pitch - cx(i)];
-                    update(g[j], yg, true, bad);
+                    update(g[j], yg, (sbits >> j) & 1u, true, bad);
                 }
             }
         }
@@ -206,8 +214,8 @@ __global__ void __launch_bounds__(NW * 64, (col_waves_per_simd<NW>())) k_stepc_c
                         for (int i = 0; i < Q; ++i) f[i] = outside_value(row_in, col_in, i);
                         store = false;
                     } else {
-                        update(f, yg, valid && y <= y_end + HW - L, badl);
-                        store = store && y < y_end && !(near_cyl && is_solid_cell(x, yg, a.cyl_x, a.cyl_y, a.cyl_r2));
+                        update(f, yg, (sbits >> j) & 1u, valid && y <= y_end + HW - L, badl);
+                        store = store && y < y_end && !((sbits >> j) & 1u);
                     }
                 }
                 if (L < D) {

@@ -58,6 +58,30 @@ template <typename T> __host__ __device__ constexpr T wgt(int i) {
     return i == 0 ? T(4.0 / 9.0) : (i < 5 ? T(1.0 / 9.0) : T(1.0 / 36.0));
 }
 
+// User-defined geometry (lbm_set_solid_mask): a read-only bitmap of the rows a strip can ever query, its own rows +- GR
+// clipped to the domain, built on the host and uploaded once; no kernel writes it. Beside it a summed-area table of the solid
+// counts of 8x8-cell blocks of the same window, so that "can this tile touch a solid cell" stays O(1) (four lookups) for any mask.
+struct MaskView {
+    const unsigned long long* bits = nullptr;   // [rows][words]: bit x & 63 of word x >> 6 of row r = cell (x, y0 + r)
+    const int* sat = nullptr;                   // [nby + 1][nbx + 1]: sat[b][c] = solid cells in the blocks < b (rows) and < c (columns)
+    int y0 = 0, rows = 0, words = 0, nbx = 0, nby = 0;
+};
+__host__ __device__ inline bool mask_cell(const MaskView& m, int x, int yg) {   // 0 <= x < nx; rows outside the window: fluid
+    const int r = yg - m.y0;
+    if (r < 0 || r >= m.rows) return false;
+    return (m.bits[(long)r * m.words + (x >> 6)] >> (x & 63)) & 1ull;
+}
+// any solid cell in [x0, x1] x [yg0, yg1] (global, inclusive)? Exact at block granularity, so a superset of the cell test: it never
+// answers false where a solid cell lies in the box.
+__host__ __device__ inline bool mask_box_any(const MaskView& m, int x0, int x1, int yg0, int yg1) {
+    x0 = x0 < 0 ? 0 : x0;
+    x1 = x1 > m.nbx * 8 - 1 ? m.nbx * 8 - 1 : x1;
+    const int r0 = yg0 - m.y0 < 0 ? 0 : yg0 - m.y0, r1 = yg1 - m.y0 > m.rows - 1 ? m.rows - 1 : yg1 - m.y0;
+    if (x0 > x1 || r0 > r1) return false;
+    const int W = m.nbx + 1, c0 = x0 >> 3, c1 = (x1 >> 3) + 1, b0 = r0 >> 3, b1 = (r1 >> 3) + 1;
+    return m.sat[b1 * W + c1] - m.sat[b0 * W + c1] - m.sat[b1 * W + c0] + m.sat[b0 * W + c0] > 0;
+}
+
 template <typename T>
 struct KArgs {
     const T* src;      // plane 0 of the buffer read  (P_t)
@@ -70,6 +94,7 @@ struct KArgs {
     int y_start;       // global row of local y = 0
     int cyl_x, cyl_y;  // LBMConfig.h:61-63 (integer cells)
     double cyl_r2;     // (double)(r*r), LBMGrid.h:169
+    MaskView mv;       // user-defined geometry (lbm_set_solid_mask); mv.bits == nullptr: the disc above
     T tau_inv;         // 1/tau, LBMSolver.h:85
     T u_in;            // inlet velocity
     int* unstable_t;   // device word: first unstable iteration (INT_MAX if none)
@@ -108,12 +133,21 @@ __device__ __forceinline__ bool is_solid_cell(int x, int yg, int cyl_x, int cyl_
     return dx * dx + dy * dy <= cyl_r2;
 }
 
-// Block-uniform test: can any cell of the tile [X0, X0+TX) x [Y0, Y0+TY) grown by `ring` cells be solid? (bounding
-// boxes in integer cells; cyl_r2 = r*r exactly, so r is recovered by an exact sqrt of a perfect square).
+// The one geometry test of every kernel: the mask where one is set, else the disc. `a` is any argument block with the disc
+// and a MaskView (KArgs, InitArgs, MacroArgs, ForceArgs); the branch is uniform over the launch. 0 <= x < nx.
+template <typename A>
+__device__ __forceinline__ bool solid_at(const A& a, int x, int yg) {
+    return a.mv.bits ? mask_cell(a.mv, x, yg) : is_solid_cell(x, yg, a.cyl_x, a.cyl_y, a.cyl_r2);
+}
+
+// Block-uniform test: can any cell of the tile [X0, X0+TX) x [Y0, Y0+TY) grown by `ring` cells be solid? Disc: bounding
+// boxes in integer cells (cyl_r2 = r*r exactly, so r is recovered by an exact sqrt of a perfect square). Mask: the coarse table
+// with the box rounded outward to 8x8 blocks. Both exact or conservative: false only where no cell of the box is solid.
 template <typename T>
-__device__ __forceinline__ bool tile_near_cylinder(const KArgs<T>& a, int X0, int Y0, int TX, int TY, int ring) {
-    const int r = (int)sqrt(a.cyl_r2) + 1;
+__device__ __forceinline__ bool tile_near_solid(const KArgs<T>& a, int X0, int Y0, int TX, int TY, int ring) {
     const int yg0 = a.y_start + Y0;
+    if (a.mv.bits) return mask_box_any(a.mv, X0 - ring, X0 + TX - 1 + ring, yg0 - ring, yg0 + TY - 1 + ring);
+    const int r = (int)sqrt(a.cyl_r2) + 1;
     return X0 - ring <= a.cyl_x + r && X0 + TX - 1 + ring >= a.cyl_x - r &&
            yg0 - ring <= a.cyl_y + r && yg0 + TY - 1 + ring >= a.cyl_y - r;
 }
@@ -325,7 +359,7 @@ __global__ void __launch_bounds__(256) k_step_site(const KArgs<T> a) {
         const long off = (MODE == MODE_COLLIDE_ONLY) ? 0 : (long)cy(i) * a.pitch + cx(i);
         f[i] = a.src[(long)i * a.plane + c - off];
     }
-    const bool solid = is_solid_cell(x, yg, a.cyl_x, a.cyl_y, a.cyl_r2);
+    const bool solid = solid_at(a, x, yg);
     if (MODE != MODE_COLLIDE_ONLY) {
         T rho_bc, u_out;
         if (!solid)
@@ -417,7 +451,7 @@ __global__ void __launch_bounds__(NTH) k_step2_tile(const KArgs<T> a, const K2Ex
     const int X0 = bx * TX;
     int y_end;                                                 // rows >= y_end belong to another band / launch
     const int Y0 = band_origin(a, by, TY, y_end);
-    const bool near_cyl = tile_near_cylinder(a, X0, Y0, TX, TY, 1);   // block-uniform: most tiles skip the mask math
+    const bool near_cyl = tile_near_solid(a, X0, Y0, TX, TY, 1);   // block-uniform: most tiles skip the mask math
     bool bad = false;
     for (int r = threadIdx.x; r < RW * RH; r += NTH) {         // phase 1: iteration t on the region
         const int ry = r / RW, rx = r - ry * RW;
@@ -434,7 +468,7 @@ __global__ void __launch_bounds__(NTH) k_step2_tile(const KArgs<T> a, const K2Ex
 #pragma unroll
             for (int i = 0; i < Q; ++i) f[i] = a.src[(long)i * a.plane + c - (long)cy(i) * a.pitch - cx(i)];
             bool solid = false;
-            if (near_cyl) solid = is_solid_cell(x, yg, a.cyl_x, a.cyl_y, a.cyl_r2);   // block-uniform branch
+            if (near_cyl) solid = solid_at(a, x, yg);   // block-uniform branch
             T rho_bc, u_out;
             if (!solid) apply_bcs(f, yg == 0, yg == a.ny_glob - 1, x == 0, x == a.nx - 1, a.u_in, rho_bc, u_out);
             bad |= any_unstable(f);
@@ -458,7 +492,7 @@ __global__ void __launch_bounds__(NTH) k_step2_tile(const KArgs<T> a, const K2Ex
         T f[Q];
 #pragma unroll
         for (int i = 0; i < Q; ++i) f[i] = lds[i][ly + 1 - cy(i)][lx + 1 - cx(i)];
-        const bool solid = near_cyl && is_solid_cell(x, yg, a.cyl_x, a.cyl_y, a.cyl_r2);
+        const bool solid = near_cyl && solid_at(a, x, yg);
         T rho_bc, u_out;
         if (!solid) apply_bcs(f, yg == 0, yg == a.ny_glob - 1, x == 0, x == a.nx - 1, a.u_in, rho_bc, u_out);
         bad |= any_unstable(f);
@@ -494,7 +528,7 @@ __global__ void __launch_bounds__(NTH, (2 * NTH / 256)) k_step3_tile(const KArgs
     const int X0 = bx * TX;
     int y_end;
     const int Y0 = band_origin(a, by, TY, y_end);
-    const bool near_cyl = tile_near_cylinder(a, X0, Y0, TX, TY, 2);
+    const bool near_cyl = tile_near_solid(a, X0, Y0, TX, TY, 2);
     auto outside_value = [&](bool row_in, bool col_in, int i) -> T { return (row_in && !col_in) ? T(0) : e.feq_in[i]; };
     // LEAN (block-uniform): the tile and its two rings lie strictly inside the domain, the tile is full, nothing is near
     // the cylinder — every cell of all three regions is a plain fluid cell: no boundary, ghost, solid or validity logic.
@@ -539,7 +573,7 @@ __global__ void __launch_bounds__(NTH, (2 * NTH / 256)) k_step3_tile(const KArgs
                     bgk_collide<T, AR>(f, a.tau_inv);
                 } else {
                     bool solid = false;
-                    if (near_cyl) solid = is_solid_cell(x, yg, a.cyl_x, a.cyl_y, a.cyl_r2);   // block-uniform branch
+                    if (near_cyl) solid = solid_at(a, x, yg);   // block-uniform branch
                     T rho_bc, u_out;
                     if (!solid) apply_bcs(f, yg == 0, yg == a.ny_glob - 1, x == 0, x == a.nx - 1, a.u_in, rho_bc, u_out);
                     bad |= any_unstable(f);
@@ -595,7 +629,7 @@ __global__ void __launch_bounds__(NTH, (2 * NTH / 256)) k_step3_tile(const KArgs
                     bgk_collide<T, AR>(f, a.tau_inv);
                 } else {
                     bool solid = false;
-                    if (near_cyl) solid = is_solid_cell(x, yg, a.cyl_x, a.cyl_y, a.cyl_r2);   // block-uniform branch
+                    if (near_cyl) solid = solid_at(a, x, yg);   // block-uniform branch
                     T rho_bc, u_out;
                     if (!solid) apply_bcs(f, yg == 0, yg == a.ny_glob - 1, x == 0, x == a.nx - 1, a.u_in, rho_bc, u_out);
                     if (y <= y_end) bad |= any_unstable(f);
@@ -623,7 +657,7 @@ __global__ void __launch_bounds__(NTH, (2 * NTH / 256)) k_step3_tile(const KArgs
             if (LEAN) {
                 bad |= any_unstable(f);
             } else {
-                const bool solid = near_cyl && is_solid_cell(x, yg, a.cyl_x, a.cyl_y, a.cyl_r2);
+                const bool solid = near_cyl && solid_at(a, x, yg);
                 T rho_bc, u_out;
                 if (!solid) apply_bcs(f, yg == 0, yg == a.ny_glob - 1, x == 0, x == a.nx - 1, a.u_in, rho_bc, u_out);
                 bad |= any_unstable(f);
@@ -666,7 +700,7 @@ __global__ void __launch_bounds__(NTH, (2 * NTH / 256)) k_step4_tile(const KArgs
     const int X0 = bx * TX;
     int y_end;
     const int Y0 = band_origin(a, by, TY, y_end);
-    const bool near_cyl = tile_near_cylinder(a, X0, Y0, TX, TY, HW);
+    const bool near_cyl = tile_near_solid(a, X0, Y0, TX, TY, HW);
     auto outside_value = [&](bool row_in, bool col_in, int i) -> T { return (row_in && !col_in) ? T(0) : e.feq_in[i]; };
     // LEAN (block-uniform): tile + three rings strictly inside the domain, full tile, nothing near the cylinder
     const int yg0 = a.y_start + Y0;
@@ -684,7 +718,7 @@ __global__ void __launch_bounds__(NTH, (2 * NTH / 256)) k_step4_tile(const KArgs
             return;
         }
         bool solid = false;
-        if (near_cyl) solid = is_solid_cell(x, yg, a.cyl_x, a.cyl_y, a.cyl_r2);   // block-uniform branch
+        if (near_cyl) solid = solid_at(a, x, yg);   // block-uniform branch
         T rho_bc, u_out;
         if (!solid) apply_bcs(f, yg == 0, yg == a.ny_glob - 1, x == 0, x == a.nx - 1, a.u_in, rho_bc, u_out);
         if (count) bad |= any_unstable(f);
@@ -782,7 +816,7 @@ __global__ void __launch_bounds__(NTH, (2 * NTH / 256)) k_step4_tile(const KArgs
             buf_store_pops(f, rdst, voff, ub, planeB, e.nt != 0);
             continue;
         }
-        const bool solid = near_cyl && is_solid_cell(x, yg, a.cyl_x, a.cyl_y, a.cyl_r2);
+        const bool solid = near_cyl && solid_at(a, x, yg);
         T rho_bc, u_out;
         if (!solid) apply_bcs(f, yg == 0, yg == a.ny_glob - 1, x == 0, x == a.nx - 1, a.u_in, rho_bc, u_out);
         bad |= any_unstable(f);
@@ -871,7 +905,7 @@ __global__ void __launch_bounds__(TX * TY, (deep_waves_per_simd<T, TX, TY, D>())
     const int X0 = bx * TX;
     int y_end;
     const int Y0 = band_origin(a, by, TY, y_end);
-    const bool near_cyl = tile_near_cylinder(a, X0, Y0, TX, TY, HW);
+    const bool near_cyl = tile_near_solid(a, X0, Y0, TX, TY, HW);
     auto outside_value = [&](bool row_in, bool col_in, int i) -> T { return (row_in && !col_in) ? T(0) : e.feq_in[i]; };
     const int yg0 = a.y_start + Y0;
     const bool lean = !near_cyl && X0 >= HW + 1 && X0 + TX + HW <= a.nx - 1 && yg0 >= HW + 1 && yg0 + TY + HW <= a.ny_glob - 1 &&
@@ -883,7 +917,7 @@ __global__ void __launch_bounds__(TX * TY, (deep_waves_per_simd<T, TX, TY, D>())
     // one general cell: BCs, stability, collision (solid cells keep w_i); `count` = the cell's instability is reported
     auto update = [&](T (&f)[Q], int x, int yg, bool count, bool& bad) {
         bool solid = false;
-        if (near_cyl) solid = is_solid_cell(x, yg, a.cyl_x, a.cyl_y, a.cyl_r2);   // block-uniform branch
+        if (near_cyl) solid = solid_at(a, x, yg);   // block-uniform branch
         T rho_bc, u_out;
         if (!solid) apply_bcs(f, yg == 0, yg == a.ny_glob - 1, x == 0, x == a.nx - 1, a.u_in, rho_bc, u_out);
         if (count) bad |= any_unstable(f);
@@ -993,7 +1027,7 @@ __global__ void __launch_bounds__(TX * TY, (deep_waves_per_simd<T, TX, TY, D>())
                     const unsigned voff = (unsigned)ly * pitchB + (unsigned)lx * (unsigned)sizeof(T);
                     buf_store_pops(f, rdst, voff, ub, planeB, e.nt != 0);
                 } else {
-                    const bool solid = near_cyl && is_solid_cell(x, yg, a.cyl_x, a.cyl_y, a.cyl_r2);
+                    const bool solid = near_cyl && solid_at(a, x, yg);
                     T rho_bc, u_out;
                     if (!solid) apply_bcs(f, yg == 0, yg == a.ny_glob - 1, x == 0, x == a.nx - 1, a.u_in, rho_bc, u_out);
                     bad |= any_unstable(f);
@@ -1025,6 +1059,7 @@ struct InitArgs {
     T* a; T* b;
     long plane; int pitch, xoff, nx, ny_loc, ny_glob, y_start;
     int cyl_x, cyl_y; double cyl_r2;
+    MaskView mv;
     T feq_in[Q];
     int* solid_count;
 };
@@ -1039,7 +1074,7 @@ __global__ void __launch_bounds__(256) k_init(const InitArgs<T> p) {
     const bool col_interior = (x >= 0 && x < p.nx);
     const bool own_row = (gy >= GR && gy < p.ny_loc + GR);
     bool solid = false;
-    if (row_interior && col_interior) solid = is_solid_cell(x, yg, p.cyl_x, p.cyl_y, p.cyl_r2);
+    if (row_interior && col_interior) solid = solid_at(p, x, yg);
     if (solid && own_row) atomicAdd(p.solid_count, 1);
     const long c = (long)gy * p.pitch + p.xoff + x;
 #pragma unroll
@@ -1063,6 +1098,7 @@ template <typename T>
 struct MacroArgs {
     const T* old; long plane; int pitch, xoff, nx, ny_loc, ny_glob, y_start;
     int cyl_x, cyl_y; double cyl_r2; T u_in;
+    MaskView mv;
     int initial;        // steps_done == 0: analytic initial macros (LBMGrid.h:219-228)
     double* rho; double* ux; double* uy;   // [ny_loc][nx]
     unsigned long long* max_usq_bits;      // optional running max of ux^2+uy^2 (bit pattern of a double >= 0)
@@ -1076,7 +1112,7 @@ __global__ void __launch_bounds__(256) k_macros(const MacroArgs<T> p) {
     if (x < p.nx) {
         const int yg = p.y_start + y;
         const long c = (long)(y + GR) * p.pitch + p.xoff + x;
-        const bool solid = is_solid_cell(x, yg, p.cyl_x, p.cyl_y, p.cyl_r2);
+        const bool solid = solid_at(p, x, yg);
         double r, vx, vy;
         if (solid) { r = 1.0; vx = 0.0; vy = 0.0; }
         else if (p.initial) { r = 1.0; vx = (double)p.u_in; vy = 0.0; }
@@ -1114,17 +1150,23 @@ __global__ void __launch_bounds__(256) k_macros(const MacroArgs<T> p) {
 
 // ---------------------------------------------------------------------------------------------------------
 // IOManager::record_forces, LBMIO.h:133-160: momentum exchange over solid->fluid links, evaluated on the
-// post-collision populations P_t. One block scans the cylinder's bounding box (+1 cell) restricted to the rows
-// this strip owns, visiting FLUID cells and their solid neighbours (mask from global coordinates), so strip
+// post-collision populations P_t. One block scans the obstacle's bounding box (+1 cell) restricted to the rows
+// this strip owns, visiting FLUID cells and their solid neighbours (geometry from global coordinates), so strip
 // partial sums add up to the one-rank value. Deterministic tree reduction in LDS.
+// A box of more than FORCE_CHUNK cells (a mask that covers much of the domain, e.g. a porous bed) is cut into fixed chunks of
+// FORCE_CHUNK cells, one block each, whose partial sums k_forces_sum adds in chunk order: a partition and a summation order that
+// depend on the box alone, so every plan and every repetition gives the same bits. One chunk is exactly the one-block scan.
 template <typename T>
 struct ForceArgs {
     const T* cur; long plane; int pitch, xoff, nx, ny_loc, ny_glob, y_start;
     int cyl_x, cyl_y, cyl_r; double cyl_r2;
+    MaskView mv;
     int x0, x1, y0, y1;     // inclusive box in (x, local y)
     double* out;            // out[0] = t (as double), out[1] = fx, out[2] = fy
+    double* part;           // several chunks: [gridDim.x][2] partial sums (k_forces_sum writes `out`)
     int t;
 };
+constexpr long FORCE_CHUNK = 65536;
 
 template <typename T>
 __global__ void __launch_bounds__(1024) k_forces(const ForceArgs<T> p) {
@@ -1133,16 +1175,18 @@ __global__ void __launch_bounds__(1024) k_forces(const ForceArgs<T> p) {
     double fx = 0.0, fy = 0.0;
     const int bw = p.x1 - p.x0 + 1, bh = p.y1 - p.y0 + 1;
     const long ncell = (bw > 0 && bh > 0) ? (long)bw * bh : 0;
-    for (long k = threadIdx.x; k < ncell; k += 1024) {
+    const long k0 = gridDim.x > 1 ? (long)blockIdx.x * FORCE_CHUNK : 0;
+    const long k1 = gridDim.x > 1 ? (k0 + FORCE_CHUNK < ncell ? k0 + FORCE_CHUNK : ncell) : ncell;
+    for (long k = k0 + threadIdx.x; k < k1; k += 1024) {
         const int x = p.x0 + (int)(k % bw), y = p.y0 + (int)(k / bw);
         const int yg = p.y_start + y;
-        if (is_solid_cell(x, yg, p.cyl_x, p.cyl_y, p.cyl_r2)) continue;
+        if (solid_at(p, x, yg)) continue;
         const long c = (long)(y + GR) * p.pitch + p.xoff + x;
 #pragma unroll
         for (int i = 1; i < Q; ++i) {
             const int sx = x + cx(i), sy = yg + cy(i);
             if (sx < 0 || sx >= p.nx || sy < 0 || sy >= p.ny_glob) continue;
-            if (!is_solid_cell(sx, sy, p.cyl_x, p.cyl_y, p.cyl_r2)) continue;
+            if (!solid_at(p, sx, sy)) continue;
             const double fi = (double)p.cur[(long)i * p.plane + c];
             fx += 2.0 * cx(i) * fi;
             fy += 2.0 * cy(i) * fi;
@@ -1154,7 +1198,18 @@ __global__ void __launch_bounds__(1024) k_forces(const ForceArgs<T> p) {
         if ((int)threadIdx.x < s) { sfx[threadIdx.x] += sfx[threadIdx.x + s]; sfy[threadIdx.x] += sfy[threadIdx.x + s]; }
         __syncthreads();
     }
-    if (threadIdx.x == 0) { p.out[0] = (double)p.t; p.out[1] = sfx[0]; p.out[2] = sfy[0]; }
+    if (threadIdx.x == 0) {
+        if (gridDim.x > 1) { p.part[2 * blockIdx.x] = sfx[0]; p.part[2 * blockIdx.x + 1] = sfy[0]; }
+        else { p.out[0] = (double)p.t; p.out[1] = sfx[0]; p.out[2] = sfy[0]; }
+    }
+}
+// the chunks' partial sums of k_forces in chunk order (one thread: at most a few hundred chunks)
+template <typename T>   // (T: one instantiation per element type of the launcher, like every kernel of this header)
+__global__ void __launch_bounds__(64) k_forces_sum(const double* part, int nchunks, double* out, int t) {
+    if (threadIdx.x != 0) return;
+    double fx = 0.0, fy = 0.0;
+    for (int b = 0; b < nchunks; ++b) { fx += part[2 * b]; fy += part[2 * b + 1]; }
+    out[0] = (double)t; out[1] = fx; out[2] = fy;
 }
 
 // ---------------------------------------------------------------------------------------------------------

@@ -16,6 +16,7 @@ KArgs<T> make_kargs(const lbm_ctx* c, int src, int dst, int t) {
     a.cyl_x = c->cyl_x;
     a.cyl_y = c->cyl_y;
     a.cyl_r2 = (double)(c->cyl_r * c->cyl_r);
+    if (c->has_mask) a.mv = c->mview;
     a.tau_inv = (T)(1.0 / c->p.tau);
     a.u_in = (T)c->p.inlet_velocity;
     a.unstable_t = c->d_unstable;
@@ -159,11 +160,26 @@ int launch_forces(lbm_ctx* c, double* out, int t) {
     f.plane = (long)c->plane; f.pitch = c->pitch; f.xoff = c->xoff;
     f.nx = c->nx; f.ny_loc = c->nyl; f.ny_glob = c->p.ny; f.y_start = c->p.y_start;
     f.cyl_x = c->cyl_x; f.cyl_y = c->cyl_y; f.cyl_r = c->cyl_r; f.cyl_r2 = (double)(c->cyl_r * c->cyl_r);
+    f.out = out; f.t = t; f.part = c->d_fpart;
+    if (c->has_mask) {   // the mask's bounding box + 1 cell, within this strip's rows; large boxes in fixed chunks (k_forces)
+        const HostMask& h = c->hmask;
+        f.mv = c->mview;
+        f.x0 = std::max(0, h.bx0 - 1);
+        f.x1 = std::min(c->nx - 1, h.bx1 + 1);
+        f.y0 = std::max(0, h.by0 - 1 - c->p.y_start);
+        f.y1 = std::min(c->nyl - 1, h.by1 + 1 - c->p.y_start);
+        if (h.bx1 < h.bx0) f.x1 = f.x0 - 1;    // no solid cell: no link
+        const long ncell = (f.x1 >= f.x0 && f.y1 >= f.y0) ? (long)(f.x1 - f.x0 + 1) * (f.y1 - f.y0 + 1) : 0;
+        const int nchunks = (int)std::max(1L, (ncell + FORCE_CHUNK - 1) / FORCE_CHUNK);
+        hipLaunchKernelGGL((k_forces<T>), dim3(nchunks), dim3(1024), 0, c->stream, f);
+        if (nchunks > 1) hipLaunchKernelGGL((k_forces_sum<T>), dim3(1), dim3(64), 0, c->stream, (const double*)c->d_fpart, nchunks, out, t);
+        HIPCHK(hipGetLastError());
+        return LBM_OK;
+    }
     f.x0 = std::max(0, c->cyl_x - c->cyl_r - 1);
     f.x1 = std::min(c->nx - 1, c->cyl_x + c->cyl_r + 1);
     f.y0 = std::max(0, c->cyl_y - c->cyl_r - 1 - c->p.y_start);
     f.y1 = std::min(c->nyl - 1, c->cyl_y + c->cyl_r + 1 - c->p.y_start);
-    f.out = out; f.t = t;
     hipLaunchKernelGGL((k_forces<T>), dim3(1), dim3(1024), 0, c->stream, f);
     HIPCHK(hipGetLastError());
     return LBM_OK;

@@ -538,6 +538,7 @@ int init_state(lbm_ctx* c) {
     ia.plane = (long)c->plane; ia.pitch = c->pitch; ia.xoff = c->xoff;
     ia.nx = c->nx; ia.ny_loc = c->nyl; ia.ny_glob = c->p.ny; ia.y_start = c->p.y_start;
     ia.cyl_x = c->cyl_x; ia.cyl_y = c->cyl_y; ia.cyl_r2 = (double)(c->cyl_r * c->cyl_r);
+    if (c->has_mask) ia.mv = c->mview;
     for (int i = 0; i < Q; ++i) ia.feq_in[i] = (T)c->feq_in[i];
     ia.solid_count = c->d_solid_count;
     HIPCHK(hipMemsetAsync(c->d_solid_count, 0, sizeof(int), c->stream));

@@ -46,6 +46,7 @@ public:
             devs_.push_back(dev);
             check(lbm_set_option(c, "tune", opt.tune ? 1 : 0), "lbm_set_option");
             check(lbm_set_option(c, "arith", opt.contracted ? 1 : 0), "lbm_set_option");
+            if (p.masked()) check(lbm_set_solid_mask(c, p.obstacle_mask.data(), p.nx, p.ny), "lbm_set_solid_mask");
             y += n;
         }
         check(lbm_group_link(ctx_.data(), (int)ctx_.size(), opt.rccl ? 1 : 0), "lbm_group_link");

@@ -61,7 +61,7 @@ public:
     }
     // Same row from a device-log entry (Solver::run drains the log at output cadence).
     void append_force_row(int timestep, double fx, double fy, const SimulationParams& params) {
-        const double d_ref = 2.0 * params.get_cylinder_radius_cells();
+        const double d_ref = params.masked() ? (double)params.mask_frontal_height : 2.0 * params.get_cylinder_radius_cells();
         const double q_ref = 0.5 * 1.0 * params.inlet_velocity * params.inlet_velocity * d_ref;
         const double cd = (q_ref > 1e-12) ? fx / q_ref : 0.0;
         const double cl = (q_ref > 1e-12) ? fy / q_ref : 0.0;
@@ -179,6 +179,10 @@ private:
         row_d("reynolds_number", p.reynolds()); row_i("cylinder_x", p.get_cylinder_x());
         row_i("cylinder_y", p.get_cylinder_y()); row_i("cylinder_radius", p.get_cylinder_radius_cells());
         row_d("max_velocity", vmax); row_d("avg_velocity", vavg);
+        if (p.masked()) {   // (not in the reference's file: masked runs only, appended so that its rows keep their places)
+            row_i("reference_length", p.mask_frontal_height);
+            f.put("obstacle_mask,"); f.put(p.obstacle_mask_file.c_str()); f.put("\n");
+        }
         std::printf("  simulation_params.csv written\n");
     }
     // calculate_time_averaged_drag (LBMIO.h:367-413): statistics of the CSV values (8 decimals) for timestep > 1000.

@@ -3,6 +3,8 @@
 // surface a caller of the reference touches: LBMConfig.h:9-34 constants, :36-66 SimulationParams).
 #pragma once
 #include <array>
+#include <string>
+#include <vector>
 
 namespace LBM {
 
@@ -27,9 +29,18 @@ struct SimulationParams {
     double cylinder_y = 0.5;        // fraction of ny
     double cylinder_radius = 0.05;  // fraction of ny
     int vtk_start_step = 0;
+    // user-defined obstacle (lbm_solver --obstacle-mask; not in the reference): the global [ny][nx] mask, row 0 first, in place of
+    // the cylinder. Its reference length D is the frontal height: the number of rows that hold a solid cell.
+    std::string obstacle_mask_file;
+    std::vector<unsigned char> obstacle_mask;
+    int mask_frontal_height = 0;
 
     double nu() const { return (tau - 0.5) / 3.0; }
-    double reynolds() const { return inlet_velocity * (2.0 * cylinder_radius * ny) / nu(); }
+    bool masked() const { return !obstacle_mask.empty(); }
+    double reynolds() const {
+        if (masked()) return inlet_velocity * mask_frontal_height / nu();
+        return inlet_velocity * (2.0 * cylinder_radius * ny) / nu();
+    }
     int get_cylinder_x() const { return static_cast<int>(cylinder_x * nx); }
     int get_cylinder_y() const { return static_cast<int>(cylinder_y * ny); }
     int get_cylinder_radius_cells() const { return static_cast<int>(cylinder_radius * ny); }

@@ -24,7 +24,11 @@ public:
                         "  Reynolds number = %g\n", params_.nx, params_.ny, params_.tau, params_.nu(),
                         params_.inlet_velocity, params_.reynolds());
         const int solid = grid_.setup_and_initialise();
-        if (!opt_.quiet) {
+        if (!opt_.quiet && params_.masked()) {
+            std::printf("  Obstacle: mask %s, frontal height D=%d cells\n  Solid cells: %d\n  Plan: %s\n", params_.obstacle_mask_file.c_str(),
+                        params_.mask_frontal_height, solid, grid_.plan());
+            std::fflush(stdout);
+        } else if (!opt_.quiet) {
             std::printf("  Cylinder: center=(%d,%d), radius=%d cells\n  Solid cells: %d\n  Plan: %s\n",
                         params_.get_cylinder_x(), params_.get_cylinder_y(), params_.get_cylinder_radius_cells(), solid,
                         grid_.plan());

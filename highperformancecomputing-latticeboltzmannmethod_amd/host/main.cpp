@@ -4,6 +4,7 @@
 #include "compat/LBMConfig.h"
 #include "compat/LBMIO.h"
 #include "compat/LBMSolver.h"
+#include "lbm/geometry.hpp"
 
 #include <cstdio>
 #include <cstdlib>
@@ -16,12 +17,14 @@ static void usage() {
               "           [--reynolds RE] [--cylinder-x F] [--cylinder-y F] [--cylinder-radius F] [--vtk-start-step N]\n"
               "           [--no-vtk] [--no-final] [--sync-vtk] [--fp32] [--contracted] [--no-tune] [--device D] [--quiet]\n"
               "           [--gpus N] [--strips N] [--rccl]\n"
-              "           [--checkpoint FILE] [--restart FILE]\n"
+              "           [--checkpoint FILE] [--restart FILE] [--obstacle-mask FILE.pgm]\n"
               "Defaults are the reference's SimulationParams (LBMConfig.h:37-51). --reynolds sets the inlet velocity\n"
               "from tau and the cylinder diameter so that params.reynolds() equals RE.\n"
               "--gpus N cuts the lattice into N row strips, one per GPU of this node, advanced in lockstep by this process\n"
               "with the halo rows copied GPU to GPU over xGMI (--rccl: RCCL send/recv instead); --strips M > N puts several\n"
-              "strips on one GPU. --contracted: FMA-contracted collision (as the reference's -ffast-math -mfma build).");
+              "strips on one GPU. --contracted: FMA-contracted collision (as the reference's -ffast-math -mfma build).\n"
+              "--obstacle-mask: the obstacle as a P5 / P2 PGM of exactly nx x ny pixels (nonzero = solid; the first image row\n"
+              "is the top lattice row) in place of the cylinder; Cd / Cl and the Reynolds number then use its frontal height.");
 }
 
 int main(int argc, char** argv) {
@@ -60,10 +63,22 @@ int main(int argc, char** argv) {
         else if (k == "--quiet") opt.quiet = true;
         else if (k == "--restart") restart_from = val();
         else if (k == "--checkpoint") checkpoint_to = val();
+        else if (k == "--obstacle-mask") params.obstacle_mask_file = val();
         else if (k == "--help" || k == "-h") { usage(); return 0; }
         else { std::fprintf(stderr, "unknown option %s\n", k.c_str()); usage(); return 2; }
     }
-    if (reynolds > 0.0) params.inlet_velocity = reynolds * params.nu() / (2.0 * params.cylinder_radius * params.ny);
+    if (!params.obstacle_mask_file.empty()) {   // parsed and checked before any device is touched
+        try {
+            LBM::ObstacleMask m = LBM::read_obstacle_pgm(params.obstacle_mask_file, params.nx, params.ny);
+            params.obstacle_mask = std::move(m.cells);
+            params.mask_frontal_height = m.frontal_height;
+        } catch (const std::exception& e) {
+            std::fprintf(stderr, "%s\n", e.what());
+            return 2;
+        }
+    }
+    if (reynolds > 0.0 && params.masked()) params.inlet_velocity = reynolds * params.nu() / params.mask_frontal_height;
+    else if (reynolds > 0.0) params.inlet_velocity = reynolds * params.nu() / (2.0 * params.cylinder_radius * params.ny);
     try {
         LBM::Solver solver(params, vtk, opt);
         LBM::IOManager io_manager;

@@ -111,8 +111,18 @@ int  lbm_get_populations(lbm_ctx* c, int which, double* aos);
  * ignored, they belong to the halo logic) and redoes collision_step() on it. Custom initial conditions enter here.
  * Until the next lbm_step the snapshots still show the values before the call. Synchronises. */
 int  lbm_set_f_current(lbm_ctx* c, const double* aos);
-/* Grid::is_solid (LBMGrid.h:146-148) for this strip, [local_ny][nx] bytes. */
+/* Grid::is_solid (LBMGrid.h:146-148) for this strip, [local_ny][nx] bytes (the mask of lbm_set_solid_mask where one is set). */
 int  lbm_get_solid(lbm_ctx* c, unsigned char* mask);
+/* The write side of the geometry: generalises Grid::setup_geometry (LBMGrid.h:152-173), which marks the one disc of the
+ * cylinder_* parameters, to any set of solid cells. `mask` is the GLOBAL [ny][nx] byte array, row y = 0 first (the layout of
+ * lbm_get_solid); nonzero = solid. Every strip of a run is given the same global array and keeps the rows it can ever query (its
+ * own +- 12 ghost rows). Call after lbm_create and before lbm_initialise, like the options (the plan is measured on this geometry);
+ * from then on the cylinder_* parameters no longer define the geometry. The reference's semantics carry over unchanged: solid cells
+ * hold w_i for ever, the collision and the wall / inlet / outlet conditions skip them, fluid cells pull w_i from solid neighbours,
+ * forces are the momentum exchange over solid->fluid links (LBMSolver.h:84-265, LBMIO.h:133-168). lbm_get_solid, the solid count
+ * of lbm_initialise, lbm_get_macros and the force log follow the mask; checkpoints carry its digest (lbm_save_state).
+ * LBM_ERR_ARG: null pointer, nx / ny other than the domain's, or an initialised context. */
+int  lbm_set_solid_mask(lbm_ctx* c, const unsigned char* mask, int nx, int ny);
 
 /* ---- strip halo exchange (replaces Grid::exchange_ghost_cells, LBMGrid.h:249-283) ----
  * Device path: RCCL send/recv of the LBM_HALO_ROWS edge rows per face (one contiguous run in the row-interleaved
@@ -271,6 +281,13 @@ int lbm_debug_choreography(int nx, int ny, const int* bounds2, int nstrips, int 
  * flagged. Replaces the tag / count matching of the reference's MPI_Isend / MPI_Irecv pairs (LBMGrid.h:255-276). */
 int lbm_debug_p2p_matching(int nx, int ny, const int* bounds2, int nranks, int precision, const char* options, const char* options_rank1,
                            const int* calls2, int ncalls, char* out, int cap);
+/* Test hook, callable without a device: the packing lbm_set_solid_mask makes for the strip [y_start, y_start + local_ny) of a global
+ * [ny][nx] mask (csrc/lbm_geom.hpp). dims9 = {first window row, window rows, 64-bit words per row, 8x8 blocks per row, block rows,
+ * bounding box of the whole mask x0, x1, y0, y1 (x1 < x0: no solid cell)}; bits ([rows][words]) and sat ([block rows + 1][blocks + 1],
+ * the summed-area table of solid counts per 8x8 block) are copied where not null. near_out[k] = the kernels' block-uniform query
+ * "any solid cell in the box" for boxes4[k] = {x0, x1, y0, y1} (global, inclusive), answered from the coarse table. */
+int lbm_debug_geometry(const unsigned char* mask, int nx, int ny, int y_start, int local_ny, int* dims9, unsigned long long* bits, long bits_cap,
+                       int* sat, long sat_cap, const int* boxes4, int nbox, int* near_out);
 /* SHA-256 (16 hex digits) of the sources this binary was compiled from (csrc/ and this header); build.py rebuilds
  * when it differs from the tree, bench.py prints it. */
 const char* lbm_build_id(void);
