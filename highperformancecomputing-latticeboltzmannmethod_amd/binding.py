@@ -57,6 +57,7 @@ def lib():
         L.lbm_set_f_current.argtypes = [vp, dp]
         L.lbm_get_solid.argtypes = [vp, C.POINTER(C.c_ubyte)]
         L.lbm_set_solid_mask.argtypes = [vp, C.POINTER(C.c_ubyte), C.c_int, C.c_int]
+        L.lbm_set_inlet_profile.argtypes = [vp, dp, C.c_int]
         ip = C.POINTER(C.c_int)
         L.lbm_debug_geometry.argtypes = [C.POINTER(C.c_ubyte), C.c_int, C.c_int, C.c_int, C.c_int, ip, C.POINTER(C.c_ulonglong), C.c_long,
                                          ip, C.c_long, ip, C.c_int, ip]
@@ -147,17 +148,45 @@ def debug_geometry(solid, y_start=0, local_ny=0, boxes=()):
     return d, bits, sat, near
 
 
+def parabolic_profile(ny, mean):
+    """The inlet profile of lbm_solver --inlet-profile parabolic (host/lbm/inlet.hpp, operation by operation): the Poiseuille
+    shape s(1-s), s = (y + 0.5)/ny, scaled so that its mean over the ny rows is `mean`. float64 [ny], row 0 (bottom) first."""
+    return scale_inlet_profile(parabolic_shape(ny), mean)
+
+
+def parabolic_shape(ny):
+    s = (np.arange(ny, dtype=np.float64) + 0.5) / ny
+    return s * (1.0 - s)
+
+
+def scale_inlet_profile(shape, mean):
+    """u[y] = shape[y] * (mean / (sum of the shape, rows in order, / ny)), as lbm_solver scales a profile file's shape."""
+    shape = np.asarray(shape, dtype=np.float64)
+    total = 0.0
+    for v in shape.tolist():   # sequential, in row order (numpy's pairwise sum would round differently)
+        total += v
+    shape_mean = total / len(shape)
+    if not (np.isfinite(shape_mean) and shape_mean > 0.0):
+        raise ValueError("the mean of an inlet profile's shape must be positive")
+    u = shape * (mean / shape_mean)
+    if not np.all(u < 1.0):
+        raise ValueError("inlet velocities must stay below 1")
+    return u
+
+
 def _dp(a):
     return a.ctypes.data_as(C.POINTER(C.c_double)) if a is not None else None
 
 
 class Context:
     """One strip of the lattice on one GPU (struct lbm_ctx). solid: optional bool / uint8 (ny, nx) array of the WHOLE domain, row
-    y = 0 first, nonzero = solid (lbm_set_solid_mask): the obstacle geometry in place of the cylinder_* disc."""
+    y = 0 first, nonzero = solid (lbm_set_solid_mask): the obstacle geometry in place of the cylinder_* disc. inlet_profile: optional
+    float64 [ny] of absolute inlet x-velocities of the WHOLE domain, row y = 0 first (lbm_set_inlet_profile), in place of the
+    uniform inlet_velocity (see parabolic_profile)."""
 
     def __init__(self, nx, ny, tau=0.6, inlet_velocity=0.01333, cylinder_x=0.2, cylinder_y=0.5,
                  cylinder_radius=0.05, y_start=0, local_ny=0, precision="f64", device=0, force_log_capacity=0,
-                 options=None, solid=None):
+                 options=None, solid=None, inlet_profile=None):
         self.L = lib()
         self.params = Params(tau, inlet_velocity, nx, ny, cylinder_x, cylinder_y, cylinder_radius, y_start,
                              local_ny, {"f64": 0, "f32": 1}[precision], force_log_capacity)
@@ -171,6 +200,8 @@ class Context:
             self.set_option(k, v)
         if solid is not None:
             self.set_solid_mask(solid)
+        if inlet_profile is not None:
+            self.set_inlet_profile(inlet_profile)
 
     def _chk(self, rc):
         if rc < 0:
@@ -201,6 +232,13 @@ class Context:
         """lbm_set_solid_mask: the global (ny, nx) mask; before initialise()."""
         m = _mask_bytes(solid, self.nx, self.ny)
         self._chk(self.L.lbm_set_solid_mask(self.h, m.ctypes.data_as(C.POINTER(C.c_ubyte)), self.nx, self.ny))
+
+    def set_inlet_profile(self, u):
+        """lbm_set_inlet_profile: the global [ny] inlet velocities (absolute, row 0 first); before initialise()."""
+        a = np.ascontiguousarray(u, dtype=np.float64)
+        if a.ndim != 1:
+            raise ValueError(f"inlet profile must be one-dimensional, not of shape {a.shape}")
+        self._chk(self.L.lbm_set_inlet_profile(self.h, _dp(a), a.size))
 
     def initialise(self):
         n = C.c_int()
@@ -328,15 +366,15 @@ class Context:
 class Group:
     """n strips of one lattice driven in lockstep by this process (lbm_group_*): one Context per strip, bottom to top.
     transport: "peer" (device copies / hipMemcpyPeerAsync) or "rccl" (ncclCommInitAll; distinct devices).
-    solid: optional global (ny, nx) obstacle mask, given to every member (Context)."""
+    solid: optional global (ny, nx) obstacle mask, inlet_profile: optional global [ny] inlet velocities; both given to every member."""
 
-    def __init__(self, nx, ny, bounds, devices=None, transport="peer", options=None, solid=None, **kw):
+    def __init__(self, nx, ny, bounds, devices=None, transport="peer", options=None, solid=None, inlet_profile=None, **kw):
         from .strips import partition_rows
         if isinstance(bounds, int):
             bounds = partition_rows(ny, bounds)
         devices = devices or [0] * len(bounds)
         self.nx, self.ny = nx, ny
-        self.ctxs = [Context(nx, ny, y_start=y0, local_ny=n, device=d, options=options, solid=solid, **kw)
+        self.ctxs = [Context(nx, ny, y_start=y0, local_ny=n, device=d, options=options, solid=solid, inlet_profile=inlet_profile, **kw)
                      for (y0, n), d in zip(bounds, devices)]
         self.L = lib()
         self._arr = (C.c_void_p * len(self.ctxs))(*[c.h for c in self.ctxs])

@@ -246,6 +246,13 @@ struct lbm_ctx {
     MaskView mview;                  // device pointers of hmask's bitmap and coarse table
     double* d_fpart = nullptr;       // k_forces: partial sums of the chunks of a large force box (masked contexts only)
     int fpart_chunks = 0;
+    // The inflow: d_urow = the inlet velocity of every global row in the element type, read-only (step kernels, k_macros): inlet_velocity
+    // on every row, or the profile of lbm_set_inlet_profile (has_profile), whose digest checkpoints carry and whose initial
+    // equilibria f_eq(1,(u[y],0)), [ny][Q], k_init reads from d_feqrow.
+    void* d_urow = nullptr;
+    bool has_profile = false;
+    unsigned long long prof_digest = 0;
+    void* d_feqrow = nullptr;
     // options
     int alternate = 1;   // walk the rows bottom-up / top-down on alternate steps (Infinity Cache reuse)
     int use_nt = 0;      // non-temporal stores in the step kernel

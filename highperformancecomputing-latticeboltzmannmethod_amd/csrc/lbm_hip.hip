@@ -51,12 +51,39 @@ int allreduce_doubles(lbm_ctx* c, double* vals, int n, int op) {
 }
 }  // namespace
 
+namespace {
+// f_eq(rho=1, u=(ux,0)) as Grid::initialise evaluates it (LBMUtils.h:9-12,22-65): the initial state of the inflow, uniform
+// (inlet_velocity) or per row (lbm_set_inlet_profile)
+void feq_inflow(double ux, double (&f)[Q]) {
+    const double uy = 0.0, rho = 1.0;
+    const double usq = ux * ux + uy * uy, t3 = 1.5 * usq;
+    f[0] = wgt<double>(0) * rho * (1.0 - 1.5 * usq);
+    for (int i = 1; i < Q; ++i) {
+        const double cu = (double)cx(i) * ux + (double)cy(i) * uy;
+        f[i] = (wgt<double>(i) * rho) * (((1.0 + 3.0 * cu) - t3) + 4.5 * (cu * cu));
+    }
+}
+// host doubles -> a device table in the context's element type (fp32: converted as inlet_velocity is)
+int upload_rows(const lbm_ctx* c, void* dst, const double* v, size_t n) {
+    if (c->esize == 4) {
+        std::vector<float> w(v, v + n);
+        HIPCHK(hipMemcpy(dst, w.data(), n * sizeof(float), hipMemcpyHostToDevice));
+    } else {
+        HIPCHK(hipMemcpy(dst, v, n * sizeof(double), hipMemcpyHostToDevice));
+    }
+    return LBM_OK;
+}
+}  // namespace
+
 // ---- checkpoint / restart (the reference keeps its state in memory only) ------------------------
 // File: header {magic "LBMCKPT1", nx, ny, y_start, local_ny, precision, steps_done, tau, inlet_velocity, cylinder_*}
 // followed by the post-collision populations P_{steps_done} of the strip's interior, [9][local_ny][nx] in the
 // element type. The state is complete: ghost cells and solid cells are reconstructed by lbm_initialise.
 // A context with a user-defined geometry (lbm_set_solid_mask) writes magic "LBMCKPT2" and the mask's 64-bit digest between the
 // header and the populations; it loads only such a file with the same digest, and an unmasked context only "LBMCKPT1" files.
+// A context with a per-row inlet profile (lbm_set_inlet_profile) writes magic "LBMCKPT3", then a 64-bit word of flags that say which
+// digests follow (bit 0 the mask's, bit 1 the profile's), then those digests in that order; it loads only a "LBMCKPT3" file with the
+// same profile digest (and the same mask digest, or none where it has no mask). Contexts without a profile never write or read it.
 namespace {
 struct CkptHeader {
     char magic[8];
@@ -141,15 +168,7 @@ int lbm_create(const lbm_params* p, int device, lbm_ctx** out) {
     c->cyl_x = (int)(p->cylinder_x * p->nx);
     c->cyl_y = (int)(p->cylinder_y * p->ny);
     c->cyl_r = (int)(p->cylinder_radius * p->ny);
-    {   // f_eq(rho=1, u=(u_in,0)) as Grid::initialise evaluates it (LBMUtils.h:9-12,22-65)
-        const double ux = p->inlet_velocity, uy = 0.0, rho = 1.0;
-        const double usq = ux * ux + uy * uy, t3 = 1.5 * usq;
-        c->feq_in[0] = wgt<double>(0) * rho * (1.0 - 1.5 * usq);
-        for (int i = 1; i < Q; ++i) {
-            const double cu = (double)cx(i) * ux + (double)cy(i) * uy;
-            c->feq_in[i] = (wgt<double>(i) * rho) * (((1.0 + 3.0 * cu) - t3) + 4.5 * (cu * cu));
-        }
-    }
+    feq_inflow(p->inlet_velocity, c->feq_in);
     c->log_cap = p->force_log_capacity > 0 ? p->force_log_capacity : 4096;
     auto bail = [&](int code) { lbm_destroy(c); return code; };
 #define HIPTRY(expr)                                                                                             \
@@ -192,6 +211,11 @@ int lbm_create(const lbm_params* p, int device, lbm_ctx** out) {
     } else {
         HIPTRY(hipMemcpy(c->d_feq, c->feq_in, Q * sizeof(double), hipMemcpyHostToDevice));
     }
+    HIPTRY(hipMalloc(&c->d_urow, (size_t)p->ny * c->esize));   // the uniform inflow until lbm_set_inlet_profile replaces it
+    {
+        const std::vector<double> u((size_t)p->ny, p->inlet_velocity);
+        if (int rc = upload_rows(c, c->d_urow, u.data(), u.size())) return bail(rc);
+    }
     HIPTRY(hipMalloc(&c->d_force_log, 3 * sizeof(double) * c->log_cap));
     HIPTRY(hipMalloc(&c->d_halo, 4 * HR1 * Q * sizeof(double) * (size_t)c->nx));
     HIPTRY(hipMalloc(&c->d_red, 64 * sizeof(double)));
@@ -232,7 +256,8 @@ void lbm_destroy(lbm_ctx* c) {
     if (c->comm) { lbm_trace("destroy", "ctx %p ncclCommDestroy", (void*)c); ncclCommDestroy(c->comm); }
     c->pool.reset();
     void* ptrs[] = {c->buf[0], c->buf[1], c->scratch, c->d_macro, c->d_maxbits, c->d_unstable, c->d_tbase, c->d_solid_count, c->d_feq,
-                    c->d_force_now, c->d_force_log, c->d_halo, c->d_red, (void*)c->mview.bits, (void*)c->mview.sat, c->d_fpart};
+                    c->d_force_now, c->d_force_log, c->d_halo, c->d_red, (void*)c->mview.bits, (void*)c->mview.sat, c->d_fpart,
+                    c->d_urow, c->d_feqrow};
     for (void* q : ptrs)
         if (q) (void)hipFree(q);
     hipEvent_t evs[] = {c->ev_edge, c->ev_comm, c->ev_main, c->ev_t0, c->ev_t1, c->gev_main, c->gev_edge, c->gev_comm};
@@ -430,6 +455,40 @@ int lbm_set_solid_mask(lbm_ctx* c, const unsigned char* mask, int nx, int ny) {
     return LBM_OK;
 }
 
+int lbm_set_inlet_profile(lbm_ctx* c, const double* u, int ny) {
+    if (!c || !u) return fail(LBM_ERR_ARG, "lbm_set_inlet_profile: null argument");
+    if (c->initialised) return fail(LBM_ERR_ARG, "lbm_set_inlet_profile must be called before lbm_initialise");
+    if (ny != c->p.ny) return fail(LBM_ERR_ARG, "lbm_set_inlet_profile: %d rows given, the domain has %d", ny, c->p.ny);
+    for (int y = 0; y < ny; ++y)   // the Zou-He inlet divides by 1 - u
+        if (!std::isfinite(u[y]) || u[y] >= 1.0)
+            return fail(LBM_ERR_ARG, "lbm_set_inlet_profile: row %d has velocity %g (finite values below 1 only)", y, u[y]);
+    // The tables cover every global row, not only the strip's rows +- GR: the register kernel's garbage cells beyond a partial band
+    // may evaluate the inlet of any row of the domain, and a whole table keeps that read in bounds without a test in the kernel.
+    std::vector<double> feqrow((size_t)ny * Q);
+    for (int y = 0; y < ny; ++y) {
+        double f[Q];
+        feq_inflow(u[y], f);
+        for (int i = 0; i < Q; ++i) feqrow[(size_t)y * Q + i] = f[i];
+    }
+    unsigned long long d = 1469598103934665603ull;   // FNV-1a over ny and the bit patterns of the velocities
+    auto mix = [&](unsigned v) { d ^= v; d *= 1099511628211ull; };
+    mix((unsigned)ny);
+    for (int y = 0; y < ny; ++y) {
+        unsigned long long b;
+        memcpy(&b, &u[y], sizeof(b));
+        mix((unsigned)b); mix((unsigned)(b >> 32));
+    }
+    HIPCHK(hipSetDevice(c->device));
+    c->has_profile = false;
+    if (c->d_feqrow) { HIPCHK(hipFree(c->d_feqrow)); c->d_feqrow = nullptr; }
+    HIPCHK(hipMalloc(&c->d_feqrow, feqrow.size() * c->esize));
+    if (int rc = upload_rows(c, c->d_feqrow, feqrow.data(), feqrow.size())) return rc;
+    if (int rc = upload_rows(c, c->d_urow, u, (size_t)ny)) return rc;
+    c->prof_digest = d;
+    c->has_profile = true;
+    return LBM_OK;
+}
+
 int lbm_comm_unique_id(void* id128) {
     if (!id128) return fail(LBM_ERR_ARG, "null argument");
     static_assert(sizeof(ncclUniqueId) == 128, "ncclUniqueId is 128 bytes");
@@ -608,12 +667,17 @@ int lbm_save_state(lbm_ctx* c, const char* path) {
     FILE* fp = fopen(path, "wb");
     if (!fp) return fail(LBM_ERR_ARG, "cannot open %s for writing", path);
     CkptHeader h{};
-    memcpy(h.magic, c->has_mask ? "LBMCKPT2" : "LBMCKPT1", 8);
+    memcpy(h.magic, c->has_profile ? "LBMCKPT3" : c->has_mask ? "LBMCKPT2" : "LBMCKPT1", 8);
     h.nx = c->nx; h.ny = c->p.ny; h.y_start = c->p.y_start; h.local_ny = c->nyl; h.precision = c->p.precision;
     h.steps_done = c->steps_done; h.tau = c->p.tau; h.inlet_velocity = c->p.inlet_velocity;
     h.cylinder_x = c->p.cylinder_x; h.cylinder_y = c->p.cylinder_y; h.cylinder_radius = c->p.cylinder_radius;
     int rc = fwrite(&h, sizeof(h), 1, fp) == 1 ? LBM_OK : fail(LBM_ERR_ARG, "short write");
+    if (!rc && c->has_profile) {   // LBMCKPT3: flags, then the digests they announce
+        const unsigned long long flags = (c->has_mask ? 1ull : 0ull) | 2ull;
+        if (fwrite(&flags, sizeof(flags), 1, fp) != 1) rc = fail(LBM_ERR_ARG, "short write");
+    }
     if (!rc && c->has_mask && fwrite(&c->hmask.digest, sizeof(c->hmask.digest), 1, fp) != 1) rc = fail(LBM_ERR_ARG, "short write");
+    if (!rc && c->has_profile && fwrite(&c->prof_digest, sizeof(c->prof_digest), 1, fp) != 1) rc = fail(LBM_ERR_ARG, "short write");
     if (!rc) rc = DISPATCH(c, do_save<double>(c, fp), do_save<float>(c, fp));
     fclose(fp);
     return rc;
@@ -636,13 +700,20 @@ int lbm_load_state(lbm_ctx* c, const char* path) {
     if (!fp) return fail(LBM_ERR_ARG, "cannot open %s", path);
     CkptHeader h{};
     int rc = LBM_OK;
-    unsigned long long digest = 0;
-    const bool v1 = fread(&h, sizeof(h), 1, fp) == 1 && memcmp(h.magic, "LBMCKPT1", 8) == 0;
-    const bool v2 = !v1 && memcmp(h.magic, "LBMCKPT2", 8) == 0 && fread(&digest, sizeof(digest), 1, fp) == 1;
-    if (!v1 && !v2) rc = fail(LBM_ERR_ARG, "%s is not a checkpoint", path);
-    else if (v1 && c->has_mask) rc = fail(LBM_ERR_ARG, "checkpoint %s was written without an obstacle mask; this context has one", path);
-    else if (v2 && !c->has_mask) rc = fail(LBM_ERR_ARG, "checkpoint %s was written with an obstacle mask; this context has none", path);
-    else if (v2 && digest != c->hmask.digest) rc = fail(LBM_ERR_ARG, "checkpoint %s was written for a different obstacle mask", path);
+    unsigned long long digest = 0, flags = 0, pdigest = 0;
+    const bool head = fread(&h, sizeof(h), 1, fp) == 1;
+    const bool v1 = head && memcmp(h.magic, "LBMCKPT1", 8) == 0;
+    const bool v2 = head && memcmp(h.magic, "LBMCKPT2", 8) == 0 && fread(&digest, sizeof(digest), 1, fp) == 1;
+    const bool v3 = head && memcmp(h.magic, "LBMCKPT3", 8) == 0 && fread(&flags, sizeof(flags), 1, fp) == 1 && (flags & ~3ull) == 0 &&
+                    (!(flags & 1) || fread(&digest, sizeof(digest), 1, fp) == 1) && (!(flags & 2) || fread(&pdigest, sizeof(pdigest), 1, fp) == 1);
+    const bool f_mask = v2 || (v3 && (flags & 1)), f_prof = v3 && (flags & 2);
+    if (!v1 && !v2 && !v3) rc = fail(LBM_ERR_ARG, "%s is not a checkpoint", path);
+    else if (!f_prof && c->has_profile) rc = fail(LBM_ERR_ARG, "checkpoint %s was written without an inlet profile; this context has one", path);
+    else if (f_prof && !c->has_profile) rc = fail(LBM_ERR_ARG, "checkpoint %s was written with an inlet profile; this context has none", path);
+    else if (f_prof && pdigest != c->prof_digest) rc = fail(LBM_ERR_ARG, "checkpoint %s was written for a different inlet profile", path);
+    else if (!f_mask && c->has_mask) rc = fail(LBM_ERR_ARG, "checkpoint %s was written without an obstacle mask; this context has one", path);
+    else if (f_mask && !c->has_mask) rc = fail(LBM_ERR_ARG, "checkpoint %s was written with an obstacle mask; this context has none", path);
+    else if (f_mask && digest != c->hmask.digest) rc = fail(LBM_ERR_ARG, "checkpoint %s was written for a different obstacle mask", path);
     else if (h.nx != c->nx || h.ny != c->p.ny || h.y_start != c->p.y_start || h.local_ny != c->nyl ||
              h.precision != c->p.precision || h.tau != c->p.tau || h.inlet_velocity != c->p.inlet_velocity ||
              h.cylinder_x != c->p.cylinder_x || h.cylinder_y != c->p.cylinder_y || h.cylinder_radius != c->p.cylinder_radius)

@@ -121,7 +121,7 @@ __global__ void __launch_bounds__(NW * 64, (col_waves_per_simd<NW>())) k_stepc_c
     // one general cell: BCs, stability, collision (solid cells keep w_i); `count` = the cell's instability is reported
     auto update = [&](T (&f)[Q], int yg, bool solid, bool count, bool& bad) {
         T rho_bc, u_out;
-        if (!solid) apply_bcs(f, yg == 0, yg == a.ny_glob - 1, x == 0, x == a.nx - 1, a.u_in, rho_bc, u_out);
+        if (!solid) apply_bcs(f, yg == 0, yg == a.ny_glob - 1, x == 0, x == a.nx - 1, a.u_row, yg, rho_bc, u_out);
         bad |= unstable_if(f, count);
         bgk_collide<T, AR>(f, a.tau_inv);
         if (near_cyl) {

@@ -96,7 +96,8 @@ struct KArgs {
     double cyl_r2;     // (double)(r*r), LBMGrid.h:169
     MaskView mv;       // user-defined geometry (lbm_set_solid_mask); mv.bits == nullptr: the disc above
     T tau_inv;         // 1/tau, LBMSolver.h:85
-    T u_in;            // inlet velocity
+    const T* u_row;    // inlet velocity of global row yg at u_row[yg], every row of the domain: inlet_velocity on every row, or the
+                       // profile of lbm_set_inlet_profile. Read on the inlet column (x == 0) only, inside apply_bcs
     int* unstable_t;   // device word: first unstable iteration (INT_MAX if none)
     int t;             // iteration this launch completes, RELATIVE to *t_base (stability bookkeeping only)
     const int* t_base; // device word: the iteration `t` counts from. A launch replayed from a hipGraph carries a fixed `t`; the
@@ -155,12 +156,15 @@ __device__ __forceinline__ bool tile_near_solid(const KArgs<T>& a, int X0, int Y
 // apply_boundary_conditions on the pulled populations of ONE cell, in the reference's sequential loop order
 // bottom -> top -> inlet -> outlet (LBMSolver.h:152-236). Solid cells are skipped by every one
 // of those loops. Returns nothing; rho_bc/u_out are exposed for the macro snapshot kernel.
+// The inlet velocity of global row yg is u_row[yg] (KArgs::u_row): loaded inside the inlet branch only, so no cell off column 0
+// carries its address or value.
 template <typename T>
-__device__ __forceinline__ void apply_bcs(T (&f)[Q], bool bottom, bool top, bool inlet, bool outlet, T u_in,
+__device__ __forceinline__ void apply_bcs(T (&f)[Q], bool bottom, bool top, bool inlet, bool outlet, const T* u_row, int yg,
                                           T& rho_bc, T& u_out) {
     if (bottom) { f[2] = f[4]; f[5] = f[7]; f[6] = f[8]; }                    // :155-163
     if (top)    { f[4] = f[2]; f[7] = f[5]; f[8] = f[6]; }                    // :168-176
     if (inlet) {                                                              // :181-206 (Zou-He velocity)
+        const T u_in = u_row[yg];
         rho_bc = (f[0] + f[2] + f[4] + T(2.0) * (f[3] + f[6] + f[7])) / (T(1.0) - u_in);
         f[1] = f[3] + T(2.0 / 3.0) * rho_bc * u_in;
         f[5] = f[7] - T(0.5) * (f[2] - f[4]) + T(1.0 / 6.0) * rho_bc * u_in;
@@ -363,7 +367,7 @@ __global__ void __launch_bounds__(256) k_step_site(const KArgs<T> a) {
     if (MODE != MODE_COLLIDE_ONLY) {
         T rho_bc, u_out;
         if (!solid)
-            apply_bcs(f, yg == 0, yg == a.ny_glob - 1, x == 0, x == a.nx - 1, a.u_in, rho_bc, u_out);
+            apply_bcs(f, yg == 0, yg == a.ny_glob - 1, x == 0, x == a.nx - 1, a.u_row, yg, rho_bc, u_out);
     }
     if (MODE == MODE_STEP) {
         if (any_unstable(f)) atomicMin(a.unstable_t, *a.t_base + a.t);
@@ -470,7 +474,7 @@ __global__ void __launch_bounds__(NTH) k_step2_tile(const KArgs<T> a, const K2Ex
             bool solid = false;
             if (near_cyl) solid = solid_at(a, x, yg);   // block-uniform branch
             T rho_bc, u_out;
-            if (!solid) apply_bcs(f, yg == 0, yg == a.ny_glob - 1, x == 0, x == a.nx - 1, a.u_in, rho_bc, u_out);
+            if (!solid) apply_bcs(f, yg == 0, yg == a.ny_glob - 1, x == 0, x == a.nx - 1, a.u_row, yg, rho_bc, u_out);
             bad |= any_unstable(f);
             bgk_collide<T, AR>(f, a.tau_inv);
             if (near_cyl) {                    // solid cells keep w_i (the collision result of such a cell is discarded)
@@ -494,7 +498,7 @@ __global__ void __launch_bounds__(NTH) k_step2_tile(const KArgs<T> a, const K2Ex
         for (int i = 0; i < Q; ++i) f[i] = lds[i][ly + 1 - cy(i)][lx + 1 - cx(i)];
         const bool solid = near_cyl && solid_at(a, x, yg);
         T rho_bc, u_out;
-        if (!solid) apply_bcs(f, yg == 0, yg == a.ny_glob - 1, x == 0, x == a.nx - 1, a.u_in, rho_bc, u_out);
+        if (!solid) apply_bcs(f, yg == 0, yg == a.ny_glob - 1, x == 0, x == a.nx - 1, a.u_row, yg, rho_bc, u_out);
         bad |= any_unstable(f);
         if (solid) continue;
         bgk_collide<T, AR>(f, a.tau_inv);
@@ -575,7 +579,7 @@ __global__ void __launch_bounds__(NTH, (2 * NTH / 256)) k_step3_tile(const KArgs
                     bool solid = false;
                     if (near_cyl) solid = solid_at(a, x, yg);   // block-uniform branch
                     T rho_bc, u_out;
-                    if (!solid) apply_bcs(f, yg == 0, yg == a.ny_glob - 1, x == 0, x == a.nx - 1, a.u_in, rho_bc, u_out);
+                    if (!solid) apply_bcs(f, yg == 0, yg == a.ny_glob - 1, x == 0, x == a.nx - 1, a.u_row, yg, rho_bc, u_out);
                     bad |= any_unstable(f);
                     bgk_collide<T, AR>(f, a.tau_inv);
                     if (near_cyl) {            // solid cells keep w_i (the collision result of such a cell is discarded)
@@ -631,7 +635,7 @@ __global__ void __launch_bounds__(NTH, (2 * NTH / 256)) k_step3_tile(const KArgs
                     bool solid = false;
                     if (near_cyl) solid = solid_at(a, x, yg);   // block-uniform branch
                     T rho_bc, u_out;
-                    if (!solid) apply_bcs(f, yg == 0, yg == a.ny_glob - 1, x == 0, x == a.nx - 1, a.u_in, rho_bc, u_out);
+                    if (!solid) apply_bcs(f, yg == 0, yg == a.ny_glob - 1, x == 0, x == a.nx - 1, a.u_row, yg, rho_bc, u_out);
                     if (y <= y_end) bad |= any_unstable(f);
                     bgk_collide<T, AR>(f, a.tau_inv);
                     if (near_cyl) {            // solid cells keep w_i (the collision result of such a cell is discarded)
@@ -659,7 +663,7 @@ __global__ void __launch_bounds__(NTH, (2 * NTH / 256)) k_step3_tile(const KArgs
             } else {
                 const bool solid = near_cyl && solid_at(a, x, yg);
                 T rho_bc, u_out;
-                if (!solid) apply_bcs(f, yg == 0, yg == a.ny_glob - 1, x == 0, x == a.nx - 1, a.u_in, rho_bc, u_out);
+                if (!solid) apply_bcs(f, yg == 0, yg == a.ny_glob - 1, x == 0, x == a.nx - 1, a.u_row, yg, rho_bc, u_out);
                 bad |= any_unstable(f);
                 if (solid) continue;
             }
@@ -720,7 +724,7 @@ __global__ void __launch_bounds__(NTH, (2 * NTH / 256)) k_step4_tile(const KArgs
         bool solid = false;
         if (near_cyl) solid = solid_at(a, x, yg);   // block-uniform branch
         T rho_bc, u_out;
-        if (!solid) apply_bcs(f, yg == 0, yg == a.ny_glob - 1, x == 0, x == a.nx - 1, a.u_in, rho_bc, u_out);
+        if (!solid) apply_bcs(f, yg == 0, yg == a.ny_glob - 1, x == 0, x == a.nx - 1, a.u_row, yg, rho_bc, u_out);
         if (count) bad |= any_unstable(f);
         bgk_collide<T, AR>(f, a.tau_inv);
         if (near_cyl) {
@@ -818,7 +822,7 @@ __global__ void __launch_bounds__(NTH, (2 * NTH / 256)) k_step4_tile(const KArgs
         }
         const bool solid = near_cyl && solid_at(a, x, yg);
         T rho_bc, u_out;
-        if (!solid) apply_bcs(f, yg == 0, yg == a.ny_glob - 1, x == 0, x == a.nx - 1, a.u_in, rho_bc, u_out);
+        if (!solid) apply_bcs(f, yg == 0, yg == a.ny_glob - 1, x == 0, x == a.nx - 1, a.u_row, yg, rho_bc, u_out);
         bad |= any_unstable(f);
         if (solid) continue;
         bgk_collide<T, AR>(f, a.tau_inv);
@@ -919,7 +923,7 @@ __global__ void __launch_bounds__(TX * TY, (deep_waves_per_simd<T, TX, TY, D>())
         bool solid = false;
         if (near_cyl) solid = solid_at(a, x, yg);   // block-uniform branch
         T rho_bc, u_out;
-        if (!solid) apply_bcs(f, yg == 0, yg == a.ny_glob - 1, x == 0, x == a.nx - 1, a.u_in, rho_bc, u_out);
+        if (!solid) apply_bcs(f, yg == 0, yg == a.ny_glob - 1, x == 0, x == a.nx - 1, a.u_row, yg, rho_bc, u_out);
         if (count) bad |= any_unstable(f);
         bgk_collide<T, AR>(f, a.tau_inv);
         if (near_cyl) {
@@ -1029,7 +1033,7 @@ __global__ void __launch_bounds__(TX * TY, (deep_waves_per_simd<T, TX, TY, D>())
                 } else {
                     const bool solid = near_cyl && solid_at(a, x, yg);
                     T rho_bc, u_out;
-                    if (!solid) apply_bcs(f, yg == 0, yg == a.ny_glob - 1, x == 0, x == a.nx - 1, a.u_in, rho_bc, u_out);
+                    if (!solid) apply_bcs(f, yg == 0, yg == a.ny_glob - 1, x == 0, x == a.nx - 1, a.u_row, yg, rho_bc, u_out);
                     bad |= any_unstable(f);
                     if (!solid) {
                         bgk_collide<T, AR>(f, a.tau_inv);
@@ -1053,7 +1057,8 @@ __global__ void __launch_bounds__(TX * TY, (deep_waves_per_simd<T, TX, TY, D>())
 // ---------------------------------------------------------------------------------------------------------
 // Initialisation: Grid::initialise (LBMGrid.h:185-246) written into BOTH buffers, plus the permanent ghost
 // values of N1/N2 (see top of file). feq_in = f_eq(1,(u_in,0)) evaluated on the host in double with the
-// reference's bracket order (LBMUtils.h:9-12,46); solid cells get f_eq(1,0,0) = w_i.
+// reference's bracket order (LBMUtils.h:9-12,46); solid cells get f_eq(1,0,0) = w_i. With a per-row inlet profile the interior
+// fluid cells of row yg take f_eq(1,(u[yg],0)) instead, from a table built on the host the same way (the ghost frame keeps feq_in).
 template <typename T>
 struct InitArgs {
     T* a; T* b;
@@ -1061,6 +1066,7 @@ struct InitArgs {
     int cyl_x, cyl_y; double cyl_r2;
     MaskView mv;
     T feq_in[Q];
+    const T* feq_row = nullptr;   // lbm_set_inlet_profile: row yg (global) at feq_row[yg * Q + i], rows of the strip's window; nullptr: feq_in
     int* solid_count;
 };
 
@@ -1080,6 +1086,7 @@ __global__ void __launch_bounds__(256) k_init(const InitArgs<T> p) {
 #pragma unroll
     for (int i = 0; i < Q; ++i) {
         T v = p.feq_in[i];
+        if (p.feq_row && row_interior && col_interior) v = p.feq_row[(long)yg * Q + i];
         if (solid) v = wgt<T>(i);
         if (row_interior && !col_interior) v = T(0);   // N1: E/W ghost column of a globally-interior row
         p.a[(long)i * p.plane + c] = v;
@@ -1092,12 +1099,14 @@ __global__ void __launch_bounds__(256) k_init(const InitArgs<T> p) {
 //   fluid interior : moments of P_t at the cell. collision conserves rho and rho*u, so these equal the
 //                    pre-collision moments the reference stored at LBMSolver.h:112-114 to round-off (~1e-16).
 //   inlet/outlet   : (rho_bc, u_in, 0) / (1, u_out, 0) of apply_boundary_conditions of iteration t,
-//                    recomputed exactly as the step kernel did (pull from P_t + wall BC + Zou-He).
+//                    recomputed exactly as the step kernel did (pull from P_t + wall BC + Zou-He); u_in is the row's
+//                    value (u_row), also in the initial snapshot.
 //   solid          : (1, 0, 0) (rho never rewritten after init, u zeroed at LBMSolver.h:260-261).
 template <typename T>
 struct MacroArgs {
     const T* old; long plane; int pitch, xoff, nx, ny_loc, ny_glob, y_start;
-    int cyl_x, cyl_y; double cyl_r2; T u_in;
+    int cyl_x, cyl_y; double cyl_r2;
+    const T* u_row;     // inlet velocity per global row, as KArgs::u_row
     MaskView mv;
     int initial;        // steps_done == 0: analytic initial macros (LBMGrid.h:219-228)
     double* rho; double* ux; double* uy;   // [ny_loc][nx]
@@ -1115,16 +1124,16 @@ __global__ void __launch_bounds__(256) k_macros(const MacroArgs<T> p) {
         const bool solid = solid_at(p, x, yg);
         double r, vx, vy;
         if (solid) { r = 1.0; vx = 0.0; vy = 0.0; }
-        else if (p.initial) { r = 1.0; vx = (double)p.u_in; vy = 0.0; }
+        else if (p.initial) { r = 1.0; vx = (double)p.u_row[yg]; vy = 0.0; }
         else if (x == 0 || x == p.nx - 1) {
             T f[Q];
 #pragma unroll
             for (int i = 0; i < Q; ++i) f[i] = p.old[(long)i * p.plane + c - (long)cy(i) * p.pitch - cx(i)];
             T rho_bc = T(1), u_out = T(0);
-            apply_bcs(f, yg == 0, yg == p.ny_glob - 1, x == 0, x == p.nx - 1, p.u_in, rho_bc, u_out);
+            apply_bcs(f, yg == 0, yg == p.ny_glob - 1, x == 0, x == p.nx - 1, p.u_row, yg, rho_bc, u_out);
             // the outlet loop runs after the inlet loop (only matters for nx == 1)
             if (x == p.nx - 1) { r = 1.0; vx = (double)u_out; vy = 0.0; }
-            else { r = (double)rho_bc; vx = (double)p.u_in; vy = 0.0; }
+            else { r = (double)rho_bc; vx = (double)p.u_row[yg]; vy = 0.0; }
         } else {
             T rr = T(0), sx = T(0), sy = T(0);
 #pragma unroll

@@ -18,7 +18,7 @@ KArgs<T> make_kargs(const lbm_ctx* c, int src, int dst, int t) {
     a.cyl_r2 = (double)(c->cyl_r * c->cyl_r);
     if (c->has_mask) a.mv = c->mview;
     a.tau_inv = (T)(1.0 / c->p.tau);
-    a.u_in = (T)c->p.inlet_velocity;
+    a.u_row = static_cast<const T*>(c->d_urow);
     a.unstable_t = c->d_unstable;
     a.t = t - c->tbase_host;
     a.t_base = c->d_tbase;

@@ -275,7 +275,7 @@ int do_macros(lbm_ctx* c, bool want_max) {
     m.nx = c->nx; m.ny_loc = c->nyl; m.ny_glob = c->p.ny; m.y_start = c->p.y_start;
     m.cyl_x = c->cyl_x; m.cyl_y = c->cyl_y; m.cyl_r2 = (double)(c->cyl_r * c->cyl_r);
     if (c->has_mask) m.mv = c->mview;
-    m.u_in = (T)c->p.inlet_velocity;
+    m.u_row = static_cast<const T*>(c->d_urow);
     m.initial = (c->steps_done == 0);
     m.rho = c->d_macro; m.ux = c->d_macro + n; m.uy = c->d_macro + 2 * n;
     m.max_usq_bits = want_max ? c->d_maxbits : nullptr;

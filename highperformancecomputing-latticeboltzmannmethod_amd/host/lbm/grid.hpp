@@ -47,6 +47,7 @@ public:
             check(lbm_set_option(c, "tune", opt.tune ? 1 : 0), "lbm_set_option");
             check(lbm_set_option(c, "arith", opt.contracted ? 1 : 0), "lbm_set_option");
             if (p.masked()) check(lbm_set_solid_mask(c, p.obstacle_mask.data(), p.nx, p.ny), "lbm_set_solid_mask");
+            if (p.profiled()) check(lbm_set_inlet_profile(c, p.inlet_profile.data(), p.ny), "lbm_set_inlet_profile");
             y += n;
         }
         check(lbm_group_link(ctx_.data(), (int)ctx_.size(), opt.rccl ? 1 : 0), "lbm_group_link");

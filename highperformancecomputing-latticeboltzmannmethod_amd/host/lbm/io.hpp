@@ -183,6 +183,7 @@ private:
             row_i("reference_length", p.mask_frontal_height);
             f.put("obstacle_mask,"); f.put(p.obstacle_mask_file.c_str()); f.put("\n");
         }
+        if (p.profiled()) { f.put("inlet_profile,"); f.put(p.inlet_profile_spec.c_str()); f.put("\n"); }   // (profiled runs only, likewise)
         std::printf("  simulation_params.csv written\n");
     }
     // calculate_time_averaged_drag (LBMIO.h:367-413): statistics of the CSV values (8 decimals) for timestep > 1000.

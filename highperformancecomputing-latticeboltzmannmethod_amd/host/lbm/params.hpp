@@ -34,9 +34,14 @@ struct SimulationParams {
     std::string obstacle_mask_file;
     std::vector<unsigned char> obstacle_mask;
     int mask_frontal_height = 0;
+    // per-row inlet profile (lbm_solver --inlet-profile; not in the reference): "parabolic" or the file of its shape, and the ny
+    // absolute velocities, row 0 first, whose mean is inlet_velocity (host/lbm/inlet.hpp). Empty: inlet_velocity on every row.
+    std::string inlet_profile_spec;
+    std::vector<double> inlet_profile;
 
     double nu() const { return (tau - 0.5) / 3.0; }
     bool masked() const { return !obstacle_mask.empty(); }
+    bool profiled() const { return !inlet_profile.empty(); }
     double reynolds() const {
         if (masked()) return inlet_velocity * mask_frontal_height / nu();
         return inlet_velocity * (2.0 * cylinder_radius * ny) / nu();

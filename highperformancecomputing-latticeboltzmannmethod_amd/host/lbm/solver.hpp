@@ -24,6 +24,8 @@ public:
                         "  Reynolds number = %g\n", params_.nx, params_.ny, params_.tau, params_.nu(),
                         params_.inlet_velocity, params_.reynolds());
         const int solid = grid_.setup_and_initialise();
+        if (!opt_.quiet && params_.profiled())
+            std::printf("  Inlet: profile %s, mean velocity %g (Cd / Cl refer to it)\n", params_.inlet_profile_spec.c_str(), params_.inlet_velocity);
         if (!opt_.quiet && params_.masked()) {
             std::printf("  Obstacle: mask %s, frontal height D=%d cells\n  Solid cells: %d\n  Plan: %s\n", params_.obstacle_mask_file.c_str(),
                         params_.mask_frontal_height, solid, grid_.plan());

@@ -5,6 +5,7 @@
 #include "compat/LBMIO.h"
 #include "compat/LBMSolver.h"
 #include "lbm/geometry.hpp"
+#include "lbm/inlet.hpp"
 
 #include <cstdio>
 #include <cstdlib>
@@ -18,13 +19,19 @@ static void usage() {
               "           [--no-vtk] [--no-final] [--sync-vtk] [--fp32] [--contracted] [--no-tune] [--device D] [--quiet]\n"
               "           [--gpus N] [--strips N] [--rccl]\n"
               "           [--checkpoint FILE] [--restart FILE] [--obstacle-mask FILE.pgm]\n"
+              "           [--inlet-profile parabolic|FILE] [--print-inlet-profile]\n"
               "Defaults are the reference's SimulationParams (LBMConfig.h:37-51). --reynolds sets the inlet velocity\n"
               "from tau and the cylinder diameter so that params.reynolds() equals RE.\n"
               "--gpus N cuts the lattice into N row strips, one per GPU of this node, advanced in lockstep by this process\n"
               "with the halo rows copied GPU to GPU over xGMI (--rccl: RCCL send/recv instead); --strips M > N puts several\n"
               "strips on one GPU. --contracted: FMA-contracted collision (as the reference's -ffast-math -mfma build).\n"
               "--obstacle-mask: the obstacle as a P5 / P2 PGM of exactly nx x ny pixels (nonzero = solid; the first image row\n"
-              "is the top lattice row) in place of the cylinder; Cd / Cl and the Reynolds number then use its frontal height.");
+              "is the top lattice row) in place of the cylinder; Cd / Cl and the Reynolds number then use its frontal height.\n"
+              "--inlet-profile: one inlet velocity per row instead of the plug inflow. parabolic: the Poiseuille profile\n"
+              "s(1-s), s = (y+0.5)/ny; FILE: a text file of ny numbers, row 0 (bottom) first ('#' comments and blank lines\n"
+              "allowed), giving the shape. Either is scaled so that its mean over the ny rows is the inlet velocity, which\n"
+              "stays the reference velocity: Reynolds number, --reynolds and Cd / Cl refer to the bulk (mean) velocity.\n"
+              "--print-inlet-profile: print the ny inlet velocities (row 0 first) and exit without opening a device.");
 }
 
 int main(int argc, char** argv) {
@@ -32,6 +39,7 @@ int main(int argc, char** argv) {
     LBM::BackendOptions opt;
     bool vtk = true, final_results = true;
     std::string restart_from, checkpoint_to;
+    bool print_profile = false;
     double reynolds = -1.0;
     for (int a = 1; a < argc; ++a) {
         const std::string k = argv[a];
@@ -64,6 +72,8 @@ int main(int argc, char** argv) {
         else if (k == "--restart") restart_from = val();
         else if (k == "--checkpoint") checkpoint_to = val();
         else if (k == "--obstacle-mask") params.obstacle_mask_file = val();
+        else if (k == "--inlet-profile") params.inlet_profile_spec = val();
+        else if (k == "--print-inlet-profile") print_profile = true;
         else if (k == "--help" || k == "-h") { usage(); return 0; }
         else { std::fprintf(stderr, "unknown option %s\n", k.c_str()); usage(); return 2; }
     }
@@ -79,6 +89,19 @@ int main(int argc, char** argv) {
     }
     if (reynolds > 0.0 && params.masked()) params.inlet_velocity = reynolds * params.nu() / params.mask_frontal_height;
     else if (reynolds > 0.0) params.inlet_velocity = reynolds * params.nu() / (2.0 * params.cylinder_radius * params.ny);
+    if (!params.inlet_profile_spec.empty()) {   // scaled to the final inlet velocity, checked before any device is touched
+        try {
+            params.inlet_profile = LBM::build_inlet_profile(params.inlet_profile_spec, params.ny, params.inlet_velocity);
+        } catch (const std::exception& e) {
+            std::fprintf(stderr, "%s\n", e.what());
+            return 2;
+        }
+    }
+    if (print_profile) {
+        if (!params.profiled()) { std::fprintf(stderr, "--print-inlet-profile needs --inlet-profile\n"); return 2; }
+        for (double u : params.inlet_profile) std::printf("%.17g\n", u);
+        return 0;
+    }
     try {
         LBM::Solver solver(params, vtk, opt);
         LBM::IOManager io_manager;

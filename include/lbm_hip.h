@@ -123,6 +123,17 @@ int  lbm_get_solid(lbm_ctx* c, unsigned char* mask);
  * of lbm_initialise, lbm_get_macros and the force log follow the mask; checkpoints carry its digest (lbm_save_state).
  * LBM_ERR_ARG: null pointer, nx / ny other than the domain's, or an initialised context. */
 int  lbm_set_solid_mask(lbm_ctx* c, const unsigned char* mask, int nx, int ny);
+/* The inflow: generalises the Zou-He velocity inlet (LBMSolver.h:181-206), which imposes inlet_velocity on every row, to one
+ * x-velocity per row. `u` is the GLOBAL array of ny absolute lattice velocities, row y = 0 (bottom) first; no scaling is applied.
+ * Every strip of a run is given the same global array. Call after lbm_create and before lbm_initialise, like lbm_set_solid_mask.
+ * The reference's semantics carry over with u_in replaced by u[y] on row y: the wall rows still take bottom / top bounce-back first,
+ * then the inlet; solid inlet cells are skipped; interior fluid cells of row y start at f_eq(1, (u[y], 0)) (evaluated on the host in
+ * double, in the reference's bracket order), solid cells and the ghost frame as before; lbm_get_macros reports (rho_bc, u[y], 0) on
+ * the inlet column and ux = u[y] in the initial snapshot. inlet_velocity then only names the run (checkpoint header, the
+ * caller's Reynolds number). Checkpoints carry the profile's digest (lbm_save_state: magic "LBMCKPT3").
+ * LBM_ERR_ARG: null pointer, ny other than the domain's, an initialised context, or a value that is not finite or is >= 1 (the
+ * inlet divides by 1 - u). */
+int  lbm_set_inlet_profile(lbm_ctx* c, const double* u, int ny);
 
 /* ---- strip halo exchange (replaces Grid::exchange_ghost_cells, LBMGrid.h:249-283) ----
  * Device path: RCCL send/recv of the LBM_HALO_ROWS edge rows per face (one contiguous run in the row-interleaved
@@ -178,7 +189,8 @@ int  lbm_halo_import(lbm_ctx* c, const double* south_in, const double* north_in)
 
 /* Checkpoint / restart (the reference has none): the strip's post-collision populations and the
  * iteration counter. lbm_load_state needs an initialised context created with the same parameters; the macro /
- * population snapshots become available again after the next lbm_step. */
+ * population snapshots become available again after the next lbm_step. A file written with an obstacle mask or an inlet
+ * profile loads only into a context with the same mask and the same profile (the failure names which one differs). */
 int  lbm_save_state(lbm_ctx* c, const char* path);
 int  lbm_load_state(lbm_ctx* c, const char* path);
 

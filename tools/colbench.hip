@@ -26,7 +26,7 @@ struct Lattice {
     int nx, ny, pitch, xoff;
     long plane;
     size_t total;
-    T *A, *B, *d_feq;
+    T *A, *B, *d_feq, *d_urow;
     int* d_unst;
     int* d_zero;
     hipStream_t s;
@@ -53,12 +53,14 @@ struct Lattice {
         CK(hipMalloc(&d_zero, sizeof(int)));
         CK(hipMemset(d_zero, 0, sizeof(int)));
         CK(hipMalloc(&d_feq, Q * sizeof(T)));
+        CK(hipMalloc(&d_urow, ny * sizeof(T)));
         CK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
         CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
         u_in = 200.0 * (0.1 / 3.0) / (0.1 * ny);
         if (u_in > 0.1) u_in = 0.1;
+        { std::vector<T> u((size_t)ny, (T)u_in); CK(hipMemcpy(d_urow, u.data(), ny * sizeof(T), hipMemcpyHostToDevice)); }
     }
-    ~Lattice() { hipFree(A); hipFree(B); hipFree(d_unst); hipFree(d_feq); hipStreamDestroy(s); hipEventDestroy(e0); hipEventDestroy(e1); }
+    ~Lattice() { hipFree(A); hipFree(B); hipFree(d_unst); hipFree(d_feq); hipFree(d_urow); hipStreamDestroy(s); hipEventDestroy(e0); hipEventDestroy(e1); }
     KArgs<T> args(int depth_t) {
         KArgs<T> a{};
         a.y_lo = 0; a.y_cnt = ny; a.reverse = 0;
@@ -66,7 +68,7 @@ struct Lattice {
         a.plane = plane; a.pitch = pitch; a.xoff = xoff; a.nx = nx; a.ny_loc = ny; a.ny_glob = ny; a.y_start = 0;
         a.cyl_x = (int)(0.2 * nx); a.cyl_y = (int)(0.5 * ny);
         const int r = (int)(0.05 * ny); a.cyl_r2 = (double)(r * r);
-        a.tau_inv = (T)(1.0 / 0.6); a.u_in = (T)u_in; a.unstable_t = d_unst; a.t = depth_t; a.t_base = d_zero;
+        a.tau_inv = (T)(1.0 / 0.6); a.u_row = d_urow; a.unstable_t = d_unst; a.t = depth_t; a.t_base = d_zero;
         return a;
     }
     K2Extra<T> extra() { K2Extra<T> e; e.feq_in = d_feq; e.xcd = 1; e.nt = 1; e.ntl = g_ntl; e.small = (total * sizeof(T) + 4096 < (size_t(1) << 32)) ? 1 : 0; return e; }

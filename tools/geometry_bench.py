@@ -9,6 +9,9 @@ One JSON line per case, each on the plan the context measured for its own geomet
     square        a square cylinder of the disc's diameter
     porous        200 random discs in a bed of 1 % random solid cells: every tile is near a solid cell (no plain-fluid path)
     porous-site   the same bed on the one-iteration site kernel (k_step_site, pinned): the floor for comparison
+    disc-parabolic, disc-mask-parabolic
+                  disc and disc-mask with a parabolic inlet (lbm_set_inlet_profile, parabolic_profile of the same mean velocity):
+                  the per-row inlet table's cost (only the inlet column reads it)
 The timed window uses bench.py's fence: warm-up, lbm_sync, then K steps that end in lbm_sync."""
 import argparse
 import importlib
@@ -37,8 +40,8 @@ def porous(nx, ny, n=200, seed=7):
     return m
 
 
-def run(args, name, solid, kw, options=None):
-    with lbm.Context(args.nx, args.ny, device=args.device, solid=solid, options=options, **kw) as ctx:
+def run(args, name, solid, kw, options=None, inlet_profile=None):
+    with lbm.Context(args.nx, args.ny, device=args.device, solid=solid, options=options, inlet_profile=inlet_profile, **kw) as ctx:
         ctx.set_option("arith", 0 if args.strict else 1)
         ctx.set_option("trailing_pair", 1)
         nsolid = ctx.initialise()
@@ -80,6 +83,9 @@ def main():
     run(args, "porous", bed, kw)
     # the same bed on the one-iteration site kernel (pinned plan): the floor the fused kernels must stay above
     run(args, "porous-site", bed, kw, options=dict(tune=0, layout=1, nt=1, alternate=0, fuse=1))
+    prof = lbm.parabolic_profile(ny, kw["inlet_velocity"])
+    run(args, "disc-parabolic", None, kw, inlet_profile=prof)
+    run(args, "disc-mask-parabolic", disc, kw, inlet_profile=prof)
 
 
 if __name__ == "__main__":
