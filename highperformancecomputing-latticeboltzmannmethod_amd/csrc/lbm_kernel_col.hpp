@@ -50,22 +50,6 @@ __device__ __forceinline__ float from_right(float v) { return __builtin_bit_cast
 // 12 waves: six per SIMD, 80 VGPRs — the two-row fp64 strict shape), else one
 template <int NW> constexpr int col_waves_per_simd() { return NW == 12 ? 6 : NW <= 8 ? (2 * NW) / 4 : NW / 4; }
 
-// stability verdict of one cell, counted only where `valid` (garbage cells may hold anything, NaN included)
-template <typename T>
-__device__ __forceinline__ bool unstable_if(const T (&f)[Q], bool valid) {
-    unsigned o = 0;
-#pragma unroll
-    for (int i = 0; i < Q; ++i) o |= exp_word(f[i]);
-    o = valid ? o : 0u;
-    bool bad = false;
-    if (o & 0x40000000u) {
-#pragma unroll
-        for (int i = 0; i < Q; ++i) bad |= !(fabs(f[i]) <= T(1e5));
-        bad = bad && valid;
-    }
-    return bad;
-}
-
 // Tile walk: blocks are dealt round-robin over the 8 XCDs (each with its own 4 MiB L2) in index order; here every XCD walks
 // one contiguous run of the row-major tile order instead, so that x-neighbours — which share the lines at their common
 // edge — meet in the same L2 at the same time and every XCD streams whole lattice rows (149.6 -> 161.7 GLUPS at 4096x1024
@@ -108,27 +92,8 @@ __global__ void __launch_bounds__(NW * 64, (col_waves_per_simd<NW>())) k_stepc_c
     const int Xo = bx * OW;
     const int X0 = Xo - HW, Yr = Yo - HW;                  // region origin
     const int ry0 = w * R;                                 // this wave's first region row
-    const bool near_cyl = tile_near_solid(a, Xo, Yo, OW, OH, HW);
-    auto outside_value = [&](bool row_in, bool col_in, int i) -> T { return (row_in && !col_in) ? T(0) : e.feq_in[i]; };
-    const int yg0 = a.y_start + Yo;
-    // LEAN (block-uniform): every cell of the region is a plain fluid cell strictly inside the domain and the tile is full
-    const bool lean = !near_cyl && Xo >= HW + 1 && Xo + OW + HW <= a.nx - 1 && yg0 >= HW + 1 && yg0 + OH + HW <= a.ny_glob - 1 &&
-                      Yo + OH <= y_end && e.small;
-    const unsigned pitchB = (unsigned)a.pitch * (unsigned)sizeof(T), planeB = (unsigned)a.plane * (unsigned)sizeof(T);
-    const unsigned KB = pitchB + (unsigned)sizeof(T);
-    const __amdgpu_buffer_rsrc_t rsrc = buf_desc(reinterpret_cast<const char*>(a.src) - KB), rdst = buf_desc(a.dst);
+    const TileFrame<T> fr(a, e, Xo, Yo, y_end, OW, OH, HW);   // (its X0 / Y0 are the output origin Xo / Yo)
     const int x = X0 + lane;
-    // one general cell: BCs, stability, collision (solid cells keep w_i); `count` = the cell's instability is reported
-    auto update = [&](T (&f)[Q], int yg, bool solid, bool count, bool& bad) {
-        T rho_bc, u_out;
-        if (!solid) apply_bcs(f, yg == 0, yg == a.ny_glob - 1, x == 0, x == a.nx - 1, a.u_row, yg, rho_bc, u_out);
-        bad |= unstable_if(f, count);
-        bgk_collide<T, AR>(f, a.tau_inv);
-        if (near_cyl) {
-#pragma unroll
-            for (int i = 0; i < Q; ++i) f[i] = solid ? wgt<T>(i) : f[i];
-        }
-    };
     auto run = [&]<bool LEAN>() {
         T g[R][Q];
         bool bad = false;
@@ -136,7 +101,7 @@ __global__ void __launch_bounds__(NW * 64, (col_waves_per_simd<NW>())) k_stepc_c
         // bit j: the thread's cell of row j is solid. The thread <-> cell map is fixed for all D levels, so the geometry is looked
         // up once, here, and serves every level and the store predicate (block-uniform branch: only tiles near a solid cell)
         unsigned sbits = 0;
-        if (!LEAN && near_cyl && col_in) {
+        if (!LEAN && fr.near_solid && col_in) {
 #pragma unroll
             for (int j = 0; j < R; ++j) {
                 const int yg = a.y_start + Yr + ry0 + j;
@@ -147,14 +112,10 @@ __global__ void __launch_bounds__(NW * 64, (col_waves_per_simd<NW>())) k_stepc_c
         LBM_PROF(b, NW, w, 0);
         // ---- level 1: iteration t on the whole region, from HBM
         if (LEAN) {
-            const unsigned ub = (unsigned)(Yr + ry0 + GR) * pitchB + (unsigned)(a.xoff + X0) * (unsigned)sizeof(T) + KB;   // wave-uniform
-            const unsigned voff = (unsigned)lane * (unsigned)sizeof(T);
+            const unsigned ub = fr.src_off(a, Yr + ry0, X0), voff = (unsigned)lane * (unsigned)sizeof(T);   // wave-uniform, lane
             auto load_all = [&]<int AUX>() {
 #pragma unroll
-                for (int j = 0; j < R; ++j)
-#pragma unroll
-                    for (int i = 0; i < Q; ++i)
-                        g[j][i] = buf_load<T, AUX>(rsrc, voff, ub + (unsigned)j * pitchB + (unsigned)i * planeB - (unsigned)cy(i) * pitchB - (unsigned)(cx(i) * (int)sizeof(T)));
+                for (int j = 0; j < R; ++j) fr.template load<AUX>(g[j], voff, ub + (unsigned)j * fr.pitchB);
             };
             if (e.ntl) load_all.template operator()<2>(); else load_all.template operator()<0>();      // (block-uniform)
 #pragma unroll
@@ -169,12 +130,12 @@ __global__ void __launch_bounds__(NW * 64, (col_waves_per_simd<NW>())) k_stepc_c
                 const bool row_in = (yg >= 0 && yg < a.ny_glob);
                 if (!(row_in && col_in) || y > y_end + HW - 1) {
 #pragma unroll
-                    for (int i = 0; i < Q; ++i) g[j][i] = outside_value(row_in, col_in, i);
+                    for (int i = 0; i < Q; ++i) g[j][i] = outside_value(e, row_in, col_in, i);
                 } else {
                     const long c = (long)(y + GR) * a.pitch + a.xoff + x;
 #pragma unroll
                     for (int i = 0; i < Q; ++i) g[j][i] = a.src[(long)i * a.plane + c - (long)cy(i) * a.pitch - cx(i)];
-                    update(g[j], yg, (sbits >> j) & 1u, true, bad);
+                    cell_update_as<T, AR, true>(a, g[j], x, yg, (sbits >> j) & 1u, fr.near_solid, true, bad);
                 }
             }
         }
@@ -211,10 +172,10 @@ __global__ void __launch_bounds__(NW * 64, (col_waves_per_simd<NW>())) k_stepc_c
                     const bool row_in = (yg >= 0 && yg < a.ny_glob);
                     if (!(row_in && col_in)) {
 #pragma unroll
-                        for (int i = 0; i < Q; ++i) f[i] = outside_value(row_in, col_in, i);
+                        for (int i = 0; i < Q; ++i) f[i] = outside_value(e, row_in, col_in, i);
                         store = false;
                     } else {
-                        update(f, yg, (sbits >> j) & 1u, valid && y <= y_end + HW - L, badl);
+                        cell_update_as<T, AR, true>(a, f, x, yg, (sbits >> j) & 1u, fr.near_solid, valid && y <= y_end + HW - L, badl);
                         store = store && y < y_end && !((sbits >> j) & 1u);
                     }
                 }
@@ -222,19 +183,8 @@ __global__ void __launch_bounds__(NW * 64, (col_waves_per_simd<NW>())) k_stepc_c
 #pragma unroll
                     for (int i = 0; i < Q; ++i) g[j][i] = f[i];
                 } else if (store) {
-                    if (LEAN) {
-                        const unsigned ub = (unsigned)(y + GR) * pitchB + (unsigned)(a.xoff + X0) * (unsigned)sizeof(T);
-                        const unsigned voff = (unsigned)lane * (unsigned)sizeof(T);
-#pragma unroll
-                        for (int i = 0; i < Q; ++i) buf_store<NT>(f[i], rdst, voff, ub + (unsigned)i * planeB);
-                    } else {
-                        const long c = (long)(y + GR) * a.pitch + a.xoff + x;
-#pragma unroll
-                        for (int i = 0; i < Q; ++i) {
-                            T* p = a.dst + (long)i * a.plane + c;
-                            if (NT) __builtin_nontemporal_store(f[i], p); else *p = f[i];
-                        }
-                    }
+                    if (LEAN) fr.template store<NT>(f, (unsigned)lane * (unsigned)sizeof(T), fr.dst_off(a, y, X0));
+                    else store_cell<NT>(a, f, x, y);
                 }
                 }
                 if (j < R - 1) { p2 = n2; p5 = from_left(n5); p6 = from_right(n6); }   // row j+1 pulls them from this row
@@ -244,7 +194,7 @@ __global__ void __launch_bounds__(NW * 64, (col_waves_per_simd<NW>())) k_stepc_c
         };
         [&]<int... Ls>(std::integer_sequence<int, Ls...>) { (level.template operator()<Ls + 2>(), ...); }(std::make_integer_sequence<int, D - 1>{});
     };
-    if (lean) run.template operator()<true>();
+    if (fr.lean) run.template operator()<true>();
     else run.template operator()<false>();
 }
 

@@ -28,6 +28,8 @@
 //   k_stepc_col                  (lbm_kernel_col.hpp) five / six iterations with the lattice of a 64x32 region held in
 //                                registers: the production kernel of large grids and tall strips
 //   k_init, k_macros, k_forces, k_halo_pack/unpack   set-up and the output cadence
+// The fused kernels share the per-cell rule (cell_update / cell_update_last over bcs_at) and the block prologue (TileFrame);
+// k_step3_tile and k_step4_tile are one body (step_tile) at depth 3 and 4.
 // Arithmetic modes of the collision (enum Arith): strict IEEE operation by operation (bit-identical to the CPU oracle)
 // or FMA-contracted with one reciprocal (what the reference's -ffast-math -mfma build permits; <= 1e-10).
 //
@@ -177,6 +179,12 @@ __device__ __forceinline__ void apply_bcs(T (&f)[Q], bool bottom, bool top, bool
         f[6] = f[8] - T(0.5) * (f[2] - f[4]) - T(1.0 / 6.0) * rho_out * u_out;
         f[7] = f[5] + T(0.5) * (f[2] - f[4]) - T(1.0 / 6.0) * rho_out * u_out;
     }
+}
+// apply_bcs at global cell (x, yg) for the step kernels. `a`: any argument block with nx, ny_glob and u_row (KArgs, MacroArgs).
+template <typename A, typename T>
+__device__ __forceinline__ void bcs_at(const A& a, T (&f)[Q], int x, int yg) {
+    T rho_bc, u_out;
+    apply_bcs(f, yg == 0, yg == a.ny_glob - 1, x == 0, x == a.nx - 1, a.u_row, yg, rho_bc, u_out);
 }
 
 // Arithmetic of the collision (the only place the two modes differ):
@@ -341,6 +349,21 @@ __device__ __forceinline__ bool any_unstable(const T (&f)[Q]) {
     }
     return bad;
 }
+// the same verdict counted only where `valid`, branch-free in `valid` (k_stepc_col: its garbage cells may hold anything, NaN included)
+template <typename T>
+__device__ __forceinline__ bool unstable_if(const T (&f)[Q], bool valid) {
+    unsigned o = 0;
+#pragma unroll
+    for (int i = 0; i < Q; ++i) o |= exp_word(f[i]);
+    o = valid ? o : 0u;
+    bool bad = false;
+    if (o & 0x40000000u) {
+#pragma unroll
+        for (int i = 0; i < Q; ++i) bad |= !(fabs(f[i]) <= T(1e5));
+        bad = bad && valid;
+    }
+    return bad;
+}
 
 enum StepMode { MODE_STEP = 0, MODE_COLLIDE_ONLY = 1, MODE_STREAM_ONLY = 2 };
 
@@ -364,11 +387,7 @@ __global__ void __launch_bounds__(256) k_step_site(const KArgs<T> a) {
         f[i] = a.src[(long)i * a.plane + c - off];
     }
     const bool solid = solid_at(a, x, yg);
-    if (MODE != MODE_COLLIDE_ONLY) {
-        T rho_bc, u_out;
-        if (!solid)
-            apply_bcs(f, yg == 0, yg == a.ny_glob - 1, x == 0, x == a.nx - 1, a.u_row, yg, rho_bc, u_out);
-    }
+    if (MODE != MODE_COLLIDE_ONLY && !solid) bcs_at(a, f, x, yg);
     if (MODE == MODE_STEP) {
         if (any_unstable(f)) atomicMin(a.unstable_t, *a.t_base + a.t);
     }
@@ -396,54 +415,134 @@ __global__ void __launch_bounds__(256) k_step_site(const KArgs<T> a) {
 // at 4096x1024 fp64 against 112 for this kernel and 100 for this kernel with non-temporal stores; no measured plan ever took it. Retired
 // in round 4 with its 14 instantiations; round 5 removed the option "variant" that used to select it.)
 
-// Two timesteps per launch: temporal blocking through LDS. A block owns a TX x TY tile of outputs at iteration
-// t+1. Phase 1 computes P_{t+1} on the (TX+2) x (TY+2) region around it from global P_t — the step kernel's
-// per-cell sequence, with cells outside the domain taking their permanent ghost constants (N1/N2) and solid cells
-// w_i — into LDS; after one barrier phase 2 pulls from LDS, applies the BCs of iteration t+1, collides and stores
-// P_{t+2}. P_{t+1} never touches HBM: traffic per lattice update drops from 144 B to ~(1 + (TX+2)(TY+2)/(TX TY))*36 B
-// (82 B at 64x8, less when the tile halo is still in L2 / Infinity Cache). Same arithmetic per cell => results
-// bit-identical to two k_step_site launches (tests). Any nx (partial tiles at the right edge); rows of neighbouring strips must be
-// present (at least) two deep. LDS: 9*(TY+2)*(TX+4)*sizeof(T) (47.9 KB at TY=8, fp64: three blocks per CU).
 // feq_in: the nine initial-equilibrium values (permanent content of physical N/S ghost rows and corner ghosts), in
 // device memory: they are needed by the few cells of a region that lie outside the domain only, and passing them by
 // value would pin 18 scalar registers for the whole kernel (the fused kernels are SGPR-bound).
 template <typename T> struct K2Extra {
     const T* feq_in;
-    int small;   // the buffer is below 4 GiB: the lean path of k_step3_tile may address it with 32-bit byte offsets
+    int small;   // the buffer is below 4 GiB: the lean paths may address it with 32-bit byte offsets
     int xcd;     // remap the blocks so that every XCD walks one contiguous run of tiles (run-time: scalar index arithmetic only)
     int nt;      // non-temporal stores (run-time in the fused tile kernels: one block-uniform branch around the nine stores)
     int ntl;     // non-temporal LOADS at level 1 of the register kernel (run-time: one block-uniform branch around its 36 loads)
 };
 
-// the nine stores of one cell, plain or non-temporal (block-uniform choice)
-template <typename T>
-__device__ __forceinline__ void store_pops(T* base, long plane, const T (&f)[Q], bool nt) {
-    if (nt) {
+// ---------------------------------------------------------------------------------------------------------
+// What the fused step kernels (k_step2/3/4_tile, k_stepd_tile, k_stepc_col) share: the update of one cell, its loads and
+// stores, and the block prologue (TileFrame). Every per-cell rule of those kernels lives here.
+// (The general nine pulls stay written out in the kernels, and outside_value gives one value, not a cell: a loop over a cell
+// that is unrolled inside a helper before it is inlined compiles differently — two more VGPRs in k_step2_tile fp32.)
+
+// One general cell of a level (any cell of a non-LEAN path): BCs unless solid, the stability test where `count`, the
+// collision; a solid cell keeps w_i (its collision result is discarded). `near_solid` is block-uniform: tiles far from every
+// solid cell skip the select. BRANCH_FREE: the stability test is unstable_if (k_stepc_col, whose garbage cells are masked).
+template <typename T, int AR, bool BRANCH_FREE = false>
+__device__ __forceinline__ void cell_update_as(const KArgs<T>& a, T (&f)[Q], int x, int yg, bool solid, bool near_solid, bool count,
+                                               bool& bad) {
+    if (!solid) bcs_at(a, f, x, yg);
+    if (BRANCH_FREE) bad |= unstable_if(f, count);
+    else if (count) bad |= any_unstable(f);
+    bgk_collide<T, AR>(f, a.tau_inv);
+    if (near_solid) {
 #pragma unroll
-        for (int i = 0; i < Q; ++i) __builtin_nontemporal_store(f[i], base + (long)i * plane);
-    } else {
-#pragma unroll
-        for (int i = 0; i < Q; ++i) base[(long)i * plane] = f[i];
+        for (int i = 0; i < Q; ++i) f[i] = solid ? wgt<T>(i) : f[i];
     }
 }
-template <typename T>
-__device__ __forceinline__ void buf_store_pops(const T (&f)[Q], __amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff, unsigned planeB, bool nt) {
-    if (nt) {
-#pragma unroll
-        for (int i = 0; i < Q; ++i) buf_store<true>(f[i], r, voff, soff + (unsigned)i * planeB);
-    } else {
-#pragma unroll
-        for (int i = 0; i < Q; ++i) buf_store<false>(f[i], r, voff, soff + (unsigned)i * planeB);
-    }
+// ... with the geometry looked up here (block-uniform branch: only tiles near a solid cell)
+template <typename T, int AR>
+__device__ __forceinline__ void cell_update(const KArgs<T>& a, T (&f)[Q], int x, int yg, bool near_solid, bool count, bool& bad) {
+    bool solid = false;
+    if (near_solid) solid = solid_at(a, x, yg);
+    cell_update_as<T, AR>(a, f, x, yg, solid, near_solid, count, bad);
+}
+// A general cell of the last level, which stores: every cell is counted, and a solid cell is neither collided nor stored
+// (false: do not store the cell).
+template <typename T, int AR>
+__device__ __forceinline__ bool cell_update_last(const KArgs<T>& a, T (&f)[Q], int x, int yg, bool near_solid, bool& bad) {
+    const bool solid = near_solid && solid_at(a, x, yg);
+    if (!solid) bcs_at(a, f, x, yg);
+    bad |= any_unstable(f);
+    if (solid) return false;
+    bgk_collide<T, AR>(f, a.tau_inv);
+    return true;
 }
 
-template <typename T, int TY, int NTH, int AR = AR_STRICT>
-__global__ void __launch_bounds__(NTH) k_step2_tile(const KArgs<T> a, const K2Extra<T> e) {
-    constexpr int TX = 64, RW = TX + 2, RH = TY + 2, LP = RW + 2;
-    __shared__ T lds[Q][RH][LP];
-    // Tile of this block. Workgroups are dealt round-robin over the 8 XCDs (each with its own L2); with XCD the
-    // linear block id is remapped so that every XCD walks one contiguous run of tiles: horizontally adjacent tiles,
-    // which share the cache lines at their common edge, then run on the same L2 at the same time.
+// a region cell outside the domain (or beyond what any output needs) takes its permanent ghost value (N1/N2): 0 in the E/W
+// ghost columns of interior rows, else the initial equilibrium
+template <typename T>
+__device__ __forceinline__ T outside_value(const K2Extra<T>& e, bool row_in, bool col_in, int i) {
+    return (row_in && !col_in) ? T(0) : e.feq_in[i];
+}
+// the nine stores of interior cell (x, local row y), plain or non-temporal
+template <bool NT, typename T>
+__device__ __forceinline__ void store_cell(const KArgs<T>& a, const T (&f)[Q], int x, int y) {
+    T* base = a.dst + ((long)(y + GR) * a.pitch + a.xoff + x);
+#pragma unroll
+    for (int i = 0; i < Q; ++i) {
+        if (NT) __builtin_nontemporal_store(f[i], base + (long)i * a.plane); else base[(long)i * a.plane] = f[i];
+    }
+}
+template <typename T>
+__device__ __forceinline__ void store_cell(const KArgs<T>& a, const T (&f)[Q], int x, int y, bool nt) {   // (block-uniform nt)
+    if (nt) store_cell<true>(a, f, x, y); else store_cell<false>(a, f, x, y);
+}
+
+// The block-uniform prologue of a fused kernel whose outputs are the OW x OH cells at (X0, Y0) and whose first level reaches HW
+// rings beyond them.
+template <typename T>
+struct TileFrame {
+    int X0, Y0;          // first output column / local row
+    int y_end;           // rows >= y_end belong to another band / launch
+    bool near_solid;     // a cell of the outputs grown by HW rings may be solid
+    // LEAN: the outputs and their HW rings lie strictly inside the domain, the output tile is full, nothing is near a solid cell
+    // and the buffer is below 4 GiB — every cell of every level is a plain fluid cell: no boundary, ghost, solid or validity logic
+    bool lean;
+    // (lean path) one uniform base per buffer + a 32-bit byte offset per access: nine scalar offsets + one vector offset per cell
+    // (see buf_load). The source descriptor starts KB bytes early: every scalar offset stays >= 0.
+    unsigned pitchB, planeB, KB;
+    __amdgpu_buffer_rsrc_t rsrc, rdst;
+
+    __device__ __forceinline__ TileFrame(const KArgs<T>& a, const K2Extra<T>& e, int X0_, int Y0_, int y_end_, int OW, int OH, int HW)
+        : X0(X0_), Y0(Y0_), y_end(y_end_) {
+        near_solid = tile_near_solid(a, X0, Y0, OW, OH, HW);
+        const int yg0 = a.y_start + Y0;
+        lean = !near_solid && X0 >= HW + 1 && X0 + OW + HW <= a.nx - 1 && yg0 >= HW + 1 && yg0 + OH + HW <= a.ny_glob - 1 &&
+               Y0 + OH <= y_end && e.small;
+        pitchB = (unsigned)a.pitch * (unsigned)sizeof(T);
+        planeB = (unsigned)a.plane * (unsigned)sizeof(T);
+        KB = pitchB + (unsigned)sizeof(T);
+        rsrc = buf_desc(reinterpret_cast<const char*>(a.src) - KB);
+        rdst = buf_desc(a.dst);
+    }
+    // (lean path) scalar byte offsets of cell (x, local row y) for load / store, and the vector byte offset of (row, col) from it
+    __device__ __forceinline__ unsigned src_off(const KArgs<T>& a, int y, int x) const {
+        return (unsigned)(y + GR) * pitchB + (unsigned)(a.xoff + x) * (unsigned)sizeof(T) + KB;
+    }
+    __device__ __forceinline__ unsigned dst_off(const KArgs<T>& a, int y, int x) const {
+        return (unsigned)(y + GR) * pitchB + (unsigned)(a.xoff + x) * (unsigned)sizeof(T);
+    }
+    __device__ __forceinline__ unsigned at(int row, int col) const { return (unsigned)row * pitchB + (unsigned)col * (unsigned)sizeof(T); }
+    // (lean path) the nine pulls / stores of one cell
+    template <int AUX = 0>
+    __device__ __forceinline__ void load(T (&f)[Q], unsigned voff, unsigned soff) const {
+#pragma unroll
+        for (int i = 0; i < Q; ++i)
+            f[i] = buf_load<T, AUX>(rsrc, voff, soff + (unsigned)i * planeB - (unsigned)cy(i) * pitchB - (unsigned)(cx(i) * (int)sizeof(T)));
+    }
+    template <bool NT>
+    __device__ __forceinline__ void store(const T (&f)[Q], unsigned voff, unsigned soff) const {
+#pragma unroll
+        for (int i = 0; i < Q; ++i) buf_store<NT>(f[i], rdst, voff, soff + (unsigned)i * planeB);
+    }
+    __device__ __forceinline__ void store(const T (&f)[Q], unsigned voff, unsigned soff, bool nt) const {   // (block-uniform nt)
+        if (nt) store<true>(f, voff, soff); else store<false>(f, voff, soff);
+    }
+};
+
+// The frame of the LDS tile kernels: tile (bx, by) of TX x TY outputs, grid = tiles x bands. Workgroups are dealt round-robin
+// over the 8 XCDs (each with its own L2); with e.xcd the linear block id is remapped so that every XCD walks one contiguous run
+// of tiles: horizontally adjacent tiles, which share the cache lines at their common edge, then run on the same L2 at the same time.
+template <typename T>
+__device__ __forceinline__ TileFrame<T> tile_frame(const KArgs<T>& a, const K2Extra<T>& e, int TX, int TY, int HW) {
     int bx = blockIdx.x, by = blockIdx.y;
     if (e.xcd) {
         const int nb = gridDim.x * gridDim.y;
@@ -452,10 +551,25 @@ __global__ void __launch_bounds__(NTH) k_step2_tile(const KArgs<T> a, const K2Ex
         by = b / gridDim.x; bx = b - by * gridDim.x;
     }
     if (a.reverse) by = (int)gridDim.y - 1 - by;               // (the host never combines reverse with a second range)
-    const int X0 = bx * TX;
-    int y_end;                                                 // rows >= y_end belong to another band / launch
+    int y_end;
     const int Y0 = band_origin(a, by, TY, y_end);
-    const bool near_cyl = tile_near_solid(a, X0, Y0, TX, TY, 1);   // block-uniform: most tiles skip the mask math
+    return TileFrame<T>(a, e, bx * TX, Y0, y_end, TX, TY, HW);
+}
+
+// Two timesteps per launch: temporal blocking through LDS. A block owns a TX x TY tile of outputs at iteration
+// t+1. Phase 1 computes P_{t+1} on the (TX+2) x (TY+2) region around it from global P_t — the step kernel's
+// per-cell sequence, with cells outside the domain taking their permanent ghost constants (N1/N2) and solid cells
+// w_i — into LDS; after one barrier phase 2 pulls from LDS, applies the BCs of iteration t+1, collides and stores
+// P_{t+2}. P_{t+1} never touches HBM: traffic per lattice update drops from 144 B to ~(1 + (TX+2)(TY+2)/(TX TY))*36 B
+// (82 B at 64x8, less when the tile halo is still in L2 / Infinity Cache). Same arithmetic per cell => results
+// bit-identical to two k_step_site launches (tests). Any nx (partial tiles at the right edge); rows of neighbouring strips must be
+// present (at least) two deep. LDS: 9*(TY+2)*(TX+4)*sizeof(T) (47.9 KB at TY=8, fp64: three blocks per CU). No LEAN path.
+template <typename T, int TY, int NTH, int AR = AR_STRICT>
+__global__ void __launch_bounds__(NTH) k_step2_tile(const KArgs<T> a, const K2Extra<T> e) {
+    constexpr int TX = 64, RW = TX + 2, RH = TY + 2, LP = RW + 2;
+    __shared__ T lds[Q][RH][LP];
+    const TileFrame<T> fr = tile_frame(a, e, TX, TY, 1);
+    const int X0 = fr.X0, Y0 = fr.Y0, y_end = fr.y_end;
     bool bad = false;
     for (int r = threadIdx.x; r < RW * RH; r += NTH) {         // phase 1: iteration t on the region
         const int ry = r / RW, rx = r - ry * RW;
@@ -466,21 +580,12 @@ __global__ void __launch_bounds__(NTH) k_step2_tile(const KArgs<T> a, const K2Ex
         T f[Q];
         if (!(row_in && col_in)) {
 #pragma unroll
-            for (int i = 0; i < Q; ++i) f[i] = (row_in && !col_in) ? T(0) : e.feq_in[i];
+            for (int i = 0; i < Q; ++i) f[i] = outside_value(e, row_in, col_in, i);
         } else {
             const long c = (long)(y + GR) * a.pitch + a.xoff + x;
 #pragma unroll
             for (int i = 0; i < Q; ++i) f[i] = a.src[(long)i * a.plane + c - (long)cy(i) * a.pitch - cx(i)];
-            bool solid = false;
-            if (near_cyl) solid = solid_at(a, x, yg);   // block-uniform branch
-            T rho_bc, u_out;
-            if (!solid) apply_bcs(f, yg == 0, yg == a.ny_glob - 1, x == 0, x == a.nx - 1, a.u_row, yg, rho_bc, u_out);
-            bad |= any_unstable(f);
-            bgk_collide<T, AR>(f, a.tau_inv);
-            if (near_cyl) {                    // solid cells keep w_i (the collision result of such a cell is discarded)
-#pragma unroll
-                for (int i = 0; i < Q; ++i) f[i] = solid ? wgt<T>(i) : f[i];
-            }
+            cell_update<T, AR>(a, f, x, yg, fr.near_solid, true, bad);
         }
 #pragma unroll
         for (int i = 0; i < Q; ++i) lds[i][ry][rx] = f[i];
@@ -492,100 +597,54 @@ __global__ void __launch_bounds__(NTH) k_step2_tile(const KArgs<T> a, const K2Ex
         const int ly = o / TX, lx = o - ly * TX;
         const int x = X0 + lx, y = Y0 + ly;
         if (y >= y_end || x >= a.nx) continue;               // partial tiles at the right / top edge
-        const int yg = a.y_start + y;
         T f[Q];
 #pragma unroll
         for (int i = 0; i < Q; ++i) f[i] = lds[i][ly + 1 - cy(i)][lx + 1 - cx(i)];
-        const bool solid = near_cyl && solid_at(a, x, yg);
-        T rho_bc, u_out;
-        if (!solid) apply_bcs(f, yg == 0, yg == a.ny_glob - 1, x == 0, x == a.nx - 1, a.u_row, yg, rho_bc, u_out);
-        bad |= any_unstable(f);
-        if (solid) continue;
-        bgk_collide<T, AR>(f, a.tau_inv);
-        const long c = (long)(y + GR) * a.pitch + a.xoff + x;
-        store_pops(a.dst + c, a.plane, f, e.nt != 0);
+        if (cell_update_last<T, AR>(a, f, x, a.y_start + y, fr.near_solid, bad)) store_cell(a, f, x, y, e.nt != 0);
     }
     if (bad) atomicMin(a.unstable_t, *a.t_base + a.t + 1);
 }
 
-// Three iterations per launch. Same idea one level deeper; the LDS image is reused in place:
-//   phase 1  region 1 = tile + 2 rings: P_{t+1} from global P_t into LDS (9*(TY+4)*(TX+4)*sizeof(T): 78 KB at 64x12
-//            fp64, two blocks of 1024 threads per CU = all 32 wave slots; the lean path needs 48 VGPRs);
-//   phase 2  region 2 = tile + 1 ring: every thread first pulls its (<= 2) cells' nine values of P_{t+1} from LDS into
-//            registers, barrier, then computes P_{t+2} and writes it IN PLACE (no second LDS image);
-//   phase 3  the tile: pull P_{t+2} from LDS, BCs, collide, store P_{t+3}.
-// HBM traffic per update ~ (1 + (TX+4)(TY+4)/(TX TY)) * 24 B (58 B at 64x12); redundant collisions 1.21x. Bit-identical to
-// three single launches (tests). Rows of neighbouring strips must be present three deep beyond the rows written.
-template <typename T, int TY, int NTH, int AR = AR_STRICT>
-__global__ void __launch_bounds__(NTH, (2 * NTH / 256)) k_step3_tile(const KArgs<T> a, const K2Extra<T> e) {
-    constexpr int TX = 64, R1W = TX + 4, R1H = TY + 4, R2W = TX + 2, R2H = TY + 2, LP = R1W;
-    static_assert(R2W * R2H <= 2 * NTH, "two region-2 cells per thread at most");
+// Three / four iterations per launch (D = 3 / 4): the same idea one / two levels deeper, the LDS image reused in place:
+//   level 1      region 1 = tile + HW = D-1 rings: P_{t+1} from global P_t into LDS (9*(TY+2HW)*(TX+2HW)*sizeof(T): 78 KB at
+//                64x12 fp64 for D = 3, two blocks of 1024 threads per CU = all 32 wave slots, the lean path needs 48 VGPRs; 70.5 KB at 64x8 fp64, 35 KB fp32 for D = 4);
+//   levels 2..D-1  region L = region 1 shrunk by L-1 rings, in place: every thread first pulls its (<= 2) cells' nine values
+//                from LDS into registers, barrier, then computes the next state and writes it IN PLACE (no second LDS image);
+//   level D      the tile: pull from LDS, BCs, collide, store P_{t+D}.
+// HBM traffic per update ~ (1 + (TX+2HW)(TY+2HW)/(TX TY)) * 72/D B (fp64: 58 B at 64x12, D = 3); redundant collisions 1.21x
+// (64x12, D = 3) / 1.45x (64x8, D = 4) — D = 4 is worth it where the three-iteration kernel is close to the memory roof (fp32).
+// Bit-identical to D single launches (tests). Rows of neighbouring strips must be present D deep beyond the rows written, so
+// strips (six rows per exchange = 2 x 3) never use D = 4; the plan measurement decides elsewhere.
+template <typename T, int TY, int NTH, int D, int AR>
+__device__ __forceinline__ void step_tile(const KArgs<T>& a, const K2Extra<T>& e) {
+    constexpr int TX = 64, HW = D - 1, R1W = TX + 2 * HW, R1H = TY + 2 * HW, LP = R1W;
+    static_assert((R1W - 2) * (R1H - 2) <= 2 * NTH, "two cells per thread at most in the in-place levels");
     __shared__ T lds[Q][R1H][LP];
-    int bx = blockIdx.x, by = blockIdx.y;
-    if (e.xcd) {
-        const int nb = gridDim.x * gridDim.y;
-        int b = by * gridDim.x + bx;
-        if (nb % 8 == 0) b = (b % 8) * (nb / 8) + b / 8;
-        by = b / gridDim.x; bx = b - by * gridDim.x;
-    }
-    if (a.reverse) by = (int)gridDim.y - 1 - by;
-    const int X0 = bx * TX;
-    int y_end;
-    const int Y0 = band_origin(a, by, TY, y_end);
-    const bool near_cyl = tile_near_solid(a, X0, Y0, TX, TY, 2);
-    auto outside_value = [&](bool row_in, bool col_in, int i) -> T { return (row_in && !col_in) ? T(0) : e.feq_in[i]; };
-    // LEAN (block-uniform): the tile and its two rings lie strictly inside the domain, the tile is full, nothing is near
-    // the cylinder — every cell of all three regions is a plain fluid cell: no boundary, ghost, solid or validity logic.
-    const int yg0 = a.y_start + Y0;
-    const bool lean = !near_cyl && X0 >= 3 && X0 + TX + 2 <= a.nx - 1 && yg0 >= 3 && yg0 + TY + 2 <= a.ny_glob - 1 &&
-                      Y0 + TY <= y_end && e.small;
-    // (lean path) one uniform base per buffer + a 32-bit byte offset per access: a vector add per plane instead of a 64-bit one
-    const unsigned pitchB = (unsigned)a.pitch * (unsigned)sizeof(T), planeB = (unsigned)a.plane * (unsigned)sizeof(T);
-    const unsigned KB = pitchB + (unsigned)sizeof(T);   // the source descriptor starts KB bytes early: every scalar offset stays >= 0
-    const __amdgpu_buffer_rsrc_t rsrc = buf_desc(reinterpret_cast<const char*>(a.src) - KB), rdst = buf_desc(a.dst);
+    const TileFrame<T> fr = tile_frame(a, e, TX, TY, HW);
+    const int X0 = fr.X0, Y0 = fr.Y0, y_end = fr.y_end;
+    // The whole tile twice: LEAN (fr.lean) or general; a block takes one of the two (block-uniform)
     auto run = [&]<bool LEAN>() {
         bool bad = false;
 #pragma unroll
-        for (int r = threadIdx.x; r < R1W * R1H; r += NTH) {                 // phase 1: iteration t
+        for (int r = threadIdx.x; r < R1W * R1H; r += NTH) {                 // level 1 on region 1: iteration t
             const int ry = r / R1W, rx = r - ry * R1W;
-            const int x = X0 + rx - 2, y = Y0 + ry - 2;
-            const int yg = a.y_start + y;
             T f[Q];
-            bool inside = true;
-            if (!LEAN) {
+            if (LEAN) {
+                fr.load(f, fr.at(ry, rx), fr.src_off(a, Y0 - HW, X0 - HW));
+                bad |= any_unstable(f);
+                bgk_collide<T, AR>(f, a.tau_inv);
+            } else {
+                const int x = X0 + rx - HW, y = Y0 + ry - HW;
+                const int yg = a.y_start + y;
                 const bool row_in = (yg >= 0 && yg < a.ny_glob), col_in = (x >= 0 && x < a.nx);
-                inside = row_in && col_in && y <= y_end + 1;
-                if (!inside) {
+                if (!(row_in && col_in) || y > y_end + HW - 1) {
 #pragma unroll
-                    for (int i = 0; i < Q; ++i) f[i] = outside_value(row_in, col_in, i);
-                }
-            }
-            if (inside) {
-                if (LEAN) {
-                    const unsigned ub = (unsigned)(Y0 - 2 + GR) * pitchB + (unsigned)(a.xoff + X0 - 2) * (unsigned)sizeof(T) + KB;   // block-uniform
-                    const unsigned voff = (unsigned)ry * pitchB + (unsigned)rx * (unsigned)sizeof(T);
-#pragma unroll
-                    for (int i = 0; i < Q; ++i)
-                        f[i] = buf_load<T>(rsrc, voff, ub + (unsigned)i * planeB - (unsigned)cy(i) * pitchB - (unsigned)(cx(i) * (int)sizeof(T)));
+                    for (int i = 0; i < Q; ++i) f[i] = outside_value(e, row_in, col_in, i);
                 } else {
                     const long c = (long)(y + GR) * a.pitch + a.xoff + x;
 #pragma unroll
                     for (int i = 0; i < Q; ++i) f[i] = a.src[(long)i * a.plane + c - (long)cy(i) * a.pitch - cx(i)];
-                }
-                if (LEAN) {
-                    bad |= any_unstable(f);
-                    bgk_collide<T, AR>(f, a.tau_inv);
-                } else {
-                    bool solid = false;
-                    if (near_cyl) solid = solid_at(a, x, yg);   // block-uniform branch
-                    T rho_bc, u_out;
-                    if (!solid) apply_bcs(f, yg == 0, yg == a.ny_glob - 1, x == 0, x == a.nx - 1, a.u_row, yg, rho_bc, u_out);
-                    bad |= any_unstable(f);
-                    bgk_collide<T, AR>(f, a.tau_inv);
-                    if (near_cyl) {            // solid cells keep w_i (the collision result of such a cell is discarded)
-#pragma unroll
-                        for (int i = 0; i < Q; ++i) f[i] = solid ? wgt<T>(i) : f[i];
-                    }
+                    cell_update<T, AR>(a, f, x, yg, fr.near_solid, true, bad);
                 }
             }
 #pragma unroll
@@ -593,244 +652,72 @@ __global__ void __launch_bounds__(NTH, (2 * NTH / 256)) k_step3_tile(const KArgs
         }
         if (bad) atomicMin(a.unstable_t, *a.t_base + a.t);
         __syncthreads();
-        // phase 2: iteration t+1 on region 2, in place
-        T g[2][Q];
-        int cell[2];
+        auto in_place = [&]<int L>() {                                        // level L on region L, in place
+            constexpr int O = L - 1, RW = R1W - 2 * O, RH = R1H - 2 * O;
+            T g[2][Q];
+            int cell[2];
 #pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const int r = threadIdx.x + k * NTH;
-            cell[k] = (r < R2W * R2H) ? r : -1;
-            if (cell[k] >= 0) {
-                const int ry = r / R2W + 1, rx = r - (r / R2W) * R2W + 1;    // LDS coordinates of the cell
+            for (int k = 0; k < 2; ++k) {
+                const int r = (int)threadIdx.x + k * NTH;
+                cell[k] = (r < RW * RH) ? r : -1;
+                if (cell[k] >= 0) {
+                    const int ry = r / RW + O, rx = r - (r / RW) * RW + O;    // LDS coordinates of the cell
 #pragma unroll
-                for (int i = 0; i < Q; ++i) g[k][i] = lds[i][ry - cy(i)][rx - cx(i)];
+                    for (int i = 0; i < Q; ++i) g[k][i] = lds[i][ry - cy(i)][rx - cx(i)];
+                }
             }
-        }
-        __syncthreads();
-        bad = false;
+            __syncthreads();
+            bool badl = false;
 #pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            if (cell[k] < 0) continue;
-            const int r = cell[k];
-            const int ry = r / R2W + 1, rx = r - (r / R2W) * R2W + 1;
-            const int x = X0 + rx - 2, y = Y0 + ry - 2;
-            const int yg = a.y_start + y;
-            T f[Q];
-            bool inside = true;
-            if (!LEAN) {
+            for (int k = 0; k < 2; ++k) {
+                if (cell[k] < 0) continue;
+                const int r = cell[k];
+                const int ry = r / RW + O, rx = r - (r / RW) * RW + O;
+                const int x = X0 + rx - HW, y = Y0 + ry - HW;
+                const int yg = a.y_start + y;
                 const bool row_in = (yg >= 0 && yg < a.ny_glob), col_in = (x >= 0 && x < a.nx);
-                inside = row_in && col_in;
-                if (!inside) {
+                T f[Q];
+                if (!LEAN && !(row_in && col_in)) {
 #pragma unroll
-                    for (int i = 0; i < Q; ++i) f[i] = outside_value(row_in, col_in, i);
-                }
-            }
-            if (inside) {
-#pragma unroll
-                for (int i = 0; i < Q; ++i) f[i] = g[k][i];
-                if (LEAN) {
-                    bad |= any_unstable(f);
-                    bgk_collide<T, AR>(f, a.tau_inv);
+                    for (int i = 0; i < Q; ++i) f[i] = outside_value(e, row_in, col_in, i);
                 } else {
-                    bool solid = false;
-                    if (near_cyl) solid = solid_at(a, x, yg);   // block-uniform branch
-                    T rho_bc, u_out;
-                    if (!solid) apply_bcs(f, yg == 0, yg == a.ny_glob - 1, x == 0, x == a.nx - 1, a.u_row, yg, rho_bc, u_out);
-                    if (y <= y_end) bad |= any_unstable(f);
-                    bgk_collide<T, AR>(f, a.tau_inv);
-                    if (near_cyl) {            // solid cells keep w_i (the collision result of such a cell is discarded)
 #pragma unroll
-                        for (int i = 0; i < Q; ++i) f[i] = solid ? wgt<T>(i) : f[i];
-                    }
+                    for (int i = 0; i < Q; ++i) f[i] = g[k][i];
+                    if (LEAN) {
+                        badl |= any_unstable(f);
+                        bgk_collide<T, AR>(f, a.tau_inv);
+                    } else cell_update<T, AR>(a, f, x, yg, fr.near_solid, y <= y_end + HW - L, badl);
                 }
-            }
 #pragma unroll
-            for (int i = 0; i < Q; ++i) lds[i][ry][rx] = f[i];
-        }
-        if (bad) atomicMin(a.unstable_t, *a.t_base + a.t + 1);
-        __syncthreads();
+                for (int i = 0; i < Q; ++i) lds[i][ry][rx] = f[i];
+            }
+            if (badl) atomicMin(a.unstable_t, *a.t_base + a.t + L - 1);
+            __syncthreads();
+        };
+        [&]<int... Ls>(std::integer_sequence<int, Ls...>) { (in_place.template operator()<Ls + 2>(), ...); }(std::make_integer_sequence<int, D - 2>{});
         bad = false;
-        for (int o = threadIdx.x; o < TX * TY; o += NTH) {                    // phase 3: iteration t+2 on the tile
+        for (int o = threadIdx.x; o < TX * TY; o += NTH) {                    // level D on the tile: iteration t+D-1
             const int ly = o / TX, lx = o - ly * TX;
             const int x = X0 + lx, y = Y0 + ly;
             if (!LEAN && (y >= y_end || x >= a.nx)) continue;
-            const int yg = a.y_start + y;
             T f[Q];
 #pragma unroll
-            for (int i = 0; i < Q; ++i) f[i] = lds[i][ly + 2 - cy(i)][lx + 2 - cx(i)];
+            for (int i = 0; i < Q; ++i) f[i] = lds[i][ly + HW - cy(i)][lx + HW - cx(i)];
             if (LEAN) {
                 bad |= any_unstable(f);
-            } else {
-                const bool solid = near_cyl && solid_at(a, x, yg);
-                T rho_bc, u_out;
-                if (!solid) apply_bcs(f, yg == 0, yg == a.ny_glob - 1, x == 0, x == a.nx - 1, a.u_row, yg, rho_bc, u_out);
-                bad |= any_unstable(f);
-                if (solid) continue;
-            }
-            bgk_collide<T, AR>(f, a.tau_inv);
-            if (LEAN) {
-                const unsigned ub = (unsigned)(Y0 + GR) * pitchB + (unsigned)(a.xoff + X0) * (unsigned)sizeof(T);
-                const unsigned voff = (unsigned)ly * pitchB + (unsigned)lx * (unsigned)sizeof(T);
-                buf_store_pops(f, rdst, voff, ub, planeB, e.nt != 0);
-            } else {
-                const long c = (long)(y + GR) * a.pitch + a.xoff + x;
-                store_pops(a.dst + c, a.plane, f, e.nt != 0);
-            }
+                bgk_collide<T, AR>(f, a.tau_inv);
+                fr.store(f, fr.at(ly, lx), fr.dst_off(a, Y0, X0), e.nt != 0);
+            } else if (cell_update_last<T, AR>(a, f, x, a.y_start + y, fr.near_solid, bad)) store_cell(a, f, x, y, e.nt != 0);
         }
-        if (bad) atomicMin(a.unstable_t, *a.t_base + a.t + 2);
+        if (bad) atomicMin(a.unstable_t, *a.t_base + a.t + D - 1);
     };
-    if (lean) run.template operator()<true>();
+    if (fr.lean) run.template operator()<true>();
     else run.template operator()<false>();
 }
-
-// Four iterations per launch: k_step3_tile one level deeper (two in-place levels). Region 1 = tile + 3 rings from HBM
-// into LDS (9*(TY+6)*(TX+6)*sizeof(T): 70.5 KB at 64x8 fp64, 35 KB fp32), regions 2 and 3 in place, then the tile.
-// HBM traffic per update ~ (1 + (TX+6)(TY+6)/(TX TY)) * 18 B; redundant collisions 1.45x at 64x8 — worth it where the
-// three-iteration kernel is close to the memory roof (fp32). Needs four valid rows beyond the rows written, so strips
-// (six rows per exchange = 2 x 3) never use it; the plan measurement decides elsewhere. Bit-identical to four single launches (tests).
 template <typename T, int TY, int NTH, int AR = AR_STRICT>
-__global__ void __launch_bounds__(NTH, (2 * NTH / 256)) k_step4_tile(const KArgs<T> a, const K2Extra<T> e) {
-    constexpr int TX = 64, HW = 3, R1W = TX + 2 * HW, R1H = TY + 2 * HW, LP = R1W;
-    static_assert((R1W - 2) * (R1H - 2) <= 2 * NTH, "two cells per thread at most in the in-place levels");
-    __shared__ T lds[Q][R1H][LP];
-    int bx = blockIdx.x, by = blockIdx.y;
-    if (e.xcd) {
-        const int nb = gridDim.x * gridDim.y;
-        int b = by * gridDim.x + bx;
-        if (nb % 8 == 0) b = (b % 8) * (nb / 8) + b / 8;
-        by = b / gridDim.x; bx = b - by * gridDim.x;
-    }
-    if (a.reverse) by = (int)gridDim.y - 1 - by;
-    const int X0 = bx * TX;
-    int y_end;
-    const int Y0 = band_origin(a, by, TY, y_end);
-    const bool near_cyl = tile_near_solid(a, X0, Y0, TX, TY, HW);
-    auto outside_value = [&](bool row_in, bool col_in, int i) -> T { return (row_in && !col_in) ? T(0) : e.feq_in[i]; };
-    // LEAN (block-uniform): tile + three rings strictly inside the domain, full tile, nothing near the cylinder
-    const int yg0 = a.y_start + Y0;
-    const bool lean = !near_cyl && X0 >= HW + 1 && X0 + TX + HW <= a.nx - 1 && yg0 >= HW + 1 && yg0 + TY + HW <= a.ny_glob - 1 &&
-                      Y0 + TY <= y_end && e.small;
-    // one cell: BCs, stability, collision (solid cells keep w_i); `count` = the cell's instability is reported
-    // (lean path) buffer descriptors: nine scalar offsets + one vector offset per cell (see buf_load)
-    const unsigned pitchB = (unsigned)a.pitch * (unsigned)sizeof(T), planeB = (unsigned)a.plane * (unsigned)sizeof(T);
-    const unsigned KB = pitchB + (unsigned)sizeof(T);
-    const __amdgpu_buffer_rsrc_t rsrc = buf_desc(reinterpret_cast<const char*>(a.src) - KB), rdst = buf_desc(a.dst);
-    auto update = [&](T (&f)[Q], int x, int yg, bool count, bool& bad) {
-        if (lean) {                                 // block-uniform
-            bad |= any_unstable(f);
-            bgk_collide<T, AR>(f, a.tau_inv);
-            return;
-        }
-        bool solid = false;
-        if (near_cyl) solid = solid_at(a, x, yg);   // block-uniform branch
-        T rho_bc, u_out;
-        if (!solid) apply_bcs(f, yg == 0, yg == a.ny_glob - 1, x == 0, x == a.nx - 1, a.u_row, yg, rho_bc, u_out);
-        if (count) bad |= any_unstable(f);
-        bgk_collide<T, AR>(f, a.tau_inv);
-        if (near_cyl) {
-#pragma unroll
-            for (int i = 0; i < Q; ++i) f[i] = solid ? wgt<T>(i) : f[i];
-        }
-    };
-    bool bad = false;
-#pragma unroll
-    for (int r = threadIdx.x; r < R1W * R1H; r += NTH) {                 // level 1 on region 1: iteration t
-        const int ry = r / R1W, rx = r - ry * R1W;
-        const int x = X0 + rx - HW, y = Y0 + ry - HW;
-        const int yg = a.y_start + y;
-        const bool row_in = (yg >= 0 && yg < a.ny_glob), col_in = (x >= 0 && x < a.nx);
-        T f[Q];
-        if (lean) {                                                       // block-uniform
-            const unsigned ub = (unsigned)(Y0 - HW + GR) * pitchB + (unsigned)(a.xoff + X0 - HW) * (unsigned)sizeof(T) + KB;
-            const unsigned voff = (unsigned)ry * pitchB + (unsigned)rx * (unsigned)sizeof(T);
-#pragma unroll
-            for (int i = 0; i < Q; ++i)
-                f[i] = buf_load<T>(rsrc, voff, ub + (unsigned)i * planeB - (unsigned)cy(i) * pitchB - (unsigned)(cx(i) * (int)sizeof(T)));
-            update(f, x, yg, true, bad);
-        } else if (!(row_in && col_in) || y > y_end + HW - 1) {
-#pragma unroll
-            for (int i = 0; i < Q; ++i) f[i] = outside_value(row_in, col_in, i);
-        } else {
-            const long c = (long)(y + GR) * a.pitch + a.xoff + x;
-#pragma unroll
-            for (int i = 0; i < Q; ++i) f[i] = a.src[(long)i * a.plane + c - (long)cy(i) * a.pitch - cx(i)];
-            update(f, x, yg, true, bad);
-        }
-#pragma unroll
-        for (int i = 0; i < Q; ++i) lds[i][ry][rx] = f[i];
-    }
-    if (bad) atomicMin(a.unstable_t, *a.t_base + a.t);
-    __syncthreads();
-    // levels 2 and 3 on regions 2 and 3, in place: pull into registers, barrier, compute and overwrite, barrier
-    auto in_place = [&]<int L>() {
-        constexpr int O = L - 1, RW = R1W - 2 * O, RH = R1H - 2 * O;      // region L = region 1 shrunk by L-1 rings
-        T g[2][Q];
-        int cell[2];
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const int r = (int)threadIdx.x + k * NTH;
-            cell[k] = (r < RW * RH) ? r : -1;
-            if (cell[k] >= 0) {
-                const int ry = r / RW + O, rx = r - (r / RW) * RW + O;    // LDS coordinates of the cell
-#pragma unroll
-                for (int i = 0; i < Q; ++i) g[k][i] = lds[i][ry - cy(i)][rx - cx(i)];
-            }
-        }
-        __syncthreads();
-        bool badl = false;
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            if (cell[k] < 0) continue;
-            const int r = cell[k];
-            const int ry = r / RW + O, rx = r - (r / RW) * RW + O;
-            const int x = X0 + rx - HW, y = Y0 + ry - HW;
-            const int yg = a.y_start + y;
-            const bool row_in = (yg >= 0 && yg < a.ny_glob), col_in = (x >= 0 && x < a.nx);
-            T f[Q];
-            if (!lean && !(row_in && col_in)) {
-#pragma unroll
-                for (int i = 0; i < Q; ++i) f[i] = outside_value(row_in, col_in, i);
-            } else {
-#pragma unroll
-                for (int i = 0; i < Q; ++i) f[i] = g[k][i];
-                update(f, x, yg, y <= y_end + HW - L, badl);
-            }
-#pragma unroll
-            for (int i = 0; i < Q; ++i) lds[i][ry][rx] = f[i];
-        }
-        if (badl) atomicMin(a.unstable_t, *a.t_base + a.t + L - 1);
-        __syncthreads();
-    };
-    in_place.template operator()<2>();
-    in_place.template operator()<3>();
-    bad = false;
-    for (int o = threadIdx.x; o < TX * TY; o += NTH) {                    // level 4 on the tile: iteration t+3
-        const int ly = o / TX, lx = o - ly * TX;
-        const int x = X0 + lx, y = Y0 + ly;
-        if (y >= y_end || x >= a.nx) continue;
-        const int yg = a.y_start + y;
-        T f[Q];
-#pragma unroll
-        for (int i = 0; i < Q; ++i) f[i] = lds[i][ly + HW - cy(i)][lx + HW - cx(i)];
-        if (lean) {                                                       // block-uniform
-            bad |= any_unstable(f);
-            bgk_collide<T, AR>(f, a.tau_inv);
-            const unsigned ub = (unsigned)(Y0 + GR) * pitchB + (unsigned)(a.xoff + X0) * (unsigned)sizeof(T);
-            const unsigned voff = (unsigned)ly * pitchB + (unsigned)lx * (unsigned)sizeof(T);
-            buf_store_pops(f, rdst, voff, ub, planeB, e.nt != 0);
-            continue;
-        }
-        const bool solid = near_cyl && solid_at(a, x, yg);
-        T rho_bc, u_out;
-        if (!solid) apply_bcs(f, yg == 0, yg == a.ny_glob - 1, x == 0, x == a.nx - 1, a.u_row, yg, rho_bc, u_out);
-        bad |= any_unstable(f);
-        if (solid) continue;
-        bgk_collide<T, AR>(f, a.tau_inv);
-        const long c = (long)(y + GR) * a.pitch + a.xoff + x;
-        store_pops(a.dst + c, a.plane, f, e.nt != 0);
-    }
-    if (bad) atomicMin(a.unstable_t, *a.t_base + a.t + 3);
-}
+__global__ void __launch_bounds__(NTH, (2 * NTH / 256)) k_step3_tile(const KArgs<T> a, const K2Extra<T> e) { step_tile<T, TY, NTH, 3, AR>(a, e); }
+template <typename T, int TY, int NTH, int AR = AR_STRICT>
+__global__ void __launch_bounds__(NTH, (2 * NTH / 256)) k_step4_tile(const KArgs<T> a, const K2Extra<T> e) { step_tile<T, TY, NTH, 4, AR>(a, e); }
 
 // In-kernel phase record (tools/colbench -DLBM_COL_PROF only; never in the library): lane 0 of every wave writes the 100 MHz
 // real-time counter at the marks below, plus HW_ID / XCC_ID, so that the host can lay the blocks of one CU side by side (profiles/r04).
@@ -898,41 +785,10 @@ __global__ void __launch_bounds__(TX * TY, (deep_waves_per_simd<T, TX, TY, D>())
             rx = c < HALO ? O + c : HW + TX + (c - HALO);
         }
     };
-    int bx = blockIdx.x, by = blockIdx.y;
-    if (e.xcd) {
-        const int nb = gridDim.x * gridDim.y;
-        int b = by * gridDim.x + bx;
-        if (nb % 8 == 0) b = (b % 8) * (nb / 8) + b / 8;
-        by = b / gridDim.x; bx = b - by * gridDim.x;
-    }
-    if (a.reverse) by = (int)gridDim.y - 1 - by;
-    const int X0 = bx * TX;
-    int y_end;
-    const int Y0 = band_origin(a, by, TY, y_end);
-    const bool near_cyl = tile_near_solid(a, X0, Y0, TX, TY, HW);
-    auto outside_value = [&](bool row_in, bool col_in, int i) -> T { return (row_in && !col_in) ? T(0) : e.feq_in[i]; };
-    const int yg0 = a.y_start + Y0;
-    const bool lean = !near_cyl && X0 >= HW + 1 && X0 + TX + HW <= a.nx - 1 && yg0 >= HW + 1 && yg0 + TY + HW <= a.ny_glob - 1 &&
-                      Y0 + TY <= y_end && e.small;
-    // (lean path) buffer descriptors: nine scalar offsets + one vector offset per cell (see buf_load)
-    const unsigned pitchB = (unsigned)a.pitch * (unsigned)sizeof(T), planeB = (unsigned)a.plane * (unsigned)sizeof(T);
-    const unsigned KB = pitchB + (unsigned)sizeof(T);
-    const __amdgpu_buffer_rsrc_t rsrc = buf_desc(reinterpret_cast<const char*>(a.src) - KB), rdst = buf_desc(a.dst);
-    // one general cell: BCs, stability, collision (solid cells keep w_i); `count` = the cell's instability is reported
-    auto update = [&](T (&f)[Q], int x, int yg, bool count, bool& bad) {
-        bool solid = false;
-        if (near_cyl) solid = solid_at(a, x, yg);   // block-uniform branch
-        T rho_bc, u_out;
-        if (!solid) apply_bcs(f, yg == 0, yg == a.ny_glob - 1, x == 0, x == a.nx - 1, a.u_row, yg, rho_bc, u_out);
-        if (count) bad |= any_unstable(f);
-        bgk_collide<T, AR>(f, a.tau_inv);
-        if (near_cyl) {
-#pragma unroll
-            for (int i = 0; i < Q; ++i) f[i] = solid ? wgt<T>(i) : f[i];
-        }
-    };
-    // The whole tile twice: LEAN = every cell of every level is a plain fluid cell (no boundary, ghost, solid or validity
-    // logic, buffer addressing); a block takes one of the two (block-uniform), so neither pays for merging with the other.
+    const TileFrame<T> fr = tile_frame(a, e, TX, TY, HW);
+    const int X0 = fr.X0, Y0 = fr.Y0, y_end = fr.y_end;
+    // The whole tile twice: LEAN (fr.lean) or general; a block takes one of the two (block-uniform), so neither pays for merging
+    // with the other.
     auto run = [&]<bool LEAN>() {
         bool bad = false;
         [[maybe_unused]] const int pb = (int)(blockIdx.y * gridDim.x + blockIdx.x), pw = (int)threadIdx.x >> 6;
@@ -944,11 +800,7 @@ __global__ void __launch_bounds__(TX * TY, (deep_waves_per_simd<T, TX, TY, D>())
             cell_xy.template operator()<0>(r, ry, rx);
             T f[Q];
             if (LEAN) {
-                const unsigned ub = (unsigned)(Y0 - HW + GR) * pitchB + (unsigned)(a.xoff + X0 - HW) * (unsigned)sizeof(T) + KB;
-                const unsigned voff = (unsigned)ry * pitchB + (unsigned)rx * (unsigned)sizeof(T);
-#pragma unroll
-                for (int i = 0; i < Q; ++i)
-                    f[i] = buf_load<T>(rsrc, voff, ub + (unsigned)i * planeB - (unsigned)cy(i) * pitchB - (unsigned)(cx(i) * (int)sizeof(T)));
+                fr.load(f, fr.at(ry, rx), fr.src_off(a, Y0 - HW, X0 - HW));
                 bad |= any_unstable(f);
                 bgk_collide<T, AR>(f, a.tau_inv);
             } else {
@@ -957,12 +809,12 @@ __global__ void __launch_bounds__(TX * TY, (deep_waves_per_simd<T, TX, TY, D>())
                 const bool row_in = (yg >= 0 && yg < a.ny_glob), col_in = (x >= 0 && x < a.nx);
                 if (!(row_in && col_in) || y > y_end + HW - 1) {
 #pragma unroll
-                    for (int i = 0; i < Q; ++i) f[i] = outside_value(row_in, col_in, i);
+                    for (int i = 0; i < Q; ++i) f[i] = outside_value(e, row_in, col_in, i);
                 } else {
                     const long c = (long)(y + GR) * a.pitch + a.xoff + x;
 #pragma unroll
                     for (int i = 0; i < Q; ++i) f[i] = a.src[(long)i * a.plane + c - (long)cy(i) * a.pitch - cx(i)];
-                    update(f, x, yg, true, bad);
+                    cell_update<T, AR>(a, f, x, yg, fr.near_solid, true, bad);
                 }
             }
 #pragma unroll
@@ -1003,8 +855,8 @@ __global__ void __launch_bounds__(TX * TY, (deep_waves_per_simd<T, TX, TY, D>())
                     const bool row_in = (yg >= 0 && yg < a.ny_glob), col_in = (x >= 0 && x < a.nx);
                     if (!(row_in && col_in)) {
 #pragma unroll
-                        for (int i = 0; i < Q; ++i) g[k][i] = outside_value(row_in, col_in, i);
-                    } else update(g[k], x, yg, y <= y_end + HW - L, badl);
+                        for (int i = 0; i < Q; ++i) g[k][i] = outside_value(e, row_in, col_in, i);
+                    } else cell_update<T, AR>(a, g[k], x, yg, fr.near_solid, y <= y_end + HW - L, badl);
                 }
 #pragma unroll
                 for (int i = 0; i < Q; ++i) lds[i][ry][rx] = g[k][i];
@@ -1020,27 +872,14 @@ __global__ void __launch_bounds__(TX * TY, (deep_waves_per_simd<T, TX, TY, D>())
             const int ly = o / TX, lx = o - ly * TX;
             const int x = X0 + lx, y = Y0 + ly;
             if (LEAN || (y < y_end && x < a.nx)) {
-                const int yg = a.y_start + y;
                 T f[Q];
 #pragma unroll
                 for (int i = 0; i < Q; ++i) f[i] = lds[i][ly + HW - cy(i)][lx + HW - cx(i)];
                 if (LEAN) {
                     bad |= any_unstable(f);
                     bgk_collide<T, AR>(f, a.tau_inv);
-                    const unsigned ub = (unsigned)(Y0 + GR) * pitchB + (unsigned)(a.xoff + X0) * (unsigned)sizeof(T);
-                    const unsigned voff = (unsigned)ly * pitchB + (unsigned)lx * (unsigned)sizeof(T);
-                    buf_store_pops(f, rdst, voff, ub, planeB, e.nt != 0);
-                } else {
-                    const bool solid = near_cyl && solid_at(a, x, yg);
-                    T rho_bc, u_out;
-                    if (!solid) apply_bcs(f, yg == 0, yg == a.ny_glob - 1, x == 0, x == a.nx - 1, a.u_row, yg, rho_bc, u_out);
-                    bad |= any_unstable(f);
-                    if (!solid) {
-                        bgk_collide<T, AR>(f, a.tau_inv);
-                        const long c = (long)(y + GR) * a.pitch + a.xoff + x;
-                        store_pops(a.dst + c, a.plane, f, e.nt != 0);
-                    }
-                }
+                    fr.store(f, fr.at(ly, lx), fr.dst_off(a, Y0, X0), e.nt != 0);
+                } else if (cell_update_last<T, AR>(a, f, x, a.y_start + y, fr.near_solid, bad)) store_cell(a, f, x, y, e.nt != 0);
             }
         }
         if (bad) atomicMin(a.unstable_t, *a.t_base + a.t + D - 1);
@@ -1050,7 +889,7 @@ __global__ void __launch_bounds__(TX * TY, (deep_waves_per_simd<T, TX, TY, D>())
         LBM_PROF(pb, NTH / 64, pw, D + 1);
 #endif
     };
-    if (lean) run.template operator()<true>();
+    if (fr.lean) run.template operator()<true>();
     else run.template operator()<false>();
 }
 
