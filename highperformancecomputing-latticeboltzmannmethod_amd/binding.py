@@ -58,6 +58,7 @@ def lib():
         L.lbm_get_solid.argtypes = [vp, C.POINTER(C.c_ubyte)]
         L.lbm_set_solid_mask.argtypes = [vp, C.POINTER(C.c_ubyte), C.c_int, C.c_int]
         L.lbm_set_inlet_profile.argtypes = [vp, dp, C.c_int]
+        L.lbm_set_smagorinsky.argtypes = [vp, C.c_double]
         ip = C.POINTER(C.c_int)
         L.lbm_debug_geometry.argtypes = [C.POINTER(C.c_ubyte), C.c_int, C.c_int, C.c_int, C.c_int, ip, C.POINTER(C.c_ulonglong), C.c_long,
                                          ip, C.c_long, ip, C.c_int, ip]
@@ -182,11 +183,12 @@ class Context:
     """One strip of the lattice on one GPU (struct lbm_ctx). solid: optional bool / uint8 (ny, nx) array of the WHOLE domain, row
     y = 0 first, nonzero = solid (lbm_set_solid_mask): the obstacle geometry in place of the cylinder_* disc. inlet_profile: optional
     float64 [ny] of absolute inlet x-velocities of the WHOLE domain, row y = 0 first (lbm_set_inlet_profile), in place of the
-    uniform inlet_velocity (see parabolic_profile)."""
+    uniform inlet_velocity (see parabolic_profile). smagorinsky: optional constant Cs of a Smagorinsky LES collision
+    (lbm_set_smagorinsky) in place of plain BGK; 0 / None: BGK."""
 
     def __init__(self, nx, ny, tau=0.6, inlet_velocity=0.01333, cylinder_x=0.2, cylinder_y=0.5,
                  cylinder_radius=0.05, y_start=0, local_ny=0, precision="f64", device=0, force_log_capacity=0,
-                 options=None, solid=None, inlet_profile=None):
+                 options=None, solid=None, inlet_profile=None, smagorinsky=None):
         self.L = lib()
         self.params = Params(tau, inlet_velocity, nx, ny, cylinder_x, cylinder_y, cylinder_radius, y_start,
                              local_ny, {"f64": 0, "f32": 1}[precision], force_log_capacity)
@@ -202,6 +204,8 @@ class Context:
             self.set_solid_mask(solid)
         if inlet_profile is not None:
             self.set_inlet_profile(inlet_profile)
+        if smagorinsky is not None:
+            self.set_smagorinsky(smagorinsky)
 
     def _chk(self, rc):
         if rc < 0:
@@ -239,6 +243,10 @@ class Context:
         if a.ndim != 1:
             raise ValueError(f"inlet profile must be one-dimensional, not of shape {a.shape}")
         self._chk(self.L.lbm_set_inlet_profile(self.h, _dp(a), a.size))
+
+    def set_smagorinsky(self, cs):
+        """lbm_set_smagorinsky: the Smagorinsky constant Cs in [0, 1] (0: plain BGK); before initialise()."""
+        self._chk(self.L.lbm_set_smagorinsky(self.h, float(cs)))
 
     def initialise(self):
         n = C.c_int()
@@ -366,15 +374,17 @@ class Context:
 class Group:
     """n strips of one lattice driven in lockstep by this process (lbm_group_*): one Context per strip, bottom to top.
     transport: "peer" (device copies / hipMemcpyPeerAsync) or "rccl" (ncclCommInitAll; distinct devices).
-    solid: optional global (ny, nx) obstacle mask, inlet_profile: optional global [ny] inlet velocities; both given to every member."""
+    solid: optional global (ny, nx) obstacle mask, inlet_profile: optional global [ny] inlet velocities, smagorinsky: optional LES
+    constant Cs; all given to every member."""
 
-    def __init__(self, nx, ny, bounds, devices=None, transport="peer", options=None, solid=None, inlet_profile=None, **kw):
+    def __init__(self, nx, ny, bounds, devices=None, transport="peer", options=None, solid=None, inlet_profile=None, smagorinsky=None, **kw):
         from .strips import partition_rows
         if isinstance(bounds, int):
             bounds = partition_rows(ny, bounds)
         devices = devices or [0] * len(bounds)
         self.nx, self.ny = nx, ny
-        self.ctxs = [Context(nx, ny, y_start=y0, local_ny=n, device=d, options=options, solid=solid, inlet_profile=inlet_profile, **kw)
+        self.ctxs = [Context(nx, ny, y_start=y0, local_ny=n, device=d, options=options, solid=solid, inlet_profile=inlet_profile,
+                             smagorinsky=smagorinsky, **kw)
                      for (y0, n), d in zip(bounds, devices)]
         self.L = lib()
         self._arr = (C.c_void_p * len(self.ctxs))(*[c.h for c in self.ctxs])

@@ -1,6 +1,7 @@
 // csrc/lbm_col.hip — the translation unit(s) of k_stepc_col (lbm_kernel_col.hpp): its 26 instantiations (five / six iterations x
 // store policy + seven iterations, x arithmetic x element type: ten per element type and object file, plus the tall fp32 ones, three per
-// arithmetic mode and object file) and the launchers lbm_hip.hip calls (lbm_col_api.hpp). Four objects from this one source (build.py).
+// arithmetic mode and object file) and the launchers lbm_hip.hip calls (lbm_col_api.hpp). Four objects from this one source (build.py),
+// and two more with -DLBM_COL_LES=1: the ten Smagorinsky instantiations per element type (no tall ones).
 #include "lbm_kernel_col.hpp"
 #include "lbm_col_api.hpp"
 
@@ -13,20 +14,29 @@ namespace lbmk {
         hipLaunchKernelGGL((k_stepc_col<T_, R_, NW_, D_, NT_, AR_>), gridc, blockc, 0, s, a, e); } while (0)
 
 #if defined(LBM_COL_T)       // the 64 x 32 (fp64 strict: 64 x 24 on twelve waves) regions of one element type
+// -DLBM_COL_LES=1: the same launcher and regions with the Smagorinsky arithmetic values (launch_col_les, two more objects)
+#if defined(LBM_COL_LES) && LBM_COL_LES
+#define LBM_COL_FN launch_col_les
+constexpr int ARS = AR_STRICT_LES, ARC = AR_CONTRACTED_LES;
+#else
+#define LBM_COL_FN launch_col
+constexpr int ARS = AR_STRICT, ARC = AR_CONTRACTED;
+#endif
 template <typename T>
-void launch_col(const KArgs<T>& a, const K2Extra<T>& e, int depth, bool nt, bool contracted, hipStream_t s) {
+void LBM_COL_FN(const KArgs<T>& a, const K2Extra<T>& e, int depth, bool nt, bool contracted, hipStream_t s) {
 #define LBM_KD(D_) do { \
-        if (contracted) { if (nt) LBM_KC(T, D_, RC, WC, true, AR_CONTRACTED); else LBM_KC(T, D_, RC, WC, false, AR_CONTRACTED); } \
-        else { if (nt) LBM_KC(T, D_, RS, WS, true, AR_STRICT); else LBM_KC(T, D_, RS, WS, false, AR_STRICT); } } while (0)
+        if (contracted) { if (nt) LBM_KC(T, D_, RC, WC, true, ARC); else LBM_KC(T, D_, RC, WC, false, ARC); } \
+        else { if (nt) LBM_KC(T, D_, RS, WS, true, ARS); else LBM_KC(T, D_, RS, WS, false, ARS); } } while (0)
     constexpr int RC = col_rows_per_thread((int)sizeof(T), false), RS = col_rows_per_thread((int)sizeof(T), true);
     constexpr int WC = col_waves((int)sizeof(T), false), WS = col_waves((int)sizeof(T), true);
     // (seven iterations: plain stores only — the depth of a call's remainders and of the "deep" 9 plans, whose candidates all store plainly)
     if (depth == 5) LBM_KD(5);
-    else if (depth == 7) { if (contracted) LBM_KC(T, 7, RC, WC, false, AR_CONTRACTED); else LBM_KC(T, 7, RS, WS, false, AR_STRICT); }
+    else if (depth == 7) { if (contracted) LBM_KC(T, 7, RC, WC, false, ARC); else LBM_KC(T, 7, RS, WS, false, ARS); }
     else LBM_KD(6);
 #undef LBM_KD
 }
-template void launch_col<LBM_COL_T>(const KArgs<LBM_COL_T>&, const K2Extra<LBM_COL_T>&, int, bool, bool, hipStream_t);
+template void LBM_COL_FN<LBM_COL_T>(const KArgs<LBM_COL_T>&, const K2Extra<LBM_COL_T>&, int, bool, bool, hipStream_t);
+#undef LBM_COL_FN
 #elif defined(LBM_COL_TALL)  // the tall fp32 regions (64 x 48) of one arithmetic mode: contracted 12 waves x 4 rows (1), strict 8 x 6 (0)
 #if LBM_COL_TALL
 void launch_col_tall_contracted(const KArgs<float>& a, const K2Extra<float>& e, int depth, hipStream_t s) {
@@ -38,7 +48,7 @@ void launch_col_tall_strict(const KArgs<float>& a, const K2Extra<float>& e, int 
     if (depth == 6) LBM_KC(float, 6, R, W, false, AR); else if (depth == 8) LBM_KC(float, 8, R, W, false, AR); else LBM_KC(float, 7, R, W, false, AR);
 }
 #else
-#error "compile with -DLBM_COL_T=double, -DLBM_COL_T=float, -DLBM_COL_TALL=1 or -DLBM_COL_TALL=0"
+#error "compile with -DLBM_COL_T=double, -DLBM_COL_T=float (either with or without -DLBM_COL_LES=1), -DLBM_COL_TALL=1 or -DLBM_COL_TALL=0"
 #endif
 #undef LBM_KC
 

@@ -35,6 +35,9 @@ constexpr int col_tile_h(int depth, int esize, bool strict, bool tall) {
 // 64 x 32 regions (one object file per element type: lbm_col.hip -DLBM_COL_T=double / float)
 template <typename T>
 void launch_col(const KArgs<T>& a, const K2Extra<T>& e, int depth, bool nt, bool contracted, hipStream_t s);
+// ... the same with the Smagorinsky arithmetic (AR_STRICT_LES / AR_CONTRACTED_LES; lbm_col.hip -DLBM_COL_T=... -DLBM_COL_LES=1)
+template <typename T>
+void launch_col_les(const KArgs<T>& a, const K2Extra<T>& e, int depth, bool nt, bool contracted, hipStream_t s);
 // ... and on the tall fp32 regions, depth 6, 7 or 8, plain stores only (non-temporal ones cost 14 % there); one object file per
 // arithmetic mode (lbm_col.hip -DLBM_COL_TALL=1 contracted / 0 strict: eight unrolled rows x up to eight levels compile slowly)
 void launch_col_tall_contracted(const KArgs<float>& a, const K2Extra<float>& e, int depth, hipStream_t s);

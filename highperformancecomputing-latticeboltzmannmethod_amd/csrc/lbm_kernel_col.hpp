@@ -121,7 +121,7 @@ __global__ void __launch_bounds__(NW * 64, (col_waves_per_simd<NW>())) k_stepc_c
 #pragma unroll
             for (int j = 0; j < R; ++j) {
                 bad |= any_unstable(g[j]);
-                bgk_collide<T, AR>(g[j], a.tau_inv);
+                collide<T, AR>(g[j], a);
             }
         } else {
 #pragma unroll
@@ -167,7 +167,7 @@ __global__ void __launch_bounds__(NW * 64, (col_waves_per_simd<NW>())) k_stepc_c
                 bool store = L == D && lane >= HW && lane < 64 - HW && ry >= HW && ry < H - HW;
                 if (LEAN) {
                     badl |= unstable_if(f, valid);
-                    bgk_collide<T, AR>(f, a.tau_inv);
+                    collide<T, AR>(f, a);
                 } else {
                     const bool row_in = (yg >= 0 && yg < a.ny_glob);
                     if (!(row_in && col_in)) {

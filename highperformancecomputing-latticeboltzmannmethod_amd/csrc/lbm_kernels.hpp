@@ -108,6 +108,9 @@ struct KArgs {
     int y_lo2, y_cnt2; // optional second range [y_lo2, y_lo2 + y_cnt2) of the same launch (both edge bands of a strip
                        // in one grid); y_cnt2 == 0: none
     int reverse;       // 1: blockIdx.y walks the rows top-down (alternated per launch by the host, see row_of_block)
+    // Smagorinsky LES (lbm_set_smagorinsky): tau, tau*tau and C = 18*sqrt(2)*Cs^2, computed on the host in double. Read only by the
+    // LES instantiations (AR_STRICT_LES / AR_CONTRACTED_LES); appended so that the fields BGK kernels read keep their offsets.
+    T les_tau, les_tau2, les_c;
 };
 
 // Row handled by blockIdx.y. Blocks are dispatched roughly in index order; walking the rows in the opposite
@@ -193,7 +196,13 @@ __device__ __forceinline__ void bcs_at(const A& a, T (&f)[Q], int x, int yg) {
 //   AR_CONTRACTED the same formulas as fused multiply-adds with ONE reciprocal of rho (two Newton steps on v_rcp): what the
 //                 reference's own build flags permit its compiler to do (CMakeLists.txt:21-22: -ffast-math -mfma). 70
 //                 instead of 150 floating-point instructions per cell; rho/u stay within 1e-10 of the reference (tests).
-enum Arith { AR_STRICT = 0, AR_CONTRACTED = 1 };
+//   AR_STRICT_LES / AR_CONTRACTED_LES  the same two arithmetic modes with the Smagorinsky relaxation time of each cell (les_tau_inv)
+//                 in place of the global 1/tau. Separate instantiations, never a runtime branch: a kernel's VGPR count is the maximum
+//                 over its paths, and the BGK kernels have no headroom.
+enum Arith { AR_STRICT = 0, AR_CONTRACTED = 1, AR_STRICT_LES = 2, AR_CONTRACTED_LES = 3 };
+constexpr bool ar_contracted(int ar) { return (ar & 1) != 0; }
+constexpr bool ar_les(int ar) { return (ar & 2) != 0; }
+constexpr int ar_of(bool contracted, bool les) { return (contracted ? 1 : 0) | (les ? 2 : 0); }
 
 __device__ __forceinline__ double fma_t(double a, double b, double c) { return __builtin_fma(a, b, c); }
 __device__ __forceinline__ float fma_t(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
@@ -207,6 +216,18 @@ __device__ __forceinline__ float recip_t(float d) {        // v_rcp_f32 (1 ulp) 
     float r = __builtin_amdgcn_rcpf(d);
     return fma_t(fma_t(-d, r, 1.0f), r, r);
 }
+__device__ __forceinline__ double sqrt_t(double v) { return __builtin_sqrt(v); }   // correctly rounded (rsq + refinement + scaling)
+__device__ __forceinline__ float sqrt_t(float v) { return __builtin_sqrtf(v); }
+// contracted arithmetic (LES): v_rsq_f64 and one Goldschmidt step, to about an ulp, for ~5 instead of ~17 instructions and fewer live
+// registers (the fp64 register kernel has four spare VGPRs). Values below 1e-300, zero included, are raised to it first (rsq(0) is
+// inf): a square root of 1e-150 instead of 0 beside tau^2 >= 0.25 changes nothing. fp32: v_sqrt_f32 (1 ulp).
+__device__ __forceinline__ double sqrt_c(double v) {
+    v = __builtin_fmax(v, 1e-300);
+    const double y = __builtin_amdgcn_rsq(v);
+    const double s = v * y;
+    return fma_t(s, fma_t(-s, 0.5 * y, 0.5), s);
+}
+__device__ __forceinline__ float sqrt_c(float v) { return __builtin_amdgcn_sqrtf(v); }
 
 // Buffer-descriptor access for the block-uniform "lean" paths: address = descriptor base + SGPR offset + ONE 32-bit VGPR
 // offset, so the nine populations of a cell cost nine scalar adds and no vector address arithmetic at all (a global_load
@@ -265,11 +286,29 @@ __global__ void k_debug_strict_div2(const double* a1, const double* a2, const do
     r1[k] = a1[k] / b[k]; r2[k] = a2[k] / b[k];
 }   // (fp32 has no oracle to be bit-equal to: plain divisions)
 
-// collision_step for one cell, LBMSolver.h:101-123 (moments i = 0..8 ascending from 0, N7).
+// Smagorinsky relaxation rate of one cell, 1/tau_eff with tau_eff = (tau + sqrt(tau^2 + C*|Pi_neq|/rho))/2: the closed form of
+// tau = tau0 + 3 Cs^2 |S|, |S| = sqrt(2 S:S), for cs^2 = 1/3 and dx = dt = 1, where Pi_neq is the non-equilibrium momentum flux of
+// the post-BC populations. STRICT: the operation tree of the issue's reference operator (tests/test_gpu_les.py les_collide) in IEEE
+// arithmetic with correctly rounded square roots and divisions, on ux, uy already divided by rho — bit-identical to numpy.
+template <typename T>
+__device__ __forceinline__ T les_tau_inv_strict(const T (&f)[Q], T rho, T ux, T uy, T tau, T tau2, T c) {
+    const T sxx = ((((f[1] + f[3]) + f[5]) + f[6]) + f[7]) + f[8];
+    const T syy = ((((f[2] + f[4]) + f[5]) + f[6]) + f[7]) + f[8];
+    const T sxy = ((f[5] - f[6]) + f[7]) - f[8];
+    const T pxx = (sxx - rho * (ux * ux)) - rho * T(1.0 / 3.0);
+    const T pyy = (syy - rho * (uy * uy)) - rho * T(1.0 / 3.0);
+    const T pxy = sxy - rho * (ux * uy);
+    const T qn = sqrt_t((pxx * pxx + pyy * pyy) + T(2.0) * (pxy * pxy));
+    const T tau_eff = T(0.5) * (tau + sqrt_t(tau2 + c * (qn / rho)));
+    return T(1.0) / tau_eff;
+}
+
+// collision_step for one cell, LBMSolver.h:101-123 (moments i = 0..8 ascending from 0, N7). LES modes: tau_inv is ignored and the
+// relaxation rate of the cell comes from les_tau / les_tau2 / les_c (KArgs); BGK modes never read those three.
 template <typename T, int AR = AR_STRICT>
-__device__ __forceinline__ void bgk_collide(T (&f)[Q], T tau_inv) {
+__device__ __forceinline__ void bgk_collide(T (&f)[Q], T tau_inv, T les_tau = T(0), T les_tau2 = T(0), T les_c = T(0)) {
     T rho = T(0), ux = T(0), uy = T(0);
-    if (AR == AR_CONTRACTED) {
+    if constexpr (ar_contracted(AR)) {
         // moments as short trees over opposite pairs (depth 4 / 3 instead of chains of 9 / 6 dependent additions)
         const T a13 = f[1] + f[3], a24 = f[2] + f[4], a57 = f[5] + f[7], a68 = f[6] + f[8];
         const T d13 = f[1] - f[3], d24 = f[2] - f[4], d57 = f[5] - f[7], d68 = f[6] - f[8];
@@ -279,8 +318,18 @@ __device__ __forceinline__ void bgk_collide(T (&f)[Q], T tau_inv) {
         // v = 3u. 1 + 3cu + 4.5cu^2 - 1.5u^2 = base + cv*(1 + 0.5cv) with cv = c.v and base = 1 - v^2/6: the inner bracket
         // is one FMA with INLINE constants (0.5, 1.0). gfx950 VALU instructions take one SGPR/literal operand at most, so
         // fma(4.5, cu, 3.0) cost two v_mov per direction to build the 3.0 — 16 of ~100 vector instructions per cell.
-        const T inv3 = recip_t(rho) * T(3.0);
+        const T rinv = recip_t(rho);
+        const T inv3 = rinv * T(3.0);
         const T vx = ux * inv3, vy = uy * inv3;
+        if constexpr (ar_les(AR)) {
+            // the same operator with FMAs on the momenta (ux, uy here are rho*u): Pi_neq = S - j j / rho - rho/3 I
+            const T sxx = (a13 + a57) + a68, syy = (a24 + a57) + a68, sxy = a57 - a68;
+            const T jxr = ux * rinv;
+            const T third = rho * T(-1.0 / 3.0);
+            const T pxx = fma_t(-jxr, ux, sxx + third), pyy = fma_t(-uy * rinv, uy, syy + third), pxy = fma_t(-jxr, uy, sxy);
+            const T qn = sqrt_c(fma_t(pxx, pxx, fma_t(pyy, pyy, T(2.0) * (pxy * pxy))));
+            tau_inv = T(2.0) * recip_t(les_tau + sqrt_c(fma_t(les_c, qn * rinv, les_tau2)));
+        }
         const T base = fma_t(T(-1.0 / 6.0), fma_t(vx, vx, vy * vy), T(1.0));
         const T wr0 = wgt<T>(0) * rho, wr1 = wgt<T>(1) * rho, wr5 = wgt<T>(5) * rho;
 #pragma unroll
@@ -303,6 +352,7 @@ __device__ __forceinline__ void bgk_collide(T (&f)[Q], T tau_inv) {
         if (cy(i) != 0) uy += T(cy(i)) * f[i];
     }
     strict_div2(ux, uy, rho);
+    if constexpr (ar_les(AR)) tau_inv = les_tau_inv_strict(f, rho, ux, uy, les_tau, les_tau2, les_c);
     const T usq = ux * ux + uy * uy;
     // feq_i = w_i*rho*(1.0 + 3.0*cu + 4.5*cu*cu - 1.5*usq), cu = c_ix*ux + c_iy*uy with integer c (LBMSolver.h:119-121), evaluated
     // operation by operation in the reference's order: ((1.0 + 3.0*cu) + (4.5*cu)*cu) - 1.5*usq. Shared WITHOUT changing a bit:
@@ -329,6 +379,13 @@ __device__ __forceinline__ void bgk_collide(T (&f)[Q], T tau_inv) {
     pair(2, 4, uy, wr1);              // c2 = (0,1),  c4 = (0,-1)
     pair(5, 7, ux + uy, wr5);         // c5 = (1,1),  c7 = (-1,-1)
     pair(8, 6, ux - uy, wr5);         // c8 = (1,-1), c6 = (-1,1): 1*ux + (-1)*uy == ux - uy
+}
+
+// The collision of the step kernels: BGK with the global 1/tau, or (LES modes) the Smagorinsky rate of each cell
+template <typename T, int AR>
+__device__ __forceinline__ void collide(T (&f)[Q], const KArgs<T>& a) {
+    if constexpr (ar_les(AR)) bgk_collide<T, AR>(f, T(0), a.les_tau, a.les_tau2, a.les_c);
+    else bgk_collide<T, AR>(f, a.tau_inv);
 }
 
 // Grid::check_stability on one cell's populations: NaN, Inf, > 1e5, < -1e5 (LBMGrid.h:296-307); 1e5 is exact in fp32 too,
@@ -401,7 +458,7 @@ __global__ void __launch_bounds__(256) k_step_site(const KArgs<T> a) {
         }
     } else {
         if (solid) return;   // collision skips solid cells: they keep w_i for ever (LBMSolver.h:92, N4)
-        bgk_collide<T, AR>(f, a.tau_inv);
+        collide<T, AR>(f, a);
     }
 #pragma unroll
     for (int i = 0; i < Q; ++i) {
@@ -441,7 +498,7 @@ __device__ __forceinline__ void cell_update_as(const KArgs<T>& a, T (&f)[Q], int
     if (!solid) bcs_at(a, f, x, yg);
     if (BRANCH_FREE) bad |= unstable_if(f, count);
     else if (count) bad |= any_unstable(f);
-    bgk_collide<T, AR>(f, a.tau_inv);
+    collide<T, AR>(f, a);
     if (near_solid) {
 #pragma unroll
         for (int i = 0; i < Q; ++i) f[i] = solid ? wgt<T>(i) : f[i];
@@ -462,7 +519,7 @@ __device__ __forceinline__ bool cell_update_last(const KArgs<T>& a, T (&f)[Q], i
     if (!solid) bcs_at(a, f, x, yg);
     bad |= any_unstable(f);
     if (solid) return false;
-    bgk_collide<T, AR>(f, a.tau_inv);
+    collide<T, AR>(f, a);
     return true;
 }
 
@@ -632,7 +689,7 @@ __device__ __forceinline__ void step_tile(const KArgs<T>& a, const K2Extra<T>& e
             if (LEAN) {
                 fr.load(f, fr.at(ry, rx), fr.src_off(a, Y0 - HW, X0 - HW));
                 bad |= any_unstable(f);
-                bgk_collide<T, AR>(f, a.tau_inv);
+                collide<T, AR>(f, a);
             } else {
                 const int x = X0 + rx - HW, y = Y0 + ry - HW;
                 const int yg = a.y_start + y;
@@ -685,7 +742,7 @@ __device__ __forceinline__ void step_tile(const KArgs<T>& a, const K2Extra<T>& e
                     for (int i = 0; i < Q; ++i) f[i] = g[k][i];
                     if (LEAN) {
                         badl |= any_unstable(f);
-                        bgk_collide<T, AR>(f, a.tau_inv);
+                        collide<T, AR>(f, a);
                     } else cell_update<T, AR>(a, f, x, yg, fr.near_solid, y <= y_end + HW - L, badl);
                 }
 #pragma unroll
@@ -705,7 +762,7 @@ __device__ __forceinline__ void step_tile(const KArgs<T>& a, const K2Extra<T>& e
             for (int i = 0; i < Q; ++i) f[i] = lds[i][ly + HW - cy(i)][lx + HW - cx(i)];
             if (LEAN) {
                 bad |= any_unstable(f);
-                bgk_collide<T, AR>(f, a.tau_inv);
+                collide<T, AR>(f, a);
                 fr.store(f, fr.at(ly, lx), fr.dst_off(a, Y0, X0), e.nt != 0);
             } else if (cell_update_last<T, AR>(a, f, x, a.y_start + y, fr.near_solid, bad)) store_cell(a, f, x, y, e.nt != 0);
         }
@@ -802,7 +859,7 @@ __global__ void __launch_bounds__(TX * TY, (deep_waves_per_simd<T, TX, TY, D>())
             if (LEAN) {
                 fr.load(f, fr.at(ry, rx), fr.src_off(a, Y0 - HW, X0 - HW));
                 bad |= any_unstable(f);
-                bgk_collide<T, AR>(f, a.tau_inv);
+                collide<T, AR>(f, a);
             } else {
                 const int x = X0 + rx - HW, y = Y0 + ry - HW;
                 const int yg = a.y_start + y;
@@ -848,7 +905,7 @@ __global__ void __launch_bounds__(TX * TY, (deep_waves_per_simd<T, TX, TY, D>())
                 cell_xy.template operator()<O>(r, ry, rx);
                 if (LEAN) {
                     badl |= any_unstable(g[k]);
-                    bgk_collide<T, AR>(g[k], a.tau_inv);
+                    collide<T, AR>(g[k], a);
                 } else {
                     const int x = X0 + rx - HW, y = Y0 + ry - HW;
                     const int yg = a.y_start + y;
@@ -877,7 +934,7 @@ __global__ void __launch_bounds__(TX * TY, (deep_waves_per_simd<T, TX, TY, D>())
                 for (int i = 0; i < Q; ++i) f[i] = lds[i][ly + HW - cy(i)][lx + HW - cx(i)];
                 if (LEAN) {
                     bad |= any_unstable(f);
-                    bgk_collide<T, AR>(f, a.tau_inv);
+                    collide<T, AR>(f, a);
                     fr.store(f, fr.at(ly, lx), fr.dst_off(a, Y0, X0), e.nt != 0);
                 } else if (cell_update_last<T, AR>(a, f, x, a.y_start + y, fr.near_solid, bad)) store_cell(a, f, x, y, e.nt != 0);
             }

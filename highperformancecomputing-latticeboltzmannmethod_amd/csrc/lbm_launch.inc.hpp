@@ -27,6 +27,9 @@ KArgs<T> make_kargs(const lbm_ctx* c, int src, int dst, int t) {
     a.y_lo2 = 0;
     a.y_cnt2 = 0;
     a.reverse = 0;
+    a.les_tau = (T)c->p.tau;           // the Smagorinsky constants (read by LES instantiations only): tau, tau^2, 18 sqrt(2) Cs^2, in double
+    a.les_tau2 = (T)(c->p.tau * c->p.tau);
+    a.les_c = (T)(18.0 * std::sqrt(2.0) * (c->les_cs * c->les_cs));
     return a;
 }
 
@@ -50,22 +53,14 @@ inline void configure_layout(lbm_ctx* c, int layout) {
 inline size_t buffer_bytes(const lbm_ctx* c) { return c->total * c->esize + 256; }  // +slack: displaced vector load
 
 // Launch one step-family kernel over the local rows [a.y_lo, a.y_lo + a.y_cnt). Instantiated: MODE_STEP in both store
-// policies and both arithmetic modes, MODE_COLLIDE_ONLY in both arithmetic modes, MODE_STREAM_ONLY once (no collision in it).
+// policies and both arithmetic modes, MODE_COLLIDE_ONLY in both arithmetic modes, MODE_STREAM_ONLY once (no collision in it);
+// an LES context (lbm_set_smagorinsky) launches the LES instantiations of MODE_STEP / MODE_COLLIDE_ONLY (lbm_les.hip).
 template <typename T, int MODE>
 void launch_rows(const lbm_ctx* c, const KArgs<T>& a, hipStream_t s) {
     const bool nt = (MODE == MODE_STEP) && c->use_nt;
     const bool fast = (MODE != MODE_STREAM_ONLY) && c->arith == AR_CONTRACTED;
-    const dim3 grid((c->nx + 255) / 256, a.y_cnt + a.y_cnt2), block(256);
-#define LBM_K1(NT_, AR_) hipLaunchKernelGGL((k_step_site<T, MODE, NT_, AR_>), grid, block, 0, s, a)
-    if constexpr (MODE == MODE_STEP) {
-        if (fast) { if (nt) LBM_K1(true, AR_CONTRACTED); else LBM_K1(false, AR_CONTRACTED); }
-        else { if (nt) LBM_K1(true, AR_STRICT); else LBM_K1(false, AR_STRICT); }
-    } else if constexpr (MODE == MODE_COLLIDE_ONLY) {
-        if (fast) LBM_K1(false, AR_CONTRACTED); else LBM_K1(false, AR_STRICT);
-    } else {
-        LBM_K1(false, AR_STRICT);
-    }
-#undef LBM_K1
+    if (MODE != MODE_STREAM_ONLY && c->les) launch_site_les<T>(a, MODE, nt, fast, s);
+    else launch_site_k<T, MODE, AR_STRICT, AR_CONTRACTED>(a, nt, fast, s);
 }
 
 // "deep" plans: shape id -> iterations per launch and tile. 1..3: LDS-image tiles (k_stepd_tile: six / seven iterations on
@@ -98,38 +93,17 @@ void launch_fused_rows(const lbm_ctx* c, const KArgs<T>& a, int depth, hipStream
                 return;
             }
         }
-        launch_col<T>(a, e, depth, c->use_nt != 0, fast, s);
+        if (c->les) launch_col_les<T>(a, e, depth, c->use_nt != 0, fast, s);   // (no tall LES regions: lbm_set_option / plan_candidates)
+        else launch_col<T>(a, e, depth, c->use_nt != 0, fast, s);
         return;
     }
     if (c->deep_now) {    // D iterations on a deep LDS tile (k_stepd_tile; whole-domain launches of small grids)
-#define LBM_KD(TX_, TY_, D_) do { \
-        dim3 gridd((c->nx + TX_ - 1) / TX_, (a.y_cnt + TY_ - 1) / TY_ + (a.y_cnt2 + TY_ - 1) / TY_); \
-        if (fast) hipLaunchKernelGGL((k_stepd_tile<T, TX_, TY_, D_, AR_CONTRACTED>), gridd, dim3(TX_ * TY_), 0, s, a, e); \
-        else hipLaunchKernelGGL((k_stepd_tile<T, TX_, TY_, D_, AR_STRICT>), gridd, dim3(TX_ * TY_), 0, s, a, e); } while (0)
-        switch (shape) {
-            case 1: LBM_KD(64, 16, 6); break;
-            case 2: LBM_KD(64, 16, 7); break;
-            default: LBM_KD(32, 32, 8); break;
-        }
-#undef LBM_KD
+        if (c->les) launch_deep_les<T>(a, e, shape, fast, s);
+        else launch_deep_k<T, AR_STRICT, AR_CONTRACTED>(a, e, shape, fast, s);
         return;
     }
-    const int ty = c->pair_ty;
-    dim3 grid((c->nx + 63) / 64, (a.y_cnt + ty - 1) / ty + (a.y_cnt2 + ty - 1) / ty);
-#define LBM_KT(K_, TY_, NTH_, G_) do { if (fast) hipLaunchKernelGGL((K_<T, TY_, NTH_, AR_CONTRACTED>), G_, dim3(NTH_), 0, s, a, e); \
-                                       else hipLaunchKernelGGL((K_<T, TY_, NTH_, AR_STRICT>), G_, dim3(NTH_), 0, s, a, e); } while (0)
-    if (depth == 4) {   // four iterations: 64x8 tiles only (LDS)
-        dim3 grid4((c->nx + 63) / 64, (a.y_cnt + 7) / 8 + (a.y_cnt2 + 7) / 8);
-        // fp64: 70.5 KB of LDS per block = two blocks per CU, so 1024 threads fill the 32 wave slots; fp32 (35 KB) fills them
-        // with four 512-thread blocks (measured: 1024 threads -14 % in fp32, +3 % in fp64)
-        constexpr int N4 = sizeof(T) == 8 ? 1024 : 512;
-        LBM_KT(k_step4_tile, 8, N4, grid4);
-    } else if (depth == 3) {
-        if (ty == 12) LBM_KT(k_step3_tile, 12, 1024, grid); else LBM_KT(k_step3_tile, 8, 512, grid);
-    } else {
-        if (ty == 12) LBM_KT(k_step2_tile, 12, 768, grid); else LBM_KT(k_step2_tile, 8, 512, grid);
-    }
-#undef LBM_KT
+    if (c->les) launch_tile_les<T>(a, e, depth, c->pair_ty, fast, s);
+    else launch_tile_k<T, AR_STRICT, AR_CONTRACTED>(a, e, depth, c->pair_ty, fast, s);
 }
 inline bool pair_possible(const lbm_ctx*) { return true; }   // partial tiles cover any nx
 template <typename T>

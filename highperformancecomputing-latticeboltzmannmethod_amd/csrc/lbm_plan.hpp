@@ -40,6 +40,7 @@ struct PlanQuery {
     bool strips = false;                // this context has (or simulates) strip faces
     bool faces = false;                 // ... and at least one of them is an internal face
     bool tune = true, can_tune = true;  // option "tune"; the grid is neither too small nor too large to measure
+    bool les = false;                   // Smagorinsky LES collision: no tall fp32 regions (no LES instantiation of them)
 };
 
 // The strip rule: 0: three iterations on 64x12 LDS tiles in pairs between exchanges; 1: six iterations on 64x16 LDS tiles of
@@ -101,7 +102,7 @@ inline std::vector<Plan> plan_candidates(const PlanQuery& q, const Plan& fixed) 
         cand.push_back({1, 0, 1, 7, 12, 1, "row-interleaved/7-step 64x32 in registers/alternate/xcd", 9});
     }
     // (round 4, fp32: 64x48 regions on twelve waves — 16384x4096 320 GLUPS against 289-298 on 64x32; 4096x1024 262 against 260)
-    if (q.esize == 4 && !small_grid) {
+    if (q.esize == 4 && !small_grid && !q.les) {
         cand.push_back({1, 0, 0, 7, 12, 1, "row-interleaved/7-step 64x48 in registers/xcd", 8});
         cand.push_back({1, 0, 1, 7, 12, 1, "row-interleaved/7-step 64x48 in registers/alternate/xcd", 8});
     }
@@ -127,12 +128,13 @@ inline std::vector<Plan> plan_candidates(const PlanQuery& q, const Plan& fixed) 
 }
 
 // the dominant kernel of a plan, as rocprofv3 names it (minus "lbmk::" and blanks)
+// (arith: the kernels' Arith value, 0..3; the region shapes follow its strict / contracted half)
 inline std::string plan_kernel_name(int fuse, int deep, int pair_ty, int nt, int arith, int esize) {
     char name[96];
     const char* t = esize == 4 ? "float" : "double";
     const bool tall = deep_is_tall(deep) && esize == 4;      // (tall regions and seven-iteration launches: plain stores only)
     const char* nts = nt && !tall && !(deep_is_col(deep) && deep_depth(deep) == 7) ? "true" : "false";
-    if (fuse > 2 && deep_is_col(deep)) snprintf(name, sizeof(name), "k_stepc_col<%s,%d,%d,%d,%s,%d>", t, col_rows_per_thread(esize, arith == 0, tall), col_waves(esize, arith == 0, tall), deep_depth(deep), nts, arith);
+    if (fuse > 2 && deep_is_col(deep)) snprintf(name, sizeof(name), "k_stepc_col<%s,%d,%d,%d,%s,%d>", t, col_rows_per_thread(esize, (arith & 1) == 0, tall), col_waves(esize, (arith & 1) == 0, tall), deep_depth(deep), nts, arith);
     else if (fuse > 2 && deep) snprintf(name, sizeof(name), "k_stepd_tile<%s,%s,%d,%d>", t, deep_tile(deep), deep_depth(deep), arith);
     else if (fuse == 4) snprintf(name, sizeof(name), "k_step4_tile<%s,8,%d,%d>", t, esize == 8 ? 1024 : 512, arith);
     else if (fuse > 1) snprintf(name, sizeof(name), "k_step%d_tile<%s,%d,%d,%d>", fuse, t, pair_ty, pair_ty == 12 ? (fuse == 3 ? 1024 : 768) : 512, arith);

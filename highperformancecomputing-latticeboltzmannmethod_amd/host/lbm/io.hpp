@@ -184,6 +184,7 @@ private:
             f.put("obstacle_mask,"); f.put(p.obstacle_mask_file.c_str()); f.put("\n");
         }
         if (p.profiled()) { f.put("inlet_profile,"); f.put(p.inlet_profile_spec.c_str()); f.put("\n"); }   // (profiled runs only, likewise)
+        if (p.les()) row_d("smagorinsky_cs", p.smagorinsky_cs);                                            // (LES runs only, likewise)
         std::printf("  simulation_params.csv written\n");
     }
     // calculate_time_averaged_drag (LBMIO.h:367-413): statistics of the CSV values (8 decimals) for timestep > 1000.

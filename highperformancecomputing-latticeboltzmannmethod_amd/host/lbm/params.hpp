@@ -38,10 +38,14 @@ struct SimulationParams {
     // absolute velocities, row 0 first, whose mean is inlet_velocity (host/lbm/inlet.hpp). Empty: inlet_velocity on every row.
     std::string inlet_profile_spec;
     std::vector<double> inlet_profile;
+    // Smagorinsky LES collision (lbm_solver --smagorinsky; not in the reference): the constant Cs, 0 = plain BGK. tau, nu() and
+    // reynolds() keep referring to the molecular viscosity.
+    double smagorinsky_cs = 0.0;
 
     double nu() const { return (tau - 0.5) / 3.0; }
     bool masked() const { return !obstacle_mask.empty(); }
     bool profiled() const { return !inlet_profile.empty(); }
+    bool les() const { return smagorinsky_cs > 0.0; }
     double reynolds() const {
         if (masked()) return inlet_velocity * mask_frontal_height / nu();
         return inlet_velocity * (2.0 * cylinder_radius * ny) / nu();

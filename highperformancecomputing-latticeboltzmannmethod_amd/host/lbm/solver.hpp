@@ -26,6 +26,9 @@ public:
         const int solid = grid_.setup_and_initialise();
         if (!opt_.quiet && params_.profiled())
             std::printf("  Inlet: profile %s, mean velocity %g (Cd / Cl refer to it)\n", params_.inlet_profile_spec.c_str(), params_.inlet_velocity);
+        if (!opt_.quiet && params_.les())
+            std::printf("  Collision: Smagorinsky LES, Cs = %g (tau and the Reynolds number refer to the molecular viscosity)\n",
+                        params_.smagorinsky_cs);
         if (!opt_.quiet && params_.masked()) {
             std::printf("  Obstacle: mask %s, frontal height D=%d cells\n  Solid cells: %d\n  Plan: %s\n", params_.obstacle_mask_file.c_str(),
                         params_.mask_frontal_height, solid, grid_.plan());

@@ -7,6 +7,7 @@
 #include "lbm/geometry.hpp"
 #include "lbm/inlet.hpp"
 
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -19,7 +20,7 @@ static void usage() {
               "           [--no-vtk] [--no-final] [--sync-vtk] [--fp32] [--contracted] [--no-tune] [--device D] [--quiet]\n"
               "           [--gpus N] [--strips N] [--rccl]\n"
               "           [--checkpoint FILE] [--restart FILE] [--obstacle-mask FILE.pgm]\n"
-              "           [--inlet-profile parabolic|FILE] [--print-inlet-profile]\n"
+              "           [--inlet-profile parabolic|FILE] [--print-inlet-profile] [--smagorinsky CS]\n"
               "Defaults are the reference's SimulationParams (LBMConfig.h:37-51). --reynolds sets the inlet velocity\n"
               "from tau and the cylinder diameter so that params.reynolds() equals RE.\n"
               "--gpus N cuts the lattice into N row strips, one per GPU of this node, advanced in lockstep by this process\n"
@@ -31,7 +32,10 @@ static void usage() {
               "s(1-s), s = (y+0.5)/ny; FILE: a text file of ny numbers, row 0 (bottom) first ('#' comments and blank lines\n"
               "allowed), giving the shape. Either is scaled so that its mean over the ny rows is the inlet velocity, which\n"
               "stays the reference velocity: Reynolds number, --reynolds and Cd / Cl refer to the bulk (mean) velocity.\n"
-              "--print-inlet-profile: print the ny inlet velocities (row 0 first) and exit without opening a device.");
+              "--print-inlet-profile: print the ny inlet velocities (row 0 first) and exit without opening a device.\n"
+              "--smagorinsky CS: Smagorinsky LES collision with constant CS in [0, 1] (0: plain BGK) instead of BGK, for\n"
+              "higher Reynolds numbers at the same tau. tau, the Reynolds number and --reynolds keep referring to the\n"
+              "molecular viscosity (tau - 0.5) / 3; the eddy viscosity of the model is added per cell.");
 }
 
 int main(int argc, char** argv) {
@@ -40,6 +44,7 @@ int main(int argc, char** argv) {
     bool vtk = true, final_results = true;
     std::string restart_from, checkpoint_to;
     bool print_profile = false;
+    const char* smagorinsky = nullptr;
     double reynolds = -1.0;
     for (int a = 1; a < argc; ++a) {
         const std::string k = argv[a];
@@ -74,8 +79,18 @@ int main(int argc, char** argv) {
         else if (k == "--obstacle-mask") params.obstacle_mask_file = val();
         else if (k == "--inlet-profile") params.inlet_profile_spec = val();
         else if (k == "--print-inlet-profile") print_profile = true;
+        else if (k == "--smagorinsky") smagorinsky = val();
         else if (k == "--help" || k == "-h") { usage(); return 0; }
         else { std::fprintf(stderr, "unknown option %s\n", k.c_str()); usage(); return 2; }
+    }
+    if (smagorinsky) {   // checked before any device is touched: a whole finite number in [0, 1]
+        char* end = nullptr;
+        const double cs = std::strtod(smagorinsky, &end);
+        if (end == smagorinsky || *end != '\0' || !std::isfinite(cs) || cs < 0.0 || cs > 1.0) {
+            std::fprintf(stderr, "--smagorinsky: '%s' is not a number in [0, 1]\n", smagorinsky);
+            return 2;
+        }
+        params.smagorinsky_cs = cs;
     }
     if (!params.obstacle_mask_file.empty()) {   // parsed and checked before any device is touched
         try {

@@ -134,6 +134,16 @@ int  lbm_set_solid_mask(lbm_ctx* c, const unsigned char* mask, int nx, int ny);
  * LBM_ERR_ARG: null pointer, ny other than the domain's, an initialised context, or a value that is not finite or is >= 1 (the
  * inlet divides by 1 - u). */
 int  lbm_set_inlet_profile(lbm_ctx* c, const double* u, int ny);
+/* The collision: replaces the BGK operator's one global tau (LBMSolver.h:85) by a Smagorinsky subgrid model with constant `cs`. Each
+ * fluid cell relaxes with tau_eff = (tau + sqrt(tau^2 + 18 sqrt(2) cs^2 |Pi|/rho)) / 2, where Pi is the non-equilibrium momentum flux
+ * of its post-BC populations: the closed form of tau_eff = tau + 3 cs^2 |S|, |S| = sqrt(2 S:S), for cs^2 = 1/3 and dx = dt = 1. This
+ * stabilises runs whose tau approaches 0.5 (higher Reynolds numbers on the same grid); tau (and with it the caller's Reynolds number)
+ * keeps naming the molecular viscosity. Strict arithmetic (option arith=0) evaluates the operator in IEEE operations with correctly
+ * rounded square roots, contracted arithmetic (arith=1) with FMAs. Every strip of a run is given the same value. Call after lbm_create
+ * and before lbm_initialise, like lbm_set_solid_mask: the plan is then measured on the LES kernels (no fp32 deep=8 plan: pinning it
+ * fails). cs == 0 clears the model (the BGK kernels). Checkpoints carry cs (lbm_save_state: magic "LBMCKPT3", flag bit 2).
+ * LBM_ERR_ARG: null context, an initialised context, or a value that is not finite, < 0 or > 1. */
+int  lbm_set_smagorinsky(lbm_ctx* c, double cs);
 
 /* ---- strip halo exchange (replaces Grid::exchange_ghost_cells, LBMGrid.h:249-283) ----
  * Device path: RCCL send/recv of the LBM_HALO_ROWS edge rows per face (one contiguous run in the row-interleaved
@@ -189,8 +199,9 @@ int  lbm_halo_import(lbm_ctx* c, const double* south_in, const double* north_in)
 
 /* Checkpoint / restart (the reference has none): the strip's post-collision populations and the
  * iteration counter. lbm_load_state needs an initialised context created with the same parameters; the macro /
- * population snapshots become available again after the next lbm_step. A file written with an obstacle mask or an inlet
- * profile loads only into a context with the same mask and the same profile (the failure names which one differs). */
+ * population snapshots become available again after the next lbm_step. A file written with an obstacle mask, an inlet
+ * profile or a Smagorinsky constant loads only into a context with the same mask, profile and constant (the failure names which one
+ * differs). */
 int  lbm_save_state(lbm_ctx* c, const char* path);
 int  lbm_load_state(lbm_ctx* c, const char* path);
 
