@@ -169,7 +169,7 @@ inline lbm_ctx* choreo_fake_ctx(int nx, int ny, int y_start, int rows, int preci
     configure_layout(c, 1);
     c->cyl_x = (int)(0.2 * nx); c->cyl_y = (int)(0.5 * ny); c->cyl_r = (int)(0.05 * ny);
     const uintptr_t base = 0x10000u * (uintptr_t)(k + 1);
-    c->stream = (hipStream_t)(base + 0x10); c->comm_stream = (hipStream_t)(base + 0x20);
+    c->stream = (hipStream_t)(base + 0x10); c->comm_stream = (hipStream_t)(base + 0x20); c->split_stream = (hipStream_t)(base + 0x60);   // (a split context's second stream is the "side" stream of the record: it has no exchange stream in use)
     c->ev_main = (hipEvent_t)(base + 0x30); c->ev_edge = (hipEvent_t)(base + 0x40); c->ev_comm = (hipEvent_t)(base + 0x50);
     c->buf[0] = (void*)(base + 0x1000); c->buf[1] = (void*)(base + 0x2000);
     c->group_k = k;

@@ -280,7 +280,7 @@ struct lbm_ctx {
     bool last_was_pair = false;   // the last launch fused several iterations: buf[cur^1] is older than steps_done-1
     bool restored = false;   // state came from lbm_load_state: no previous-iteration buffer until the next step
     int tune = 1;        // lbm_initialise times the candidate plans on this device and keeps the fastest
-    char plan_desc[512] = "";
+    char plan_desc[1024] = "";
     char plan_opts[128] = "";    // the plan as lbm_set_option pairs ("layout=1 nt=0 ..."): with tune=0 they reproduce it in another process
     double depth_rel[4] = {2.8, 1.6, 1.12, 1.08};   // cost per iteration of a 1- / 2- / 3- / 4-iteration launch relative to the plan's deep
                                                     // launch (plan_launch's tail split); measured by choose_plan on a single domain,
@@ -314,6 +314,17 @@ struct lbm_ctx {
     std::shared_ptr<GroupPool> pool;   // the group's host threads (shared by its members)
     int edge_rows[2] = {0, 0};   // edge-band heights of the launch in flight (issue_before -> issue_after)
     bool ext_split_pending = false;   // overlap 2: the edge part of the last extended launch is queued on the side stream (ev_edge)
+    // Whole-domain deep launches of the register family as n staggered row-range launches on two streams (issue_split, lbm_strips.inc.hpp)
+    int split = 0;                   // option "split": 0 one launch, 3 / 4 row ranges; pinned by lbm_set_option or measured by choose_plan
+    bool split_pinned = false;
+    int split_min = 8;               // option "split_min": launches that must lie ahead in a segment for a sequence of range launches to start
+    bool split_now = false;          // the launch being issued may be split (set by plan_launch)
+    hipStream_t split_stream = nullptr;   // the second stream of the range launches (default priority: neither stream may starve the other)
+    int split_i = 0;                 // range kernels issued since the last join: kernel i runs on stream i mod 2 and records event i mod 3
+    int split_n = 0, split_depth = 0, split_cut[5] = {0, 0, 0, 0, 0};   // the ranges (first rows, end) and depth of the last split launch
+    int split_extra = 0;             // kernels beyond one per launch that the split launches of the call in progress were issued as
+    int timed_dispatches = 0;        // step kernels the launches of the last call were issued as (lbm_last_step_dispatches)
+    int debug_skip_split_wait = 0;   // TEST ONLY: a range kernel does not wait for the other stream's kernel it depends on (the detector must flag it)
     // hipGraph replay of launch groups (a strip with a device transport on a deep plan; see replay_groups)
     int use_graph = 1;               // option "graph"
     hipGraphExec_t gexec = nullptr;  // GRAPH_GROUPS consecutive launch groups captured from the eager path

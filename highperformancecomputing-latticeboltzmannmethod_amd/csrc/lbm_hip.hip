@@ -191,6 +191,7 @@ int lbm_create(const lbm_params* p, int device, lbm_ctx** out) {
         (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
         HIPTRY(hipStreamCreateWithPriority(&c->comm_stream, hipStreamNonBlocking, hi));
     }
+    HIPTRY(hipStreamCreateWithFlags(&c->split_stream, hipStreamNonBlocking));      // the second stream of split launches: default priority
     HIPTRY(hipEventCreateWithFlags(&c->ev_edge, hipEventDisableTiming | hipEventDisableSystemFence));   // device-side ordering only
     HIPTRY(hipEventCreateWithFlags(&c->ev_comm, hipEventDisableTiming | hipEventDisableSystemFence));   // device-side ordering only
     HIPTRY(hipEventCreateWithFlags(&c->ev_main, hipEventDisableTiming | hipEventDisableSystemFence));   // device-side ordering only
@@ -237,6 +238,7 @@ void lbm_destroy(lbm_ctx* c) {
     bool leak = c->pool && c->pool->S->broken.load() && !c->pool->quiesce(std::max(5000L, c->pool->S->timeout_ms));
     if (!leak && c->stream && wait_stream(c, c->stream, "compute stream (lbm_destroy)") == LBM_ERR_TIMEOUT) leak = true;
     if (!leak && c->comm_stream && wait_stream(c, c->comm_stream, "exchange stream (lbm_destroy)") == LBM_ERR_TIMEOUT) leak = true;
+    if (!leak && c->split_stream && wait_stream(c, c->split_stream, "second compute stream (lbm_destroy)") == LBM_ERR_TIMEOUT) leak = true;
     for (lbm_ctx* nb : {c->nb_south, c->nb_north}) {  // a destroyed member leaves its group
         if (!nb) continue;
         // the neighbour's exchange stream may still hold a pull (hipMemcpyPeerAsync) that READS this member's edge rows, and
@@ -268,6 +270,7 @@ void lbm_destroy(lbm_ctx* c) {
         if (e) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     if (c->comm_stream) (void)hipStreamDestroy(c->comm_stream);
+    if (c->split_stream) (void)hipStreamDestroy(c->split_stream);
     lbm_trace("destroy", "ctx %p end", (void*)c);
     delete c;
 }
@@ -279,6 +282,8 @@ int lbm_initialise(lbm_ctx* c, int* solid_count_out) {
     HIPCHK(hipSetDevice(c->device));
     { int wr = wait_stream(c, c->stream, "compute stream (lbm_initialise)"); if (wr) return wr; }        // (re-)initialisation starts from quiet streams
     { int wr = wait_stream(c, c->comm_stream, "exchange stream (lbm_initialise)"); if (wr) return wr; }
+    { int wr = wait_stream(c, c->split_stream, "second compute stream (lbm_initialise)"); if (wr) return wr; }
+    c->split_i = 0;
     c->steps_done = 0;
     c->log_count = 0;
     c->mid_pair = false;
@@ -317,6 +322,7 @@ int lbm_sync(lbm_ctx* c) {
     auto wait = [&](hipStream_t s, const char* what) { return c->wait_timeout_ms > 0 ? wait_stream(c, s, what) : sync_stream_blocking(c, s, what); };
     int rc = wait(c->stream, "compute stream");
     if (!rc) rc = wait(c->comm_stream, "exchange stream");
+    if (!rc) rc = wait(c->split_stream, "second compute stream");      // (a call joins it into the compute stream before it returns: empty by now)
     return rc;
 }
 
@@ -781,6 +787,12 @@ int lbm_set_option(lbm_ctx* c, const char* key, long value) {
     else if (k == "debug_fault_stall_ms") c->debug_fault_stall_ms = (int)value;
     else if (k == "debug_old_edge_band") c->debug_old_edge_band = (int)value ? 1 : 0;      // TEST ONLY: see lbm_ctx
     else if (k == "debug_skip_pull_wait") c->debug_skip_pull_wait = (int)value ? 1 : 0;    // TEST ONLY: see lbm_ctx
+    else if (k == "debug_skip_split_wait") c->debug_skip_split_wait = (int)value ? 1 : 0;  // TEST ONLY: see lbm_ctx
+    else if (k == "split_min") { if (value < 1) return fail(LBM_ERR_ARG, "split_min must be >= 1"); c->split_min = (int)value; }
+    else if (k == "split") {    // a whole-domain deep launch of the register family as 3 / 4 staggered row-range launches on two streams (0: one launch)
+        if (value != 0 && value != 3 && value != 4) return fail(LBM_ERR_ARG, "split must be 0, 3 or 4");
+        c->split = (int)value; c->split_pinned = true;      // (between calls nothing is in flight on the second stream: do_steps joins it)
+    }
     else if (k == "graph") { if (value < 0 || value > 2) return fail(LBM_ERR_ARG, "graph must be 0, 1 or 2"); c->use_graph = (int)value; }
     else if (k == "loopback") c->loopback = (int)value;   // 0 off, 1 device copies, 2 RCCL self send/recv
     else if (k == "pair_ty") { if (value != 8 && value != 12) return fail(LBM_ERR_ARG, "pair_ty must be 8 or 12"); c->pair_ty = (int)value; }
@@ -815,6 +827,8 @@ int lbm_last_step_stats(lbm_ctx* c, double* ms_total, int* launches, int* iterat
     if (ms_total) *ms_total = (double)ms;
     return LBM_OK;
 }
+
+int lbm_last_step_dispatches(const lbm_ctx* c) { return c ? c->timed_dispatches : 0; }
 
 long lbm_graph_replays(const lbm_ctx* c) { return c ? c->graph_replays : 0; }
 

@@ -120,6 +120,7 @@ int do_steps(lbm_ctx** cs, int n, int nsteps, int of) {
         lbm_ctx* c = cs[i];
         SETDEV(c);
         if (c->timing) HIPCHK(hipEventRecord(c->ev_t0, c->stream));
+        c->split_extra = 0;
         if (c->steps_done != cs[0]->steps_done) return fail(LBM_ERR_ARG, "the strips of a group are at different iterations");
     }
     lbm_ctx* c0 = cs[0];
@@ -225,6 +226,9 @@ int do_steps(lbm_ctx** cs, int n, int nsteps, int of) {
         k += L[0].depth;
         ++launches;
     }
+    // a call leaves everything it queued on the main stream (and behind its exchanges): whatever follows — an accessor, a checkpoint,
+    // lbm_sync, the next call's ev_t0 — need not know that its last launches ran as row ranges on two streams
+    for (int i = 0; i < n; ++i) { int jr = split_join(cs[i]); if (jr) return jr; }
     for (int i = 0; i < n; ++i) {
         lbm_ctx* c = cs[i];
         if (!c->timing) continue;
@@ -233,6 +237,7 @@ int do_steps(lbm_ctx** cs, int n, int nsteps, int of) {
         if (jr) return jr;
         HIPCHK(hipEventRecord(c->ev_t1, c->stream));
         c->timed_launches = launches;
+        c->timed_dispatches = launches + c->split_extra;
         c->timed_steps = nsteps;
     }
     return LBM_OK;

@@ -304,6 +304,7 @@ inline int plan_launch(lbm_ctx* c, int remaining, int of, bool transport, bool s
     const bool any_face = strip_logic && (face_south(c) || face_north(c));
     bool deep_plan = false;      // a deep plan exchanges after every launch (no extended first launch of a pair)
     c->deep_now = false;
+    c->split_now = false;
     if (c->fuse > 1) {
         const int room = remaining - (c->trailing_pair ? 0 : 1);       // iterations a fused launch may take now
         int dmax = std::min(c->fuse, any_face ? 3 : 4);  // (four: k_step4_tile, no faces)
@@ -325,6 +326,10 @@ inline int plan_launch(lbm_ctx* c, int remaining, int of, bool transport, bool s
             // on an LDS shape, rather than 6 + 6 + 6 + 2: the two- and one-iteration kernels run at half and a third of the
             // fused rate).
             const int seg = of > 0 ? std::min(room, of - t % of) : room;
+            // (option "split": the two streams pay for their start and their join with about one launch boundary each, which a segment
+            // of a few launches never earns back — the driver's 20-step window, three launches, ran 15 % slower split than whole. A
+            // sequence of range launches starts only with "split_min" launches ahead, and then runs to the segment's end.)
+            c->split_now = c->split_i > 0 || seg >= c->split_min * deep;
             // depths the plan's kernel family offers: the register kernel five and six iterations anywhere, seven on a
             // context without strip faces (a strip's ghost rows go six deep); the LDS shapes their own depth only
             auto in_family = [&](int d) {
@@ -387,6 +392,98 @@ inline int plan_launch(lbm_ctx* c, int remaining, int of, bool transport, bool s
     return LBM_OK;
 }
 
+// ---- a whole-domain deep launch as staggered row-range launches (option "split") ----------------------------
+// Consecutive launches on one stream meet at a kernel boundary: launch t+1 places no block before the LAST block of launch t has
+// retired, so the machine drains half empty and then ramps with every block in the same phase (all loading, nobody computing). At
+// 4096x1024 fp64 (seven rounds of blocks per launch) that boundary is worth ~20 us of a 173 us launch (profiles/split/README.md).
+// A split launch is issued as n = 3 or 4 kernels over row ranges R1..Rn, bottom to top, round-robin on two streams, so that at any
+// moment two kernels of different phase share the machine and the drain of one is filled by the undispatched blocks of the other.
+//
+// The ranges are cut at multiples of the launch's output height OH counted from row 0: the tile grid — and with it every tile's
+// `lean` verdict and every bit of the result — is the one the single launch has; only the last range holds the partial band. The
+// ranges are UNEQUAL (14 / 17 / 16 tile rows of 47) so that two kernels released together do not end together, and every range is
+// taller than twice the depth (else the launch is issued whole).
+//
+// Dependencies. The launch of step group t over Rj reads buf[src] on Rj grown by `depth` rows and writes buf[dst] on Rj. Issue
+// order is R1_t, R2_t, .., Rn_t, R1_{t+1}, ..; number the kernels K_0, K_1, .. in that order.
+//   RAW: Rj_{t+1} reads what R(j-1)_t, Rj_t, R(j+1)_t wrote.
+//   WAR: Rj_{t+1} overwrites rows that R(j-1)_t, Rj_t, R(j+1)_t read. The same three.
+//   Nothing else: Rj_{t+1} and R(j+-1)_{t+1} read one buffer and write disjoint rows of the other.
+// So K_i depends on K_{i-n-1}, K_{i-n}, K_{i-n+1} at most — with n = 3 on K_{i-4}, K_{i-3}, K_{i-2}, with n = 4 on K_{i-5}, K_{i-4},
+// K_{i-3} — and NEVER on K_{i-1}. Kernel i goes to stream i mod 2 and records event i mod 3 behind itself: kernels of equal parity are
+// ordered by their stream, and ONE wait for the event of K_{i-3} (other stream; it is event i mod 3, waited for before it is recorded
+// again) covers the rest, K_{i-5} being older on that same stream. One record and one wait per kernel, through q_record / q_wait, so
+// that the choreography checker sees them (tests/test_choreography_split_cpu.py).
+// The first kernels after a join have no K_{i-3}: K_1 is released behind an event recorded on the main stream in front of K_0, which
+// puts the second stream behind everything the main stream held. K_0 and K_1 then start together, and two kernels that share the
+// machine evenly stay in lockstep — every pair ends together and exposes MORE drains than the single launch (measured: the driver's
+// 20-step window, nine kernels, 120 against 140 GLUPS when K_1 waited for K_0 and the pairs (K_1, K_2), (K_3, K_4) .. ran in phase).
+// So the FIRST launch after a join cuts differently: a short first range (7 / 20 / 20 tile rows of 47), which ends when its partner is
+// a third done; from then on a kernel starts when the other stream's is about half done, which is the state a long run settles in.
+// Launches of different depth (a call's remainders: 20 = 6 + 7 + 7) cut at multiples of different heights. The rule above still holds
+// while range j, grown by the larger of the two depths, touches no old range but j-1, j, j+1 (split_follows); else the streams are
+// joined first. Everything that assumes the main stream holds all work — the force kernel, ev_t1, accessors, checkpoints, a launch
+// that is not split, the end of every lbm_step call — goes through split_join (join_comm calls it).
+// A start and a join cost about one boundary each: plan_launch starts a sequence only where "split_min" (8) launches lie ahead in the
+// segment (up to the next force output or the end of the call); shorter segments run as single launches, as without the option.
+inline bool split_possible(const lbm_ctx* c) {      // the context: a whole domain on its own, on a plan of the register family
+    return (c->split == 3 || c->split == 4) && deep_is_col(c->deep) && !face_south(c) && !face_north(c) && !device_transport(c) && c->group_n <= 1;
+}
+// first rows of the n ranges of a launch of `depth` iterations (cut[n] = the end); 0: the rows are too few for n ranges.
+// `first`: the cuts of the first launch after a join (a short first range: see above)
+inline int split_ranges(const lbm_ctx* c, int depth, int* cut, bool first = false) {
+    static const double frac[2][2][3] = {{{0.30, 0.66, 1.0}, {0.22, 0.49, 0.75}}, {{0.15, 0.58, 1.0}, {0.11, 0.40, 0.70}}};
+    const int n = c->split;
+    const int OH = deep_rows(c, c->deep, depth), nb = (c->nyl + OH - 1) / OH;
+    cut[0] = 0; cut[n] = c->nyl;
+    for (int j = 1; j < n; ++j) cut[j] = std::min(c->nyl, (int)std::lround(frac[first ? 1 : 0][n - 3][j - 1] * nb) * OH);
+    for (int j = 0; j < n; ++j) if (cut[j + 1] - cut[j] <= 2 * depth) return 0;
+    return n;
+}
+// does a launch over these ranges keep the dependency distance behind the last split launch?
+inline bool split_follows(const lbm_ctx* c, int n, int depth, const int* cut) {
+    if (c->split_n != n) return false;
+    const int D = std::max(depth, c->split_depth);
+    for (int j = 0; j < n; ++j) {
+        if (j >= 2 && cut[j] - D < c->split_cut[j - 1]) return false;               // reaches down into old range j-2
+        if (j + 2 < n && cut[j + 1] + D > c->split_cut[j + 2]) return false;        // reaches up into old range j+2
+    }
+    return true;
+}
+// the main stream waits for the last kernel of the second stream; the next range kernel starts a new sequence
+inline int split_join(lbm_ctx* c) {
+    if (c->split_i >= 2) {
+        hipEvent_t ev[3] = {c->ev_main, c->ev_edge, c->ev_comm};
+        const int m = ((c->split_i - 1) & 1) ? c->split_i - 1 : c->split_i - 2;     // the youngest odd kernel
+        QCHK(q_wait(c, c->stream, c, ev[m % 3]));
+    }
+    c->split_i = 0;
+    return LBM_OK;
+}
+template <typename T>
+int issue_split(lbm_ctx* c, KArgs<T> a, const Launch& L, int n, const int* cut_regular) {
+    hipEvent_t ev[3] = {c->ev_main, c->ev_edge, c->ev_comm};      // (free on a context without a device transport)
+    if (c->split_i > 0 && !split_follows(c, n, L.depth, cut_regular)) QCHK(split_join(c));
+    int cut_first[5];
+    const int* cut = (c->split_i == 0 && split_ranges(c, L.depth, cut_first, true)) ? cut_first : cut_regular;
+    for (int j = 0; j < n; ++j) {
+        const int i = c->split_i;
+        hipStream_t s = (i & 1) ? c->split_stream : c->stream;
+        if (i == 0) QCHK(q_record(c, ev[1], s));          // what the main stream holds so far: K_1 starts behind it, beside K_0
+        if (i == 1) QCHK(q_wait(c, s, c, ev[1]));
+        else if (i >= 3 && !c->debug_skip_split_wait) QCHK(q_wait(c, s, c, ev[i % 3]));      // (TEST ONLY: the checker must name the race)
+        a.y_lo = cut[j]; a.y_cnt = cut[j + 1] - cut[j];
+        launch_depth<T>(c, a, L.depth, s);
+        LAUNCHED(c);
+        QCHK(q_record(c, ev[i % 3], s));
+        c->split_i = i + 1 < 18 ? i + 1 : i + 1 - 6;      // (parity and residue mod 3 are all that matter past the first three)
+    }
+    c->split_n = n; c->split_depth = L.depth;
+    for (int j = 0; j <= n; ++j) c->split_cut[j] = cut[j];
+    c->split_extra += n - 1;
+    return LBM_OK;
+}
+
 // Everything of a launch that precedes its exchange.
 template <typename T>
 int issue_before(lbm_ctx* c, const Launch& L) {
@@ -394,6 +491,10 @@ int issue_before(lbm_ctx* c, const Launch& L) {
     const int rev = (c->alternate && (c->launches_total & 1)) ? 1 : 0;
     if (L.kind == KIND_LOCAL) {
         a.reverse = rev;
+        int cut[5];
+        const int n = (c->deep_now && c->split_now && split_possible(c)) ? split_ranges(c, L.depth, cut) : 0;
+        if (n) return issue_split<T>(c, a, L, n, cut);
+        QCHK(split_join(c));
         launch_depth<T>(c, a, L.depth, c->stream);
         LAUNCHED(c);
         return LBM_OK;
@@ -522,6 +623,7 @@ int advance(lbm_ctx* c, int remaining, int of, bool transport, bool strip_logic 
 
 // Make everything issued so far (both streams) visible to work queued on the compute stream afterwards.
 inline int join_comm(lbm_ctx* c) {
+    QCHK(split_join(c));          // the range kernels of a split launch on the second stream
     if (c->ext_split_pending) {   // overlap 2: the edge bands of the last extended launch (queued behind the exchange)
         QCHK(q_wait(c, c->stream, c, c->ev_edge));
         c->ext_split_pending = false;

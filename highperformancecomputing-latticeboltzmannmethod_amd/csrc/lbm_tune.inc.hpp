@@ -35,8 +35,12 @@ int time_plan(lbm_ctx* c, float* ms_out, int window = 36) {
     *ms_out = 1e30f;
     for (int rep = 0; rep < 2; ++rep) {      // the faster of two windows of `window` iterations (36: six to a dozen fused launches each)
         const int t0 = c->steps_done;
+        rc = split_join(c);           // (a split plan: the window starts and ends with the second stream joined into the main one)
+        if (rc) return rc;
         HIPCHK(hipEventRecord(c->ev_t0, c->stream));
         rc = run(window);
+        if (rc) return rc;
+        rc = split_join(c);
         if (rc) return rc;
         HIPCHK(hipEventRecord(c->ev_t1, c->stream));
         HIPCHK(hipEventSynchronize(c->ev_t1));
@@ -71,7 +75,22 @@ int choose_plan(lbm_ctx* c) {
     free_buffers(c);                                // a second lbm_initialise starts from no population buffers
     // First round: every candidate once; the three fastest keep their allocations. Final round: those three again with
     // longer windows (candidates within 2 % of each other are common and the first round cannot tell them apart).
-    struct Kept { int k; float ms; void* buf[2]; };
+    struct Kept { int k; float ms; void* buf[2]; int split = 0; };
+    // "split" (a whole-domain deep launch as 3 / 4 staggered row-range launches, lbm_strips.inc.hpp) is one more dimension of the
+    // finalists, measured like the rest where a launch is at least ~6 rounds of blocks (two per CU) — on fewer there is no boundary worth
+    // hiding behind three more dispatches; pinned, it holds for every trial
+    const int pinned_split = c->split_pinned ? c->split : 0;
+    c->split = pinned_split;
+    auto split_worth_trying = [&](const Plan& pl) {
+        if (c->split_pinned || !deep_is_col(pl.deep)) return false;
+        const int d = deep_depth(pl.deep), OW = col_tile_w(d), OH = deep_rows(c, pl.deep, d);
+        const long tiles = (long)((c->nx + OW - 1) / OW) * ((c->nyl + OH - 1) / OH);
+        int cut[5];
+        c->split = 3;
+        const bool ok = split_possible(c) && split_ranges(c, d, cut) && tiles >= 6L * 2 * c->num_cus;
+        c->split = 0;
+        return ok;
+    };
     std::vector<Kept> top;
     auto drop_all = [&]() { for (Kept& t : top) for (void*& q : t.buf) if (q) { (void)hipFree(q); q = nullptr; } top.clear(); };
     const bool room = can_tune && 4 * need + (1u << 28) < free_b;     // three kept allocations + the one being probed
@@ -86,12 +105,12 @@ int choose_plan(lbm_ctx* c) {
             rc = time_plan<T>(c, &ms);
             if (rc) { free_buffers(c); drop_all(); return rc; }
         }
-        top.push_back({(int)k, ms, {c->buf[0], c->buf[1]}});
+        top.push_back({(int)k, ms, {c->buf[0], c->buf[1]}, pinned_split});
         c->buf[0] = c->buf[1] = nullptr;
         std::stable_sort(top.begin(), top.end(), [](const Kept& x, const Kept& y) { return x.ms < y.ms; });
         while (top.size() > keep) { for (void* q : top.back().buf) if (q) (void)hipFree(q); top.pop_back(); }
     }
-    std::string finalists;
+    std::string finalists, split_note;
     if (top.size() > 1) {
         for (Kept& t : top) {
             apply_plan(c, cand[(size_t)t.k]);
@@ -108,11 +127,28 @@ int choose_plan(lbm_ctx* c) {
             if (rc) { drop_all(); return rc; }
             std::sort(w, w + 3);
             t.ms = w[1];
+            t.split = pinned_split;
+            if (split_worth_trying(cand[(size_t)t.k])) {
+                c->buf[0] = t.buf[0]; c->buf[1] = t.buf[1];
+                for (int sp = 3; sp <= 4 && !rc; ++sp) {
+                    c->split = sp;
+                    for (int r = 0; r < 3 && !rc; ++r) rc = time_plan<T>(c, &w[r], window);
+                    std::sort(w, w + 3);
+                    char sb[48];
+                    snprintf(sb, sizeof(sb), "%s split %d %.2f", sp == 3 ? (split_note.empty() ? "" : ";") : ",", sp, w[1] * 1e3f);
+                    if (sp == 3) split_note += (split_note.empty() ? "" : "; ") + cand[(size_t)t.k].name.substr(cand[(size_t)t.k].name.find('/') + 1) + ":";
+                    split_note += sp == 3 ? sb + (sb[0] == ';' ? 1 : 0) : sb;
+                    if (!rc && w[1] < t.ms) { t.ms = w[1]; t.split = sp; }
+                }
+                c->split = 0;
+                c->buf[0] = c->buf[1] = nullptr;
+                if (rc) { drop_all(); return rc; }
+            }
         }
         std::stable_sort(top.begin(), top.end(), [](const Kept& x, const Kept& y) { return x.ms < y.ms; });
         for (const Kept& t : top) {
             char fb[160];
-            snprintf(fb, sizeof(fb), "%s%s %.2f", finalists.empty() ? "" : "; ", cand[(size_t)t.k].name.c_str(), t.ms * 1e3f);
+            snprintf(fb, sizeof(fb), "%s%s%s %.2f", finalists.empty() ? "" : "; ", cand[(size_t)t.k].name.c_str(), t.split == 3 ? "/split 3" : t.split == 4 ? "/split 4" : "", t.ms * 1e3f);
             finalists += fb;
         }
         while (top.size() > 1) { for (void* q : top.back().buf) if (q) (void)hipFree(q); top.pop_back(); }
@@ -124,13 +160,21 @@ int choose_plan(lbm_ctx* c) {
     c->buf[0] = best_buf[0]; c->buf[1] = best_buf[1];
     c->launches_total = 0;
     c->last_was_pair = false;
+    c->split = top[0].split;
+    {   // a context or a height that cannot run the ranges keeps the single launch (and says so: lbm_plan_options reports split only where it is in effect)
+        int cut[5];
+        if (c->split && !(split_possible(c) && split_ranges(c, deep_depth(c->deep), cut))) c->split = 0;
+    }
+    const std::string split_name = c->split ? "/split " + std::to_string(c->split) : std::string();
+    if (!split_note.empty()) finalists += "; the finalists as row-range launches on two streams:" + std::string(" ") + split_note;
     if (cand.size() > 1 && !finalists.empty())
-        snprintf(c->plan_desc, sizeof(c->plan_desc), "%s (fastest of %zu measured, %.1f us/iteration; finalists, median of three windows, us/iteration: %s)",
-                 cand[best].name.c_str(), cand.size(), best_ms * 1e3f, finalists.c_str());
-    else if (cand.size() > 1) snprintf(c->plan_desc, sizeof(c->plan_desc), "%s (fastest of %zu measured, %.1f us/iteration)",
-                                       cand[best].name.c_str(), cand.size(), best_ms * 1e3f);
-    else snprintf(c->plan_desc, sizeof(c->plan_desc), "%s", cand[best].name.c_str());
-    snprintf(c->plan_opts, sizeof(c->plan_opts), "%s", plan_option_string(c->layout, c->use_nt, c->alternate, c->pair_ty, c->xcd, c->fuse, c->deep, c->use_ntl).c_str());
+        snprintf(c->plan_desc, sizeof(c->plan_desc), "%s%s (fastest of %zu measured, %.1f us/iteration; finalists, median of three windows, us/iteration: %s)",
+                 cand[best].name.c_str(), split_name.c_str(), cand.size(), best_ms * 1e3f, finalists.c_str());
+    else if (cand.size() > 1) snprintf(c->plan_desc, sizeof(c->plan_desc), "%s%s (fastest of %zu measured, %.1f us/iteration)",
+                                       cand[best].name.c_str(), split_name.c_str(), cand.size(), best_ms * 1e3f);
+    else snprintf(c->plan_desc, sizeof(c->plan_desc), "%s%s", cand[best].name.c_str(), split_name.c_str());
+    snprintf(c->plan_opts, sizeof(c->plan_opts), "%s%s", plan_option_string(c->layout, c->use_nt, c->alternate, c->pair_ty, c->xcd, c->fuse, c->deep, c->use_ntl).c_str(),
+             c->split ? (" split=" + std::to_string(c->split)).c_str() : "");
     if (cand.size() > 1 && c->deep && !strips && best_ms > 0.f) {
         // What the shallow launches cost on THIS grid and allocation, for plan_launch's split of a segment's last iterations
         // (a single domain only: the strips of a run must all split alike, so they keep the fixed table).

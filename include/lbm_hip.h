@@ -245,6 +245,10 @@ int  lbm_last_step_kernel_ms(lbm_ctx* c, double* ms_per_launch);
 /* Same measurement, unreduced: device milliseconds of the last lbm_step call, the step-kernel launches it issued and
  * the iterations it advanced (a fused launch advances two to eight). */
 int  lbm_last_step_stats(lbm_ctx* c, double* ms_total, int* launches, int* iterations);
+/* The step kernels the launches of the last lbm_step call were dispatched as: `launches` of lbm_last_step_stats, except on a plan
+ * with option "split" 3 / 4, which issues a whole-domain deep launch as that many row-range kernels on two streams (a kernel trace or a
+ * counter pass sees the dispatches; timings and traffic stay per launch). No reference counterpart: the reference has no GPU path. */
+int  lbm_last_step_dispatches(const lbm_ctx* c);
 /* How many times a captured hipGraph of four launch groups has been replayed for this context so far (a strip with a device
  * transport on a deep plan replays its launch groups instead of issuing them call by call; option "graph" 0 turns that off;
  * 0 also where the capture was refused and the eager path runs). No reference counterpart: the reference has no GPU path. */
