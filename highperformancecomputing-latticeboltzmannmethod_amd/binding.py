@@ -53,6 +53,11 @@ def lib():
         L.lbm_drain_force_log.argtypes = [vp, C.POINTER(ForceRow), C.c_int]
         L.lbm_get_macros.argtypes = [vp, dp, dp, dp]
         L.lbm_max_velocity_sq.argtypes = [vp, dp]
+        L.lbm_stats_begin.argtypes = [vp, C.c_int]
+        L.lbm_stats_end.argtypes = [vp]
+        L.lbm_stats_samples.argtypes = [vp]
+        L.lbm_get_stat_sums.argtypes = [vp, dp]
+        L.lbm_stats_restore.argtypes = [vp, dp, C.c_int]
         L.lbm_get_populations.argtypes = [vp, C.c_int, dp]
         L.lbm_set_f_current.argtypes = [vp, dp]
         L.lbm_get_solid.argtypes = [vp, C.POINTER(C.c_ubyte)]
@@ -180,6 +185,16 @@ def _dp(a):
     return a.ctypes.data_as(C.POINTER(C.c_double)) if a is not None else None
 
 
+def _stats_from_sums(sums, n):
+    """The time averages of n samples from the six sums (rho, ux, uy, ux*ux, uy*uy, ux*uy): the means and the Reynolds stresses
+    <u'u'> = S_uu / n - mean(u)^2, <v'v'>, <u'v'> (host arithmetic on the caller's side of the interface: include/lbm_hip.h)."""
+    if n <= 0:
+        raise LbmError("no statistics sample has been taken yet")
+    rho, ux, uy = sums[0] / n, sums[1] / n, sums[2] / n
+    return {"n": n, "rho": rho, "ux": ux, "uy": uy,
+            "uxux": sums[3] / n - ux * ux, "uyuy": sums[4] / n - uy * uy, "uxuy": sums[5] / n - ux * uy}
+
+
 class Context:
     """One strip of the lattice on one GPU (struct lbm_ctx). solid: optional bool / uint8 (ny, nx) array of the WHOLE domain, row
     y = 0 first, nonzero = solid (lbm_set_solid_mask): the obstacle geometry in place of the cylinder_* disc. inlet_profile: optional
@@ -290,6 +305,35 @@ class Context:
         v = C.c_double()
         self._chk(self.L.lbm_max_velocity_sq(self.h, C.byref(v)))
         return v.value
+
+    # ---- time-averaged statistics (lbm_stats_*): sampled on the device at the force-output iterations of step(n, output_frequency) ----
+    def stats_begin(self, from_step=0):
+        """Zeroes the six running sums and the sample count and samples every force-output iteration t >= from_step from now on."""
+        self._chk(self.L.lbm_stats_begin(self.h, int(from_step)))
+
+    def stats_end(self):
+        """Stops sampling; the sums stay."""
+        self._chk(self.L.lbm_stats_end(self.h))
+
+    def stats_samples(self):
+        return self._chk(self.L.lbm_stats_samples(self.h))
+
+    def stats_sums(self):
+        """(6, local_ny, nx) float64: sum of rho, ux, uy, ux*ux, uy*uy, ux*uy over the samples."""
+        s = np.empty((6, self.local_ny, self.nx), dtype=np.float64)
+        self._chk(self.L.lbm_get_stat_sums(self.h, _dp(s)))
+        return s
+
+    def stats_restore(self, sums, samples):
+        """Uploads sums and a sample count saved earlier (a run resumed with load_state continues its averages)."""
+        a = np.ascontiguousarray(sums, dtype=np.float64)
+        if a.shape != (6, self.local_ny, self.nx):
+            raise ValueError(f"statistics sums have shape {a.shape}, this strip needs {(6, self.local_ny, self.nx)}")
+        self._chk(self.L.lbm_stats_restore(self.h, _dp(a), int(samples)))
+
+    def stats(self):
+        """{'n', 'rho', 'ux', 'uy' (means), 'uxux', 'uyuy', 'uxuy' (Reynolds stresses)} of the samples so far."""
+        return _stats_from_sums(self.stats_sums(), self.stats_samples())
 
     def populations(self, which):
         """which: 'f_current' | 'f_next' -> [(local_ny+2), (nx+2), 9] like Grid::f_current(gx,gy,i)."""
@@ -431,6 +475,35 @@ class Group:
         """(rho, ux, uy) of the whole lattice: the strips' rows concatenated by y_start (LBMSolver.h:340-357)."""
         parts = [c.macros() for c in self.ctxs]
         return tuple(np.concatenate([p[j] for p in parts], axis=0) for j in range(3))
+
+    # ---- time-averaged statistics: member by member, rows concatenated by y_start like macros() ----
+    def stats_begin(self, from_step=0):
+        for c in self.ctxs:
+            c.stats_begin(from_step)
+
+    def stats_end(self):
+        for c in self.ctxs:
+            c.stats_end()
+
+    def stats_samples(self):
+        n = {c.stats_samples() for c in self.ctxs}
+        if len(n) != 1:
+            raise LbmError(f"the strips of the group disagree on the number of statistics samples: {sorted(n)}")
+        return n.pop()
+
+    def stats_sums(self):
+        """(6, ny, nx): the strips' sums concatenated by y_start."""
+        return np.concatenate([c.stats_sums() for c in self.ctxs], axis=1)
+
+    def stats_restore(self, sums, samples):
+        a = np.asarray(sums, dtype=np.float64)
+        if a.shape != (6, self.ny, self.nx):
+            raise ValueError(f"statistics sums have shape {a.shape}, the lattice needs {(6, self.ny, self.nx)}")
+        for c in self.ctxs:
+            c.stats_restore(a[:, c.y_start:c.y_start + c.local_ny], samples)
+
+    def stats(self):
+        return _stats_from_sums(self.stats_sums(), self.stats_samples())
 
     def populations(self, which):
         """Ghost-inclusive [(ny+2), (nx+2), 9]: interior rows of every strip + the physical ghost rows of the end strips."""

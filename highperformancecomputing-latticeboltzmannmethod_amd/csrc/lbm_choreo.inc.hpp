@@ -27,6 +27,8 @@ struct ChoreoChecker {
     std::vector<std::vector<int>> reader_op[2];
     std::vector<std::vector<unsigned>> vc;            // per stream
     std::vector<std::vector<unsigned>> evc;           // per (strip, event): the clock its last record snapshot; empty = never recorded
+    std::vector<RowState> acc;                        // per strip: the last writer of the statistics accumulators (one unit: every sample writes all of them)
+    static constexpr int ACC_BUF = 2;                 // the "buffer" a violation on the accumulators names
     std::vector<ChoreoViolation> bad;
 
     void init(lbm_ctx** cs, int n) {
@@ -34,6 +36,7 @@ struct ChoreoChecker {
         nyl.resize((size_t)n);
         vc.assign((size_t)nstreams, std::vector<unsigned>((size_t)nstreams, 0u));
         evc.assign((size_t)3 * n, std::vector<unsigned>());
+        acc.assign((size_t)n, RowState());
         for (int b = 0; b < 2; ++b) { rows[b].resize((size_t)n); readers[b].resize((size_t)n); reader_op[b].resize((size_t)n); }
         for (int k = 0; k < n; ++k) {
             const lbm_ctx* c = cs[k];
@@ -132,7 +135,13 @@ struct ChoreoChecker {
                     }
                     break;
                 case ChoreoOp::FORCES:
+                case ChoreoOp::STATS:
                     for (int y = o.r0; y < o.r1; ++y) { read_row(idx, s, o.strip, o.buf, y); need_level(idx, o.strip, o.buf, y, o.t); }
+                    if (o.kind == ChoreoOp::STATS) {      // a read-modify-write of the strip's accumulators: ordered behind the sample before it
+                        RowState& a = acc[(size_t)o.strip];
+                        if (!hb(a.w_stream, a.w_seq, s)) race(a.w_op, idx, o.strip, ACC_BUF, 0);
+                        a.w_stream = s; a.w_seq = me[(size_t)s]; a.w_op = idx;
+                    }
                     break;
                 default: break;
             }
@@ -141,7 +150,7 @@ struct ChoreoChecker {
 };
 
 inline std::string choreo_op_text(const ChoreoOp& o, int idx) {
-    static const char* kinds[] = {"kernel", "record", "wait", "copy", "send", "recv", "forces"};
+    static const char* kinds[] = {"kernel", "record", "wait", "copy", "send", "recv", "forces", "stats"};
     static const char* evs[] = {"ev_main", "ev_edge", "ev_comm"};
     char b[256];
     int n = snprintf(b, sizeof(b), "#%d strip %d %s stream: %s", idx, o.strip, o.stream ? "side" : "main", kinds[o.kind]);
@@ -152,7 +161,8 @@ inline std::string choreo_op_text(const ChoreoOp& o, int idx) {
     else if (o.kind == ChoreoOp::COPY) n += snprintf(b + n, sizeof(b) - n, " buf %d: rows [%d,%d) of strip %d -> rows [%d,%d)", o.buf, o.r0, o.r1, o.r_strip, o.w0[0], o.w1[0]);
     else if (o.kind == ChoreoOp::SEND) n += snprintf(b + n, sizeof(b) - n, " buf %d rows [%d,%d)", o.buf, o.r0, o.r1);
     else if (o.kind == ChoreoOp::RECV) n += snprintf(b + n, sizeof(b) - n, " buf %d rows [%d,%d)", o.buf, o.w0[0], o.w1[0]);
-    else if (o.kind == ChoreoOp::FORCES) n += snprintf(b + n, sizeof(b) - n, " t=%d reads buf %d rows [%d,%d)", o.t, o.buf, o.r0, o.r1);
+    else if (o.kind == ChoreoOp::FORCES || o.kind == ChoreoOp::STATS)
+        n += snprintf(b + n, sizeof(b) - n, " t=%d reads buf %d rows [%d,%d)%s", o.t, o.buf, o.r0, o.r1, o.kind == ChoreoOp::STATS ? ", writes the accumulators" : "");
     return b;
 }
 

@@ -196,14 +196,15 @@ struct GroupPool {
 // clocks and reports every pair of conflicting accesses that no event orders, and every launch that reads a row of the wrong
 // iteration: the class of round 4's edge-band race (a band shorter than the rows that travel), found then by a 1-in-15 flake.
 struct ChoreoOp {
-    enum { KERNEL = 0, RECORD = 1, WAIT = 2, COPY = 3, SEND = 4, RECV = 5, FORCES = 6 };
+    enum { KERNEL = 0, RECORD = 1, WAIT = 2, COPY = 3, SEND = 4, RECV = 5, FORCES = 6, STATS = 7 };
     int kind = 0;
     int strip = 0, stream = 0;      // the issuing strip, 0 main / 1 side stream
     int ev_strip = 0, ev = 0;       // RECORD / WAIT: the event's owner and 0 ev_main, 1 ev_edge, 2 ev_comm
     int buf = 0;                    // KERNEL: the buffer written (it reads buf ^ 1); COPY / SEND / RECV / FORCES: the buffer touched
-    int t = 0, depth = 0;           // KERNEL: first iteration and iterations; FORCES: the iteration
+    int t = 0, depth = 0;           // KERNEL: first iteration and iterations; FORCES / STATS: the iteration
     int w0[2] = {0, 0}, w1[2] = {0, 0};   // rows written, [w0, w1) in local rows (ghost rows: < 0 or >= nyl); KERNEL: two ranges
-    int r0 = 0, r1 = 0, r_strip = -1;     // COPY / SEND / FORCES: rows read and whose (RECV: where the data comes from; -1: another process)
+    int r0 = 0, r1 = 0, r_strip = -1;     // COPY / SEND / FORCES / STATS: rows read and whose (RECV: where the data comes from; -1: another process)
+                                          // (STATS: the strip's rows and ONE ghost row per face — the pull of the inlet / outlet cells of its first and last row)
 };
 // ... and, for one rank of a multi-process run, the transcript of what exchange_rccl's posting loops WOULD hand to RCCL, in posting order:
 // kind 0 send / 1 recv / 2 end of a group call; `off`, `cnt` in elements of the buffer. lbm_debug_p2p_matching holds the transcripts of
@@ -229,6 +230,12 @@ struct lbm_ctx {
     void* scratch = nullptr; // f_current snapshot (lazy)
     double* d_macro = nullptr;   // rho | ux | uy (lazy), each nx*nyl
     unsigned long long* d_maxbits = nullptr;
+    // Time-averaged statistics (lbm_stats_begin): six running sums per cell, [6][nyl][nx] doubles (48 B per cell: allocated when statistics
+    // are begun), to which k_stats adds the snapshot of iteration t at every force-output iteration t >= stats_from of a call.
+    double* d_stats = nullptr;
+    bool stats_active = false;
+    int stats_from = 0, stats_n = 0;     // first iteration sampled; samples accumulated so far
+    int stats_opt = -1;                  // option "stats" set before lbm_initialise: begun at its end
     int* d_unstable = nullptr;
     int* d_solid_count = nullptr;
     void* d_feq = nullptr;          // the nine initial-equilibrium values in the element type (fused kernels)

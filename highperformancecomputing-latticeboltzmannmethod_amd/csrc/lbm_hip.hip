@@ -262,7 +262,7 @@ void lbm_destroy(lbm_ctx* c) {
     c->pool.reset();
     void* ptrs[] = {c->buf[0], c->buf[1], c->scratch, c->d_macro, c->d_maxbits, c->d_unstable, c->d_tbase, c->d_solid_count, c->d_feq,
                     c->d_force_now, c->d_force_log, c->d_halo, c->d_red, (void*)c->mview.bits, (void*)c->mview.sat, c->d_fpart,
-                    c->d_urow, c->d_feqrow};
+                    c->d_urow, c->d_feqrow, c->d_stats};
     for (void* q : ptrs)
         if (q) (void)hipFree(q);
     hipEvent_t evs[] = {c->ev_edge, c->ev_comm, c->ev_main, c->ev_t0, c->ev_t1, c->gev_main, c->gev_edge, c->gev_comm};
@@ -301,6 +301,7 @@ int lbm_initialise(lbm_ctx* c, int* solid_count_out) {
     if (solid_count_out) *solid_count_out = sc;
     c->initialised = true;
     lbm_trace("initialise", "ctx %p end: %s", (void*)c, c->plan_desc);
+    if (c->stats_opt >= 0) return lbm_stats_begin(c, c->stats_opt);      // option "stats" (the plan was measured without it)
     return LBM_OK;
 }
 
@@ -397,6 +398,63 @@ int lbm_max_velocity_sq(lbm_ctx* c, double* out) {
     HIPCHK(hipMemcpyAsync(&bits, c->d_maxbits, sizeof(bits), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     memcpy(out, &bits, sizeof(double));
+    return LBM_OK;
+}
+
+/* ---- time-averaged statistics: six running sums per cell, sampled at the force-output iterations of lbm_step (k_stats) ---- */
+static size_t stats_bytes(const lbm_ctx* c) { return 6 * (size_t)c->nx * c->nyl * sizeof(double); }
+// everything queued so far precedes a change of the accumulators made on the compute stream
+static int stats_zero(lbm_ctx* c) {
+    { int jr = join_comm(c); if (jr) return jr; }
+    HIPCHK(hipMemsetAsync(c->d_stats, 0, stats_bytes(c), c->stream));
+    c->stats_n = 0;
+    return LBM_OK;
+}
+
+int lbm_stats_begin(lbm_ctx* c, int from_step) {
+    if (!c || !c->initialised) return fail(LBM_ERR_ARG, "lbm_stats_begin needs an initialised context");
+    if (from_step < 0) return fail(LBM_ERR_ARG, "from_step < 0");
+    HIPCHK(hipSetDevice(c->device));
+    if (!c->d_stats && hipMalloc(&c->d_stats, stats_bytes(c)) != hipSuccess) {
+        (void)hipGetLastError();
+        c->d_stats = nullptr;
+        return fail(LBM_ERR_ALLOC, "statistics: no device memory for %zu bytes of accumulators", stats_bytes(c));
+    }
+    int rc = stats_zero(c);
+    if (rc) return rc;
+    c->stats_from = from_step;
+    c->stats_active = true;
+    return LBM_OK;
+}
+
+int lbm_stats_end(lbm_ctx* c) {
+    if (!c) return fail(LBM_ERR_ARG, "null context");
+    c->stats_active = false;
+    return LBM_OK;
+}
+
+int lbm_stats_samples(const lbm_ctx* c) { return c ? c->stats_n : LBM_ERR_ARG; }
+
+int lbm_get_stat_sums(lbm_ctx* c, double* sums6) {
+    if (!c || !sums6) return fail(LBM_ERR_ARG, "null argument");
+    if (!c->d_stats) return fail(LBM_ERR_ARG, "statistics were never begun (lbm_stats_begin)");
+    HIPCHK(hipSetDevice(c->device));
+    { int jr = join_comm(c); if (jr) return jr; }
+    HIPCHK(hipMemcpyAsync(sums6, c->d_stats, stats_bytes(c), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return LBM_OK;
+}
+
+int lbm_stats_restore(lbm_ctx* c, const double* sums6, int samples) {
+    if (!c || !c->initialised || !sums6) return fail(LBM_ERR_ARG, "lbm_stats_restore needs an initialised context and the sums");
+    if (samples < 0) return fail(LBM_ERR_ARG, "samples < 0");
+    if (!c->d_stats) { int rc = lbm_stats_begin(c, 0); if (rc) return rc; }
+    HIPCHK(hipSetDevice(c->device));
+    { int jr = join_comm(c); if (jr) return jr; }
+    HIPCHK(hipMemcpyAsync(c->d_stats, sums6, stats_bytes(c), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));       // (the caller's array is free again)
+    c->stats_n = samples;
+    c->stats_active = true;
     return LBM_OK;
 }
 
@@ -793,6 +851,11 @@ int lbm_set_option(lbm_ctx* c, const char* key, long value) {
         if (value != 0 && value != 3 && value != 4) return fail(LBM_ERR_ARG, "split must be 0, 3 or 4");
         c->split = (int)value; c->split_pinned = true;      // (between calls nothing is in flight on the second stream: do_steps joins it)
     }
+    else if (k == "stats") {    // statistics from this step on: lbm_stats_begin now, or — not yet initialised — at the end of lbm_initialise
+        if (value < 0) return fail(LBM_ERR_ARG, "stats (the first step sampled) must be >= 0");
+        if (c->initialised) return lbm_stats_begin(c, (int)value);
+        c->stats_opt = (int)value;
+    }
     else if (k == "graph") { if (value < 0 || value > 2) return fail(LBM_ERR_ARG, "graph must be 0, 1 or 2"); c->use_graph = (int)value; }
     else if (k == "loopback") c->loopback = (int)value;   // 0 off, 1 device copies, 2 RCCL self send/recv
     else if (k == "pair_ty") { if (value != 8 && value != 12) return fail(LBM_ERR_ARG, "pair_ty must be 8 or 12"); c->pair_ty = (int)value; }
@@ -992,6 +1055,7 @@ int lbm_debug_choreography(int nx, int ny, const int* bounds2, int nstrips, int 
         } else if (transport == 3) c->loopback = 1;
         c->initialised = true;
         c->cur = 1;
+        if (c->stats_opt >= 0) { c->stats_active = true; c->stats_from = c->stats_opt; }      // (no accumulators: nothing is launched)
     }
     if (transport < 2) {
         for (int k = 0; k < nstrips; ++k) {

@@ -1009,39 +1009,56 @@ struct MacroArgs {
     unsigned long long* max_usq_bits;      // optional running max of ux^2+uy^2 (bit pattern of a double >= 0)
 };
 
+// the moments of the nine populations of a fluid cell, in the element type: rho and u = (sum c_i f_i) / rho (one definition for
+// k_macros and k_stats: the two must agree to the bit)
+template <typename T>
+__device__ __forceinline__ void macro_moments(const T (&f)[Q], double& r, double& vx, double& vy) {
+    T rr = T(0), sx = T(0), sy = T(0);
+#pragma unroll
+    for (int i = 0; i < Q; ++i) {
+        const T v = f[i];
+        rr += v;
+        if (cx(i) != 0) sx += T(cx(i)) * v;
+        if (cy(i) != 0) sy += T(cy(i)) * v;
+    }
+    sx /= rr; sy /= rr;
+    r = (double)rr; vx = (double)sx; vy = (double)sy;
+}
+
+// (rho, ux, uy) of cell (x, local row y) as the snapshot defines them above. The one definition of the snapshot: k_macros writes it
+// out, k_stats adds it to the running sums.
+template <typename T>
+__device__ __forceinline__ void macro_cell(const MacroArgs<T>& p, int x, int y, double& r, double& vx, double& vy) {
+    const int yg = p.y_start + y;
+    const long c = (long)(y + GR) * p.pitch + p.xoff + x;
+    const bool solid = solid_at(p, x, yg);
+    if (solid) { r = 1.0; vx = 0.0; vy = 0.0; }
+    else if (p.initial) { r = 1.0; vx = (double)p.u_row[yg]; vy = 0.0; }
+    else if (x == 0 || x == p.nx - 1) {
+        T f[Q];
+#pragma unroll
+        for (int i = 0; i < Q; ++i) f[i] = p.old[(long)i * p.plane + c - (long)cy(i) * p.pitch - cx(i)];
+        T rho_bc = T(1), u_out = T(0);
+        apply_bcs(f, yg == 0, yg == p.ny_glob - 1, x == 0, x == p.nx - 1, p.u_row, yg, rho_bc, u_out);
+        // the outlet loop runs after the inlet loop (only matters for nx == 1)
+        if (x == p.nx - 1) { r = 1.0; vx = (double)u_out; vy = 0.0; }
+        else { r = (double)rho_bc; vx = (double)p.u_row[yg]; vy = 0.0; }
+    } else {
+        T f[Q];
+#pragma unroll
+        for (int i = 0; i < Q; ++i) f[i] = p.old[(long)i * p.plane + c];
+        macro_moments<T>(f, r, vx, vy);
+    }
+}
+
 template <typename T>
 __global__ void __launch_bounds__(256) k_macros(const MacroArgs<T> p) {
     const int x = blockIdx.x * 256 + threadIdx.x;
     const int y = blockIdx.y;
     double usq = 0.0;
     if (x < p.nx) {
-        const int yg = p.y_start + y;
-        const long c = (long)(y + GR) * p.pitch + p.xoff + x;
-        const bool solid = solid_at(p, x, yg);
         double r, vx, vy;
-        if (solid) { r = 1.0; vx = 0.0; vy = 0.0; }
-        else if (p.initial) { r = 1.0; vx = (double)p.u_row[yg]; vy = 0.0; }
-        else if (x == 0 || x == p.nx - 1) {
-            T f[Q];
-#pragma unroll
-            for (int i = 0; i < Q; ++i) f[i] = p.old[(long)i * p.plane + c - (long)cy(i) * p.pitch - cx(i)];
-            T rho_bc = T(1), u_out = T(0);
-            apply_bcs(f, yg == 0, yg == p.ny_glob - 1, x == 0, x == p.nx - 1, p.u_row, yg, rho_bc, u_out);
-            // the outlet loop runs after the inlet loop (only matters for nx == 1)
-            if (x == p.nx - 1) { r = 1.0; vx = (double)u_out; vy = 0.0; }
-            else { r = (double)rho_bc; vx = (double)p.u_row[yg]; vy = 0.0; }
-        } else {
-            T rr = T(0), sx = T(0), sy = T(0);
-#pragma unroll
-            for (int i = 0; i < Q; ++i) {
-                const T v = p.old[(long)i * p.plane + c];
-                rr += v;
-                if (cx(i) != 0) sx += T(cx(i)) * v;
-                if (cy(i) != 0) sy += T(cy(i)) * v;
-            }
-            sx /= rr; sy /= rr;
-            r = (double)rr; vx = (double)sx; vy = (double)sy;
-        }
+        macro_cell<T>(p, x, y, r, vx, vy);
         const long m = (long)y * p.nx + x;
         p.rho[m] = r; p.ux[m] = vx; p.uy[m] = vy;
         usq = vx * vx + vy * vy;
@@ -1050,6 +1067,79 @@ __global__ void __launch_bounds__(256) k_macros(const MacroArgs<T> p) {
         // wave max, then one atomic per wave; non-negative doubles order like their bit patterns
         for (int o = 32; o > 0; o >>= 1) usq = fmax(usq, __shfl_xor(usq, o));
         if ((threadIdx.x & 63) == 0) atomicMax(p.max_usq_bits, (unsigned long long)__double_as_longlong(usq));
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Time-averaged statistics (lbm_stats_begin; the reference has none): one SAMPLE adds the snapshot macro_cell defines — taken from
+// P_t, the buffer the sampling point finds in buf[cur] — to six running sums per cell, always in double:
+//   acc[0..5][ny_loc][nx] = sum rho | sum ux | sum uy | sum ux*ux | sum uy*uy | sum ux*uy      (the layout of d_macro, six planes)
+// Every sum is S = S + v in sample order, every product rounded to double before it is added (no contraction in this kernel), so the
+// sums equal a host loop `S += ux*ux` over the snapshots bit for bit; means and Reynolds stresses are formed by the caller.
+// A pure streaming kernel: 9 sizeof(T) bytes of populations read and 96 bytes of accumulators read and written per cell. A thread
+// owns two adjacent cells of a row — one 16-byte access per lane and accumulator plane, 16 (fp64) / 8 (fp32) bytes per lane and
+// population plane — and a block of 256 threads (four waves) 512 cells. The pull + wall + Zou-He path of the inlet and outlet columns
+// is taken by the two lanes of a row that own them (and by a lattice whose width is odd, where the pairs are not 16-byte aligned);
+// every other lane runs the vector path. The accumulators are stored with plain stores: non-temporal 16-byte stores were measured
+// and are 1-2 % slower at both 4096x1024 fp64 and 16384x4096 fp32 (profiles/stats/README.md).
+template <typename T>
+struct StatsArgs {
+    MacroArgs<T> m;     // the snapshot's source: old = P_t, initial = 0; rho / ux / uy / max_usq_bits unused
+    double* acc;        // [6][ny_loc][nx]
+    long cells;         // nx * ny_loc: the plane stride of acc
+};
+
+template <typename T> struct Pair2;
+template <> struct Pair2<double> { typedef double2 type; };
+template <> struct Pair2<float> { typedef float2 type; };
+
+template <typename T>
+__global__ void __launch_bounds__(256) k_stats(const StatsArgs<T> p) {
+#pragma clang fp contract(off)
+    const MacroArgs<T>& a = p.m;
+    const int x0 = 2 * (blockIdx.x * 256 + threadIdx.x);
+    const int y = blockIdx.y;
+    if (x0 >= a.nx) return;
+    double r[2], vx[2], vy[2];
+    const bool vec = (a.nx & 1) == 0;       // (uniform) pairs start at even cells of an even-width row: 16-byte aligned
+    if (!vec || x0 == 0 || x0 + 2 >= a.nx) {
+        macro_cell<T>(a, x0, y, r[0], vx[0], vy[0]);
+        if (x0 + 1 < a.nx) macro_cell<T>(a, x0 + 1, y, r[1], vx[1], vy[1]);
+        else { r[1] = 0.0; vx[1] = 0.0; vy[1] = 0.0; }
+    } else {
+        typedef typename Pair2<T>::type T2;
+        const long c = (long)(y + GR) * a.pitch + a.xoff + x0;
+        T f0[Q], f1[Q];
+#pragma unroll
+        for (int i = 0; i < Q; ++i) {
+            const T2 v = *reinterpret_cast<const T2*>(a.old + (long)i * a.plane + c);
+            f0[i] = v.x; f1[i] = v.y;
+        }
+        macro_moments<T>(f0, r[0], vx[0], vy[0]);
+        macro_moments<T>(f1, r[1], vx[1], vy[1]);
+        const int yg = a.y_start + y;
+        if (solid_at(a, x0, yg)) { r[0] = 1.0; vx[0] = 0.0; vy[0] = 0.0; }
+        if (solid_at(a, x0 + 1, yg)) { r[1] = 1.0; vx[1] = 0.0; vy[1] = 0.0; }
+    }
+    const long m = (long)y * a.nx + x0;
+    double v0[6] = {r[0], vx[0], vy[0], vx[0] * vx[0], vy[0] * vy[0], vx[0] * vy[0]};
+    double v1[6] = {r[1], vx[1], vy[1], vx[1] * vx[1], vy[1] * vy[1], vx[1] * vy[1]};
+    if (vec) {
+        double2 s[6];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) s[k] = *reinterpret_cast<const double2*>(p.acc + (long)k * p.cells + m);
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+            s[k].x = s[k].x + v0[k]; s[k].y = s[k].y + v1[k];
+            *reinterpret_cast<double2*>(p.acc + (long)k * p.cells + m) = s[k];
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+            double* q = p.acc + (long)k * p.cells + m;
+            q[0] = q[0] + v0[k];
+            if (x0 + 1 < a.nx) q[1] = q[1] + v1[k];
+        }
     }
 }
 

@@ -122,6 +122,43 @@ int launch_step(lbm_ctx* c, int src, int dst, int t, int mode, hipStream_t s) {
     return LBM_OK;
 }
 
+// The snapshot's source as k_macros and k_stats take it: the lattice, the geometry and the inlet profile of this strip, read from
+// `src`. One fill for both launches (do_macros, launch_stats), so that the two snapshots cannot differ in their arguments either.
+// initial = 0 and no outputs: the caller sets what it needs.
+template <typename T>
+MacroArgs<T> make_macro_args(const lbm_ctx* c, const void* src) {
+    MacroArgs<T> m;
+    m.old = static_cast<const T*>(src);
+    m.plane = (long)c->plane; m.pitch = c->pitch; m.xoff = c->xoff;
+    m.nx = c->nx; m.ny_loc = c->nyl; m.ny_glob = c->p.ny; m.y_start = c->p.y_start;
+    m.cyl_x = c->cyl_x; m.cyl_y = c->cyl_y; m.cyl_r2 = (double)(c->cyl_r * c->cyl_r);
+    if (c->has_mask) m.mv = c->mview;
+    m.u_row = static_cast<const T*>(c->d_urow);
+    m.initial = 0;
+    m.rho = m.ux = m.uy = nullptr; m.max_usq_bits = nullptr;
+    return m;
+}
+
+// One sample of the running statistics (k_stats) at a force-output iteration t: buf[cur] = P_t. The snapshot it adds is the one
+// do_macros takes from buf[cur ^ 1] once steps_done == t + 1. Queued on the compute stream behind join_comm, like the force kernel.
+template <typename T>
+int launch_stats(lbm_ctx* c, int t) {
+    if (c->rec) {      // dry run: reads the strip's rows of P_t and, on the inlet / outlet columns, one ghost row per face; writes the accumulators
+        ChoreoOp o; o.kind = ChoreoOp::STATS; o.strip = c->group_k; o.stream = 0; o.buf = c->cur; o.t = t; o.r0 = -1; o.r1 = c->nyl + 1; o.r_strip = c->group_k;
+        c->rec->ops.push_back(o);
+        c->stats_n++;
+        return LBM_OK;
+    }
+    StatsArgs<T> s;
+    s.m = make_macro_args<T>(c, c->buf[c->cur]);
+    s.acc = c->d_stats; s.cells = (long)c->nx * c->nyl;
+    dim3 grid((c->nx + 511) / 512, c->nyl), block(256);
+    hipLaunchKernelGGL((k_stats<T>), grid, block, 0, c->stream, s);
+    HIPCHK(hipGetLastError());
+    c->stats_n++;
+    return LBM_OK;
+}
+
 template <typename T>
 int launch_forces(lbm_ctx* c, double* out, int t) {
     if (c->rec) {      // dry run: the force kernel reads this strip's rows of P_t on the compute stream

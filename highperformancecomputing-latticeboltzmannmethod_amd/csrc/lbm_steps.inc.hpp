@@ -161,6 +161,7 @@ int do_steps(lbm_ctx** cs, int n, int nsteps, int of) {
                     if (!rc) rc = join_comm(c);
                     if (!rc) rc = launch_forces<T>(c, c->d_force_log + 3L * c->log_count, t);
                     if (!rc) c->log_count++;
+                    if (!rc && c->stats_active && t >= c->stats_from) rc = launch_stats<T>(c, t);
                 }
                 if (!rc) rc = plan_launch(c, nsteps - k, of, transport, true, &L[(size_t)i]);
                 if (!rc) rc = issue_before<T>(c, L[(size_t)i]);
@@ -206,6 +207,10 @@ int do_steps(lbm_ctx** cs, int n, int nsteps, int of) {
                 rc = launch_forces<T>(c, c->d_force_log + 3L * c->log_count, t);
                 if (rc) return rc;
                 c->log_count++;
+                if (c->stats_active && t >= c->stats_from) {      // the sample of iteration t: behind the same join, on the same stream
+                    rc = launch_stats<T>(c, t);
+                    if (rc) return rc;
+                }
             }
             int rc = plan_launch(c, nsteps - k, of, transport, true, &L[i]);
             if (rc) return rc;
@@ -274,13 +279,7 @@ template <typename T>
 int do_macros(lbm_ctx* c, bool want_max) {
     const size_t n = (size_t)c->nx * c->nyl;
     if (!c->d_macro) HIPCHK(hipMalloc(&c->d_macro, 3 * n * sizeof(double)));
-    MacroArgs<T> m;
-    m.old = static_cast<const T*>(c->buf[c->cur ^ 1]);
-    m.plane = (long)c->plane; m.pitch = c->pitch; m.xoff = c->xoff;
-    m.nx = c->nx; m.ny_loc = c->nyl; m.ny_glob = c->p.ny; m.y_start = c->p.y_start;
-    m.cyl_x = c->cyl_x; m.cyl_y = c->cyl_y; m.cyl_r2 = (double)(c->cyl_r * c->cyl_r);
-    if (c->has_mask) m.mv = c->mview;
-    m.u_row = static_cast<const T*>(c->d_urow);
+    MacroArgs<T> m = make_macro_args<T>(c, c->buf[c->cur ^ 1]);
     m.initial = (c->steps_done == 0);
     m.rho = c->d_macro; m.ux = c->d_macro + n; m.uy = c->d_macro + 2 * n;
     m.max_usq_bits = want_max ? c->d_maxbits : nullptr;

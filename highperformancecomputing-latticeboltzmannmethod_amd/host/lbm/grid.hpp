@@ -14,6 +14,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
+#include <cstring>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -182,6 +183,63 @@ public:
         for (size_t k = 0; k < ctx_.size(); ++k) check(lbm_load_state(ctx_[k], strip_file(path, k).c_str()), "lbm_load_state");
         check(lbm_group_refresh_halos(ctx_.data(), (int)ctx_.size()), "lbm_group_refresh_halos");
         invalidate();
+    }
+    // time-averaged statistics (lbm_stats_*; the reference has none): begun on every strip, the six sums gathered like the macroscopic
+    // fields (rows concatenated by y_start) into [6][ny][nx]; the sample count is the same on every strip
+    void stats_begin(int from_step) {
+        for (lbm_ctx* c : ctx_) check(lbm_stats_begin(c, from_step), "lbm_stats_begin");
+    }
+    int stats_samples() const {
+        const int n = lbm_stats_samples(ctx_[0]);
+        for (lbm_ctx* c : ctx_)
+            if (lbm_stats_samples(c) != n) throw std::runtime_error("the strips disagree on the number of statistics samples");
+        return n;
+    }
+    std::vector<double> stat_sums() const {
+        const size_t n = static_cast<size_t>(nx_) * ny_;
+        std::vector<double> all(6 * n), part;
+        for (size_t k = 0; k < ctx_.size(); ++k) {
+            const size_t m = static_cast<size_t>(nx_) * nyl_[k];
+            part.resize(6 * m);
+            check(lbm_get_stat_sums(ctx_[k], part.data()), "lbm_get_stat_sums");
+            for (int j = 0; j < 6; ++j) std::copy(part.begin() + j * m, part.begin() + (j + 1) * m, all.begin() + j * n + static_cast<size_t>(y0_[k]) * nx_);
+        }
+        return all;
+    }
+    void stats_restore(const std::vector<double>& all, int samples) {
+        const size_t n = static_cast<size_t>(nx_) * ny_;
+        if (all.size() != 6 * n) throw std::runtime_error("statistics of a different lattice");
+        std::vector<double> part;
+        for (size_t k = 0; k < ctx_.size(); ++k) {
+            const size_t m = static_cast<size_t>(nx_) * nyl_[k];
+            part.resize(6 * m);
+            for (int j = 0; j < 6; ++j) std::copy(all.begin() + j * n + static_cast<size_t>(y0_[k]) * nx_, all.begin() + j * n + static_cast<size_t>(y0_[k]) * nx_ + m, part.begin() + j * m);
+            check(lbm_stats_restore(ctx_[k], part.data(), samples), "lbm_stats_restore");
+        }
+    }
+    // the sums beside a checkpoint (checkpoints do not carry them): "LBMSTAT1", nx, ny, samples, then [6][ny][nx] doubles of the
+    // whole lattice, whatever the strips. load_stats: false when the file does not exist (the averages start afresh).
+    void save_stats(const std::string& path) const {
+        const std::vector<double> all = stat_sums();
+        const int head[3] = {nx_, ny_, stats_samples()};
+        std::FILE* fp = std::fopen(path.c_str(), "wb");
+        const bool ok = fp && std::fwrite("LBMSTAT1", 1, 8, fp) == 8 && std::fwrite(head, sizeof(int), 3, fp) == 3 &&
+                        std::fwrite(all.data(), sizeof(double), all.size(), fp) == all.size();
+        if (fp) std::fclose(fp);
+        if (!ok) throw std::runtime_error("cannot write " + path);
+    }
+    bool load_stats(const std::string& path) {
+        std::FILE* fp = std::fopen(path.c_str(), "rb");
+        if (!fp) return false;
+        char magic[8];
+        int head[3] = {0, 0, 0};
+        std::vector<double> all(6 * static_cast<size_t>(nx_) * ny_);
+        const bool ok = std::fread(magic, 1, 8, fp) == 8 && std::memcmp(magic, "LBMSTAT1", 8) == 0 && std::fread(head, sizeof(int), 3, fp) == 3 &&
+                        head[0] == nx_ && head[1] == ny_ && head[2] >= 0 && std::fread(all.data(), sizeof(double), all.size(), fp) == all.size();
+        std::fclose(fp);
+        if (!ok) throw std::runtime_error(path + " does not hold the statistics of this lattice");
+        stats_restore(all, head[2]);
+        return true;
     }
     const char* plan() const { return lbm_plan(ctx_[0]); }
     lbm_ctx* handle(int k = 0) const { return ctx_[(size_t)k]; }

@@ -124,6 +124,48 @@ public:
         std::printf("Files written: velocity_field.csv, simulation_params.csv, forces.csv\n");
         std::fflush(stdout);
     }
+    // The time averages of a run with statistics (lbm_solver --stats-start; the reference has none): the means and the Reynolds
+    // stresses <u'u'> = S_uu / n - mean(u)^2, ... formed from the six sums ([6][ny][nx]: rho, ux, uy, ux*ux, uy*uy, ux*uy) and the
+    // sample count. mean_fields.vtk in the layout of write_vtk_timestep, mean_fields.csv in that of velocity_field.csv.
+    static void write_mean_fields(const std::vector<double>& sums, int samples, const SimulationParams& p) {
+        if (samples <= 0) { std::fprintf(stderr, "Statistics: no sample was taken (first step %d); mean_fields not written\n", p.stats_start); return; }
+        const size_t n = static_cast<size_t>(p.nx) * p.ny;
+        const double inv = 1.0 / samples;
+        std::vector<double> f[6];
+        for (int j = 0; j < 6; ++j) f[j].resize(n);
+        for (size_t k = 0; k < n; ++k) {
+            const double r = sums[k] * inv, u = sums[n + k] * inv, v = sums[2 * n + k] * inv;
+            f[0][k] = r; f[1][k] = u; f[2][k] = v;
+            f[3][k] = sums[3 * n + k] * inv - u * u;
+            f[4][k] = sums[4 * n + k] * inv - v * v;
+            f[5][k] = sums[5 * n + k] * inv - u * v;
+        }
+        {
+            detail::TextFile o("mean_fields.vtk");
+            if (!o.ok()) { std::fprintf(stderr, "ERROR: Cannot write mean_fields.vtk\n"); return; }
+            o.put("# vtk DataFile Version 3.0\nLBM Flow Time Average of "); o.put_int(samples);
+            o.put(" samples\nASCII\nDATASET STRUCTURED_POINTS\nDIMENSIONS "); o.put_int(p.nx); o.put(" "); o.put_int(p.ny);
+            o.put(" 1\nORIGIN 0 0 0\nSPACING 1 1 1\nPOINT_DATA "); o.put_int(p.nx * p.ny);
+            o.put("\nVECTORS mean_velocity double\n");
+            for (size_t k = 0; k < n; ++k) { o.put_f8(f[1][k]); o.put(" "); o.put_f8(f[2][k]); o.put(" 0.0\n"); }
+            static const char* names[6] = {"mean_density", "", "", "reynolds_stress_uxux", "reynolds_stress_uyuy", "reynolds_stress_uxuy"};
+            for (int j : {0, 3, 4, 5}) {
+                o.put("\nSCALARS "); o.put(names[j]); o.put(" double\nLOOKUP_TABLE default\n");
+                for (size_t k = 0; k < n; ++k) { o.put_f8(f[j][k]); o.put("\n"); }
+            }
+        }
+        detail::TextFile c("mean_fields.csv");
+        if (!c.ok()) { std::fprintf(stderr, "ERROR: Cannot write mean_fields.csv\n"); return; }
+        c.put("x,y,rho,ux,uy,uxux,uyuy,uxuy\n");
+        for (int y = 0; y < p.ny; ++y)
+            for (int x = 0; x < p.nx; ++x) {
+                const size_t k = static_cast<size_t>(y) * p.nx + x;
+                c.put_int(x); c.put(","); c.put_int(y);
+                for (int j = 0; j < 6; ++j) { c.put(","); c.put_f8(f[j][k]); }
+                c.put("\n");
+            }
+        std::printf("Files written: mean_fields.vtk, mean_fields.csv (%d samples)\n", samples);
+    }
     const std::vector<ForceSample>& samples() const { return samples_; }
 
 private:

@@ -41,11 +41,15 @@ struct SimulationParams {
     // Smagorinsky LES collision (lbm_solver --smagorinsky; not in the reference): the constant Cs, 0 = plain BGK. tau, nu() and
     // reynolds() keep referring to the molecular viscosity.
     double smagorinsky_cs = 0.0;
+    // time-averaged statistics (lbm_solver --stats-start; not in the reference): the first step sampled, -1 = off. Samples are taken on
+    // the device at the output_frequency cadence (lbm_stats_begin); the run ends with mean_fields.vtk / mean_fields.csv.
+    int stats_start = -1;
 
     double nu() const { return (tau - 0.5) / 3.0; }
     bool masked() const { return !obstacle_mask.empty(); }
     bool profiled() const { return !inlet_profile.empty(); }
     bool les() const { return smagorinsky_cs > 0.0; }
+    bool stats() const { return stats_start >= 0; }
     double reynolds() const {
         if (masked()) return inlet_velocity * mask_frontal_height / nu();
         return inlet_velocity * (2.0 * cylinder_radius * ny) / nu();

@@ -24,6 +24,11 @@ public:
                         "  Reynolds number = %g\n", params_.nx, params_.ny, params_.tau, params_.nu(),
                         params_.inlet_velocity, params_.reynolds());
         const int solid = grid_.setup_and_initialise();
+        if (params_.stats()) {
+            grid_.stats_begin(params_.stats_start);
+            if (!opt_.quiet)
+                std::printf("  Statistics: time averages from step %d on, one sample every %d steps\n", params_.stats_start, params_.output_frequency);
+        }
         if (!opt_.quiet && params_.profiled())
             std::printf("  Inlet: profile %s, mean velocity %g (Cd / Cl refer to it)\n", params_.inlet_profile_spec.c_str(), params_.inlet_velocity);
         if (!opt_.quiet && params_.les())
@@ -83,8 +88,16 @@ public:
     }
 
     // Restart support: continue a run from a state written by save_state (same parameters).
-    void load_state(const std::string& path) { grid_.load_state(path); }
-    void save_state(const std::string& path) const { grid_.save_state(path); }
+    // (with statistics: the sums travel beside the checkpoint as <file>.stats; a restart without that file starts its averages afresh)
+    void load_state(const std::string& path) {
+        grid_.load_state(path);
+        if (params_.stats() && grid_.load_stats(path + ".stats") && !opt_.quiet)
+            std::printf("Statistics restored from %s.stats: %d samples\n", path.c_str(), grid_.stats_samples());
+    }
+    void save_state(const std::string& path) const {
+        grid_.save_state(path);
+        if (params_.stats()) grid_.save_stats(path + ".stats");
+    }
 
     const Grid& get_grid() const { return grid_; }
     Grid& get_grid() { return grid_; }   // (the reference's Solver reaches its Grid's mutable accessors as a member)

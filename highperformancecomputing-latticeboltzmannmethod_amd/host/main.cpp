@@ -20,7 +20,7 @@ static void usage() {
               "           [--no-vtk] [--no-final] [--sync-vtk] [--fp32] [--contracted] [--no-tune] [--device D] [--quiet]\n"
               "           [--gpus N] [--strips N] [--rccl]\n"
               "           [--checkpoint FILE] [--restart FILE] [--obstacle-mask FILE.pgm]\n"
-              "           [--inlet-profile parabolic|FILE] [--print-inlet-profile] [--smagorinsky CS]\n"
+              "           [--inlet-profile parabolic|FILE] [--print-inlet-profile] [--smagorinsky CS] [--stats-start N]\n"
               "Defaults are the reference's SimulationParams (LBMConfig.h:37-51). --reynolds sets the inlet velocity\n"
               "from tau and the cylinder diameter so that params.reynolds() equals RE.\n"
               "--gpus N cuts the lattice into N row strips, one per GPU of this node, advanced in lockstep by this process\n"
@@ -35,7 +35,11 @@ static void usage() {
               "--print-inlet-profile: print the ny inlet velocities (row 0 first) and exit without opening a device.\n"
               "--smagorinsky CS: Smagorinsky LES collision with constant CS in [0, 1] (0: plain BGK) instead of BGK, for\n"
               "higher Reynolds numbers at the same tau. tau, the Reynolds number and --reynolds keep referring to the\n"
-              "molecular viscosity (tau - 0.5) / 3; the eddy viscosity of the model is added per cell.");
+              "molecular viscosity (tau - 0.5) / 3; the eddy viscosity of the model is added per cell.\n"
+              "--stats-start N: time-averaged statistics from step N on, sampled on the device every --output-frequency steps;\n"
+              "the run ends with mean_fields.vtk and mean_fields.csv (means of rho, ux, uy and the Reynolds stresses). With\n"
+              "--checkpoint / --restart the sums travel beside the checkpoint as FILE.stats. --no-final suppresses the two\n"
+              "mean_fields files like the other end-of-run fields (FILE.stats is still written with --checkpoint).");
 }
 
 int main(int argc, char** argv) {
@@ -45,6 +49,7 @@ int main(int argc, char** argv) {
     std::string restart_from, checkpoint_to;
     bool print_profile = false;
     const char* smagorinsky = nullptr;
+    const char* stats_start = nullptr;
     double reynolds = -1.0;
     for (int a = 1; a < argc; ++a) {
         const std::string k = argv[a];
@@ -80,6 +85,7 @@ int main(int argc, char** argv) {
         else if (k == "--inlet-profile") params.inlet_profile_spec = val();
         else if (k == "--print-inlet-profile") print_profile = true;
         else if (k == "--smagorinsky") smagorinsky = val();
+        else if (k == "--stats-start") stats_start = val();
         else if (k == "--help" || k == "-h") { usage(); return 0; }
         else { std::fprintf(stderr, "unknown option %s\n", k.c_str()); usage(); return 2; }
     }
@@ -91,6 +97,19 @@ int main(int argc, char** argv) {
             return 2;
         }
         params.smagorinsky_cs = cs;
+    }
+    if (stats_start) {   // checked before any device is touched: a whole number >= 0, and a cadence to sample at
+        char* end = nullptr;
+        const long n = std::strtol(stats_start, &end, 10);
+        if (end == stats_start || *end != '\0' || n < 0 || n > 2147483647L) {
+            std::fprintf(stderr, "--stats-start: '%s' is not a step number >= 0\n", stats_start);
+            return 2;
+        }
+        if (params.output_frequency <= 0) {
+            std::fprintf(stderr, "--stats-start needs --output-frequency > 0: statistics are sampled at the output cadence\n");
+            return 2;
+        }
+        params.stats_start = (int)n;
     }
     if (!params.obstacle_mask_file.empty()) {   // parsed and checked before any device is touched
         try {
@@ -126,6 +145,7 @@ int main(int argc, char** argv) {
         if (success && !checkpoint_to.empty()) solver.save_state(checkpoint_to);
         if (success) {
             if (final_results) io_manager.write_final_results(solver.get_grid(), solver.get_params());
+            if (final_results && params.stats()) LBM::IOManager::write_mean_fields(solver.get_grid().stat_sums(), solver.get_grid().stats_samples(), solver.get_params());
             std::printf("\nSimulation completed successfully!\n");
         } else {
             std::fprintf(stderr, "LBM simulation failed.\n");

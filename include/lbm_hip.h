@@ -74,7 +74,8 @@ int  lbm_initialise(lbm_ctx* c, int* solid_count_out);
  * (intermediate states stay in LDS; results are bit-identical to one launch per iteration). Asynchronous on the
  * context's streams. If output_frequency > 0, record_forces is evaluated on-device for every
  * t % output_frequency == 0 inside the range (LBMSolver.h:52-54) and appended to the force log. The last iteration
- * of a call is always a launch of its own, so that the snapshots below refer to iteration steps_done-1. With a
+ * of a call is always a launch of its own, so that the snapshots below refer to iteration steps_done-1.
+ * With output_frequency == 0 no forces are evaluated and, with statistics begun (lbm_stats_begin), nothing is sampled. With a
  * communicator attached (lbm_comm_init) the strip's six edge rows per face are exchanged once per launch of five / six
  * iterations (strips of 64 rows or more) or once per two launches of up to three (replaces
  * Grid::exchange_ghost_cells, LBMGrid.h:249-283). */
@@ -102,6 +103,34 @@ int  lbm_drain_force_log(lbm_ctx* c, lbm_force_row* rows, int max_rows);
 int  lbm_get_macros(lbm_ctx* c, double* rho, double* ux, double* uy);
 /* Grid::max_velocity (LBMGrid.h:319-344) before the cross-rank MAX and sqrt: max(ux^2+uy^2) of this strip. */
 int  lbm_max_velocity_sq(lbm_ctx* c, double* out);
+
+/* ---- time-averaged flow statistics (no reference counterpart: the reference writes instantaneous fields only, LBMIO.h:62-111; what this
+ * replaces is a caller's loop of lbm_step(c, k, 0) + lbm_get_macros + host sums, one launch boundary, one synchronisation and
+ * 3 nx local_ny doubles over the bus per sample) ----
+ * Six running sums per cell, always in double (fp32 contexts too), in this order: sum rho, sum ux, sum uy, sum ux*ux, sum uy*uy,
+ * sum ux*uy. With statistics active, lbm_step / lbm_group_step add one SAMPLE at every iteration t of a call at which they evaluate the
+ * forces (output_frequency > 0 and t % output_frequency == 0) and t >= from_step, on the device, without a synchronisation. The sample
+ * of iteration t is, cell for cell and bit for bit, the (rho, ux, uy) lbm_get_macros returns on a context with steps_done == t + 1
+ * (moments of the post-collision populations of iteration t; inlet / outlet columns by pull + wall + Zou-He; solid cells (1, 0, 0)).
+ * Every sum is S = S + v in sample order and every product is rounded to double before it is added, so the sums equal a host loop over
+ * the snapshots exactly; means and Reynolds stresses (<u'u'> = S_uu / n - (S_u / n)^2, ...) are formed by the caller from the sums and
+ * the sample count, which lets strips and restarted runs be combined without loss.
+ * lbm_stats_begin: on an initialised context; allocates the accumulators on first use (48 B per cell, freed by lbm_destroy), zeroes the
+ * sums and the sample count and activates sampling from iteration from_step on; calling it again resets. LBM_ERR_ARG: null or
+ * uninitialised context, from_step < 0; LBM_ERR_ALLOC: no device memory for the accumulators. (lbm_set_option "stats" N: the same.) */
+int  lbm_stats_begin(lbm_ctx* c, int from_step);
+/* Stops sampling and keeps the sums (lbm_get_stat_sums still returns them). */
+int  lbm_stats_end(lbm_ctx* c);
+/* Samples accumulated so far (in a group: the same on every member). */
+int  lbm_stats_samples(const lbm_ctx* c);
+/* The six sums of this strip, [6][local_ny][nx] in the order above, rows as in lbm_get_macros. Synchronises. LBM_ERR_ARG if statistics
+ * were never begun on this context. */
+int  lbm_get_stat_sums(lbm_ctx* c, double* sums6);
+/* Uploads sums ([6][local_ny][nx]) and a sample count the caller saved; begins first where statistics were never begun (from_step 0)
+ * and otherwise leaves from_step as it was; sampling is active afterwards. Checkpoints do NOT carry statistics: the bytes of the
+ * LBMCKPT1/2/3 files are unchanged and lbm_load_state leaves the accumulators alone; a run resumed with lbm_load_state continues its
+ * averages through this call. */
+int  lbm_stats_restore(lbm_ctx* c, const double* sums6, int samples);
 
 /* Debug/parity accessor: ghost-inclusive AoS [(local_ny+2)][(nx+2)][9] exactly as Grid::f_current /
  * Grid::f_next index it (LBMGrid.h:105-107,116-119). which: 0 = f_current, 1 = f_next. */
@@ -237,6 +266,7 @@ int  lbm_load_state(lbm_ctx* c, const char* path);
  *                 "graph" 0|1|2 replay the launch groups of a deep strip plan from a captured hipGraph: 1 (default) where the
  *                 transport is local to the process, 2 also between the ranks of a communicator (RCCL under capture:
  *                 exercised with a one-rank communicator only so far)
+ *   "stats" N     lbm_stats_begin(c, N) (before lbm_initialise: begun at its end)
  *   "timing" 1    record HIP events around each lbm_step call (lbm_last_step_kernel_ms). */
 int  lbm_set_option(lbm_ctx* c, const char* key, long value);
 /* Average device time per step-kernel launch (ms) measured with HIP events on the context's stream around
@@ -290,7 +320,8 @@ int lbm_debug_group_pool(int n, int rounds, int fail_strip, int fail_round, int 
  * functions that issue a launch group (plan_launch, issue_before, the exchanges, issue_after) run on contexts without a device and
  * record every kernel (with the rows it writes and, through its depth, reads), event record, cross-stream wait, copy, send and receive;
  * the record is replayed with vector clocks. Returns the number of violations — RACE: two accesses to the same row of the same buffer, at
- * least one of them a write, that no event orders; STALE: a launch (or the force kernel) reads a row that does not hold the iteration it
+ * least one of them a write, that no event orders; STALE: a launch (or the force kernel, or — option "stats" — the statistics sample, which
+ * also reads one ghost row per face) reads a row that does not hold the iteration it
  * needs — or < 0; `out` receives their description (and, with dump != 0, every recorded operation). What it replaces: the ordering the
  * reference gets from MPI_Waitall before unpack_received_data (LBMGrid.h:278-283).
  * bounds2 = nstrips x {y_start, rows}; transport 0 in-process group with peer copies, 1 in-process group over RCCL, 2 ONE strip as a rank
