@@ -24,6 +24,10 @@ class ForceRow(C.Structure):
     _fields_ = [("timestep", C.c_int), ("fx", C.c_double), ("fy", C.c_double)]
 
 
+class BodyForceRow(C.Structure):
+    _fields_ = [("timestep", C.c_int), ("body", C.c_int), ("fx", C.c_double), ("fy", C.c_double)]
+
+
 _lib = None
 
 
@@ -62,6 +66,12 @@ def lib():
         L.lbm_set_f_current.argtypes = [vp, dp]
         L.lbm_get_solid.argtypes = [vp, C.POINTER(C.c_ubyte)]
         L.lbm_set_solid_mask.argtypes = [vp, C.POINTER(C.c_ubyte), C.c_int, C.c_int]
+        L.lbm_set_body_labels.argtypes = [vp, C.POINTER(C.c_ubyte), C.c_int, C.c_int]
+        L.lbm_body_count.argtypes = [vp]
+        L.lbm_get_body_forces.argtypes = [vp, dp]
+        L.lbm_drain_body_force_log.argtypes = [vp, C.POINTER(BodyForceRow), C.c_int]
+        L.lbm_debug_body_chunks.argtypes = [C.POINTER(C.c_ubyte), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int,
+                                            C.POINTER(C.c_long), C.c_int, C.POINTER(C.c_int)]
         L.lbm_set_inlet_profile.argtypes = [vp, dp, C.c_int]
         L.lbm_set_smagorinsky.argtypes = [vp, C.c_double]
         ip = C.POINTER(C.c_int)
@@ -155,6 +165,40 @@ def debug_geometry(solid, y_start=0, local_ny=0, boxes=()):
     return d, bits, sat, near
 
 
+def _label_bytes(labels, nx, ny):
+    """An integer (ny, nx) array of body numbers 0..255 as the contiguous uint8 array lbm_set_body_labels reads."""
+    m = np.asarray(labels)
+    if m.shape != (ny, nx):
+        raise ValueError(f"body labels have shape {m.shape}, the domain is (ny, nx) = {(ny, nx)}")
+    if not np.issubdtype(m.dtype, np.integer):
+        raise TypeError(f"body labels must be integers, not {m.dtype}")
+    if m.size and (m.min() < 0 or m.max() > 255):
+        raise ValueError("body labels must lie in 0..255")
+    return np.ascontiguousarray(m, dtype=np.uint8)
+
+
+def debug_body_chunks(labels, y_start=0, local_ny=0):
+    """lbm_debug_body_chunks (no device): what lbm_set_body_labels derives for one strip of a global (ny, nx) label array.
+    Returns (B, boxes [B, 4] int32 = x0, x1, y0, y1 inclusive in (x, local y), {0, -1, 0, -1} where empty,
+    chunks [n, 3] int64 = body, first cell of the box, cells)."""
+    L = lib()
+    ny, nx = np.shape(labels)
+    m = _label_bytes(labels, nx, ny)
+    local_ny = local_ny if local_ny > 0 else ny - y_start
+    ub = C.POINTER(C.c_ubyte)
+    n = C.c_int()
+    B = L.lbm_debug_body_chunks(m.ctypes.data_as(ub), nx, ny, y_start, local_ny, None, 0, None, 0, C.byref(n))
+    if B < 0:
+        raise LbmError(L.lbm_last_error().decode())
+    boxes = np.zeros((B, 4), dtype=np.int32)
+    chunks = np.zeros((n.value, 3), dtype=np.int64)
+    rc = L.lbm_debug_body_chunks(m.ctypes.data_as(ub), nx, ny, y_start, local_ny, boxes.ctypes.data_as(C.POINTER(C.c_int)), B,
+                                 chunks.ctypes.data_as(C.POINTER(C.c_long)), n.value, None)
+    if rc < 0:
+        raise LbmError(L.lbm_last_error().decode())
+    return B, boxes, chunks
+
+
 def parabolic_profile(ny, mean):
     """The inlet profile of lbm_solver --inlet-profile parabolic (host/lbm/inlet.hpp, operation by operation): the Poiseuille
     shape s(1-s), s = (y + 0.5)/ny, scaled so that its mean over the ny rows is `mean`. float64 [ny], row 0 (bottom) first."""
@@ -200,11 +244,15 @@ class Context:
     y = 0 first, nonzero = solid (lbm_set_solid_mask): the obstacle geometry in place of the cylinder_* disc. inlet_profile: optional
     float64 [ny] of absolute inlet x-velocities of the WHOLE domain, row y = 0 first (lbm_set_inlet_profile), in place of the
     uniform inlet_velocity (see parabolic_profile). smagorinsky: optional constant Cs of a Smagorinsky LES collision
-    (lbm_set_smagorinsky) in place of plain BGK; 0 / None: BGK."""
+    (lbm_set_smagorinsky) in place of plain BGK; 0 / None: BGK. bodies: optional integer (ny, nx) array of body numbers of the WHOLE
+    domain (0 fluid, 1..255; lbm_set_body_labels): the geometry of solid=(bodies != 0) plus forces per body (body_forces,
+    drain_body_force_log); not together with solid."""
 
     def __init__(self, nx, ny, tau=0.6, inlet_velocity=0.01333, cylinder_x=0.2, cylinder_y=0.5,
                  cylinder_radius=0.05, y_start=0, local_ny=0, precision="f64", device=0, force_log_capacity=0,
-                 options=None, solid=None, inlet_profile=None, smagorinsky=None):
+                 options=None, solid=None, inlet_profile=None, smagorinsky=None, bodies=None):
+        if solid is not None and bodies is not None:
+            raise LbmError("solid= and bodies= exclude each other: the body labels are the geometry (solid where nonzero)")
         self.L = lib()
         self.params = Params(tau, inlet_velocity, nx, ny, cylinder_x, cylinder_y, cylinder_radius, y_start,
                              local_ny, {"f64": 0, "f32": 1}[precision], force_log_capacity)
@@ -218,6 +266,8 @@ class Context:
             self.set_option(k, v)
         if solid is not None:
             self.set_solid_mask(solid)
+        if bodies is not None:
+            self.set_body_labels(bodies)
         if inlet_profile is not None:
             self.set_inlet_profile(inlet_profile)
         if smagorinsky is not None:
@@ -252,6 +302,29 @@ class Context:
         """lbm_set_solid_mask: the global (ny, nx) mask; before initialise()."""
         m = _mask_bytes(solid, self.nx, self.ny)
         self._chk(self.L.lbm_set_solid_mask(self.h, m.ctypes.data_as(C.POINTER(C.c_ubyte)), self.nx, self.ny))
+
+    def set_body_labels(self, labels):
+        """lbm_set_body_labels: the global (ny, nx) body numbers (0 fluid, 1..255); sets the geometry too; before initialise()."""
+        m = _label_bytes(labels, self.nx, self.ny)
+        self._chk(self.L.lbm_set_body_labels(self.h, m.ctypes.data_as(C.POINTER(C.c_ubyte)), self.nx, self.ny))
+
+    def body_count(self):
+        """B of set_body_labels (the largest label); 0 without labels."""
+        return int(self.L.lbm_body_count(self.h))
+
+    def body_forces(self):
+        """(B, 2) float64: (fx, fy) per body for t = steps_done, this strip's partial sums (lbm_get_body_forces)."""
+        out = np.zeros((self.body_count(), 2), dtype=np.float64)
+        self._chk(self.L.lbm_get_body_forces(self.h, _dp(out)))
+        return out
+
+    def drain_body_force_log(self, max_rows=None):
+        """[(t, body, fx, fy)]: the samples step() appended beside the force log, B rows each, whole samples only."""
+        if max_rows is None:
+            max_rows = 4096 * max(1, self.body_count())
+        rows = (BodyForceRow * max(1, max_rows))()
+        n = self._chk(self.L.lbm_drain_body_force_log(self.h, rows, max_rows))
+        return [(rows[k].timestep, rows[k].body, rows[k].fx, rows[k].fy) for k in range(n)]
 
     def set_inlet_profile(self, u):
         """lbm_set_inlet_profile: the global [ny] inlet velocities (absolute, row 0 first); before initialise()."""
@@ -424,16 +497,17 @@ class Group:
     """n strips of one lattice driven in lockstep by this process (lbm_group_*): one Context per strip, bottom to top.
     transport: "peer" (device copies / hipMemcpyPeerAsync) or "rccl" (ncclCommInitAll; distinct devices).
     solid: optional global (ny, nx) obstacle mask, inlet_profile: optional global [ny] inlet velocities, smagorinsky: optional LES
-    constant Cs; all given to every member."""
+    constant Cs, bodies: optional global (ny, nx) body numbers (in place of solid); all given to every member."""
 
-    def __init__(self, nx, ny, bounds, devices=None, transport="peer", options=None, solid=None, inlet_profile=None, smagorinsky=None, **kw):
+    def __init__(self, nx, ny, bounds, devices=None, transport="peer", options=None, solid=None, inlet_profile=None, smagorinsky=None,
+                 bodies=None, **kw):
         from .strips import partition_rows
         if isinstance(bounds, int):
             bounds = partition_rows(ny, bounds)
         devices = devices or [0] * len(bounds)
         self.nx, self.ny = nx, ny
         self.ctxs = [Context(nx, ny, y_start=y0, local_ny=n, device=d, options=options, solid=solid, inlet_profile=inlet_profile,
-                             smagorinsky=smagorinsky, **kw)
+                             smagorinsky=smagorinsky, bodies=bodies, **kw)
                      for (y0, n), d in zip(bounds, devices)]
         self.L = lib()
         self._arr = (C.c_void_p * len(self.ctxs))(*[c.h for c in self.ctxs])
@@ -519,6 +593,23 @@ class Group:
     def forces(self):
         f = [c.forces() for c in self.ctxs]
         return sum(v[0] for v in f), sum(v[1] for v in f)
+
+    # ---- per-body forces: the strips' partial sums added per (t, body) in strip order ----
+    def body_count(self):
+        return self.ctxs[0].body_count()
+
+    def body_forces(self):
+        """(B, 2): the strips' partial sums added in strip order."""
+        total = self.ctxs[0].body_forces()
+        for c in self.ctxs[1:]:
+            total = total + c.body_forces()
+        return total
+
+    def drain_body_force_log(self):
+        logs = [c.drain_body_force_log() for c in self.ctxs]
+        if len({len(l) for l in logs}) != 1:
+            raise LbmError("the body force logs of the strips differ in length")
+        return [(logs[0][k][0], logs[0][k][1], sum(l[k][2] for l in logs), sum(l[k][3] for l in logs)) for k in range(len(logs[0]))]
 
     def max_velocity_sq(self):
         return max(c.max_velocity_sq() for c in self.ctxs)

@@ -196,14 +196,14 @@ struct GroupPool {
 // clocks and reports every pair of conflicting accesses that no event orders, and every launch that reads a row of the wrong
 // iteration: the class of round 4's edge-band race (a band shorter than the rows that travel), found then by a 1-in-15 flake.
 struct ChoreoOp {
-    enum { KERNEL = 0, RECORD = 1, WAIT = 2, COPY = 3, SEND = 4, RECV = 5, FORCES = 6, STATS = 7 };
+    enum { KERNEL = 0, RECORD = 1, WAIT = 2, COPY = 3, SEND = 4, RECV = 5, FORCES = 6, STATS = 7, BODIES = 8 };
     int kind = 0;
     int strip = 0, stream = 0;      // the issuing strip, 0 main / 1 side stream
     int ev_strip = 0, ev = 0;       // RECORD / WAIT: the event's owner and 0 ev_main, 1 ev_edge, 2 ev_comm
     int buf = 0;                    // KERNEL: the buffer written (it reads buf ^ 1); COPY / SEND / RECV / FORCES: the buffer touched
-    int t = 0, depth = 0;           // KERNEL: first iteration and iterations; FORCES / STATS: the iteration
+    int t = 0, depth = 0;           // KERNEL: first iteration and iterations; FORCES / STATS / BODIES: the iteration
     int w0[2] = {0, 0}, w1[2] = {0, 0};   // rows written, [w0, w1) in local rows (ghost rows: < 0 or >= nyl); KERNEL: two ranges
-    int r0 = 0, r1 = 0, r_strip = -1;     // COPY / SEND / FORCES / STATS: rows read and whose (RECV: where the data comes from; -1: another process)
+    int r0 = 0, r1 = 0, r_strip = -1;     // COPY / SEND / FORCES / STATS / BODIES: rows read and whose (RECV: where the data comes from; -1: another process)
                                           // (STATS: the strip's rows and ONE ghost row per face — the pull of the inlet / outlet cells of its first and last row)
 };
 // ... and, for one rank of a multi-process run, the transcript of what exchange_rccl's posting loops WOULD hand to RCCL, in posting order:
@@ -253,6 +253,20 @@ struct lbm_ctx {
     MaskView mview;                  // device pointers of hmask's bitmap and coarse table
     double* d_fpart = nullptr;       // k_forces: partial sums of the chunks of a large force box (masked contexts only)
     int fpart_chunks = 0;
+    // Per-body forces (lbm_set_body_labels): the labels of the strip's rows + one ghost row per face, one byte per cell, and the chunk
+    // table of the bodies' boxes (lbm_geom.hpp pack_bodies), read by k_forces_bodies alone; uploaded once, never written by a kernel.
+    // body_n = B (0: no labels). The log is a ring of log_cap samples of B rows (t, fx, fy): lbm_drain_body_force_log takes whole
+    // samples from its head.
+    int body_n = 0, body_chunks = 0;
+    unsigned char* d_labels = nullptr;
+    int* d_body_box = nullptr;
+    BodyChunk* d_body_chunks = nullptr;
+    int* d_body_first = nullptr;
+    double* d_body_part = nullptr;      // [chunks][2]
+    double* d_body_now = nullptr;       // [B][3]
+    double* d_body_log = nullptr;       // [log_cap][B][3]
+    int body_log_head = 0, body_log_count = 0;      // samples
+    int bodies_opt = 0;                 // option "bodies" (dry run only): record a body-force sample behind every force kernel
     // The inflow: d_urow = the inlet velocity of every global row in the element type, read-only (step kernels, k_macros): inlet_velocity
     // on every row, or the profile of lbm_set_inlet_profile (has_profile), whose digest checkpoints carry and whose initial
     // equilibria f_eq(1,(u[y],0)), [ny][Q], k_init reads from d_feqrow.

@@ -6,6 +6,7 @@
 #include "lbm_kernels.hpp"
 
 #include <cstdint>
+#include <cstring>
 #include <vector>
 
 namespace lbmk {
@@ -61,6 +62,61 @@ inline HostMask pack_mask(const unsigned char* mask, int nx, int ny, int y_start
         }
     if (h.bx1 < 0) { h.bx0 = 0; h.by0 = 0; }
     h.digest = d;
+    return h;
+}
+
+// Per-body force reporting (lbm_set_body_labels): what k_forces_bodies reads for ONE strip of a global [ny][nx] label array
+// (0 fluid, k = 1..255 a solid cell of body k; B = the largest label present, a label nobody carries is a body without cells).
+//   lab    [(local_ny + 2)][nx]: the strip's rows and one ghost row per face, zeros beyond the domain
+//   box    [B][4]: body k's bounding box + 1 cell, clipped to the domain and to the strip's rows, x0, x1, y0, y1 inclusive in
+//          (x, LOCAL y) — the rule of k_forces' one box, per body; {0, -1, 0, -1} where nothing of it lies in the strip
+//   chunks every non-empty box in row-major runs of FORCE_CHUNK cells, bodies in label order: the blocks of one sample
+//   first  [B + 1]: body k's chunks are [first[k - 1], first[k])
+struct HostBodies {
+    int B = 0;
+    std::vector<unsigned char> lab;
+    std::vector<int> box;
+    std::vector<BodyChunk> chunks;
+    std::vector<int> first;
+};
+
+inline HostBodies pack_bodies(const unsigned char* labels, int nx, int ny, int y_start, int local_ny) {
+    HostBodies h;
+    int bx0[256], bx1[256], by0[256], by1[256];
+    long cells[256];
+    for (int k = 0; k < 256; ++k) { bx0[k] = nx; bx1[k] = -1; by0[k] = ny; by1[k] = -1; cells[k] = 0; }
+    for (int y = 0; y < ny; ++y)
+        for (int x = 0; x < nx; ++x) {
+            const int k = labels[(size_t)y * nx + x];
+            if (!k) continue;
+            h.B = k > h.B ? k : h.B;
+            cells[k]++;
+            bx0[k] = x < bx0[k] ? x : bx0[k]; bx1[k] = x > bx1[k] ? x : bx1[k];
+            by0[k] = y < by0[k] ? y : by0[k]; by1[k] = y > by1[k] ? y : by1[k];
+        }
+    h.lab.assign((size_t)(local_ny + 2) * nx, 0);
+    for (int r = 0; r < local_ny + 2; ++r) {
+        const int y = y_start - 1 + r;
+        if (y >= 0 && y < ny) memcpy(&h.lab[(size_t)r * nx], labels + (size_t)y * nx, (size_t)nx);
+    }
+    h.first.assign(1, 0);
+    for (int k = 1; k <= h.B; ++k) {
+        int b[4] = {0, -1, 0, -1};
+        if (cells[k] > 0) {
+            const int x0 = bx0[k] - 1 < 0 ? 0 : bx0[k] - 1, x1 = bx1[k] + 1 > nx - 1 ? nx - 1 : bx1[k] + 1;
+            const int y0 = by0[k] - 1 - y_start < 0 ? 0 : by0[k] - 1 - y_start;
+            const int y1 = by1[k] + 1 - y_start > local_ny - 1 ? local_ny - 1 : by1[k] + 1 - y_start;
+            if (y1 >= y0) { b[0] = x0; b[1] = x1; b[2] = y0; b[3] = y1; }
+        }
+        h.box.insert(h.box.end(), b, b + 4);
+        const long ncell = b[1] >= b[0] ? (long)(b[1] - b[0] + 1) * (b[3] - b[2] + 1) : 0;
+        for (long f = 0; f < ncell; f += FORCE_CHUNK) {
+            BodyChunk c;
+            c.body = k; c.first = f; c.cells = (int)(ncell - f < FORCE_CHUNK ? ncell - f : FORCE_CHUNK);
+            h.chunks.push_back(c);
+        }
+        h.first.push_back((int)h.chunks.size());
+    }
     return h;
 }
 

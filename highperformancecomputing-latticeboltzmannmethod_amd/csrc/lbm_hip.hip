@@ -262,7 +262,8 @@ void lbm_destroy(lbm_ctx* c) {
     c->pool.reset();
     void* ptrs[] = {c->buf[0], c->buf[1], c->scratch, c->d_macro, c->d_maxbits, c->d_unstable, c->d_tbase, c->d_solid_count, c->d_feq,
                     c->d_force_now, c->d_force_log, c->d_halo, c->d_red, (void*)c->mview.bits, (void*)c->mview.sat, c->d_fpart,
-                    c->d_urow, c->d_feqrow, c->d_stats};
+                    c->d_urow, c->d_feqrow, c->d_stats, c->d_labels, c->d_body_box, c->d_body_chunks, c->d_body_first, c->d_body_part,
+                    c->d_body_now, c->d_body_log};
     for (void* q : ptrs)
         if (q) (void)hipFree(q);
     hipEvent_t evs[] = {c->ev_edge, c->ev_comm, c->ev_main, c->ev_t0, c->ev_t1, c->gev_main, c->gev_edge, c->gev_comm};
@@ -286,6 +287,7 @@ int lbm_initialise(lbm_ctx* c, int* solid_count_out) {
     c->split_i = 0;
     c->steps_done = 0;
     c->log_count = 0;
+    c->body_log_head = c->body_log_count = 0;
     c->mid_pair = false;
     c->comm_issued = false;
     c->ext_split_pending = false;
@@ -370,6 +372,44 @@ int lbm_drain_force_log(lbm_ctx* c, lbm_force_row* rows, int max_rows) {
     }
     c->log_count = 0;
     return n;
+}
+
+/* ---- per-body forces (lbm_set_body_labels): k_forces_bodies over the chunk table of the bodies' boxes ---- */
+int lbm_body_count(const lbm_ctx* c) { return c ? c->body_n : 0; }
+
+int lbm_get_body_forces(lbm_ctx* c, double* fxy) {
+    if (!c || !c->initialised || !fxy) return fail(LBM_ERR_ARG, "lbm_get_body_forces needs an initialised context and an output array");
+    if (c->body_n < 1) return fail(LBM_ERR_ARG, "lbm_get_body_forces: this context has no body labels (lbm_set_body_labels)");
+    HIPCHK(hipSetDevice(c->device));
+    { int jr = join_comm(c); if (jr) return jr; }
+    int rc = DISPATCH(c, launch_body_forces<double>(c, c->d_body_now, c->steps_done), launch_body_forces<float>(c, c->d_body_now, c->steps_done));
+    if (rc) return rc;
+    std::vector<double> h(3 * (size_t)c->body_n);
+    HIPCHK(hipMemcpyAsync(h.data(), c->d_body_now, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (int b = 0; b < c->body_n; ++b) { fxy[2 * b] = h[3 * (size_t)b + 1]; fxy[2 * b + 1] = h[3 * (size_t)b + 2]; }
+    return LBM_OK;
+}
+
+int lbm_drain_body_force_log(lbm_ctx* c, lbm_body_force_row* rows, int max_rows) {
+    if (!c || (!rows && max_rows > 0)) return fail(LBM_ERR_ARG, "null argument");
+    if (c->body_n < 1 || max_rows < c->body_n || c->body_log_count < 1) return 0;       // whole samples only
+    HIPCHK(hipSetDevice(c->device));
+    const int B = c->body_n, n = std::min(max_rows / B, c->body_log_count);
+    const int n1 = std::min(n, c->log_cap - c->body_log_head);      // the ring: up to the end of the buffer, then from its start
+    std::vector<double> h(3 * (size_t)B * n);
+    HIPCHK(hipMemcpyAsync(h.data(), c->d_body_log + 3L * B * c->body_log_head, 3 * sizeof(double) * B * n1, hipMemcpyDeviceToHost, c->stream));
+    if (n > n1) HIPCHK(hipMemcpyAsync(h.data() + 3 * (size_t)B * n1, c->d_body_log, 3 * sizeof(double) * B * (n - n1), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (size_t k = 0; k < (size_t)B * n; ++k) {
+        rows[k].timestep = (int)h[3 * k];
+        rows[k].body = (int)(k % B) + 1;
+        rows[k].fx = h[3 * k + 1];
+        rows[k].fy = h[3 * k + 2];
+    }
+    c->body_log_head = (c->body_log_head + n) % c->log_cap;
+    c->body_log_count -= n;
+    return B * n;
 }
 
 int lbm_get_macros(lbm_ctx* c, double* rho, double* ux, double* uy) {
@@ -501,6 +541,14 @@ int lbm_set_solid_mask(lbm_ctx* c, const unsigned char* mask, int nx, int ny) {
     if (nx != c->nx || ny != c->p.ny) return fail(LBM_ERR_ARG, "lbm_set_solid_mask: mask is %dx%d, the domain %dx%d", nx, ny, c->nx, c->p.ny);
     HostMask h = pack_mask(mask, nx, ny, c->p.y_start, c->nyl);
     HIPCHK(hipSetDevice(c->device));
+    {   // a mask replaces the geometry wholesale: the labels of an earlier lbm_set_body_labels go with it
+        void** q[] = {(void**)&c->d_labels, (void**)&c->d_body_box, (void**)&c->d_body_chunks, (void**)&c->d_body_first, (void**)&c->d_body_part,
+                      (void**)&c->d_body_now, (void**)&c->d_body_log};
+        for (void** d : q)
+            if (*d) { HIPCHK(hipFree(*d)); *d = nullptr; }
+        c->body_n = c->body_chunks = 0;
+        c->body_log_head = c->body_log_count = 0;
+    }
     if (c->mview.bits) { HIPCHK(hipFree((void*)c->mview.bits)); c->mview.bits = nullptr; }
     if (c->mview.sat) { HIPCHK(hipFree((void*)c->mview.sat)); c->mview.sat = nullptr; }
     if (c->d_fpart) { HIPCHK(hipFree(c->d_fpart)); c->d_fpart = nullptr; }
@@ -520,6 +568,31 @@ int lbm_set_solid_mask(lbm_ctx* c, const unsigned char* mask, int nx, int ny) {
     HIPCHK(hipMalloc(&c->d_fpart, 2 * sizeof(double) * (size_t)std::max(1, c->fpart_chunks)));
     c->hmask = std::move(h);
     c->has_mask = true;
+    return LBM_OK;
+}
+
+int lbm_set_body_labels(lbm_ctx* c, const unsigned char* labels, int nx, int ny) {
+    if (!c || !labels) return fail(LBM_ERR_ARG, "lbm_set_body_labels: null argument");
+    if (c->initialised) return fail(LBM_ERR_ARG, "lbm_set_body_labels must be called before lbm_initialise");
+    if (nx != c->nx || ny != c->p.ny) return fail(LBM_ERR_ARG, "lbm_set_body_labels: labels are %dx%d, the domain %dx%d", nx, ny, c->nx, c->p.ny);
+    int rc = lbm_set_solid_mask(c, labels, nx, ny);      // the geometry: nonzero = solid (clears labels set earlier)
+    if (rc) return rc;
+    const HostBodies h = pack_bodies(labels, nx, ny, c->p.y_start, c->nyl);
+    if (h.B < 1) return LBM_OK;                          // no solid cell: no body, nothing to report
+    const size_t nch = h.chunks.size();
+    HIPCHK(hipMalloc(&c->d_labels, h.lab.size()));
+    HIPCHK(hipMalloc(&c->d_body_box, h.box.size() * sizeof(int)));
+    HIPCHK(hipMalloc(&c->d_body_chunks, std::max<size_t>(1, nch) * sizeof(BodyChunk)));
+    HIPCHK(hipMalloc(&c->d_body_first, h.first.size() * sizeof(int)));
+    HIPCHK(hipMalloc(&c->d_body_part, std::max<size_t>(1, nch) * 2 * sizeof(double)));
+    HIPCHK(hipMalloc(&c->d_body_now, 3 * sizeof(double) * (size_t)h.B));
+    HIPCHK(hipMalloc(&c->d_body_log, 3 * sizeof(double) * (size_t)h.B * (size_t)c->log_cap));
+    HIPCHK(hipMemcpy(c->d_labels, h.lab.data(), h.lab.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(c->d_body_box, h.box.data(), h.box.size() * sizeof(int), hipMemcpyHostToDevice));
+    if (nch) HIPCHK(hipMemcpy(c->d_body_chunks, h.chunks.data(), nch * sizeof(BodyChunk), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(c->d_body_first, h.first.data(), h.first.size() * sizeof(int), hipMemcpyHostToDevice));
+    c->body_chunks = (int)nch;
+    c->body_n = h.B;                                     // (last: a failure above leaves a context without labels, its buffers to lbm_destroy)
     return LBM_OK;
 }
 
@@ -805,6 +878,7 @@ int lbm_load_state(lbm_ctx* c, const char* path) {
     fclose(fp);
     if (rc) return rc;
     c->log_count = 0;
+    c->body_log_head = c->body_log_count = 0;
     c->last_was_pair = false;
     c->mid_pair = false;
     if ((c->comm || c->loopback) && c->group_n <= 1)   // (a group: lbm_group_refresh_halos once every member is restored)
@@ -856,6 +930,7 @@ int lbm_set_option(lbm_ctx* c, const char* key, long value) {
         if (c->initialised) return lbm_stats_begin(c, (int)value);
         c->stats_opt = (int)value;
     }
+    else if (k == "bodies") c->bodies_opt = (int)value ? 1 : 0;      // dry run only (lbm_debug_choreography): a body-force sample behind every force kernel
     else if (k == "graph") { if (value < 0 || value > 2) return fail(LBM_ERR_ARG, "graph must be 0, 1 or 2"); c->use_graph = (int)value; }
     else if (k == "loopback") c->loopback = (int)value;   // 0 off, 1 device copies, 2 RCCL self send/recv
     else if (k == "pair_ty") { if (value != 8 && value != 12) return fail(LBM_ERR_ARG, "pair_ty must be 8 or 12"); c->pair_ty = (int)value; }
@@ -927,6 +1002,23 @@ int lbm_debug_geometry(const unsigned char* mask, int nx, int ny, int y_start, i
     const MaskView m = h.view();
     for (int k = 0; k < nbox; ++k) near_out[k] = mask_box_any(m, boxes4[4 * k], boxes4[4 * k + 1], boxes4[4 * k + 2], boxes4[4 * k + 3]) ? 1 : 0;
     return LBM_OK;
+}
+
+/* TEST HOOK (no device needed): what lbm_set_body_labels uploads for the strip [y_start, y_start + local_ny) (csrc/lbm_geom.hpp pack_bodies). */
+int lbm_debug_body_chunks(const unsigned char* labels, int nx, int ny, int y_start, int local_ny, int* boxes4, int boxes_cap,
+                          long* chunks3, int chunks_cap, int* nchunks_out) {
+    if (!labels || nx < 1 || ny < 1 || y_start < 0 || local_ny < 1 || y_start + local_ny > ny) return fail(LBM_ERR_ARG, "bad argument");
+    const HostBodies h = pack_bodies(labels, nx, ny, y_start, local_ny);
+    if (nchunks_out) *nchunks_out = (int)h.chunks.size();
+    if (boxes4) {
+        if (boxes_cap < h.B) return fail(LBM_ERR_ARG, "boxes: %d entries needed", h.B);
+        if (h.B) memcpy(boxes4, h.box.data(), h.box.size() * sizeof(int));
+    }
+    if (chunks3) {
+        if (chunks_cap < (int)h.chunks.size()) return fail(LBM_ERR_ARG, "chunks: %zu entries needed", h.chunks.size());
+        for (size_t k = 0; k < h.chunks.size(); ++k) { chunks3[3 * k] = h.chunks[k].body; chunks3[3 * k + 1] = h.chunks[k].first; chunks3[3 * k + 2] = h.chunks[k].cells; }
+    }
+    return h.B;
 }
 
 /* TEST HOOK (no device needed): the candidates lbm_initialise would time for a whole-domain context of this grid, one per line:
@@ -1056,6 +1148,7 @@ int lbm_debug_choreography(int nx, int ny, const int* bounds2, int nstrips, int 
         c->initialised = true;
         c->cur = 1;
         if (c->stats_opt >= 0) { c->stats_active = true; c->stats_from = c->stats_opt; }      // (no accumulators: nothing is launched)
+        if (c->bodies_opt) c->body_n = 1;                                                     // (no labels either)
     }
     if (transport < 2) {
         for (int k = 0; k < nstrips; ++k) {

@@ -1208,6 +1208,72 @@ __global__ void __launch_bounds__(64) k_forces_sum(const double* part, int nchun
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// The same momentum exchange PER BODY (lbm_set_body_labels; the reference has one disc and one total): the force on body k is the
+// part of the sum above whose links END in a cell of label k — fluid cell x (label 0) of this strip's rows, direction i, neighbour
+// x + c_i inside the domain with label k — so bodies that touch are told apart by the solid end of every link.
+// Geometry comes from ONE byte per cell, lab[(ny_loc + 2)][nx]: the strip's rows and one ghost row per face (the neighbour strip's
+// labels; zeros beyond the domain, which is what keeps the row test of k_forces out of this kernel). Only this kernel reads it.
+// The host cuts every body's bounding box (+1 cell, clipped to the domain and to the strip's rows) into chunks of FORCE_CHUNK cells
+// (lbm_geom.hpp pack_bodies) and uploads ONE table of them, sorted by body and by first cell: one block per chunk with the stride
+// loop and the LDS tree of k_forces unchanged, the chunks' partial sums kept in `part` and added per body in chunk order by
+// k_forces_bodies_sum. Partition and order depend on the labels and the strip alone: every plan, layout and repetition gives the
+// same bits, and with 1 as the only label the chunks, the addends of every thread and their order are those of k_forces — the row
+// of body 1 IS the total, bit for bit. A body without a cell in the box of this strip has no chunk and gets zeros.
+struct BodyChunk { int body; int cells; long first; };     // label, cells of this chunk, its first cell in the box's row-major order
+template <typename T>
+struct BodyForceArgs {
+    const T* cur; long plane; int pitch, xoff, nx;
+    const unsigned char* lab;     // [(ny_loc + 2)][nx]: row r holds local row r - 1
+    const int* box;               // [B][4]: x0, x1, y0, y1 of body b + 1, inclusive, in (x, local y)
+    const BodyChunk* chunks;
+    double* part;                 // [chunks][2]
+};
+
+template <typename T>
+__global__ void __launch_bounds__(1024) k_forces_bodies(const BodyForceArgs<T> p) {
+    __shared__ double sfx[1024];
+    __shared__ double sfy[1024];
+    double fx = 0.0, fy = 0.0;
+    const BodyChunk ch = p.chunks[blockIdx.x];
+    const int b = ch.body;
+    const int x0 = p.box[4 * (b - 1)], bw = p.box[4 * (b - 1) + 1] - x0 + 1, y0 = p.box[4 * (b - 1) + 2];
+    const long k1 = ch.first + ch.cells;
+    for (long k = ch.first + threadIdx.x; k < k1; k += 1024) {
+        const int x = x0 + (int)(k % bw), y = y0 + (int)(k / bw);
+        const unsigned char* row = p.lab + (long)(y + 1) * p.nx;
+        if (row[x] != 0) continue;
+        const long c = (long)(y + GR) * p.pitch + p.xoff + x;
+#pragma unroll
+        for (int i = 1; i < Q; ++i) {
+            const int sx = x + cx(i);
+            if (sx < 0 || sx >= p.nx) continue;
+            if (row[(long)cy(i) * p.nx + sx] != b) continue;
+            const double fi = (double)p.cur[(long)i * p.plane + c];
+            fx += 2.0 * cx(i) * fi;
+            fy += 2.0 * cy(i) * fi;
+        }
+    }
+    sfx[threadIdx.x] = fx; sfy[threadIdx.x] = fy;
+    __syncthreads();
+    for (int s = 512; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) { sfx[threadIdx.x] += sfx[threadIdx.x + s]; sfy[threadIdx.x] += sfy[threadIdx.x + s]; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) { p.part[2 * blockIdx.x] = sfx[0]; p.part[2 * blockIdx.x + 1] = sfy[0]; }
+}
+// one thread per body: the partial sums of its chunks [first[b], first[b + 1]) in chunk order; out = [B][3] rows (t, fx, fy)
+template <typename T>
+__global__ void __launch_bounds__(64) k_forces_bodies_sum(const double* part, const int* first, int nbodies, double* out, int t) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= nbodies) return;
+    const int c0 = first[b], c1 = first[b + 1];
+    double fx = 0.0, fy = 0.0;
+    if (c1 - c0 == 1) { fx = part[2 * c0]; fy = part[2 * c0 + 1]; }      // (k_forces writes the sum of a single chunk as it is)
+    else for (int c = c0; c < c1; ++c) { fx += part[2 * c]; fy += part[2 * c + 1]; }
+    out[3 * b] = (double)t; out[3 * b + 1] = fx; out[3 * b + 2] = fy;
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // Host-staged halo rows (lbm_halo_export / lbm_halo_import): GR rows x 9 planes x nx interior columns per face,
 // as double, [GR][9][nx]. `row0` = first local gy of the GR consecutive rows.
 template <typename T>

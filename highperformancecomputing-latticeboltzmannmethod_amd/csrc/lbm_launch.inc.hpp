@@ -196,3 +196,34 @@ int launch_forces(lbm_ctx* c, double* out, int t) {
     return LBM_OK;
 }
 
+// The per-body sample of iteration t (k_forces_bodies + k_forces_bodies_sum, lbm_set_body_labels): B rows (t, fx, fy) at `out`. Queued
+// directly behind the force kernel on the compute stream: it reads the same rows of the same buffer, so the join that kernel sits
+// behind covers it. One launch of one block per chunk of the table and one ordered sum, whatever the plan.
+template <typename T>
+int launch_body_forces(lbm_ctx* c, double* out, int t) {
+    if (c->rec) {      // dry run: reads this strip's rows of P_t, like the force kernel (the labels carry the ghost rows' geometry)
+        ChoreoOp o; o.kind = ChoreoOp::BODIES; o.strip = c->group_k; o.stream = 0; o.buf = c->cur; o.t = t; o.r0 = 0; o.r1 = c->nyl; o.r_strip = c->group_k;
+        c->rec->ops.push_back(o);
+        return LBM_OK;
+    }
+    BodyForceArgs<T> a;
+    a.cur = static_cast<const T*>(c->buf[c->cur]);
+    a.plane = (long)c->plane; a.pitch = c->pitch; a.xoff = c->xoff; a.nx = c->nx;
+    a.lab = c->d_labels; a.box = c->d_body_box; a.chunks = c->d_body_chunks; a.part = c->d_body_part;
+    if (c->body_chunks > 0) hipLaunchKernelGGL((k_forces_bodies<T>), dim3(c->body_chunks), dim3(1024), 0, c->stream, a);
+    hipLaunchKernelGGL((k_forces_bodies_sum<T>), dim3((c->body_n + 63) / 64), dim3(64), 0, c->stream, (const double*)c->d_body_part,
+                       (const int*)c->d_body_first, c->body_n, out, t);
+    HIPCHK(hipGetLastError());
+    return LBM_OK;
+}
+
+// ... appended to the ring of the body-force log (do_steps: at exactly the iterations that append a force-log row, after it has checked
+// that both logs have room)
+template <typename T>
+int log_body_forces(lbm_ctx* c, int t) {
+    const long slot = (c->body_log_head + c->body_log_count) % c->log_cap;
+    const int rc = launch_body_forces<T>(c, c->d_body_log + 3L * c->body_n * slot, t);
+    if (!rc) c->body_log_count++;
+    return rc;
+}
+

@@ -158,9 +158,11 @@ int do_steps(lbm_ctx** cs, int n, int nsteps, int of) {
                 int rc = LBM_OK;
                 if (of > 0 && t % of == 0) {
                     if (c->log_count >= c->log_cap) rc = fail(LBM_ERR_ARG, "force log full (%d rows): drain it", c->log_cap);
+                    if (!rc && c->body_n > 0 && c->body_log_count >= c->log_cap) rc = fail(LBM_ERR_ARG, "body force log full (%d samples): drain it", c->log_cap);
                     if (!rc) rc = join_comm(c);
                     if (!rc) rc = launch_forces<T>(c, c->d_force_log + 3L * c->log_count, t);
                     if (!rc) c->log_count++;
+                    if (!rc && c->body_n > 0) rc = log_body_forces<T>(c, t);
                     if (!rc && c->stats_active && t >= c->stats_from) rc = launch_stats<T>(c, t);
                 }
                 if (!rc) rc = plan_launch(c, nsteps - k, of, transport, true, &L[(size_t)i]);
@@ -202,11 +204,16 @@ int do_steps(lbm_ctx** cs, int n, int nsteps, int of) {
             SETDEV(c);
             if (of > 0 && t % of == 0) {
                 if (c->log_count >= c->log_cap) return fail(LBM_ERR_ARG, "force log full (%d rows): drain it", c->log_cap);
+                if (c->body_n > 0 && c->body_log_count >= c->log_cap) return fail(LBM_ERR_ARG, "body force log full (%d samples): drain it", c->log_cap);     // (before the force row is logged)
                 int rc = join_comm(c);      // the edge bands of the previous launch live on the side stream
                 if (rc) return rc;
                 rc = launch_forces<T>(c, c->d_force_log + 3L * c->log_count, t);
                 if (rc) return rc;
                 c->log_count++;
+                if (c->body_n > 0) {      // the per-body rows of iteration t: directly behind the force kernel, no synchronisation
+                    rc = log_body_forces<T>(c, t);
+                    if (rc) return rc;
+                }
                 if (c->stats_active && t >= c->stats_from) {      // the sample of iteration t: behind the same join, on the same stream
                     rc = launch_stats<T>(c, t);
                     if (rc) return rc;

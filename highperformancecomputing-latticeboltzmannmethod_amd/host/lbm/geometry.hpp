@@ -2,6 +2,8 @@
 // pixels, a pixel is solid when it is nonzero. The file's FIRST image row is lattice row ny-1, so the picture looks like the VTK
 // view (y up). Parsed and checked on the host before any device is touched; the result is the global [ny][nx] byte mask that
 // lbm_set_solid_mask takes (row y = 0 first).
+// lbm_solver --obstacle-bodies reads the same file format with the grey value kept as the body number (0 fluid, k = 1..255 a cell of
+// body k): the array lbm_set_body_labels takes, plus each body's cell count and frontal height.
 #pragma once
 #include <cctype>
 #include <cstdio>
@@ -15,6 +17,9 @@ struct ObstacleMask {
     std::vector<unsigned char> cells;   // [ny][nx], row 0 = bottom; 1 = solid
     int frontal_height = 0;             // rows that hold a solid cell: the reference length D of a masked run
     int solid_cells = 0;
+    // read_obstacle_pgm(..., keep_labels): cells hold the grey values; per body k = 1..B (index k - 1) its cells and the rows it spans
+    // (last row - first row + 1: the reference length D of that body's coefficients; 0 for a label nobody carries)
+    std::vector<int> body_cells, body_height;
 };
 
 namespace detail {
@@ -41,11 +46,12 @@ inline bool pgm_int(std::FILE* fp, long& v) {
 }  // namespace detail
 
 // Throws std::runtime_error with the reason: unreadable file, bad header, wrong size, maxval outside 1..255, short or bad data.
-inline ObstacleMask read_obstacle_pgm(const std::string& path, int nx, int ny) {
+// what: how the messages name the file ("obstacle mask" / "--obstacle-bodies"); keep_labels: see ObstacleMask.
+inline ObstacleMask read_obstacle_pgm(const std::string& path, int nx, int ny, const std::string& what = "obstacle mask", bool keep_labels = false) {
     std::FILE* fp = std::fopen(path.c_str(), "rb");
-    if (!fp) throw std::runtime_error("cannot open obstacle mask " + path);
+    if (!fp) throw std::runtime_error("cannot open " + what + " " + path);
     struct Closer { std::FILE* f; ~Closer() { std::fclose(f); } } closer{fp};
-    auto bad = [&](const std::string& why) { return std::runtime_error("obstacle mask " + path + ": " + why); };
+    auto bad = [&](const std::string& why) { return std::runtime_error(what + " " + path + ": " + why); };
     std::string magic;
     if (!detail::pgm_token(fp, magic) || (magic != "P5" && magic != "P2")) throw bad("not a PGM file (magic P5 or P2 expected)");
     long w = 0, h = 0, maxval = 0;
@@ -70,13 +76,30 @@ inline ObstacleMask read_obstacle_pgm(const std::string& path, int nx, int ny) {
         bool any = false;
         unsigned char* dst = m.cells.data() + (size_t)(ny - 1 - r) * nx;
         for (int x = 0; x < nx; ++x) {
-            dst[x] = row[(size_t)x] ? 1 : 0;
+            dst[x] = keep_labels ? row[(size_t)x] : (row[(size_t)x] ? 1 : 0);
             any |= dst[x] != 0;
-            m.solid_cells += dst[x];
+            m.solid_cells += dst[x] != 0;
         }
         m.frontal_height += any ? 1 : 0;
     }
     if (m.solid_cells == 0) throw bad("no solid pixel (the reference length of the force coefficients would be zero)");
+    if (keep_labels) {
+        std::vector<int> lo(256, ny), hi(256, -1), cells(256, 0);
+        int B = 0;
+        for (int y = 0; y < ny; ++y)
+            for (int x = 0; x < nx; ++x) {
+                const int k = m.cells[(size_t)y * nx + x];
+                if (!k) continue;
+                B = k > B ? k : B;
+                cells[(size_t)k]++;
+                lo[(size_t)k] = y < lo[(size_t)k] ? y : lo[(size_t)k];
+                hi[(size_t)k] = y > hi[(size_t)k] ? y : hi[(size_t)k];
+            }
+        for (int k = 1; k <= B; ++k) {
+            m.body_cells.push_back(cells[(size_t)k]);
+            m.body_height.push_back(cells[(size_t)k] ? hi[(size_t)k] - lo[(size_t)k] + 1 : 0);
+        }
+    }
     return m;
 }
 

@@ -47,7 +47,8 @@ public:
             devs_.push_back(dev);
             check(lbm_set_option(c, "tune", opt.tune ? 1 : 0), "lbm_set_option");
             check(lbm_set_option(c, "arith", opt.contracted ? 1 : 0), "lbm_set_option");
-            if (p.masked()) check(lbm_set_solid_mask(c, p.obstacle_mask.data(), p.nx, p.ny), "lbm_set_solid_mask");
+            if (p.bodied()) check(lbm_set_body_labels(c, p.obstacle_mask.data(), p.nx, p.ny), "lbm_set_body_labels");
+            else if (p.masked()) check(lbm_set_solid_mask(c, p.obstacle_mask.data(), p.nx, p.ny), "lbm_set_solid_mask");
             if (p.profiled()) check(lbm_set_inlet_profile(c, p.inlet_profile.data(), p.ny), "lbm_set_inlet_profile");
             if (p.les()) check(lbm_set_smagorinsky(c, p.smagorinsky_cs), "lbm_set_smagorinsky");
             y += n;
@@ -169,6 +170,36 @@ public:
             if (k == 0) sum = rows;
             else {
                 if (rows.size() != sum.size()) throw std::runtime_error("force logs of the strips differ in length");
+                for (size_t r = 0; r < rows.size(); ++r) { sum[r].fx += rows[r].fx; sum[r].fy += rows[r].fy; }
+            }
+        }
+        return sum;
+    }
+    // per-body forces (lbm_set_body_labels; the reference has none): the strips' partial sums added per (sample, body) in strip order
+    int body_count() const { return lbm_body_count(ctx_[0]); }
+    std::vector<lbm_body_force_row> body_forces_now(int timestep) const {
+        const int B = body_count();
+        std::vector<lbm_body_force_row> sum((size_t)B);
+        std::vector<double> fxy(2 * (size_t)B);
+        for (int b = 0; b < B; ++b) sum[(size_t)b] = {timestep, b + 1, 0.0, 0.0};
+        for (lbm_ctx* c : ctx_) {
+            check(lbm_get_body_forces(c, fxy.data()), "lbm_get_body_forces");
+            for (int b = 0; b < B; ++b) { sum[(size_t)b].fx += fxy[2 * (size_t)b]; sum[(size_t)b].fy += fxy[2 * (size_t)b + 1]; }
+        }
+        return sum;
+    }
+    std::vector<lbm_body_force_row> drain_body_force_log() const {
+        std::vector<lbm_body_force_row> sum;
+        const int B = body_count();
+        if (B < 1) return sum;
+        for (size_t k = 0; k < ctx_.size(); ++k) {
+            std::vector<lbm_body_force_row> rows((size_t)B * 4096);
+            const int n = lbm_drain_body_force_log(ctx_[k], rows.data(), (int)rows.size());
+            check(n, "lbm_drain_body_force_log");
+            rows.resize((size_t)n);
+            if (k == 0) sum = rows;
+            else {
+                if (rows.size() != sum.size()) throw std::runtime_error("body force logs of the strips differ in length");
                 for (size_t r = 0; r < rows.size(); ++r) { sum[r].fx += rows[r].fx; sum[r].fy += rows[r].fy; }
             }
         }

@@ -58,6 +58,8 @@ public:
         double fx = 0.0, fy = 0.0;
         grid.forces_now(fx, fy);
         append_force_row(timestep, fx, fy, params);
+        if (params.bodied())
+            for (const auto& r : grid.body_forces_now(timestep)) append_body_force_row(r.timestep, r.body, r.fx, r.fy, params);
     }
     // Same row from a device-log entry (Solver::run drains the log at output cadence).
     void append_force_row(int timestep, double fx, double fy, const SimulationParams& params) {
@@ -71,6 +73,27 @@ public:
         for (double v : {fx, fy, cd, cl}) { forces_->put(","); forces_->put_f8(v); }
         forces_->put("\n");
         if (timestep % 10000 == 0) forces_->flush();
+    }
+
+    // forces_bodies.csv (lbm_solver --obstacle-bodies; the reference has none): one row per sample and body, the coefficients by the
+    // formula of forces.csv with that body's own frontal height as D. Created with the first row (or by open_body_forces).
+    void open_body_forces() {
+        if (bodies_) return;
+        bodies_ = std::make_unique<detail::TextFile>("forces_bodies.csv");
+        if (bodies_->ok()) bodies_->put("timestep,body,drag_force,lift_force,drag_coeff,lift_coeff\n");
+        else std::fprintf(stderr, "ERROR: Could not open forces_bodies.csv\n");
+    }
+    void append_body_force_row(int timestep, int body, double fx, double fy, const SimulationParams& params) {
+        open_body_forces();
+        if (!bodies_->ok()) return;
+        const double d_ref = body >= 1 && body <= params.body_count() ? (double)params.body_height[(size_t)body - 1] : 0.0;
+        const double q_ref = 0.5 * 1.0 * params.inlet_velocity * params.inlet_velocity * d_ref;
+        const double cd = (q_ref > 1e-12) ? fx / q_ref : 0.0;
+        const double cl = (q_ref > 1e-12) ? fy / q_ref : 0.0;
+        bodies_->put_int(timestep); bodies_->put(","); bodies_->put_int(body);
+        for (double v : {fx, fy, cd, cl}) { bodies_->put(","); bodies_->put_f8(v); }
+        bodies_->put("\n");
+        if (timestep % 10000 == 0) bodies_->flush();
     }
 
     // IOManager::write_vtk_timestep (LBMIO.h:55-111): legacy ASCII STRUCTURED_POINTS, vtk_output/lbm_%06d.vtk.
@@ -120,6 +143,7 @@ public:
         write_velocity_field(ux, uy, rho, params);
         write_simulation_params(ux, uy, params);
         forces_->flush();
+        if (bodies_) bodies_->flush();
         print_force_statistics();
         std::printf("Files written: velocity_field.csv, simulation_params.csv, forces.csv\n");
         std::fflush(stdout);
@@ -223,7 +247,8 @@ private:
         row_d("max_velocity", vmax); row_d("avg_velocity", vavg);
         if (p.masked()) {   // (not in the reference's file: masked runs only, appended so that its rows keep their places)
             row_i("reference_length", p.mask_frontal_height);
-            f.put("obstacle_mask,"); f.put(p.obstacle_mask_file.c_str()); f.put("\n");
+            if (p.bodied()) { f.put("obstacle_bodies,"); f.put(p.obstacle_bodies_file.c_str()); f.put("\n"); row_i("body_count", p.body_count()); }
+            else { f.put("obstacle_mask,"); f.put(p.obstacle_mask_file.c_str()); f.put("\n"); }
         }
         if (p.profiled()) { f.put("inlet_profile,"); f.put(p.inlet_profile_spec.c_str()); f.put("\n"); }   // (profiled runs only, likewise)
         if (p.les()) row_d("smagorinsky_cs", p.smagorinsky_cs);                                            // (LES runs only, likewise)
@@ -250,6 +275,7 @@ private:
     }
 
     std::unique_ptr<detail::TextFile> forces_;
+    std::unique_ptr<detail::TextFile> bodies_;      // forces_bodies.csv: runs with --obstacle-bodies only
     std::vector<ForceSample> samples_;
     std::mutex mu_;
     std::condition_variable cv_;

@@ -34,6 +34,11 @@ struct SimulationParams {
     std::string obstacle_mask_file;
     std::vector<unsigned char> obstacle_mask;
     int mask_frontal_height = 0;
+    // per-body forces (lbm_solver --obstacle-bodies; not in the reference): the same geometry from a PGM whose grey value is the body
+    // number; obstacle_mask then holds the labels (nonzero = solid, as lbm_set_body_labels reads them). Per body 1..B: its cells and
+    // the rows it spans, the D of its own coefficients in forces_bodies.csv. Everything a masked run writes stays as it is.
+    std::string obstacle_bodies_file;
+    std::vector<int> body_cells, body_height;
     // per-row inlet profile (lbm_solver --inlet-profile; not in the reference): "parabolic" or the file of its shape, and the ny
     // absolute velocities, row 0 first, whose mean is inlet_velocity (host/lbm/inlet.hpp). Empty: inlet_velocity on every row.
     std::string inlet_profile_spec;
@@ -47,6 +52,8 @@ struct SimulationParams {
 
     double nu() const { return (tau - 0.5) / 3.0; }
     bool masked() const { return !obstacle_mask.empty(); }
+    bool bodied() const { return !obstacle_bodies_file.empty(); }
+    int body_count() const { return (int)body_height.size(); }
     bool profiled() const { return !inlet_profile.empty(); }
     bool les() const { return smagorinsky_cs > 0.0; }
     bool stats() const { return stats_start >= 0; }

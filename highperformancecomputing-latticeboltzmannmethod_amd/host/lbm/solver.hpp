@@ -35,8 +35,11 @@ public:
             std::printf("  Collision: Smagorinsky LES, Cs = %g (tau and the Reynolds number refer to the molecular viscosity)\n",
                         params_.smagorinsky_cs);
         if (!opt_.quiet && params_.masked()) {
-            std::printf("  Obstacle: mask %s, frontal height D=%d cells\n  Solid cells: %d\n  Plan: %s\n", params_.obstacle_mask_file.c_str(),
+            std::printf("  Obstacle: %s %s, frontal height D=%d cells\n  Solid cells: %d\n  Plan: %s\n", params_.bodied() ? "bodies" : "mask",
+                        params_.bodied() ? params_.obstacle_bodies_file.c_str() : params_.obstacle_mask_file.c_str(),
                         params_.mask_frontal_height, solid, grid_.plan());
+            for (int b = 0; b < params_.body_count(); ++b)
+                std::printf("  Body %d: %d cells, D=%d\n", b + 1, params_.body_cells[(size_t)b], params_.body_height[(size_t)b]);
             std::fflush(stdout);
         } else if (!opt_.quiet) {
             std::printf("  Cylinder: center=(%d,%d), radius=%d cells\n  Solid cells: %d\n  Plan: %s\n",
@@ -62,6 +65,7 @@ public:
     bool run(IOManager& io) {
         if (!opt_.quiet) { std::printf("Starting LBM cylinder flow simulation...\n"); std::fflush(stdout); }
         const int T = params_.num_timesteps, of = std::max(1, params_.output_frequency);
+        if (params_.bodied()) io.open_body_forces();
         const auto w0 = std::chrono::steady_clock::now();
         int t = grid_.steps_done();
         const int t_begin = t;
@@ -72,6 +76,8 @@ public:
             const int bad = grid_.first_unstable_step();
             for (const auto& r : grid_.drain_force_log())
                 if (bad < 0 || r.timestep <= bad) io.append_force_row(r.timestep, r.fx, r.fy, params_);
+            for (const auto& r : grid_.drain_body_force_log())
+                if (bad < 0 || r.timestep <= bad) io.append_body_force_row(r.timestep, r.body, r.fx, r.fy, params_);
             if (bad >= 0) {
                 std::fprintf(stderr, "Simulation unstable at timestep %d\n", bad);
                 return false;

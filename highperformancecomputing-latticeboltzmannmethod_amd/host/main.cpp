@@ -19,7 +19,7 @@ static void usage() {
               "           [--reynolds RE] [--cylinder-x F] [--cylinder-y F] [--cylinder-radius F] [--vtk-start-step N]\n"
               "           [--no-vtk] [--no-final] [--sync-vtk] [--fp32] [--contracted] [--no-tune] [--device D] [--quiet]\n"
               "           [--gpus N] [--strips N] [--rccl]\n"
-              "           [--checkpoint FILE] [--restart FILE] [--obstacle-mask FILE.pgm]\n"
+              "           [--checkpoint FILE] [--restart FILE] [--obstacle-mask FILE.pgm] [--obstacle-bodies FILE.pgm]\n"
               "           [--inlet-profile parabolic|FILE] [--print-inlet-profile] [--smagorinsky CS] [--stats-start N]\n"
               "Defaults are the reference's SimulationParams (LBMConfig.h:37-51). --reynolds sets the inlet velocity\n"
               "from tau and the cylinder diameter so that params.reynolds() equals RE.\n"
@@ -28,6 +28,9 @@ static void usage() {
               "strips on one GPU. --contracted: FMA-contracted collision (as the reference's -ffast-math -mfma build).\n"
               "--obstacle-mask: the obstacle as a P5 / P2 PGM of exactly nx x ny pixels (nonzero = solid; the first image row\n"
               "is the top lattice row) in place of the cylinder; Cd / Cl and the Reynolds number then use its frontal height.\n"
+              "--obstacle-bodies: the same PGM with the grey value as the body number (0 fluid, 1..255; maxval above 255 is refused; not\n"
+              "together with --obstacle-mask). Geometry, forces.csv and the Cd / Cl summary are those of the mask; forces_bodies.csv adds\n"
+              "drag and lift per body (momentum exchange over the links that end in it), with the rows a body spans as its own D.\n"
               "--inlet-profile: one inlet velocity per row instead of the plug inflow. parabolic: the Poiseuille profile\n"
               "s(1-s), s = (y+0.5)/ny; FILE: a text file of ny numbers, row 0 (bottom) first ('#' comments and blank lines\n"
               "allowed), giving the shape. Either is scaled so that its mean over the ny rows is the inlet velocity, which\n"
@@ -82,6 +85,7 @@ int main(int argc, char** argv) {
         else if (k == "--restart") restart_from = val();
         else if (k == "--checkpoint") checkpoint_to = val();
         else if (k == "--obstacle-mask") params.obstacle_mask_file = val();
+        else if (k == "--obstacle-bodies") params.obstacle_bodies_file = val();
         else if (k == "--inlet-profile") params.inlet_profile_spec = val();
         else if (k == "--print-inlet-profile") print_profile = true;
         else if (k == "--smagorinsky") smagorinsky = val();
@@ -110,6 +114,22 @@ int main(int argc, char** argv) {
             return 2;
         }
         params.stats_start = (int)n;
+    }
+    if (!params.obstacle_bodies_file.empty() && !params.obstacle_mask_file.empty()) {
+        std::fprintf(stderr, "--obstacle-bodies and --obstacle-mask exclude each other: the labels are the mask\n");
+        return 2;
+    }
+    if (!params.obstacle_bodies_file.empty()) {   // parsed and checked before any device is touched, like the mask
+        try {
+            LBM::ObstacleMask m = LBM::read_obstacle_pgm(params.obstacle_bodies_file, params.nx, params.ny, "--obstacle-bodies", true);
+            params.obstacle_mask = std::move(m.cells);
+            params.mask_frontal_height = m.frontal_height;
+            params.body_cells = std::move(m.body_cells);
+            params.body_height = std::move(m.body_height);
+        } catch (const std::exception& e) {
+            std::fprintf(stderr, "%s\n", e.what());
+            return 2;
+        }
     }
     if (!params.obstacle_mask_file.empty()) {   // parsed and checked before any device is touched
         try {

@@ -55,6 +55,7 @@ typedef struct lbm_params {
 typedef struct lbm_ctx lbm_ctx;
 
 typedef struct lbm_force_row { int timestep; double fx, fy; } lbm_force_row;
+typedef struct lbm_body_force_row { int timestep; int body; double fx, fy; } lbm_body_force_row;   /* lbm_drain_body_force_log */
 
 const char* lbm_last_error(void);
 int  lbm_device_count(void);
@@ -97,6 +98,37 @@ int  lbm_first_unstable_step(lbm_ctx* c, int* t_out);
 int  lbm_get_forces(lbm_ctx* c, double* fx, double* fy);
 /* Rows appended by lbm_step (this strip's partial sums); returns the number copied, clears the log. */
 int  lbm_drain_force_log(lbm_ctx* c, lbm_force_row* rows, int max_rows);
+
+/* ---- forces per obstacle body (no reference counterpart: the reference has one disc and one total, LBMIO.h:133-168; what this replaces
+ * is a caller's lbm_get_populations — 9 (nx+2)(local_ny+2) doubles over the bus and a synchronisation per sample — and link sums on the
+ * host) ----
+ * lbm_set_body_labels sets the geometry exactly as lbm_set_solid_mask does with the same bytes (nonzero = solid: solid count,
+ * lbm_get_solid, macros, total force and the checkpoint digest of the solid set are those of the mask) and KEEPS the bytes as labels:
+ * 0 = fluid, k in 1..255 = a solid cell of body k. The body count B is the largest label present; a label in 1..B that no cell carries
+ * is a body whose force is zero. The force on body k at iteration t is the part of lbm_get_forces' sum whose links END in body k: every
+ * fluid cell x of this strip's rows, every direction i whose neighbour x + c_i lies in the domain and carries label k, sum 2 c_i f_i(x)
+ * on the post-collision populations. A link belongs to the body of its solid end, so bodies that touch are told apart; a strip reports
+ * the partial sums over the fluid cells of its own rows (strips add up; a strip that holds no cell next to a body reports zeros for it).
+ * The partition of the work and the order of every sum depend on the labels and the strip alone: plans, layouts and repetitions give the
+ * same bits, and where 1 is the only label the row of body 1 equals the total of lbm_get_forces / the force log bit for bit.
+ * Device memory: one byte per cell of the strip's rows + one ghost row per face, read by the per-body force kernel only (the step
+ * kernels keep the packed mask); the log takes 24 B x B x force_log_capacity.
+ * Call after lbm_create and before lbm_initialise; every strip of a run is given the same global [ny][nx] array. A later
+ * lbm_set_solid_mask clears the labels; a later lbm_set_body_labels replaces mask and labels. Labels change reporting only: checkpoints
+ * are byte for byte those of a context given the same solid set as a mask, and load into either.
+ * LBM_ERR_ARG: null pointer, nx / ny other than the domain's, or an initialised context (the errors of lbm_set_solid_mask). */
+int  lbm_set_body_labels(lbm_ctx* c, const unsigned char* labels, int nx, int ny);
+/* B of lbm_set_body_labels; 0 without labels (no reference counterpart). */
+int  lbm_body_count(const lbm_ctx* c);
+/* The per-body forces for t = steps_done, like lbm_get_forces: fxy = [B][2] (fx, fy of body 1 first), this strip's partial sums.
+ * Synchronises. LBM_ERR_ARG without labels (no reference counterpart). */
+int  lbm_get_body_forces(lbm_ctx* c, double* fxy);
+/* With labels set, lbm_step / lbm_group_step append one SAMPLE of B rows (body 1..B) at exactly the iterations at which they append a
+ * force-log row, issued directly behind the force kernel on the same stream without a synchronisation. The log holds
+ * force_log_capacity samples (lbm_step fails when it is full: drain it). A drain copies whole samples only, oldest first — as many as
+ * fit into max_rows rows (none if max_rows < B) — removes them from the log and returns the number of ROWS copied; 0 without labels.
+ * Synchronises (no reference counterpart). */
+int  lbm_drain_body_force_log(lbm_ctx* c, lbm_body_force_row* rows, int max_rows);
 
 /* rho/ux/uy of this strip, row-major [local_ny][nx] (LBMGrid.h:109-111; the layout gathered at
  * LBMSolver.h:340-357). Any pointer may be NULL. Synchronises. */
@@ -267,6 +299,8 @@ int  lbm_load_state(lbm_ctx* c, const char* path);
  *                 transport is local to the process, 2 also between the ranks of a communicator (RCCL under capture:
  *                 exercised with a one-rank communicator only so far)
  *   "stats" N     lbm_stats_begin(c, N) (before lbm_initialise: begun at its end)
+ *   "bodies" 1    lbm_debug_choreography only: the dry run records a per-body force sample behind every force kernel (a real context
+ *                 gets its bodies from lbm_set_body_labels and ignores the key)
  *   "timing" 1    record HIP events around each lbm_step call (lbm_last_step_kernel_ms). */
 int  lbm_set_option(lbm_ctx* c, const char* key, long value);
 /* Average device time per step-kernel launch (ms) measured with HIP events on the context's stream around
@@ -321,7 +355,7 @@ int lbm_debug_group_pool(int n, int rounds, int fail_strip, int fail_round, int 
  * record every kernel (with the rows it writes and, through its depth, reads), event record, cross-stream wait, copy, send and receive;
  * the record is replayed with vector clocks. Returns the number of violations — RACE: two accesses to the same row of the same buffer, at
  * least one of them a write, that no event orders; STALE: a launch (or the force kernel, or — option "stats" — the statistics sample, which
- * also reads one ghost row per face) reads a row that does not hold the iteration it
+ * also reads one ghost row per face, or — option "bodies" — the per-body force sample, which reads the force kernel's rows and writes a log slot of its own) reads a row that does not hold the iteration it
  * needs — or < 0; `out` receives their description (and, with dump != 0, every recorded operation). What it replaces: the ordering the
  * reference gets from MPI_Waitall before unpack_received_data (LBMGrid.h:278-283).
  * bounds2 = nstrips x {y_start, rows}; transport 0 in-process group with peer copies, 1 in-process group over RCCL, 2 ONE strip as a rank
@@ -346,6 +380,14 @@ int lbm_debug_p2p_matching(int nx, int ny, const int* bounds2, int nranks, int p
  * "any solid cell in the box" for boxes4[k] = {x0, x1, y0, y1} (global, inclusive), answered from the coarse table. */
 int lbm_debug_geometry(const unsigned char* mask, int nx, int ny, int y_start, int local_ny, int* dims9, unsigned long long* bits, long bits_cap,
                        int* sat, long sat_cap, const int* boxes4, int nbox, int* near_out);
+/* Test hook, callable without a device: what lbm_set_body_labels derives from a global [ny][nx] label array for the strip
+ * [y_start, y_start + local_ny) (csrc/lbm_geom.hpp pack_bodies). Returns B (or < 0). boxes4 (nullable, boxes_cap entries of four ints) =
+ * B x {x0, x1, y0, y1}: body k's bounding box dilated by one cell, clipped to the domain and to the strip's rows, inclusive, y in LOCAL
+ * rows; {0, -1, 0, -1} for a body with no cell or with nothing of its box in the strip. chunks3 (nullable, chunks_cap entries of three
+ * longs) = the chunk table {body, first cell in the box's row-major order, cells}: every non-empty box cut into runs of 65536 cells,
+ * bodies in label order; *nchunks_out (nullable) = its length. No reference counterpart. */
+int lbm_debug_body_chunks(const unsigned char* labels, int nx, int ny, int y_start, int local_ny, int* boxes4, int boxes_cap,
+                          long* chunks3, int chunks_cap, int* nchunks_out);
 /* SHA-256 (16 hex digits) of the sources this binary was compiled from (csrc/ and this header); build.py rebuilds
  * when it differs from the tree, bench.py prints it. */
 const char* lbm_build_id(void);
