@@ -62,6 +62,10 @@ def lib():
         L.lbm_stats_samples.argtypes = [vp]
         L.lbm_get_stat_sums.argtypes = [vp, dp]
         L.lbm_stats_restore.argtypes = [vp, dp, C.c_int]
+        L.lbm_frames_begin.argtypes = [vp, C.c_int, C.c_int]
+        L.lbm_frames_end.argtypes = [vp]
+        L.lbm_frames_pending.argtypes = [vp]
+        L.lbm_drain_frames.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_float), C.c_int]
         L.lbm_get_populations.argtypes = [vp, C.c_int, dp]
         L.lbm_set_f_current.argtypes = [vp, dp]
         L.lbm_get_solid.argtypes = [vp, C.POINTER(C.c_ubyte)]
@@ -246,11 +250,12 @@ class Context:
     uniform inlet_velocity (see parabolic_profile). smagorinsky: optional constant Cs of a Smagorinsky LES collision
     (lbm_set_smagorinsky) in place of plain BGK; 0 / None: BGK. bodies: optional integer (ny, nx) array of body numbers of the WHOLE
     domain (0 fluid, 1..255; lbm_set_body_labels): the geometry of solid=(bodies != 0) plus forces per body (body_forces,
-    drain_body_force_log); not together with solid."""
+    drain_body_force_log); not together with solid. frames: optional stride k of coarsened flow frames (lbm_frames_begin with the
+    default capacity at the end of initialise(); see frames_begin)."""
 
     def __init__(self, nx, ny, tau=0.6, inlet_velocity=0.01333, cylinder_x=0.2, cylinder_y=0.5,
                  cylinder_radius=0.05, y_start=0, local_ny=0, precision="f64", device=0, force_log_capacity=0,
-                 options=None, solid=None, inlet_profile=None, smagorinsky=None, bodies=None):
+                 options=None, solid=None, inlet_profile=None, smagorinsky=None, bodies=None, frames=None):
         if solid is not None and bodies is not None:
             raise LbmError("solid= and bodies= exclude each other: the body labels are the geometry (solid where nonzero)")
         self.L = lib()
@@ -262,6 +267,7 @@ class Context:
         self.h = C.c_void_p()
         self._chk(self.L.lbm_create(C.byref(self.params), device, C.byref(self.h)))
         self.solid_count = None
+        self._frames_k = 0
         for k, v in (options or {}).items():
             self.set_option(k, v)
         if solid is not None:
@@ -272,6 +278,8 @@ class Context:
             self.set_inlet_profile(inlet_profile)
         if smagorinsky is not None:
             self.set_smagorinsky(smagorinsky)
+        if frames is not None:
+            self.set_option("frames", frames)
 
     def _chk(self, rc):
         if rc < 0:
@@ -297,6 +305,8 @@ class Context:
 
     def set_option(self, key, value):
         self._chk(self.L.lbm_set_option(self.h, key.encode(), int(value)))
+        if key == "frames":
+            self._frames_k = int(value)
 
     def set_solid_mask(self, solid):
         """lbm_set_solid_mask: the global (ny, nx) mask; before initialise()."""
@@ -408,6 +418,35 @@ class Context:
         """{'n', 'rho', 'ux', 'uy' (means), 'uxux', 'uyuy', 'uxuy' (Reynolds stresses)} of the samples so far."""
         return _stats_from_sums(self.stats_sums(), self.stats_samples())
 
+    # ---- coarsened flow frames (lbm_frames_*): written on the device at the force-output iterations of step(n, output_frequency) ----
+    FRAMES_DEFAULT_CAPACITY = 8   # LBM_FRAMES_DEFAULT_CAPACITY
+
+    def frames_begin(self, k, capacity=FRAMES_DEFAULT_CAPACITY):
+        """From now on every force-output iteration appends one frame — rho, ux, uy and vorticity block-averaged k x k, float32 — to a
+        device ring of `capacity` frames; k must divide nx, y_start and local_ny. Calling it again empties the ring."""
+        self._chk(self.L.lbm_frames_begin(self.h, int(k), int(capacity)))
+        self._frames_k = int(k)
+
+    def frames_end(self):
+        """Stops sampling; the undrained frames stay."""
+        self._chk(self.L.lbm_frames_end(self.h))
+
+    def frames_pending(self):
+        return self._chk(self.L.lbm_frames_pending(self.h))
+
+    def drain_frames(self, max_frames=None):
+        """[(t, float32 [4, local_ny / k, nx / k])]: the oldest max_frames (default: all) undrained frames, planes rho, ux, uy, vorticity."""
+        n = self.frames_pending()
+        if max_frames is not None:
+            n = min(n, int(max_frames))
+        if n < 1:
+            return []
+        k = self._frames_k
+        out = np.empty((n, 4, self.local_ny // k, self.nx // k), dtype=np.float32)
+        ts = (C.c_int * n)()
+        got = self._chk(self.L.lbm_drain_frames(self.h, ts, out.ctypes.data_as(C.POINTER(C.c_float)), n))
+        return [(ts[j], out[j]) for j in range(got)]
+
     def populations(self, which):
         """which: 'f_current' | 'f_next' -> [(local_ny+2), (nx+2), 9] like Grid::f_current(gx,gy,i)."""
         out = np.empty((self.local_ny + 2, self.nx + 2, 9), dtype=np.float64)
@@ -497,17 +536,18 @@ class Group:
     """n strips of one lattice driven in lockstep by this process (lbm_group_*): one Context per strip, bottom to top.
     transport: "peer" (device copies / hipMemcpyPeerAsync) or "rccl" (ncclCommInitAll; distinct devices).
     solid: optional global (ny, nx) obstacle mask, inlet_profile: optional global [ny] inlet velocities, smagorinsky: optional LES
-    constant Cs, bodies: optional global (ny, nx) body numbers (in place of solid); all given to every member."""
+    constant Cs, bodies: optional global (ny, nx) body numbers (in place of solid), frames: optional frame stride k; all given to every
+    member."""
 
     def __init__(self, nx, ny, bounds, devices=None, transport="peer", options=None, solid=None, inlet_profile=None, smagorinsky=None,
-                 bodies=None, **kw):
+                 bodies=None, frames=None, **kw):
         from .strips import partition_rows
         if isinstance(bounds, int):
             bounds = partition_rows(ny, bounds)
         devices = devices or [0] * len(bounds)
         self.nx, self.ny = nx, ny
         self.ctxs = [Context(nx, ny, y_start=y0, local_ny=n, device=d, options=options, solid=solid, inlet_profile=inlet_profile,
-                             smagorinsky=smagorinsky, bodies=bodies, **kw)
+                             smagorinsky=smagorinsky, bodies=bodies, frames=frames, **kw)
                      for (y0, n), d in zip(bounds, devices)]
         self.L = lib()
         self._arr = (C.c_void_p * len(self.ctxs))(*[c.h for c in self.ctxs])
@@ -578,6 +618,36 @@ class Group:
 
     def stats(self):
         return _stats_from_sums(self.stats_sums(), self.stats_samples())
+
+    # ---- coarsened flow frames: begun on every member (k must divide every strip's y_start and rows); the members sample at the same
+    # iterations, and a drained frame is their rows concatenated by y_start ----
+    def frames_begin(self, k, capacity=Context.FRAMES_DEFAULT_CAPACITY):
+        for c in self.ctxs:
+            c.frames_begin(k, capacity)
+
+    def frames_end(self):
+        for c in self.ctxs:
+            c.frames_end()
+
+    def frames_pending(self):
+        n = {c.frames_pending() for c in self.ctxs}
+        if len(n) != 1:
+            raise LbmError(f"the strips of the group disagree on the number of pending frames: {sorted(n)}")
+        return n.pop()
+
+    def drain_frames(self, max_frames=None):
+        """[(t, float32 [4, ny / k, nx / k])]: the strips' frames concatenated by y_start."""
+        n = self.frames_pending()
+        if max_frames is not None:
+            n = min(n, int(max_frames))
+        parts = [c.drain_frames(n) for c in self.ctxs]
+        out = []
+        for j in range(n):
+            ts = {p[j][0] for p in parts}
+            if len(ts) != 1:
+                raise LbmError(f"the strips of the group disagree on the iteration of a frame: {sorted(ts)}")
+            out.append((ts.pop(), np.concatenate([p[j][1] for p in parts], axis=1)))
+        return out
 
     def populations(self, which):
         """Ghost-inclusive [(ny+2), (nx+2), 9]: interior rows of every strip + the physical ghost rows of the end strips."""

@@ -196,15 +196,16 @@ struct GroupPool {
 // clocks and reports every pair of conflicting accesses that no event orders, and every launch that reads a row of the wrong
 // iteration: the class of round 4's edge-band race (a band shorter than the rows that travel), found then by a 1-in-15 flake.
 struct ChoreoOp {
-    enum { KERNEL = 0, RECORD = 1, WAIT = 2, COPY = 3, SEND = 4, RECV = 5, FORCES = 6, STATS = 7, BODIES = 8 };
+    enum { KERNEL = 0, RECORD = 1, WAIT = 2, COPY = 3, SEND = 4, RECV = 5, FORCES = 6, STATS = 7, BODIES = 8, FRAME = 9 };
     int kind = 0;
     int strip = 0, stream = 0;      // the issuing strip, 0 main / 1 side stream
     int ev_strip = 0, ev = 0;       // RECORD / WAIT: the event's owner and 0 ev_main, 1 ev_edge, 2 ev_comm
     int buf = 0;                    // KERNEL: the buffer written (it reads buf ^ 1); COPY / SEND / RECV / FORCES: the buffer touched
-    int t = 0, depth = 0;           // KERNEL: first iteration and iterations; FORCES / STATS / BODIES: the iteration
+    int t = 0, depth = 0;           // KERNEL: first iteration and iterations; FORCES / STATS / BODIES / FRAME: the iteration
     int w0[2] = {0, 0}, w1[2] = {0, 0};   // rows written, [w0, w1) in local rows (ghost rows: < 0 or >= nyl); KERNEL: two ranges
-    int r0 = 0, r1 = 0, r_strip = -1;     // COPY / SEND / FORCES / STATS / BODIES: rows read and whose (RECV: where the data comes from; -1: another process)
-                                          // (STATS: the strip's rows and ONE ghost row per face — the pull of the inlet / outlet cells of its first and last row)
+    int r0 = 0, r1 = 0, r_strip = -1;     // COPY / SEND / FORCES / STATS / BODIES / FRAME: rows read and whose (RECV: where the data comes from; -1: another process)
+                                          // (STATS: the strip's rows and ONE ghost row per face — the pull of the inlet / outlet cells of its first and last row;
+                                          //  FRAME: TWO per face — the ghost row next to the face for d/dy, whose outlet cell pulls from the row beyond it)
 };
 // ... and, for one rank of a multi-process run, the transcript of what exchange_rccl's posting loops WOULD hand to RCCL, in posting order:
 // kind 0 send / 1 recv / 2 end of a group call; `off`, `cnt` in elements of the buffer. lbm_debug_p2p_matching holds the transcripts of
@@ -267,6 +268,14 @@ struct lbm_ctx {
     double* d_body_log = nullptr;       // [log_cap][B][3]
     int body_log_head = 0, body_log_count = 0;      // samples
     int bodies_opt = 0;                 // option "bodies" (dry run only): record a body-force sample behind every force kernel
+    // Coarsened flow frames (lbm_frames_begin): a ring of frames_cap slots of [4][nyl / k][nx / k] floats (rho, ux, uy, vorticity), one
+    // written by k_frame at every force-output iteration while frames are active; the iteration of each slot is kept on the host
+    // (it is known when the sample is issued). lbm_drain_frames takes whole frames from the ring's head.
+    float* d_frames = nullptr;
+    int frames_k = 0, frames_cap = 0, frames_head = 0, frames_count = 0;
+    bool frames_active = false;
+    std::vector<int> frames_t;          // [frames_cap]
+    int frames_opt = 0;                 // option "frames" K set before lbm_initialise: begun at its end (dry run: a frame sample behind every force kernel)
     // The inflow: d_urow = the inlet velocity of every global row in the element type, read-only (step kernels, k_macros): inlet_velocity
     // on every row, or the profile of lbm_set_inlet_profile (has_profile), whose digest checkpoints carry and whose initial
     // equilibria f_eq(1,(u[y],0)), [ny][Q], k_init reads from d_feqrow.

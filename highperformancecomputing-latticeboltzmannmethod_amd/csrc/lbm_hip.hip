@@ -3,6 +3,7 @@
 #include "lbm_kernels.hpp"
 #include "lbm_col_api.hpp"
 #include "lbm_launch_k.hpp"
+#include "lbm_frames.hpp"
 #include "lbm_plan.hpp"
 #include "lbm_geom.hpp"
 #include "../../include/lbm_hip.h"
@@ -263,7 +264,7 @@ void lbm_destroy(lbm_ctx* c) {
     void* ptrs[] = {c->buf[0], c->buf[1], c->scratch, c->d_macro, c->d_maxbits, c->d_unstable, c->d_tbase, c->d_solid_count, c->d_feq,
                     c->d_force_now, c->d_force_log, c->d_halo, c->d_red, (void*)c->mview.bits, (void*)c->mview.sat, c->d_fpart,
                     c->d_urow, c->d_feqrow, c->d_stats, c->d_labels, c->d_body_box, c->d_body_chunks, c->d_body_first, c->d_body_part,
-                    c->d_body_now, c->d_body_log};
+                    c->d_body_now, c->d_body_log, c->d_frames};
     for (void* q : ptrs)
         if (q) (void)hipFree(q);
     hipEvent_t evs[] = {c->ev_edge, c->ev_comm, c->ev_main, c->ev_t0, c->ev_t1, c->gev_main, c->gev_edge, c->gev_comm};
@@ -288,6 +289,7 @@ int lbm_initialise(lbm_ctx* c, int* solid_count_out) {
     c->steps_done = 0;
     c->log_count = 0;
     c->body_log_head = c->body_log_count = 0;
+    c->frames_head = c->frames_count = 0;
     c->mid_pair = false;
     c->comm_issued = false;
     c->ext_split_pending = false;
@@ -303,7 +305,8 @@ int lbm_initialise(lbm_ctx* c, int* solid_count_out) {
     if (solid_count_out) *solid_count_out = sc;
     c->initialised = true;
     lbm_trace("initialise", "ctx %p end: %s", (void*)c, c->plan_desc);
-    if (c->stats_opt >= 0) return lbm_stats_begin(c, c->stats_opt);      // option "stats" (the plan was measured without it)
+    if (c->stats_opt >= 0) { int sr = lbm_stats_begin(c, c->stats_opt); if (sr) return sr; }      // option "stats" (the plan was measured without it)
+    if (c->frames_opt > 0) return lbm_frames_begin(c, c->frames_opt, LBM_FRAMES_DEFAULT_CAPACITY);  // option "frames", likewise
     return LBM_OK;
 }
 
@@ -496,6 +499,60 @@ int lbm_stats_restore(lbm_ctx* c, const double* sums6, int samples) {
     c->stats_n = samples;
     c->stats_active = true;
     return LBM_OK;
+}
+
+/* ---- coarsened flow frames: rho, ux, uy and vorticity block-averaged k x k into a device ring at the force-output iterations (k_frame) ---- */
+static size_t frame_floats(const lbm_ctx* c) { return 4 * (size_t)(c->nx / c->frames_k) * (size_t)(c->nyl / c->frames_k); }
+
+int lbm_frames_begin(lbm_ctx* c, int k, int capacity) {
+    if (!c || !c->initialised) return fail(LBM_ERR_ARG, "lbm_frames_begin needs an initialised context");
+    if (k < 1 || k > lbmk::FRAME_MAX_K) return fail(LBM_ERR_ARG, "frame stride k = %d outside 1..%d", k, lbmk::FRAME_MAX_K);
+    if (capacity < 1) return fail(LBM_ERR_ARG, "frame ring capacity %d < 1", capacity);
+    if (c->nx < 2 || c->p.ny < 2) return fail(LBM_ERR_ARG, "frames need nx >= 2 and ny >= 2 (the vorticity differences)");
+    if (c->nx % k) return fail(LBM_ERR_ARG, "frame stride k = %d does not divide nx = %d", k, c->nx);
+    if (c->p.y_start % k) return fail(LBM_ERR_ARG, "frame stride k = %d does not divide the strip's y_start = %d", k, c->p.y_start);
+    if (c->nyl % k) return fail(LBM_ERR_ARG, "frame stride k = %d does not divide the strip's local_ny = %d", k, c->nyl);
+    HIPCHK(hipSetDevice(c->device));
+    { int jr = join_comm(c); if (jr) return jr; }
+    HIPCHK(hipStreamSynchronize(c->stream));      // (a sample still in flight writes the ring this call replaces)
+    if (c->d_frames) { (void)hipFree(c->d_frames); c->d_frames = nullptr; }
+    c->frames_active = false;
+    c->frames_head = c->frames_count = 0;
+    c->frames_k = k; c->frames_cap = capacity;
+    const size_t bytes = frame_floats(c) * sizeof(float) * (size_t)capacity;
+    if (hipMalloc(&c->d_frames, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        c->d_frames = nullptr; c->frames_cap = 0;
+        return fail(LBM_ERR_ALLOC, "frames: no device memory for a ring of %d frames (%zu bytes)", capacity, bytes);
+    }
+    c->frames_t.assign((size_t)capacity, 0);
+    c->frames_active = true;
+    return LBM_OK;
+}
+
+int lbm_frames_end(lbm_ctx* c) {
+    if (!c) return fail(LBM_ERR_ARG, "null context");
+    c->frames_active = false;
+    return LBM_OK;
+}
+
+int lbm_frames_pending(const lbm_ctx* c) { return c ? c->frames_count : LBM_ERR_ARG; }
+
+int lbm_drain_frames(lbm_ctx* c, int* timesteps, float* frames, int max_frames) {
+    if (!c || max_frames < 0 || (max_frames > 0 && !frames)) return fail(LBM_ERR_ARG, "lbm_drain_frames: null argument or max_frames < 0");
+    if (!c->d_frames || c->frames_count < 1 || max_frames < 1) return 0;
+    HIPCHK(hipSetDevice(c->device));
+    { int jr = join_comm(c); if (jr) return jr; }
+    const int n = std::min(max_frames, c->frames_count);
+    const size_t per = frame_floats(c);
+    const int n1 = std::min(n, c->frames_cap - c->frames_head);      // the ring: up to the end of the buffer, then from its start
+    HIPCHK(hipMemcpyAsync(frames, c->d_frames + per * (size_t)c->frames_head, per * sizeof(float) * (size_t)n1, hipMemcpyDeviceToHost, c->stream));
+    if (n > n1) HIPCHK(hipMemcpyAsync(frames + per * (size_t)n1, c->d_frames, per * sizeof(float) * (size_t)(n - n1), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (timesteps) for (int j = 0; j < n; ++j) timesteps[j] = c->frames_t[(size_t)((c->frames_head + j) % c->frames_cap)];
+    c->frames_head = (c->frames_head + n) % c->frames_cap;
+    c->frames_count -= n;
+    return n;
 }
 
 int lbm_get_populations(lbm_ctx* c, int which, double* aos) {
@@ -930,6 +987,11 @@ int lbm_set_option(lbm_ctx* c, const char* key, long value) {
         if (c->initialised) return lbm_stats_begin(c, (int)value);
         c->stats_opt = (int)value;
     }
+    else if (k == "frames") {   // frames of stride K from now on: lbm_frames_begin(c, K, default capacity) now, or — not yet initialised — at the end of lbm_initialise
+        if (value < 1 || value > lbmk::FRAME_MAX_K) return fail(LBM_ERR_ARG, "frames (the stride k) must be in 1..%d", lbmk::FRAME_MAX_K);
+        if (c->initialised) return lbm_frames_begin(c, (int)value, LBM_FRAMES_DEFAULT_CAPACITY);
+        c->frames_opt = (int)value;
+    }
     else if (k == "bodies") c->bodies_opt = (int)value ? 1 : 0;      // dry run only (lbm_debug_choreography): a body-force sample behind every force kernel
     else if (k == "graph") { if (value < 0 || value > 2) return fail(LBM_ERR_ARG, "graph must be 0, 1 or 2"); c->use_graph = (int)value; }
     else if (k == "loopback") c->loopback = (int)value;   // 0 off, 1 device copies, 2 RCCL self send/recv
@@ -1149,6 +1211,7 @@ int lbm_debug_choreography(int nx, int ny, const int* bounds2, int nstrips, int 
         c->cur = 1;
         if (c->stats_opt >= 0) { c->stats_active = true; c->stats_from = c->stats_opt; }      // (no accumulators: nothing is launched)
         if (c->bodies_opt) c->body_n = 1;                                                     // (no labels either)
+        if (c->frames_opt > 0) { c->frames_active = true; c->frames_k = c->frames_opt; }      // (no ring: nothing is launched)
     }
     if (transport < 2) {
         for (int k = 0; k < nstrips; ++k) {

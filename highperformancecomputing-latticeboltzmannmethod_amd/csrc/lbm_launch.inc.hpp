@@ -227,3 +227,25 @@ int log_body_forces(lbm_ctx* c, int t) {
     return rc;
 }
 
+
+// One frame (k_frame, lbm_frames_begin) of a force-output iteration t into the next free slot of the ring: buf[cur] = P_t, the snapshot
+// that of launch_stats. Queued directly behind the force kernel on the compute stream, behind the same join. do_steps has checked
+// that the ring has room.
+template <typename T>
+int launch_frame_sample(lbm_ctx* c, int t) {
+    if (c->rec) {      // dry run: the strip's rows of P_t and two ghost rows per face (d/dy at the face; its outlet cell pulls one row further); writes its own slot
+        ChoreoOp o; o.kind = ChoreoOp::FRAME; o.strip = c->group_k; o.stream = 0; o.buf = c->cur; o.t = t; o.r0 = -2; o.r1 = c->nyl + 2; o.r_strip = c->group_k;
+        c->rec->ops.push_back(o);
+        return LBM_OK;
+    }
+    const int slot = (c->frames_head + c->frames_count) % c->frames_cap;
+    FrameArgs<T> f;
+    f.m = make_macro_args<T>(c, c->buf[c->cur]);
+    f.k = c->frames_k; f.cnx = c->nx / c->frames_k; f.cny = c->nyl / c->frames_k;
+    f.out = c->d_frames + 4 * (size_t)f.cnx * f.cny * slot;
+    launch_frame<T>(f, c->stream);
+    HIPCHK(hipGetLastError());
+    c->frames_t[(size_t)slot] = t;
+    c->frames_count++;
+    return LBM_OK;
+}

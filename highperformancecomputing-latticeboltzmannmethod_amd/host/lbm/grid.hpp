@@ -272,6 +272,39 @@ public:
         stats_restore(all, head[2]);
         return true;
     }
+    // coarsened flow frames (lbm_frames_*; the reference has none): begun on every strip; a drained frame is the strips' rows
+    // concatenated by y_start into [4][ny / k][nx / k] (rho, ux, uy, vorticity). Every strip samples at the same iterations.
+    struct CoarseFrame { int timestep; std::vector<float> planes; };
+    void frames_begin(int k, int capacity) {
+        for (lbm_ctx* c : ctx_) check(lbm_frames_begin(c, k, capacity), "lbm_frames_begin");
+        frame_k_ = k;
+    }
+    std::vector<CoarseFrame> drain_frames() const {
+        std::vector<CoarseFrame> out;
+        if (frame_k_ < 1) return out;
+        const int n = lbm_frames_pending(ctx_[0]);
+        check(n, "lbm_frames_pending");
+        const size_t cnx = static_cast<size_t>(nx_ / frame_k_), cny = static_cast<size_t>(ny_ / frame_k_);
+        out.resize((size_t)n);
+        for (auto& f : out) f.planes.resize(4 * cnx * cny);
+        std::vector<float> part;
+        std::vector<int> ts((size_t)std::max(n, 1));
+        for (size_t k = 0; k < ctx_.size() && n > 0; ++k) {
+            const size_t rows = static_cast<size_t>(nyl_[k] / frame_k_), y0 = static_cast<size_t>(y0_[k] / frame_k_);
+            part.resize((size_t)n * 4 * rows * cnx);
+            const int got = lbm_drain_frames(ctx_[k], ts.data(), part.data(), n);
+            check(got, "lbm_drain_frames");
+            if (got != n) throw std::runtime_error("the strips disagree on the number of pending frames");
+            for (int j = 0; j < n; ++j) {
+                if (k == 0) out[(size_t)j].timestep = ts[(size_t)j];
+                else if (out[(size_t)j].timestep != ts[(size_t)j]) throw std::runtime_error("the strips disagree on the iteration of a frame");
+                for (size_t pl = 0; pl < 4; ++pl)
+                    std::copy(part.begin() + ((size_t)j * 4 + pl) * rows * cnx, part.begin() + ((size_t)j * 4 + pl + 1) * rows * cnx,
+                              out[(size_t)j].planes.begin() + pl * cny * cnx + y0 * cnx);
+            }
+        }
+        return out;
+    }
     const char* plan() const { return lbm_plan(ctx_[0]); }
     lbm_ctx* handle(int k = 0) const { return ctx_[(size_t)k]; }
 
@@ -333,6 +366,7 @@ private:
     mutable bool macros_ok_ = false;
     mutable bool f_ok_[2] = {false, false};
     bool fc_dirty_ = false;
+    int frame_k_ = 0;
 };
 
 }  // namespace LBM

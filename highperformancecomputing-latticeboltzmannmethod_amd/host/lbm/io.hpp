@@ -114,6 +114,38 @@ public:
         f.put("\nSCALARS density double\nLOOKUP_TABLE default\n");
         for (size_t k = 0; k < n; ++k) { f.put_f8(rho_g[k]); f.put("\n"); }
     }
+    // A coarsened frame of lbm_solver --frame-stride K (the reference has none): vtk_output/frame_%06d.vtk, legacy ASCII
+    // STRUCTURED_POINTS of nx / K x ny / K points at the centres of the K x K blocks (spacing K), from the planes [4][ny / K][nx / K]
+    // rho, ux, uy, vorticity of lbm_drain_frames: vector `velocity`, scalars `density` and `vorticity`.
+    static void write_frame_vtk(const std::vector<float>& planes, const SimulationParams& p, int timestep) {
+        char name[256];
+        std::snprintf(name, sizeof(name), "vtk_output/frame_%06d.vtk", timestep);
+        detail::TextFile f(name);
+        if (!f.ok()) { std::fprintf(stderr, "ERROR: Cannot write %s\n", name); return; }
+        const int K = p.frame_stride, cnx = p.nx / K, cny = p.ny / K;
+        const size_t n = static_cast<size_t>(cnx) * cny;
+        char origin[64];
+        std::snprintf(origin, sizeof(origin), "%g %g 0", 0.5 * (K - 1), 0.5 * (K - 1));
+        f.put("# vtk DataFile Version 3.0\nLBM Flow Frame Timestep "); f.put_int(timestep);
+        f.put("\nASCII\nDATASET STRUCTURED_POINTS\nDIMENSIONS "); f.put_int(cnx); f.put(" "); f.put_int(cny);
+        f.put(" 1\nORIGIN "); f.put(origin); f.put("\nSPACING "); f.put_int(K); f.put(" "); f.put_int(K); f.put(" 1\nPOINT_DATA "); f.put_int((long)n);
+        f.put("\nVECTORS velocity float\n");
+        for (size_t k = 0; k < n; ++k) { f.put_f8(planes[n + k]); f.put(" "); f.put_f8(planes[2 * n + k]); f.put(" 0.0\n"); }
+        f.put("\nSCALARS density float\nLOOKUP_TABLE default\n");
+        for (size_t k = 0; k < n; ++k) { f.put_f8(planes[k]); f.put("\n"); }
+        f.put("\nSCALARS vorticity float\nLOOKUP_TABLE default\n");
+        for (size_t k = 0; k < n; ++k) { f.put_f8(planes[3 * n + k]); f.put("\n"); }
+    }
+    // ... through the writer thread's queue, like a full-resolution frame
+    void write_frame_async(std::vector<float> planes, const SimulationParams& p, int timestep) {
+        std::unique_lock<std::mutex> lk(mu_);
+        cv_.wait(lk, [&] { return queue_.size() < 2; });
+        Frame fr;
+        fr.coarse = std::move(planes); fr.p = p; fr.t = timestep;
+        queue_.push_back(std::move(fr));
+        if (!writer_.joinable()) writer_ = std::thread([this] { writer_loop(); });
+        cv_.notify_all();
+    }
     // Asynchronous frame: the three fields are moved to a writer thread, at most 2 frames queued.
     void write_vtk_async(std::vector<double> ux, std::vector<double> uy, std::vector<double> rho,
                          const SimulationParams& p, int timestep) {
@@ -193,7 +225,7 @@ public:
     const std::vector<ForceSample>& samples() const { return samples_; }
 
 private:
-    struct Frame { std::vector<double> ux, uy, rho; SimulationParams p; int t; };
+    struct Frame { std::vector<double> ux, uy, rho; SimulationParams p; int t; std::vector<float> coarse; };   // coarse non-empty: a --frame-stride frame
 
     void writer_loop() {
         for (;;) {
@@ -204,7 +236,8 @@ private:
                 if (queue_.empty()) return;
                 fr = std::move(queue_.front());
             }
-            write_vtk_timestep(fr.ux, fr.uy, fr.rho, fr.p, fr.t);
+            if (!fr.coarse.empty()) write_frame_vtk(fr.coarse, fr.p, fr.t);
+            else write_vtk_timestep(fr.ux, fr.uy, fr.rho, fr.p, fr.t);
             {
                 std::unique_lock<std::mutex> lk(mu_);
                 queue_.pop_front();
@@ -252,6 +285,7 @@ private:
         }
         if (p.profiled()) { f.put("inlet_profile,"); f.put(p.inlet_profile_spec.c_str()); f.put("\n"); }   // (profiled runs only, likewise)
         if (p.les()) row_d("smagorinsky_cs", p.smagorinsky_cs);                                            // (LES runs only, likewise)
+        if (p.frames()) row_i("frame_stride", p.frame_stride);                                             // (runs with --frame-stride only, likewise)
         std::printf("  simulation_params.csv written\n");
     }
     // calculate_time_averaged_drag (LBMIO.h:367-413): statistics of the CSV values (8 decimals) for timestep > 1000.

@@ -49,6 +49,10 @@ struct SimulationParams {
     // time-averaged statistics (lbm_solver --stats-start; not in the reference): the first step sampled, -1 = off. Samples are taken on
     // the device at the output_frequency cadence (lbm_stats_begin); the run ends with mean_fields.vtk / mean_fields.csv.
     int stats_start = -1;
+    // coarsened flow frames (lbm_solver --frame-stride; not in the reference): the stride K of the k x k block averages, 0 = off. One
+    // frame (rho, ux, uy, vorticity) is written on the device at every output iteration (lbm_frames_begin) and drained into
+    // vtk_output/frame_%06d.vtk; the full-resolution fields are not fetched for it.
+    int frame_stride = 0;
 
     double nu() const { return (tau - 0.5) / 3.0; }
     bool masked() const { return !obstacle_mask.empty(); }
@@ -57,6 +61,7 @@ struct SimulationParams {
     bool profiled() const { return !inlet_profile.empty(); }
     bool les() const { return smagorinsky_cs > 0.0; }
     bool stats() const { return stats_start >= 0; }
+    bool frames() const { return frame_stride > 0; }
     double reynolds() const {
         if (masked()) return inlet_velocity * mask_frontal_height / nu();
         return inlet_velocity * (2.0 * cylinder_radius * ny) / nu();

@@ -15,7 +15,7 @@ class Solver {
 public:
     explicit Solver(const SimulationParams& params, bool enable_vtk = false, const BackendOptions& opt = {})
         : params_(params), opt_(opt), grid_(params, opt), enable_vtk_output_(enable_vtk) {
-        if (enable_vtk) mkdir("vtk_output", 0755);   // LBMSolver.h:26-28
+        if (enable_vtk || params.frames()) mkdir("vtk_output", 0755);   // LBMSolver.h:26-28
     }
 
     void initialise() {   // LBMSolver.h:31-41
@@ -28,6 +28,12 @@ public:
             grid_.stats_begin(params_.stats_start);
             if (!opt_.quiet)
                 std::printf("  Statistics: time averages from step %d on, one sample every %d steps\n", params_.stats_start, params_.output_frequency);
+        }
+        if (params_.frames()) {      // (two frames per chunk of run(): iterations 0 and output_frequency fall into the first one)
+            grid_.frames_begin(params_.frame_stride, 4);
+            if (!opt_.quiet)
+                std::printf("  Frames: rho, u and vorticity averaged over %dx%d cells, one every %d steps (vtk_output/frame_*.vtk)\n", params_.frame_stride,
+                            params_.frame_stride, params_.output_frequency);
         }
         if (!opt_.quiet && params_.profiled())
             std::printf("  Inlet: profile %s, mean velocity %g (Cd / Cl refer to it)\n", params_.inlet_profile_spec.c_str(), params_.inlet_velocity);
@@ -78,6 +84,11 @@ public:
                 if (bad < 0 || r.timestep <= bad) io.append_force_row(r.timestep, r.fx, r.fy, params_);
             for (const auto& r : grid_.drain_body_force_log())
                 if (bad < 0 || r.timestep <= bad) io.append_body_force_row(r.timestep, r.body, r.fx, r.fy, params_);
+            for (auto& fr : grid_.drain_frames()) {      // the coarsened frames of this chunk: no full-resolution field is fetched for them
+                if (bad >= 0 && fr.timestep > bad) continue;
+                if (opt_.async_vtk) io.write_frame_async(std::move(fr.planes), params_, fr.timestep);
+                else IOManager::write_frame_vtk(fr.planes, params_, fr.timestep);
+            }
             if (bad >= 0) {
                 std::fprintf(stderr, "Simulation unstable at timestep %d\n", bad);
                 return false;

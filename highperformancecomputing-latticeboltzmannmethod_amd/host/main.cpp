@@ -21,6 +21,7 @@ static void usage() {
               "           [--gpus N] [--strips N] [--rccl]\n"
               "           [--checkpoint FILE] [--restart FILE] [--obstacle-mask FILE.pgm] [--obstacle-bodies FILE.pgm]\n"
               "           [--inlet-profile parabolic|FILE] [--print-inlet-profile] [--smagorinsky CS] [--stats-start N]\n"
+              "           [--frame-stride K]\n"
               "Defaults are the reference's SimulationParams (LBMConfig.h:37-51). --reynolds sets the inlet velocity\n"
               "from tau and the cylinder diameter so that params.reynolds() equals RE.\n"
               "--gpus N cuts the lattice into N row strips, one per GPU of this node, advanced in lockstep by this process\n"
@@ -42,7 +43,11 @@ static void usage() {
               "--stats-start N: time-averaged statistics from step N on, sampled on the device every --output-frequency steps;\n"
               "the run ends with mean_fields.vtk and mean_fields.csv (means of rho, ux, uy and the Reynolds stresses). With\n"
               "--checkpoint / --restart the sums travel beside the checkpoint as FILE.stats. --no-final suppresses the two\n"
-              "mean_fields files like the other end-of-run fields (FILE.stats is still written with --checkpoint).");
+              "mean_fields files like the other end-of-run fields (FILE.stats is still written with --checkpoint).\n"
+              "--frame-stride K: at every output iteration the device averages rho, ux, uy and the vorticity d uy/dx - d ux/dy over\n"
+              "K x K cells (1 <= K <= 64; K must divide nx, ny and the rows of every strip) and the frame is written as\n"
+              "vtk_output/frame_%06d.vtk (STRUCTURED_POINTS, spacing K; vector velocity, scalars density and vorticity), also with\n"
+              "--no-vtk: 4 nx ny / K^2 floats per frame leave the device instead of the full-resolution fields.");
 }
 
 int main(int argc, char** argv) {
@@ -53,6 +58,7 @@ int main(int argc, char** argv) {
     bool print_profile = false;
     const char* smagorinsky = nullptr;
     const char* stats_start = nullptr;
+    const char* frame_stride = nullptr;
     double reynolds = -1.0;
     for (int a = 1; a < argc; ++a) {
         const std::string k = argv[a];
@@ -90,6 +96,7 @@ int main(int argc, char** argv) {
         else if (k == "--print-inlet-profile") print_profile = true;
         else if (k == "--smagorinsky") smagorinsky = val();
         else if (k == "--stats-start") stats_start = val();
+        else if (k == "--frame-stride") frame_stride = val();
         else if (k == "--help" || k == "-h") { usage(); return 0; }
         else { std::fprintf(stderr, "unknown option %s\n", k.c_str()); usage(); return 2; }
     }
@@ -114,6 +121,33 @@ int main(int argc, char** argv) {
             return 2;
         }
         params.stats_start = (int)n;
+    }
+    if (frame_stride) {   // checked before any device is touched: a whole number in 1..64 that divides nx and every strip's rows
+        char* end = nullptr;
+        const long K = std::strtol(frame_stride, &end, 10);
+        if (end == frame_stride || *end != '\0' || K < 1 || K > 64) {
+            std::fprintf(stderr, "--frame-stride: '%s' is not a whole number in 1..64\n", frame_stride);
+            return 2;
+        }
+        if (params.output_frequency <= 0) {
+            std::fprintf(stderr, "--frame-stride needs --output-frequency > 0: frames are written at the output cadence\n");
+            return 2;
+        }
+        if (params.nx < 2 || params.ny < 2 || params.nx % K != 0 || params.ny % K != 0) {
+            std::fprintf(stderr, "--frame-stride: %ld does not divide the lattice %dx%d\n", K, params.nx, params.ny);
+            return 2;
+        }
+        // the row strips as Grid cuts them (the first ny % n strips get one more row)
+        const int nstrips = std::min(params.ny, opt.strips > 0 ? opt.strips : std::max(1, opt.gpus));
+        for (int s = 0, y = 0; s < nstrips; ++s) {
+            const int rows = params.ny / nstrips + (s < params.ny % nstrips ? 1 : 0);
+            if (y % K != 0 || rows % K != 0) {
+                std::fprintf(stderr, "--frame-stride: %ld does not divide the rows of strip %d of %d (rows %d..%d)\n", K, s, nstrips, y, y + rows - 1);
+                return 2;
+            }
+            y += rows;
+        }
+        params.frame_stride = (int)K;
     }
     if (!params.obstacle_bodies_file.empty() && !params.obstacle_mask_file.empty()) {
         std::fprintf(stderr, "--obstacle-bodies and --obstacle-mask exclude each other: the labels are the mask\n");

@@ -164,6 +164,35 @@ int  lbm_get_stat_sums(lbm_ctx* c, double* sums6);
  * averages through this call. */
 int  lbm_stats_restore(lbm_ctx* c, const double* sums6, int samples);
 
+/* ---- coarsened flow frames with vorticity (no reference counterpart: the reference gathers full-resolution fields for every VTK frame,
+ * LBMSolver.h:340-357, and scripts/visualise_results.py recomputes the vorticity on the host from velocity_field.csv; what this replaces
+ * is a caller's lbm_step(c, n, 0) + lbm_get_macros per picture: a synchronisation and 3 nx local_ny doubles over the bus each time) ----
+ * The FRAME of iteration t with stride k is four planes [local_ny / k][nx / k] of float, in the order rho, ux, uy, vorticity. Fine
+ * fields: (rho, ux, uy) are, cell for cell, what lbm_get_macros returns on a context with steps_done == t + 1 (the statistics sample's
+ * definition; fp32 contexts widen to double first). Vorticity w = d uy / dx - d ux / dy on the fine grid in double: the central
+ * difference 0.5 * (v[x+1] - v[x-1]) inside, the one-sided v[1] - v[0] and v[n-1] - v[n-2] on the four edges of the DOMAIN (global
+ * columns 0, nx - 1 and rows 0, ny - 1; a strip face is interior: the neighbour's row comes from the ghost rows); solid cells enter with
+ * their (0, 0) and get their w by the same formula. Each coarse value is the mean over its k x k fine cells: summed in double (per fine
+ * column bottom to top, then the k columns left to right), divided by k * k, rounded once to float. The order depends on k alone: every
+ * plan, layout, arithmetic mode and strip decomposition gives the same bits for the same macros. k = 1: the fine grid plus w.
+ * With frames active lbm_step / lbm_group_step append one frame to a device ring at exactly the iterations at which they append a
+ * force-log row (output_frequency > 0 and t % output_frequency == 0), directly behind the force kernel, without a synchronisation;
+ * with the ring full they fail like the force logs (LBM_ERR_ARG, "frame ring full ...: drain it"). Frames change reporting only:
+ * populations, force logs, statistics, checkpoints (which do not carry frames) and lbm_kernel_name are those of a run without.
+ * lbm_frames_begin: on an initialised context; 1 <= k <= 64, and nx, the strip's y_start and its local_ny multiples of k; capacity >= 1
+ * frames. Allocates the ring (4 (nx / k) (local_ny / k) floats per frame; freed by lbm_destroy); calling it again — or lbm_initialise —
+ * empties the ring. LBM_ERR_ARG (the text names the offending quantity) otherwise; LBM_ERR_ALLOC: no device memory for the ring.
+ * (lbm_set_option "frames" K: the same with LBM_FRAMES_DEFAULT_CAPACITY frames.) */
+#define LBM_FRAMES_DEFAULT_CAPACITY 8
+int  lbm_frames_begin(lbm_ctx* c, int k, int capacity);
+/* Stops sampling and keeps the undrained frames. */
+int  lbm_frames_end(lbm_ctx* c);
+/* Frames in the ring that have not been drained (in a group: the same on every member). */
+int  lbm_frames_pending(const lbm_ctx* c);
+/* Copies up to max_frames whole frames, oldest first, as [n][4][local_ny / k][nx / k] floats, their iterations into timesteps (may be
+ * NULL), removes them from the ring and returns n. Synchronises. 0 when frames were never begun or none is pending. */
+int  lbm_drain_frames(lbm_ctx* c, int* timesteps, float* frames, int max_frames);
+
 /* Debug/parity accessor: ghost-inclusive AoS [(local_ny+2)][(nx+2)][9] exactly as Grid::f_current /
  * Grid::f_next index it (LBMGrid.h:105-107,116-119). which: 0 = f_current, 1 = f_next. */
 int  lbm_get_populations(lbm_ctx* c, int which, double* aos);
@@ -299,6 +328,8 @@ int  lbm_load_state(lbm_ctx* c, const char* path);
  *                 transport is local to the process, 2 also between the ranks of a communicator (RCCL under capture:
  *                 exercised with a one-rank communicator only so far)
  *   "stats" N     lbm_stats_begin(c, N) (before lbm_initialise: begun at its end)
+ *   "frames" K    lbm_frames_begin(c, K, LBM_FRAMES_DEFAULT_CAPACITY) (before lbm_initialise: begun at its end). In
+ *                 lbm_debug_choreography: the dry run records a frame sample behind every force kernel
  *   "bodies" 1    lbm_debug_choreography only: the dry run records a per-body force sample behind every force kernel (a real context
  *                 gets its bodies from lbm_set_body_labels and ignores the key)
  *   "timing" 1    record HIP events around each lbm_step call (lbm_last_step_kernel_ms). */
@@ -355,7 +386,9 @@ int lbm_debug_group_pool(int n, int rounds, int fail_strip, int fail_round, int 
  * record every kernel (with the rows it writes and, through its depth, reads), event record, cross-stream wait, copy, send and receive;
  * the record is replayed with vector clocks. Returns the number of violations — RACE: two accesses to the same row of the same buffer, at
  * least one of them a write, that no event orders; STALE: a launch (or the force kernel, or — option "stats" — the statistics sample, which
- * also reads one ghost row per face, or — option "bodies" — the per-body force sample, which reads the force kernel's rows and writes a log slot of its own) reads a row that does not hold the iteration it
+ * also reads one ghost row per face, or — option "bodies" — the per-body force sample, which reads the force kernel's rows and writes a log slot of its own, or — option "frames" —
+ * the frame sample, which reads the force kernel's rows plus TWO ghost rows per face (the ghost row next to the face for d/dy, and the
+ * row beyond it that this row's outlet cell pulls from) and writes a ring slot of its own) reads a row that does not hold the iteration it
  * needs — or < 0; `out` receives their description (and, with dump != 0, every recorded operation). What it replaces: the ordering the
  * reference gets from MPI_Waitall before unpack_received_data (LBMGrid.h:278-283).
  * bounds2 = nstrips x {y_start, rows}; transport 0 in-process group with peer copies, 1 in-process group over RCCL, 2 ONE strip as a rank
