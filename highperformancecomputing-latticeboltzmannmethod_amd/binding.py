@@ -78,6 +78,7 @@ def lib():
                                             C.POINTER(C.c_long), C.c_int, C.POINTER(C.c_int)]
         L.lbm_set_inlet_profile.argtypes = [vp, dp, C.c_int]
         L.lbm_set_smagorinsky.argtypes = [vp, C.c_double]
+        L.lbm_set_trt.argtypes = [vp, C.c_double]
         ip = C.POINTER(C.c_int)
         L.lbm_debug_geometry.argtypes = [C.POINTER(C.c_ubyte), C.c_int, C.c_int, C.c_int, C.c_int, ip, C.POINTER(C.c_ulonglong), C.c_long,
                                          ip, C.c_long, ip, C.c_int, ip]
@@ -248,14 +249,16 @@ class Context:
     y = 0 first, nonzero = solid (lbm_set_solid_mask): the obstacle geometry in place of the cylinder_* disc. inlet_profile: optional
     float64 [ny] of absolute inlet x-velocities of the WHOLE domain, row y = 0 first (lbm_set_inlet_profile), in place of the
     uniform inlet_velocity (see parabolic_profile). smagorinsky: optional constant Cs of a Smagorinsky LES collision
-    (lbm_set_smagorinsky) in place of plain BGK; 0 / None: BGK. bodies: optional integer (ny, nx) array of body numbers of the WHOLE
+    (lbm_set_smagorinsky) in place of plain BGK; 0 / None: BGK. trt_magic: optional magic parameter of a two-relaxation-time
+    collision (lbm_set_trt; 1/4 most stable, 3/16 most accurate at walls) in place of plain BGK; 0 / None: BGK; not with smagorinsky.
+    bodies: optional integer (ny, nx) array of body numbers of the WHOLE
     domain (0 fluid, 1..255; lbm_set_body_labels): the geometry of solid=(bodies != 0) plus forces per body (body_forces,
     drain_body_force_log); not together with solid. frames: optional stride k of coarsened flow frames (lbm_frames_begin with the
     default capacity at the end of initialise(); see frames_begin)."""
 
     def __init__(self, nx, ny, tau=0.6, inlet_velocity=0.01333, cylinder_x=0.2, cylinder_y=0.5,
                  cylinder_radius=0.05, y_start=0, local_ny=0, precision="f64", device=0, force_log_capacity=0,
-                 options=None, solid=None, inlet_profile=None, smagorinsky=None, bodies=None, frames=None):
+                 options=None, solid=None, inlet_profile=None, smagorinsky=None, bodies=None, frames=None, trt_magic=None):
         if solid is not None and bodies is not None:
             raise LbmError("solid= and bodies= exclude each other: the body labels are the geometry (solid where nonzero)")
         self.L = lib()
@@ -278,6 +281,8 @@ class Context:
             self.set_inlet_profile(inlet_profile)
         if smagorinsky is not None:
             self.set_smagorinsky(smagorinsky)
+        if trt_magic is not None:
+            self.set_trt(trt_magic)
         if frames is not None:
             self.set_option("frames", frames)
 
@@ -346,6 +351,10 @@ class Context:
     def set_smagorinsky(self, cs):
         """lbm_set_smagorinsky: the Smagorinsky constant Cs in [0, 1] (0: plain BGK); before initialise()."""
         self._chk(self.L.lbm_set_smagorinsky(self.h, float(cs)))
+
+    def set_trt(self, magic):
+        """lbm_set_trt: the TRT magic parameter (tau - 1/2)(tau_minus - 1/2) in [0, 1] (0: plain BGK); before initialise()."""
+        self._chk(self.L.lbm_set_trt(self.h, float(magic)))
 
     def initialise(self):
         n = C.c_int()
@@ -536,18 +545,18 @@ class Group:
     """n strips of one lattice driven in lockstep by this process (lbm_group_*): one Context per strip, bottom to top.
     transport: "peer" (device copies / hipMemcpyPeerAsync) or "rccl" (ncclCommInitAll; distinct devices).
     solid: optional global (ny, nx) obstacle mask, inlet_profile: optional global [ny] inlet velocities, smagorinsky: optional LES
-    constant Cs, bodies: optional global (ny, nx) body numbers (in place of solid), frames: optional frame stride k; all given to every
+    constant Cs, trt_magic: optional TRT magic parameter, bodies: optional global (ny, nx) body numbers (in place of solid), frames: optional frame stride k; all given to every
     member."""
 
     def __init__(self, nx, ny, bounds, devices=None, transport="peer", options=None, solid=None, inlet_profile=None, smagorinsky=None,
-                 bodies=None, frames=None, **kw):
+                 bodies=None, frames=None, trt_magic=None, **kw):
         from .strips import partition_rows
         if isinstance(bounds, int):
             bounds = partition_rows(ny, bounds)
         devices = devices or [0] * len(bounds)
         self.nx, self.ny = nx, ny
         self.ctxs = [Context(nx, ny, y_start=y0, local_ny=n, device=d, options=options, solid=solid, inlet_profile=inlet_profile,
-                             smagorinsky=smagorinsky, bodies=bodies, frames=frames, **kw)
+                             smagorinsky=smagorinsky, bodies=bodies, frames=frames, trt_magic=trt_magic, **kw)
                      for (y0, n), d in zip(bounds, devices)]
         self.L = lib()
         self._arr = (C.c_void_p * len(self.ctxs))(*[c.h for c in self.ctxs])

@@ -1,7 +1,8 @@
 // csrc/lbm_col.hip — the translation unit(s) of k_stepc_col (lbm_kernel_col.hpp): its 26 instantiations (five / six iterations x
 // store policy + seven iterations, x arithmetic x element type: ten per element type and object file, plus the tall fp32 ones, three per
 // arithmetic mode and object file) and the launchers lbm_hip.hip calls (lbm_col_api.hpp). Four objects from this one source (build.py),
-// and two more with -DLBM_COL_LES=1: the ten Smagorinsky instantiations per element type (no tall ones).
+// and two more each with -DLBM_COL_LES=1 / -DLBM_COL_TRT=1: the ten Smagorinsky / two-relaxation-time instantiations per element type
+// (no tall ones).
 #include "lbm_kernel_col.hpp"
 #include "lbm_col_api.hpp"
 
@@ -18,6 +19,9 @@ namespace lbmk {
 #if defined(LBM_COL_LES) && LBM_COL_LES
 #define LBM_COL_FN launch_col_les
 constexpr int ARS = AR_STRICT_LES, ARC = AR_CONTRACTED_LES;
+#elif defined(LBM_COL_TRT) && LBM_COL_TRT   // -DLBM_COL_TRT=1: likewise with the TRT arithmetic values (launch_col_trt)
+#define LBM_COL_FN launch_col_trt
+constexpr int ARS = AR_STRICT_TRT, ARC = AR_CONTRACTED_TRT;
 #else
 #define LBM_COL_FN launch_col
 constexpr int ARS = AR_STRICT, ARC = AR_CONTRACTED;
@@ -48,7 +52,7 @@ void launch_col_tall_strict(const KArgs<float>& a, const K2Extra<float>& e, int 
     if (depth == 6) LBM_KC(float, 6, R, W, false, AR); else if (depth == 8) LBM_KC(float, 8, R, W, false, AR); else LBM_KC(float, 7, R, W, false, AR);
 }
 #else
-#error "compile with -DLBM_COL_T=double, -DLBM_COL_T=float (either with or without -DLBM_COL_LES=1), -DLBM_COL_TALL=1 or -DLBM_COL_TALL=0"
+#error "compile with -DLBM_COL_T=double, -DLBM_COL_T=float (either alone, with -DLBM_COL_LES=1 or with -DLBM_COL_TRT=1), -DLBM_COL_TALL=1 or -DLBM_COL_TALL=0"
 #endif
 #undef LBM_KC
 

@@ -38,6 +38,9 @@ void launch_col(const KArgs<T>& a, const K2Extra<T>& e, int depth, bool nt, bool
 // ... the same with the Smagorinsky arithmetic (AR_STRICT_LES / AR_CONTRACTED_LES; lbm_col.hip -DLBM_COL_T=... -DLBM_COL_LES=1)
 template <typename T>
 void launch_col_les(const KArgs<T>& a, const K2Extra<T>& e, int depth, bool nt, bool contracted, hipStream_t s);
+// ... and with the two-relaxation-time arithmetic (AR_STRICT_TRT / AR_CONTRACTED_TRT; lbm_col.hip -DLBM_COL_T=... -DLBM_COL_TRT=1)
+template <typename T>
+void launch_col_trt(const KArgs<T>& a, const K2Extra<T>& e, int depth, bool nt, bool contracted, hipStream_t s);
 // ... and on the tall fp32 regions, depth 6, 7 or 8, plain stores only (non-temporal ones cost 14 % there); one object file per
 // arithmetic mode (lbm_col.hip -DLBM_COL_TALL=1 contracted / 0 strict: eight unrolled rows x up to eight levels compile slowly)
 void launch_col_tall_contracted(const KArgs<float>& a, const K2Extra<float>& e, int depth, hipStream_t s);

@@ -296,6 +296,8 @@ struct lbm_ctx {
                          // one reciprocal, as the reference's -ffast-math -mfma build permits); see lbm_kernels.hpp Arith
     bool les = false;    // Smagorinsky LES collision (lbm_set_smagorinsky, constant les_cs > 0): the LES instantiations of every step family
     double les_cs = 0.0;
+    bool trt = false;    // two-relaxation-time collision (lbm_set_trt, magic parameter trt_magic > 0): the TRT instantiations; never with les
+    double trt_magic = 0.0;
     int num_cus = 256;   // compute units of the device (what counts as a small grid: one round of blocks)
     int loopback = 0;    // TEST ONLY: the strip is its own north and south neighbour (exercises the overlap choreography):
                          // 1 = device copies, 2 = RCCL send/recv to self on a one-rank communicator

@@ -88,6 +88,8 @@ int upload_rows(const lbm_ctx* c, void* dst, const double* v, size_t n) {
 // same profile digest (and the same mask digest, or none where it has no mask). Contexts without a profile never write or read it.
 // A Smagorinsky (LES) context (lbm_set_smagorinsky) writes "LBMCKPT3" too, with flag bit 2 set and its constant Cs as a double after
 // the digests; it loads only a file with the same Cs, and a BGK context only a file without bit 2.
+// A TRT context (lbm_set_trt) writes "LBMCKPT3" with flag bit 3 set and its magic parameter as a double after the slot where Cs would
+// stand; it loads only a file with the same magic parameter, and a context without TRT only a file without bit 3.
 namespace {
 struct CkptHeader {
     char magic[8];
@@ -281,6 +283,7 @@ int lbm_initialise(lbm_ctx* c, int* solid_count_out) {
     if (!c) return fail(LBM_ERR_ARG, "null context");
     lbm_trace("initialise", "ctx %p %dx%d rows %d..%d begin", (void*)c, c->nx, c->p.ny, c->p.y_start, c->p.y_start + c->nyl);
     if (c->les && deep_is_tall(c->deep)) return fail(LBM_ERR_ARG, "deep 8 (64x48 regions in registers) has no Smagorinsky (LES) kernel");
+    if (c->trt && deep_is_tall(c->deep)) return fail(LBM_ERR_ARG, "deep 8 (64x48 regions in registers) has no two-relaxation-time (TRT) kernel");
     HIPCHK(hipSetDevice(c->device));
     { int wr = wait_stream(c, c->stream, "compute stream (lbm_initialise)"); if (wr) return wr; }        // (re-)initialisation starts from quiet streams
     { int wr = wait_stream(c, c->comm_stream, "exchange stream (lbm_initialise)"); if (wr) return wr; }
@@ -691,8 +694,24 @@ int lbm_set_smagorinsky(lbm_ctx* c, double cs) {
     if (!c) return fail(LBM_ERR_ARG, "lbm_set_smagorinsky: null context");
     if (c->initialised) return fail(LBM_ERR_ARG, "lbm_set_smagorinsky must be called before lbm_initialise");
     if (!std::isfinite(cs) || cs < 0.0 || cs > 1.0) return fail(LBM_ERR_ARG, "lbm_set_smagorinsky: Cs = %g (finite values in [0, 1] only)", cs);
+    if (cs > 0.0 && c->trt)
+        return fail(LBM_ERR_ARG, "lbm_set_smagorinsky: Cs = %g on a context with TRT magic parameter %g (the two collisions cannot be combined)", cs, c->trt_magic);
     c->les = cs > 0.0;              // 0: off, the BGK kernels
     c->les_cs = c->les ? cs : 0.0;
+    return LBM_OK;
+}
+
+int lbm_set_trt(lbm_ctx* c, double magic) {
+    if (!c) return fail(LBM_ERR_ARG, "lbm_set_trt: null context");
+    if (c->initialised) return fail(LBM_ERR_ARG, "lbm_set_trt must be called before lbm_initialise");
+    if (!std::isfinite(magic) || magic < 0.0 || magic > 1.0)
+        return fail(LBM_ERR_ARG, "lbm_set_trt: magic parameter = %g (finite values in [0, 1] only)", magic);
+    if (magic > 0.0 && !(c->p.tau > 0.5)) return fail(LBM_ERR_ARG, "lbm_set_trt: tau = %g (the magic parameter needs tau > 0.5)", c->p.tau);
+    if (magic > 0.0 && c->les)
+        return fail(LBM_ERR_ARG, "lbm_set_trt: magic parameter %g on a context with Smagorinsky constant Cs = %g (the two collisions cannot be combined)", magic, c->les_cs);
+    if (magic > 0.0 && deep_is_tall(c->deep)) return fail(LBM_ERR_ARG, "deep 8 (64x48 regions in registers) has no two-relaxation-time (TRT) kernel");
+    c->trt = magic > 0.0;           // 0: off, the BGK kernels
+    c->trt_magic = c->trt ? magic : 0.0;
     return LBM_OK;
 }
 
@@ -874,18 +893,19 @@ int lbm_save_state(lbm_ctx* c, const char* path) {
     FILE* fp = fopen(path, "wb");
     if (!fp) return fail(LBM_ERR_ARG, "cannot open %s for writing", path);
     CkptHeader h{};
-    memcpy(h.magic, c->has_profile || c->les ? "LBMCKPT3" : c->has_mask ? "LBMCKPT2" : "LBMCKPT1", 8);
+    memcpy(h.magic, c->has_profile || c->les || c->trt ? "LBMCKPT3" : c->has_mask ? "LBMCKPT2" : "LBMCKPT1", 8);
     h.nx = c->nx; h.ny = c->p.ny; h.y_start = c->p.y_start; h.local_ny = c->nyl; h.precision = c->p.precision;
     h.steps_done = c->steps_done; h.tau = c->p.tau; h.inlet_velocity = c->p.inlet_velocity;
     h.cylinder_x = c->p.cylinder_x; h.cylinder_y = c->p.cylinder_y; h.cylinder_radius = c->p.cylinder_radius;
     int rc = fwrite(&h, sizeof(h), 1, fp) == 1 ? LBM_OK : fail(LBM_ERR_ARG, "short write");
-    if (!rc && (c->has_profile || c->les)) {   // LBMCKPT3: flags, then the digests they announce, then Cs
-        const unsigned long long flags = (c->has_mask ? 1ull : 0ull) | (c->has_profile ? 2ull : 0ull) | (c->les ? 4ull : 0ull);
+    if (!rc && (c->has_profile || c->les || c->trt)) {   // LBMCKPT3: flags, then the digests they announce, then Cs, then the TRT magic parameter
+        const unsigned long long flags = (c->has_mask ? 1ull : 0ull) | (c->has_profile ? 2ull : 0ull) | (c->les ? 4ull : 0ull) | (c->trt ? 8ull : 0ull);
         if (fwrite(&flags, sizeof(flags), 1, fp) != 1) rc = fail(LBM_ERR_ARG, "short write");
     }
     if (!rc && c->has_mask && fwrite(&c->hmask.digest, sizeof(c->hmask.digest), 1, fp) != 1) rc = fail(LBM_ERR_ARG, "short write");
     if (!rc && c->has_profile && fwrite(&c->prof_digest, sizeof(c->prof_digest), 1, fp) != 1) rc = fail(LBM_ERR_ARG, "short write");
     if (!rc && c->les && fwrite(&c->les_cs, sizeof(c->les_cs), 1, fp) != 1) rc = fail(LBM_ERR_ARG, "short write");
+    if (!rc && c->trt && fwrite(&c->trt_magic, sizeof(c->trt_magic), 1, fp) != 1) rc = fail(LBM_ERR_ARG, "short write");
     if (!rc) rc = DISPATCH(c, do_save<double>(c, fp), do_save<float>(c, fp));
     fclose(fp);
     return rc;
@@ -909,15 +929,18 @@ int lbm_load_state(lbm_ctx* c, const char* path) {
     CkptHeader h{};
     int rc = LBM_OK;
     unsigned long long digest = 0, flags = 0, pdigest = 0;
-    double cs = 0.0;
+    double cs = 0.0, magic = 0.0;
     const bool head = fread(&h, sizeof(h), 1, fp) == 1;
     const bool v1 = head && memcmp(h.magic, "LBMCKPT1", 8) == 0;
     const bool v2 = head && memcmp(h.magic, "LBMCKPT2", 8) == 0 && fread(&digest, sizeof(digest), 1, fp) == 1;
-    const bool v3 = head && memcmp(h.magic, "LBMCKPT3", 8) == 0 && fread(&flags, sizeof(flags), 1, fp) == 1 && (flags & ~7ull) == 0 &&
+    const bool v3 = head && memcmp(h.magic, "LBMCKPT3", 8) == 0 && fread(&flags, sizeof(flags), 1, fp) == 1 && (flags & ~15ull) == 0 &&
                     (!(flags & 1) || fread(&digest, sizeof(digest), 1, fp) == 1) && (!(flags & 2) || fread(&pdigest, sizeof(pdigest), 1, fp) == 1) &&
-                    (!(flags & 4) || fread(&cs, sizeof(cs), 1, fp) == 1);
-    const bool f_mask = v2 || (v3 && (flags & 1)), f_prof = v3 && (flags & 2), f_les = v3 && (flags & 4);
+                    (!(flags & 4) || fread(&cs, sizeof(cs), 1, fp) == 1) && (!(flags & 8) || fread(&magic, sizeof(magic), 1, fp) == 1);
+    const bool f_mask = v2 || (v3 && (flags & 1)), f_prof = v3 && (flags & 2), f_les = v3 && (flags & 4), f_trt = v3 && (flags & 8);
     if (!v1 && !v2 && !v3) rc = fail(LBM_ERR_ARG, "%s is not a checkpoint", path);
+    else if (!f_trt && c->trt) rc = fail(LBM_ERR_ARG, "checkpoint %s was written without a TRT magic parameter; this context has %g", path, c->trt_magic);
+    else if (f_trt && !c->trt) rc = fail(LBM_ERR_ARG, "checkpoint %s was written with TRT magic parameter %g; this context has none", path, magic);
+    else if (f_trt && magic != c->trt_magic) rc = fail(LBM_ERR_ARG, "checkpoint %s was written with TRT magic parameter %.17g; this context has %.17g", path, magic, c->trt_magic);
     else if (!f_les && c->les) rc = fail(LBM_ERR_ARG, "checkpoint %s was written without a Smagorinsky constant (BGK); this context has Cs = %g", path, c->les_cs);
     else if (f_les && !c->les) rc = fail(LBM_ERR_ARG, "checkpoint %s was written with Smagorinsky constant Cs = %g; this context has none (BGK)", path, cs);
     else if (f_les && cs != c->les_cs) rc = fail(LBM_ERR_ARG, "checkpoint %s was written with Smagorinsky constant Cs = %.17g; this context has Cs = %.17g", path, cs, c->les_cs);
@@ -959,6 +982,7 @@ int lbm_set_option(lbm_ctx* c, const char* key, long value) {
         if (!deep_valid((int)value)) return fail(LBM_ERR_ARG, "deep must be 0..3 or 6..9 (4 / 5, round 2's 32x16 LDS tiles, are retired)");
         if (deep_is_tall((int)value) && c->esize != 4) return fail(LBM_ERR_ARG, "deep 8 (64x48 regions in registers, twelve waves x four rows) exists in fp32 only");
         if (deep_is_tall((int)value) && c->les) return fail(LBM_ERR_ARG, "deep 8 (64x48 regions in registers) has no Smagorinsky (LES) kernel");
+        if (deep_is_tall((int)value) && c->trt) return fail(LBM_ERR_ARG, "deep 8 (64x48 regions in registers) has no two-relaxation-time (TRT) kernel");
         c->deep = (int)value;
         if (c->deep) c->fuse = deep_depth(c->deep);
     }
@@ -1040,7 +1064,7 @@ const char* lbm_kernel_name(const lbm_ctx* c) {
     const bool phys_face = face_south(c) || face_north(c);
     const bool usable = c->deep && (!phys_face || deep_depth(c->deep) <= (device_transport(c) ? GR : HR1));
     const int deep = usable ? c->deep : 0, fuse = usable || !c->deep ? c->fuse : std::min(c->fuse, 3);
-    snprintf(name, sizeof(name), "%s", plan_kernel_name(fuse, deep, c->pair_ty, c->use_nt, ar_of(c->arith == AR_CONTRACTED, c->les), (int)c->esize).c_str());
+    snprintf(name, sizeof(name), "%s", plan_kernel_name(fuse, deep, c->pair_ty, c->use_nt, ar_of(c->arith == AR_CONTRACTED, c->les, c->trt), (int)c->esize).c_str());
     return name;
 }
 
@@ -1084,12 +1108,12 @@ int lbm_debug_body_chunks(const unsigned char* labels, int nx, int ny, int y_sta
 }
 
 /* TEST HOOK (no device needed): the candidates lbm_initialise would time for a whole-domain context of this grid, one per line:
- * "name|lbm_set_option pairs|dominant kernel|iterations per launch". arith: 0 / 1, or 2 / 3 for a Smagorinsky (LES) context. */
+ * "name|lbm_set_option pairs|dominant kernel|iterations per launch". arith: 0 / 1, 2 / 3 for a Smagorinsky (LES) context, 4 / 5 for a TRT one. */
 int lbm_debug_plan_candidates(int nx, int ny, int precision, int arith, int num_cus, char* out, int cap) {
     if (!out || cap < 1 || nx < 1 || ny < 1) return fail(LBM_ERR_ARG, "bad argument");
     PlanQuery q;
     q.nx = nx; q.nyl = ny; q.ny_glob = ny; q.esize = precision == LBM_PRECISION_F32 ? 4 : 8; q.num_cus = num_cus > 0 ? num_cus : 256;
-    q.les = ar_les(arith);
+    q.les = ar_les(arith) || ar_trt(arith);
     const Plan none{};
     std::string text;
     for (const Plan& pl : plan_candidates(q, none)) {

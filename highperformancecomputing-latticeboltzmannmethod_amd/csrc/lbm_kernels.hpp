@@ -110,7 +110,13 @@ struct KArgs {
     int reverse;       // 1: blockIdx.y walks the rows top-down (alternated per launch by the host, see row_of_block)
     // Smagorinsky LES (lbm_set_smagorinsky): tau, tau*tau and C = 18*sqrt(2)*Cs^2, computed on the host in double. Read only by the
     // LES instantiations (AR_STRICT_LES / AR_CONTRACTED_LES); appended so that the fields BGK kernels read keep their offsets.
-    T les_tau, les_tau2, les_c;
+    // A TRT context (lbm_set_trt; never LES as well) carries its second rate wm = 1/tau_minus in the first of the three slots instead,
+    // and the folded rates of the contracted arithmetic, (wp + wm)/2 and (wp - wm)/2, in the other two (formed on the host: a uniform
+    // value formed by the kernel would sit in vector registers). The struct, and with it every BGK and LES kernel, keeps its size
+    // and offsets.
+    union { T les_tau; T trt_wm; };
+    union { T les_tau2; T trt_wa; };
+    union { T les_c; T trt_wb; };
 };
 
 // Row handled by blockIdx.y. Blocks are dispatched roughly in index order; walking the rows in the opposite
@@ -199,10 +205,14 @@ __device__ __forceinline__ void bcs_at(const A& a, T (&f)[Q], int x, int yg) {
 //   AR_STRICT_LES / AR_CONTRACTED_LES  the same two arithmetic modes with the Smagorinsky relaxation time of each cell (les_tau_inv)
 //                 in place of the global 1/tau. Separate instantiations, never a runtime branch: a kernel's VGPR count is the maximum
 //                 over its paths, and the BGK kernels have no headroom.
-enum Arith { AR_STRICT = 0, AR_CONTRACTED = 1, AR_STRICT_LES = 2, AR_CONTRACTED_LES = 3 };
+//   AR_STRICT_TRT / AR_CONTRACTED_TRT  the same two arithmetic modes with the two-relaxation-time operator (lbm_set_trt): the even
+//                 part of each opposite pair relaxes with 1/tau, the odd part with the launch-uniform second rate trt_wm. Separate
+//                 instantiations for the same reason. TRT and LES exclude each other: there are no values 6 and 7.
+enum Arith { AR_STRICT = 0, AR_CONTRACTED = 1, AR_STRICT_LES = 2, AR_CONTRACTED_LES = 3, AR_STRICT_TRT = 4, AR_CONTRACTED_TRT = 5 };
 constexpr bool ar_contracted(int ar) { return (ar & 1) != 0; }
 constexpr bool ar_les(int ar) { return (ar & 2) != 0; }
-constexpr int ar_of(bool contracted, bool les) { return (contracted ? 1 : 0) | (les ? 2 : 0); }
+constexpr bool ar_trt(int ar) { return (ar & 4) != 0; }
+constexpr int ar_of(bool contracted, bool les, bool trt = false) { return (contracted ? 1 : 0) | (les ? 2 : 0) | (trt ? 4 : 0); }
 
 __device__ __forceinline__ double fma_t(double a, double b, double c) { return __builtin_fma(a, b, c); }
 __device__ __forceinline__ float fma_t(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
@@ -304,7 +314,8 @@ __device__ __forceinline__ T les_tau_inv_strict(const T (&f)[Q], T rho, T ux, T 
 }
 
 // collision_step for one cell, LBMSolver.h:101-123 (moments i = 0..8 ascending from 0, N7). LES modes: tau_inv is ignored and the
-// relaxation rate of the cell comes from les_tau / les_tau2 / les_c (KArgs); BGK modes never read those three.
+// relaxation rate of the cell comes from les_tau / les_tau2 / les_c (KArgs); BGK modes never read those three. TRT modes: tau_inv
+// relaxes the even part of each opposite pair (and the rest population), `les_tau` carries the rate of the odd part, wm = 1/tau_minus, and les_tau2 / les_c the folded rates (wp + wm)/2, (wp - wm)/2.
 template <typename T, int AR = AR_STRICT>
 __device__ __forceinline__ void bgk_collide(T (&f)[Q], T tau_inv, T les_tau = T(0), T les_tau2 = T(0), T les_c = T(0)) {
     T rho = T(0), ux = T(0), uy = T(0);
@@ -332,6 +343,29 @@ __device__ __forceinline__ void bgk_collide(T (&f)[Q], T tau_inv, T les_tau = T(
         }
         const T base = fma_t(T(-1.0 / 6.0), fma_t(vx, vx, vy * vy), T(1.0));
         const T wr0 = wgt<T>(0) * rho, wr1 = wgt<T>(1) * rho, wr5 = wgt<T>(5) * rho;
+        if constexpr (ar_trt(AR)) {
+            // f_i' = f_i + wa (feq_i - f_i) + wb (feq_ib - f_ib) with wa = (wp + wm)/2, wb = (wp - wm)/2: BGK's residuals of the two
+            // directions (c.v changes its sign for the opposite one), then two FMAs each, in place. Two temporaries beyond BGK's.
+            const T wa = les_tau2, wb = les_c;
+            f[0] = fma_t(tau_inv, fma_t(wr0, base, -f[0]), f[0]);
+            auto pair = [&](int i, int ib, T cv, T wr) {     // i: the direction whose c.v is `cv`; ib: its opposite
+                const T ri = fma_t(wr, fma_t(cv, fma_t(cv, T(0.5), T(1.0)), base), -f[i]);
+                const T rb = fma_t(wr, fma_t(cv, fma_t(cv, T(0.5), T(-1.0)), base), -f[ib]);
+                f[i] = fma_t(wa, ri, fma_t(wb, rb, f[i]));
+                f[ib] = fma_t(wa, rb, fma_t(wb, ri, f[ib]));
+            };
+            // One pair after the other: an empty asm statement that "rewrites" a finished pair together with the next pair's inputs keeps
+            // the compiler from starting the next pair's residuals early (it would hold all eight and spill in the fp64 register kernel).
+            auto then = [&](int i, int ib, int j, int jb) { asm volatile("" : "+v"(f[i]), "+v"(f[ib]), "+v"(f[j]), "+v"(f[jb])); };
+            pair(5, 7, vx + vy, wr5);
+            then(5, 7, 8, 6);
+            pair(8, 6, vx - vy, wr5);
+            then(8, 6, 1, 3);
+            pair(1, 3, vx, wr1);
+            then(1, 3, 2, 4);
+            pair(2, 4, vy, wr1);
+            return;
+        }
 #pragma unroll
         for (int i = 0; i < Q; ++i) {
             T cv;
@@ -372,6 +406,17 @@ __device__ __forceinline__ void bgk_collide(T (&f)[Q], T tau_inv, T les_tau = T(
     relax(f[0], wr0, (T(1.0) + T(0.0)) - c15);      // cu = 0: 1.0 + 3.0*0 + 4.5*0*0 = 1.0 exactly
     auto pair = [&](int i, int ib, T cu, T wr) {     // i: the direction whose c.u is `cu`; ib: its opposite
         const T t3 = T(3.0) * cu, t45 = (T(4.5) * cu) * cu;
+        if constexpr (ar_trt(AR)) {
+            // TRT (tests/test_gpu_trt.py trt_collide, operation by operation): the same two feq, then the even (np) and odd (nm)
+            // non-equilibrium parts of the pair, relaxed with wp = 1/tau and wm = 1/tau_minus
+            const T feq = wr * (((T(1.0) + t3) + t45) - c15), feqb = wr * (((T(1.0) - t3) + t45) - c15);
+            const T np = T(0.5) * ((f[i] + f[ib]) - (feq + feqb));
+            const T nm = T(0.5) * ((f[i] - f[ib]) - (feq - feqb));
+            const T wpn = tau_inv * np, wmn = les_tau * nm;
+            f[i] = (f[i] - wpn) - wmn;
+            f[ib] = (f[ib] - wpn) + wmn;
+            return;
+        }
         relax(f[i], wr, ((T(1.0) + t3) + t45) - c15);
         relax(f[ib], wr, ((T(1.0) - t3) + t45) - c15);
     };
@@ -381,10 +426,13 @@ __device__ __forceinline__ void bgk_collide(T (&f)[Q], T tau_inv, T les_tau = T(
     pair(8, 6, ux - uy, wr5);         // c8 = (1,-1), c6 = (-1,1): 1*ux + (-1)*uy == ux - uy
 }
 
-// The collision of the step kernels: BGK with the global 1/tau, or (LES modes) the Smagorinsky rate of each cell
+// The collision of the step kernels: BGK with the global 1/tau, (LES modes) the Smagorinsky rate of each cell, or (TRT modes) 1/tau
+// for the even and trt_wm for the odd part of each pair (contracted: the two folded into trt_wa, trt_wb)
 template <typename T, int AR>
 __device__ __forceinline__ void collide(T (&f)[Q], const KArgs<T>& a) {
-    if constexpr (ar_les(AR)) bgk_collide<T, AR>(f, T(0), a.les_tau, a.les_tau2, a.les_c);
+    static_assert(!(ar_les(AR) && ar_trt(AR)), "TRT and LES exclude each other");
+    if constexpr (ar_trt(AR)) bgk_collide<T, AR>(f, a.tau_inv, a.trt_wm, a.trt_wa, a.trt_wb);
+    else if constexpr (ar_les(AR)) bgk_collide<T, AR>(f, T(0), a.les_tau, a.les_tau2, a.les_c);
     else bgk_collide<T, AR>(f, a.tau_inv);
 }
 

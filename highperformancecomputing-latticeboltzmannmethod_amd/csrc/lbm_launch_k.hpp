@@ -1,6 +1,6 @@
 // csrc/lbm_launch_k.hpp — the kernel launches of the single-iteration and fused tile families for one pair of arithmetic values
 // (ARS strict, ARC contracted): AR_STRICT / AR_CONTRACTED in lbm_hip.hip (BGK), AR_STRICT_LES / AR_CONTRACTED_LES in lbm_les.hip
-// (Smagorinsky). A template is instantiated where it is used, so each translation unit holds the kernels of its own pair only.
+// (Smagorinsky), AR_STRICT_TRT / AR_CONTRACTED_TRT in lbm_trt.hip (two relaxation times). A template is instantiated where it is used, so each translation unit holds the kernels of its own pair only.
 #pragma once
 #include "lbm_kernels.hpp"
 
@@ -66,5 +66,13 @@ template <typename T>
 void launch_deep_les(const KArgs<T>& a, const K2Extra<T>& e, int shape, bool fast, hipStream_t s);
 template <typename T>
 void launch_tile_les(const KArgs<T>& a, const K2Extra<T>& e, int depth, int ty, bool fast, hipStream_t s);
+
+// ---- the TRT instantiations (lbm_trt.hip; k_stepc_col's: lbm_col.hip -DLBM_COL_TRT=1) -----------------------------------------
+template <typename T>
+void launch_site_trt(const KArgs<T>& a, int mode, bool nt, bool fast, hipStream_t s);
+template <typename T>
+void launch_deep_trt(const KArgs<T>& a, const K2Extra<T>& e, int shape, bool fast, hipStream_t s);
+template <typename T>
+void launch_tile_trt(const KArgs<T>& a, const K2Extra<T>& e, int depth, int ty, bool fast, hipStream_t s);
 
 }  // namespace lbmk

@@ -40,7 +40,7 @@ struct PlanQuery {
     bool strips = false;                // this context has (or simulates) strip faces
     bool faces = false;                 // ... and at least one of them is an internal face
     bool tune = true, can_tune = true;  // option "tune"; the grid is neither too small nor too large to measure
-    bool les = false;                   // Smagorinsky LES collision: no tall fp32 regions (no LES instantiation of them)
+    bool les = false;                   // Smagorinsky LES or TRT collision: no tall fp32 regions (no such instantiation of them)
 };
 
 // The strip rule: 0: three iterations on 64x12 LDS tiles in pairs between exchanges; 1: six iterations on 64x16 LDS tiles of
@@ -128,7 +128,7 @@ inline std::vector<Plan> plan_candidates(const PlanQuery& q, const Plan& fixed) 
 }
 
 // the dominant kernel of a plan, as rocprofv3 names it (minus "lbmk::" and blanks)
-// (arith: the kernels' Arith value, 0..3; the region shapes follow its strict / contracted half)
+// (arith: the kernels' Arith value, 0..5; the region shapes follow its strict / contracted half)
 inline std::string plan_kernel_name(int fuse, int deep, int pair_ty, int nt, int arith, int esize) {
     char name[96];
     const char* t = esize == 4 ? "float" : "double";

@@ -51,6 +51,7 @@ public:
             else if (p.masked()) check(lbm_set_solid_mask(c, p.obstacle_mask.data(), p.nx, p.ny), "lbm_set_solid_mask");
             if (p.profiled()) check(lbm_set_inlet_profile(c, p.inlet_profile.data(), p.ny), "lbm_set_inlet_profile");
             if (p.les()) check(lbm_set_smagorinsky(c, p.smagorinsky_cs), "lbm_set_smagorinsky");
+            if (p.trt()) check(lbm_set_trt(c, p.trt_magic), "lbm_set_trt");
             y += n;
         }
         check(lbm_group_link(ctx_.data(), (int)ctx_.size(), opt.rccl ? 1 : 0), "lbm_group_link");

@@ -285,6 +285,7 @@ private:
         }
         if (p.profiled()) { f.put("inlet_profile,"); f.put(p.inlet_profile_spec.c_str()); f.put("\n"); }   // (profiled runs only, likewise)
         if (p.les()) row_d("smagorinsky_cs", p.smagorinsky_cs);                                            // (LES runs only, likewise)
+        if (p.trt()) row_d("trt_magic", p.trt_magic);                                                      // (TRT runs only, likewise)
         if (p.frames()) row_i("frame_stride", p.frame_stride);                                             // (runs with --frame-stride only, likewise)
         std::printf("  simulation_params.csv written\n");
     }

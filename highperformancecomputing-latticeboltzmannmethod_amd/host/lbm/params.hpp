@@ -46,6 +46,9 @@ struct SimulationParams {
     // Smagorinsky LES collision (lbm_solver --smagorinsky; not in the reference): the constant Cs, 0 = plain BGK. tau, nu() and
     // reynolds() keep referring to the molecular viscosity.
     double smagorinsky_cs = 0.0;
+    // Two-relaxation-time collision (lbm_solver --trt-magic; not in the reference): the magic parameter, 0 = plain BGK. Never
+    // together with smagorinsky_cs. tau keeps setting the viscosity.
+    double trt_magic = 0.0;
     // time-averaged statistics (lbm_solver --stats-start; not in the reference): the first step sampled, -1 = off. Samples are taken on
     // the device at the output_frequency cadence (lbm_stats_begin); the run ends with mean_fields.vtk / mean_fields.csv.
     int stats_start = -1;
@@ -60,6 +63,7 @@ struct SimulationParams {
     int body_count() const { return (int)body_height.size(); }
     bool profiled() const { return !inlet_profile.empty(); }
     bool les() const { return smagorinsky_cs > 0.0; }
+    bool trt() const { return trt_magic > 0.0; }
     bool stats() const { return stats_start >= 0; }
     bool frames() const { return frame_stride > 0; }
     double reynolds() const {

@@ -20,7 +20,8 @@ static void usage() {
               "           [--no-vtk] [--no-final] [--sync-vtk] [--fp32] [--contracted] [--no-tune] [--device D] [--quiet]\n"
               "           [--gpus N] [--strips N] [--rccl]\n"
               "           [--checkpoint FILE] [--restart FILE] [--obstacle-mask FILE.pgm] [--obstacle-bodies FILE.pgm]\n"
-              "           [--inlet-profile parabolic|FILE] [--print-inlet-profile] [--smagorinsky CS] [--stats-start N]\n"
+              "           [--inlet-profile parabolic|FILE] [--print-inlet-profile] [--smagorinsky CS] [--trt-magic LAMBDA]\n"
+              "           [--stats-start N]\n"
               "           [--frame-stride K]\n"
               "Defaults are the reference's SimulationParams (LBMConfig.h:37-51). --reynolds sets the inlet velocity\n"
               "from tau and the cylinder diameter so that params.reynolds() equals RE.\n"
@@ -40,6 +41,10 @@ static void usage() {
               "--smagorinsky CS: Smagorinsky LES collision with constant CS in [0, 1] (0: plain BGK) instead of BGK, for\n"
               "higher Reynolds numbers at the same tau. tau, the Reynolds number and --reynolds keep referring to the\n"
               "molecular viscosity (tau - 0.5) / 3; the eddy viscosity of the model is added per cell.\n"
+              "--trt-magic LAMBDA: two-relaxation-time (TRT) collision with magic parameter LAMBDA in [0, 1] (0: plain BGK)\n"
+              "instead of BGK: the even part of each opposite pair of populations relaxes with 1/tau (the viscosity is\n"
+              "unchanged), the odd part with 1/(0.5 + LAMBDA/(tau - 0.5)). 0.25 is the most stable choice, 0.1875 (3/16) the\n"
+              "most accurate at walls. Needs tau > 0.5; cannot be combined with --smagorinsky.\n"
               "--stats-start N: time-averaged statistics from step N on, sampled on the device every --output-frequency steps;\n"
               "the run ends with mean_fields.vtk and mean_fields.csv (means of rho, ux, uy and the Reynolds stresses). With\n"
               "--checkpoint / --restart the sums travel beside the checkpoint as FILE.stats. --no-final suppresses the two\n"
@@ -57,6 +62,7 @@ int main(int argc, char** argv) {
     std::string restart_from, checkpoint_to;
     bool print_profile = false;
     const char* smagorinsky = nullptr;
+    const char* trt_magic = nullptr;
     const char* stats_start = nullptr;
     const char* frame_stride = nullptr;
     double reynolds = -1.0;
@@ -95,6 +101,7 @@ int main(int argc, char** argv) {
         else if (k == "--inlet-profile") params.inlet_profile_spec = val();
         else if (k == "--print-inlet-profile") print_profile = true;
         else if (k == "--smagorinsky") smagorinsky = val();
+        else if (k == "--trt-magic") trt_magic = val();
         else if (k == "--stats-start") stats_start = val();
         else if (k == "--frame-stride") frame_stride = val();
         else if (k == "--help" || k == "-h") { usage(); return 0; }
@@ -108,6 +115,23 @@ int main(int argc, char** argv) {
             return 2;
         }
         params.smagorinsky_cs = cs;
+    }
+    if (trt_magic) {     // likewise: a whole finite number in [0, 1], a tau it is defined for, and no second collision model
+        char* end = nullptr;
+        const double magic = std::strtod(trt_magic, &end);
+        if (end == trt_magic || *end != '\0' || !std::isfinite(magic) || magic < 0.0 || magic > 1.0) {
+            std::fprintf(stderr, "--trt-magic: '%s' is not a number in [0, 1]\n", trt_magic);
+            return 2;
+        }
+        if (magic > 0.0 && !(params.tau > 0.5)) {
+            std::fprintf(stderr, "--trt-magic: needs tau > 0.5, not %g\n", params.tau);
+            return 2;
+        }
+        if (magic > 0.0 && params.smagorinsky_cs > 0.0) {
+            std::fprintf(stderr, "--trt-magic cannot be combined with --smagorinsky (one collision model at a time)\n");
+            return 2;
+        }
+        params.trt_magic = magic;
     }
     if (stats_start) {   // checked before any device is touched: a whole number >= 0, and a cadence to sample at
         char* end = nullptr;

@@ -232,8 +232,24 @@ int  lbm_set_inlet_profile(lbm_ctx* c, const double* u, int ny);
  * rounded square roots, contracted arithmetic (arith=1) with FMAs. Every strip of a run is given the same value. Call after lbm_create
  * and before lbm_initialise, like lbm_set_solid_mask: the plan is then measured on the LES kernels (no fp32 deep=8 plan: pinning it
  * fails). cs == 0 clears the model (the BGK kernels). Checkpoints carry cs (lbm_save_state: magic "LBMCKPT3", flag bit 2).
- * LBM_ERR_ARG: null context, an initialised context, or a value that is not finite, < 0 or > 1. */
+ * LBM_ERR_ARG: null context, an initialised context, a value that is not finite, < 0 or > 1, or a nonzero value on a context with a
+ * TRT magic parameter (lbm_set_trt): the two collisions cannot be combined. */
 int  lbm_set_smagorinsky(lbm_ctx* c, double cs);
+/* The collision: replaces the single-relaxation-time BGK operator by the two-relaxation-time one (TRT: Ginzburg, d'Humieres) with
+ * "magic" parameter `magic` = (tau - 1/2)(tau_minus - 1/2). With feq as BGK forms it, the rest population relaxes with wp = 1/tau, and
+ * each opposite pair (i, ib) of (1,3), (2,4), (5,7), (8,6) is split into its even and odd non-equilibrium parts,
+ *     np = ((f_i + f_ib) - (feq_i + feq_ib)) / 2,  nm = ((f_i - f_ib) - (feq_i - feq_ib)) / 2,
+ *     f_i' = f_i - wp np - wm nm,  f_ib' = f_ib - wp np + wm nm,     wp = 1 / tau,  wm = 1 / (1/2 + magic / (tau - 1/2)).
+ * The even rate sets the viscosity, (tau - 1/2) / 3 as before; the odd rate is free, and with magic fixed the place of a bounce-back
+ * wall no longer moves with the viscosity. magic = 1/4 is the most stable choice, 3/16 puts the wall of a straight channel exactly
+ * half-way; magic = (tau - 1/2)^2 makes the two rates equal (BGK up to rounding). Both rates are computed in double and cast to the
+ * element type. Strict arithmetic (option arith=0) evaluates the lines above operation by operation in IEEE arithmetic, contracted
+ * arithmetic (arith=1) with FMAs. No extra memory traffic. Every strip of a run is given the same value. Call after lbm_create and
+ * before lbm_initialise, like lbm_set_smagorinsky: the plan is then measured on the TRT kernels (no fp32 deep=8 plan: pinning it fails).
+ * magic == 0 clears the model (the BGK kernels). Checkpoints carry magic (lbm_save_state: magic word "LBMCKPT3", flag bit 3).
+ * LBM_ERR_ARG: null context, an initialised context, a value that is not finite, < 0 or > 1, a context whose tau <= 0.5, or a
+ * context with a nonzero Smagorinsky constant: the two collisions cannot be combined. */
+int  lbm_set_trt(lbm_ctx* c, double magic);
 
 /* ---- strip halo exchange (replaces Grid::exchange_ghost_cells, LBMGrid.h:249-283) ----
  * Device path: RCCL send/recv of the LBM_HALO_ROWS edge rows per face (one contiguous run in the row-interleaved
@@ -290,8 +306,8 @@ int  lbm_halo_import(lbm_ctx* c, const double* south_in, const double* north_in)
 /* Checkpoint / restart (the reference has none): the strip's post-collision populations and the
  * iteration counter. lbm_load_state needs an initialised context created with the same parameters; the macro /
  * population snapshots become available again after the next lbm_step. A file written with an obstacle mask, an inlet
- * profile or a Smagorinsky constant loads only into a context with the same mask, profile and constant (the failure names which one
- * differs). */
+ * profile, a Smagorinsky constant or a TRT magic parameter loads only into a context with the same mask, profile, constant and
+ * parameter (the failure names which one differs). */
 int  lbm_save_state(lbm_ctx* c, const char* path);
 int  lbm_load_state(lbm_ctx* c, const char* path);
 
