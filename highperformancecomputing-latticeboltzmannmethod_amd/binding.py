@@ -66,6 +66,12 @@ def lib():
         L.lbm_frames_end.argtypes = [vp]
         L.lbm_frames_pending.argtypes = [vp]
         L.lbm_drain_frames.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_float), C.c_int]
+        L.lbm_probes_begin.argtypes = [vp, dp, C.c_int, C.c_int]
+        L.lbm_probes_end.argtypes = [vp]
+        L.lbm_probes_count.argtypes = [vp]
+        L.lbm_probes_pending.argtypes = [vp]
+        L.lbm_drain_probes.argtypes = [vp, C.POINTER(C.c_int), dp, C.c_int]
+        L.lbm_debug_probe_table.argtypes = [dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), dp, C.POINTER(C.c_int)]
         L.lbm_get_populations.argtypes = [vp, C.c_int, dp]
         L.lbm_set_f_current.argtypes = [vp, dp]
         L.lbm_get_solid.argtypes = [vp, C.POINTER(C.c_ubyte)]
@@ -244,6 +250,14 @@ def _stats_from_sums(sums, n):
             "uxux": sums[3] / n - ux * ux, "uyuy": sums[4] / n - uy * uy, "uxuy": sums[5] / n - ux * uy}
 
 
+def _probe_points(xy):
+    """(n, 2) float64, C-contiguous: the probe points as lbm_probes_begin takes them."""
+    a = np.ascontiguousarray(xy, dtype=np.float64)
+    if a.ndim != 2 or a.shape[1] != 2:
+        raise ValueError(f"probe points must have shape (n, 2), not {a.shape}")
+    return a
+
+
 class Context:
     """One strip of the lattice on one GPU (struct lbm_ctx). solid: optional bool / uint8 (ny, nx) array of the WHOLE domain, row
     y = 0 first, nonzero = solid (lbm_set_solid_mask): the obstacle geometry in place of the cylinder_* disc. inlet_profile: optional
@@ -254,11 +268,13 @@ class Context:
     bodies: optional integer (ny, nx) array of body numbers of the WHOLE
     domain (0 fluid, 1..255; lbm_set_body_labels): the geometry of solid=(bodies != 0) plus forces per body (body_forces,
     drain_body_force_log); not together with solid. frames: optional stride k of coarsened flow frames (lbm_frames_begin with the
-    default capacity at the end of initialise(); see frames_begin)."""
+    default capacity at the end of initialise(); see frames_begin). probes: optional (n, 2) array of probe points (x, y) in GLOBAL lattice
+    coordinates (lbm_probes_begin with a ring of probe_capacity samples at the end of initialise(); see probes_begin)."""
 
     def __init__(self, nx, ny, tau=0.6, inlet_velocity=0.01333, cylinder_x=0.2, cylinder_y=0.5,
                  cylinder_radius=0.05, y_start=0, local_ny=0, precision="f64", device=0, force_log_capacity=0,
-                 options=None, solid=None, inlet_profile=None, smagorinsky=None, bodies=None, frames=None, trt_magic=None):
+                 options=None, solid=None, inlet_profile=None, smagorinsky=None, bodies=None, frames=None, trt_magic=None,
+                 probes=None, probe_capacity=None):
         if solid is not None and bodies is not None:
             raise LbmError("solid= and bodies= exclude each other: the body labels are the geometry (solid where nonzero)")
         self.L = lib()
@@ -271,6 +287,7 @@ class Context:
         self._chk(self.L.lbm_create(C.byref(self.params), device, C.byref(self.h)))
         self.solid_count = None
         self._frames_k = 0
+        self._probes_kw = None if probes is None else (_probe_points(probes), probe_capacity)
         for k, v in (options or {}).items():
             self.set_option(k, v)
         if solid is not None:
@@ -360,7 +377,13 @@ class Context:
         n = C.c_int()
         self._chk(self.L.lbm_initialise(self.h, C.byref(n)))
         self.solid_count = n.value
+        self._begin_probes_kw()
         return n.value
+
+    def _begin_probes_kw(self):
+        if self._probes_kw is not None:      # the probes= keyword: begun on the initialised context
+            xy, cap = self._probes_kw
+            self.probes_begin(xy, self.PROBES_DEFAULT_CAPACITY if cap is None else cap)
 
     def step(self, nsteps=1, output_frequency=0):
         self._chk(self.L.lbm_step(self.h, nsteps, output_frequency))
@@ -456,6 +479,37 @@ class Context:
         got = self._chk(self.L.lbm_drain_frames(self.h, ts, out.ctypes.data_as(C.POINTER(C.c_float)), n))
         return [(ts[j], out[j]) for j in range(got)]
 
+    # ---- point probes (lbm_probes_*): sampled on the device at the force-output iterations of step(n, output_frequency) ----
+    PROBES_DEFAULT_CAPACITY = 64
+    PROBES_MAX = 65536            # LBM_PROBES_MAX
+
+    def probes_begin(self, xy, capacity=PROBES_DEFAULT_CAPACITY):
+        """From now on every force-output iteration appends one sample — (rho, ux, uy) in float64, interpolated bilinearly at each of the
+        n points xy[j] = (x, y), GLOBAL lattice coordinates — to a device ring of `capacity` samples. Calling it again replaces the points
+        and empties the ring. A strip samples the probes whose floor(y) lies in its rows and reports +0.0 for the others."""
+        a = _probe_points(xy)
+        self._chk(self.L.lbm_probes_begin(self.h, _dp(a), a.shape[0], int(capacity)))
+
+    def probes_end(self):
+        """Stops sampling; the undrained samples stay."""
+        self._chk(self.L.lbm_probes_end(self.h))
+
+    def probes_count(self):
+        return self._chk(self.L.lbm_probes_count(self.h))
+
+    def probes_pending(self):
+        return self._chk(self.L.lbm_probes_pending(self.h))
+
+    def drain_probes(self, max_samples=None):
+        """(timesteps int32 [m], float64 [m, n, 3]): the oldest max_samples (default: all) undrained samples, (rho, ux, uy) per probe."""
+        m, n = self.probes_pending(), self.probes_count()
+        if max_samples is not None:
+            m = min(m, int(max_samples))
+        out = np.zeros((max(m, 0), n, 3), dtype=np.float64)
+        ts = (C.c_int * max(m, 1))()
+        got = self._chk(self.L.lbm_drain_probes(self.h, ts, _dp(out), m)) if m > 0 else 0
+        return np.array(ts[:got], dtype=np.int32), out[:got]
+
     def populations(self, which):
         """which: 'f_current' | 'f_next' -> [(local_ny+2), (nx+2), 9] like Grid::f_current(gx,gy,i)."""
         out = np.empty((self.local_ny + 2, self.nx + 2, 9), dtype=np.float64)
@@ -545,18 +599,19 @@ class Group:
     """n strips of one lattice driven in lockstep by this process (lbm_group_*): one Context per strip, bottom to top.
     transport: "peer" (device copies / hipMemcpyPeerAsync) or "rccl" (ncclCommInitAll; distinct devices).
     solid: optional global (ny, nx) obstacle mask, inlet_profile: optional global [ny] inlet velocities, smagorinsky: optional LES
-    constant Cs, trt_magic: optional TRT magic parameter, bodies: optional global (ny, nx) body numbers (in place of solid), frames: optional frame stride k; all given to every
+    constant Cs, trt_magic: optional TRT magic parameter, bodies: optional global (ny, nx) body numbers (in place of solid), frames: optional frame stride k, probes / probe_capacity: optional probe points (global coordinates); all given to every
     member."""
 
     def __init__(self, nx, ny, bounds, devices=None, transport="peer", options=None, solid=None, inlet_profile=None, smagorinsky=None,
-                 bodies=None, frames=None, trt_magic=None, **kw):
+                 bodies=None, frames=None, trt_magic=None, probes=None, probe_capacity=None, **kw):
         from .strips import partition_rows
         if isinstance(bounds, int):
             bounds = partition_rows(ny, bounds)
         devices = devices or [0] * len(bounds)
         self.nx, self.ny = nx, ny
         self.ctxs = [Context(nx, ny, y_start=y0, local_ny=n, device=d, options=options, solid=solid, inlet_profile=inlet_profile,
-                             smagorinsky=smagorinsky, bodies=bodies, frames=frames, trt_magic=trt_magic, **kw)
+                             smagorinsky=smagorinsky, bodies=bodies, frames=frames, trt_magic=trt_magic, probes=probes,
+                             probe_capacity=probe_capacity, **kw)
                      for (y0, n), d in zip(bounds, devices)]
         self.L = lib()
         self._arr = (C.c_void_p * len(self.ctxs))(*[c.h for c in self.ctxs])
@@ -573,6 +628,8 @@ class Group:
         n = C.c_int()
         self._chk(self.L.lbm_group_initialise(self._arr, self._n, C.byref(n)))
         self.solid_count = n.value
+        for c in self.ctxs:
+            c._begin_probes_kw()
         return n.value
 
     def step(self, nsteps=1, output_frequency=0):
@@ -657,6 +714,38 @@ class Group:
                 raise LbmError(f"the strips of the group disagree on the iteration of a frame: {sorted(ts)}")
             out.append((ts.pop(), np.concatenate([p[j][1] for p in parts], axis=1)))
         return out
+
+    # ---- point probes: every member is given the same global points and samples those of its rows (+0.0 for the others); the members
+    # sample at the same iterations, and a drained sample is the SUM of theirs, like the partial force sums ----
+    def probes_begin(self, xy, capacity=Context.PROBES_DEFAULT_CAPACITY):
+        for c in self.ctxs:
+            c.probes_begin(xy, capacity)
+
+    def probes_end(self):
+        for c in self.ctxs:
+            c.probes_end()
+
+    def probes_count(self):
+        return self.ctxs[0].probes_count()
+
+    def probes_pending(self):
+        n = {c.probes_pending() for c in self.ctxs}
+        if len(n) != 1:
+            raise LbmError(f"the strips of the group disagree on the number of pending probe samples: {sorted(n)}")
+        return n.pop()
+
+    def drain_probes(self, max_samples=None):
+        """(timesteps int32 [m], float64 [m, n, 3]): the members' samples added up in strip order."""
+        m = self.probes_pending()
+        if max_samples is not None:
+            m = min(m, int(max_samples))
+        parts = [c.drain_probes(m) for c in self.ctxs]
+        ts, total = parts[0][0], parts[0][1].copy()
+        for t, v in parts[1:]:
+            if not np.array_equal(t, ts):
+                raise LbmError(f"the strips of the group disagree on the iterations of the probe samples: {ts.tolist()} / {t.tolist()}")
+            total = total + v
+        return ts, total
 
     def populations(self, which):
         """Ghost-inclusive [(ny+2), (nx+2), 9]: interior rows of every strip + the physical ghost rows of the end strips."""

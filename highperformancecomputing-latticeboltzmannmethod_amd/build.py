@@ -48,9 +48,10 @@ def build_all(force=False, verbose=False):
     if force or embedded_id() != want:
         # -ffp-contract=off: no fused multiply-add is formed behind the source's back, so every formulation of the
         # step kernel (site / vector / fused, any layout) and the strict-IEEE oracle evaluate the same operation sequence.
-        # Twelve objects compiled side by side (the column kernel's instantiations of one element type take as long as all
+        # Thirteen objects compiled side by side (the column kernel's instantiations of one element type take as long as all
         # the other kernels together), then linked. Three hold the Smagorinsky (LES) instantiations only, three the
-        # two-relaxation-time (TRT) ones, the last one the frame kernel (lbm_frames_begin).
+        # two-relaxation-time (TRT) ones, one the frame kernel (lbm_frames_begin), the last one the probe kernel
+        # (lbm_probes_begin).
         units = [("lbm_hip.hip", ["-DLBM_BUILD_ID_STR=\"" + want + "\""], "lbm_hip.o"),
                  ("lbm_col.hip", ["-DLBM_COL_T=double"], "lbm_col_f64.o"), ("lbm_col.hip", ["-DLBM_COL_T=float"], "lbm_col_f32.o"),
                  ("lbm_col.hip", ["-DLBM_COL_TALL=1"], "lbm_col_tall_c.o"), ("lbm_col.hip", ["-DLBM_COL_TALL=0"], "lbm_col_tall_s.o"),
@@ -59,7 +60,7 @@ def build_all(force=False, verbose=False):
                  ("lbm_les.hip", [], "lbm_les.o"),
                  ("lbm_col.hip", ["-DLBM_COL_T=double", "-DLBM_COL_TRT=1"], "lbm_col_trt_f64.o"),
                  ("lbm_col.hip", ["-DLBM_COL_T=float", "-DLBM_COL_TRT=1"], "lbm_col_trt_f32.o"),
-                 ("lbm_trt.hip", [], "lbm_trt.o"), ("lbm_frames.hip", [], "lbm_frames.o")]
+                 ("lbm_trt.hip", [], "lbm_trt.o"), ("lbm_frames.hip", [], "lbm_frames.o"), ("lbm_probes.hip", [], "lbm_probes.o")]
         common = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++20", "-ffp-contract=off", "-fPIC", "-pthread", "-c"]
         procs, objs = [], []
         for src, extra, oname in units:

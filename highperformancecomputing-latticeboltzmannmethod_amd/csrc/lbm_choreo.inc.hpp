@@ -138,6 +138,7 @@ struct ChoreoChecker {
                 case ChoreoOp::STATS:
                 case ChoreoOp::BODIES:      // the per-body sample reads what the force kernel reads; every sample writes a log slot of its own
                 case ChoreoOp::FRAME:       // the frame sample reads two ghost rows per face too and writes a ring slot of its own
+                case ChoreoOp::PROBES:      // the probe sample reads one ghost row below and two above (y1 of a probe on the last row, and its pull); a ring slot of its own
                     for (int y = o.r0; y < o.r1; ++y) { read_row(idx, s, o.strip, o.buf, y); need_level(idx, o.strip, o.buf, y, o.t); }
                     if (o.kind == ChoreoOp::STATS) {      // a read-modify-write of the strip's accumulators: ordered behind the sample before it
                         RowState& a = acc[(size_t)o.strip];
@@ -152,7 +153,7 @@ struct ChoreoChecker {
 };
 
 inline std::string choreo_op_text(const ChoreoOp& o, int idx) {
-    static const char* kinds[] = {"kernel", "record", "wait", "copy", "send", "recv", "forces", "stats", "body forces", "frame"};
+    static const char* kinds[] = {"kernel", "record", "wait", "copy", "send", "recv", "forces", "stats", "body forces", "frame", "probes"};
     static const char* evs[] = {"ev_main", "ev_edge", "ev_comm"};
     char b[256];
     int n = snprintf(b, sizeof(b), "#%d strip %d %s stream: %s", idx, o.strip, o.stream ? "side" : "main", kinds[o.kind]);
@@ -163,9 +164,9 @@ inline std::string choreo_op_text(const ChoreoOp& o, int idx) {
     else if (o.kind == ChoreoOp::COPY) n += snprintf(b + n, sizeof(b) - n, " buf %d: rows [%d,%d) of strip %d -> rows [%d,%d)", o.buf, o.r0, o.r1, o.r_strip, o.w0[0], o.w1[0]);
     else if (o.kind == ChoreoOp::SEND) n += snprintf(b + n, sizeof(b) - n, " buf %d rows [%d,%d)", o.buf, o.r0, o.r1);
     else if (o.kind == ChoreoOp::RECV) n += snprintf(b + n, sizeof(b) - n, " buf %d rows [%d,%d)", o.buf, o.w0[0], o.w1[0]);
-    else if (o.kind == ChoreoOp::FORCES || o.kind == ChoreoOp::STATS || o.kind == ChoreoOp::BODIES || o.kind == ChoreoOp::FRAME)
+    else if (o.kind == ChoreoOp::FORCES || o.kind == ChoreoOp::STATS || o.kind == ChoreoOp::BODIES || o.kind == ChoreoOp::FRAME || o.kind == ChoreoOp::PROBES)
         n += snprintf(b + n, sizeof(b) - n, " t=%d reads buf %d rows [%d,%d)%s", o.t, o.buf, o.r0, o.r1,
-                      o.kind == ChoreoOp::STATS ? ", writes the accumulators" : o.kind == ChoreoOp::BODIES ? ", writes its log slot" : o.kind == ChoreoOp::FRAME ? ", writes its ring slot" : "");
+                      o.kind == ChoreoOp::STATS ? ", writes the accumulators" : o.kind == ChoreoOp::BODIES ? ", writes its log slot" : (o.kind == ChoreoOp::FRAME || o.kind == ChoreoOp::PROBES) ? ", writes its ring slot" : "");
     return b;
 }
 

@@ -196,16 +196,17 @@ struct GroupPool {
 // clocks and reports every pair of conflicting accesses that no event orders, and every launch that reads a row of the wrong
 // iteration: the class of round 4's edge-band race (a band shorter than the rows that travel), found then by a 1-in-15 flake.
 struct ChoreoOp {
-    enum { KERNEL = 0, RECORD = 1, WAIT = 2, COPY = 3, SEND = 4, RECV = 5, FORCES = 6, STATS = 7, BODIES = 8, FRAME = 9 };
+    enum { KERNEL = 0, RECORD = 1, WAIT = 2, COPY = 3, SEND = 4, RECV = 5, FORCES = 6, STATS = 7, BODIES = 8, FRAME = 9, PROBES = 10 };
     int kind = 0;
     int strip = 0, stream = 0;      // the issuing strip, 0 main / 1 side stream
     int ev_strip = 0, ev = 0;       // RECORD / WAIT: the event's owner and 0 ev_main, 1 ev_edge, 2 ev_comm
     int buf = 0;                    // KERNEL: the buffer written (it reads buf ^ 1); COPY / SEND / RECV / FORCES: the buffer touched
-    int t = 0, depth = 0;           // KERNEL: first iteration and iterations; FORCES / STATS / BODIES / FRAME: the iteration
+    int t = 0, depth = 0;           // KERNEL: first iteration and iterations; FORCES / STATS / BODIES / FRAME / PROBES: the iteration
     int w0[2] = {0, 0}, w1[2] = {0, 0};   // rows written, [w0, w1) in local rows (ghost rows: < 0 or >= nyl); KERNEL: two ranges
     int r0 = 0, r1 = 0, r_strip = -1;     // COPY / SEND / FORCES / STATS / BODIES / FRAME: rows read and whose (RECV: where the data comes from; -1: another process)
                                           // (STATS: the strip's rows and ONE ghost row per face — the pull of the inlet / outlet cells of its first and last row;
-                                          //  FRAME: TWO per face — the ghost row next to the face for d/dy, whose outlet cell pulls from the row beyond it)
+                                          //  FRAME: TWO per face — the ghost row next to the face for d/dy, whose outlet cell pulls from the row beyond it;
+                                          //  PROBES: rows [-1, nyl + 2) — a probe's y1 may be the ghost row next to the north face, whose inlet / outlet cell pulls one row further)
 };
 // ... and, for one rank of a multi-process run, the transcript of what exchange_rccl's posting loops WOULD hand to RCCL, in posting order:
 // kind 0 send / 1 recv / 2 end of a group call; `off`, `cnt` in elements of the buffer. lbm_debug_p2p_matching holds the transcripts of
@@ -276,6 +277,15 @@ struct lbm_ctx {
     bool frames_active = false;
     std::vector<int> frames_t;          // [frames_cap]
     int frames_opt = 0;                 // option "frames" K set before lbm_initialise: begun at its end (dry run: a frame sample behind every force kernel)
+    // Point probes (lbm_probes_begin): a device table of probe_n entries (lbm_probes.hpp ProbeEntry: cell, weights, owned) and a ring of
+    // probes_cap slots of [probe_n][3] doubles (rho, ux, uy), one written by k_probes at every force-output iteration while probes are
+    // active; the iteration of each slot is kept on the host, as for the frames. lbm_drain_probes takes whole samples from the ring's head.
+    void* d_probe_table = nullptr;
+    double* d_probes = nullptr;
+    int probe_n = 0, probes_cap = 0, probes_head = 0, probes_count = 0;
+    bool probes_active = false;
+    std::vector<int> probes_t;          // [probes_cap]
+    int probes_opt = 0;                 // option "probes" (dry run only): record a probe sample behind every force kernel
     // The inflow: d_urow = the inlet velocity of every global row in the element type, read-only (step kernels, k_macros): inlet_velocity
     // on every row, or the profile of lbm_set_inlet_profile (has_profile), whose digest checkpoints carry and whose initial
     // equilibria f_eq(1,(u[y],0)), [ny][Q], k_init reads from d_feqrow.

@@ -4,6 +4,7 @@
 #include "lbm_col_api.hpp"
 #include "lbm_launch_k.hpp"
 #include "lbm_frames.hpp"
+#include "lbm_probes.hpp"
 #include "lbm_plan.hpp"
 #include "lbm_geom.hpp"
 #include "../../include/lbm_hip.h"
@@ -266,7 +267,7 @@ void lbm_destroy(lbm_ctx* c) {
     void* ptrs[] = {c->buf[0], c->buf[1], c->scratch, c->d_macro, c->d_maxbits, c->d_unstable, c->d_tbase, c->d_solid_count, c->d_feq,
                     c->d_force_now, c->d_force_log, c->d_halo, c->d_red, (void*)c->mview.bits, (void*)c->mview.sat, c->d_fpart,
                     c->d_urow, c->d_feqrow, c->d_stats, c->d_labels, c->d_body_box, c->d_body_chunks, c->d_body_first, c->d_body_part,
-                    c->d_body_now, c->d_body_log, c->d_frames};
+                    c->d_body_now, c->d_body_log, c->d_frames, c->d_probe_table, c->d_probes};
     for (void* q : ptrs)
         if (q) (void)hipFree(q);
     hipEvent_t evs[] = {c->ev_edge, c->ev_comm, c->ev_main, c->ev_t0, c->ev_t1, c->gev_main, c->gev_edge, c->gev_comm};
@@ -293,6 +294,7 @@ int lbm_initialise(lbm_ctx* c, int* solid_count_out) {
     c->log_count = 0;
     c->body_log_head = c->body_log_count = 0;
     c->frames_head = c->frames_count = 0;
+    c->probes_head = c->probes_count = 0;
     c->mid_pair = false;
     c->comm_issued = false;
     c->ext_split_pending = false;
@@ -555,6 +557,92 @@ int lbm_drain_frames(lbm_ctx* c, int* timesteps, float* frames, int max_frames) 
     if (timesteps) for (int j = 0; j < n; ++j) timesteps[j] = c->frames_t[(size_t)((c->frames_head + j) % c->frames_cap)];
     c->frames_head = (c->frames_head + n) % c->frames_cap;
     c->frames_count -= n;
+    return n;
+}
+
+/* ---- point probes: (rho, ux, uy) interpolated bilinearly at chosen points into a device ring at the force-output iterations (k_probes) ---- */
+// The argument checks shared by lbm_probes_begin and lbm_debug_probe_table; the text names the offender.
+static int check_probes(const double* xy, int n, int nx, int ny) {
+    if (!xy) return fail(LBM_ERR_ARG, "probes: null coordinate array");
+    if (n < 1) return fail(LBM_ERR_ARG, "probes: n = %d < 1", n);
+    if (n > LBM_PROBES_MAX) return fail(LBM_ERR_ARG, "probes: n = %d > LBM_PROBES_MAX = %d", n, LBM_PROBES_MAX);
+    for (int j = 0; j < n; ++j) {
+        const double px = xy[2 * j], py = xy[2 * j + 1];
+        if (!std::isfinite(px) || !std::isfinite(py)) return fail(LBM_ERR_ARG, "probe %d: (%g, %g) is not finite", j, px, py);
+        if (px < 0.0 || px > (double)(nx - 1)) return fail(LBM_ERR_ARG, "probe %d: x = %.17g outside the domain 0..%d", j, px, nx - 1);
+        if (py < 0.0 || py > (double)(ny - 1)) return fail(LBM_ERR_ARG, "probe %d: y = %.17g outside the domain 0..%d", j, py, ny - 1);
+    }
+    return LBM_OK;
+}
+
+int lbm_probes_begin(lbm_ctx* c, const double* xy, int n, int capacity) {
+    if (!c || !c->initialised) return fail(LBM_ERR_ARG, "lbm_probes_begin needs an initialised context");
+    { int cr = check_probes(xy, n, c->nx, c->p.ny); if (cr) return cr; }
+    if (capacity < 1) return fail(LBM_ERR_ARG, "probe ring capacity %d < 1", capacity);
+    HIPCHK(hipSetDevice(c->device));
+    { int jr = join_comm(c); if (jr) return jr; }
+    HIPCHK(hipStreamSynchronize(c->stream));      // (a sample still in flight reads the table and writes the ring this call replaces)
+    if (c->d_probes) { (void)hipFree(c->d_probes); c->d_probes = nullptr; }
+    if (c->d_probe_table) { (void)hipFree(c->d_probe_table); c->d_probe_table = nullptr; }
+    c->probes_active = false;
+    c->probes_head = c->probes_count = 0;
+    c->probe_n = 0; c->probes_cap = 0;
+    std::vector<lbmk::ProbeEntry> table((size_t)n);
+    for (int j = 0; j < n; ++j) table[(size_t)j] = lbmk::probe_entry(xy[2 * j], xy[2 * j + 1], c->p.y_start, c->nyl);
+    const size_t tbytes = sizeof(lbmk::ProbeEntry) * (size_t)n, bytes = 3 * sizeof(double) * (size_t)n * (size_t)capacity;
+    if (hipMalloc(&c->d_probe_table, tbytes) != hipSuccess || hipMalloc(&c->d_probes, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        if (c->d_probe_table) { (void)hipFree(c->d_probe_table); c->d_probe_table = nullptr; }
+        c->d_probes = nullptr;
+        return fail(LBM_ERR_ALLOC, "probes: no device memory for a ring of %d samples of %d probes (%zu bytes)", capacity, n, bytes);
+    }
+    HIPCHK(hipMemcpy(c->d_probe_table, table.data(), tbytes, hipMemcpyHostToDevice));
+    c->probe_n = n; c->probes_cap = capacity;
+    c->probes_t.assign((size_t)capacity, 0);
+    c->probes_active = true;
+    return LBM_OK;
+}
+
+int lbm_probes_end(lbm_ctx* c) {
+    if (!c) return fail(LBM_ERR_ARG, "null context");
+    c->probes_active = false;
+    return LBM_OK;
+}
+
+int lbm_probes_count(const lbm_ctx* c) { return c ? c->probe_n : LBM_ERR_ARG; }
+int lbm_probes_pending(const lbm_ctx* c) { return c ? c->probes_count : LBM_ERR_ARG; }
+
+int lbm_drain_probes(lbm_ctx* c, int* timesteps, double* vals, int max_samples) {
+    if (!c || max_samples < 0 || (max_samples > 0 && !vals)) return fail(LBM_ERR_ARG, "lbm_drain_probes: null argument or max_samples < 0");
+    if (!c->d_probes || c->probes_count < 1 || max_samples < 1) return 0;
+    HIPCHK(hipSetDevice(c->device));
+    { int jr = join_comm(c); if (jr) return jr; }
+    const int m = std::min(max_samples, c->probes_count);
+    const size_t per = 3 * (size_t)c->probe_n;
+    const int m1 = std::min(m, c->probes_cap - c->probes_head);      // the ring: up to the end of the buffer, then from its start
+    HIPCHK(hipMemcpyAsync(vals, c->d_probes + per * (size_t)c->probes_head, per * sizeof(double) * (size_t)m1, hipMemcpyDeviceToHost, c->stream));
+    if (m > m1) HIPCHK(hipMemcpyAsync(vals + per * (size_t)m1, c->d_probes, per * sizeof(double) * (size_t)(m - m1), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (timesteps) for (int j = 0; j < m; ++j) timesteps[j] = c->probes_t[(size_t)((c->probes_head + j) % c->probes_cap)];
+    c->probes_head = (c->probes_head + m) % c->probes_cap;
+    c->probes_count -= m;
+    return m;
+}
+
+/* TEST HOOK (no device needed): the probe table lbm_probes_begin uploads for the strip [y_start, y_start + local_ny): see include/lbm_hip.h. */
+int lbm_debug_probe_table(const double* xy, int n, int nx, int ny, int y_start, int local_ny, int* cells4, double* weights2, int* owned) {
+    if (nx < 1 || ny < 1 || y_start < 0 || local_ny < 1 || y_start + local_ny > ny) return fail(LBM_ERR_ARG, "probe table: strip [%d, %d) outside the lattice %dx%d", y_start, y_start + local_ny, nx, ny);
+    { int cr = check_probes(xy, n, nx, ny); if (cr) return cr; }
+    for (int j = 0; j < n; ++j) {
+        const lbmk::ProbeEntry e = lbmk::probe_entry(xy[2 * j], xy[2 * j + 1], y_start, local_ny);
+        if (cells4) {      // x1, y1 as k_probes forms them from the entry
+            cells4[4 * j] = e.x0; cells4[4 * j + 1] = e.y0;
+            cells4[4 * j + 2] = e.x0 + 1 < nx ? e.x0 + 1 : nx - 1;
+            cells4[4 * j + 3] = y_start + e.y0 + 1 < ny ? e.y0 + 1 : e.y0;
+        }
+        if (weights2) { weights2[2 * j] = e.fx; weights2[2 * j + 1] = e.fy; }
+        if (owned) owned[j] = e.owned;
+    }
     return n;
 }
 
@@ -1016,6 +1104,7 @@ int lbm_set_option(lbm_ctx* c, const char* key, long value) {
         if (c->initialised) return lbm_frames_begin(c, (int)value, LBM_FRAMES_DEFAULT_CAPACITY);
         c->frames_opt = (int)value;
     }
+    else if (k == "probes") c->probes_opt = (int)value ? 1 : 0;      // dry run only (lbm_debug_choreography): a probe sample behind every force kernel
     else if (k == "bodies") c->bodies_opt = (int)value ? 1 : 0;      // dry run only (lbm_debug_choreography): a body-force sample behind every force kernel
     else if (k == "graph") { if (value < 0 || value > 2) return fail(LBM_ERR_ARG, "graph must be 0, 1 or 2"); c->use_graph = (int)value; }
     else if (k == "loopback") c->loopback = (int)value;   // 0 off, 1 device copies, 2 RCCL self send/recv
@@ -1236,6 +1325,7 @@ int lbm_debug_choreography(int nx, int ny, const int* bounds2, int nstrips, int 
         if (c->stats_opt >= 0) { c->stats_active = true; c->stats_from = c->stats_opt; }      // (no accumulators: nothing is launched)
         if (c->bodies_opt) c->body_n = 1;                                                     // (no labels either)
         if (c->frames_opt > 0) { c->frames_active = true; c->frames_k = c->frames_opt; }      // (no ring: nothing is launched)
+        if (c->probes_opt) { c->probes_active = true; c->probe_n = 1; }                       // (no table and no ring either)
     }
     if (transport < 2) {
         for (int k = 0; k < nstrips; ++k) {

@@ -262,3 +262,26 @@ int launch_frame_sample(lbm_ctx* c, int t) {
     c->frames_count++;
     return LBM_OK;
 }
+
+// One sample of the point probes (k_probes, lbm_probes_begin) of a force-output iteration t into the next free slot of the ring:
+// buf[cur] = P_t, the snapshot that of launch_stats. Queued directly behind the force kernel (and the body, statistics and frame samples)
+// on the compute stream, behind the same join. do_steps has checked that the ring has room.
+template <typename T>
+int launch_probe_sample(lbm_ctx* c, int t) {
+    if (c->rec) {      // dry run: the strip's rows of P_t, the ghost row below (the pull of an inlet / outlet cell of row 0) and two above (y1 of a probe on the last row; its pull); writes its own slot
+        ChoreoOp o; o.kind = ChoreoOp::PROBES; o.strip = c->group_k; o.stream = 0; o.buf = c->cur; o.t = t; o.r0 = -1; o.r1 = c->nyl + 2; o.r_strip = c->group_k;
+        c->rec->ops.push_back(o);
+        return LBM_OK;
+    }
+    const int slot = (c->probes_head + c->probes_count) % c->probes_cap;
+    ProbeArgs<T> a;
+    a.m = make_macro_args<T>(c, c->buf[c->cur]);
+    a.table = static_cast<const ProbeEntry*>(c->d_probe_table);
+    a.n = c->probe_n;
+    a.out = c->d_probes + 3 * (size_t)c->probe_n * (size_t)slot;
+    launch_probes<T>(a, c->stream);
+    HIPCHK(hipGetLastError());
+    c->probes_t[(size_t)slot] = t;
+    c->probes_count++;
+    return LBM_OK;
+}

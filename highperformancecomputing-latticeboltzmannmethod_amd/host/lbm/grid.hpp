@@ -306,6 +306,36 @@ public:
         }
         return out;
     }
+    // point probes (lbm_probes_*; the reference has none): every strip is given the same global points and samples those of its rows
+    // (+0.0 for the others); a drained sample is the strips' values added up in strip order, like the partial force sums.
+    struct ProbeSample { int timestep; std::vector<double> vals; };      // [n][3]: rho, ux, uy
+    void probes_begin(const std::vector<double>& xy, int capacity) {
+        for (lbm_ctx* c : ctx_) check(lbm_probes_begin(c, xy.data(), (int)(xy.size() / 2), capacity), "lbm_probes_begin");
+    }
+    std::vector<ProbeSample> drain_probes() const {
+        std::vector<ProbeSample> out;
+        const int n = lbm_probes_count(ctx_[0]), m = lbm_probes_pending(ctx_[0]);
+        check(m, "lbm_probes_pending");
+        if (n < 1 || m < 1) return out;
+        const size_t per = 3 * (size_t)n;
+        out.resize((size_t)m);
+        std::vector<double> part((size_t)m * per);
+        std::vector<int> ts((size_t)m);
+        for (size_t k = 0; k < ctx_.size(); ++k) {
+            const int got = lbm_drain_probes(ctx_[k], ts.data(), part.data(), m);
+            check(got, "lbm_drain_probes");
+            if (got != m) throw std::runtime_error("the strips disagree on the number of pending probe samples");
+            for (int j = 0; j < m; ++j) {
+                ProbeSample& s = out[(size_t)j];
+                if (k == 0) { s.timestep = ts[(size_t)j]; s.vals.assign(part.begin() + (size_t)j * per, part.begin() + ((size_t)j + 1) * per); }
+                else {
+                    if (s.timestep != ts[(size_t)j]) throw std::runtime_error("the strips disagree on the iteration of a probe sample");
+                    for (size_t q = 0; q < per; ++q) s.vals[q] += part[(size_t)j * per + q];
+                }
+            }
+        }
+        return out;
+    }
     const char* plan() const { return lbm_plan(ctx_[0]); }
     lbm_ctx* handle(int k = 0) const { return ctx_[(size_t)k]; }
 

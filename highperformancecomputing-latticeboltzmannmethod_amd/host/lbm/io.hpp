@@ -35,6 +35,7 @@ public:
     void put(const char* s) { std::fputs(s, fp_); }
     void put_int(long v) { std::fprintf(fp_, "%ld", v); }
     void put_f8(double v) { std::fprintf(fp_, "%.8f", v); }
+    void put_g17(double v) { std::fprintf(fp_, "%.17g", v); }      // round-trips a double
     void flush() { if (fp_) std::fflush(fp_); }
     void close() { if (fp_) { std::fclose(fp_); fp_ = nullptr; } }
 private:
@@ -94,6 +95,27 @@ public:
         for (double v : {fx, fy, cd, cl}) { bodies_->put(","); bodies_->put_f8(v); }
         bodies_->put("\n");
         if (timestep % 10000 == 0) bodies_->flush();
+    }
+
+    // probes.csv (lbm_solver --probes / --probe-line; the reference has none): one row per sample and probe, the probe's point and its
+    // (rho, ux, uy) at %.17g, which reads back to the very doubles the device wrote. Created with the first row (or by open_probes).
+    void open_probes() {
+        if (probes_) return;
+        probes_ = std::make_unique<detail::TextFile>("probes.csv");
+        if (probes_->ok()) probes_->put("timestep,probe,x,y,rho,ux,uy\n");
+        else std::fprintf(stderr, "ERROR: Could not open probes.csv\n");
+    }
+    void append_probe_sample(int timestep, const std::vector<double>& vals, const SimulationParams& params) {
+        open_probes();
+        if (!probes_->ok()) return;
+        for (int j = 0; j < params.probe_count(); ++j) {
+            probes_->put_int(timestep); probes_->put(","); probes_->put_int(j);
+            for (double v : {params.probe_xy[2 * (size_t)j], params.probe_xy[2 * (size_t)j + 1], vals[3 * (size_t)j], vals[3 * (size_t)j + 1], vals[3 * (size_t)j + 2]}) {
+                probes_->put(","); probes_->put_g17(v);
+            }
+            probes_->put("\n");
+        }
+        if (timestep % 10000 == 0) probes_->flush();
     }
 
     // IOManager::write_vtk_timestep (LBMIO.h:55-111): legacy ASCII STRUCTURED_POINTS, vtk_output/lbm_%06d.vtk.
@@ -311,6 +333,7 @@ private:
 
     std::unique_ptr<detail::TextFile> forces_;
     std::unique_ptr<detail::TextFile> bodies_;      // forces_bodies.csv: runs with --obstacle-bodies only
+    std::unique_ptr<detail::TextFile> probes_;      // probes.csv: runs with --probes / --probe-line only
     std::vector<ForceSample> samples_;
     std::mutex mu_;
     std::condition_variable cv_;

@@ -56,6 +56,10 @@ struct SimulationParams {
     // frame (rho, ux, uy, vorticity) is written on the device at every output iteration (lbm_frames_begin) and drained into
     // vtk_output/frame_%06d.vtk; the full-resolution fields are not fetched for it.
     int frame_stride = 0;
+    // point probes (lbm_solver --probes / --probe-line; not in the reference): [n][2] points (x, y) in global lattice coordinates, empty =
+    // off. (rho, ux, uy) is sampled at them on the device at every output iteration, bilinearly (lbm_probes_begin), and drained into
+    // probes.csv; no field is fetched for it.
+    std::vector<double> probe_xy;
 
     double nu() const { return (tau - 0.5) / 3.0; }
     bool masked() const { return !obstacle_mask.empty(); }
@@ -66,6 +70,8 @@ struct SimulationParams {
     bool trt() const { return trt_magic > 0.0; }
     bool stats() const { return stats_start >= 0; }
     bool frames() const { return frame_stride > 0; }
+    bool probes() const { return !probe_xy.empty(); }
+    int probe_count() const { return (int)(probe_xy.size() / 2); }
     double reynolds() const {
         if (masked()) return inlet_velocity * mask_frontal_height / nu();
         return inlet_velocity * (2.0 * cylinder_radius * ny) / nu();

@@ -35,6 +35,11 @@ public:
                 std::printf("  Frames: rho, u and vorticity averaged over %dx%d cells, one every %d steps (vtk_output/frame_*.vtk)\n", params_.frame_stride,
                             params_.frame_stride, params_.output_frequency);
         }
+        if (params_.probes()) {      // (two samples per chunk of run(), like the frames)
+            grid_.probes_begin(params_.probe_xy, 4);
+            if (!opt_.quiet)
+                std::printf("  Probes: rho and u at %d points, one sample every %d steps (probes.csv)\n", params_.probe_count(), params_.output_frequency);
+        }
         if (!opt_.quiet && params_.profiled())
             std::printf("  Inlet: profile %s, mean velocity %g (Cd / Cl refer to it)\n", params_.inlet_profile_spec.c_str(), params_.inlet_velocity);
         if (!opt_.quiet && params_.les())
@@ -75,6 +80,7 @@ public:
         if (!opt_.quiet) { std::printf("Starting LBM cylinder flow simulation...\n"); std::fflush(stdout); }
         const int T = params_.num_timesteps, of = std::max(1, params_.output_frequency);
         if (params_.bodied()) io.open_body_forces();
+        if (params_.probes()) io.open_probes();
         const auto w0 = std::chrono::steady_clock::now();
         int t = grid_.steps_done();
         const int t_begin = t;
@@ -92,6 +98,8 @@ public:
                 if (opt_.async_vtk) io.write_frame_async(std::move(fr.planes), params_, fr.timestep);
                 else IOManager::write_frame_vtk(fr.planes, params_, fr.timestep);
             }
+            for (const auto& s : grid_.drain_probes())      // the probe samples of this chunk
+                if (bad < 0 || s.timestep <= bad) io.append_probe_sample(s.timestep, s.vals, params_);
             if (bad >= 0) {
                 std::fprintf(stderr, "Simulation unstable at timestep %d\n", bad);
                 return false;

@@ -6,6 +6,7 @@
 #include "compat/LBMSolver.h"
 #include "lbm/geometry.hpp"
 #include "lbm/inlet.hpp"
+#include "lbm/probes.hpp"
 
 #include <cmath>
 #include <cstdio>
@@ -13,6 +14,7 @@
 #include <cstring>
 #include <exception>
 #include <string>
+#include <vector>
 
 static void usage() {
     std::puts("lbm_solver [--nx N] [--ny N] [--steps N] [--output-frequency N] [--tau X] [--inlet-velocity X]\n"
@@ -22,7 +24,7 @@ static void usage() {
               "           [--checkpoint FILE] [--restart FILE] [--obstacle-mask FILE.pgm] [--obstacle-bodies FILE.pgm]\n"
               "           [--inlet-profile parabolic|FILE] [--print-inlet-profile] [--smagorinsky CS] [--trt-magic LAMBDA]\n"
               "           [--stats-start N]\n"
-              "           [--frame-stride K]\n"
+              "           [--frame-stride K] [--probes FILE] [--probe-line x0 y0 x1 y1 n]\n"
               "Defaults are the reference's SimulationParams (LBMConfig.h:37-51). --reynolds sets the inlet velocity\n"
               "from tau and the cylinder diameter so that params.reynolds() equals RE.\n"
               "--gpus N cuts the lattice into N row strips, one per GPU of this node, advanced in lockstep by this process\n"
@@ -52,7 +54,12 @@ static void usage() {
               "--frame-stride K: at every output iteration the device averages rho, ux, uy and the vorticity d uy/dx - d ux/dy over\n"
               "K x K cells (1 <= K <= 64; K must divide nx, ny and the rows of every strip) and the frame is written as\n"
               "vtk_output/frame_%06d.vtk (STRUCTURED_POINTS, spacing K; vector velocity, scalars density and vorticity), also with\n"
-              "--no-vtk: 4 nx ny / K^2 floats per frame leave the device instead of the full-resolution fields.");
+              "--no-vtk: 4 nx ny / K^2 floats per frame leave the device instead of the full-resolution fields.\n"
+              "--probes FILE: point probes, one `x y` per line in lattice coordinates (0 <= x <= nx-1, 0 <= y <= ny-1; '#' starts a\n"
+              "comment). --probe-line x0 y0 x1 y1 n: n equally spaced probes from (x0, y0) to (x1, y1), end points included; may be\n"
+              "repeated and combined with --probes (at most 65536 points in all, numbered in the order given). At every output\n"
+              "iteration the device interpolates rho, ux, uy bilinearly at the probes and probes.csv gains one row per probe\n"
+              "(timestep,probe,x,y,rho,ux,uy at %.17g); no field leaves the device for it.");
 }
 
 int main(int argc, char** argv) {
@@ -65,6 +72,8 @@ int main(int argc, char** argv) {
     const char* trt_magic = nullptr;
     const char* stats_start = nullptr;
     const char* frame_stride = nullptr;
+    std::vector<LBM::ProbePoint> probe_points;
+    bool probes_asked = false;
     double reynolds = -1.0;
     for (int a = 1; a < argc; ++a) {
         const std::string k = argv[a];
@@ -104,6 +113,22 @@ int main(int argc, char** argv) {
         else if (k == "--trt-magic") trt_magic = val();
         else if (k == "--stats-start") stats_start = val();
         else if (k == "--frame-stride") frame_stride = val();
+        else if (k == "--probes" || k == "--probe-line") {   // parsed here, in the order given; checked against the lattice below
+            try {
+                std::vector<LBM::ProbePoint> more;
+                if (k == "--probes") more = LBM::read_probe_file(val());
+                else {
+                    if (a + 5 >= argc) { std::fprintf(stderr, "--probe-line takes five values: x0 y0 x1 y1 n\n"); return 2; }
+                    more = LBM::parse_probe_line(argv + a + 1);
+                    a += 5;
+                }
+                probe_points.insert(probe_points.end(), more.begin(), more.end());
+                probes_asked = true;
+            } catch (const std::exception& e) {
+                std::fprintf(stderr, "%s\n", e.what());
+                return 2;
+            }
+        }
         else if (k == "--help" || k == "-h") { usage(); return 0; }
         else { std::fprintf(stderr, "unknown option %s\n", k.c_str()); usage(); return 2; }
     }
@@ -172,6 +197,19 @@ int main(int argc, char** argv) {
             y += rows;
         }
         params.frame_stride = (int)K;
+    }
+    if (probes_asked) {   // checked before any device is touched: points inside the lattice, and a cadence to sample at
+        if (params.output_frequency <= 0) {
+            std::fprintf(stderr, "--probes / --probe-line need --output-frequency > 0: probes are sampled at the output cadence\n");
+            return 2;
+        }
+        try {
+            LBM::check_probe_points(probe_points, params.nx, params.ny);
+        } catch (const std::exception& e) {
+            std::fprintf(stderr, "%s\n", e.what());
+            return 2;
+        }
+        for (const LBM::ProbePoint& p : probe_points) { params.probe_xy.push_back(p.x); params.probe_xy.push_back(p.y); }
     }
     if (!params.obstacle_bodies_file.empty() && !params.obstacle_mask_file.empty()) {
         std::fprintf(stderr, "--obstacle-bodies and --obstacle-mask exclude each other: the labels are the mask\n");

@@ -193,6 +193,44 @@ int  lbm_frames_pending(const lbm_ctx* c);
  * NULL), removes them from the ring and returns n. Synchronises. 0 when frames were never begun or none is pending. */
 int  lbm_drain_frames(lbm_ctx* c, int* timesteps, float* frames, int max_frames);
 
+/* ---- point probes with bilinear sampling (no reference counterpart: the reference writes whole fields, LBMIO.h:62-111; what this replaces
+ * is a caller's lbm_get_macros — a synchronisation and 3 nx local_ny doubles over the bus — or a k = 1 frame — 4 nx local_ny floats —
+ * per sample, to read a few dozen values) ----
+ * A PROBE is a point (px, py) in GLOBAL lattice coordinates, given as doubles, 0 <= px <= nx - 1 and 0 <= py <= ny - 1. The SAMPLE of
+ * iteration t at a probe is (rho, ux, uy) in double, interpolated bilinearly from the fine snapshot: cell for cell what lbm_get_macros
+ * returns on a context with steps_done == t + 1 (the definition the statistics and the frames use; fp32 contexts widen to double first):
+ *     x0 = floor(px), fx = px - x0, x1 = min(x0 + 1, nx - 1);   y likewise with ny - 1
+ *     a = (1 - fx) v(x0, y0) + fx v(x1, y0);   b = (1 - fx) v(x0, y1) + fx v(x1, y1);   v = (1 - fy) a + fy b
+ * Every product and every sum is rounded to double (no contraction). A cell whose weight is exactly zero is NOT read and its term is left
+ * out: with fx == 0, a = v(x0, y0); with fy == 0, v = a. A probe on a lattice node therefore returns that cell's macros bit for bit and
+ * reads no neighbour, in particular no ghost row. Solid cells enter with the (1, 0, 0) the snapshot gives them: documented, not corrected.
+ * Strips: a probe belongs to the strip whose rows contain floor(py). The owner may read the ghost row next to its north face (y1) and,
+ * for a probe in column 0 or nx - 1, the row beyond it, which the inlet / outlet cell pulls from: the rows the frame sample reads at the
+ * same point of the schedule. Every other strip writes +0.0 for that probe: strips ADD UP like partial force sums. Every plan, layout,
+ * arithmetic mode and decomposition gives the same bits for the same macros.
+ * With probes active lbm_step / lbm_group_step append one sample to a device ring at exactly the iterations at which they append a
+ * force-log row (output_frequency > 0 and t % output_frequency == 0), directly behind the force kernel (and the body, statistics and frame
+ * samples), on the compute stream without a synchronisation; with the ring full they fail like the frame ring (LBM_ERR_ARG, "probe ring
+ * full (%d samples): drain it (lbm_drain_probes)"). Probes change reporting only: populations, force logs, statistics, frames,
+ * lbm_kernel_name and checkpoints (which do not carry probes) are those of a run without.
+ * lbm_probes_begin: on an initialised context; xy = [n][2] GLOBAL coordinates (every strip of a run is given the same array),
+ * 1 <= n <= LBM_PROBES_MAX, capacity >= 1 samples. Uploads a table {cell x0, local y0, fx, fy, owned} per probe and allocates the ring
+ * (capacity x n x 3 doubles; the iterations stay on the host; freed by lbm_destroy). Calling it again replaces the table and empties the
+ * ring; lbm_initialise empties the ring. LBM_ERR_ARG (the text names the offender): a null pointer, an uninitialised context, n < 1,
+ * n > LBM_PROBES_MAX, capacity < 1, a coordinate that is not finite or lies outside the domain; LBM_ERR_ALLOC: no device memory for the ring. */
+#define LBM_PROBES_MAX 65536
+int  lbm_probes_begin(lbm_ctx* c, const double* xy, int n, int capacity);
+/* Stops sampling and keeps the undrained samples. */
+int  lbm_probes_end(lbm_ctx* c);
+/* n of lbm_probes_begin; 0 without probes. */
+int  lbm_probes_count(const lbm_ctx* c);
+/* Samples in the ring that have not been drained (in a group: the same on every member). */
+int  lbm_probes_pending(const lbm_ctx* c);
+/* Copies up to max_samples whole samples, oldest first, as [m][n][3] doubles (rho, ux, uy; this strip's contribution: +0.0 for a probe
+ * another strip owns), their iterations into timesteps (may be NULL), removes them from the ring and returns m. Synchronises. 0 when
+ * probes were never begun or none is pending. */
+int  lbm_drain_probes(lbm_ctx* c, int* timesteps, double* vals, int max_samples);
+
 /* Debug/parity accessor: ghost-inclusive AoS [(local_ny+2)][(nx+2)][9] exactly as Grid::f_current /
  * Grid::f_next index it (LBMGrid.h:105-107,116-119). which: 0 = f_current, 1 = f_next. */
 int  lbm_get_populations(lbm_ctx* c, int which, double* aos);
@@ -346,6 +384,8 @@ int  lbm_load_state(lbm_ctx* c, const char* path);
  *   "stats" N     lbm_stats_begin(c, N) (before lbm_initialise: begun at its end)
  *   "frames" K    lbm_frames_begin(c, K, LBM_FRAMES_DEFAULT_CAPACITY) (before lbm_initialise: begun at its end). In
  *                 lbm_debug_choreography: the dry run records a frame sample behind every force kernel
+ *   "probes" 1    lbm_debug_choreography only: the dry run records a probe sample behind every force kernel (a real context gets its
+ *                 probes from lbm_probes_begin and ignores the key)
  *   "bodies" 1    lbm_debug_choreography only: the dry run records a per-body force sample behind every force kernel (a real context
  *                 gets its bodies from lbm_set_body_labels and ignores the key)
  *   "timing" 1    record HIP events around each lbm_step call (lbm_last_step_kernel_ms). */
@@ -404,7 +444,9 @@ int lbm_debug_group_pool(int n, int rounds, int fail_strip, int fail_round, int 
  * least one of them a write, that no event orders; STALE: a launch (or the force kernel, or — option "stats" — the statistics sample, which
  * also reads one ghost row per face, or — option "bodies" — the per-body force sample, which reads the force kernel's rows and writes a log slot of its own, or — option "frames" —
  * the frame sample, which reads the force kernel's rows plus TWO ghost rows per face (the ghost row next to the face for d/dy, and the
- * row beyond it that this row's outlet cell pulls from) and writes a ring slot of its own) reads a row that does not hold the iteration it
+ * row beyond it that this row's outlet cell pulls from) and writes a ring slot of its own, or — option "probes" — the probe sample, which
+ * reads rows [-1, local_ny + 2) of buf[cur] (a probe's y1 on the ghost row next to the north face and the row its inlet / outlet cell
+ * pulls from; the pull of row 0) and writes a ring slot of its own) reads a row that does not hold the iteration it
  * needs — or < 0; `out` receives their description (and, with dump != 0, every recorded operation). What it replaces: the ordering the
  * reference gets from MPI_Waitall before unpack_received_data (LBMGrid.h:278-283).
  * bounds2 = nstrips x {y_start, rows}; transport 0 in-process group with peer copies, 1 in-process group over RCCL, 2 ONE strip as a rank
@@ -437,6 +479,12 @@ int lbm_debug_geometry(const unsigned char* mask, int nx, int ny, int y_start, i
  * bodies in label order; *nchunks_out (nullable) = its length. No reference counterpart. */
 int lbm_debug_body_chunks(const unsigned char* labels, int nx, int ny, int y_start, int local_ny, int* boxes4, int boxes_cap,
                           long* chunks3, int chunks_cap, int* nchunks_out);
+/* Test hook, callable without a device: the table lbm_probes_begin uploads for the strip [y_start, y_start + local_ny) of an nx x ny
+ * lattice (csrc/lbm_probes.hpp probe_entry), with lbm_probes_begin's checks of xy and n. Per probe: cells4 = {x0, LOCAL y0, x1, LOCAL y1}
+ * with x1, y1 clamped at the domain's edge as k_probes clamps them (local y1 == local_ny: the ghost row next to the north face), weights2 =
+ * {fx, fy}, owned = 1 where floor(py) lies in the strip's rows; a probe that is not owned has cell (0, 0) and weights 0. Any output may be
+ * NULL. Returns n or < 0. No reference counterpart. */
+int lbm_debug_probe_table(const double* xy, int n, int nx, int ny, int y_start, int local_ny, int* cells4, double* weights2, int* owned);
 /* SHA-256 (16 hex digits) of the sources this binary was compiled from (csrc/ and this header); build.py rebuilds
  * when it differs from the tree, bench.py prints it. */
 const char* lbm_build_id(void);
