@@ -88,6 +88,7 @@ def lib():
         ip = C.POINTER(C.c_int)
         L.lbm_debug_geometry.argtypes = [C.POINTER(C.c_ubyte), C.c_int, C.c_int, C.c_int, C.c_int, ip, C.POINTER(C.c_ulonglong), C.c_long,
                                          ip, C.c_long, ip, C.c_int, ip]
+        L.lbm_debug_ring.argtypes = [C.c_int, ip, C.c_int, ip]
         L.lbm_comm_unique_id.argtypes = [vp]
         L.lbm_comm_init.argtypes = [vp, C.c_int, C.c_int, vp]
         L.lbm_comm_allreduce.argtypes = [vp, dp, C.c_int, C.c_int]
@@ -174,6 +175,19 @@ def debug_geometry(solid, y_start=0, local_ny=0, boxes=()):
     if rc < 0:
         raise LbmError(L.lbm_last_error().decode())
     return d, bits, sat, near
+
+
+def debug_ring(capacity, ops):
+    """lbm_debug_ring (no device): the index arithmetic of the sample rings (body-force log, frames, probes) on a ring of `capacity` slots.
+    ops: -1 pushes, m >= 0 takes up to m of the oldest. Returns (one triple per operation, samples pending at the end): a push gives
+    (slot, -1, -1), or (-1, -1, -1) on a full ring; a take gives (start, n1, n2): slots [start, start + n1), then [0, n2)."""
+    ops = np.ascontiguousarray(ops, dtype=np.int32)
+    out = np.zeros((len(ops), 3), dtype=np.int32)
+    ip = C.POINTER(C.c_int)
+    rc = lib().lbm_debug_ring(capacity, ops.ctypes.data_as(ip), len(ops), out.ctypes.data_as(ip))
+    if rc < 0:
+        raise LbmError(lib().lbm_last_error().decode())
+    return out, rc
 
 
 def _label_bytes(labels, nx, ny):

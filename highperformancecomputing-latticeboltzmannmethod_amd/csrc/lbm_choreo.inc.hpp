@@ -134,19 +134,15 @@ struct ChoreoChecker {
                         write_row(idx, s, o.strip, o.buf, o.w0[0] + j, level);
                     }
                     break;
-                case ChoreoOp::FORCES:
-                case ChoreoOp::STATS:
-                case ChoreoOp::BODIES:      // the per-body sample reads what the force kernel reads; every sample writes a log slot of its own
-                case ChoreoOp::FRAME:       // the frame sample reads two ghost rows per face too and writes a ring slot of its own
-                case ChoreoOp::PROBES:      // the probe sample reads one ghost row below and two above (y1 of a probe on the last row, and its pull); a ring slot of its own
-                    for (int y = o.r0; y < o.r1; ++y) { read_row(idx, s, o.strip, o.buf, y); need_level(idx, o.strip, o.buf, y, o.t); }
-                    if (o.kind == ChoreoOp::STATS) {      // a read-modify-write of the strip's accumulators: ordered behind the sample before it
-                        RowState& a = acc[(size_t)o.strip];
-                        if (!hb(a.w_stream, a.w_seq, s)) race(a.w_op, idx, o.strip, ACC_BUF, 0);
-                        a.w_stream = s; a.w_seq = me[(size_t)s]; a.w_op = idx;
-                    }
-                    break;
                 default: break;
+            }
+            if (o.is_sample()) {      // reads the rows of ChoreoOp::samples; writes a log or ring slot of its own, which nothing else touches
+                for (int y = o.r0; y < o.r1; ++y) { read_row(idx, s, o.strip, o.buf, y); need_level(idx, o.strip, o.buf, y, o.t); }
+                if (o.kind == ChoreoOp::STATS) {      // a read-modify-write of the strip's accumulators: ordered behind the sample before it
+                    RowState& a = acc[(size_t)o.strip];
+                    if (!hb(a.w_stream, a.w_seq, s)) race(a.w_op, idx, o.strip, ACC_BUF, 0);
+                    a.w_stream = s; a.w_seq = me[(size_t)s]; a.w_op = idx;
+                }
             }
         }
     }
@@ -164,9 +160,7 @@ inline std::string choreo_op_text(const ChoreoOp& o, int idx) {
     else if (o.kind == ChoreoOp::COPY) n += snprintf(b + n, sizeof(b) - n, " buf %d: rows [%d,%d) of strip %d -> rows [%d,%d)", o.buf, o.r0, o.r1, o.r_strip, o.w0[0], o.w1[0]);
     else if (o.kind == ChoreoOp::SEND) n += snprintf(b + n, sizeof(b) - n, " buf %d rows [%d,%d)", o.buf, o.r0, o.r1);
     else if (o.kind == ChoreoOp::RECV) n += snprintf(b + n, sizeof(b) - n, " buf %d rows [%d,%d)", o.buf, o.w0[0], o.w1[0]);
-    else if (o.kind == ChoreoOp::FORCES || o.kind == ChoreoOp::STATS || o.kind == ChoreoOp::BODIES || o.kind == ChoreoOp::FRAME || o.kind == ChoreoOp::PROBES)
-        n += snprintf(b + n, sizeof(b) - n, " t=%d reads buf %d rows [%d,%d)%s", o.t, o.buf, o.r0, o.r1,
-                      o.kind == ChoreoOp::STATS ? ", writes the accumulators" : o.kind == ChoreoOp::BODIES ? ", writes its log slot" : (o.kind == ChoreoOp::FRAME || o.kind == ChoreoOp::PROBES) ? ", writes its ring slot" : "");
+    else if (o.is_sample()) n += snprintf(b + n, sizeof(b) - n, " t=%d reads buf %d rows [%d,%d)%s", o.t, o.buf, o.r0, o.r1, o.sample().writes);
     return b;
 }
 

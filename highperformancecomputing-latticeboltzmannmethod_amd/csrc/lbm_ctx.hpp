@@ -200,19 +200,60 @@ struct ChoreoOp {
     int kind = 0;
     int strip = 0, stream = 0;      // the issuing strip, 0 main / 1 side stream
     int ev_strip = 0, ev = 0;       // RECORD / WAIT: the event's owner and 0 ev_main, 1 ev_edge, 2 ev_comm
-    int buf = 0;                    // KERNEL: the buffer written (it reads buf ^ 1); COPY / SEND / RECV / FORCES: the buffer touched
-    int t = 0, depth = 0;           // KERNEL: first iteration and iterations; FORCES / STATS / BODIES / FRAME / PROBES: the iteration
+    int buf = 0;                    // KERNEL: the buffer written (it reads buf ^ 1); COPY / SEND / RECV / a sample: the buffer touched
+    int t = 0, depth = 0;           // KERNEL: first iteration and iterations; a sample: the iteration
     int w0[2] = {0, 0}, w1[2] = {0, 0};   // rows written, [w0, w1) in local rows (ghost rows: < 0 or >= nyl); KERNEL: two ranges
-    int r0 = 0, r1 = 0, r_strip = -1;     // COPY / SEND / FORCES / STATS / BODIES / FRAME: rows read and whose (RECV: where the data comes from; -1: another process)
-                                          // (STATS: the strip's rows and ONE ghost row per face — the pull of the inlet / outlet cells of its first and last row;
-                                          //  FRAME: TWO per face — the ghost row next to the face for d/dy, whose outlet cell pulls from the row beyond it;
-                                          //  PROBES: rows [-1, nyl + 2) — a probe's y1 may be the ghost row next to the north face, whose inlet / outlet cell pulls one row further)
+    int r0 = 0, r1 = 0, r_strip = -1;     // COPY / SEND / a sample: rows read and whose (RECV: where the data comes from; -1: another process)
+    // The samples of an output point (sample_outputs, lbm_launch.inc.hpp), one row per kind from FORCES on: each reads rows
+    // [lo, nyl + hi) of its own strip's P_t on the compute stream and writes memory of its own, named in the dump.
+    struct Sample { int lo, hi; const char* writes; };
+    static constexpr Sample samples[5] = {
+        {0, 0, ""},                               // FORCES: the strip's rows
+        {-1, 1, ", writes the accumulators"},     // STATS: and ONE ghost row per face — the pull of the inlet / outlet cells of its first and last row
+        {0, 0, ", writes its log slot"},          // BODIES: what the force kernel reads (the labels carry the ghost rows' geometry)
+        {-2, 2, ", writes its ring slot"},        // FRAME: TWO ghost rows per face — the one next to the face for d/dy, whose outlet cell pulls from the row beyond it
+        {-1, 2, ", writes its ring slot"},        // PROBES: the ghost row below (the pull of an inlet / outlet cell of row 0) and two above (y1 of a probe on the last row; its pull)
+    };
+    bool is_sample() const { return kind >= FORCES && kind <= PROBES; }
+    const Sample& sample() const { return samples[kind - FORCES]; }
 };
 // ... and, for one rank of a multi-process run, the transcript of what exchange_rccl's posting loops WOULD hand to RCCL, in posting order:
 // kind 0 send / 1 recv / 2 end of a group call; `off`, `cnt` in elements of the buffer. lbm_debug_p2p_matching holds the transcripts of
 // neighbouring ranks against each other (RCCL pairs the k-th send to a peer with the peer's k-th receive from the sender).
 struct ChoreoP2P { int kind, peer; long off, cnt; };
 struct Choreo { std::vector<ChoreoOp> ops; std::vector<ChoreoP2P> p2p; };
+
+// A ring of samples on the device: ix.cap slots of `per` elements, one written at each output iteration (sample_outputs), drained oldest
+// first. `t` keeps the iteration of each slot on the host — it is known when the sample is issued — for the rings whose rows do not
+// carry it (frames, probes; empty for the body-force log). The index arithmetic is RingIndex (lbm_plan.hpp).
+template <typename E>
+struct DeviceRing {
+    E* d = nullptr;
+    size_t per = 0;
+    RingIndex ix;
+    std::vector<int> t;
+    E* next_slot() const { return d + per * (size_t)ix.next(); }
+    void commit(int step) { if (!t.empty()) t[(size_t)ix.next()] = step; ix.commit(); }      // once the sample is queued
+    void release() { if (d) (void)hipFree(d); d = nullptr; per = 0; ix = {}; t.clear(); }
+    hipError_t alloc(size_t per_slot, int cap, bool timesteps) {      // in place of the old ring; a failure leaves none
+        release();
+        const hipError_t e = hipMalloc(&d, per_slot * sizeof(E) * (size_t)cap);
+        if (e != hipSuccess) { d = nullptr; return e; }
+        per = per_slot; ix = {cap, 0, 0};
+        if (timesteps) t.assign((size_t)cap, 0);
+        return hipSuccess;
+    }
+    // up to `m` of the oldest samples to the host, through stream `s` (which everything that wrote them precedes); how many, or an error
+    int drain(hipStream_t s, E* out, int* timesteps, int m) {
+        const RingIndex::Span o = ix.oldest(m);
+        if (o.n1 > 0) HIPCHK(hipMemcpyAsync(out, d + per * (size_t)o.start, per * sizeof(E) * (size_t)o.n1, hipMemcpyDeviceToHost, s));
+        if (o.n2 > 0) HIPCHK(hipMemcpyAsync(out + per * (size_t)o.n1, d, per * sizeof(E) * (size_t)o.n2, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (timesteps && !t.empty()) { std::copy_n(t.begin() + o.start, o.n1, timesteps); std::copy_n(t.begin(), o.n2, timesteps + o.n1); }
+        ix.drop(o.n1 + o.n2);
+        return o.n1 + o.n2;
+    }
+};
 
 struct lbm_ctx {
     lbm_params p{};
@@ -257,8 +298,8 @@ struct lbm_ctx {
     int fpart_chunks = 0;
     // Per-body forces (lbm_set_body_labels): the labels of the strip's rows + one ghost row per face, one byte per cell, and the chunk
     // table of the bodies' boxes (lbm_geom.hpp pack_bodies), read by k_forces_bodies alone; uploaded once, never written by a kernel.
-    // body_n = B (0: no labels). The log is a ring of log_cap samples of B rows (t, fx, fy): lbm_drain_body_force_log takes whole
-    // samples from its head.
+    // body_n = B (0: no labels). The log (body_log) is a ring of log_cap samples of B rows (t, fx, fy): lbm_drain_body_force_log takes
+    // whole samples from its head.
     int body_n = 0, body_chunks = 0;
     unsigned char* d_labels = nullptr;
     int* d_body_box = nullptr;
@@ -266,25 +307,21 @@ struct lbm_ctx {
     int* d_body_first = nullptr;
     double* d_body_part = nullptr;      // [chunks][2]
     double* d_body_now = nullptr;       // [B][3]
-    double* d_body_log = nullptr;       // [log_cap][B][3]
-    int body_log_head = 0, body_log_count = 0;      // samples
+    DeviceRing<double> body_log;        // [log_cap][B][3]
     int bodies_opt = 0;                 // option "bodies" (dry run only): record a body-force sample behind every force kernel
-    // Coarsened flow frames (lbm_frames_begin): a ring of frames_cap slots of [4][nyl / k][nx / k] floats (rho, ux, uy, vorticity), one
-    // written by k_frame at every force-output iteration while frames are active; the iteration of each slot is kept on the host
-    // (it is known when the sample is issued). lbm_drain_frames takes whole frames from the ring's head.
-    float* d_frames = nullptr;
-    int frames_k = 0, frames_cap = 0, frames_head = 0, frames_count = 0;
+    // Coarsened flow frames (lbm_frames_begin): a ring of slots of [4][nyl / k][nx / k] floats (rho, ux, uy, vorticity), one written by
+    // k_frame at every force-output iteration while frames are active. lbm_drain_frames takes whole frames from the ring's head.
+    DeviceRing<float> frames;
+    int frames_k = 0;
     bool frames_active = false;
-    std::vector<int> frames_t;          // [frames_cap]
     int frames_opt = 0;                 // option "frames" K set before lbm_initialise: begun at its end (dry run: a frame sample behind every force kernel)
     // Point probes (lbm_probes_begin): a device table of probe_n entries (lbm_probes.hpp ProbeEntry: cell, weights, owned) and a ring of
-    // probes_cap slots of [probe_n][3] doubles (rho, ux, uy), one written by k_probes at every force-output iteration while probes are
-    // active; the iteration of each slot is kept on the host, as for the frames. lbm_drain_probes takes whole samples from the ring's head.
+    // slots of [probe_n][3] doubles (rho, ux, uy), one written by k_probes at every force-output iteration while probes are active.
+    // lbm_drain_probes takes whole samples from the ring's head.
     void* d_probe_table = nullptr;
-    double* d_probes = nullptr;
-    int probe_n = 0, probes_cap = 0, probes_head = 0, probes_count = 0;
+    DeviceRing<double> probes;
+    int probe_n = 0;
     bool probes_active = false;
-    std::vector<int> probes_t;          // [probes_cap]
     int probes_opt = 0;                 // option "probes" (dry run only): record a probe sample behind every force kernel
     // The inflow: d_urow = the inlet velocity of every global row in the element type, read-only (step kernels, k_macros): inlet_velocity
     // on every row, or the profile of lbm_set_inlet_profile (has_profile), whose digest checkpoints carry and whose initial

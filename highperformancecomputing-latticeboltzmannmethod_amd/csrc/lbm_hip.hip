@@ -267,7 +267,7 @@ void lbm_destroy(lbm_ctx* c) {
     void* ptrs[] = {c->buf[0], c->buf[1], c->scratch, c->d_macro, c->d_maxbits, c->d_unstable, c->d_tbase, c->d_solid_count, c->d_feq,
                     c->d_force_now, c->d_force_log, c->d_halo, c->d_red, (void*)c->mview.bits, (void*)c->mview.sat, c->d_fpart,
                     c->d_urow, c->d_feqrow, c->d_stats, c->d_labels, c->d_body_box, c->d_body_chunks, c->d_body_first, c->d_body_part,
-                    c->d_body_now, c->d_body_log, c->d_frames, c->d_probe_table, c->d_probes};
+                    c->d_body_now, c->body_log.d, c->frames.d, c->d_probe_table, c->probes.d};
     for (void* q : ptrs)
         if (q) (void)hipFree(q);
     hipEvent_t evs[] = {c->ev_edge, c->ev_comm, c->ev_main, c->ev_t0, c->ev_t1, c->gev_main, c->gev_edge, c->gev_comm};
@@ -292,9 +292,7 @@ int lbm_initialise(lbm_ctx* c, int* solid_count_out) {
     c->split_i = 0;
     c->steps_done = 0;
     c->log_count = 0;
-    c->body_log_head = c->body_log_count = 0;
-    c->frames_head = c->frames_count = 0;
-    c->probes_head = c->probes_count = 0;
+    c->body_log.ix.reset(); c->frames.ix.reset(); c->probes.ix.reset();
     c->mid_pair = false;
     c->comm_issued = false;
     c->ext_split_pending = false;
@@ -401,22 +399,18 @@ int lbm_get_body_forces(lbm_ctx* c, double* fxy) {
 
 int lbm_drain_body_force_log(lbm_ctx* c, lbm_body_force_row* rows, int max_rows) {
     if (!c || (!rows && max_rows > 0)) return fail(LBM_ERR_ARG, "null argument");
-    if (c->body_n < 1 || max_rows < c->body_n || c->body_log_count < 1) return 0;       // whole samples only
+    if (c->body_n < 1 || max_rows < c->body_n || c->body_log.ix.count < 1) return 0;       // whole samples only
     HIPCHK(hipSetDevice(c->device));
-    const int B = c->body_n, n = std::min(max_rows / B, c->body_log_count);
-    const int n1 = std::min(n, c->log_cap - c->body_log_head);      // the ring: up to the end of the buffer, then from its start
-    std::vector<double> h(3 * (size_t)B * n);
-    HIPCHK(hipMemcpyAsync(h.data(), c->d_body_log + 3L * B * c->body_log_head, 3 * sizeof(double) * B * n1, hipMemcpyDeviceToHost, c->stream));
-    if (n > n1) HIPCHK(hipMemcpyAsync(h.data() + 3 * (size_t)B * n1, c->d_body_log, 3 * sizeof(double) * B * (n - n1), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
+    const int B = c->body_n;
+    std::vector<double> h(3 * (size_t)B * std::min(max_rows / B, c->body_log.ix.count));
+    const int n = c->body_log.drain(c->stream, h.data(), nullptr, max_rows / B);
+    if (n < 0) return n;
     for (size_t k = 0; k < (size_t)B * n; ++k) {
         rows[k].timestep = (int)h[3 * k];
         rows[k].body = (int)(k % B) + 1;
         rows[k].fx = h[3 * k + 1];
         rows[k].fy = h[3 * k + 2];
     }
-    c->body_log_head = (c->body_log_head + n) % c->log_cap;
-    c->body_log_count -= n;
     return B * n;
 }
 
@@ -507,8 +501,6 @@ int lbm_stats_restore(lbm_ctx* c, const double* sums6, int samples) {
 }
 
 /* ---- coarsened flow frames: rho, ux, uy and vorticity block-averaged k x k into a device ring at the force-output iterations (k_frame) ---- */
-static size_t frame_floats(const lbm_ctx* c) { return 4 * (size_t)(c->nx / c->frames_k) * (size_t)(c->nyl / c->frames_k); }
-
 int lbm_frames_begin(lbm_ctx* c, int k, int capacity) {
     if (!c || !c->initialised) return fail(LBM_ERR_ARG, "lbm_frames_begin needs an initialised context");
     if (k < 1 || k > lbmk::FRAME_MAX_K) return fail(LBM_ERR_ARG, "frame stride k = %d outside 1..%d", k, lbmk::FRAME_MAX_K);
@@ -517,21 +509,12 @@ int lbm_frames_begin(lbm_ctx* c, int k, int capacity) {
     if (c->nx % k) return fail(LBM_ERR_ARG, "frame stride k = %d does not divide nx = %d", k, c->nx);
     if (c->p.y_start % k) return fail(LBM_ERR_ARG, "frame stride k = %d does not divide the strip's y_start = %d", k, c->p.y_start);
     if (c->nyl % k) return fail(LBM_ERR_ARG, "frame stride k = %d does not divide the strip's local_ny = %d", k, c->nyl);
-    HIPCHK(hipSetDevice(c->device));
-    { int jr = join_comm(c); if (jr) return jr; }
-    HIPCHK(hipStreamSynchronize(c->stream));      // (a sample still in flight writes the ring this call replaces)
-    if (c->d_frames) { (void)hipFree(c->d_frames); c->d_frames = nullptr; }
-    c->frames_active = false;
-    c->frames_head = c->frames_count = 0;
-    c->frames_k = k; c->frames_cap = capacity;
-    const size_t bytes = frame_floats(c) * sizeof(float) * (size_t)capacity;
-    if (hipMalloc(&c->d_frames, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        c->d_frames = nullptr; c->frames_cap = 0;
-        return fail(LBM_ERR_ALLOC, "frames: no device memory for a ring of %d frames (%zu bytes)", capacity, bytes);
-    }
-    c->frames_t.assign((size_t)capacity, 0);
-    c->frames_active = true;
+    const size_t per = 4 * (size_t)(c->nx / k) * (size_t)(c->nyl / k);
+    const int rc = replace_ring(c, c->frames, per, capacity);
+    if (rc && rc != LBM_ERR_ALLOC) return rc;
+    c->frames_k = k;
+    c->frames_active = !rc;
+    if (rc) return fail(LBM_ERR_ALLOC, "frames: no device memory for a ring of %d frames (%zu bytes)", capacity, per * sizeof(float) * (size_t)capacity);
     return LBM_OK;
 }
 
@@ -541,23 +524,14 @@ int lbm_frames_end(lbm_ctx* c) {
     return LBM_OK;
 }
 
-int lbm_frames_pending(const lbm_ctx* c) { return c ? c->frames_count : LBM_ERR_ARG; }
+int lbm_frames_pending(const lbm_ctx* c) { return c ? c->frames.ix.count : LBM_ERR_ARG; }
 
 int lbm_drain_frames(lbm_ctx* c, int* timesteps, float* frames, int max_frames) {
     if (!c || max_frames < 0 || (max_frames > 0 && !frames)) return fail(LBM_ERR_ARG, "lbm_drain_frames: null argument or max_frames < 0");
-    if (!c->d_frames || c->frames_count < 1 || max_frames < 1) return 0;
+    if (c->frames.ix.count < 1 || max_frames < 1) return 0;
     HIPCHK(hipSetDevice(c->device));
     { int jr = join_comm(c); if (jr) return jr; }
-    const int n = std::min(max_frames, c->frames_count);
-    const size_t per = frame_floats(c);
-    const int n1 = std::min(n, c->frames_cap - c->frames_head);      // the ring: up to the end of the buffer, then from its start
-    HIPCHK(hipMemcpyAsync(frames, c->d_frames + per * (size_t)c->frames_head, per * sizeof(float) * (size_t)n1, hipMemcpyDeviceToHost, c->stream));
-    if (n > n1) HIPCHK(hipMemcpyAsync(frames + per * (size_t)n1, c->d_frames, per * sizeof(float) * (size_t)(n - n1), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (timesteps) for (int j = 0; j < n; ++j) timesteps[j] = c->frames_t[(size_t)((c->frames_head + j) % c->frames_cap)];
-    c->frames_head = (c->frames_head + n) % c->frames_cap;
-    c->frames_count -= n;
-    return n;
+    return c->frames.drain(c->stream, frames, timesteps, max_frames);
 }
 
 /* ---- point probes: (rho, ux, uy) interpolated bilinearly at chosen points into a device ring at the force-output iterations (k_probes) ---- */
@@ -579,26 +553,22 @@ int lbm_probes_begin(lbm_ctx* c, const double* xy, int n, int capacity) {
     if (!c || !c->initialised) return fail(LBM_ERR_ARG, "lbm_probes_begin needs an initialised context");
     { int cr = check_probes(xy, n, c->nx, c->p.ny); if (cr) return cr; }
     if (capacity < 1) return fail(LBM_ERR_ARG, "probe ring capacity %d < 1", capacity);
-    HIPCHK(hipSetDevice(c->device));
-    { int jr = join_comm(c); if (jr) return jr; }
-    HIPCHK(hipStreamSynchronize(c->stream));      // (a sample still in flight reads the table and writes the ring this call replaces)
-    if (c->d_probes) { (void)hipFree(c->d_probes); c->d_probes = nullptr; }
+    int rc = replace_ring(c, c->probes, 3 * (size_t)n, capacity);
+    if (rc && rc != LBM_ERR_ALLOC) return rc;
+    // (the sample that was in flight read the old table too)
     if (c->d_probe_table) { (void)hipFree(c->d_probe_table); c->d_probe_table = nullptr; }
     c->probes_active = false;
-    c->probes_head = c->probes_count = 0;
-    c->probe_n = 0; c->probes_cap = 0;
+    c->probe_n = 0;
     std::vector<lbmk::ProbeEntry> table((size_t)n);
     for (int j = 0; j < n; ++j) table[(size_t)j] = lbmk::probe_entry(xy[2 * j], xy[2 * j + 1], c->p.y_start, c->nyl);
-    const size_t tbytes = sizeof(lbmk::ProbeEntry) * (size_t)n, bytes = 3 * sizeof(double) * (size_t)n * (size_t)capacity;
-    if (hipMalloc(&c->d_probe_table, tbytes) != hipSuccess || hipMalloc(&c->d_probes, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        if (c->d_probe_table) { (void)hipFree(c->d_probe_table); c->d_probe_table = nullptr; }
-        c->d_probes = nullptr;
-        return fail(LBM_ERR_ALLOC, "probes: no device memory for a ring of %d samples of %d probes (%zu bytes)", capacity, n, bytes);
+    const size_t tbytes = sizeof(lbmk::ProbeEntry) * (size_t)n;
+    if (!rc && hipMalloc(&c->d_probe_table, tbytes) != hipSuccess) { (void)hipGetLastError(); c->d_probe_table = nullptr; rc = LBM_ERR_ALLOC; }
+    if (rc) {
+        c->probes.release();
+        return fail(LBM_ERR_ALLOC, "probes: no device memory for a ring of %d samples of %d probes (%zu bytes)", capacity, n, 3 * sizeof(double) * (size_t)n * (size_t)capacity);
     }
     HIPCHK(hipMemcpy(c->d_probe_table, table.data(), tbytes, hipMemcpyHostToDevice));
-    c->probe_n = n; c->probes_cap = capacity;
-    c->probes_t.assign((size_t)capacity, 0);
+    c->probe_n = n;
     c->probes_active = true;
     return LBM_OK;
 }
@@ -610,23 +580,14 @@ int lbm_probes_end(lbm_ctx* c) {
 }
 
 int lbm_probes_count(const lbm_ctx* c) { return c ? c->probe_n : LBM_ERR_ARG; }
-int lbm_probes_pending(const lbm_ctx* c) { return c ? c->probes_count : LBM_ERR_ARG; }
+int lbm_probes_pending(const lbm_ctx* c) { return c ? c->probes.ix.count : LBM_ERR_ARG; }
 
 int lbm_drain_probes(lbm_ctx* c, int* timesteps, double* vals, int max_samples) {
     if (!c || max_samples < 0 || (max_samples > 0 && !vals)) return fail(LBM_ERR_ARG, "lbm_drain_probes: null argument or max_samples < 0");
-    if (!c->d_probes || c->probes_count < 1 || max_samples < 1) return 0;
+    if (c->probes.ix.count < 1 || max_samples < 1) return 0;
     HIPCHK(hipSetDevice(c->device));
     { int jr = join_comm(c); if (jr) return jr; }
-    const int m = std::min(max_samples, c->probes_count);
-    const size_t per = 3 * (size_t)c->probe_n;
-    const int m1 = std::min(m, c->probes_cap - c->probes_head);      // the ring: up to the end of the buffer, then from its start
-    HIPCHK(hipMemcpyAsync(vals, c->d_probes + per * (size_t)c->probes_head, per * sizeof(double) * (size_t)m1, hipMemcpyDeviceToHost, c->stream));
-    if (m > m1) HIPCHK(hipMemcpyAsync(vals + per * (size_t)m1, c->d_probes, per * sizeof(double) * (size_t)(m - m1), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (timesteps) for (int j = 0; j < m; ++j) timesteps[j] = c->probes_t[(size_t)((c->probes_head + j) % c->probes_cap)];
-    c->probes_head = (c->probes_head + m) % c->probes_cap;
-    c->probes_count -= m;
-    return m;
+    return c->probes.drain(c->stream, vals, timesteps, max_samples);
 }
 
 /* TEST HOOK (no device needed): the probe table lbm_probes_begin uploads for the strip [y_start, y_start + local_ny): see include/lbm_hip.h. */
@@ -691,11 +652,11 @@ int lbm_set_solid_mask(lbm_ctx* c, const unsigned char* mask, int nx, int ny) {
     HIPCHK(hipSetDevice(c->device));
     {   // a mask replaces the geometry wholesale: the labels of an earlier lbm_set_body_labels go with it
         void** q[] = {(void**)&c->d_labels, (void**)&c->d_body_box, (void**)&c->d_body_chunks, (void**)&c->d_body_first, (void**)&c->d_body_part,
-                      (void**)&c->d_body_now, (void**)&c->d_body_log};
+                      (void**)&c->d_body_now};
         for (void** d : q)
             if (*d) { HIPCHK(hipFree(*d)); *d = nullptr; }
         c->body_n = c->body_chunks = 0;
-        c->body_log_head = c->body_log_count = 0;
+        c->body_log.release();
     }
     if (c->mview.bits) { HIPCHK(hipFree((void*)c->mview.bits)); c->mview.bits = nullptr; }
     if (c->mview.sat) { HIPCHK(hipFree((void*)c->mview.sat)); c->mview.sat = nullptr; }
@@ -734,7 +695,7 @@ int lbm_set_body_labels(lbm_ctx* c, const unsigned char* labels, int nx, int ny)
     HIPCHK(hipMalloc(&c->d_body_first, h.first.size() * sizeof(int)));
     HIPCHK(hipMalloc(&c->d_body_part, std::max<size_t>(1, nch) * 2 * sizeof(double)));
     HIPCHK(hipMalloc(&c->d_body_now, 3 * sizeof(double) * (size_t)h.B));
-    HIPCHK(hipMalloc(&c->d_body_log, 3 * sizeof(double) * (size_t)h.B * (size_t)c->log_cap));
+    HIPCHK(c->body_log.alloc(3 * (size_t)h.B, c->log_cap, false));
     HIPCHK(hipMemcpy(c->d_labels, h.lab.data(), h.lab.size(), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(c->d_body_box, h.box.data(), h.box.size() * sizeof(int), hipMemcpyHostToDevice));
     if (nch) HIPCHK(hipMemcpy(c->d_body_chunks, h.chunks.data(), nch * sizeof(BodyChunk), hipMemcpyHostToDevice));
@@ -1046,7 +1007,7 @@ int lbm_load_state(lbm_ctx* c, const char* path) {
     fclose(fp);
     if (rc) return rc;
     c->log_count = 0;
-    c->body_log_head = c->body_log_count = 0;
+    c->body_log.ix.reset();
     c->last_was_pair = false;
     c->mid_pair = false;
     if ((c->comm || c->loopback) && c->group_n <= 1)   // (a group: lbm_group_refresh_halos once every member is restored)
@@ -1263,6 +1224,24 @@ int lbm_debug_face_runs(int hr, int trim, int south_block, int* runs10) {
     return r.n;
 }
 
+/* TEST HOOK (no device needed): one RingIndex (csrc/lbm_plan.hpp) driven through pushes (ops[k] < 0) and takes of up to ops[k]: see include/lbm_hip.h. */
+int lbm_debug_ring(int capacity, const int* ops, int nops, int* out3) {
+    if (capacity < 1 || nops < 0 || (nops > 0 && (!ops || !out3))) return fail(LBM_ERR_ARG, "bad argument");
+    RingIndex r{capacity, 0, 0};
+    for (int k = 0; k < nops; ++k) {
+        int* o = out3 + 3 * k;
+        if (ops[k] < 0) {
+            o[0] = r.full() ? -1 : r.next(); o[1] = o[2] = -1;
+            if (!r.full()) r.commit();
+        } else {
+            const RingIndex::Span s = r.oldest(ops[k]);
+            o[0] = s.start; o[1] = s.n1; o[2] = s.n2;
+            r.drop(s.n1 + s.n2);
+        }
+    }
+    return r.count;
+}
+
 /* TEST HOOK (no device needed): the host threads of a group (GroupPool, csrc/lbm_ctx.hpp) on a dummy job of `rounds` rounds with one
  * rendezvous each. Strip `fail_strip` reports an injected error in round `fail_round`; strip `stall_strip` sleeps `stall_ms` before
  * the rendezvous of round `stall_round` (-1: nobody). The job runs `repeat` times on the same pool. Returns what the LAST run returned
@@ -1323,7 +1302,7 @@ int lbm_debug_choreography(int nx, int ny, const int* bounds2, int nstrips, int 
         c->initialised = true;
         c->cur = 1;
         if (c->stats_opt >= 0) { c->stats_active = true; c->stats_from = c->stats_opt; }      // (no accumulators: nothing is launched)
-        if (c->bodies_opt) c->body_n = 1;                                                     // (no labels either)
+        if (c->bodies_opt) { c->body_n = 1; c->body_log.ix.cap = c->log_cap; }                // (no labels and no log either)
         if (c->frames_opt > 0) { c->frames_active = true; c->frames_k = c->frames_opt; }      // (no ring: nothing is launched)
         if (c->probes_opt) { c->probes_active = true; c->probe_n = 1; }                       // (no table and no ring either)
     }

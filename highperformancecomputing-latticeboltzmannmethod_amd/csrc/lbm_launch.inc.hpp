@@ -152,16 +152,20 @@ MacroArgs<T> make_macro_args(const lbm_ctx* c, const void* src) {
     return m;
 }
 
+// Dry run: the record of a sample of iteration t, with the rows ChoreoOp::samples says its kind reads.
+inline int record_sample(lbm_ctx* c, int kind, int t) {
+    ChoreoOp o;
+    o.kind = kind; o.strip = o.r_strip = c->group_k; o.stream = 0; o.buf = c->cur; o.t = t;
+    o.r0 = o.sample().lo; o.r1 = c->nyl + o.sample().hi;
+    c->rec->ops.push_back(o);
+    return LBM_OK;
+}
+
 // One sample of the running statistics (k_stats) at a force-output iteration t: buf[cur] = P_t. The snapshot it adds is the one
 // do_macros takes from buf[cur ^ 1] once steps_done == t + 1. Queued on the compute stream behind join_comm, like the force kernel.
 template <typename T>
 int launch_stats(lbm_ctx* c, int t) {
-    if (c->rec) {      // dry run: reads the strip's rows of P_t and, on the inlet / outlet columns, one ghost row per face; writes the accumulators
-        ChoreoOp o; o.kind = ChoreoOp::STATS; o.strip = c->group_k; o.stream = 0; o.buf = c->cur; o.t = t; o.r0 = -1; o.r1 = c->nyl + 1; o.r_strip = c->group_k;
-        c->rec->ops.push_back(o);
-        c->stats_n++;
-        return LBM_OK;
-    }
+    if (c->rec) { c->stats_n++; return record_sample(c, ChoreoOp::STATS, t); }
     StatsArgs<T> s;
     s.m = make_macro_args<T>(c, c->buf[c->cur]);
     s.acc = c->d_stats; s.cells = (long)c->nx * c->nyl;
@@ -174,11 +178,7 @@ int launch_stats(lbm_ctx* c, int t) {
 
 template <typename T>
 int launch_forces(lbm_ctx* c, double* out, int t) {
-    if (c->rec) {      // dry run: the force kernel reads this strip's rows of P_t on the compute stream
-        ChoreoOp o; o.kind = ChoreoOp::FORCES; o.strip = c->group_k; o.stream = 0; o.buf = c->cur; o.t = t; o.r0 = 0; o.r1 = c->nyl; o.r_strip = c->group_k;
-        c->rec->ops.push_back(o);
-        return LBM_OK;
-    }
+    if (c->rec) return record_sample(c, ChoreoOp::FORCES, t);
     ForceArgs<T> f;
     f.cur = static_cast<const T*>(c->buf[c->cur]);
     f.plane = (long)c->plane; f.pitch = c->pitch; f.xoff = c->xoff;
@@ -214,11 +214,7 @@ int launch_forces(lbm_ctx* c, double* out, int t) {
 // behind covers it. One launch of one block per chunk of the table and one ordered sum, whatever the plan.
 template <typename T>
 int launch_body_forces(lbm_ctx* c, double* out, int t) {
-    if (c->rec) {      // dry run: reads this strip's rows of P_t, like the force kernel (the labels carry the ghost rows' geometry)
-        ChoreoOp o; o.kind = ChoreoOp::BODIES; o.strip = c->group_k; o.stream = 0; o.buf = c->cur; o.t = t; o.r0 = 0; o.r1 = c->nyl; o.r_strip = c->group_k;
-        c->rec->ops.push_back(o);
-        return LBM_OK;
-    }
+    if (c->rec) return record_sample(c, ChoreoOp::BODIES, t);
     BodyForceArgs<T> a;
     a.cur = static_cast<const T*>(c->buf[c->cur]);
     a.plane = (long)c->plane; a.pitch = c->pitch; a.xoff = c->xoff; a.nx = c->nx;
@@ -230,58 +226,69 @@ int launch_body_forces(lbm_ctx* c, double* out, int t) {
     return LBM_OK;
 }
 
-// ... appended to the ring of the body-force log (do_steps: at exactly the iterations that append a force-log row, after it has checked
-// that both logs have room)
-template <typename T>
-int log_body_forces(lbm_ctx* c, int t) {
-    const long slot = (c->body_log_head + c->body_log_count) % c->log_cap;
-    const int rc = launch_body_forces<T>(c, c->d_body_log + 3L * c->body_n * slot, t);
-    if (!rc) c->body_log_count++;
-    return rc;
-}
-
-
 // One frame (k_frame, lbm_frames_begin) of a force-output iteration t into the next free slot of the ring: buf[cur] = P_t, the snapshot
-// that of launch_stats. Queued directly behind the force kernel on the compute stream, behind the same join. do_steps has checked
-// that the ring has room.
+// that of launch_stats. Queued directly behind the force kernel on the compute stream, behind the same join. sample_outputs has
+// checked that the ring has room.
 template <typename T>
 int launch_frame_sample(lbm_ctx* c, int t) {
-    if (c->rec) {      // dry run: the strip's rows of P_t and two ghost rows per face (d/dy at the face; its outlet cell pulls one row further); writes its own slot
-        ChoreoOp o; o.kind = ChoreoOp::FRAME; o.strip = c->group_k; o.stream = 0; o.buf = c->cur; o.t = t; o.r0 = -2; o.r1 = c->nyl + 2; o.r_strip = c->group_k;
-        c->rec->ops.push_back(o);
-        return LBM_OK;
-    }
-    const int slot = (c->frames_head + c->frames_count) % c->frames_cap;
+    if (c->rec) return record_sample(c, ChoreoOp::FRAME, t);
     FrameArgs<T> f;
     f.m = make_macro_args<T>(c, c->buf[c->cur]);
     f.k = c->frames_k; f.cnx = c->nx / c->frames_k; f.cny = c->nyl / c->frames_k;
-    f.out = c->d_frames + 4 * (size_t)f.cnx * f.cny * slot;
+    f.out = c->frames.next_slot();
     launch_frame<T>(f, c->stream);
     HIPCHK(hipGetLastError());
-    c->frames_t[(size_t)slot] = t;
-    c->frames_count++;
+    c->frames.commit(t);
     return LBM_OK;
 }
 
 // One sample of the point probes (k_probes, lbm_probes_begin) of a force-output iteration t into the next free slot of the ring:
 // buf[cur] = P_t, the snapshot that of launch_stats. Queued directly behind the force kernel (and the body, statistics and frame samples)
-// on the compute stream, behind the same join. do_steps has checked that the ring has room.
+// on the compute stream, behind the same join. sample_outputs has checked that the ring has room.
 template <typename T>
 int launch_probe_sample(lbm_ctx* c, int t) {
-    if (c->rec) {      // dry run: the strip's rows of P_t, the ghost row below (the pull of an inlet / outlet cell of row 0) and two above (y1 of a probe on the last row; its pull); writes its own slot
-        ChoreoOp o; o.kind = ChoreoOp::PROBES; o.strip = c->group_k; o.stream = 0; o.buf = c->cur; o.t = t; o.r0 = -1; o.r1 = c->nyl + 2; o.r_strip = c->group_k;
-        c->rec->ops.push_back(o);
-        return LBM_OK;
-    }
-    const int slot = (c->probes_head + c->probes_count) % c->probes_cap;
+    if (c->rec) return record_sample(c, ChoreoOp::PROBES, t);
     ProbeArgs<T> a;
     a.m = make_macro_args<T>(c, c->buf[c->cur]);
     a.table = static_cast<const ProbeEntry*>(c->d_probe_table);
     a.n = c->probe_n;
-    a.out = c->d_probes + 3 * (size_t)c->probe_n * (size_t)slot;
+    a.out = c->probes.next_slot();
     launch_probes<T>(a, c->stream);
     HIPCHK(hipGetLastError());
-    c->probes_t[(size_t)slot] = t;
-    c->probes_count++;
+    c->probes.commit(t);
+    return LBM_OK;
+}
+
+// The output point of a force-output iteration t (buf[cur] = P_t), the one place a sampler plugs into do_steps: every capacity check
+// before anything is queued (a dry run has no frame or probe ring: nothing is launched), the join — the edge bands of the previous
+// launch live on the side stream —, the force kernel and its log row, then the per-body rows, the statistics, the frame and the probes
+// of iteration t, each directly behind it on the compute stream with no synchronisation. A counter advances once its launch is queued.
+inline int join_comm(lbm_ctx* c);
+template <typename T>
+int sample_outputs(lbm_ctx* c, int t) {
+    if (c->log_count >= c->log_cap) return fail(LBM_ERR_ARG, "force log full (%d rows): drain it", c->log_cap);
+    if (c->body_n > 0 && c->body_log.ix.full()) return fail(LBM_ERR_ARG, "body force log full (%d samples): drain it", c->body_log.ix.cap);
+    if (c->frames_active && !c->rec && c->frames.ix.full()) return fail(LBM_ERR_ARG, "frame ring full (%d frames): drain it (lbm_drain_frames)", c->frames.ix.cap);
+    if (c->probes_active && !c->rec && c->probes.ix.full()) return fail(LBM_ERR_ARG, "probe ring full (%d samples): drain it (lbm_drain_probes)", c->probes.ix.cap);
+    int rc = join_comm(c);
+    if (!rc) rc = launch_forces<T>(c, c->d_force_log + 3L * c->log_count, t);
+    if (!rc) c->log_count++;
+    if (!rc && c->body_n > 0) rc = launch_body_forces<T>(c, c->body_log.next_slot(), t);      // (a sample of the log at exactly the iterations of a force-log row)
+    if (!rc && c->body_n > 0) c->body_log.commit(t);
+    if (!rc && c->stats_active && t >= c->stats_from) rc = launch_stats<T>(c, t);
+    if (!rc && c->frames_active) rc = launch_frame_sample<T>(c, t);
+    if (!rc && c->probes_active) rc = launch_probe_sample<T>(c, t);
+    return rc;
+}
+
+// What lbm_frames_begin and lbm_probes_begin share once the arguments are accepted: everything queued is waited for (a sample still in
+// flight writes the ring this call replaces), the old ring goes and one of `capacity` slots of `per` elements takes its place.
+// LBM_ERR_ALLOC: no device memory, and no ring (the caller says which); any other error: nothing was touched.
+template <typename E>
+int replace_ring(lbm_ctx* c, DeviceRing<E>& ring, size_t per, int capacity) {
+    HIPCHK(hipSetDevice(c->device));
+    { int jr = join_comm(c); if (jr) return jr; }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (ring.alloc(per, capacity, true) != hipSuccess) { (void)hipGetLastError(); return LBM_ERR_ALLOC; }
     return LBM_OK;
 }

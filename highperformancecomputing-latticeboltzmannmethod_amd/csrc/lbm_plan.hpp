@@ -153,4 +153,23 @@ inline std::string plan_option_string(int layout, int nt, int alternate, int pai
     return s;
 }
 
+// The index arithmetic of a ring of `cap` slots that is filled at the output iterations of lbm_step and drained oldest first (the
+// body-force log, the frame ring, the probe ring: DeviceRing, lbm_ctx.hpp). The only place that wraps an index; exported through
+// lbm_debug_ring (tests/test_ring_cpu.py holds it against a deque).
+struct RingIndex {
+    int cap = 0, head = 0, count = 0;
+    void reset() { head = count = 0; }                     // forget what is pending
+    bool full() const { return count >= cap; }
+    int next() const { return (head + count) % cap; }      // the slot of the next sample (not full, so cap > 0)
+    void commit() { ++count; }                             // ... once it has been queued
+    // up to `m` of the oldest samples: slots [start, start + n1), then [0, n2)
+    struct Span { int start, n1, n2; };
+    Span oldest(int m) const {
+        const int n = m < 0 ? 0 : m < count ? m : count;
+        const int n1 = n < cap - head ? n : cap - head;
+        return {head, n1, n - n1};
+    }
+    void drop(int n) { if (n > 0) { head = (head + n) % cap; count -= n; } }      // (n <= count, as `oldest` counted them)
+};
+
 }  // namespace lbmk

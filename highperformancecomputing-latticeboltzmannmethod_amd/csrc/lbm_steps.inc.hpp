@@ -156,19 +156,7 @@ int do_steps(lbm_ctx** cs, int n, int nsteps, int of) {
             for (int k = 0; k < nsteps; ++launch) {
                 const int t = c->steps_done;
                 int rc = LBM_OK;
-                if (of > 0 && t % of == 0) {
-                    if (c->log_count >= c->log_cap) rc = fail(LBM_ERR_ARG, "force log full (%d rows): drain it", c->log_cap);
-                    if (!rc && c->body_n > 0 && c->body_log_count >= c->log_cap) rc = fail(LBM_ERR_ARG, "body force log full (%d samples): drain it", c->log_cap);
-                    if (!rc && c->frames_active && !c->rec && c->frames_count >= c->frames_cap) rc = fail(LBM_ERR_ARG, "frame ring full (%d frames): drain it (lbm_drain_frames)", c->frames_cap);
-                    if (!rc && c->probes_active && !c->rec && c->probes_count >= c->probes_cap) rc = fail(LBM_ERR_ARG, "probe ring full (%d samples): drain it (lbm_drain_probes)", c->probes_cap);
-                    if (!rc) rc = join_comm(c);
-                    if (!rc) rc = launch_forces<T>(c, c->d_force_log + 3L * c->log_count, t);
-                    if (!rc) c->log_count++;
-                    if (!rc && c->body_n > 0) rc = log_body_forces<T>(c, t);
-                    if (!rc && c->stats_active && t >= c->stats_from) rc = launch_stats<T>(c, t);
-                    if (!rc && c->frames_active) rc = launch_frame_sample<T>(c, t);
-                    if (!rc && c->probes_active) rc = launch_probe_sample<T>(c, t);
-                }
+                if (of > 0 && t % of == 0) rc = sample_outputs<T>(c, t);
                 if (!rc) rc = plan_launch(c, nsteps - k, of, transport, true, &L[(size_t)i]);
                 if (!rc) rc = issue_before<T>(c, L[(size_t)i]);
                 if (!rc) rc = fault(launch, 0);
@@ -206,34 +194,9 @@ int do_steps(lbm_ctx** cs, int n, int nsteps, int of) {
         for (int i = 0; i < n; ++i) {
             lbm_ctx* c = cs[i];
             SETDEV(c);
-            if (of > 0 && t % of == 0) {
-                if (c->log_count >= c->log_cap) return fail(LBM_ERR_ARG, "force log full (%d rows): drain it", c->log_cap);
-                if (c->body_n > 0 && c->body_log_count >= c->log_cap) return fail(LBM_ERR_ARG, "body force log full (%d samples): drain it", c->log_cap);     // (before the force row is logged)
-                if (c->frames_active && !c->rec && c->frames_count >= c->frames_cap) return fail(LBM_ERR_ARG, "frame ring full (%d frames): drain it (lbm_drain_frames)", c->frames_cap);
-                if (c->probes_active && !c->rec && c->probes_count >= c->probes_cap) return fail(LBM_ERR_ARG, "probe ring full (%d samples): drain it (lbm_drain_probes)", c->probes_cap);
-                int rc = join_comm(c);      // the edge bands of the previous launch live on the side stream
-                if (rc) return rc;
-                rc = launch_forces<T>(c, c->d_force_log + 3L * c->log_count, t);
-                if (rc) return rc;
-                c->log_count++;
-                if (c->body_n > 0) {      // the per-body rows of iteration t: directly behind the force kernel, no synchronisation
-                    rc = log_body_forces<T>(c, t);
-                    if (rc) return rc;
-                }
-                if (c->stats_active && t >= c->stats_from) {      // the sample of iteration t: behind the same join, on the same stream
-                    rc = launch_stats<T>(c, t);
-                    if (rc) return rc;
-                }
-                if (c->frames_active) {     // the frame of iteration t: likewise, into a ring slot of its own
-                    rc = launch_frame_sample<T>(c, t);
-                    if (rc) return rc;
-                }
-                if (c->probes_active) {     // the probes' sample of iteration t: likewise
-                    rc = launch_probe_sample<T>(c, t);
-                    if (rc) return rc;
-                }
-            }
-            int rc = plan_launch(c, nsteps - k, of, transport, true, &L[i]);
+            int rc = LBM_OK;
+            if (of > 0 && t % of == 0) rc = sample_outputs<T>(c, t);
+            if (!rc) rc = plan_launch(c, nsteps - k, of, transport, true, &L[i]);
             if (rc) return rc;
             if (L[i].depth != L[0].depth || L[i].kind != L[0].kind)
                 return fail(LBM_ERR_ARG, "the strips of a group disagree on the next launch (different options?)");

@@ -426,6 +426,12 @@ int lbm_debug_strip_pins(const int* per_rank7, int nranks, int* agreed7);
  * sub-rows per lattice row); south_block != 0: the block lies below the strip it borders (a sender's top rows / a receiver's south ghost
  * rows). Returns the number of runs. Replaces the nine-values-per-edge-cell buffers of pack_data_for_sending, LBMGrid.h:395-440. */
 int lbm_debug_face_runs(int hr, int trim, int south_block, int* runs10);
+/* Test hook, callable without a device: the index arithmetic of the device rings that the output iterations fill and the drains empty
+ * (body-force log, frames, probes: csrc/lbm_plan.hpp RingIndex), on one ring of `capacity` slots driven through `nops` operations.
+ * ops[k] < 0 pushes a sample, ops[k] = m >= 0 takes up to m of the oldest. out3[3k..3k+2]: a push: {its slot, -1, -1}, or {-1, -1, -1}
+ * on a full ring (nothing changes); a take: {start, n1, n2}: slots [start, start + n1), then [0, n2). Returns the samples pending at
+ * the end; LBM_ERR_ARG: capacity < 1 or a null pointer. Replaces nothing in the reference. */
+int lbm_debug_ring(int capacity, const int* ops, int nops, int* out3);
 /* Test hook, callable without a device: the candidate plans lbm_initialise would time on a whole-domain context of this grid
  * (csrc/lbm_plan.hpp), one per line: "name|lbm_set_option pairs|dominant kernel|iterations per launch". */
 int lbm_debug_plan_candidates(int nx, int ny, int precision, int arith, int num_cus, char* out, int cap);
