@@ -42,28 +42,35 @@ def embedded_id(path=LIB):
     return m.group(1).decode() if m else None
 
 
+# the Arith bases of the collision models (csrc/lbm_plan.hpp collision_models): BGK, Smagorinsky (LES), two relaxation times (TRT)
+COLLISION_BASES = (0, 2, 4)
+
+
+def units(build_id):
+    """Every object of the library as (source, extra flags, object name). Per collision model: the site and tile families
+    (lbm_step_k.hip) and the column kernel's instantiations of each element type, which take as long as all other kernels together."""
+    out = [("lbm_hip.hip", ["-DLBM_BUILD_ID_STR=\"" + build_id + "\""], "lbm_hip.o")]
+    for base in COLLISION_BASES:
+        ar = "-DLBM_AR_BASE=%d" % base
+        out += [("lbm_col.hip", ["-DLBM_COL_T=double", ar], "lbm_col_ar%d_f64.o" % base),
+                ("lbm_col.hip", ["-DLBM_COL_T=float", ar], "lbm_col_ar%d_f32.o" % base),
+                ("lbm_step_k.hip", [ar], "lbm_step_k_ar%d.o" % base)]
+    # the tall fp32 regions (BGK only), the frame kernel (lbm_frames_begin), the probe kernel (lbm_probes_begin)
+    out += [("lbm_col.hip", ["-DLBM_COL_TALL=1"], "lbm_col_tall_c.o"), ("lbm_col.hip", ["-DLBM_COL_TALL=0"], "lbm_col_tall_s.o"),
+            ("lbm_frames.hip", [], "lbm_frames.o"), ("lbm_probes.hip", [], "lbm_probes.o")]
+    return out
+
+
 def build_all(force=False, verbose=False):
     hipcc = shutil.which("hipcc") or os.path.join(ROCM, "bin", "hipcc")
     want = source_id()
     if force or embedded_id() != want:
         # -ffp-contract=off: no fused multiply-add is formed behind the source's back, so every formulation of the
         # step kernel (site / vector / fused, any layout) and the strict-IEEE oracle evaluate the same operation sequence.
-        # Thirteen objects compiled side by side (the column kernel's instantiations of one element type take as long as all
-        # the other kernels together), then linked. Three hold the Smagorinsky (LES) instantiations only, three the
-        # two-relaxation-time (TRT) ones, one the frame kernel (lbm_frames_begin), the last one the probe kernel
-        # (lbm_probes_begin).
-        units = [("lbm_hip.hip", ["-DLBM_BUILD_ID_STR=\"" + want + "\""], "lbm_hip.o"),
-                 ("lbm_col.hip", ["-DLBM_COL_T=double"], "lbm_col_f64.o"), ("lbm_col.hip", ["-DLBM_COL_T=float"], "lbm_col_f32.o"),
-                 ("lbm_col.hip", ["-DLBM_COL_TALL=1"], "lbm_col_tall_c.o"), ("lbm_col.hip", ["-DLBM_COL_TALL=0"], "lbm_col_tall_s.o"),
-                 ("lbm_col.hip", ["-DLBM_COL_T=double", "-DLBM_COL_LES=1"], "lbm_col_les_f64.o"),
-                 ("lbm_col.hip", ["-DLBM_COL_T=float", "-DLBM_COL_LES=1"], "lbm_col_les_f32.o"),
-                 ("lbm_les.hip", [], "lbm_les.o"),
-                 ("lbm_col.hip", ["-DLBM_COL_T=double", "-DLBM_COL_TRT=1"], "lbm_col_trt_f64.o"),
-                 ("lbm_col.hip", ["-DLBM_COL_T=float", "-DLBM_COL_TRT=1"], "lbm_col_trt_f32.o"),
-                 ("lbm_trt.hip", [], "lbm_trt.o"), ("lbm_frames.hip", [], "lbm_frames.o"), ("lbm_probes.hip", [], "lbm_probes.o")]
+        # every object compiled side by side, then linked
         common = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++20", "-ffp-contract=off", "-fPIC", "-pthread", "-c"]
         procs, objs = [], []
-        for src, extra, oname in units:
+        for src, extra, oname in units(want):
             obj = os.path.join(CSRC, oname)
             cmd = common + extra + ["-o", obj, os.path.join(CSRC, src)]
             if verbose:
@@ -84,3 +91,12 @@ def build_all(force=False, verbose=False):
         os.replace(tmp, LIB)
         assert embedded_id() == want, "the built library does not carry the expected build id"
     return LIB
+
+
+if __name__ == "__main__":      # build.py --print-units: one "source<TAB>object<TAB>flags" line per object (tools/sanitize_host.sh)
+    import sys
+    if sys.argv[1:] == ["--print-units"]:
+        for src, extra, oname in units("unit-list-------"):
+            print("\t".join((src, oname, " ".join(extra))))
+    else:
+        sys.exit("usage: build.py --print-units")

@@ -1,8 +1,7 @@
-// csrc/lbm_col.hip — the translation unit(s) of k_stepc_col (lbm_kernel_col.hpp): its 26 instantiations (five / six iterations x
-// store policy + seven iterations, x arithmetic x element type: ten per element type and object file, plus the tall fp32 ones, three per
-// arithmetic mode and object file) and the launchers lbm_hip.hip calls (lbm_col_api.hpp). Four objects from this one source (build.py),
-// and two more each with -DLBM_COL_LES=1 / -DLBM_COL_TRT=1: the ten Smagorinsky / two-relaxation-time instantiations per element type
-// (no tall ones).
+// csrc/lbm_col.hip — the translation unit(s) of k_stepc_col (lbm_kernel_col.hpp) and the launchers lbm_hip.hip calls (lbm_col_api.hpp).
+// -DLBM_COL_T=<element type> -DLBM_AR_BASE=<a collision model's Arith base>: the ten instantiations of that type and model on 64 x 32
+// regions (five / six iterations x store policy + seven iterations, x arithmetic); -DLBM_COL_TALL=1 / 0: the three tall fp32 ones of
+// one arithmetic mode, BGK only. One object each (build.py).
 #include "lbm_kernel_col.hpp"
 #include "lbm_col_api.hpp"
 
@@ -14,20 +13,10 @@ namespace lbmk {
         const dim3 gridc((unsigned)((nb_ + 7) / 8 * 8)), blockc(NW_ * 64); \
         hipLaunchKernelGGL((k_stepc_col<T_, R_, NW_, D_, NT_, AR_>), gridc, blockc, 0, s, a, e); } while (0)
 
-#if defined(LBM_COL_T)       // the 64 x 32 (fp64 strict: 64 x 24 on twelve waves) regions of one element type
-// -DLBM_COL_LES=1: the same launcher and regions with the Smagorinsky arithmetic values (launch_col_les, two more objects)
-#if defined(LBM_COL_LES) && LBM_COL_LES
-#define LBM_COL_FN launch_col_les
-constexpr int ARS = AR_STRICT_LES, ARC = AR_CONTRACTED_LES;
-#elif defined(LBM_COL_TRT) && LBM_COL_TRT   // -DLBM_COL_TRT=1: likewise with the TRT arithmetic values (launch_col_trt)
-#define LBM_COL_FN launch_col_trt
-constexpr int ARS = AR_STRICT_TRT, ARC = AR_CONTRACTED_TRT;
-#else
-#define LBM_COL_FN launch_col
-constexpr int ARS = AR_STRICT, ARC = AR_CONTRACTED;
-#endif
-template <typename T>
-void LBM_COL_FN(const KArgs<T>& a, const K2Extra<T>& e, int depth, bool nt, bool contracted, hipStream_t s) {
+#if defined(LBM_COL_T) && defined(LBM_AR_BASE)   // the 64 x 32 (fp64 strict: 64 x 24 on twelve waves) regions of one element type and model
+template <typename T, int ARB>
+void launch_col(const KArgs<T>& a, const K2Extra<T>& e, int depth, bool nt, bool contracted, hipStream_t s) {
+    constexpr int ARS = ARB, ARC = ARB | 1;
 #define LBM_KD(D_) do { \
         if (contracted) { if (nt) LBM_KC(T, D_, RC, WC, true, ARC); else LBM_KC(T, D_, RC, WC, false, ARC); } \
         else { if (nt) LBM_KC(T, D_, RS, WS, true, ARS); else LBM_KC(T, D_, RS, WS, false, ARS); } } while (0)
@@ -39,8 +28,7 @@ void LBM_COL_FN(const KArgs<T>& a, const K2Extra<T>& e, int depth, bool nt, bool
     else LBM_KD(6);
 #undef LBM_KD
 }
-template void LBM_COL_FN<LBM_COL_T>(const KArgs<LBM_COL_T>&, const K2Extra<LBM_COL_T>&, int, bool, bool, hipStream_t);
-#undef LBM_COL_FN
+template void launch_col<LBM_COL_T, LBM_AR_BASE>(const KArgs<LBM_COL_T>&, const K2Extra<LBM_COL_T>&, int, bool, bool, hipStream_t);
 #elif defined(LBM_COL_TALL)  // the tall fp32 regions (64 x 48) of one arithmetic mode: contracted 12 waves x 4 rows (1), strict 8 x 6 (0)
 #if LBM_COL_TALL
 void launch_col_tall_contracted(const KArgs<float>& a, const K2Extra<float>& e, int depth, hipStream_t s) {
@@ -52,7 +40,7 @@ void launch_col_tall_strict(const KArgs<float>& a, const K2Extra<float>& e, int 
     if (depth == 6) LBM_KC(float, 6, R, W, false, AR); else if (depth == 8) LBM_KC(float, 8, R, W, false, AR); else LBM_KC(float, 7, R, W, false, AR);
 }
 #else
-#error "compile with -DLBM_COL_T=double, -DLBM_COL_T=float (either alone, with -DLBM_COL_LES=1 or with -DLBM_COL_TRT=1), -DLBM_COL_TALL=1 or -DLBM_COL_TALL=0"
+#error "compile with -DLBM_COL_T=double or float and -DLBM_AR_BASE=0, 2 or 4 (a collision model's Arith base), or with -DLBM_COL_TALL=1 or 0"
 #endif
 #undef LBM_KC
 

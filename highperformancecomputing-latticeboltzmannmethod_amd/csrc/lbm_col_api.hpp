@@ -1,5 +1,5 @@
 // csrc/lbm_col_api.hpp — what the host translation unit (lbm_hip.hip) sees of the register-resident column kernel: its region
-// shape and one launcher per element type. The kernel itself (lbm_kernel_col.hpp) is compiled in its own translation unit
+// shape and its launchers. The kernel itself (lbm_kernel_col.hpp) is compiled in its own translation unit
 // (lbm_col.hip) so that the two halves of the device code build side by side (build.py).
 #pragma once
 #include "lbm_kernels.hpp"
@@ -32,17 +32,13 @@ constexpr int col_tile_h(int depth, int esize, bool strict, bool tall) {
 }
 
 // k_stepc_col<T, rows per thread, waves, depth, nt, arith> over the rows a.y_lo.. / a.y_lo2.. of the launch: depth 5, 6 or 7 on
-// 64 x 32 regions (one object file per element type: lbm_col.hip -DLBM_COL_T=double / float)
-template <typename T>
+// 64 x 32 regions, with the Arith values ARB (strict) / ARB | 1 (contracted) of one collision model (collision_models, lbm_plan.hpp).
+// Declared only: lbm_col.hip defines it and instantiates it explicitly, one object file per element type and model
+// (-DLBM_COL_T=double / float -DLBM_AR_BASE=<base>), so no other translation unit can instantiate the kernel.
+template <typename T, int ARB>
 void launch_col(const KArgs<T>& a, const K2Extra<T>& e, int depth, bool nt, bool contracted, hipStream_t s);
-// ... the same with the Smagorinsky arithmetic (AR_STRICT_LES / AR_CONTRACTED_LES; lbm_col.hip -DLBM_COL_T=... -DLBM_COL_LES=1)
-template <typename T>
-void launch_col_les(const KArgs<T>& a, const K2Extra<T>& e, int depth, bool nt, bool contracted, hipStream_t s);
-// ... and with the two-relaxation-time arithmetic (AR_STRICT_TRT / AR_CONTRACTED_TRT; lbm_col.hip -DLBM_COL_T=... -DLBM_COL_TRT=1)
-template <typename T>
-void launch_col_trt(const KArgs<T>& a, const K2Extra<T>& e, int depth, bool nt, bool contracted, hipStream_t s);
 // ... and on the tall fp32 regions, depth 6, 7 or 8, plain stores only (non-temporal ones cost 14 % there); one object file per
-// arithmetic mode (lbm_col.hip -DLBM_COL_TALL=1 contracted / 0 strict: eight unrolled rows x up to eight levels compile slowly)
+// arithmetic mode, BGK only (lbm_col.hip -DLBM_COL_TALL=1 contracted / 0 strict: eight unrolled rows x up to eight levels compile slowly)
 void launch_col_tall_contracted(const KArgs<float>& a, const K2Extra<float>& e, int depth, hipStream_t s);
 void launch_col_tall_strict(const KArgs<float>& a, const K2Extra<float>& e, int depth, hipStream_t s);
 

@@ -341,10 +341,9 @@ struct lbm_ctx {
     int deep = 0;        // 1..3: k_stepd_tile shape (6/7/8 iterations per launch on an LDS-filling tile); 6/7: k_stepc_col (registers)
     int arith = 0;       // collision arithmetic: 0 strict IEEE op-by-op (bit-identical to the oracle), 1 contracted (FMA +
                          // one reciprocal, as the reference's -ffast-math -mfma build permits); see lbm_kernels.hpp Arith
-    bool les = false;    // Smagorinsky LES collision (lbm_set_smagorinsky, constant les_cs > 0): the LES instantiations of every step family
-    double les_cs = 0.0;
-    bool trt = false;    // two-relaxation-time collision (lbm_set_trt, magic parameter trt_magic > 0): the TRT instantiations; never with les
-    double trt_magic = 0.0;
+    int collision = 0;   // the collision model, the `base` of its row in collision_models (lbm_plan.hpp): 0 BGK, AR_STRICT_LES (lbm_set_smagorinsky),
+                         // AR_STRICT_TRT (lbm_set_trt); collision | arith is the Arith value of every step kernel the context launches
+    double collision_param = 0.0;   // ... and the model's parameter: Cs > 0, the magic parameter > 0; BGK: 0
     int num_cus = 256;   // compute units of the device (what counts as a small grid: one round of blocks)
     int loopback = 0;    // TEST ONLY: the strip is its own north and south neighbour (exercises the overlap choreography):
                          // 1 = device copies, 2 = RCCL send/recv to self on a one-rank communicator

@@ -79,24 +79,32 @@ int upload_rows(const lbm_ctx* c, void* dst, const double* v, size_t n) {
 }  // namespace
 
 // ---- checkpoint / restart (the reference keeps its state in memory only) ------------------------
-// File: header {magic "LBMCKPT1", nx, ny, y_start, local_ny, precision, steps_done, tau, inlet_velocity, cylinder_*}
-// followed by the post-collision populations P_{steps_done} of the strip's interior, [9][local_ny][nx] in the
-// element type. The state is complete: ghost cells and solid cells are reconstructed by lbm_initialise.
-// A context with a user-defined geometry (lbm_set_solid_mask) writes magic "LBMCKPT2" and the mask's 64-bit digest between the
-// header and the populations; it loads only such a file with the same digest, and an unmasked context only "LBMCKPT1" files.
-// A context with a per-row inlet profile (lbm_set_inlet_profile) writes magic "LBMCKPT3", then a 64-bit word of flags that say which
-// digests follow (bit 0 the mask's, bit 1 the profile's), then those digests in that order; it loads only a "LBMCKPT3" file with the
-// same profile digest (and the same mask digest, or none where it has no mask). Contexts without a profile never write or read it.
-// A Smagorinsky (LES) context (lbm_set_smagorinsky) writes "LBMCKPT3" too, with flag bit 2 set and its constant Cs as a double after
-// the digests; it loads only a file with the same Cs, and a BGK context only a file without bit 2.
-// A TRT context (lbm_set_trt) writes "LBMCKPT3" with flag bit 3 set and its magic parameter as a double after the slot where Cs would
-// stand; it loads only a file with the same magic parameter, and a context without TRT only a file without bit 3.
+// File: CkptHeader; in an "LBMCKPT3" file a 64-bit word of flags; the fields the flags announce, in the order of their bits (bit 0: the
+// obstacle mask's 64-bit digest, bit 1: the inlet profile's, then one double per collision model that has a parameter — ckpt_bit in
+// collision_models, lbm_plan.hpp: bit 2 Cs, bit 3 the TRT magic parameter); then the post-collision populations P_{steps_done} of the
+// strip's interior, [9][local_ny][nx] in the element type. The state is complete: ghost cells and solid cells are reconstructed by
+// lbm_initialise. A context with neither profile nor collision parameter writes "LBMCKPT2" (header, mask digest, populations) if it has a
+// mask and "LBMCKPT1" (header, populations) otherwise. A context loads only a file that announces exactly what it has, with equal values.
 namespace {
 struct CkptHeader {
     char magic[8];
     int nx, ny, y_start, local_ny, precision, steps_done;
     double tau, inlet_velocity, cylinder_x, cylinder_y, cylinder_radius;
 };
+
+// lbm_load_state: the collision parameters a file announces (param: one slot per row of collision_models) against the context's; the last
+// model first, the order mismatches have always been reported in
+int refuse_collision_mismatch(const lbm_ctx* c, const char* path, unsigned long long flags, const double* param) {
+    const double mine = c->collision_param;
+    for (int i = (int)std::size(collision_models) - 1; i >= 0; --i) {
+        const CollisionModel& m = collision_models[i];
+        const bool in_file = flags & m.ckpt_bit, here = m.ckpt_bit && c->collision == m.base;
+        if (!in_file && here) return fail(LBM_ERR_ARG, "checkpoint %s was written without a %s%s; this context has %s%g", path, m.param, m.none, m.value, mine);
+        if (in_file && !here) return fail(LBM_ERR_ARG, "checkpoint %s was written with %s %s%g; this context has none%s", path, m.param, m.value, param[i], m.none);
+        if (in_file && param[i] != mine) return fail(LBM_ERR_ARG, "checkpoint %s was written with %s %s%.17g; this context has %s%.17g", path, m.param, m.value, param[i], m.value, mine);
+    }
+    return LBM_OK;
+}
 
 template <typename T>
 int do_save(lbm_ctx* c, FILE* fp) {
@@ -280,11 +288,31 @@ void lbm_destroy(lbm_ctx* c) {
     delete c;
 }
 
+namespace {
+// the tall fp32 regions (deep 8) exist for the models whose row says so
+int refuse_tall(int collision, int deep) {
+    const CollisionModel& m = collision_model(collision);
+    if (deep_is_tall(deep) && !m.tall) return fail(LBM_ERR_ARG, "deep 8 (64x48 regions in registers) has no %s kernel", m.noun);
+    return LBM_OK;
+}
+// What the setters of the collision models share once the value is accepted. value > 0: the model `base` with that parameter, unless
+// the context has another model (`what`: the caller's name and its word for the value) or, where the setter checks it (`tall_now`), is
+// pinned to tall regions the model lacks; 0: that model off, the BGK kernels.
+int set_collision(lbm_ctx* c, int base, double value, const char* what, bool tall_now) {
+    const CollisionModel& cur = collision_model(c->collision);
+    if (value > 0.0 && c->collision != base && c->collision != AR_STRICT)
+        return fail(LBM_ERR_ARG, "%s %g on a context with %s %s%g (the two collisions cannot be combined)", what, value, cur.param, cur.value, c->collision_param);
+    if (value > 0.0 && tall_now) { if (int rc = refuse_tall(base, c->deep)) return rc; }
+    if (value > 0.0) { c->collision = base; c->collision_param = value; }
+    else if (c->collision == base) { c->collision = AR_STRICT; c->collision_param = 0.0; }
+    return LBM_OK;
+}
+}  // namespace
+
 int lbm_initialise(lbm_ctx* c, int* solid_count_out) {
     if (!c) return fail(LBM_ERR_ARG, "null context");
     lbm_trace("initialise", "ctx %p %dx%d rows %d..%d begin", (void*)c, c->nx, c->p.ny, c->p.y_start, c->p.y_start + c->nyl);
-    if (c->les && deep_is_tall(c->deep)) return fail(LBM_ERR_ARG, "deep 8 (64x48 regions in registers) has no Smagorinsky (LES) kernel");
-    if (c->trt && deep_is_tall(c->deep)) return fail(LBM_ERR_ARG, "deep 8 (64x48 regions in registers) has no two-relaxation-time (TRT) kernel");
+    if (int rc = refuse_tall(c->collision, c->deep)) return rc;
     HIPCHK(hipSetDevice(c->device));
     { int wr = wait_stream(c, c->stream, "compute stream (lbm_initialise)"); if (wr) return wr; }        // (re-)initialisation starts from quiet streams
     { int wr = wait_stream(c, c->comm_stream, "exchange stream (lbm_initialise)"); if (wr) return wr; }
@@ -743,11 +771,7 @@ int lbm_set_smagorinsky(lbm_ctx* c, double cs) {
     if (!c) return fail(LBM_ERR_ARG, "lbm_set_smagorinsky: null context");
     if (c->initialised) return fail(LBM_ERR_ARG, "lbm_set_smagorinsky must be called before lbm_initialise");
     if (!std::isfinite(cs) || cs < 0.0 || cs > 1.0) return fail(LBM_ERR_ARG, "lbm_set_smagorinsky: Cs = %g (finite values in [0, 1] only)", cs);
-    if (cs > 0.0 && c->trt)
-        return fail(LBM_ERR_ARG, "lbm_set_smagorinsky: Cs = %g on a context with TRT magic parameter %g (the two collisions cannot be combined)", cs, c->trt_magic);
-    c->les = cs > 0.0;              // 0: off, the BGK kernels
-    c->les_cs = c->les ? cs : 0.0;
-    return LBM_OK;
+    return set_collision(c, AR_STRICT_LES, cs, "lbm_set_smagorinsky: Cs =", false);    // (pinned to deep 8: lbm_initialise refuses, as it always has)
 }
 
 int lbm_set_trt(lbm_ctx* c, double magic) {
@@ -756,12 +780,7 @@ int lbm_set_trt(lbm_ctx* c, double magic) {
     if (!std::isfinite(magic) || magic < 0.0 || magic > 1.0)
         return fail(LBM_ERR_ARG, "lbm_set_trt: magic parameter = %g (finite values in [0, 1] only)", magic);
     if (magic > 0.0 && !(c->p.tau > 0.5)) return fail(LBM_ERR_ARG, "lbm_set_trt: tau = %g (the magic parameter needs tau > 0.5)", c->p.tau);
-    if (magic > 0.0 && c->les)
-        return fail(LBM_ERR_ARG, "lbm_set_trt: magic parameter %g on a context with Smagorinsky constant Cs = %g (the two collisions cannot be combined)", magic, c->les_cs);
-    if (magic > 0.0 && deep_is_tall(c->deep)) return fail(LBM_ERR_ARG, "deep 8 (64x48 regions in registers) has no two-relaxation-time (TRT) kernel");
-    c->trt = magic > 0.0;           // 0: off, the BGK kernels
-    c->trt_magic = c->trt ? magic : 0.0;
-    return LBM_OK;
+    return set_collision(c, AR_STRICT_TRT, magic, "lbm_set_trt: magic parameter", true);
 }
 
 int lbm_comm_unique_id(void* id128) {
@@ -942,19 +961,20 @@ int lbm_save_state(lbm_ctx* c, const char* path) {
     FILE* fp = fopen(path, "wb");
     if (!fp) return fail(LBM_ERR_ARG, "cannot open %s for writing", path);
     CkptHeader h{};
-    memcpy(h.magic, c->has_profile || c->les || c->trt ? "LBMCKPT3" : c->has_mask ? "LBMCKPT2" : "LBMCKPT1", 8);
+    const CollisionModel& cm = collision_model(c->collision);
+    const bool v3 = c->has_profile || cm.ckpt_bit;
+    memcpy(h.magic, v3 ? "LBMCKPT3" : c->has_mask ? "LBMCKPT2" : "LBMCKPT1", 8);
     h.nx = c->nx; h.ny = c->p.ny; h.y_start = c->p.y_start; h.local_ny = c->nyl; h.precision = c->p.precision;
     h.steps_done = c->steps_done; h.tau = c->p.tau; h.inlet_velocity = c->p.inlet_velocity;
     h.cylinder_x = c->p.cylinder_x; h.cylinder_y = c->p.cylinder_y; h.cylinder_radius = c->p.cylinder_radius;
     int rc = fwrite(&h, sizeof(h), 1, fp) == 1 ? LBM_OK : fail(LBM_ERR_ARG, "short write");
-    if (!rc && (c->has_profile || c->les || c->trt)) {   // LBMCKPT3: flags, then the digests they announce, then Cs, then the TRT magic parameter
-        const unsigned long long flags = (c->has_mask ? 1ull : 0ull) | (c->has_profile ? 2ull : 0ull) | (c->les ? 4ull : 0ull) | (c->trt ? 8ull : 0ull);
+    if (!rc && v3) {   // flags, then what they announce
+        const unsigned long long flags = (c->has_mask ? 1ull : 0ull) | (c->has_profile ? 2ull : 0ull) | cm.ckpt_bit;
         if (fwrite(&flags, sizeof(flags), 1, fp) != 1) rc = fail(LBM_ERR_ARG, "short write");
     }
     if (!rc && c->has_mask && fwrite(&c->hmask.digest, sizeof(c->hmask.digest), 1, fp) != 1) rc = fail(LBM_ERR_ARG, "short write");
     if (!rc && c->has_profile && fwrite(&c->prof_digest, sizeof(c->prof_digest), 1, fp) != 1) rc = fail(LBM_ERR_ARG, "short write");
-    if (!rc && c->les && fwrite(&c->les_cs, sizeof(c->les_cs), 1, fp) != 1) rc = fail(LBM_ERR_ARG, "short write");
-    if (!rc && c->trt && fwrite(&c->trt_magic, sizeof(c->trt_magic), 1, fp) != 1) rc = fail(LBM_ERR_ARG, "short write");
+    if (!rc && cm.ckpt_bit && fwrite(&c->collision_param, sizeof(c->collision_param), 1, fp) != 1) rc = fail(LBM_ERR_ARG, "short write");
     if (!rc) rc = DISPATCH(c, do_save<double>(c, fp), do_save<float>(c, fp));
     fclose(fp);
     return rc;
@@ -978,21 +998,19 @@ int lbm_load_state(lbm_ctx* c, const char* path) {
     CkptHeader h{};
     int rc = LBM_OK;
     unsigned long long digest = 0, flags = 0, pdigest = 0;
-    double cs = 0.0, magic = 0.0;
+    constexpr int NM = (int)std::size(collision_models);
+    double param[NM] = {};             // the parameter of each model the file announces
+    unsigned long long known = 3;
+    for (const CollisionModel& m : collision_models) known |= m.ckpt_bit;
     const bool head = fread(&h, sizeof(h), 1, fp) == 1;
     const bool v1 = head && memcmp(h.magic, "LBMCKPT1", 8) == 0;
     const bool v2 = head && memcmp(h.magic, "LBMCKPT2", 8) == 0 && fread(&digest, sizeof(digest), 1, fp) == 1;
-    const bool v3 = head && memcmp(h.magic, "LBMCKPT3", 8) == 0 && fread(&flags, sizeof(flags), 1, fp) == 1 && (flags & ~15ull) == 0 &&
-                    (!(flags & 1) || fread(&digest, sizeof(digest), 1, fp) == 1) && (!(flags & 2) || fread(&pdigest, sizeof(pdigest), 1, fp) == 1) &&
-                    (!(flags & 4) || fread(&cs, sizeof(cs), 1, fp) == 1) && (!(flags & 8) || fread(&magic, sizeof(magic), 1, fp) == 1);
-    const bool f_mask = v2 || (v3 && (flags & 1)), f_prof = v3 && (flags & 2), f_les = v3 && (flags & 4), f_trt = v3 && (flags & 8);
+    bool v3 = head && memcmp(h.magic, "LBMCKPT3", 8) == 0 && fread(&flags, sizeof(flags), 1, fp) == 1 && (flags & ~known) == 0 &&
+              (!(flags & 1) || fread(&digest, sizeof(digest), 1, fp) == 1) && (!(flags & 2) || fread(&pdigest, sizeof(pdigest), 1, fp) == 1);
+    for (int i = 0; i < NM; ++i) v3 = v3 && (!(flags & collision_models[i].ckpt_bit) || fread(&param[i], sizeof(double), 1, fp) == 1);
+    const bool f_mask = v2 || (v3 && (flags & 1)), f_prof = v3 && (flags & 2);
     if (!v1 && !v2 && !v3) rc = fail(LBM_ERR_ARG, "%s is not a checkpoint", path);
-    else if (!f_trt && c->trt) rc = fail(LBM_ERR_ARG, "checkpoint %s was written without a TRT magic parameter; this context has %g", path, c->trt_magic);
-    else if (f_trt && !c->trt) rc = fail(LBM_ERR_ARG, "checkpoint %s was written with TRT magic parameter %g; this context has none", path, magic);
-    else if (f_trt && magic != c->trt_magic) rc = fail(LBM_ERR_ARG, "checkpoint %s was written with TRT magic parameter %.17g; this context has %.17g", path, magic, c->trt_magic);
-    else if (!f_les && c->les) rc = fail(LBM_ERR_ARG, "checkpoint %s was written without a Smagorinsky constant (BGK); this context has Cs = %g", path, c->les_cs);
-    else if (f_les && !c->les) rc = fail(LBM_ERR_ARG, "checkpoint %s was written with Smagorinsky constant Cs = %g; this context has none (BGK)", path, cs);
-    else if (f_les && cs != c->les_cs) rc = fail(LBM_ERR_ARG, "checkpoint %s was written with Smagorinsky constant Cs = %.17g; this context has Cs = %.17g", path, cs, c->les_cs);
+    else if ((rc = refuse_collision_mismatch(c, path, v3 ? flags : 0, param))) {}
     else if (!f_prof && c->has_profile) rc = fail(LBM_ERR_ARG, "checkpoint %s was written without an inlet profile; this context has one", path);
     else if (f_prof && !c->has_profile) rc = fail(LBM_ERR_ARG, "checkpoint %s was written with an inlet profile; this context has none", path);
     else if (f_prof && pdigest != c->prof_digest) rc = fail(LBM_ERR_ARG, "checkpoint %s was written for a different inlet profile", path);
@@ -1030,8 +1048,7 @@ int lbm_set_option(lbm_ctx* c, const char* key, long value) {
                                 // k_stepc_col (registers): 6 / 7 / 9: 5 / 6 / 7 iterations on 64x32 regions; 8 (fp32): 7 iterations on 64x48 regions.
         if (!deep_valid((int)value)) return fail(LBM_ERR_ARG, "deep must be 0..3 or 6..9 (4 / 5, round 2's 32x16 LDS tiles, are retired)");
         if (deep_is_tall((int)value) && c->esize != 4) return fail(LBM_ERR_ARG, "deep 8 (64x48 regions in registers, twelve waves x four rows) exists in fp32 only");
-        if (deep_is_tall((int)value) && c->les) return fail(LBM_ERR_ARG, "deep 8 (64x48 regions in registers) has no Smagorinsky (LES) kernel");
-        if (deep_is_tall((int)value) && c->trt) return fail(LBM_ERR_ARG, "deep 8 (64x48 regions in registers) has no two-relaxation-time (TRT) kernel");
+        if (int rc = refuse_tall(c->collision, (int)value)) return rc;
         c->deep = (int)value;
         if (c->deep) c->fuse = deep_depth(c->deep);
     }
@@ -1114,7 +1131,7 @@ const char* lbm_kernel_name(const lbm_ctx* c) {
     const bool phys_face = face_south(c) || face_north(c);
     const bool usable = c->deep && (!phys_face || deep_depth(c->deep) <= (device_transport(c) ? GR : HR1));
     const int deep = usable ? c->deep : 0, fuse = usable || !c->deep ? c->fuse : std::min(c->fuse, 3);
-    snprintf(name, sizeof(name), "%s", plan_kernel_name(fuse, deep, c->pair_ty, c->use_nt, ar_of(c->arith == AR_CONTRACTED, c->les, c->trt), (int)c->esize).c_str());
+    snprintf(name, sizeof(name), "%s", plan_kernel_name(fuse, deep, c->pair_ty, c->use_nt, c->collision | (c->arith == AR_CONTRACTED ? 1 : 0), (int)c->esize).c_str());
     return name;
 }
 
@@ -1163,7 +1180,7 @@ int lbm_debug_plan_candidates(int nx, int ny, int precision, int arith, int num_
     if (!out || cap < 1 || nx < 1 || ny < 1) return fail(LBM_ERR_ARG, "bad argument");
     PlanQuery q;
     q.nx = nx; q.nyl = ny; q.ny_glob = ny; q.esize = precision == LBM_PRECISION_F32 ? 4 : 8; q.num_cus = num_cus > 0 ? num_cus : 256;
-    q.les = ar_les(arith) || ar_trt(arith);
+    q.no_tall = !collision_model(arith).tall;
     const Plan none{};
     std::string text;
     for (const Plan& pl : plan_candidates(q, none)) {

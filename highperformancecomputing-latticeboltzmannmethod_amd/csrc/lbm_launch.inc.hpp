@@ -27,13 +27,14 @@ KArgs<T> make_kargs(const lbm_ctx* c, int src, int dst, int t) {
     a.y_lo2 = 0;
     a.y_cnt2 = 0;
     a.reverse = 0;
+    const double cs = c->collision == AR_STRICT_LES ? c->collision_param : 0.0;
     a.les_tau = (T)c->p.tau;           // the Smagorinsky constants (read by LES instantiations only): tau, tau^2, 18 sqrt(2) Cs^2, in double
     a.les_tau2 = (T)(c->p.tau * c->p.tau);
-    a.les_c = (T)(18.0 * std::sqrt(2.0) * (c->les_cs * c->les_cs));
-    // a TRT context (never LES as well): the rate of the odd parts, 1/tau_minus with (tau - 1/2)(tau_minus - 1/2) = magic, in that slot
+    a.les_c = (T)(18.0 * std::sqrt(2.0) * (cs * cs));
+    // a TRT context: the rate of the odd parts, 1/tau_minus with (tau - 1/2)(tau_minus - 1/2) = magic, in that slot
     // (and the two folded rates of the contracted arithmetic in the other two)
-    if (c->trt) {
-        const double wp = 1.0 / c->p.tau, wm = 1.0 / (0.5 + c->trt_magic / (c->p.tau - 0.5));
+    if (c->collision == AR_STRICT_TRT) {
+        const double wp = 1.0 / c->p.tau, wm = 1.0 / (0.5 + c->collision_param / (c->p.tau - 0.5));
         a.trt_wm = (T)wm;
         a.trt_wa = (T)(0.5 * (wp + wm));
         a.trt_wb = (T)(0.5 * (wp - wm));
@@ -60,17 +61,23 @@ inline void configure_layout(lbm_ctx* c, int layout) {
 }
 inline size_t buffer_bytes(const lbm_ctx* c) { return c->total * c->esize + 256; }  // +slack: displaced vector load
 
-// Launch one step-family kernel over the local rows [a.y_lo, a.y_lo + a.y_cnt). Instantiated: MODE_STEP in both store
-// policies and both arithmetic modes, MODE_COLLIDE_ONLY in both arithmetic modes, MODE_STREAM_ONLY once (no collision in it);
-// an LES context (lbm_set_smagorinsky) launches the LES instantiations of MODE_STEP / MODE_COLLIDE_ONLY (lbm_les.hip), a TRT context
-// (lbm_set_trt) the TRT ones (lbm_trt.hip).
+// The one place a collision model (lbm_ctx::collision, the base of a row of collision_models) becomes a template argument:
+// f(std::integral_constant<int, base>) for the row whose base it is.
+template <typename F>
+void with_collision_base(int collision, F&& f) {
+    [&]<size_t... I>(std::index_sequence<I...>) {
+        (void)((collision == collision_models[I].base && (f(std::integral_constant<int, collision_models[I].base>{}), true)) || ...);
+    }(std::make_index_sequence<std::size(collision_models)>{});
+}
+
+// Launch one step-family kernel over the local rows [a.y_lo, a.y_lo + a.y_cnt), with the context's collision model. Instantiated
+// (lbm_step_k.hip) per model: MODE_STEP in both store policies and both arithmetic modes, MODE_COLLIDE_ONLY in both arithmetic modes;
+// MODE_STREAM_ONLY once, under BGK (no collision in it).
 template <typename T, int MODE>
 void launch_rows(const lbm_ctx* c, const KArgs<T>& a, hipStream_t s) {
     const bool nt = (MODE == MODE_STEP) && c->use_nt;
     const bool fast = (MODE != MODE_STREAM_ONLY) && c->arith == AR_CONTRACTED;
-    if (MODE != MODE_STREAM_ONLY && c->les) launch_site_les<T>(a, MODE, nt, fast, s);
-    else if (MODE != MODE_STREAM_ONLY && c->trt) launch_site_trt<T>(a, MODE, nt, fast, s);
-    else launch_site_k<T, MODE, AR_STRICT, AR_CONTRACTED>(a, nt, fast, s);
+    with_collision_base(MODE == MODE_STREAM_ONLY ? (int)AR_STRICT : c->collision, [&](auto arb) { launch_site<T, arb()>(a, MODE, nt, fast, s); });
 }
 
 // "deep" plans: shape id -> iterations per launch and tile. 1..3: LDS-image tiles (k_stepd_tile: six / seven iterations on
@@ -103,20 +110,14 @@ void launch_fused_rows(const lbm_ctx* c, const KArgs<T>& a, int depth, hipStream
                 return;
             }
         }
-        if (c->les) launch_col_les<T>(a, e, depth, c->use_nt != 0, fast, s);   // (no tall LES or TRT regions: lbm_set_option / plan_candidates)
-        else if (c->trt) launch_col_trt<T>(a, e, depth, c->use_nt != 0, fast, s);
-        else launch_col<T>(a, e, depth, c->use_nt != 0, fast, s);
+        // (no tall regions but BGK's: lbm_set_option / plan_candidates)
+        with_collision_base(c->collision, [&](auto arb) { launch_col<T, arb()>(a, e, depth, c->use_nt != 0, fast, s); });
         return;
     }
-    if (c->deep_now) {    // D iterations on a deep LDS tile (k_stepd_tile; whole-domain launches of small grids)
-        if (c->les) launch_deep_les<T>(a, e, shape, fast, s);
-        else if (c->trt) launch_deep_trt<T>(a, e, shape, fast, s);
-        else launch_deep_k<T, AR_STRICT, AR_CONTRACTED>(a, e, shape, fast, s);
-        return;
-    }
-    if (c->les) launch_tile_les<T>(a, e, depth, c->pair_ty, fast, s);
-    else if (c->trt) launch_tile_trt<T>(a, e, depth, c->pair_ty, fast, s);
-    else launch_tile_k<T, AR_STRICT, AR_CONTRACTED>(a, e, depth, c->pair_ty, fast, s);
+    with_collision_base(c->collision, [&](auto arb) {
+        if (c->deep_now) launch_deep<T, arb()>(a, e, shape, fast, s);    // D iterations on a deep LDS tile (k_stepd_tile; whole-domain launches of small grids)
+        else launch_tile<T, arb()>(a, e, depth, c->pair_ty, fast, s);
+    });
 }
 inline bool pair_possible(const lbm_ctx*) { return true; }   // partial tiles cover any nx
 template <typename T>

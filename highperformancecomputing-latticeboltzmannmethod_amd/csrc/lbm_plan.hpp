@@ -32,6 +32,24 @@ inline const char* deep_tile(int id) {
     return id >= 0 && id <= 3 ? t[id] : "";
 }
 
+// The collision models, one row each: everything the host knows about a model beyond its C-ABI setter. `base` is the model's strict
+// Arith value (lbm_kernels.hpp; base | 1: its contracted one) and what lbm_ctx::collision holds; `noun` names it in messages;
+// `tall`: the tall fp32 regions (deep 8) are instantiated for it; `ckpt_bit`: the LBMCKPT3 flag that announces its parameter (0: none —
+// rows in ascending order of this bit, the order the parameters stand in the file); the last three are the words checkpoints and
+// setters use for the parameter, its value and a context without it.
+struct CollisionModel { int base; const char* noun; bool tall; unsigned long long ckpt_bit; const char *param, *value, *none; };
+constexpr CollisionModel collision_models[] = {
+    {AR_STRICT, "BGK", true, 0, "", "", ""},
+    {AR_STRICT_LES, "Smagorinsky (LES)", false, 4, "Smagorinsky constant", "Cs = ", " (BGK)"},
+    {AR_STRICT_TRT, "two-relaxation-time (TRT)", false, 8, "TRT magic parameter", "", ""},
+};
+// the row of an Arith value, strict or contracted
+constexpr const CollisionModel& collision_model(int arith) {
+    for (const CollisionModel& m : collision_models)
+        if (m.base == (arith & ~1)) return m;
+    return collision_models[0];
+}
+
 struct PlanQuery {
     int nx = 0, nyl = 0, ny_glob = 0;   // columns, rows of this strip, rows of the lattice
     int esize = 8;                      // bytes per element
@@ -40,7 +58,7 @@ struct PlanQuery {
     bool strips = false;                // this context has (or simulates) strip faces
     bool faces = false;                 // ... and at least one of them is an internal face
     bool tune = true, can_tune = true;  // option "tune"; the grid is neither too small nor too large to measure
-    bool les = false;                   // Smagorinsky LES or TRT collision: no tall fp32 regions (no such instantiation of them)
+    bool no_tall = false;               // the collision model has no tall fp32 regions (collision_models: no such instantiation of them)
 };
 
 // The strip rule: 0: three iterations on 64x12 LDS tiles in pairs between exchanges; 1: six iterations on 64x16 LDS tiles of
@@ -102,7 +120,7 @@ inline std::vector<Plan> plan_candidates(const PlanQuery& q, const Plan& fixed) 
         cand.push_back({1, 0, 1, 7, 12, 1, "row-interleaved/7-step 64x32 in registers/alternate/xcd", 9});
     }
     // (round 4, fp32: 64x48 regions on twelve waves — 16384x4096 320 GLUPS against 289-298 on 64x32; 4096x1024 262 against 260)
-    if (q.esize == 4 && !small_grid && !q.les) {
+    if (q.esize == 4 && !small_grid && !q.no_tall) {
         cand.push_back({1, 0, 0, 7, 12, 1, "row-interleaved/7-step 64x48 in registers/xcd", 8});
         cand.push_back({1, 0, 1, 7, 12, 1, "row-interleaved/7-step 64x48 in registers/alternate/xcd", 8});
     }

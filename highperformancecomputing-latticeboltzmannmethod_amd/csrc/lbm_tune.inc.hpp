@@ -70,7 +70,7 @@ int choose_plan(lbm_ctx* c) {
     PlanQuery q;
     q.nx = c->nx; q.nyl = c->nyl; q.ny_glob = c->p.ny; q.esize = (int)c->esize; q.num_cus = c->num_cus; q.nstrips = nstrips; q.strips = strips;
     q.tune = c->tune != 0; q.can_tune = can_tune; q.faces = face_south(c) || face_north(c);
-    q.les = c->les || c->trt;
+    q.no_tall = !collision_model(c->collision).tall;
     const std::vector<Plan> cand = plan_candidates(q, fixed);
     free_buffers(c);                                // a second lbm_initialise starts from no population buffers
     // First round: every candidate once; the three fastest keep their allocations. Final round: those three again with
