@@ -97,6 +97,22 @@ def lib():
         L.lbm_group_initialise.argtypes = [pp, C.c_int, C.POINTER(C.c_int)]
         L.lbm_group_step.argtypes = [pp, C.c_int, C.c_int, C.c_int]
         L.lbm_group_refresh_halos.argtypes = [pp, C.c_int]
+        L.lbm_group_first_unstable_step.argtypes = [pp, C.c_int, ip]
+        L.lbm_group_max_velocity_sq.argtypes = [pp, C.c_int, dp]
+        L.lbm_group_get_forces.argtypes = [pp, C.c_int, dp, dp]
+        L.lbm_group_drain_force_log.argtypes = [pp, C.c_int, C.POINTER(ForceRow), C.c_int]
+        L.lbm_group_get_body_forces.argtypes = [pp, C.c_int, dp]
+        L.lbm_group_drain_body_force_log.argtypes = [pp, C.c_int, C.POINTER(BodyForceRow), C.c_int]
+        L.lbm_group_get_macros.argtypes = [pp, C.c_int, dp, dp, dp]
+        L.lbm_group_get_populations.argtypes = [pp, C.c_int, C.c_int, dp]
+        L.lbm_group_stats_samples.argtypes = [pp, C.c_int]
+        L.lbm_group_get_stat_sums.argtypes = [pp, C.c_int, dp]
+        L.lbm_group_stats_restore.argtypes = [pp, C.c_int, dp, C.c_int]
+        L.lbm_group_frames_pending.argtypes = [pp, C.c_int]
+        L.lbm_group_probes_pending.argtypes = [pp, C.c_int]
+        L.lbm_group_drain_frames.argtypes = [pp, C.c_int, ip, C.POINTER(C.c_float), C.c_int]
+        L.lbm_group_drain_probes.argtypes = [pp, C.c_int, ip, dp, C.c_int]
+        L.lbm_debug_gather.argtypes = [C.c_int, C.c_int, ip, C.c_int, C.c_int, C.c_int, C.c_int, pp, vp]
         L.lbm_halo_export.argtypes = [vp, dp, dp]
         L.lbm_halo_import.argtypes = [vp, dp, dp]
         L.lbm_set_option.argtypes = [vp, C.c_char_p, C.c_long]
@@ -188,6 +204,17 @@ def debug_ring(capacity, ops):
     if rc < 0:
         raise LbmError(lib().lbm_last_error().decode())
     return out, rc
+
+
+def debug_gather(what, bounds, nx, ny, parts, whole, k=1, planes=1):
+    """lbm_debug_gather (no device): the rules of the group gathers on one C-contiguous array per strip, bounds = [(y_start, rows)].
+    what: "stack" / "stack_f32" (parts -> whole at row y_start / k), "unstack" (whole -> parts), "populations" (the ghost-row rule),
+    "sum" (the strips' nx * planes doubles added in strip order into whole). Writes whole (unstack: the parts) in place."""
+    b = np.ascontiguousarray(bounds, dtype=np.int32).reshape(-1, 2)
+    ptrs = (C.c_void_p * len(parts))(*[p.ctypes.data for p in parts])
+    code = {"stack": 0, "unstack": 1, "stack_f32": 2, "populations": 3, "sum": 4}[what]
+    if lib().lbm_debug_gather(code, len(parts), b.ctypes.data_as(C.POINTER(C.c_int)), nx, ny, k, planes, ptrs, whole.ctypes.data) < 0:
+        raise LbmError(lib().lbm_last_error().decode())
 
 
 def _label_bytes(labels, nx, ny):
@@ -660,17 +687,21 @@ class Group:
     def steps_done(self):
         return self.ctxs[0].steps_done
 
+    # ---- the whole lattice's results: one library call each (lbm_group_get_* / lbm_group_drain_*, include/lbm_hip.h), which puts the
+    # members' parts together — rows by y_start, sums in strip order, counts that must agree; g.ctxs[k] still gives a member's part ----
     def first_unstable_step(self):
         """min over the strips (the reference's MPI_Allreduce(MIN) of the stability flag, LBMGrid.h:315)."""
-        bad = [t for t in (c.first_unstable_step() for c in self.ctxs) if t >= 0]
-        return min(bad) if bad else -1
+        t = C.c_int()
+        self._chk(self.L.lbm_group_first_unstable_step(self._arr, self._n, C.byref(t)))
+        return t.value
 
     def macros(self):
-        """(rho, ux, uy) of the whole lattice: the strips' rows concatenated by y_start (LBMSolver.h:340-357)."""
-        parts = [c.macros() for c in self.ctxs]
-        return tuple(np.concatenate([p[j] for p in parts], axis=0) for j in range(3))
+        """(rho, ux, uy) of the whole lattice: the strips' rows by y_start (LBMSolver.h:340-357)."""
+        rho, ux, uy = (np.empty((self.ny, self.nx), dtype=np.float64) for _ in range(3))
+        self._chk(self.L.lbm_group_get_macros(self._arr, self._n, _dp(rho), _dp(ux), _dp(uy)))
+        return rho, ux, uy
 
-    # ---- time-averaged statistics: member by member, rows concatenated by y_start like macros() ----
+    # ---- time-averaged statistics: begun and ended member by member ----
     def stats_begin(self, from_step=0):
         for c in self.ctxs:
             c.stats_begin(from_step)
@@ -680,27 +711,25 @@ class Group:
             c.stats_end()
 
     def stats_samples(self):
-        n = {c.stats_samples() for c in self.ctxs}
-        if len(n) != 1:
-            raise LbmError(f"the strips of the group disagree on the number of statistics samples: {sorted(n)}")
-        return n.pop()
+        return self._chk(self.L.lbm_group_stats_samples(self._arr, self._n))
 
     def stats_sums(self):
-        """(6, ny, nx): the strips' sums concatenated by y_start."""
-        return np.concatenate([c.stats_sums() for c in self.ctxs], axis=1)
+        """(6, ny, nx): the strips' sums by y_start."""
+        s = np.empty((6, self.ny, self.nx), dtype=np.float64)
+        self._chk(self.L.lbm_group_get_stat_sums(self._arr, self._n, _dp(s)))
+        return s
 
     def stats_restore(self, sums, samples):
-        a = np.asarray(sums, dtype=np.float64)
+        a = np.ascontiguousarray(sums, dtype=np.float64)
         if a.shape != (6, self.ny, self.nx):
             raise ValueError(f"statistics sums have shape {a.shape}, the lattice needs {(6, self.ny, self.nx)}")
-        for c in self.ctxs:
-            c.stats_restore(a[:, c.y_start:c.y_start + c.local_ny], samples)
+        self._chk(self.L.lbm_group_stats_restore(self._arr, self._n, _dp(a), int(samples)))
 
     def stats(self):
         return _stats_from_sums(self.stats_sums(), self.stats_samples())
 
     # ---- coarsened flow frames: begun on every member (k must divide every strip's y_start and rows); the members sample at the same
-    # iterations, and a drained frame is their rows concatenated by y_start ----
+    # iterations, and a drained frame is their rows by y_start / k ----
     def frames_begin(self, k, capacity=Context.FRAMES_DEFAULT_CAPACITY):
         for c in self.ctxs:
             c.frames_begin(k, capacity)
@@ -710,24 +739,20 @@ class Group:
             c.frames_end()
 
     def frames_pending(self):
-        n = {c.frames_pending() for c in self.ctxs}
-        if len(n) != 1:
-            raise LbmError(f"the strips of the group disagree on the number of pending frames: {sorted(n)}")
-        return n.pop()
+        return self._chk(self.L.lbm_group_frames_pending(self._arr, self._n))
 
     def drain_frames(self, max_frames=None):
-        """[(t, float32 [4, ny / k, nx / k])]: the strips' frames concatenated by y_start."""
+        """[(t, float32 [4, ny / k, nx / k])]: the oldest max_frames (default: all) undrained frames of the whole lattice."""
         n = self.frames_pending()
         if max_frames is not None:
             n = min(n, int(max_frames))
-        parts = [c.drain_frames(n) for c in self.ctxs]
-        out = []
-        for j in range(n):
-            ts = {p[j][0] for p in parts}
-            if len(ts) != 1:
-                raise LbmError(f"the strips of the group disagree on the iteration of a frame: {sorted(ts)}")
-            out.append((ts.pop(), np.concatenate([p[j][1] for p in parts], axis=1)))
-        return out
+        if n < 1:
+            return []
+        k = self.ctxs[0]._frames_k
+        out = np.empty((n, 4, self.ny // k, self.nx // k), dtype=np.float32)
+        ts = (C.c_int * n)()
+        got = self._chk(self.L.lbm_group_drain_frames(self._arr, self._n, ts, out.ctypes.data_as(C.POINTER(C.c_float)), n))
+        return [(ts[j], out[j]) for j in range(got)]
 
     # ---- point probes: every member is given the same global points and samples those of its rows (+0.0 for the others); the members
     # sample at the same iterations, and a drained sample is the SUM of theirs, like the partial force sums ----
@@ -743,38 +768,34 @@ class Group:
         return self.ctxs[0].probes_count()
 
     def probes_pending(self):
-        n = {c.probes_pending() for c in self.ctxs}
-        if len(n) != 1:
-            raise LbmError(f"the strips of the group disagree on the number of pending probe samples: {sorted(n)}")
-        return n.pop()
+        return self._chk(self.L.lbm_group_probes_pending(self._arr, self._n))
 
     def drain_probes(self, max_samples=None):
         """(timesteps int32 [m], float64 [m, n, 3]): the members' samples added up in strip order."""
-        m = self.probes_pending()
+        m, n = self.probes_pending(), self.probes_count()
         if max_samples is not None:
             m = min(m, int(max_samples))
-        parts = [c.drain_probes(m) for c in self.ctxs]
-        ts, total = parts[0][0], parts[0][1].copy()
-        for t, v in parts[1:]:
-            if not np.array_equal(t, ts):
-                raise LbmError(f"the strips of the group disagree on the iterations of the probe samples: {ts.tolist()} / {t.tolist()}")
-            total = total + v
-        return ts, total
+        out = np.zeros((max(m, 0), n, 3), dtype=np.float64)
+        ts = (C.c_int * max(m, 1))()
+        got = self._chk(self.L.lbm_group_drain_probes(self._arr, self._n, ts, _dp(out), m)) if m > 0 else 0
+        return np.array(ts[:got], dtype=np.int32), out[:got]
 
     def populations(self, which):
         """Ghost-inclusive [(ny+2), (nx+2), 9]: interior rows of every strip + the physical ghost rows of the end strips."""
-        parts = [c.populations(which) for c in self.ctxs]
-        rows = [parts[0][:1]] + [p[1:-1] for p in parts] + [parts[-1][-1:]]
-        return np.concatenate(rows, axis=0)
+        out = np.empty((self.ny + 2, self.nx + 2, 9), dtype=np.float64)
+        self._chk(self.L.lbm_group_get_populations(self._arr, self._n, {"f_current": 0, "f_next": 1}[which], _dp(out)))
+        return out
 
     def drain_force_log(self):
         """Rows summed over the strips (the reference's MPI_Reduce(SUM), LBMIO.h:167-168)."""
-        logs = [c.drain_force_log() for c in self.ctxs]
-        return [(logs[0][k][0], sum(l[k][1] for l in logs), sum(l[k][2] for l in logs)) for k in range(len(logs[0]))]
+        rows = (ForceRow * 4096)()
+        n = self._chk(self.L.lbm_group_drain_force_log(self._arr, self._n, rows, 4096))
+        return [(rows[k].timestep, rows[k].fx, rows[k].fy) for k in range(n)]
 
     def forces(self):
-        f = [c.forces() for c in self.ctxs]
-        return sum(v[0] for v in f), sum(v[1] for v in f)
+        fx, fy = C.c_double(), C.c_double()
+        self._chk(self.L.lbm_group_get_forces(self._arr, self._n, C.byref(fx), C.byref(fy)))
+        return fx.value, fy.value
 
     # ---- per-body forces: the strips' partial sums added per (t, body) in strip order ----
     def body_count(self):
@@ -782,19 +803,20 @@ class Group:
 
     def body_forces(self):
         """(B, 2): the strips' partial sums added in strip order."""
-        total = self.ctxs[0].body_forces()
-        for c in self.ctxs[1:]:
-            total = total + c.body_forces()
-        return total
+        out = np.zeros((self.body_count(), 2), dtype=np.float64)
+        self._chk(self.L.lbm_group_get_body_forces(self._arr, self._n, _dp(out)))
+        return out
 
     def drain_body_force_log(self):
-        logs = [c.drain_body_force_log() for c in self.ctxs]
-        if len({len(l) for l in logs}) != 1:
-            raise LbmError("the body force logs of the strips differ in length")
-        return [(logs[0][k][0], logs[0][k][1], sum(l[k][2] for l in logs), sum(l[k][3] for l in logs)) for k in range(len(logs[0]))]
+        max_rows = 4096 * max(1, self.body_count())
+        rows = (BodyForceRow * max_rows)()
+        n = self._chk(self.L.lbm_group_drain_body_force_log(self._arr, self._n, rows, max_rows))
+        return [(rows[k].timestep, rows[k].body, rows[k].fx, rows[k].fy) for k in range(n)]
 
     def max_velocity_sq(self):
-        return max(c.max_velocity_sq() for c in self.ctxs)
+        v = C.c_double()
+        self._chk(self.L.lbm_group_max_velocity_sq(self._arr, self._n, C.byref(v)))
+        return v.value
 
     def close(self):
         for c in self.ctxs:

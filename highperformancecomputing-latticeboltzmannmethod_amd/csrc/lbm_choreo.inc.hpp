@@ -183,5 +183,6 @@ inline lbm_ctx* choreo_fake_ctx(int nx, int ny, int y_start, int rows, int preci
     c->group_k = k;
     c->tune = 0;
     c->log_cap = 1 << 20;
+    c->force_log.per = 3; c->force_log.ix.cap = c->log_cap;      // (no log: nothing is launched)
     return c;
 }

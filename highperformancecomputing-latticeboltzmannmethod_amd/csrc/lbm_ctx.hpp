@@ -225,7 +225,7 @@ struct Choreo { std::vector<ChoreoOp> ops; std::vector<ChoreoP2P> p2p; };
 
 // A ring of samples on the device: ix.cap slots of `per` elements, one written at each output iteration (sample_outputs), drained oldest
 // first. `t` keeps the iteration of each slot on the host — it is known when the sample is issued — for the rings whose rows do not
-// carry it (frames, probes; empty for the body-force log). The index arithmetic is RingIndex (lbm_plan.hpp).
+// carry it (frames, probes; empty for the two force logs). The index arithmetic is RingIndex (lbm_plan.hpp).
 template <typename E>
 struct DeviceRing {
     E* d = nullptr;
@@ -249,9 +249,14 @@ struct DeviceRing {
         if (o.n1 > 0) HIPCHK(hipMemcpyAsync(out, d + per * (size_t)o.start, per * sizeof(E) * (size_t)o.n1, hipMemcpyDeviceToHost, s));
         if (o.n2 > 0) HIPCHK(hipMemcpyAsync(out + per * (size_t)o.n1, d, per * sizeof(E) * (size_t)o.n2, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
-        if (timesteps && !t.empty()) { std::copy_n(t.begin() + o.start, o.n1, timesteps); std::copy_n(t.begin(), o.n2, timesteps + o.n1); }
+        if (timesteps) oldest_timesteps(m, timesteps);
         ix.drop(o.n1 + o.n2);
         return o.n1 + o.n2;
+    }
+    // the iterations of up to `m` of the oldest samples, known without a device call (nothing where the ring keeps none)
+    void oldest_timesteps(int m, int* out) const {
+        const RingIndex::Span o = ix.oldest(m);
+        if (!t.empty()) { std::copy_n(t.begin() + o.start, o.n1, out); std::copy_n(t.begin(), o.n2, out + o.n1); }
     }
 };
 
@@ -283,8 +288,8 @@ struct lbm_ctx {
     int* d_solid_count = nullptr;
     void* d_feq = nullptr;          // the nine initial-equilibrium values in the element type (fused kernels)
     double* d_force_now = nullptr;  // 3 doubles
-    double* d_force_log = nullptr;  // capacity x 3 doubles
-    int log_cap = 0, log_count = 0;
+    DeviceRing<double> force_log;   // [log_cap] rows (t, fx, fy), one appended at every force-output iteration; lbm_drain_force_log takes them all
+    int log_cap = 0;
     int steps_done = 0;
     bool initialised = false;
     double feq_in[Q];

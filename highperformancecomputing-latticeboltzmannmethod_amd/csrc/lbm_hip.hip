@@ -6,6 +6,7 @@
 #include "lbm_frames.hpp"
 #include "lbm_probes.hpp"
 #include "lbm_plan.hpp"
+#include "lbm_gather.hpp"
 #include "lbm_geom.hpp"
 #include "../../include/lbm_hip.h"
 
@@ -138,6 +139,21 @@ int do_load(lbm_ctx* c, FILE* fp, int steps_done) {
     c->restored = true;
     return LBM_OK;
 }
+
+// What the two force-log drains share: up to `m` of the oldest samples of a log of B rows (t, fx, fy) per sample leave the ring and are
+// unpacked into the caller's rows through `put(row, k, t)`, k counting the rows drained; the samples drained, or an error.
+template <typename Row, typename Put>
+int drain_force_rows(lbm_ctx* c, DeviceRing<double>& log, int B, Row* rows, int m, Put put) {
+    HIPCHK(hipSetDevice(c->device));
+    std::vector<double> h(3 * (size_t)B * std::max(1, std::min(m, log.ix.count)));
+    const int n = log.drain(c->stream, h.data(), nullptr, m);
+    for (size_t k = 0; n > 0 && k < (size_t)B * n; ++k) {
+        put(rows[k], k, (int)h[3 * k]);
+        rows[k].fx = h[3 * k + 1];
+        rows[k].fy = h[3 * k + 2];
+    }
+    return n;
+}
 }  // namespace
 
 extern "C" {
@@ -232,7 +248,7 @@ int lbm_create(const lbm_params* p, int device, lbm_ctx** out) {
         const std::vector<double> u((size_t)p->ny, p->inlet_velocity);
         if (int rc = upload_rows(c, c->d_urow, u.data(), u.size())) return bail(rc);
     }
-    HIPTRY(hipMalloc(&c->d_force_log, 3 * sizeof(double) * c->log_cap));
+    HIPTRY(c->force_log.alloc(3, c->log_cap, false));
     HIPTRY(hipMalloc(&c->d_halo, 4 * HR1 * Q * sizeof(double) * (size_t)c->nx));
     HIPTRY(hipMalloc(&c->d_red, 64 * sizeof(double)));
 #undef HIPTRY
@@ -273,7 +289,7 @@ void lbm_destroy(lbm_ctx* c) {
     if (c->comm) { lbm_trace("destroy", "ctx %p ncclCommDestroy", (void*)c); ncclCommDestroy(c->comm); }
     c->pool.reset();
     void* ptrs[] = {c->buf[0], c->buf[1], c->scratch, c->d_macro, c->d_maxbits, c->d_unstable, c->d_tbase, c->d_solid_count, c->d_feq,
-                    c->d_force_now, c->d_force_log, c->d_halo, c->d_red, (void*)c->mview.bits, (void*)c->mview.sat, c->d_fpart,
+                    c->d_force_now, c->force_log.d, c->d_halo, c->d_red, (void*)c->mview.bits, (void*)c->mview.sat, c->d_fpart,
                     c->d_urow, c->d_feqrow, c->d_stats, c->d_labels, c->d_body_box, c->d_body_chunks, c->d_body_first, c->d_body_part,
                     c->d_body_now, c->body_log.d, c->frames.d, c->d_probe_table, c->probes.d};
     for (void* q : ptrs)
@@ -319,8 +335,7 @@ int lbm_initialise(lbm_ctx* c, int* solid_count_out) {
     { int wr = wait_stream(c, c->split_stream, "second compute stream (lbm_initialise)"); if (wr) return wr; }
     c->split_i = 0;
     c->steps_done = 0;
-    c->log_count = 0;
-    c->body_log.ix.reset(); c->frames.ix.reset(); c->probes.ix.reset();
+    c->force_log.ix.reset(); c->body_log.ix.reset(); c->frames.ix.reset(); c->probes.ix.reset();
     c->mid_pair = false;
     c->comm_issued = false;
     c->ext_split_pending = false;
@@ -393,19 +408,9 @@ int lbm_get_forces(lbm_ctx* c, double* fx, double* fy) {
 
 int lbm_drain_force_log(lbm_ctx* c, lbm_force_row* rows, int max_rows) {
     if (!c || (!rows && max_rows > 0)) return fail(LBM_ERR_ARG, "null argument");
-    HIPCHK(hipSetDevice(c->device));
-    const int n = std::min(max_rows, c->log_count);
-    if (n < c->log_count) return fail(LBM_ERR_ARG, "force log holds %d rows, buffer takes %d", c->log_count, max_rows);
-    std::vector<double> h(3 * (size_t)std::max(n, 1));
-    if (n > 0) HIPCHK(hipMemcpyAsync(h.data(), c->d_force_log, 3 * sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    for (int k = 0; k < n; ++k) {
-        rows[k].timestep = (int)h[3 * k];
-        rows[k].fx = h[3 * k + 1];
-        rows[k].fy = h[3 * k + 2];
-    }
-    c->log_count = 0;
-    return n;
+    const int n = c->force_log.ix.count;
+    if (max_rows < n) return fail(LBM_ERR_ARG, "force log holds %d rows, buffer takes %d", n, max_rows);
+    return drain_force_rows(c, c->force_log, 1, rows, n, [](lbm_force_row& r, size_t, int t) { r.timestep = t; });
 }
 
 /* ---- per-body forces (lbm_set_body_labels): k_forces_bodies over the chunk table of the bodies' boxes ---- */
@@ -428,18 +433,9 @@ int lbm_get_body_forces(lbm_ctx* c, double* fxy) {
 int lbm_drain_body_force_log(lbm_ctx* c, lbm_body_force_row* rows, int max_rows) {
     if (!c || (!rows && max_rows > 0)) return fail(LBM_ERR_ARG, "null argument");
     if (c->body_n < 1 || max_rows < c->body_n || c->body_log.ix.count < 1) return 0;       // whole samples only
-    HIPCHK(hipSetDevice(c->device));
     const int B = c->body_n;
-    std::vector<double> h(3 * (size_t)B * std::min(max_rows / B, c->body_log.ix.count));
-    const int n = c->body_log.drain(c->stream, h.data(), nullptr, max_rows / B);
-    if (n < 0) return n;
-    for (size_t k = 0; k < (size_t)B * n; ++k) {
-        rows[k].timestep = (int)h[3 * k];
-        rows[k].body = (int)(k % B) + 1;
-        rows[k].fx = h[3 * k + 1];
-        rows[k].fy = h[3 * k + 2];
-    }
-    return B * n;
+    const int n = drain_force_rows(c, c->body_log, B, rows, max_rows / B, [B](lbm_body_force_row& r, size_t k, int t) { r.timestep = t; r.body = (int)(k % B) + 1; });
+    return n < 0 ? n : B * n;
 }
 
 int lbm_get_macros(lbm_ctx* c, double* rho, double* ux, double* uy) {
@@ -1024,8 +1020,7 @@ int lbm_load_state(lbm_ctx* c, const char* path) {
     if (!rc) rc = DISPATCH(c, do_load<double>(c, fp, h.steps_done), do_load<float>(c, fp, h.steps_done));
     fclose(fp);
     if (rc) return rc;
-    c->log_count = 0;
-    c->body_log.ix.reset();
+    c->force_log.ix.reset(); c->body_log.ix.reset();
     c->last_was_pair = false;
     c->mid_pair = false;
     if ((c->comm || c->loopback) && c->group_n <= 1)   // (a group: lbm_group_refresh_halos once every member is restored)
@@ -1441,3 +1436,5 @@ const char* lbm_build_id(void) {
 }
 
 }  // extern "C"
+
+#include "lbm_group.inc.hpp"

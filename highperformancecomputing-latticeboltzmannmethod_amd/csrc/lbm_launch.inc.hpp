@@ -267,13 +267,13 @@ int launch_probe_sample(lbm_ctx* c, int t) {
 inline int join_comm(lbm_ctx* c);
 template <typename T>
 int sample_outputs(lbm_ctx* c, int t) {
-    if (c->log_count >= c->log_cap) return fail(LBM_ERR_ARG, "force log full (%d rows): drain it", c->log_cap);
+    if (c->force_log.ix.full()) return fail(LBM_ERR_ARG, "force log full (%d rows): drain it", c->force_log.ix.cap);
     if (c->body_n > 0 && c->body_log.ix.full()) return fail(LBM_ERR_ARG, "body force log full (%d samples): drain it", c->body_log.ix.cap);
     if (c->frames_active && !c->rec && c->frames.ix.full()) return fail(LBM_ERR_ARG, "frame ring full (%d frames): drain it (lbm_drain_frames)", c->frames.ix.cap);
     if (c->probes_active && !c->rec && c->probes.ix.full()) return fail(LBM_ERR_ARG, "probe ring full (%d samples): drain it (lbm_drain_probes)", c->probes.ix.cap);
     int rc = join_comm(c);
-    if (!rc) rc = launch_forces<T>(c, c->d_force_log + 3L * c->log_count, t);
-    if (!rc) c->log_count++;
+    if (!rc) rc = launch_forces<T>(c, c->force_log.next_slot(), t);
+    if (!rc) c->force_log.commit(t);
     if (!rc && c->body_n > 0) rc = launch_body_forces<T>(c, c->body_log.next_slot(), t);      // (a sample of the log at exactly the iterations of a force-log row)
     if (!rc && c->body_n > 0) c->body_log.commit(t);
     if (!rc && c->stats_active && t >= c->stats_from) rc = launch_stats<T>(c, t);

@@ -172,7 +172,7 @@ inline std::string plan_option_string(int layout, int nt, int alternate, int pai
 }
 
 // The index arithmetic of a ring of `cap` slots that is filled at the output iterations of lbm_step and drained oldest first (the
-// body-force log, the frame ring, the probe ring: DeviceRing, lbm_ctx.hpp). The only place that wraps an index; exported through
+// two force logs, the frame ring, the probe ring: DeviceRing, lbm_ctx.hpp). The only place that wraps an index; exported through
 // lbm_debug_ring (tests/test_ring_cpu.py holds it against a deque).
 struct RingIndex {
     int cap = 0, head = 0, count = 0;

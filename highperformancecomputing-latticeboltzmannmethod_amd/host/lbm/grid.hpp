@@ -5,8 +5,9 @@
 // Decomposition. The reference's Grid is one MPI rank's block of a 2-D Cartesian topology, and Solver / IOManager gather
 // across ranks (LBMGrid.h:347-392, LBMSolver.h:269-362, LBMIO.h:167-168,225-300). Here ONE Grid is the whole lattice and
 // owns N row strips, one lbm_ctx each, on one or several GPUs of the node (lbm_group_*): the strips advance in lockstep
-// with their halo rows exchanged device to device, and this class does the gathers — rows concatenated by y_start,
-// force partial sums added, the stability word reduced by min, max|u| by max.
+// with their halo rows exchanged device to device, and the library does the gathers (lbm_group_get_* / lbm_group_drain_*:
+// rows stacked by y_start, force partial sums added in strip order, the stability word reduced by min, max|u| by max):
+// every accessor below that returns a result of the whole lattice is one such call.
 #pragma once
 #include "../../../include/lbm_hip.h"
 #include "params.hpp"
@@ -54,7 +55,7 @@ public:
             if (p.trt()) check(lbm_set_trt(c, p.trt_magic), "lbm_set_trt");
             y += n;
         }
-        check(lbm_group_link(ctx_.data(), (int)ctx_.size(), opt.rccl ? 1 : 0), "lbm_group_link");
+        check(lbm_group_link(group(), num_strips(), opt.rccl ? 1 : 0), "lbm_group_link");
         if (!opt.quiet) {   // the banner of Grid::Grid (LBMGrid.h:92-102), restated for this backend
             std::printf("MI355X HIP Grid\n  Global domain: %dx%d\n  GPUs: %d, row strips: %d (halo transport: %s)\n"
                         "  Local with ghosts: %dx%d\n  Ghost layers: 1\n  Precision: %s, collision arithmetic: %s\n"
@@ -120,61 +121,38 @@ public:
     bool check_stability() const { return first_unstable_step() < 0; }
     int first_unstable_step() const {
         int first = -1;
-        for (lbm_ctx* c : ctx_) {
-            int t = -1;
-            check(lbm_first_unstable_step(c, &t), "lbm_first_unstable_step");
-            if (t >= 0 && (first < 0 || t < first)) first = t;
-        }
+        check(lbm_group_first_unstable_step(group(), num_strips(), &first), "lbm_group_first_unstable_step");
         return first;
     }
     // Grid::max_velocity (LBMGrid.h:319-344): max over the strips, then the square root
     double max_velocity() const {
         double m = 0.0;
-        for (lbm_ctx* c : ctx_) {
-            double v = 0.0;
-            check(lbm_max_velocity_sq(c, &v), "lbm_max_velocity_sq");
-            m = std::max(m, v);
-        }
+        check(lbm_group_max_velocity_sq(group(), num_strips(), &m), "lbm_group_max_velocity_sq");
         return std::sqrt(m);
     }
 
     // ---- device control used by Solver / IOManager ----
     int setup_and_initialise() {   // setup_geometry + initialise (LBMGrid.h:152-246) + collision of iteration 0
         int solid = 0;
-        check(lbm_group_initialise(ctx_.data(), (int)ctx_.size(), &solid), "lbm_group_initialise");
+        check(lbm_group_initialise(group(), num_strips(), &solid), "lbm_group_initialise");
         invalidate();
         return solid;
     }
     void advance(int nsteps, int output_frequency) {
         upload_f_current();
-        check(lbm_group_step(ctx_.data(), (int)ctx_.size(), nsteps, output_frequency), "lbm_group_step");
+        check(lbm_group_step(group(), num_strips(), nsteps, output_frequency), "lbm_group_step");
         invalidate();
     }
     int steps_done() const { return lbm_steps_done(ctx_[0]); }
     // IOManager::record_forces' MPI_Reduce(SUM) over the ranks (LBMIO.h:167-168): each strip sums the links whose fluid
     // end it owns
-    void forces_now(double& fx, double& fy) const {
-        fx = fy = 0.0;
-        for (lbm_ctx* c : ctx_) {
-            double a = 0.0, b = 0.0;
-            check(lbm_get_forces(c, &a, &b), "lbm_get_forces");
-            fx += a; fy += b;
-        }
-    }
+    void forces_now(double& fx, double& fy) const { check(lbm_group_get_forces(group(), num_strips(), &fx, &fy), "lbm_group_get_forces"); }
     std::vector<lbm_force_row> drain_force_log() const {
-        std::vector<lbm_force_row> sum;
-        for (size_t k = 0; k < ctx_.size(); ++k) {
-            std::vector<lbm_force_row> rows(4096);
-            const int n = lbm_drain_force_log(ctx_[k], rows.data(), (int)rows.size());
-            check(n, "lbm_drain_force_log");
-            rows.resize((size_t)n);
-            if (k == 0) sum = rows;
-            else {
-                if (rows.size() != sum.size()) throw std::runtime_error("force logs of the strips differ in length");
-                for (size_t r = 0; r < rows.size(); ++r) { sum[r].fx += rows[r].fx; sum[r].fy += rows[r].fy; }
-            }
-        }
-        return sum;
+        std::vector<lbm_force_row> rows(4096);
+        const int got = lbm_group_drain_force_log(group(), num_strips(), rows.data(), (int)rows.size());
+        check(got, "lbm_group_drain_force_log");
+        rows.resize((size_t)got);
+        return rows;
     }
     // per-body forces (lbm_set_body_labels; the reference has none): the strips' partial sums added per (sample, body) in strip order
     int body_count() const { return lbm_body_count(ctx_[0]); }
@@ -182,29 +160,16 @@ public:
         const int B = body_count();
         std::vector<lbm_body_force_row> sum((size_t)B);
         std::vector<double> fxy(2 * (size_t)B);
-        for (int b = 0; b < B; ++b) sum[(size_t)b] = {timestep, b + 1, 0.0, 0.0};
-        for (lbm_ctx* c : ctx_) {
-            check(lbm_get_body_forces(c, fxy.data()), "lbm_get_body_forces");
-            for (int b = 0; b < B; ++b) { sum[(size_t)b].fx += fxy[2 * (size_t)b]; sum[(size_t)b].fy += fxy[2 * (size_t)b + 1]; }
-        }
+        if (B > 0) check(lbm_group_get_body_forces(group(), num_strips(), fxy.data()), "lbm_group_get_body_forces");
+        for (int b = 0; b < B; ++b) sum[(size_t)b] = {timestep, b + 1, fxy[2 * (size_t)b], fxy[2 * (size_t)b + 1]};
         return sum;
     }
     std::vector<lbm_body_force_row> drain_body_force_log() const {
-        std::vector<lbm_body_force_row> sum;
-        const int B = body_count();
-        if (B < 1) return sum;
-        for (size_t k = 0; k < ctx_.size(); ++k) {
-            std::vector<lbm_body_force_row> rows((size_t)B * 4096);
-            const int n = lbm_drain_body_force_log(ctx_[k], rows.data(), (int)rows.size());
-            check(n, "lbm_drain_body_force_log");
-            rows.resize((size_t)n);
-            if (k == 0) sum = rows;
-            else {
-                if (rows.size() != sum.size()) throw std::runtime_error("body force logs of the strips differ in length");
-                for (size_t r = 0; r < rows.size(); ++r) { sum[r].fx += rows[r].fx; sum[r].fy += rows[r].fy; }
-            }
-        }
-        return sum;
+        std::vector<lbm_body_force_row> rows((size_t)body_count() * 4096);
+        const int got = lbm_group_drain_body_force_log(group(), num_strips(), rows.data(), (int)rows.size());
+        check(got, "lbm_group_drain_body_force_log");
+        rows.resize((size_t)got);
+        return rows;
     }
     // checkpoint / restart (build-only feature; the reference keeps its state in memory only): one file per strip
     // (`path` itself for a single strip, `path.k` otherwise)
@@ -213,7 +178,7 @@ public:
     }
     void load_state(const std::string& path) {
         for (size_t k = 0; k < ctx_.size(); ++k) check(lbm_load_state(ctx_[k], strip_file(path, k).c_str()), "lbm_load_state");
-        check(lbm_group_refresh_halos(ctx_.data(), (int)ctx_.size()), "lbm_group_refresh_halos");
+        check(lbm_group_refresh_halos(group(), num_strips()), "lbm_group_refresh_halos");
         invalidate();
     }
     // time-averaged statistics (lbm_stats_*; the reference has none): begun on every strip, the six sums gathered like the macroscopic
@@ -222,32 +187,18 @@ public:
         for (lbm_ctx* c : ctx_) check(lbm_stats_begin(c, from_step), "lbm_stats_begin");
     }
     int stats_samples() const {
-        const int n = lbm_stats_samples(ctx_[0]);
-        for (lbm_ctx* c : ctx_)
-            if (lbm_stats_samples(c) != n) throw std::runtime_error("the strips disagree on the number of statistics samples");
-        return n;
+        const int samples = lbm_group_stats_samples(group(), num_strips());
+        check(samples, "lbm_group_stats_samples");
+        return samples;
     }
     std::vector<double> stat_sums() const {
-        const size_t n = static_cast<size_t>(nx_) * ny_;
-        std::vector<double> all(6 * n), part;
-        for (size_t k = 0; k < ctx_.size(); ++k) {
-            const size_t m = static_cast<size_t>(nx_) * nyl_[k];
-            part.resize(6 * m);
-            check(lbm_get_stat_sums(ctx_[k], part.data()), "lbm_get_stat_sums");
-            for (int j = 0; j < 6; ++j) std::copy(part.begin() + j * m, part.begin() + (j + 1) * m, all.begin() + j * n + static_cast<size_t>(y0_[k]) * nx_);
-        }
+        std::vector<double> all(6 * static_cast<size_t>(nx_) * ny_);
+        check(lbm_group_get_stat_sums(group(), num_strips(), all.data()), "lbm_group_get_stat_sums");
         return all;
     }
     void stats_restore(const std::vector<double>& all, int samples) {
-        const size_t n = static_cast<size_t>(nx_) * ny_;
-        if (all.size() != 6 * n) throw std::runtime_error("statistics of a different lattice");
-        std::vector<double> part;
-        for (size_t k = 0; k < ctx_.size(); ++k) {
-            const size_t m = static_cast<size_t>(nx_) * nyl_[k];
-            part.resize(6 * m);
-            for (int j = 0; j < 6; ++j) std::copy(all.begin() + j * n + static_cast<size_t>(y0_[k]) * nx_, all.begin() + j * n + static_cast<size_t>(y0_[k]) * nx_ + m, part.begin() + j * m);
-            check(lbm_stats_restore(ctx_[k], part.data(), samples), "lbm_stats_restore");
-        }
+        if (all.size() != 6 * static_cast<size_t>(nx_) * ny_) throw std::runtime_error("statistics of a different lattice");
+        check(lbm_group_stats_restore(group(), num_strips(), all.data(), samples), "lbm_group_stats_restore");
     }
     // the sums beside a checkpoint (checkpoints do not carry them): "LBMSTAT1", nx, ny, samples, then [6][ny][nx] doubles of the
     // whole lattice, whatever the strips. load_stats: false when the file does not exist (the averages start afresh).
@@ -283,27 +234,13 @@ public:
     std::vector<CoarseFrame> drain_frames() const {
         std::vector<CoarseFrame> out;
         if (frame_k_ < 1) return out;
-        const int n = lbm_frames_pending(ctx_[0]);
-        check(n, "lbm_frames_pending");
-        const size_t cnx = static_cast<size_t>(nx_ / frame_k_), cny = static_cast<size_t>(ny_ / frame_k_);
-        out.resize((size_t)n);
-        for (auto& f : out) f.planes.resize(4 * cnx * cny);
-        std::vector<float> part;
-        std::vector<int> ts((size_t)std::max(n, 1));
-        for (size_t k = 0; k < ctx_.size() && n > 0; ++k) {
-            const size_t rows = static_cast<size_t>(nyl_[k] / frame_k_), y0 = static_cast<size_t>(y0_[k] / frame_k_);
-            part.resize((size_t)n * 4 * rows * cnx);
-            const int got = lbm_drain_frames(ctx_[k], ts.data(), part.data(), n);
-            check(got, "lbm_drain_frames");
-            if (got != n) throw std::runtime_error("the strips disagree on the number of pending frames");
-            for (int j = 0; j < n; ++j) {
-                if (k == 0) out[(size_t)j].timestep = ts[(size_t)j];
-                else if (out[(size_t)j].timestep != ts[(size_t)j]) throw std::runtime_error("the strips disagree on the iteration of a frame");
-                for (size_t pl = 0; pl < 4; ++pl)
-                    std::copy(part.begin() + ((size_t)j * 4 + pl) * rows * cnx, part.begin() + ((size_t)j * 4 + pl + 1) * rows * cnx,
-                              out[(size_t)j].planes.begin() + pl * cny * cnx + y0 * cnx);
-            }
-        }
+        const int m = lbm_group_frames_pending(group(), num_strips());
+        check(m, "lbm_group_frames_pending");
+        const size_t per = 4 * static_cast<size_t>(nx_ / frame_k_) * static_cast<size_t>(ny_ / frame_k_);
+        std::vector<float> all((size_t)m * per);
+        std::vector<int> ts((size_t)m);
+        check(lbm_group_drain_frames(group(), num_strips(), ts.data(), all.data(), m), "lbm_group_drain_frames");
+        for (int j = 0; j < m; ++j) out.push_back({ts[(size_t)j], {all.begin() + (size_t)j * per, all.begin() + ((size_t)j + 1) * per}});
         return out;
     }
     // point probes (lbm_probes_*; the reference has none): every strip is given the same global points and samples those of its rows
@@ -314,32 +251,20 @@ public:
     }
     std::vector<ProbeSample> drain_probes() const {
         std::vector<ProbeSample> out;
-        const int n = lbm_probes_count(ctx_[0]), m = lbm_probes_pending(ctx_[0]);
-        check(m, "lbm_probes_pending");
-        if (n < 1 || m < 1) return out;
-        const size_t per = 3 * (size_t)n;
-        out.resize((size_t)m);
-        std::vector<double> part((size_t)m * per);
+        const int m = lbm_group_probes_pending(group(), num_strips());
+        check(m, "lbm_group_probes_pending");
+        const size_t per = 3 * (size_t)lbm_probes_count(ctx_[0]);
+        std::vector<double> all((size_t)m * per);
         std::vector<int> ts((size_t)m);
-        for (size_t k = 0; k < ctx_.size(); ++k) {
-            const int got = lbm_drain_probes(ctx_[k], ts.data(), part.data(), m);
-            check(got, "lbm_drain_probes");
-            if (got != m) throw std::runtime_error("the strips disagree on the number of pending probe samples");
-            for (int j = 0; j < m; ++j) {
-                ProbeSample& s = out[(size_t)j];
-                if (k == 0) { s.timestep = ts[(size_t)j]; s.vals.assign(part.begin() + (size_t)j * per, part.begin() + ((size_t)j + 1) * per); }
-                else {
-                    if (s.timestep != ts[(size_t)j]) throw std::runtime_error("the strips disagree on the iteration of a probe sample");
-                    for (size_t q = 0; q < per; ++q) s.vals[q] += part[(size_t)j * per + q];
-                }
-            }
-        }
+        check(lbm_group_drain_probes(group(), num_strips(), ts.data(), all.data(), m), "lbm_group_drain_probes");
+        for (int j = 0; j < m; ++j) out.push_back({ts[(size_t)j], {all.begin() + (size_t)j * per, all.begin() + ((size_t)j + 1) * per}});
         return out;
     }
     const char* plan() const { return lbm_plan(ctx_[0]); }
     lbm_ctx* handle(int k = 0) const { return ctx_[(size_t)k]; }
 
 private:
+    lbm_ctx** group() const { return const_cast<lbm_ctx**>(ctx_.data()); }      // the group as linked, for the lbm_group_* calls
     static void check(int rc, const char* what) {
         if (rc < 0) throw std::runtime_error(std::string(what) + ": " + lbm_last_error());
     }
@@ -351,27 +276,16 @@ private:
     void invalidate() { macros_ok_ = false; f_ok_[0] = f_ok_[1] = false; fc_dirty_ = false; }
     void ensure_macros() const {   // the gather of Solver::write_vtk_frame (LBMSolver.h:340-357): strips stacked by y_start
         if (macros_ok_) return;
-        const size_t n = static_cast<size_t>(nx_) * ny_;
-        rho_.resize(n); ux_.resize(n); uy_.resize(n);
-        for (size_t k = 0; k < ctx_.size(); ++k) {
-            const size_t off = static_cast<size_t>(y0_[k]) * nx_;
-            check(lbm_get_macros(ctx_[k], rho_.data() + off, ux_.data() + off, uy_.data() + off), "lbm_get_macros");
-        }
+        const size_t cells = static_cast<size_t>(nx_) * ny_;
+        rho_.resize(cells); ux_.resize(cells); uy_.resize(cells);
+        check(lbm_group_get_macros(group(), num_strips(), rho_.data(), ux_.data(), uy_.data()), "lbm_group_get_macros");
         macros_ok_ = true;
     }
     void ensure_f(int which) const {
         if (f_ok_[which]) return;
         auto& v = which == 0 ? fc_ : fn_;
-        const size_t row = static_cast<size_t>(nx_ + 2) * Q;
-        v.resize(row * (ny_ + 2));
-        std::vector<double> part;
-        for (size_t k = 0; k < ctx_.size(); ++k) {
-            part.resize(row * (nyl_[k] + 2));
-            check(lbm_get_populations(ctx_[k], which, part.data()), "lbm_get_populations");
-            // interior rows of the strip; the physical ghost rows come from the first / last strip
-            const size_t first = (k == 0) ? 0 : 1, last = (k + 1 == ctx_.size()) ? nyl_[k] + 2 : nyl_[k] + 1;
-            std::copy(part.begin() + first * row, part.begin() + last * row, v.begin() + (y0_[k] + first) * row);
-        }
+        v.resize(static_cast<size_t>(nx_ + 2) * Q * (ny_ + 2));
+        check(lbm_group_get_populations(group(), num_strips(), which, v.data()), "lbm_group_get_populations");
         f_ok_[which] = true;
     }
     void upload_f_current() {   // values a client wrote through f_current(x,y,i): re-collided into the device state
@@ -379,7 +293,7 @@ private:
         const size_t row = static_cast<size_t>(nx_ + 2) * Q;
         for (size_t k = 0; k < ctx_.size(); ++k)
             check(lbm_set_f_current(ctx_[k], fc_.data() + static_cast<size_t>(y0_[k]) * row), "lbm_set_f_current");
-        check(lbm_group_refresh_halos(ctx_.data(), (int)ctx_.size()), "lbm_group_refresh_halos");
+        check(lbm_group_refresh_halos(group(), num_strips()), "lbm_group_refresh_halos");
         fc_dirty_ = false;
     }
     void ensure_solid() const {

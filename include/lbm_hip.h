@@ -96,7 +96,8 @@ int  lbm_first_unstable_step(lbm_ctx* c, int* t_out);
 
 /* IOManager::record_forces (LBMIO.h:133-168) for t = steps_done: this strip's partial sums. Synchronises. */
 int  lbm_get_forces(lbm_ctx* c, double* fx, double* fy);
-/* Rows appended by lbm_step (this strip's partial sums); returns the number copied, clears the log. */
+/* Rows appended by lbm_step (this strip's partial sums), oldest first: all of them are copied and leave the log, and their number is
+ * returned — or, where max_rows is fewer, LBM_ERR_ARG "force log holds %d rows, buffer takes %d" and the log stays. Synchronises. */
 int  lbm_drain_force_log(lbm_ctx* c, lbm_force_row* rows, int max_rows);
 
 /* ---- forces per obstacle body (no reference counterpart: the reference has one disc and one total, LBMIO.h:133-168; what this replaces
@@ -306,9 +307,8 @@ int  lbm_comm_allreduce(lbm_ctx* c, double* vals, int n, int op);
  * transport 0: every strip pulls its neighbours' edge rows with hipMemcpyPeerAsync over xGMI (plain device copies when
  * two strips share a device) on its side stream, behind the neighbour's edge-rows event; transport 1: RCCL, one
  * communicator per member (ncclCommInitAll; distinct devices), all members' ncclSend/ncclRecv in one group call.
- * The launch sequence, the exchange cadence and the overlap are those of lbm_step. Per-strip results
- * (lbm_get_macros, lbm_drain_force_log, lbm_first_unstable_step, ...) are read member by member and combined by the
- * caller (sum of forces, min of the unstable step, rows concatenated by y_start: LBMSolver.h:269-362, LBMIO.h:167-168).
+ * The launch sequence, the exchange cadence and the overlap are those of lbm_step. The results of the whole lattice are read
+ * through the gathers below (lbm_group_get_* / lbm_group_drain_*); the per-member entry points keep returning a strip's part.
  * lbm_group_refresh_halos: after lbm_load_state on every member.
  * Errors: a member's failure (or LBM_ERR_TIMEOUT: a strip thread that did not reach a rendezvous within "wait_timeout_ms") makes
  * lbm_group_step return that error on the caller with every strip thread parked again; the launch in flight was abandoned half-way,
@@ -318,6 +318,46 @@ int  lbm_group_link(lbm_ctx** ctxs, int n, int transport);
 int  lbm_group_initialise(lbm_ctx** ctxs, int n, int* solid_total_out);
 int  lbm_group_step(lbm_ctx** ctxs, int n, int nsteps, int output_frequency);
 int  lbm_group_refresh_halos(lbm_ctx** ctxs, int n);
+/* The gathers of a group: every result of the per-member entry points put together for the WHOLE lattice, in one place (replaces the
+ * gathers of the reference's Solver / IOManager across its ranks: MPI_Gatherv of the fields, LBMSolver.h:340-357, MPI_Reduce(SUM) of the
+ * forces, LBMIO.h:167-168, MPI_Allreduce(MIN / MAX) of the stability flag and max|u|, LBMGrid.h:315,342). ctxs / n: the group as linked
+ * (LBM_ERR_ARG otherwise); one linked or unlinked whole-domain context (n == 1) is a group. Each call runs the member's entry point of
+ * the same name on member 0, 1, .. n-1 in turn on the calling thread and returns its first error; arrays are those of the member call
+ * with ny in place of local_ny. The rules (csrc/lbm_gather.hpp; lbm_debug_gather runs them without a device):
+ *   ROWS   a plane of a member lies at row y_start of the plane of the whole lattice (a frame's at row y_start / k);
+ *   SUM    strip 0's value, then += the values of strips 1 .. n-1 in that order, for forces, body forces and probes alike. There is no
+ *          leading 0 +: a sum whose only terms are -0.0 is -0.0 (a caller that starts from 0.0 gets +0.0; nonzero sums are the same bits);
+ *   COUNT  a count every member must hold alike is returned as that value; LBM_ERR_ARG "... disagree ..." if the members differ.
+ * ALL OR NOTHING: a drain compares, before the first member is drained, what the host knows without a device call — every member's
+ * number of pending samples and, for frames and probes, the iteration of each sample it would take — and on a difference returns
+ * LBM_ERR_ARG "... disagree ..." with every ring as it was. (They are equal whenever lbm_group_step was the only thing that stepped the
+ * members.) The two force logs keep their iterations in device memory: those are compared row by row after the copy, and a difference
+ * there is reported as LBM_ERR_ARG "... disagree ... the drained rows are gone". */
+int  lbm_group_first_unstable_step(lbm_ctx** ctxs, int n, int* t_out);    /* min over the members that report a step; -1 if none does */
+int  lbm_group_max_velocity_sq(lbm_ctx** ctxs, int n, double* out);       /* max over the members */
+int  lbm_group_get_forces(lbm_ctx** ctxs, int n, double* fx, double* fy); /* SUM */
+/* Every row of the members' force logs, the partial sums added per row (SUM); the members' row counts and the iteration of every row
+ * must agree. Like lbm_drain_force_log it returns every row, or LBM_ERR_ARG "force log holds %d rows, buffer takes %d" with nothing drained. */
+int  lbm_group_drain_force_log(lbm_ctx** ctxs, int n, lbm_force_row* rows, int max_rows);
+int  lbm_group_get_body_forces(lbm_ctx** ctxs, int n, double* fxy);       /* [B][2], SUM */
+/* Whole samples of B rows, as many as fit into max_rows, summed per row like the force log; returns the ROWS copied, 0 without labels. */
+int  lbm_group_drain_body_force_log(lbm_ctx** ctxs, int n, lbm_body_force_row* rows, int max_rows);
+/* [ny][nx] each (any may be NULL); every member writes its rows into place (ROWS), without a staging copy. */
+int  lbm_group_get_macros(lbm_ctx** ctxs, int n, double* rho, double* ux, double* uy);
+/* [(ny+2)][(nx+2)][9]: every member gives its interior rows, member 0 also the south physical ghost row, member n-1 the north one. */
+int  lbm_group_get_populations(lbm_ctx** ctxs, int n, int which, double* aos);
+int  lbm_group_stats_samples(lbm_ctx** ctxs, int n);                      /* COUNT */
+int  lbm_group_get_stat_sums(lbm_ctx** ctxs, int n, double* sums6);       /* [6][ny][nx], ROWS */
+/* The inverse of lbm_group_get_stat_sums: every member is given its rows of sums6 = [6][ny][nx] and the sample count. */
+int  lbm_group_stats_restore(lbm_ctx** ctxs, int n, const double* sums6, int samples);
+int  lbm_group_frames_pending(lbm_ctx** ctxs, int n);                     /* COUNT (the pending iterations must agree too) */
+int  lbm_group_probes_pending(lbm_ctx** ctxs, int n);                     /* COUNT (likewise) */
+/* Up to max_frames whole frames, oldest first, as [m][4][ny / k][nx / k] floats (ROWS at y_start / k; k must be the same on every
+ * member), their iterations into timesteps (may be NULL); returns m; 0 when frames were never begun or none is pending. */
+int  lbm_group_drain_frames(lbm_ctx** ctxs, int n, int* timesteps, float* frames, int max_frames);
+/* Up to max_samples whole samples, oldest first, as [m][probes][3] doubles (SUM; the number of probes must be the same on every member),
+ * their iterations into timesteps (may be NULL); returns m; 0 when probes were never begun or none is pending. */
+int  lbm_group_drain_probes(lbm_ctx** ctxs, int n, int* timesteps, double* vals, int max_samples);
 /* What this process actually bound at run time (another library loaded first may have brought its own RCCL / HIP):
  * ncclGetVersion, hipRuntimeGetVersion, hipDriverGetVersion. Any pointer may be NULL. */
 int  lbm_runtime_versions(int* rccl, int* hip_runtime, int* hip_driver);
@@ -427,7 +467,7 @@ int lbm_debug_strip_pins(const int* per_rank7, int nranks, int* agreed7);
  * rows). Returns the number of runs. Replaces the nine-values-per-edge-cell buffers of pack_data_for_sending, LBMGrid.h:395-440. */
 int lbm_debug_face_runs(int hr, int trim, int south_block, int* runs10);
 /* Test hook, callable without a device: the index arithmetic of the device rings that the output iterations fill and the drains empty
- * (body-force log, frames, probes: csrc/lbm_plan.hpp RingIndex), on one ring of `capacity` slots driven through `nops` operations.
+ * (the two force logs, frames, probes: csrc/lbm_plan.hpp RingIndex), on one ring of `capacity` slots driven through `nops` operations.
  * ops[k] < 0 pushes a sample, ops[k] = m >= 0 takes up to m of the oldest. out3[3k..3k+2]: a push: {its slot, -1, -1}, or {-1, -1, -1}
  * on a full ring (nothing changes); a take: {start, n1, n2}: slots [start, start + n1), then [0, n2). Returns the samples pending at
  * the end; LBM_ERR_ARG: capacity < 1 or a null pointer. Replaces nothing in the reference. */
@@ -491,6 +531,14 @@ int lbm_debug_body_chunks(const unsigned char* labels, int nx, int ny, int y_sta
  * {fx, fy}, owned = 1 where floor(py) lies in the strip's rows; a probe that is not owned has cell (0, 0) and weights 0. Any output may be
  * NULL. Returns n or < 0. No reference counterpart. */
 int lbm_debug_probe_table(const double* xy, int n, int nx, int ny, int y_start, int local_ny, int* cells4, double* weights2, int* owned);
+/* Test hook, callable without a device: the rules of the group gathers (csrc/lbm_gather.hpp) applied to caller-supplied host arrays, one
+ * per strip. bounds2 = n x {y_start, rows} of a lattice of ny rows of nx cells; parts[i] = strip i's array; what selects the routine:
+ * 0 stack `planes` planes of doubles, parts[i] = [planes][rows / k][nx / k], into whole = [planes][ny / k][nx / k] at row y_start / k
+ * (k = 1: the fine grid); 1 its inverse (whole -> parts); 2 as 0 on floats (frames); 3 ghost-inclusive populations, parts[i] =
+ * [rows + 2][nx + 2][9] into whole = [ny + 2][nx + 2][9] by the ghost-row rule of lbm_group_get_populations; 4 the in-order sum of the
+ * strips' nx * planes doubles into whole (the bounds only have to lie in the lattice). LBM_ERR_ARG: a null pointer, what outside 0..4, a
+ * size < 1 or a strip outside the lattice. No reference counterpart. */
+int lbm_debug_gather(int what, int n, const int* bounds2, int nx, int ny, int k, int planes, void* const* parts, void* whole);
 /* SHA-256 (16 hex digits) of the sources this binary was compiled from (csrc/ and this header); build.py rebuilds
  * when it differs from the tree, bench.py prints it. */
 const char* lbm_build_id(void);

@@ -82,6 +82,26 @@ def test_argument_errors_are_reported_without_a_device(pkg):
     L.lbm_destroy(None)                                                     # destroying nothing is a no-op
 
 
+def test_group_gathers_refuse_an_empty_group_without_a_device(pkg):
+    """Every lbm_group_* gather starts with the group check: a null group or n < 1 is LBM_ERR_ARG, whatever else is passed."""
+    import ctypes as C
+    L = pkg.lib()
+    one = (C.c_void_p * 1)(None)
+    t, v, rows, brows = C.c_int(), C.c_double(), (pkg.binding.ForceRow * 1)(), (pkg.binding.BodyForceRow * 1)()
+    f = (C.c_float * 1)()
+    dv = C.byref(v)
+    calls = {"first_unstable_step": (C.byref(t),), "max_velocity_sq": (dv,), "get_forces": (dv, dv), "drain_force_log": (rows, 1),
+             "get_body_forces": (dv,), "drain_body_force_log": (brows, 1), "get_macros": (dv, dv, dv), "get_populations": (0, dv),
+             "stats_samples": (), "get_stat_sums": (dv,), "stats_restore": (dv, 0), "frames_pending": (), "probes_pending": (),
+             "drain_frames": (C.byref(t), f, 1), "drain_probes": (C.byref(t), dv, 1)}
+    for name, rest in calls.items():
+        fn = getattr(L, "lbm_group_" + name)
+        assert fn(None, 1, *rest) == -1 and b"empty group" in L.lbm_last_error(), name
+        assert fn(one, 0, *rest) == -1 and b"empty group" in L.lbm_last_error(), name
+        assert fn(one, 1, *rest) == -1 and b"null context in group" in L.lbm_last_error(), name
+    assert L.lbm_debug_gather(0, 0, None, 8, 8, 1, 1, None, None) == -1 and b"bad argument" in L.lbm_last_error()
+
+
 def test_strip_schedule_pins_are_agreed_over_the_ranks(pkg):
     """the schedule trials of lbm_initialise are collective, so ranks with different overlap / deep_halo pins must get
     an error on every rank, not a different number of trials (a hang in RCCL). lbm_debug_strip_pins runs the very decision

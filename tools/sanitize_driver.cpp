@@ -1,13 +1,50 @@
 // tools/sanitize_driver.cpp — the host-side logic that runs WITHOUT a GPU (the group threads' rendezvous with its error and time-out paths,
-// the dry run of the strip choreography and its checker) under ThreadSanitizer and AddressSanitizer + UBSan: tools/sanitize_host.sh.
+// the dry run of the strip choreography and its checker, the stacking arithmetic of the group gathers) under ThreadSanitizer and AddressSanitizer + UBSan: tools/sanitize_host.sh.
 // (GPU AddressSanitizer is not available on this pool; the device code is covered by the parity tests.)
+#include <algorithm>
 #include <cstdio>
 #include <cstring>
+#include <vector>
 extern "C" {
 int lbm_debug_group_pool(int n, int rounds, int fail_strip, int fail_round, int stall_strip, int stall_round, int stall_ms, long timeout_ms, int repeat, int* rendezvous_out);
 int lbm_debug_choreography(int nx, int ny, const int* bounds2, int nstrips, int precision, int transport, const char* options, const int* calls2, int ncalls, int dump, char* out, int cap);
 int lbm_debug_p2p_matching(int nx, int ny, const int* bounds2, int nranks, int precision, const char* options, const char* options_rank1, const int* calls2, int ncalls, char* out, int cap);
+int lbm_debug_gather(int what, int n, const int* bounds2, int nx, int ny, int k, int planes, void* const* parts, void* whole);
 const char* lbm_last_error(void);
+}
+// The gather hook on exactly-sized heap arrays (an index past a strip's part or past the whole is a heap-buffer-overflow): strips of
+// 12 + 16 + 20 rows of 8 cells; six double planes stacked and cut out again, four float planes at k = 4, the populations of 1 - 3
+// strips, a sum. Returns the cases whose result is wrong.
+static int gather_cases() {
+    const int nx = 8, ny = 48, b[6] = {0, 12, 12, 16, 28, 20};
+    int bad = 0;
+    auto run = [&](int what, int n, int lattice_ny, int k, int planes, size_t per_row, int extra_rows, auto zero) {
+        using E = decltype(zero);
+        std::vector<std::vector<E>> parts;
+        std::vector<void*> ptrs;
+        const size_t part_planes = what == 3 || what == 4 ? 1 : (size_t)planes, whole_rows = what == 4 ? 1 : (size_t)(lattice_ny / k + extra_rows);
+        for (int i = 0; i < n; ++i) {
+            const size_t rows = what == 4 ? 1 : (size_t)(b[2 * i + 1] / k + extra_rows);
+            parts.emplace_back(part_planes * rows * per_row);
+            for (size_t q = 0; q < parts.back().size(); ++q) parts.back()[q] = (E)(1000 * (i + 1) + (int)(q % 997));
+        }
+        for (auto& p : parts) ptrs.push_back(p.data());
+        std::vector<E> whole(part_planes * whole_rows * per_row, (E)-1);
+        int rc = lbm_debug_gather(what, n, b, nx, lattice_ny, k, planes, ptrs.data(), whole.data());
+        if (what == 0 && rc == 0) {      // and back: every part must come out as it went in
+            std::vector<std::vector<E>> back = parts;
+            for (size_t i = 0; i < back.size(); ++i) { std::fill(back[i].begin(), back[i].end(), (E)-2); ptrs[i] = back[i].data(); }
+            rc = lbm_debug_gather(1, n, b, nx, lattice_ny, k, planes, ptrs.data(), whole.data());
+            if (back != parts) ++bad;
+        }
+        for (E v : whole) if (v == (E)-1) { ++bad; break; }      // every element of the whole was written
+        if (rc) ++bad;
+    };
+    run(0, 3, ny, 1, 6, nx, 0, 0.0);
+    run(2, 3, ny, 4, 4, nx / 4, 0, 0.0f);
+    for (int n = 1; n <= 3; ++n) run(3, n, b[2 * (n - 1)] + b[2 * n - 1], 1, 1, (size_t)(nx + 2) * 9, 2, 0.0);
+    run(4, 3, ny, 1, 5, (size_t)nx * 5, 0, 0.0);
+    return bad;
 }
 int main() {
     int passed = 0;
@@ -41,5 +78,6 @@ int main() {
             bad2 += rc != 0; ++runs2;
         }
     printf("p2p matching: %d eight-rank dry runs, %d mismatching or failed\n", runs2, bad2);
+    printf("group gathers: 6 cases through lbm_debug_gather, %d wrong\n", gather_cases());
     return 0;
 }
