@@ -1,12 +1,40 @@
-"""Shared helpers for the parity tests (test infrastructure)."""
+"""What the test modules share (test infrastructure): paths, fixtures, the GPU plan table, masks and files, context runs, case tables.
+
+A fixture is shared by importing it by name into the test module (pytest finds it there like one defined there)."""
+import importlib
 import os
+import re
+import subprocess
 
 import numpy as np
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
+PKG = "highperformancecomputing-latticeboltzmannmethod_amd"
+EXE = os.path.join(ROOT, PKG, "host", "lbm_solver")
 
 
+# ---- fixtures ------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module", name="lbm")
+def lbm_gpu():
+    pkg = importlib.import_module(PKG)
+    assert pkg.device_count() >= 1, "no HIP device: the product path has no CPU fallback"
+    return pkg
+
+
+@pytest.fixture(scope="module", name="lbm")
+def lbm_cpu():
+    return importlib.import_module(PKG)
+
+
+@pytest.fixture(scope="module")
+def solver():
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, PKG, "host")])
+    return EXE
+
+
+# ---- golden fixtures and error norms ---------------------------------------------------------------------------------------------
 def load_golden(name):
     z = np.load(os.path.join(GOLDEN, name + ".npz"), allow_pickle=False)
     return {k: z[k] for k in z.files}
@@ -45,3 +73,226 @@ def record(name, **values):
             f.write(json.dumps(dict(test=name, **values)) + "\n")
     except OSError:
         pass
+
+
+# ---- the GPU plan table ----------------------------------------------------------------------------------------------------------
+# Every formulation the plan may pick (lbm_set_option, include/lbm_hip.h) computes the same per-cell arithmetic;
+# the parity tests run each of them explicitly. None = the measured plan (tune=1, the default).
+PLANS = {
+    "auto": None,
+    "planar-vec-alt": dict(tune=0, layout=0, nt=0, alternate=1),
+    "planar-site": dict(tune=0, layout=0, nt=0, alternate=0),
+    "rowil-site-nt": dict(tune=0, layout=1, nt=1, alternate=0),
+    "rowil-vec-nt-alt": dict(tune=0, layout=1, nt=1, alternate=1),
+    # two iterations fused per launch through LDS (k_step2_tile; partial tiles cover any nx)
+    "planar-pair8-nt": dict(tune=0, layout=0, nt=1, alternate=0, pair=1, pair_ty=8),
+    "rowil-pair12-alt": dict(tune=0, layout=1, nt=0, alternate=1, pair=1, pair_ty=12, xcd=1),
+    # three iterations fused per launch (k_step3_tile)
+    "planar-fuse3-8": dict(tune=0, layout=0, nt=0, alternate=1, fuse=3, pair_ty=8),
+    "rowil-fuse3-12-nt-xcd": dict(tune=0, layout=1, nt=1, alternate=0, fuse=3, pair_ty=12, xcd=1),
+    # four iterations fused per launch (k_step4_tile, 64x8 tiles; strips fall back to three)
+    "rowil-fuse4-nt-xcd": dict(tune=0, layout=1, nt=1, alternate=0, fuse=4, pair_ty=8, xcd=1),
+    "planar-fuse4-alt": dict(tune=0, layout=0, nt=0, alternate=1, fuse=4, pair_ty=8, xcd=0),
+    # six / seven / eight iterations per launch on an LDS-filling tile (k_stepd_tile; what a small grid's measurement picks);
+    # calls whose length is no multiple of the depth finish with the four-/three-/two-iteration tile kernels
+    "rowil-deep6-nt": dict(tune=0, layout=1, nt=1, alternate=0, pair_ty=12, xcd=1, deep=1),
+    "planar-deep7-alt": dict(tune=0, layout=0, nt=0, alternate=1, pair_ty=8, xcd=0, deep=2),
+    "rowil-deep8-nt": dict(tune=0, layout=1, nt=1, alternate=0, pair_ty=12, xcd=1, deep=3),
+    # five / six iterations per launch with the lattice held in registers (k_stepc_col: 64x32 regions, DPP x-shifts, six LDS
+    # values per wave and level; round 3's production kernel — what a large grid's measurement and the strip rule pick)
+    "rowil-col5-nt": dict(tune=0, layout=1, nt=1, alternate=0, pair_ty=12, xcd=1, deep=6),
+    "planar-col6-alt": dict(tune=0, layout=0, nt=0, alternate=1, pair_ty=8, xcd=1, deep=7),
+    # contracted collision arithmetic (option "arith" 1: FMA + one reciprocal, what the reference's -ffast-math -mfma build
+    # permits): not bit-identical to the strict oracle, held to the north-star tolerance 1e-10 like every other plan
+    "fast-auto": dict(arith=1),
+    "fast-site": dict(tune=0, layout=1, nt=1, alternate=0, fuse=1, arith=1),
+    "fast-vec-alt": dict(tune=0, layout=0, nt=0, alternate=1, fuse=1, arith=1),
+    "fast-rowil-fuse3-12-xcd": dict(tune=0, layout=1, nt=1, alternate=0, fuse=3, pair_ty=12, xcd=1, arith=1),
+    "fast-planar-pair8": dict(tune=0, layout=0, nt=0, alternate=1, pair=1, pair_ty=8, arith=1),
+    "fast-rowil-fuse4-xcd": dict(tune=0, layout=1, nt=1, alternate=0, fuse=4, pair_ty=8, xcd=1, arith=1),
+    "fast-rowil-deep7": dict(tune=0, layout=1, nt=1, alternate=0, pair_ty=12, xcd=1, deep=2, arith=1),
+    "fast-planar-deep8": dict(tune=0, layout=0, nt=0, alternate=0, pair_ty=8, xcd=1, deep=3, arith=1),
+    "fast-rowil-col6": dict(tune=0, layout=1, nt=1, alternate=0, pair_ty=12, xcd=1, deep=7, arith=1),
+    "fast-planar-col5": dict(tune=0, layout=0, nt=0, alternate=0, pair_ty=8, xcd=1, deep=6, arith=1),
+    # non-temporal level-1 loads in the register kernel (round 4: a store-policy-like choice of the plan measurement)
+    "rowil-col6-ntl-alt": dict(tune=0, layout=1, nt=0, ntl=1, alternate=1, pair_ty=12, xcd=1, deep=7),
+    "fast-rowil-col6-ntl": dict(tune=0, layout=1, nt=0, ntl=1, alternate=0, pair_ty=12, xcd=1, deep=7, arith=1),
+    # seven iterations as the plan's own depth (round 4: what the largest grids' measurement picks; strips exchange seven rows)
+    "rowil-col7-alt": dict(tune=0, layout=1, nt=0, alternate=1, pair_ty=12, xcd=1, deep=9),
+    "fast-rowil-col7": dict(tune=0, layout=1, nt=0, alternate=0, pair_ty=12, xcd=1, deep=9, arith=1),
+}
+FAST = [k for k, v in PLANS.items() if v and v.get("arith")]
+# fp32 contexts only (round 4): seven iterations per launch on TALL 64x48 regions in registers (contracted: twelve waves x four rows; strict: eight x six)
+TALL_F32 = dict(tune=0, layout=1, nt=0, alternate=1, pair_ty=12, xcd=1, deep=8)
+# the plans the feature tests hold against the oracle: one per kernel family and arithmetic mode
+ORACLE_PLANS = ["rowil-site-nt", "planar-fuse3-8", "rowil-deep6-nt", "rowil-col5-nt", "planar-col6-alt", "rowil-col7-alt",
+                "fast-rowil-col6", "fast-planar-col5", "fast-rowil-deep7"]
+
+
+def strict(plan):
+    """True when the plan evaluates the oracle's operation sequence (populations bit-identical to it)."""
+    return plan not in FAST
+
+
+# ---- masks and files -------------------------------------------------------------------------------------------------------------
+def square(nx, ny):
+    m = np.zeros((ny, nx), np.uint8)
+    m[ny // 2 - 8:ny // 2 + 8, nx // 5:nx // 5 + 16] = 1
+    return m
+
+
+def disc(m, cx, cy, r):
+    y, x = np.mgrid[0:m.shape[0], 0:m.shape[1]]
+    m[(x - cx) ** 2 + (y - cy) ** 2 <= r * r] = 1
+    return m
+
+
+def masks(nx, ny):
+    out = {"square": square(nx, ny)}
+    out["tandem"] = disc(disc(np.zeros((ny, nx), np.uint8), 50, ny // 2, 6), 90, ny // 2, 6)
+    m = np.zeros((ny, nx), np.uint8); m[0:12, 60:76] = 1
+    out["bottom-block"] = m
+    m = np.zeros((ny, nx), np.uint8); m[10:21, 0] = 1; m[40:51, nx - 1] = 1
+    out["inlet-outlet"] = m
+    m = np.zeros((ny, nx), np.uint8); m[10, 30] = m[50, 100] = m[33, 150] = m[0, 120] = m[ny - 1, 77] = 1
+    out["single-cells"] = m
+    m = np.zeros((ny, nx), np.uint8); m[30, nx - 2] = m[31, nx - 3] = 1
+    out["ragged-last-column"] = m
+    out["random20"] = (np.random.default_rng(1234).random((ny, nx)) < 0.2).astype(np.uint8)
+    return out
+
+
+def write_pgm(path, cells, maxval=255):
+    """P5 with a comment line; the first image row is the top lattice row; maxval > 255: two bytes per pixel, most significant
+    first. `cells` holds the pixel values: body labels as they are, a 0 / 1 mask as mask * 255."""
+    ny, nx = cells.shape
+    img = cells[::-1]
+    data = img.astype(">u2").tobytes() if maxval > 255 else img.astype(np.uint8).tobytes()
+    with open(path, "wb") as f:
+        f.write(b"P5\n# obstacle\n%d %d\n%d\n" % (nx, ny, maxval) + data)
+
+
+def read_velocity_field(path, nx, ny):
+    d = np.loadtxt(path, delimiter=",", skiprows=1)
+    assert d.shape == (nx * ny, 6)
+    return d[:, 2].reshape(ny, nx), d[:, 3].reshape(ny, nx), d[:, 4].reshape(ny, nx)
+
+
+def read_csv_rows(path):
+    """The rows of forces.csv (or any of the solver's tables) below the header, as lists of strings."""
+    return [l.split(",") for l in open(path).read().splitlines()[1:]]
+
+
+def read_params(path):
+    """simulation_params.csv as {key: value string}, in file order."""
+    return dict(l.split(",", 1) for l in open(path).read().splitlines()[1:])
+
+
+def run_solver(args, cwd):
+    pr = subprocess.run([EXE] + args, cwd=cwd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+    assert pr.returncode == 0, pr.stderr
+    return pr
+
+
+NUM = re.compile(r"^-?\d+\.\d+$")
+
+
+def same_text(ours, ref, tol=1.5e-8):
+    lo, lr = ours.splitlines(), ref.splitlines()
+    assert len(lo) == len(lr), (len(lo), len(lr))
+    for a, b in zip(lo, lr):
+        if a == b:
+            continue
+        ta, tb = re.split(r"[ ,]", a), re.split(r"[ ,]", b)
+        assert len(ta) == len(tb), (a, b)
+        for u, v in zip(ta, tb):
+            if u == v:
+                continue
+            assert NUM.match(u) and NUM.match(v), (a, b)
+            assert abs(float(u) - float(v)) <= tol, (a, b)
+
+
+# ---- context runs ----------------------------------------------------------------------------------------------------------------
+def whole_run(lbm, nx, ny, plan, steps, of, **kw):
+    with lbm.Context(nx, ny, options=PLANS[plan], **kw) as whole:
+        whole.initialise()
+        whole.step(steps, of)
+        return whole.macros(), whole.populations("f_next"), whole.drain_force_log()
+
+
+def run_ctx(lbm, nx, ny, opts, steps, of, **kw):
+    with lbm.Context(nx, ny, options=opts, **kw) as ctx:
+        n = ctx.initialise()
+        ctx.step(steps, of)
+        ctx.step(1, 0)
+        return (n, ctx.populations("f_current"), ctx.populations("f_next"), ctx.macros(), ctx.drain_force_log(),
+                ctx.first_unstable_step())
+
+
+def host_staged_two_strips(lbm, nx, ny, rounds, steps_per_round, strip_options, **ctx_kw):
+    """The MPI-hosted calling pattern on two contexts of ny / 2 rows: lbm_halo_export / lbm_halo_import once, then after every
+    step(steps_per_round, 0) of both. Returns ([f_next of each strip], [solid() of each strip]); closes both contexts."""
+    half = ny // 2
+    ctxs = [lbm.Context(nx, ny, y_start=y0, local_ny=half, options=strip_options, **ctx_kw) for y0 in (0, half)]
+    try:
+        for c in ctxs:
+            c.initialise()
+
+        def exchange():
+            lo, hi = ctxs[0].halo_export(south=False, north=True), ctxs[1].halo_export(south=True, north=False)
+            ctxs[0].halo_import(south=None, north=hi[0])
+            ctxs[1].halo_import(south=lo[1], north=None)
+        exchange()
+        for _ in range(rounds):
+            for c in ctxs:
+                c.step(steps_per_round, 0)
+            exchange()
+        return [c.populations("f_next") for c in ctxs], [c.solid() for c in ctxs]
+    finally:
+        for c in ctxs:
+            c.close()
+
+
+def assert_group_is_whole(group, whole):
+    """A stepped group against whole_run's (macros, f_next, force log) of the one-domain run: fields bit for bit, force rows at the
+    strips-against-whole bar."""
+    for u, v in zip(group.macros(), whole[0]):
+        assert np.array_equal(u, v)
+    assert np.array_equal(group.populations("f_next"), whole[1])
+    log = group.drain_force_log()
+    assert [r[0] for r in log] == [r[0] for r in whole[2]]
+    for (t, fx, fy), (_, wx, wy) in zip(log, whole[2]):
+        assert abs(fx - wx) <= 1e-13 * max(1.0, abs(wx)) and abs(fy - wy) <= 1e-13 * max(1.0, abs(wy))
+
+
+# ---- case tables of the CPU choreography tests -----------------------------------------------------------------------------------
+# calls with a force output inside (the sample points); the last one samples from a later step over three calls of awkward lengths
+STAT_CALLS = [[(31, 7)], [(50, 13)], [(64, 8)], [(97, 31), (5, 0)], [(5, 10), (20, 10), (97, 10)], [(40, 1)]]
+FRAME_PLANS = [(dict(deep=1), 0), (dict(deep=7, arith=1), 0)]
+
+
+def sample_points(calls, from_step):
+    pts, t = [], 0
+    for n, of in calls:
+        pts += [u for u in range(t, t + n) if of > 0 and u % of == 0 and u >= from_step]
+        t += n
+    return pts
+
+
+def ops_of(text, kind):
+    return [(int(m.group(1)), int(m.group(2))) for m in re.finditer(r"strip (\d+) main stream: %s t=(\d+) reads" % kind, text)]
+
+
+def geometries():
+    """every transport; a few of the strip bounds of tests/test_choreography_cpu.py per transport (odd boundaries, twelve-row strips)"""
+    from tests import test_choreography_cpu as tc      # (its table is the one the choreography tests enumerate in full)
+    keep = {0: 4, 1: 2, 2: None, 3: None}
+    seen = {0: 0, 1: 0}
+    for transport, bounds, ny in tc.geometries():
+        if transport in seen:
+            seen[transport] += 1
+            if seen[transport] > keep[transport]:
+                continue
+        if transport == 2 and bounds[0][1] not in (12, 13, 23, 44, 64, 79, 128, 191, 600):
+            continue
+        yield transport, bounds, ny

@@ -19,9 +19,8 @@ import pytest
 
 from tests import test_choreography_cpu as tc
 from tests import test_choreography_split_cpu as ts
-from tests import test_stats_cpu as tstats
+from tests.helpers import PKG, STAT_CALLS, geometries, ops_of, sample_points, write_pgm
 
-PKG = "highperformancecomputing-latticeboltzmannmethod_amd"
 SYMBOLS = ("lbm_set_body_labels", "lbm_body_count", "lbm_get_body_forces", "lbm_drain_body_force_log", "lbm_debug_body_chunks")
 LBM_ERR_ARG = -1
 FORCE_CHUNK = 65536
@@ -199,10 +198,6 @@ def test_labels_outside_a_byte_are_refused_by_the_binding(lbm):
 
 
 # ---- the choreography: the per-body sample sits directly behind the force kernel, in every schedule -------------------------
-def ops_of(text, kind):
-    return [(int(m.group(1)), int(m.group(2))) for m in re.finditer(r"strip (\d+) main stream: %s t=(\d+) reads" % kind, text)]
-
-
 def test_the_body_sample_is_ordered_and_fresh_in_every_schedule(dry):
     """bodies=1: 0 violations (no RACE, no STALE) for transports 0-3, every overlap x deep_halo schedule and every plan family of
     tests/test_stats_cpu.py; one "body forces" operation per strip and force point, directly behind the force kernel of that strip and
@@ -210,14 +205,14 @@ def test_the_body_sample_is_ordered_and_fresh_in_every_schedule(dry):
     runs = 0
     for (plan, prec), dh, ov in itertools.product(tc.PLANS, (0, 1, 2), (0, 1, 2)):
         opts = dict(tune=0, nt=1, xcd=1, overlap=ov, deep_halo=dh, trailing_pair=0, **plan)
-        for transport, bounds, ny in tstats.geometries():
-            for calls in tstats.STAT_CALLS:
+        for transport, bounds, ny in geometries():
+            for calls in STAT_CALLS:
                 rc, text = dry(256, ny, bounds, transport, dict(opts, bodies=1), calls, prec, dump=1)
                 runs += 1
                 assert rc == 0, f"{opts} bodies=1 transport {transport} bounds {bounds} calls {calls}: rc {rc}\n{text[:3000]}"
                 forces, bodies = ops_of(text, "forces"), ops_of(text, "body forces")
                 for k in range(len(bounds)):
-                    assert [t for s, t in bodies if s == k] == [t for s, t in forces if s == k] == tstats.sample_points(calls, 0)
+                    assert [t for s, t in bodies if s == k] == [t for s, t in forces if s == k] == sample_points(calls, 0)
                 lines = text.splitlines()
                 for i, ln in enumerate(lines):
                     if ": body forces t=" in ln:
@@ -255,7 +250,7 @@ def test_split_plans_take_the_body_sample_on_the_joined_main_stream(dry):
                 rc, text = dry(256, ny, [(0, ny)], 0, dict(opts, bodies=1), calls, prec, dump=1)
                 runs += 1
                 assert rc == 0, f"{opts} ny {ny} calls {calls}: rc {rc}\n{text[:3000]}"
-                assert [t for _, t in ops_of(text, "body forces")] == tstats.sample_points(calls, 0)
+                assert [t for _, t in ops_of(text, "body forces")] == sample_points(calls, 0)
     assert runs > 300
 
 
@@ -265,15 +260,6 @@ def solver(lbm):
     exe = os.path.join(os.path.dirname(lbm.__file__), "host", "lbm_solver")
     assert os.path.exists(exe), "host/lbm_solver was not built"
     return exe
-
-
-def write_pgm(path, labels, maxval=255):
-    """P5; the first image row is the top lattice row; maxval > 255: two bytes per pixel, most significant first."""
-    ny, nx = labels.shape
-    img = labels[::-1]
-    data = img.astype(">u2").tobytes() if maxval > 255 else img.astype(np.uint8).tobytes()
-    with open(path, "wb") as f:
-        f.write(b"P5\n%d %d\n%d\n" % (nx, ny, maxval) + data)
 
 
 def test_lbm_solver_refuses_bodies_together_with_a_mask(solver, tmp_path):

@@ -7,8 +7,7 @@ import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = "highperformancecomputing-latticeboltzmannmethod_amd"
+from tests.helpers import PKG, ROOT
 
 
 @pytest.fixture(scope="module")

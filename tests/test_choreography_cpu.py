@@ -21,7 +21,7 @@ import itertools
 
 import pytest
 
-PKG = "highperformancecomputing-latticeboltzmannmethod_amd"
+from tests.helpers import PKG
 
 
 @pytest.fixture(scope="module")

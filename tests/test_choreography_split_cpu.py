@@ -17,7 +17,7 @@ import re
 
 import pytest
 
-PKG = "highperformancecomputing-latticeboltzmannmethod_amd"
+from tests.helpers import PKG
 
 
 @pytest.fixture(scope="module")

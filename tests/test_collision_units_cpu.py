@@ -7,7 +7,7 @@ import subprocess
 
 import pytest
 
-PKG = "highperformancecomputing-latticeboltzmannmethod_amd"
+from tests.helpers import PKG
 
 
 @pytest.fixture(scope="module")

@@ -18,9 +18,8 @@ import pytest
 
 from tests import test_choreography_cpu as tc
 from tests import test_choreography_split_cpu as ts
-from tests.test_stats_cpu import STAT_CALLS, geometries, ops_of, sample_points
+from tests.helpers import FRAME_PLANS, PKG, STAT_CALLS, geometries, ops_of, sample_points
 
-PKG = "highperformancecomputing-latticeboltzmannmethod_amd"
 LBM_ERR_ARG = -1
 
 
@@ -69,10 +68,6 @@ def test_the_binding_declares_the_entry_points():
     for cls in (pkg.Context, pkg.Group):
         for name in ("frames_begin", "frames_end", "frames_pending", "drain_frames"):
             assert callable(getattr(cls, name)), (cls, name)
-
-
-# one LDS-deep and one register-kernel plan (tests/test_choreography_cpu.py PLANS), fp64
-FRAME_PLANS = [(dict(deep=1), 0), (dict(deep=7, arith=1), 0)]
 
 
 def test_the_frame_sample_is_ordered_and_fresh_in_every_schedule(dry):

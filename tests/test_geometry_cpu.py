@@ -1,28 +1,14 @@
 """User-defined obstacle geometry, the parts that need no GPU: lbm_solver's PGM checks (a bad --obstacle-mask file is refused before
 any device is touched) and the host-side packing lbm_set_solid_mask hands to the kernels (lbm_debug_geometry): the window bitmap of a
 strip and the coarse summed-area table behind the kernels' block-uniform near-solid query, against numpy."""
-import importlib
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
-PKG = "highperformancecomputing-latticeboltzmannmethod_amd"
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, PKG, "host", "lbm_solver")
+from tests.helpers import lbm_cpu, solver  # noqa: F401
 GR = 12   # ghost rows a strip's window reaches beyond its own rows (csrc/lbm_kernels.hpp GR)
-
-
-@pytest.fixture(scope="module")
-def lbm():
-    return importlib.import_module(PKG)
-
-
-@pytest.fixture(scope="module")
-def solver():
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, PKG, "host")])
-    return EXE
 
 
 def run_solver(solver, cwd, pgm, nx=16, ny=8):

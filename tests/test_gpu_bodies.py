@@ -1,7 +1,7 @@
 """Momentum-exchange forces per obstacle body (lbm_set_body_labels, Context(bodies=...), Group(bodies=...), lbm_solver --obstacle-bodies)
 on the GPU.
 
-The reference for every comparison is numpy, below: `link_forces` of tests/test_gpu_geometry.py with the selection "fluid cell (label 0)
+The reference for every comparison is numpy, below: `link_forces` of tests/reference.py with the selection "fluid cell (label 0)
 whose neighbour carries label k", applied to the post-collision populations P_t the kernel itself read. The device holds P_t in
 buf[cur] at steps_done == t and hands it out as populations("f_next") once steps_done == t + 1 (include/lbm_hip.h, time convention), so
 every sample point t is driven as: step to t, read body_forces() and forces(), step(1, of) — which logs row t — and read
@@ -10,32 +10,20 @@ populations("f_next") == P_t of the same context. Only the new kernel is under t
 The bar is 1e-13 * max(1, sum |2 c_i f_i|) per component, the sum running over the links of that body (of all bodies for a total):
 both sides add the same addends in tree order, error O(log N * 2^-53 * sum |a|) ~ 1e-15 * sum |a|; 1e-13 is the project's
 strips-against-whole figure."""
-import importlib
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
-from tests.test_gpu_parity import PLANS
+from tests.helpers import EXE, PLANS, lbm_gpu, read_params, write_pgm  # noqa: F401
+from tests.reference import CX, CY
 
 pytestmark = pytest.mark.gpu
-PKG = "highperformancecomputing-latticeboltzmannmethod_amd"
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, PKG, "host", "lbm_solver")
-CX = [0, 1, 0, -1, 0, 1, -1, -1, 1]
-CY = [0, 0, 1, 0, -1, 1, 1, -1, -1]
 NX, NY, STEPS, OF = 192, 64, 120, 30
-# {planar, row-interleaved} x {fp64, fp32} of tests.test_gpu_parity.PLANS, and one register-kernel plan (k_stepc_col)
+# {planar, row-interleaved} x {fp64, fp32} of tests.helpers.PLANS, and one register-kernel plan (k_stepc_col)
 CONFIGS = {"planar-f64": ("planar-site", "f64"), "planar-f32": ("planar-site", "f32"), "rowil-f64": ("rowil-site-nt", "f64"),
            "rowil-f32": ("rowil-site-nt", "f32"), "register-f64": ("rowil-col5-nt", "f64")}
-
-
-@pytest.fixture(scope="module")
-def lbm():
-    pkg = importlib.import_module(PKG)
-    assert pkg.device_count() >= 1, "no HIP device: the product path has no CPU fallback"
-    return pkg
 
 
 def shifted(a, i):
@@ -355,12 +343,6 @@ def test_the_log_is_a_ring_of_force_log_capacity_samples(lbm):
 
 
 # ---- 9. lbm_solver --obstacle-bodies ----------------------------------------------------------------------------------------
-def write_pgm(path, labels):
-    ny, nx = labels.shape
-    with open(path, "wb") as f:
-        f.write(b"P5\n%d %d\n255\n" % (nx, ny) + labels[::-1].astype(np.uint8).tobytes())      # the first image row is the top lattice row
-
-
 @pytest.mark.parametrize("extra", [["--gpus", "1"], ["--gpus", "1", "--strips", "3"]])
 def test_lbm_solver_writes_forces_per_body(lbm, tmp_path, extra):
     nx, ny, steps, of = 128, 48, 301, 100
@@ -381,7 +363,7 @@ def test_lbm_solver_writes_forces_per_body(lbm, tmp_path, extra):
     assert not os.path.exists(dm / "forces_bodies.csv")
     cells = int((labels == 1).sum())
     assert f"Body 1: {cells} cells, D=13" in banner and f"Body 2: {cells} cells, D=13" in banner, banner
-    params = dict(l.split(",", 1) for l in open(db / "simulation_params.csv").read().splitlines()[1:])
+    params = read_params(db / "simulation_params.csv")
     assert params["obstacle_bodies"] == str(tmp_path / "bodies.pgm") and params["body_count"] == "2" and "obstacle_mask" not in params
     lines = open(db / "forces_bodies.csv").read().splitlines()
     assert lines[0] == "timestep,body,drag_force,lift_force,drag_coeff,lift_coeff"

@@ -15,11 +15,8 @@ import subprocess
 import numpy as np
 import pytest
 
-from tests.test_gpu_geometry import square
-from tests.test_gpu_parity import PLANS
-from tests.test_host_cpp import EXE
+from tests.helpers import EXE, PKG, PLANS, square
 
-PKG = "highperformancecomputing-latticeboltzmannmethod_amd"
 pytestmark = pytest.mark.gpu
 
 BAR = 2.4e-7          # two float32 ulps (2 * 2^-23), relative to the plane's largest value

@@ -4,96 +4,14 @@ The reference's semantics hold for any solid set: solid cells keep w_i, the coll
 them, fluid cells pull w_i from them, and forces are the momentum exchange over solid->fluid links. The oracle runs on a mask too
 (Oracle.solid is a writable view of the array its collision, BCs, initialisation and stability scan read), so it checks any geometry;
 only its lbmo_forces recomputes the disc, so the forces here are recomputed in numpy with the reference's link rule."""
-import importlib
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
-from oracle.oracle import Oracle, make_params
-from tests.test_gpu_parity import PLANS, TALL_F32, strict
+from tests.helpers import (ORACLE_PLANS, PLANS, TALL_F32, assert_group_is_whole, disc, host_staged_two_strips, lbm_gpu, masks,  # noqa: F401
+                           read_csv_rows, read_params, run_solver, square, strict, write_pgm)
+from tests.reference import oracle_run
 
 pytestmark = pytest.mark.gpu
-PKG = "highperformancecomputing-latticeboltzmannmethod_amd"
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, PKG, "host", "lbm_solver")
-CX = [0, 1, 0, -1, 0, 1, -1, -1, 1]
-CY = [0, 0, 1, 0, -1, 1, 1, -1, -1]
-
-
-@pytest.fixture(scope="module")
-def lbm():
-    pkg = importlib.import_module(PKG)
-    assert pkg.device_count() >= 1, "no HIP device: the product path has no CPU fallback"
-    return pkg
-
-
-def link_forces(f_next, solid):
-    """IOManager::record_forces (LBMIO.h:133-160; oracle/lbm_oracle.c lbmo_forces): every solid cell, every direction i whose
-    fluid end x - c_i lies in the domain: F += 2 c_i f_i(x - c_i) on the post-collision populations (ghost-inclusive array)."""
-    ny, nx = solid.shape
-    fx = fy = 0.0
-    f = f_next[1:-1, 1:-1]
-    for i in range(1, 9):
-        # fluid cell (x, y) whose neighbour (x + cx, y + cy) is solid
-        nb = np.zeros_like(solid)
-        ys, yd = (slice(CY[i], None), slice(0, ny - CY[i])) if CY[i] >= 0 else (slice(0, ny + CY[i]), slice(-CY[i], None))
-        xs, xd = (slice(CX[i], None), slice(0, nx - CX[i])) if CX[i] >= 0 else (slice(0, nx + CX[i]), slice(-CX[i], None))
-        nb[yd, xd] = solid[ys, xs]
-        sel = nb & ~solid
-        s = float(np.sum(f[..., i][sel]))
-        fx += 2.0 * CX[i] * s
-        fy += 2.0 * CY[i] * s
-    return fx, fy
-
-
-def oracle_run(nx, ny, mask, steps, of, **kw):
-    """The oracle on `mask`: (f_next, rho, ux, uy, forces [(t, fx, fy)], first unstable step, solid count)."""
-    o = Oracle(make_params(nx, ny, **kw))
-    o.solid[:] = mask
-    o.L.lbmo_initialise(o.h)
-    forces, bad = [], -1
-    for t in range(steps):
-        o.collide()
-        if of and t % of == 0:
-            forces.append((t,) + link_forces(o.f_next, mask.astype(bool)))
-        o.exchange_physical()
-        o.stream()
-        o.boundaries()
-        if not o.stable():
-            bad = t
-            break
-    out = (o.f_next.copy(), o.rho.copy(), o.ux.copy(), o.uy.copy(), forces, bad, o.solid_count())
-    o.close()
-    return out
-
-
-def square(nx, ny):
-    m = np.zeros((ny, nx), np.uint8)
-    m[ny // 2 - 8:ny // 2 + 8, nx // 5:nx // 5 + 16] = 1
-    return m
-
-
-def disc(m, cx, cy, r):
-    y, x = np.mgrid[0:m.shape[0], 0:m.shape[1]]
-    m[(x - cx) ** 2 + (y - cy) ** 2 <= r * r] = 1
-    return m
-
-
-def masks(nx, ny):
-    out = {"square": square(nx, ny)}
-    out["tandem"] = disc(disc(np.zeros((ny, nx), np.uint8), 50, ny // 2, 6), 90, ny // 2, 6)
-    m = np.zeros((ny, nx), np.uint8); m[0:12, 60:76] = 1
-    out["bottom-block"] = m
-    m = np.zeros((ny, nx), np.uint8); m[10:21, 0] = 1; m[40:51, nx - 1] = 1
-    out["inlet-outlet"] = m
-    m = np.zeros((ny, nx), np.uint8); m[10, 30] = m[50, 100] = m[33, 150] = m[0, 120] = m[ny - 1, 77] = 1
-    out["single-cells"] = m
-    m = np.zeros((ny, nx), np.uint8); m[30, nx - 2] = m[31, nx - 3] = 1
-    out["ragged-last-column"] = m
-    out["random20"] = (np.random.default_rng(1234).random((ny, nx)) < 0.2).astype(np.uint8)
-    return out
 
 
 # ---- 1. the disc passed as a mask is the analytic disc, bit for bit, on every plan -------------------------------------------
@@ -141,43 +59,39 @@ def test_disc_as_mask_first_unstable_step(lbm):
 
 
 # ---- 2. other geometries against the oracle -----------------------------------------------------------------------------------
-ORACLE_PLANS = ["rowil-site-nt", "planar-fuse3-8", "rowil-deep6-nt", "rowil-col5-nt", "planar-col6-alt", "rowil-col7-alt",
-                "fast-rowil-col6", "fast-planar-col5", "fast-rowil-deep7"]
-
-
 @pytest.mark.parametrize("name", list(masks(200, 64)))
 def test_masks_against_the_oracle(lbm, name):
     nx, ny, steps, of = 200, 64, 60, 20        # (200 % 64 != 0: a ragged last tile column)
     kw = dict(inlet_velocity=0.05)
     mask = masks(nx, ny)[name]
-    f_ref, rho_ref, ux_ref, uy_ref, forces_ref, bad_ref, count_ref = oracle_run(nx, ny, mask, steps, of, **kw)
-    assert count_ref == int(mask.sum())
+    ref = oracle_run(nx, ny, steps, of, mask=mask, **kw)
+    assert ref.solid_count == int(mask.sum())
     fast = {}
     for plan in ORACLE_PLANS:
         with lbm.Context(nx, ny, options=PLANS[plan], solid=mask, **kw) as ctx:
-            assert ctx.initialise() == count_ref
+            assert ctx.initialise() == ref.solid_count
             assert np.array_equal(ctx.solid(), mask)
             ctx.step(steps, of)
-            assert ctx.first_unstable_step() == bad_ref
-            if bad_ref >= 0:
+            assert ctx.first_unstable_step() == ref.first_unstable
+            if ref.first_unstable >= 0:
                 continue
             log = ctx.drain_force_log()
             fn = ctx.populations("f_next")
             rho, ux, uy = ctx.macros()
-        assert [r[0] for r in log] == [r[0] for r in forces_ref]
-        for (t, fx, fy), (_, rx, ry) in zip(log, forces_ref):
+        assert [r[0] for r in log] == [r[0] for r in ref.forces]
+        for (t, fx, fy), (_, rx, ry) in zip(log, ref.forces):
             assert abs(fx - rx) <= 1e-10 * max(1.0, abs(rx)) and abs(fy - ry) <= 1e-10 * max(1.0, abs(ry)), (plan, t)
         key = "strict" if strict(plan) else "fast"
         fast.setdefault(key, fn)
         assert np.array_equal(fn, fast[key]), plan      # every plan of one arithmetic mode: the same bits
-        scale = float(np.max(np.abs(f_ref)))
+        scale = float(np.max(np.abs(ref.f_next)))
         if key == "strict":
-            assert np.array_equal(fn, f_ref), plan
-            assert np.array_equal(rho, rho_ref) or float(np.max(np.abs(rho - rho_ref))) <= 1e-14, plan
+            assert np.array_equal(fn, ref.f_next), plan
+            assert np.array_equal(rho, ref.rho) or float(np.max(np.abs(rho - ref.rho))) <= 1e-14, plan
         else:
-            assert float(np.max(np.abs(fn - f_ref))) <= 1e-10 * scale, plan
-        uscale = float(np.max(np.sqrt(ux_ref ** 2 + uy_ref ** 2)))
-        assert float(np.max(np.abs(ux - ux_ref))) <= 1e-10 * uscale and float(np.max(np.abs(uy - uy_ref))) <= 1e-10 * uscale, plan
+            assert float(np.max(np.abs(fn - ref.f_next))) <= 1e-10 * scale, plan
+        uscale = float(np.max(np.sqrt(ref.ux ** 2 + ref.uy ** 2)))
+        assert float(np.max(np.abs(ux - ref.ux))) <= 1e-10 * uscale and float(np.max(np.abs(uy - ref.uy))) <= 1e-10 * uscale, plan
 
 
 def test_whole_domain_mask_forces_in_fixed_chunks(lbm):
@@ -187,8 +101,8 @@ def test_whole_domain_mask_forces_in_fixed_chunks(lbm):
     kw = dict(inlet_velocity=0.04)
     mask = (np.random.default_rng(99).random((ny, nx)) < 0.02).astype(np.uint8)
     mask[0, 0] = mask[ny - 1, nx - 1] = 1
-    _, _, _, _, forces_ref, bad_ref, _ = oracle_run(nx, ny, mask, steps, of, **kw)
-    assert bad_ref == -1
+    ref = oracle_run(nx, ny, steps, of, mask=mask, **kw)
+    assert ref.first_unstable == -1
     logs = []
     for plan in ("rowil-site-nt", "rowil-col5-nt", "rowil-col5-nt", "planar-fuse3-8"):
         with lbm.Context(nx, ny, options=PLANS[plan], solid=mask, **kw) as ctx:
@@ -196,8 +110,8 @@ def test_whole_domain_mask_forces_in_fixed_chunks(lbm):
             ctx.step(steps, of)
             logs.append(ctx.drain_force_log())
     assert all(l == logs[0] for l in logs)
-    assert [r[0] for r in logs[0]] == [r[0] for r in forces_ref]
-    for (t, fx, fy), (_, rx, ry) in zip(logs[0], forces_ref):
+    assert [r[0] for r in logs[0]] == [r[0] for r in ref.forces]
+    for (t, fx, fy), (_, rx, ry) in zip(logs[0], ref.forces):
         assert abs(fx - rx) <= 1e-10 * max(1.0, abs(rx)) and abs(fy - ry) <= 1e-10 * max(1.0, abs(ry)), t
 
 
@@ -217,13 +131,7 @@ def test_group_strips_with_a_straddling_obstacle(lbm, plan):
         assert g.initialise() == solid == int(mask.sum())
         g.step(steps, of)
         assert g.first_unstable_step() == -1
-        for u, v in zip(g.macros(), w[0]):
-            assert np.array_equal(u, v)
-        assert np.array_equal(g.populations("f_next"), w[1])
-        log = g.drain_force_log()
-        assert [r[0] for r in log] == [r[0] for r in w[2]]
-        for (t, fx, fy), (_, wx, wy) in zip(log, w[2]):
-            assert abs(fx - wx) <= 1e-13 * max(1.0, abs(wx)) and abs(fy - wy) <= 1e-13 * max(1.0, abs(wy))
+        assert_group_is_whole(g, w)
 
 
 @pytest.mark.parametrize("plan", [None, "rowil-col5-nt"])
@@ -236,25 +144,8 @@ def test_host_staged_strips_with_a_straddling_obstacle(lbm, plan):
         whole.initialise()
         whole.step(48, 0)
         w_fn = whole.populations("f_next")
-    ctxs = [lbm.Context(nx, ny, y_start=y0, local_ny=128, options=PLANS[plan] if plan else None, solid=mask, **kw) for y0 in (0, 128)]
-    try:
-        for c in ctxs:
-            c.initialise()
-
-        def exchange():
-            lo, hi = ctxs[0].halo_export(south=False, north=True), ctxs[1].halo_export(south=True, north=False)
-            ctxs[0].halo_import(south=None, north=hi[0])
-            ctxs[1].halo_import(south=lo[1], north=None)
-        exchange()
-        for _ in range(12):
-            for c in ctxs:
-                c.step(4, 0)
-            exchange()
-        parts = [c.populations("f_next") for c in ctxs]
-        assert np.array_equal(ctxs[0].solid(), mask[:128]) and np.array_equal(ctxs[1].solid(), mask[128:])
-    finally:
-        for c in ctxs:
-            c.close()
+    parts, solids = host_staged_two_strips(lbm, nx, ny, 12, 4, PLANS[plan] if plan else None, solid=mask, **kw)
+    assert np.array_equal(solids[0], mask[:128]) and np.array_equal(solids[1], mask[128:])
     assert np.array_equal(parts[0][1:129], w_fn[1:129]) and np.array_equal(parts[1][1:129], w_fn[129:257])
 
 
@@ -341,26 +232,18 @@ def test_set_solid_mask_arguments(lbm):
 
 
 # ---- 7. the host CLI ---------------------------------------------------------------------------------------------------------
-def write_pgm(path, mask):
-    ny, nx = mask.shape
-    with open(path, "wb") as f:
-        f.write(b"P5\n# obstacle\n%d %d\n255\n" % (nx, ny))
-        f.write((mask[::-1] * 255).astype(np.uint8).tobytes())   # first image row = top lattice row
-
-
 @pytest.mark.parametrize("extra", [[], ["--gpus", "2", "--strips", "2"]])
 def test_lbm_solver_obstacle_mask_matches_the_binding(lbm, tmp_path, extra):
     nx, ny, steps, of = 128, 48, 301, 100
     mask = np.zeros((ny, nx), np.uint8)
     mask[18:30, 30:42] = 1                    # square, frontal height D = 12
-    write_pgm(tmp_path / "sq.pgm", mask)
+    write_pgm(tmp_path / "sq.pgm", mask * 255)
     u = 0.04
-    cmd = [EXE, "--nx", str(nx), "--ny", str(ny), "--steps", str(steps), "--output-frequency", str(of), "--inlet-velocity", str(u),
-           "--no-vtk", "--obstacle-mask", str(tmp_path / "sq.pgm")] + extra
-    pr = subprocess.run(cmd, cwd=tmp_path, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
-    assert pr.returncode == 0, pr.stderr
+    args = ["--nx", str(nx), "--ny", str(ny), "--steps", str(steps), "--output-frequency", str(of), "--inlet-velocity", str(u),
+            "--no-vtk", "--obstacle-mask", str(tmp_path / "sq.pgm")] + extra
+    pr = run_solver(args, tmp_path)
     assert "frontal height D=12" in pr.stdout and f"Solid cells: {int(mask.sum())}" in pr.stdout
-    rows = [l.split(",") for l in open(tmp_path / "forces.csv").read().splitlines()[1:]]
+    rows = read_csv_rows(tmp_path / "forces.csv")
     with lbm.Context(nx, ny, inlet_velocity=u, solid=mask) as ctx:
         ctx.initialise()
         ctx.step(steps, of)
@@ -370,12 +253,10 @@ def test_lbm_solver_obstacle_mask_matches_the_binding(lbm, tmp_path, extra):
     for r, (t, fx, fy) in zip(rows, log):
         for got, want in zip(map(float, r[1:]), (fx, fy, fx / q, fy / q)):
             assert abs(got - want) <= 1.5e-8, (t, r)
-    params = dict(l.split(",", 1) for l in open(tmp_path / "simulation_params.csv").read().splitlines()[1:])
+    params = read_params(tmp_path / "simulation_params.csv")
     assert params["reference_length"] == "12" and params["obstacle_mask"].endswith("sq.pgm")
     assert abs(float(params["reynolds_number"]) - u * 12 / ((0.6 - 0.5) / 3.0)) < 1e-8
     # --reynolds sets the inlet velocity from D
-    pr = subprocess.run(cmd[:5] + ["--steps", "2", "--output-frequency", "1", "--no-vtk", "--no-final", "--reynolds", "20",
-                                   "--obstacle-mask", str(tmp_path / "sq.pgm")] + extra,
-                        cwd=tmp_path, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
-    assert pr.returncode == 0, pr.stderr
+    pr = run_solver(args[:4] + ["--steps", "2", "--output-frequency", "1", "--no-vtk", "--no-final", "--reynolds", "20",
+                                "--obstacle-mask", str(tmp_path / "sq.pgm")] + extra, tmp_path)
     assert f"Inlet velocity = {20 * ((0.6 - 0.5) / 3.0) / 12:g}" in pr.stdout and "Reynolds number = 20" in pr.stdout, pr.stdout

@@ -4,85 +4,15 @@ The reference's Zou-He inlet with u_in replaced by u[y] on row y, and an initial
 imposes one velocity; its arrays are writable views, so the stepwise oracle plus a numpy fix-up of the inlet column (in the
 oracle's operation order) is the per-row reference: strict plans must match it bit for bit."""
 import ctypes as C
-import importlib
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from oracle.oracle import Oracle, make_params
-from tests.helpers import record
-from tests.test_gpu_geometry import ORACLE_PLANS, link_forces, masks, square, write_pgm
-from tests.test_gpu_parity import PLANS, TALL_F32, strict
+from tests.helpers import (ORACLE_PLANS, PLANS, TALL_F32, assert_group_is_whole, host_staged_two_strips, lbm_gpu, masks, read_csv_rows,  # noqa: F401
+                           read_params, read_velocity_field, record, run_ctx, run_solver, square, strict, whole_run, write_pgm)
+from tests.reference import oracle_run
 
 pytestmark = pytest.mark.gpu
-PKG = "highperformancecomputing-latticeboltzmannmethod_amd"
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, PKG, "host", "lbm_solver")
-CX = np.array([0, 1, 0, -1, 0, 1, -1, -1, 1], dtype=np.float64)
-CY = np.array([0, 0, 1, 0, -1, 1, 1, -1, -1], dtype=np.float64)
-W = np.array([4.0 / 9.0] + [1.0 / 9.0] * 4 + [1.0 / 36.0] * 4)
-
-
-@pytest.fixture(scope="module")
-def lbm():
-    pkg = importlib.import_module(PKG)
-    assert pkg.device_count() >= 1, "no HIP device: the product path has no CPU fallback"
-    return pkg
-
-
-def feq_rows(u):
-    """f_eq(1, (u[y], 0)) per row in the oracle's feq_init order (lbm_oracle.c): [ny, 9]."""
-    u = np.asarray(u, dtype=np.float64)[:, None]
-    uy = 0.0
-    usq = u * u + uy * uy
-    t3 = 1.5 * usq
-    cu = CX[None, :] * u + CY[None, :] * uy
-    f = (W[None, :] * 1.0) * (((1.0 + 3.0 * cu) - t3) + 4.5 * (cu * cu))
-    f[:, 0] = (W[0] * 1.0 * (1.0 - 1.5 * usq))[:, 0]
-    return f
-
-
-def oracle_profile_run(nx, ny, u, steps, of, mask=None, **kw):
-    """The stepwise oracle with the inlet of row y at u[y]: (f_next, rho, ux, uy, forces [(t, fx, fy)], first unstable step)."""
-    o = Oracle(make_params(nx, ny, **kw))
-    if mask is not None:
-        o.solid[:] = mask
-    o.L.lbmo_initialise(o.h)
-    solid = o.solid.astype(bool).copy()
-    fluid = ~solid
-    fr = feq_rows(u)
-    for arr in (o.f_current, o.f_next):          # interior fluid cells of row y start at f_eq(1, (u[y], 0))
-        inner = arr[1:-1, 1:-1]
-        inner[fluid] = np.broadcast_to(fr[:, None, :], (ny, nx, 9))[fluid]
-    o.ux[fluid] = np.broadcast_to(np.asarray(u)[:, None], (ny, nx))[fluid]
-    rows = np.nonzero(fluid[:, 0])[0]
-    ur = np.asarray(u, dtype=np.float64)[rows]
-    forces, bad = [], -1
-    for t in range(steps):
-        o.collide()
-        if of and t % of == 0:
-            forces.append((t,) + link_forces(o.f_next, solid))
-        o.exchange_physical()
-        o.stream()
-        o.boundaries()
-        # the inlet again, with u[y]: it reads f0, f2, f3, f4, f6, f7 after the wall conditions (which it leaves alone) and
-        # rewrites f1, f5, f8 (lbm_oracle.c inlet block, same operation order)
-        f = o.f_current[rows + 1, 1, :]
-        rho_bc = (f[:, 0] + f[:, 2] + f[:, 4] + 2.0 * (f[:, 3] + f[:, 6] + f[:, 7])) / (1.0 - ur)
-        f[:, 1] = f[:, 3] + (2.0 / 3.0) * rho_bc * ur
-        f[:, 5] = f[:, 7] - 0.5 * (f[:, 2] - f[:, 4]) + (1.0 / 6.0) * rho_bc * ur
-        f[:, 8] = f[:, 6] + 0.5 * (f[:, 2] - f[:, 4]) + (1.0 / 6.0) * rho_bc * ur
-        o.f_current[rows + 1, 1, :] = f
-        o.rho[rows, 0] = rho_bc
-        o.ux[rows, 0] = ur
-        if not o.stable():
-            bad = t
-            break
-    out = (o.f_next.copy(), o.rho.copy(), o.ux.copy(), o.uy.copy(), forces, bad)
-    o.close()
-    return out
 
 
 def shear(ny, mean):
@@ -95,15 +25,6 @@ def reversed_near_bottom(ny, mean):
     u = s * (1 - s)
     u[:8] = -0.6 * u[:8] - 0.002          # back-flow over the bottom eight rows (the inlet-outlet mask blocks rows 10..20 of x = 0)
     return u * (mean / np.mean(u))
-
-
-def run_ctx(lbm, nx, ny, opts, steps, of, **kw):
-    with lbm.Context(nx, ny, options=opts, **kw) as ctx:
-        n = ctx.initialise()
-        ctx.step(steps, of)
-        ctx.step(1, 0)
-        return (n, ctx.populations("f_current"), ctx.populations("f_next"), ctx.macros(), ctx.drain_force_log(),
-                ctx.first_unstable_step())
 
 
 # ---- 1. a constant profile is the uniform inlet, bit for bit -----------------------------------------------------------------
@@ -141,10 +62,10 @@ def test_profiles_against_the_oracle(lbm, name):
         u = reversed_near_bottom(ny, 0.05)
         mask = masks(nx, ny)["inlet-outlet"]
         assert np.min(u) < 0
-    f_ref, rho_ref, ux_ref, uy_ref, forces_ref, bad_ref = oracle_profile_run(nx, ny, u, steps, of, mask=mask, **kw)
-    assert bad_ref == -1
+    ref = oracle_run(nx, ny, steps, of, mask=mask, u=u, **kw)
+    assert ref.first_unstable == -1
     fluid0 = np.ones(ny, bool) if mask is None else mask[:, 0] == 0
-    assert np.array_equal(ux_ref[fluid0, 0], u[fluid0])
+    assert np.array_equal(ref.ux[fluid0, 0], u[fluid0])
     seen = {}
     for plan in ORACLE_PLANS:
         with lbm.Context(nx, ny, options=PLANS[plan], solid=mask, inlet_profile=u, **kw) as ctx:
@@ -158,20 +79,20 @@ def test_profiles_against_the_oracle(lbm, name):
             fn = ctx.populations("f_next")
             rho, ux, uy = ctx.macros()
         assert np.array_equal(ux[fluid0, 0], u[fluid0]), plan       # the inlet column reports u[y]
-        assert [r[0] for r in log] == [r[0] for r in forces_ref]
-        for (t, fx, fy), (_, rx, ry) in zip(log, forces_ref):
+        assert [r[0] for r in log] == [r[0] for r in ref.forces]
+        for (t, fx, fy), (_, rx, ry) in zip(log, ref.forces):
             assert abs(fx - rx) <= 1e-10 * max(1.0, abs(rx)) and abs(fy - ry) <= 1e-10 * max(1.0, abs(ry)), (plan, t)
         key = "strict" if strict(plan) else "fast"
         seen.setdefault(key, fn)
         assert np.array_equal(fn, seen[key]), plan      # every plan of one arithmetic mode: the same bits
-        scale = float(np.max(np.abs(f_ref)))
+        scale = float(np.max(np.abs(ref.f_next)))
         if key == "strict":
-            assert np.array_equal(fn, f_ref), plan
-            assert float(np.max(np.abs(rho - rho_ref))) <= 1e-14, plan
+            assert np.array_equal(fn, ref.f_next), plan
+            assert float(np.max(np.abs(rho - ref.rho))) <= 1e-14, plan
         else:
-            assert float(np.max(np.abs(fn - f_ref))) <= 1e-10 * scale, plan
-        uscale = float(np.max(np.sqrt(ux_ref ** 2 + uy_ref ** 2)))
-        assert float(np.max(np.abs(ux - ux_ref))) <= 1e-10 * uscale and float(np.max(np.abs(uy - uy_ref))) <= 1e-10 * uscale, plan
+            assert float(np.max(np.abs(fn - ref.f_next))) <= 1e-10 * scale, plan
+        uscale = float(np.max(np.sqrt(ref.ux ** 2 + ref.uy ** 2)))
+        assert float(np.max(np.abs(ux - ref.ux))) <= 1e-10 * uscale and float(np.max(np.abs(uy - ref.uy))) <= 1e-10 * uscale, plan
 
 
 # ---- 3. strips ---------------------------------------------------------------------------------------------------------------
@@ -189,21 +110,12 @@ def test_group_strips_with_a_profile(lbm, plan, nstrips):
     nx, ny, steps, of = 320, 100, 131, 45
     kw = dict(inlet_velocity=0.06)
     u = wavy(ny, 0.06)
-    with lbm.Context(nx, ny, options=PLANS[plan], inlet_profile=u, **kw) as whole:
-        whole.initialise()
-        whole.step(steps, of)
-        w = (whole.macros(), whole.populations("f_next"), whole.drain_force_log())
+    w = whole_run(lbm, nx, ny, plan, steps, of, inlet_profile=u, **kw)
     with lbm.Group(nx, ny, nstrips, options=PLANS[plan], inlet_profile=u, **kw) as g:
         g.initialise()
         g.step(steps, of)
         assert g.first_unstable_step() == -1
-        for a, b in zip(g.macros(), w[0]):
-            assert np.array_equal(a, b)
-        assert np.array_equal(g.populations("f_next"), w[1])
-        log = g.drain_force_log()
-        assert [r[0] for r in log] == [r[0] for r in w[2]]
-        for (t, fx, fy), (_, wx, wy) in zip(log, w[2]):
-            assert abs(fx - wx) <= 1e-13 * max(1.0, abs(wx)) and abs(fy - wy) <= 1e-13 * max(1.0, abs(wy))
+        assert_group_is_whole(g, w)
 
 
 @pytest.mark.parametrize("plan", [None, "rowil-col5-nt"])
@@ -215,25 +127,7 @@ def test_host_staged_strips_with_a_profile(lbm, plan):
         whole.initialise()
         whole.step(48, 0)
         w_fn = whole.populations("f_next")
-    ctxs = [lbm.Context(nx, ny, y_start=y0, local_ny=128, options=PLANS[plan] if plan else None, inlet_profile=u, **kw)
-            for y0 in (0, 128)]
-    try:
-        for c in ctxs:
-            c.initialise()
-
-        def exchange():
-            lo, hi = ctxs[0].halo_export(south=False, north=True), ctxs[1].halo_export(south=True, north=False)
-            ctxs[0].halo_import(south=None, north=hi[0])
-            ctxs[1].halo_import(south=lo[1], north=None)
-        exchange()
-        for _ in range(12):
-            for c in ctxs:
-                c.step(4, 0)
-            exchange()
-        parts = [c.populations("f_next") for c in ctxs]
-    finally:
-        for c in ctxs:
-            c.close()
+    parts, _ = host_staged_two_strips(lbm, nx, ny, 12, 4, PLANS[plan] if plan else None, inlet_profile=u, **kw)
     assert np.array_equal(parts[0][1:129], w_fn[1:129]) and np.array_equal(parts[1][1:129], w_fn[129:257])
 
 
@@ -377,12 +271,6 @@ def test_set_inlet_profile_arguments(lbm):
 
 
 # ---- 8. the host CLI ---------------------------------------------------------------------------------------------------------
-def read_velocity_field(path, nx, ny):
-    d = np.loadtxt(path, delimiter=",", skiprows=1)
-    assert d.shape == (nx * ny, 6)
-    return d[:, 2].reshape(ny, nx), d[:, 3].reshape(ny, nx), d[:, 4].reshape(ny, nx)
-
-
 @pytest.mark.parametrize("extra", [["--gpus", "1"], ["--gpus", "1", "--strips", "3"]])
 @pytest.mark.parametrize("source", ["parabolic", "file"])
 def test_lbm_solver_inlet_profile_matches_the_binding(lbm, tmp_path, source, extra):
@@ -390,19 +278,17 @@ def test_lbm_solver_inlet_profile_matches_the_binding(lbm, tmp_path, source, ext
     mean = 0.04
     mask = np.zeros((ny, nx), np.uint8)
     mask[18:30, 30:42] = 1                    # square, frontal height D = 12
-    write_pgm(tmp_path / "sq.pgm", mask)
+    write_pgm(tmp_path / "sq.pgm", mask * 255)
     if source == "parabolic":
         spec, u = "parabolic", lbm.parabolic_profile(ny, mean)
     else:
         shape = 1.0 + 0.5 * np.cos(np.arange(ny) * 0.3)
         (tmp_path / "shape.txt").write_text("# a shape\n" + "\n".join(repr(float(v)) for v in shape) + "\n")
         spec, u = str(tmp_path / "shape.txt"), lbm.scale_inlet_profile(shape, mean)
-    cmd = [EXE, "--nx", str(nx), "--ny", str(ny), "--steps", str(steps), "--output-frequency", str(of), "--inlet-velocity", str(mean),
-           "--no-vtk", "--obstacle-mask", str(tmp_path / "sq.pgm"), "--inlet-profile", spec] + extra
-    pr = subprocess.run(cmd, cwd=tmp_path, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
-    assert pr.returncode == 0, pr.stderr
+    pr = run_solver(["--nx", str(nx), "--ny", str(ny), "--steps", str(steps), "--output-frequency", str(of), "--inlet-velocity", str(mean),
+                     "--no-vtk", "--obstacle-mask", str(tmp_path / "sq.pgm"), "--inlet-profile", spec] + extra, tmp_path)
     assert "Inlet: profile" in pr.stdout
-    rows = [l.split(",") for l in open(tmp_path / "forces.csv").read().splitlines()[1:]]
+    rows = read_csv_rows(tmp_path / "forces.csv")
     with lbm.Context(nx, ny, inlet_velocity=mean, solid=mask, inlet_profile=u) as ctx:
         ctx.initialise()
         ctx.step(steps, of)
@@ -417,7 +303,7 @@ def test_lbm_solver_inlet_profile_matches_the_binding(lbm, tmp_path, source, ext
     assert np.max(np.abs(cux[:, 0] - u)) <= 5.1e-9           # the inlet column is the profile (8 decimals)
     for got, want in ((cux, ux), (cuy, uy), (crho, rho)):
         assert np.max(np.abs(got - want)) <= 5.1e-9
-    params = dict(l.split(",", 1) for l in open(tmp_path / "simulation_params.csv").read().splitlines()[1:])
+    params = read_params(tmp_path / "simulation_params.csv")
     assert params["inlet_profile"] == spec and params["obstacle_mask"].endswith("sq.pgm")
     assert abs(float(params["inlet_velocity"]) - mean) < 1e-12
     keys = list(params)

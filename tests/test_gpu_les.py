@@ -1,129 +1,19 @@
 """Smagorinsky LES collision (lbm_set_smagorinsky, Context/Group(smagorinsky=...), lbm_solver --smagorinsky) on the GPU.
 
-The reference operator is les_collide below: numpy, fp64, IEEE, in the operation order the library's strict arithmetic evaluates
-(lbm_kernels.hpp les_tau_inv_strict). It replaces o.collide() in the stepwise oracle loop, the way test_gpu_inlet_profile.py patches
-the inlet; oracle/ is untouched. Strict plans must match it bit for bit, contracted ones within 1e-10."""
+The reference operator is les_collide of tests/reference.py: numpy, fp64, IEEE, in the operation order the library's strict arithmetic
+evaluates (lbm_kernels.hpp les_tau_inv_strict). It replaces o.collide() in the stepwise oracle loop (oracle_run there); oracle/ is
+untouched. Strict plans must match it bit for bit, contracted ones within 1e-10."""
 import functools
 import importlib
-import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from oracle.oracle import Oracle, make_params
-from tests.helpers import record
-from tests.test_gpu_geometry import ORACLE_PLANS, link_forces, square
-from tests.test_gpu_inlet_profile import feq_rows
-from tests.test_gpu_parity import PLANS, strict
+from tests.helpers import (ORACLE_PLANS, PKG, PLANS, assert_group_is_whole, host_staged_two_strips, lbm_gpu, read_csv_rows, read_params,  # noqa: F401
+                           read_velocity_field, record, run_solver, square, strict, whole_run)
+from tests.reference import les_collide, oracle_run
 
 pytestmark = pytest.mark.gpu
-PKG = "highperformancecomputing-latticeboltzmannmethod_amd"
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, PKG, "host", "lbm_solver")
-CX = [0, 1, 0, -1, 0, 1, -1, -1, 1]
-CY = [0, 0, 1, 0, -1, 1, 1, -1, -1]
-W = [4.0 / 9.0] + [1.0 / 9.0] * 4 + [1.0 / 36.0] * 4
-
-
-@pytest.fixture(scope="module")
-def lbm():
-    pkg = importlib.import_module(PKG)
-    assert pkg.device_count() >= 1, "no HIP device: the product path has no CPU fallback"
-    return pkg
-
-
-def les_collide(o, tau, cs):
-    """lbmo_collide with the Smagorinsky relaxation time of each fluid cell: f_next = f - (1/tau_eff)(f - feq) on the interior,
-    rho / ux / uy recorded as the oracle does. Returns the largest tau_eff."""
-    tau2, c = tau * tau, 18.0 * math.sqrt(2.0) * (cs * cs)
-    fluid = ~o.solid.astype(bool)
-    f = [o.f_current[1:-1, 1:-1, i][fluid] for i in range(9)]
-    r = np.zeros_like(f[0]); vx = np.zeros_like(f[0]); vy = np.zeros_like(f[0])
-    for i in range(9):                        # lbm_oracle.c: r += f_i; vx += cx_i f_i; vy += cy_i f_i, i ascending
-        r = r + f[i]
-        vx = vx + float(CX[i]) * f[i]
-        vy = vy + float(CY[i]) * f[i]
-    vx = vx / r
-    vy = vy / r
-    sxx = ((((f[1] + f[3]) + f[5]) + f[6]) + f[7]) + f[8]
-    syy = ((((f[2] + f[4]) + f[5]) + f[6]) + f[7]) + f[8]
-    sxy = ((f[5] - f[6]) + f[7]) - f[8]
-    pxx = (sxx - r * (vx * vx)) - r * (1.0 / 3.0)
-    pyy = (syy - r * (vy * vy)) - r * (1.0 / 3.0)
-    pxy = sxy - r * (vx * vy)
-    with np.errstate(invalid="ignore"):       # (a diverging run reaches NaN; the stability test then ends it)
-        qn = np.sqrt((pxx * pxx + pyy * pyy) + 2.0 * (pxy * pxy))
-        tau_eff = 0.5 * (tau + np.sqrt(tau2 + c * (qn / r)))
-    tinv = 1.0 / tau_eff
-    usq = vx * vx + vy * vy
-    inner = o.f_next[1:-1, 1:-1]
-    for i in range(9):
-        cu = float(CX[i]) * vx + float(CY[i]) * vy
-        feq = W[i] * r * (((1.0 + 3.0 * cu) + (4.5 * cu) * cu) - 1.5 * usq)
-        col = inner[:, :, i]
-        col[fluid] = f[i] - tinv * (f[i] - feq)
-        inner[:, :, i] = col
-    o.rho[fluid] = r
-    o.ux[fluid] = vx
-    o.uy[fluid] = vy
-    return float(np.max(tau_eff)) if tau_eff.size else tau
-
-
-def oracle_les_run(nx, ny, steps, of, cs, mask=None, u=None, **kw):
-    """The stepwise oracle with les_collide (and, where u is given, the per-row inlet of test_gpu_inlet_profile.py):
-    (f_next, rho, ux, uy, forces [(t, fx, fy)], first unstable step, largest tau_eff)."""
-    o = Oracle(make_params(nx, ny, **kw))
-    if mask is not None:
-        o.solid[:] = mask
-    o.L.lbmo_initialise(o.h)
-    solid = o.solid.astype(bool).copy()
-    fluid = ~solid
-    if u is not None:
-        fr = feq_rows(u)
-        for arr in (o.f_current, o.f_next):
-            inner = arr[1:-1, 1:-1]
-            inner[fluid] = np.broadcast_to(fr[:, None, :], (ny, nx, 9))[fluid]
-        o.ux[fluid] = np.broadcast_to(np.asarray(u)[:, None], (ny, nx))[fluid]
-        rows = np.nonzero(fluid[:, 0])[0]
-        ur = np.asarray(u, dtype=np.float64)[rows]
-    tau = o.p.tau
-    forces, bad, tmax = [], -1, tau
-    for t in range(steps):
-        tmax = max(tmax, les_collide(o, tau, cs))
-        if of and t % of == 0:
-            forces.append((t,) + link_forces(o.f_next, solid))
-        o.exchange_physical()
-        o.stream()
-        o.boundaries()
-        if u is not None:     # test_gpu_inlet_profile.py oracle_profile_run, operation for operation
-            f = o.f_current[rows + 1, 1, :]
-            rho_bc = (f[:, 0] + f[:, 2] + f[:, 4] + 2.0 * (f[:, 3] + f[:, 6] + f[:, 7])) / (1.0 - ur)
-            f[:, 1] = f[:, 3] + (2.0 / 3.0) * rho_bc * ur
-            f[:, 5] = f[:, 7] - 0.5 * (f[:, 2] - f[:, 4]) + (1.0 / 6.0) * rho_bc * ur
-            f[:, 8] = f[:, 6] + 0.5 * (f[:, 2] - f[:, 4]) + (1.0 / 6.0) * rho_bc * ur
-            o.f_current[rows + 1, 1, :] = f
-            o.rho[rows, 0] = rho_bc
-            o.ux[rows, 0] = ur
-        if not o.stable():
-            bad = t
-            break
-    out = (o.f_next.copy(), o.rho.copy(), o.ux.copy(), o.uy.copy(), forces, bad, tmax)
-    o.close()
-    return out
-
-
-def oracle_bgk_first_unstable(nx, ny, steps, **kw):
-    o = Oracle(make_params(nx, ny, **kw))
-    o.L.lbmo_initialise(o.h)
-    bad = -1
-    for t in range(steps):
-        if not o.step():
-            bad = t
-            break
-    o.close()
-    return bad
 
 
 # ---- 1 / 2. every plan against the reference ----------------------------------------------------------------------------------
@@ -143,35 +33,35 @@ def case_inputs(name, lbm):
 def reference(name):
     lbm = importlib.import_module(PKG)
     mask, u = case_inputs(name, lbm)
-    return oracle_les_run(NX, NY, STEPS, OF, CS, mask=mask, u=u, **KW)
+    return oracle_run(NX, NY, STEPS, OF, mask=mask, u=u, collide=functools.partial(les_collide, cs=CS), **KW)
 
 
 @pytest.mark.parametrize("plan", ALL_PLANS)
 @pytest.mark.parametrize("name", CASES)
 def test_les_against_the_reference(lbm, name, plan):
     mask, u = case_inputs(name, lbm)
-    f_ref, rho_ref, ux_ref, uy_ref, forces_ref, bad_ref, tmax = reference(name)
-    assert bad_ref == -1
-    assert tmax - KW["tau"] > 1e-3, tmax          # the model is active: the test cannot pass with LES doing nothing
+    ref = reference(name)
+    assert ref.first_unstable == -1
+    assert ref.tau_max - KW["tau"] > 1e-3, ref.tau_max          # the model is active: the test cannot pass with LES doing nothing
     with lbm.Context(NX, NY, options=PLANS[plan], solid=mask, inlet_profile=u, smagorinsky=CS, **KW) as ctx:
         ctx.initialise()
         ctx.step(STEPS, OF)
-        assert ctx.first_unstable_step() == bad_ref
+        assert ctx.first_unstable_step() == ref.first_unstable
         log = ctx.drain_force_log()
         fn = ctx.populations("f_next")
         rho, ux, uy = ctx.macros()
         assert ctx.kernel_name().endswith((",2>", ",3>")), ctx.kernel_name()
-    assert [r[0] for r in log] == [r[0] for r in forces_ref]
+    assert [r[0] for r in log] == [r[0] for r in ref.forces]
     if strict(plan):
-        assert np.array_equal(fn, f_ref), plan
-        assert float(np.max(np.abs(rho - rho_ref))) <= 1e-14, plan      # (the macro snapshot: the bars of test_gpu_inlet_profile.py)
+        assert np.array_equal(fn, ref.f_next), plan
+        assert float(np.max(np.abs(rho - ref.rho))) <= 1e-14, plan      # (the macro snapshot: the bars of test_gpu_inlet_profile.py)
     else:
-        scale = float(np.max(np.abs(f_ref)))
-        assert float(np.max(np.abs(fn - f_ref))) <= 1e-10 * scale, plan
-        assert float(np.max(np.abs(rho - rho_ref))) <= 1e-10, plan
+        scale = float(np.max(np.abs(ref.f_next)))
+        assert float(np.max(np.abs(fn - ref.f_next))) <= 1e-10 * scale, plan
+        assert float(np.max(np.abs(rho - ref.rho))) <= 1e-10, plan
     # the contracted bar, 1e-10 (tau 0.51 amplifies: 4.6e-11 measured on the parabolic inlet, where 1e-10 * max|u| would be 1.7e-11)
-    assert float(np.max(np.abs(ux - ux_ref))) <= 1e-10 and float(np.max(np.abs(uy - uy_ref))) <= 1e-10, plan
-    for (t, fx, fy), (_, rx, ry) in zip(log, forces_ref):
+    assert float(np.max(np.abs(ux - ref.ux))) <= 1e-10 and float(np.max(np.abs(uy - ref.uy))) <= 1e-10, plan
+    for (t, fx, fy), (_, rx, ry) in zip(log, ref.forces):
         assert abs(fx - rx) <= 1e-10 * max(1.0, abs(rx)) and abs(fy - ry) <= 1e-10 * max(1.0, abs(ry)), (plan, t)
 
 
@@ -207,13 +97,6 @@ def test_fp32_les_has_no_tall_regions(lbm):
 
 
 # ---- 3. invariance within a mode ----------------------------------------------------------------------------------------------
-def whole_run(lbm, nx, ny, plan, steps, of, **kw):
-    with lbm.Context(nx, ny, options=PLANS[plan], **kw) as whole:
-        whole.initialise()
-        whole.step(steps, of)
-        return whole.macros(), whole.populations("f_next"), whole.drain_force_log()
-
-
 @pytest.mark.parametrize("nstrips", [2, 3])
 @pytest.mark.parametrize("plan", ["rowil-col5-nt", "rowil-fuse3-12-nt-xcd", "fast-rowil-col6", "rowil-site-nt"])
 def test_group_strips_are_one_les_context(lbm, plan, nstrips):
@@ -224,13 +107,7 @@ def test_group_strips_are_one_les_context(lbm, plan, nstrips):
         g.initialise()
         g.step(steps, of)
         assert g.first_unstable_step() == -1
-        for a, b in zip(g.macros(), w[0]):
-            assert np.array_equal(a, b)
-        assert np.array_equal(g.populations("f_next"), w[1])
-        log = g.drain_force_log()
-        assert [r[0] for r in log] == [r[0] for r in w[2]]
-        for (t, fx, fy), (_, wx, wy) in zip(log, w[2]):
-            assert abs(fx - wx) <= 1e-13 * max(1.0, abs(wx)) and abs(fy - wy) <= 1e-13 * max(1.0, abs(wy))
+        assert_group_is_whole(g, w)
 
 
 @pytest.mark.parametrize("plan", [None, "rowil-col5-nt", "fast-rowil-col6"])
@@ -242,24 +119,7 @@ def test_host_staged_les_strips(lbm, plan):
         whole.initialise()
         whole.step(48, 0)
         w_fn = whole.populations("f_next")
-    ctxs = [lbm.Context(nx, ny, y_start=y0, local_ny=128, options=PLANS[plan] if plan else None, **kw) for y0 in (0, 128)]
-    try:
-        for c in ctxs:
-            c.initialise()
-
-        def exchange():
-            lo, hi = ctxs[0].halo_export(south=False, north=True), ctxs[1].halo_export(south=True, north=False)
-            ctxs[0].halo_import(south=None, north=hi[0])
-            ctxs[1].halo_import(south=lo[1], north=None)
-        exchange()
-        for _ in range(12):
-            for c in ctxs:
-                c.step(4, 0)
-            exchange()
-        parts = [c.populations("f_next") for c in ctxs]
-    finally:
-        for c in ctxs:
-            c.close()
+    parts, _ = host_staged_two_strips(lbm, nx, ny, 12, 4, PLANS[plan] if plan else None, **kw)
     assert np.array_equal(parts[0][1:129], w_fn[1:129]) and np.array_equal(parts[1][1:129], w_fn[129:257])
 
 
@@ -299,7 +159,7 @@ def first_unstable(lbm, cs, arith=0, steps=4000):
 
 
 def test_bgk_diverges_where_the_oracle_does(lbm):
-    want = oracle_bgk_first_unstable(400, 100, 4000, **STAB)
+    want = oracle_run(400, 100, 4000, 0, **STAB).first_unstable
     assert 0 <= want < 4000
     assert first_unstable(lbm, 0.0) == want
 
@@ -310,7 +170,7 @@ def test_les_017_is_stable(lbm, arith):
 
 
 def test_les_010_diverges_where_the_reference_does(lbm):
-    want = oracle_les_run(400, 100, 4000, 0, 0.10, **STAB)[5]
+    want = oracle_run(400, 100, 4000, 0, collide=functools.partial(les_collide, cs=0.10), **STAB).first_unstable
     assert 0 <= want < 4000
     record("les_stabilisation", first_unstable_les_010=want)
     assert first_unstable(lbm, 0.10) == want
@@ -378,22 +238,14 @@ def test_set_smagorinsky_arguments(lbm):
 
 
 # ---- 8. the host CLI -----------------------------------------------------------------------------------------------------------
-def read_velocity_field(path, nx, ny):
-    d = np.loadtxt(path, delimiter=",", skiprows=1)
-    assert d.shape == (nx * ny, 6)
-    return d[:, 2].reshape(ny, nx), d[:, 3].reshape(ny, nx), d[:, 4].reshape(ny, nx)
-
-
 @pytest.mark.parametrize("extra", [["--gpus", "1"], ["--gpus", "1", "--strips", "3"]])
 def test_lbm_solver_smagorinsky_matches_the_binding(lbm, tmp_path, extra):
     nx, ny, steps, of = 128, 48, 301, 100
     tau, u0 = 0.51, 0.08
-    cmd = [EXE, "--nx", str(nx), "--ny", str(ny), "--steps", str(steps), "--output-frequency", str(of), "--tau", str(tau),
-           "--inlet-velocity", str(u0), "--cylinder-radius", "0.1", "--no-vtk", "--smagorinsky", "0.17"] + extra
-    pr = subprocess.run(cmd, cwd=tmp_path, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
-    assert pr.returncode == 0, pr.stderr
+    pr = run_solver(["--nx", str(nx), "--ny", str(ny), "--steps", str(steps), "--output-frequency", str(of), "--tau", str(tau),
+                     "--inlet-velocity", str(u0), "--cylinder-radius", "0.1", "--no-vtk", "--smagorinsky", "0.17"] + extra, tmp_path)
     assert "Smagorinsky LES, Cs = 0.17" in pr.stdout
-    rows = [l.split(",") for l in open(tmp_path / "forces.csv").read().splitlines()[1:]]
+    rows = read_csv_rows(tmp_path / "forces.csv")
     with lbm.Context(nx, ny, tau=tau, inlet_velocity=u0, cylinder_radius=0.1, smagorinsky=0.17) as ctx:
         ctx.initialise()
         ctx.step(steps, of)
@@ -407,6 +259,6 @@ def test_lbm_solver_smagorinsky_matches_the_binding(lbm, tmp_path, extra):
     cux, cuy, crho = read_velocity_field(tmp_path / "velocity_field.csv", nx, ny)
     for got, want in ((cux, ux), (cuy, uy), (crho, rho)):
         assert np.max(np.abs(got - want)) <= 5.1e-9
-    params = dict(l.split(",", 1) for l in open(tmp_path / "simulation_params.csv").read().splitlines()[1:])
+    params = read_params(tmp_path / "simulation_params.csv")
     assert abs(float(params["smagorinsky_cs"]) - 0.17) < 1e-12
     assert abs(float(params["tau"]) - tau) < 1e-12

@@ -6,79 +6,16 @@ means "same SimulationParams".
 Tolerance (north_star): rho and u within 1e-10 relative (L-inf / L-inf; velocity components relative to
 max|u|), Fx/Fy within 1e-10 relative. Observed on MI355X: see DESIGN.md §parity.
 """
-import importlib
 import os
 
 import numpy as np
 import pytest
 
-from tests.helpers import ROOT, golden_params, linf_rel, load_golden, macro_errors, record
+from tests.helpers import (FAST, PKG, PLANS, ROOT, TALL_F32, golden_params, lbm_gpu, linf_rel, load_golden, macro_errors, record,  # noqa: F401
+                           strict)
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-10
-PKG = "highperformancecomputing-latticeboltzmannmethod_amd"
-
-
-@pytest.fixture(scope="module")
-def lbm():
-    pkg = importlib.import_module(PKG)
-    assert pkg.device_count() >= 1, "no HIP device: the product path has no CPU fallback"
-    return pkg
-
-
-# Every formulation the plan may pick (lbm_set_option, include/lbm_hip.h) computes the same per-cell arithmetic;
-# the parity tests run each of them explicitly. None = the measured plan (tune=1, the default).
-PLANS = {
-    "auto": None,
-    "planar-vec-alt": dict(tune=0, layout=0, nt=0, alternate=1),
-    "planar-site": dict(tune=0, layout=0, nt=0, alternate=0),
-    "rowil-site-nt": dict(tune=0, layout=1, nt=1, alternate=0),
-    "rowil-vec-nt-alt": dict(tune=0, layout=1, nt=1, alternate=1),
-    # two iterations fused per launch through LDS (k_step2_tile; partial tiles cover any nx)
-    "planar-pair8-nt": dict(tune=0, layout=0, nt=1, alternate=0, pair=1, pair_ty=8),
-    "rowil-pair12-alt": dict(tune=0, layout=1, nt=0, alternate=1, pair=1, pair_ty=12, xcd=1),
-    # three iterations fused per launch (k_step3_tile)
-    "planar-fuse3-8": dict(tune=0, layout=0, nt=0, alternate=1, fuse=3, pair_ty=8),
-    "rowil-fuse3-12-nt-xcd": dict(tune=0, layout=1, nt=1, alternate=0, fuse=3, pair_ty=12, xcd=1),
-    # four iterations fused per launch (k_step4_tile, 64x8 tiles; strips fall back to three)
-    "rowil-fuse4-nt-xcd": dict(tune=0, layout=1, nt=1, alternate=0, fuse=4, pair_ty=8, xcd=1),
-    "planar-fuse4-alt": dict(tune=0, layout=0, nt=0, alternate=1, fuse=4, pair_ty=8, xcd=0),
-    # six / seven / eight iterations per launch on an LDS-filling tile (k_stepd_tile; what a small grid's measurement picks);
-    # calls whose length is no multiple of the depth finish with the four-/three-/two-iteration tile kernels
-    "rowil-deep6-nt": dict(tune=0, layout=1, nt=1, alternate=0, pair_ty=12, xcd=1, deep=1),
-    "planar-deep7-alt": dict(tune=0, layout=0, nt=0, alternate=1, pair_ty=8, xcd=0, deep=2),
-    "rowil-deep8-nt": dict(tune=0, layout=1, nt=1, alternate=0, pair_ty=12, xcd=1, deep=3),
-    # five / six iterations per launch with the lattice held in registers (k_stepc_col: 64x32 regions, DPP x-shifts, six LDS
-    # values per wave and level; round 3's production kernel — what a large grid's measurement and the strip rule pick)
-    "rowil-col5-nt": dict(tune=0, layout=1, nt=1, alternate=0, pair_ty=12, xcd=1, deep=6),
-    "planar-col6-alt": dict(tune=0, layout=0, nt=0, alternate=1, pair_ty=8, xcd=1, deep=7),
-    # contracted collision arithmetic (option "arith" 1: FMA + one reciprocal, what the reference's -ffast-math -mfma build
-    # permits): not bit-identical to the strict oracle, held to the north-star tolerance 1e-10 like every other plan
-    "fast-auto": dict(arith=1),
-    "fast-site": dict(tune=0, layout=1, nt=1, alternate=0, fuse=1, arith=1),
-    "fast-vec-alt": dict(tune=0, layout=0, nt=0, alternate=1, fuse=1, arith=1),
-    "fast-rowil-fuse3-12-xcd": dict(tune=0, layout=1, nt=1, alternate=0, fuse=3, pair_ty=12, xcd=1, arith=1),
-    "fast-planar-pair8": dict(tune=0, layout=0, nt=0, alternate=1, pair=1, pair_ty=8, arith=1),
-    "fast-rowil-fuse4-xcd": dict(tune=0, layout=1, nt=1, alternate=0, fuse=4, pair_ty=8, xcd=1, arith=1),
-    "fast-rowil-deep7": dict(tune=0, layout=1, nt=1, alternate=0, pair_ty=12, xcd=1, deep=2, arith=1),
-    "fast-planar-deep8": dict(tune=0, layout=0, nt=0, alternate=0, pair_ty=8, xcd=1, deep=3, arith=1),
-    "fast-rowil-col6": dict(tune=0, layout=1, nt=1, alternate=0, pair_ty=12, xcd=1, deep=7, arith=1),
-    "fast-planar-col5": dict(tune=0, layout=0, nt=0, alternate=0, pair_ty=8, xcd=1, deep=6, arith=1),
-    # non-temporal level-1 loads in the register kernel (round 4: a store-policy-like choice of the plan measurement)
-    "rowil-col6-ntl-alt": dict(tune=0, layout=1, nt=0, ntl=1, alternate=1, pair_ty=12, xcd=1, deep=7),
-    "fast-rowil-col6-ntl": dict(tune=0, layout=1, nt=0, ntl=1, alternate=0, pair_ty=12, xcd=1, deep=7, arith=1),
-    # seven iterations as the plan's own depth (round 4: what the largest grids' measurement picks; strips exchange seven rows)
-    "rowil-col7-alt": dict(tune=0, layout=1, nt=0, alternate=1, pair_ty=12, xcd=1, deep=9),
-    "fast-rowil-col7": dict(tune=0, layout=1, nt=0, alternate=0, pair_ty=12, xcd=1, deep=9, arith=1),
-}
-FAST = [k for k, v in PLANS.items() if v and v.get("arith")]
-# fp32 contexts only (round 4): seven iterations per launch on TALL 64x48 regions in registers (contracted: twelve waves x four rows; strict: eight x six)
-TALL_F32 = dict(tune=0, layout=1, nt=0, alternate=1, pair_ty=12, xcd=1, deep=8)
-
-
-def strict(plan):
-    """True when the plan evaluates the oracle's operation sequence (populations bit-identical to it)."""
-    return plan not in FAST
 
 
 def fused_depth(plan_opts, steps_left, done, of):

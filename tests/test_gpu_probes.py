@@ -16,10 +16,8 @@ import subprocess
 import numpy as np
 import pytest
 
-from tests.test_gpu_parity import PLANS
-from tests.test_host_cpp import EXE
+from tests.helpers import EXE, PKG, PLANS
 
-PKG = "highperformancecomputing-latticeboltzmannmethod_amd"
 pytestmark = pytest.mark.gpu
 
 GRIDS = [(128, 32), (256, 64)]

@@ -9,10 +9,9 @@ import importlib
 import numpy as np
 import pytest
 
-from tests.helpers import macro_errors
+from tests.helpers import PKG, macro_errors
 
 pytestmark = pytest.mark.gpu
-PKG = "highperformancecomputing-latticeboltzmannmethod_amd"
 
 
 def cases(n=36, seed=20260104):

@@ -6,23 +6,13 @@ tolerance: every comparison between `split` 3 / 4 and `split` 0 on the same plan
 (events between the two streams) is what tests/test_choreography_split_cpu.py proves on the CPU; a missing dependency would show here
 as a mismatch that comes and goes. "split_min" 1 makes every deep launch a split one, however few lie ahead (by default a sequence of
 range launches starts only with eight launches ahead in its segment); the headline run at the end keeps the default."""
-import importlib
-
 import numpy as np
 import pytest
 
-from tests.helpers import linf_rel, load_golden, golden_params, macro_errors
+from tests.helpers import lbm_gpu, linf_rel, load_golden, golden_params, macro_errors  # noqa: F401
 
-PKG = "highperformancecomputing-latticeboltzmannmethod_amd"
 pytestmark = pytest.mark.gpu
 TOL = 1e-10
-
-
-@pytest.fixture(scope="module")
-def lbm():
-    pkg = importlib.import_module(PKG)
-    assert pkg.device_count() >= 1, "no HIP device: the product path has no CPU fallback"
-    return pkg
 
 
 COL6 = dict(tune=0, layout=1, pair_ty=12, xcd=1, deep=7)

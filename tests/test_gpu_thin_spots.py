@@ -8,10 +8,9 @@ import importlib
 import numpy as np
 import pytest
 
-from tests.helpers import macro_errors, record
+from tests.helpers import PKG, macro_errors, record
 
 pytestmark = pytest.mark.gpu
-PKG = "highperformancecomputing-latticeboltzmannmethod_amd"
 TOL = 1e-10      # north_star: rho / u within 1e-10 of the reference (L-inf / L-inf; u relative to max|u|)
 
 

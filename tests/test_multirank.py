@@ -11,8 +11,8 @@ import tempfile
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = "highperformancecomputing-latticeboltzmannmethod_amd"
+from tests.helpers import PKG, ROOT
+
 WORKER = os.path.join(ROOT, "tests", "_mr_worker.py")
 
 

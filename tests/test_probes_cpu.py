@@ -20,11 +20,8 @@ import pytest
 
 from tests import test_choreography_cpu as tc
 from tests import test_choreography_split_cpu as ts
-from tests.test_frames_cpu import FRAME_PLANS
-from tests.test_stats_cpu import STAT_CALLS, geometries, ops_of, sample_points
+from tests.helpers import FRAME_PLANS, PKG, ROOT, STAT_CALLS, geometries, ops_of, sample_points
 
-PKG = "highperformancecomputing-latticeboltzmannmethod_amd"
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LBM_ERR_ARG = -1
 PROBES_MAX = 65536
 dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int)

@@ -8,7 +8,8 @@ import random
 
 import pytest
 
-PKG = "highperformancecomputing-latticeboltzmannmethod_amd"
+from tests.helpers import PKG
+
 PUSH = -1
 CAPACITIES = (1, 2, 3, 7)
 

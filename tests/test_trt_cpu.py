@@ -2,26 +2,12 @@
 and refuses a bad value (or --smagorinsky beside it) before any device is touched, and the plan candidates of a TRT context name
 the TRT kernels and leave out the tall fp32 regions (which have no TRT instantiation)."""
 import ctypes
-import importlib
 import os
 import subprocess
 
 import pytest
 
-PKG = "highperformancecomputing-latticeboltzmannmethod_amd"
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, PKG, "host", "lbm_solver")
-
-
-@pytest.fixture(scope="module")
-def lbm():
-    return importlib.import_module(PKG)
-
-
-@pytest.fixture(scope="module")
-def solver():
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, PKG, "host")])
-    return EXE
+from tests.helpers import lbm_cpu, solver  # noqa: F401
 
 
 def test_library_exports_lbm_set_trt(lbm):
