@@ -85,6 +85,9 @@ def lib():
         L.lbm_set_inlet_profile.argtypes = [vp, dp, C.c_int]
         L.lbm_set_smagorinsky.argtypes = [vp, C.c_double]
         L.lbm_set_trt.argtypes = [vp, C.c_double]
+        L.lbm_set_wall.argtypes = [vp, C.c_int, C.c_int, C.c_double]
+        L.lbm_get_wall.argtypes = [vp, C.c_int, C.POINTER(C.c_int), dp]
+        L.lbm_debug_wall_rule.argtypes = [C.c_int, C.c_int, C.c_double, C.c_int, dp, dp]
         ip = C.POINTER(C.c_int)
         L.lbm_debug_geometry.argtypes = [C.POINTER(C.c_ubyte), C.c_int, C.c_int, C.c_int, C.c_int, ip, C.POINTER(C.c_ulonglong), C.c_long,
                                          ip, C.c_long, ip, C.c_int, ip]
@@ -277,6 +280,50 @@ def scale_inlet_profile(shape, mean):
     return u
 
 
+WALL_SIDES = {"south": 0, "north": 1}                          # LBM_WALL_SOUTH / LBM_WALL_NORTH
+WALL_KINDS = {"no-slip": 0, "free-slip": 1, "moving": 2}       # LBM_WALL_NOSLIP / LBM_WALL_FREESLIP / LBM_WALL_MOVING
+_WALL_NAMES = {v: k for k, v in WALL_KINDS.items()}
+
+
+def _wall_code(table, what, v):
+    """A side / kind given by name or by its LBM_WALL_* number -> the number (numbers pass through: the library checks their range)."""
+    if isinstance(v, str):
+        if v not in table:
+            raise ValueError(f"unknown wall {what} {v!r}: one of {sorted(table)}")
+        return table[v]
+    return int(v)
+
+
+def _wall_pair(walls):
+    """The walls= keyword as ((south kind, south velocity), (north kind, north velocity)): "free-slip" / "no-slip" for both walls, or a
+    pair (south, north) whose entries are "no-slip", "free-slip" or ("moving", u_w)."""
+    def one(w):
+        if isinstance(w, str):
+            if w == "moving":
+                raise ValueError('a moving wall is given as ("moving", u_w)')
+            return _wall_code(WALL_KINDS, "kind", w), 0.0
+        kind, u = w
+        return _wall_code(WALL_KINDS, "kind", kind), float(u)
+    if isinstance(walls, str):
+        return one(walls), one(walls)
+    south, north = walls
+    return one(south), one(north)
+
+
+def debug_wall_rule(side, kind, velocity, f9, precision="f64"):
+    """lbm_debug_wall_rule (no device): the kernels' wall rule on ONE cell. f9: the nine pulled populations; they are cast to the element
+    type, the rule of wall `side` ("south" / "north") with `kind` and `velocity` is applied, and the nine results come back as float64."""
+    a = np.ascontiguousarray(f9, dtype=np.float64)
+    if a.shape != (9,):
+        raise ValueError(f"a cell has nine populations, not shape {a.shape}")
+    out = np.empty(9, dtype=np.float64)
+    rc = lib().lbm_debug_wall_rule(_wall_code(WALL_SIDES, "side", side), _wall_code(WALL_KINDS, "kind", kind), float(velocity),
+                                   {"f64": 0, "f32": 1}[precision], _dp(a), _dp(out))
+    if rc < 0:
+        raise LbmError(f"lbm_hip error {rc}: {lib().lbm_last_error().decode()}")
+    return out
+
+
 def _dp(a):
     return a.ctypes.data_as(C.POINTER(C.c_double)) if a is not None else None
 
@@ -310,12 +357,14 @@ class Context:
     domain (0 fluid, 1..255; lbm_set_body_labels): the geometry of solid=(bodies != 0) plus forces per body (body_forces,
     drain_body_force_log); not together with solid. frames: optional stride k of coarsened flow frames (lbm_frames_begin with the
     default capacity at the end of initialise(); see frames_begin). probes: optional (n, 2) array of probe points (x, y) in GLOBAL lattice
-    coordinates (lbm_probes_begin with a ring of probe_capacity samples at the end of initialise(); see probes_begin)."""
+    coordinates (lbm_probes_begin with a ring of probe_capacity samples at the end of initialise(); see probes_begin). walls: optional
+    kinds of the bottom and top walls (lbm_set_wall) in place of the two no-slip walls: "free-slip" (both), or a pair (south, north) whose
+    entries are "no-slip", "free-slip" or ("moving", u_w) with the wall's tangential velocity u_w."""
 
     def __init__(self, nx, ny, tau=0.6, inlet_velocity=0.01333, cylinder_x=0.2, cylinder_y=0.5,
                  cylinder_radius=0.05, y_start=0, local_ny=0, precision="f64", device=0, force_log_capacity=0,
                  options=None, solid=None, inlet_profile=None, smagorinsky=None, bodies=None, frames=None, trt_magic=None,
-                 probes=None, probe_capacity=None):
+                 probes=None, probe_capacity=None, walls=None):
         if solid is not None and bodies is not None:
             raise LbmError("solid= and bodies= exclude each other: the body labels are the geometry (solid where nonzero)")
         self.L = lib()
@@ -343,6 +392,9 @@ class Context:
             self.set_trt(trt_magic)
         if frames is not None:
             self.set_option("frames", frames)
+        if walls is not None:
+            for side, (kind, u) in zip(("south", "north"), _wall_pair(walls)):
+                self.set_wall(side, kind, u)
 
     def _chk(self, rc):
         if rc < 0:
@@ -413,6 +465,21 @@ class Context:
     def set_trt(self, magic):
         """lbm_set_trt: the TRT magic parameter (tau - 1/2)(tau_minus - 1/2) in [0, 1] (0: plain BGK); before initialise()."""
         self._chk(self.L.lbm_set_trt(self.h, float(magic)))
+
+    def set_wall(self, side, kind, velocity=0.0):
+        """lbm_set_wall: side "south" (row 0) / "north" (row ny - 1); kind "no-slip" / "free-slip" / "moving" with the wall's tangential
+        velocity (0 for the other kinds; "no-slip" clears a wall); before initialise()."""
+        self._chk(self.L.lbm_set_wall(self.h, _wall_code(WALL_SIDES, "side", side), _wall_code(WALL_KINDS, "kind", kind), float(velocity)))
+
+    def get_wall(self, side):
+        """(kind name, velocity) of one wall (lbm_get_wall)."""
+        k, u = C.c_int(), C.c_double()
+        self._chk(self.L.lbm_get_wall(self.h, _wall_code(WALL_SIDES, "side", side), C.byref(k), C.byref(u)))
+        return _WALL_NAMES[k.value], u.value
+
+    def walls(self):
+        """((south kind, velocity), (north kind, velocity)) as set; (("no-slip", 0.0), ("no-slip", 0.0)) on a fresh context."""
+        return self.get_wall("south"), self.get_wall("north")
 
     def initialise(self):
         n = C.c_int()
@@ -640,11 +707,11 @@ class Group:
     """n strips of one lattice driven in lockstep by this process (lbm_group_*): one Context per strip, bottom to top.
     transport: "peer" (device copies / hipMemcpyPeerAsync) or "rccl" (ncclCommInitAll; distinct devices).
     solid: optional global (ny, nx) obstacle mask, inlet_profile: optional global [ny] inlet velocities, smagorinsky: optional LES
-    constant Cs, trt_magic: optional TRT magic parameter, bodies: optional global (ny, nx) body numbers (in place of solid), frames: optional frame stride k, probes / probe_capacity: optional probe points (global coordinates); all given to every
-    member."""
+    constant Cs, trt_magic: optional TRT magic parameter, bodies: optional global (ny, nx) body numbers (in place of solid), frames: optional frame stride k, probes / probe_capacity: optional probe points (global coordinates), walls: optional kinds of the
+    bottom and top walls (as Context takes them); all given to every member."""
 
     def __init__(self, nx, ny, bounds, devices=None, transport="peer", options=None, solid=None, inlet_profile=None, smagorinsky=None,
-                 bodies=None, frames=None, trt_magic=None, probes=None, probe_capacity=None, **kw):
+                 bodies=None, frames=None, trt_magic=None, probes=None, probe_capacity=None, walls=None, **kw):
         from .strips import partition_rows
         if isinstance(bounds, int):
             bounds = partition_rows(ny, bounds)
@@ -652,7 +719,7 @@ class Group:
         self.nx, self.ny = nx, ny
         self.ctxs = [Context(nx, ny, y_start=y0, local_ny=n, device=d, options=options, solid=solid, inlet_profile=inlet_profile,
                              smagorinsky=smagorinsky, bodies=bodies, frames=frames, trt_magic=trt_magic, probes=probes,
-                             probe_capacity=probe_capacity, **kw)
+                             probe_capacity=probe_capacity, walls=walls, **kw)
                      for (y0, n), d in zip(bounds, devices)]
         self.L = lib()
         self._arr = (C.c_void_p * len(self.ctxs))(*[c.h for c in self.ctxs])

@@ -335,6 +335,11 @@ struct lbm_ctx {
     bool has_profile = false;
     unsigned long long prof_digest = 0;
     void* d_feqrow = nullptr;
+    // The two physical walls (lbm_set_wall), [0] south (global row 0) and [1] north (row ny - 1): kind (lbm_kernels.hpp WallKind) and the
+    // tangential velocity of a moving wall, 0 otherwise. Every strip of a run carries both; one that holds neither wall row never uses them.
+    int wall_kind[2] = {0, 0};
+    double wall_u[2] = {0.0, 0.0};
+    bool has_walls() const { return wall_kind[0] != 0 || wall_kind[1] != 0; }
     // options
     int alternate = 1;   // walk the rows bottom-up / top-down on alternate steps (Infinity Cache reuse)
     int use_nt = 0;      // non-temporal stores in the step kernel

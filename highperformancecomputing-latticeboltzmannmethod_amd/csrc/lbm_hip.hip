@@ -82,11 +82,13 @@ int upload_rows(const lbm_ctx* c, void* dst, const double* v, size_t n) {
 // ---- checkpoint / restart (the reference keeps its state in memory only) ------------------------
 // File: CkptHeader; in an "LBMCKPT3" file a 64-bit word of flags; the fields the flags announce, in the order of their bits (bit 0: the
 // obstacle mask's 64-bit digest, bit 1: the inlet profile's, then one double per collision model that has a parameter — ckpt_bit in
-// collision_models, lbm_plan.hpp: bit 2 Cs, bit 3 the TRT magic parameter); then the post-collision populations P_{steps_done} of the
+// collision_models, lbm_plan.hpp: bit 2 Cs, bit 3 the TRT magic parameter — then bit 4: the two walls of lbm_set_wall as four doubles,
+// south kind, south velocity, north kind, north velocity, written only where a wall is not no-slip); then the post-collision populations P_{steps_done} of the
 // strip's interior, [9][local_ny][nx] in the element type. The state is complete: ghost cells and solid cells are reconstructed by
-// lbm_initialise. A context with neither profile nor collision parameter writes "LBMCKPT2" (header, mask digest, populations) if it has a
+// lbm_initialise. A context with neither profile nor collision parameter nor such a wall writes "LBMCKPT2" (header, mask digest, populations) if it has a
 // mask and "LBMCKPT1" (header, populations) otherwise. A context loads only a file that announces exactly what it has, with equal values.
 namespace {
+constexpr unsigned long long CKPT_WALLS = 16;   // LBMCKPT3 flag bit 4: the two walls follow the collision parameters
 struct CkptHeader {
     char magic[8];
     int nx, ny, y_start, local_ny, precision, steps_done;
@@ -155,6 +157,30 @@ int drain_force_rows(lbm_ctx* c, DeviceRing<double>& log, int B, Row* rows, int 
     return n;
 }
 }  // namespace
+
+// ---- the two walls (lbm_set_wall) ----
+namespace {
+const char* wall_kind_name(int kind) { return kind == LBM_WALL_NOSLIP ? "no-slip" : kind == LBM_WALL_FREESLIP ? "free-slip" : "moving"; }
+// the argument checks shared by lbm_set_wall and lbm_debug_wall_rule; the text names the offender
+int check_wall(const char* who, int side, int kind, double velocity) {
+    if (side != LBM_WALL_SOUTH && side != LBM_WALL_NORTH) return fail(LBM_ERR_ARG, "%s: side = %d (0 south or 1 north only)", who, side);
+    if (kind < LBM_WALL_NOSLIP || kind > LBM_WALL_MOVING) return fail(LBM_ERR_ARG, "%s: kind = %d (0 no-slip, 1 free-slip or 2 moving only)", who, kind);
+    if (!std::isfinite(velocity) || std::fabs(velocity) >= 1.0)
+        return fail(LBM_ERR_ARG, "%s: velocity = %g (finite values of magnitude below 1 only)", who, velocity);
+    if (kind != LBM_WALL_MOVING && velocity != 0.0)
+        return fail(LBM_ERR_ARG, "%s: velocity = %g with a %s wall (only a moving wall takes one)", who, velocity, wall_kind_name(kind));
+    return LBM_OK;
+}
+template <typename T>
+void debug_wall_rule(int side, int kind, double velocity, const double* in9, double* out9) {
+    T f[Q];
+    for (int i = 0; i < Q; ++i) f[i] = (T)in9[i];
+    wall_rule<T>(f, side == LBM_WALL_SOUTH, side == LBM_WALL_NORTH, side == LBM_WALL_SOUTH ? wall_pack(kind, 0) : wall_pack(0, kind),
+                 wall_ks<T>(kind, velocity, kind, velocity));
+    for (int i = 0; i < Q; ++i) out9[i] = (double)f[i];
+}
+}  // namespace
+
 
 extern "C" {
 
@@ -779,6 +805,23 @@ int lbm_set_trt(lbm_ctx* c, double magic) {
     return set_collision(c, AR_STRICT_TRT, magic, "lbm_set_trt: magic parameter", true);
 }
 
+int lbm_set_wall(lbm_ctx* c, int side, int kind, double velocity) {
+    if (!c) return fail(LBM_ERR_ARG, "lbm_set_wall: null context");
+    if (c->initialised) return fail(LBM_ERR_ARG, "lbm_set_wall must be called before lbm_initialise");
+    if (int rc = check_wall("lbm_set_wall", side, kind, velocity)) return rc;
+    c->wall_kind[side] = kind;
+    c->wall_u[side] = kind == LBM_WALL_MOVING ? velocity : 0.0;
+    return LBM_OK;
+}
+
+int lbm_get_wall(const lbm_ctx* c, int side, int* kind, double* velocity) {
+    if (!c) return fail(LBM_ERR_ARG, "lbm_get_wall: null context");
+    if (side != LBM_WALL_SOUTH && side != LBM_WALL_NORTH) return fail(LBM_ERR_ARG, "lbm_get_wall: side = %d (0 south or 1 north only)", side);
+    if (kind) *kind = c->wall_kind[side];
+    if (velocity) *velocity = c->wall_u[side];
+    return LBM_OK;
+}
+
 int lbm_comm_unique_id(void* id128) {
     if (!id128) return fail(LBM_ERR_ARG, "null argument");
     static_assert(sizeof(ncclUniqueId) == 128, "ncclUniqueId is 128 bytes");
@@ -958,19 +1001,23 @@ int lbm_save_state(lbm_ctx* c, const char* path) {
     if (!fp) return fail(LBM_ERR_ARG, "cannot open %s for writing", path);
     CkptHeader h{};
     const CollisionModel& cm = collision_model(c->collision);
-    const bool v3 = c->has_profile || cm.ckpt_bit;
+    const bool v3 = c->has_profile || cm.ckpt_bit || c->has_walls();
     memcpy(h.magic, v3 ? "LBMCKPT3" : c->has_mask ? "LBMCKPT2" : "LBMCKPT1", 8);
     h.nx = c->nx; h.ny = c->p.ny; h.y_start = c->p.y_start; h.local_ny = c->nyl; h.precision = c->p.precision;
     h.steps_done = c->steps_done; h.tau = c->p.tau; h.inlet_velocity = c->p.inlet_velocity;
     h.cylinder_x = c->p.cylinder_x; h.cylinder_y = c->p.cylinder_y; h.cylinder_radius = c->p.cylinder_radius;
     int rc = fwrite(&h, sizeof(h), 1, fp) == 1 ? LBM_OK : fail(LBM_ERR_ARG, "short write");
     if (!rc && v3) {   // flags, then what they announce
-        const unsigned long long flags = (c->has_mask ? 1ull : 0ull) | (c->has_profile ? 2ull : 0ull) | cm.ckpt_bit;
+        const unsigned long long flags = (c->has_mask ? 1ull : 0ull) | (c->has_profile ? 2ull : 0ull) | cm.ckpt_bit | (c->has_walls() ? CKPT_WALLS : 0ull);
         if (fwrite(&flags, sizeof(flags), 1, fp) != 1) rc = fail(LBM_ERR_ARG, "short write");
     }
     if (!rc && c->has_mask && fwrite(&c->hmask.digest, sizeof(c->hmask.digest), 1, fp) != 1) rc = fail(LBM_ERR_ARG, "short write");
     if (!rc && c->has_profile && fwrite(&c->prof_digest, sizeof(c->prof_digest), 1, fp) != 1) rc = fail(LBM_ERR_ARG, "short write");
     if (!rc && cm.ckpt_bit && fwrite(&c->collision_param, sizeof(c->collision_param), 1, fp) != 1) rc = fail(LBM_ERR_ARG, "short write");
+    if (!rc && c->has_walls()) {
+        const double w[4] = {(double)c->wall_kind[0], c->wall_u[0], (double)c->wall_kind[1], c->wall_u[1]};
+        if (fwrite(w, sizeof(w), 1, fp) != 1) rc = fail(LBM_ERR_ARG, "short write");
+    }
     if (!rc) rc = DISPATCH(c, do_save<double>(c, fp), do_save<float>(c, fp));
     fclose(fp);
     return rc;
@@ -996,7 +1043,8 @@ int lbm_load_state(lbm_ctx* c, const char* path) {
     unsigned long long digest = 0, flags = 0, pdigest = 0;
     constexpr int NM = (int)std::size(collision_models);
     double param[NM] = {};             // the parameter of each model the file announces
-    unsigned long long known = 3;
+    double walls[4] = {0.0, 0.0, 0.0, 0.0};   // {south kind, south velocity, north kind, north velocity} of the file; none: no-slip
+    unsigned long long known = 3 | CKPT_WALLS;
     for (const CollisionModel& m : collision_models) known |= m.ckpt_bit;
     const bool head = fread(&h, sizeof(h), 1, fp) == 1;
     const bool v1 = head && memcmp(h.magic, "LBMCKPT1", 8) == 0;
@@ -1004,9 +1052,17 @@ int lbm_load_state(lbm_ctx* c, const char* path) {
     bool v3 = head && memcmp(h.magic, "LBMCKPT3", 8) == 0 && fread(&flags, sizeof(flags), 1, fp) == 1 && (flags & ~known) == 0 &&
               (!(flags & 1) || fread(&digest, sizeof(digest), 1, fp) == 1) && (!(flags & 2) || fread(&pdigest, sizeof(pdigest), 1, fp) == 1);
     for (int i = 0; i < NM; ++i) v3 = v3 && (!(flags & collision_models[i].ckpt_bit) || fread(&param[i], sizeof(double), 1, fp) == 1);
-    const bool f_mask = v2 || (v3 && (flags & 1)), f_prof = v3 && (flags & 2);
+    v3 = v3 && (!(flags & CKPT_WALLS) || fread(walls, sizeof(walls), 1, fp) == 1);
+    const bool f_mask = v2 || (v3 && (flags & 1)), f_prof = v3 && (flags & 2), f_walls = v3 && (flags & CKPT_WALLS);
     if (!v1 && !v2 && !v3) rc = fail(LBM_ERR_ARG, "%s is not a checkpoint", path);
     else if ((rc = refuse_collision_mismatch(c, path, v3 ? flags : 0, param))) {}
+    else if (!f_walls && c->has_walls()) rc = fail(LBM_ERR_ARG, "checkpoint %s was written with two no-slip walls; this context has a %s south wall and a %s north wall",
+                                                   path, wall_kind_name(c->wall_kind[0]), wall_kind_name(c->wall_kind[1]));
+    else if (f_walls && !c->has_walls()) rc = fail(LBM_ERR_ARG, "checkpoint %s was written with wall kinds %g (south) and %g (north); this context has two no-slip walls",
+                                                   path, walls[0], walls[2]);
+    else if (f_walls && (walls[0] != (double)c->wall_kind[0] || walls[1] != c->wall_u[0] || walls[2] != (double)c->wall_kind[1] || walls[3] != c->wall_u[1]))
+        rc = fail(LBM_ERR_ARG, "checkpoint %s was written for different walls: south kind %g u = %.17g, north kind %g u = %.17g; this context has south kind %d u = %.17g, north kind %d u = %.17g",
+                  path, walls[0], walls[1], walls[2], walls[3], c->wall_kind[0], c->wall_u[0], c->wall_kind[1], c->wall_u[1]);
     else if (!f_prof && c->has_profile) rc = fail(LBM_ERR_ARG, "checkpoint %s was written without an inlet profile; this context has one", path);
     else if (f_prof && !c->has_profile) rc = fail(LBM_ERR_ARG, "checkpoint %s was written with an inlet profile; this context has none", path);
     else if (f_prof && pdigest != c->prof_digest) rc = fail(LBM_ERR_ARG, "checkpoint %s was written for a different inlet profile", path);
@@ -1185,6 +1241,16 @@ int lbm_debug_plan_candidates(int nx, int ny, int precision, int arith, int num_
     }
     if ((int)text.size() + 1 > cap) return fail(LBM_ERR_ARG, "buffer too small (%zu bytes needed)", text.size() + 1);
     memcpy(out, text.c_str(), text.size() + 1);
+    return LBM_OK;
+}
+
+/* TEST HOOK (no device needed): wall_rule (lbm_kernels.hpp), the function the kernels call, on one cell in the element type of `precision`. */
+int lbm_debug_wall_rule(int side, int kind, double velocity, int precision, const double* f_in9, double* f_out9) {
+    if (!f_in9 || !f_out9) return fail(LBM_ERR_ARG, "lbm_debug_wall_rule: null pointer");
+    if (precision != LBM_PRECISION_F64 && precision != LBM_PRECISION_F32) return fail(LBM_ERR_ARG, "lbm_debug_wall_rule: precision = %d", precision);
+    if (int rc = check_wall("lbm_debug_wall_rule", side, kind, velocity)) return rc;
+    if (precision == LBM_PRECISION_F32) debug_wall_rule<float>(side, kind, velocity, f_in9, f_out9);
+    else debug_wall_rule<double>(side, kind, velocity, f_in9, f_out9);
     return LBM_OK;
 }
 

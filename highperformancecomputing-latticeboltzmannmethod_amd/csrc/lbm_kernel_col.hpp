@@ -49,6 +49,12 @@ __device__ __forceinline__ float from_right(float v) { return __builtin_bit_cast
 // waves per SIMD the register allocation may assume: two blocks per CU when they fit 32 waves (8 waves: four per SIMD, 128 VGPRs;
 // 12 waves: six per SIMD, 80 VGPRs — the two-row fp64 strict shape), else one
 template <int NW> constexpr int col_waves_per_simd() { return NW == 12 ? 6 : NW <= 8 ? (2 * NW) / 4 : NW / 4; }
+// ... per instantiation: the fp32 contracted TRT kernels of eight waves run THREE blocks per CU (six waves per SIMD, 80 VGPRs; 74 when they
+// were written). With the bound of four the allocator takes what it likes below 128, and the seven-iteration one came out at 82 once
+// KArgs carried the walls: two blocks per CU, 237 -> 208 GLUPS at 4096x1024 (profiles/walls/README.md). Said here, it stays at six.
+template <typename T, int NW, int AR> constexpr int col_min_waves() {
+    return (sizeof(T) == 4 && NW == 8 && AR == AR_CONTRACTED_TRT) ? 6 : col_waves_per_simd<NW>();
+}
 
 // Tile walk: blocks are dealt round-robin over the 8 XCDs (each with its own 4 MiB L2) in index order; here every XCD walks
 // one contiguous run of the row-major tile order instead, so that x-neighbours — which share the lines at their common
@@ -70,7 +76,7 @@ template <int NW> constexpr int col_waves_per_simd() { return NW == 12 ? 6 : NW 
 // x-shifts through the LDS CROSSBAR (ds_bpermute_b32) instead of DPP moves (bit-exact; -1..3 %: the crossbar's latency sits in every
 // row's dependency chain and vector issue is not the binding resource at the margin).
 template <typename T, int R, int NW, int D, bool NT, int AR = AR_STRICT>
-__global__ void __launch_bounds__(NW * 64, (col_waves_per_simd<NW>())) k_stepc_col(const KArgs<T> a, const K2Extra<T> e) {
+__global__ void __launch_bounds__(NW * 64, (col_min_waves<T, NW, AR>())) k_stepc_col(const KArgs<T> a, const K2Extra<T> e) {
     constexpr int H = R * NW, HW = D - 1, OW = 64 - 2 * HW, OH = H - 2 * HW, LW = 64 + 2;
     static_assert(D >= 2 && OH >= 1 && R >= 2, "(D <= GR on a strip: its ghost rows go GR deep — the host's business)");
     // exchange buffer: per wave the three north-going populations of its top row and the three south-going ones of its

@@ -84,6 +84,25 @@ __host__ __device__ inline bool mask_box_any(const MaskView& m, int x0, int x1, 
     return m.sat[b1 * W + c1] - m.sat[b0 * W + c1] - m.sat[b1 * W + c0] + m.sat[b0 * W + c0] > 0;
 }
 
+// Kinds of a physical wall (lbm_set_wall, include/lbm_hip.h LBM_WALL_*) and the word that carries both through the argument blocks:
+// the south wall's kind in bits 0-1, the north wall's in bits 2-3. 0 = both walls no-slip, the reference's.
+enum WallKind { WALL_NOSLIP = 0, WALL_FREESLIP = 1, WALL_MOVING = 2 };
+__host__ __device__ constexpr int wall_pack(int south, int north) { return south | (north << 2); }
+// What a wall adds to / subtracts from the two diagonal populations it writes, per wall (s: south, n: north). Moving: both are the momentum
+// correction k = u_w / 6 = 6 w_i rho_w (c_i . u_w) with rho_w = 1, formed in double and cast. Other kinds: the operands that change no bit
+// of any value, x + (-0.0) and x - (+0.0) (the sign of a zero included), so the rule needs no branch on "moving".
+template <typename T> struct WallK { T s_add, s_sub, n_add, n_sub; };
+template <typename T>
+inline WallK<T> wall_ks(int south, double u_south, int north, double u_north) {
+    WallK<T> k;
+    k.s_add = south == WALL_MOVING ? (T)(u_south * (1.0 / 6.0)) : T(-0.0);
+    k.s_sub = south == WALL_MOVING ? (T)(u_south * (1.0 / 6.0)) : T(0.0);
+    k.n_add = north == WALL_MOVING ? (T)(u_north * (1.0 / 6.0)) : T(-0.0);
+    k.n_sub = north == WALL_MOVING ? (T)(u_north * (1.0 / 6.0)) : T(0.0);
+    return k;
+}
+
+
 template <typename T>
 struct KArgs {
     const T* src;      // plane 0 of the buffer read  (P_t)
@@ -117,6 +136,11 @@ struct KArgs {
     union { T les_tau; T trt_wm; };
     union { T les_tau2; T trt_wa; };
     union { T les_c; T trt_wb; };
+    // The two physical walls (lbm_set_wall), appended for the same reason: wall_pack of the two kinds, and what each wall adds to and
+    // subtracts from its diagonal populations (wall_ks: k = u_w / 6 of a moving wall, formed on the host in double; the identity
+    // operands otherwise). Launch-uniform: read inside the bottom / top branches of apply_bcs only.
+    int walls;
+    WallK<T> wk;
 };
 
 // Row handled by blockIdx.y. Blocks are dispatched roughly in index order; walking the rows in the opposite
@@ -164,16 +188,41 @@ __device__ __forceinline__ bool tile_near_solid(const KArgs<T>& a, int X0, int Y
            yg0 - ring <= a.cyl_y + r && yg0 + TY - 1 + ring >= a.cyl_y - r;
 }
 
+// The wall rule of ONE cell of global row 0 (bottom) or ny - 1 (top): the reference's on-node bounce-back (:155-163, :168-176) with the
+// wall's kind deciding what the two diagonal populations it writes become:
+//   no-slip    f5 = f7, f6 = f8 (south); f7 = f5, f8 = f6 (north): the reference's
+//   free-slip  the two sources change places (specular reflection: f5 = f8, f6 = f7 at the south wall)
+//   moving     no-slip's, +k / -k with k = u_w / 6: ONE IEEE addition each, so strict and contracted arithmetic apply the same bits.
+//              rho_w is 1, not the cell's density, and the on-node scheme does not make ux on the wall's row equal u_w.
+// Every kind keeps the pair sums, hence mass, as bounce-back does. `walls` and the four operands are launch-uniform (scalar registers).
+// Written without a branch on the kind: the SOURCE of each population is chosen, then the operand of WallK is added or subtracted, which
+// for a wall that does not move is the identity on every bit pattern (wall_ks). No value is live that bounce-back does not hold, and no
+// kernel loses an occupancy step to the rule. (Bounce-back followed by a swap of the two results under a uniform branch computes the
+// same and compiled to 16 more VGPRs in k_step_site and an occupancy step less in k_frame and k_probes: profiles/walls/README.md.)
+// __host__ too: lbm_debug_wall_rule applies this very function on the CPU.
+template <typename T>
+__host__ __device__ __forceinline__ void wall_rule(T (&f)[Q], bool bottom, bool top, int walls, const WallK<T>& k) {
+    if (bottom) {
+        const bool fs = (walls & 3) == WALL_FREESLIP;
+        const T a = fs ? f[8] : f[7], b = fs ? f[7] : f[8];
+        f[2] = f[4]; f[5] = a + k.s_add; f[6] = b - k.s_sub;
+    }
+    if (top) {
+        const bool fs = ((walls >> 2) & 3) == WALL_FREESLIP;
+        const T a = fs ? f[6] : f[5], b = fs ? f[5] : f[6];
+        f[4] = f[2]; f[7] = a - k.n_sub; f[8] = b + k.n_add;
+    }
+}
+
 // apply_boundary_conditions on the pulled populations of ONE cell, in the reference's sequential loop order
 // bottom -> top -> inlet -> outlet (LBMSolver.h:152-236). Solid cells are skipped by every one
 // of those loops. Returns nothing; rho_bc/u_out are exposed for the macro snapshot kernel.
 // The inlet velocity of global row yg is u_row[yg] (KArgs::u_row): loaded inside the inlet branch only, so no cell off column 0
-// carries its address or value.
+// carries its address or value. The two walls are wall_rule above: the one statement of it, for the step kernels and the snapshot.
 template <typename T>
 __device__ __forceinline__ void apply_bcs(T (&f)[Q], bool bottom, bool top, bool inlet, bool outlet, const T* u_row, int yg,
-                                          T& rho_bc, T& u_out) {
-    if (bottom) { f[2] = f[4]; f[5] = f[7]; f[6] = f[8]; }                    // :155-163
-    if (top)    { f[4] = f[2]; f[7] = f[5]; f[8] = f[6]; }                    // :168-176
+                                          int walls, const WallK<T>& wk, T& rho_bc, T& u_out) {
+    wall_rule(f, bottom, top, walls, wk);
     if (inlet) {                                                              // :181-206 (Zou-He velocity)
         const T u_in = u_row[yg];
         rho_bc = (f[0] + f[2] + f[4] + T(2.0) * (f[3] + f[6] + f[7])) / (T(1.0) - u_in);
@@ -189,11 +238,11 @@ __device__ __forceinline__ void apply_bcs(T (&f)[Q], bool bottom, bool top, bool
         f[7] = f[5] + T(0.5) * (f[2] - f[4]) - T(1.0 / 6.0) * rho_out * u_out;
     }
 }
-// apply_bcs at global cell (x, yg) for the step kernels. `a`: any argument block with nx, ny_glob and u_row (KArgs, MacroArgs).
+// apply_bcs at global cell (x, yg) for the step kernels. `a`: any argument block with nx, ny_glob, u_row and the walls (KArgs, MacroArgs).
 template <typename A, typename T>
 __device__ __forceinline__ void bcs_at(const A& a, T (&f)[Q], int x, int yg) {
     T rho_bc, u_out;
-    apply_bcs(f, yg == 0, yg == a.ny_glob - 1, x == 0, x == a.nx - 1, a.u_row, yg, rho_bc, u_out);
+    apply_bcs(f, yg == 0, yg == a.ny_glob - 1, x == 0, x == a.nx - 1, a.u_row, yg, a.walls, a.wk, rho_bc, u_out);
 }
 
 // Arithmetic of the collision (the only place the two modes differ):
@@ -1055,6 +1104,7 @@ struct MacroArgs {
     int initial;        // steps_done == 0: analytic initial macros (LBMGrid.h:219-228)
     double* rho; double* ux; double* uy;   // [ny_loc][nx]
     unsigned long long* max_usq_bits;      // optional running max of ux^2+uy^2 (bit pattern of a double >= 0)
+    int walls; WallK<T> wk;                // the two walls, as KArgs carries them (appended: the fields above keep their offsets)
 };
 
 // the moments of the nine populations of a fluid cell, in the element type: rho and u = (sum c_i f_i) / rho (one definition for
@@ -1087,7 +1137,7 @@ __device__ __forceinline__ void macro_cell(const MacroArgs<T>& p, int x, int y, 
 #pragma unroll
         for (int i = 0; i < Q; ++i) f[i] = p.old[(long)i * p.plane + c - (long)cy(i) * p.pitch - cx(i)];
         T rho_bc = T(1), u_out = T(0);
-        apply_bcs(f, yg == 0, yg == p.ny_glob - 1, x == 0, x == p.nx - 1, p.u_row, yg, rho_bc, u_out);
+        apply_bcs(f, yg == 0, yg == p.ny_glob - 1, x == 0, x == p.nx - 1, p.u_row, yg, p.walls, p.wk, rho_bc, u_out);
         // the outlet loop runs after the inlet loop (only matters for nx == 1)
         if (x == p.nx - 1) { r = 1.0; vx = (double)u_out; vy = 0.0; }
         else { r = (double)rho_bc; vx = (double)p.u_row[yg]; vy = 0.0; }

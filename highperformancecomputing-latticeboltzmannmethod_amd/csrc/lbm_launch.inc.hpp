@@ -1,6 +1,13 @@
 // csrc/lbm_launch.inc.hpp — kernel arguments, layouts and the launchers of every step-kernel family (single iteration, fused tiles, deep LDS tiles, registers), forces
 // (part of the one host translation unit lbm_hip.hip, which includes it in this place; round 4 split a 2 100-line file by concern)
 
+// The two walls as every argument block carries them (KArgs, MacroArgs): the packed kinds and the operands of wall_ks.
+template <typename T, typename A>
+void fill_walls(const lbm_ctx* c, A& a) {
+    a.walls = wall_pack(c->wall_kind[0], c->wall_kind[1]);
+    a.wk = wall_ks<T>(c->wall_kind[0], c->wall_u[0], c->wall_kind[1], c->wall_u[1]);
+}
+
 template <typename T>
 KArgs<T> make_kargs(const lbm_ctx* c, int src, int dst, int t) {
     KArgs<T> a;
@@ -39,6 +46,7 @@ KArgs<T> make_kargs(const lbm_ctx* c, int src, int dst, int t) {
         a.trt_wa = (T)(0.5 * (wp + wm));
         a.trt_wb = (T)(0.5 * (wp - wm));
     }
+    fill_walls<T>(c, a);
     return a;
 }
 
@@ -148,6 +156,7 @@ MacroArgs<T> make_macro_args(const lbm_ctx* c, const void* src) {
     m.cyl_x = c->cyl_x; m.cyl_y = c->cyl_y; m.cyl_r2 = (double)(c->cyl_r * c->cyl_r);
     if (c->has_mask) m.mv = c->mview;
     m.u_row = static_cast<const T*>(c->d_urow);
+    fill_walls<T>(c, m);
     m.initial = 0;
     m.rho = m.ux = m.uy = nullptr; m.max_usq_bits = nullptr;
     return m;

@@ -53,6 +53,8 @@ public:
             if (p.profiled()) check(lbm_set_inlet_profile(c, p.inlet_profile.data(), p.ny), "lbm_set_inlet_profile");
             if (p.les()) check(lbm_set_smagorinsky(c, p.smagorinsky_cs), "lbm_set_smagorinsky");
             if (p.trt()) check(lbm_set_trt(c, p.trt_magic), "lbm_set_trt");
+            if (p.walled())      // every strip carries both walls; only the strips that hold row 0 / ny - 1 use them
+                for (int side = 0; side < 2; ++side) check(lbm_set_wall(c, side, p.wall_kind[side], p.wall_velocity[side]), "lbm_set_wall");
             y += n;
         }
         check(lbm_group_link(group(), num_strips(), opt.rccl ? 1 : 0), "lbm_group_link");

@@ -309,6 +309,10 @@ private:
         if (p.les()) row_d("smagorinsky_cs", p.smagorinsky_cs);                                            // (LES runs only, likewise)
         if (p.trt()) row_d("trt_magic", p.trt_magic);                                                      // (TRT runs only, likewise)
         if (p.frames()) row_i("frame_stride", p.frame_stride);                                             // (runs with --frame-stride only, likewise)
+        if (p.walled()) {                                                                                  // (runs with a wall that is not no-slip only, likewise)
+            f.put("wall_south,"); f.put(p.wall_text(0).c_str()); f.put("\n");
+            f.put("wall_north,"); f.put(p.wall_text(1).c_str()); f.put("\n");
+        }
         std::printf("  simulation_params.csv written\n");
     }
     // calculate_time_averaged_drag (LBMIO.h:367-413): statistics of the CSV values (8 decimals) for timestep > 1000.

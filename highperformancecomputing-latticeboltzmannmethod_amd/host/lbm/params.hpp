@@ -3,6 +3,10 @@
 // surface a caller of the reference touches: LBMConfig.h:9-34 constants, :36-66 SimulationParams).
 #pragma once
 #include <array>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -60,6 +64,11 @@ struct SimulationParams {
     // off. (rho, ux, uy) is sampled at them on the device at every output iteration, bilinearly (lbm_probes_begin), and drained into
     // probes.csv; no field is fetched for it.
     std::vector<double> probe_xy;
+    // the bottom and top walls (lbm_solver --wall-south / --wall-north / --walls; not in the reference, whose two walls are no-slip):
+    // [0] south (row 0), [1] north (row ny - 1); kind 0 no-slip, 1 free-slip, 2 moving with the tangential velocity beside it
+    // (lbm_set_wall). Both no-slip: everything the run prints and writes is the reference's.
+    int wall_kind[2] = {0, 0};
+    double wall_velocity[2] = {0.0, 0.0};
 
     double nu() const { return (tau - 0.5) / 3.0; }
     bool masked() const { return !obstacle_mask.empty(); }
@@ -72,6 +81,42 @@ struct SimulationParams {
     bool frames() const { return frame_stride > 0; }
     bool probes() const { return !probe_xy.empty(); }
     int probe_count() const { return (int)(probe_xy.size() / 2); }
+    bool walled() const { return wall_kind[0] != 0 || wall_kind[1] != 0; }
+    // the velocity of wall `side` with the fewest digits that read back exactly
+    std::string wall_velocity_text(int side) const {
+        char b[64];
+        for (int digits = 1; digits <= 17; ++digits) {
+            std::snprintf(b, sizeof(b), "%.*g", digits, wall_velocity[side]);
+            if (std::strtod(b, nullptr) == wall_velocity[side]) break;
+        }
+        return b;
+    }
+    // a wall as the command line names it: "no-slip", "free-slip" or "moving:U"
+    std::string wall_text(int side) const {
+        if (wall_kind[side] == 0) return "no-slip";
+        if (wall_kind[side] == 1) return "free-slip";
+        return "moving:" + wall_velocity_text(side);
+    }
+    // ... and as the banner prints it: "no-slip", "free-slip" or "moving u = U"
+    std::string wall_banner(int side) const {
+        return wall_kind[side] == 2 ? "moving u = " + wall_velocity_text(side) : wall_text(side);
+    }
+    // KIND of --wall-south / --wall-north / --walls into wall `side`: no-slip | free-slip | moving:U with a finite |U| < 1
+    // (std::invalid_argument with the one-line message otherwise)
+    void set_wall(int side, const std::string& option, const std::string& text) {
+        const auto bad = [&](const char* why) {
+            return std::invalid_argument(option + ": '" + text + "' " + why + " (no-slip, free-slip or moving:U with |U| < 1)");
+        };
+        if (text == "no-slip") { wall_kind[side] = 0; wall_velocity[side] = 0.0; return; }
+        if (text == "free-slip") { wall_kind[side] = 1; wall_velocity[side] = 0.0; return; }
+        if (text.rfind("moving:", 0) != 0) throw bad("is not a wall kind");
+        const char* num = text.c_str() + 7;
+        char* end = nullptr;
+        const double u = std::strtod(num, &end);
+        if (end == num || *end != '\0') throw bad("has no wall velocity");
+        if (!std::isfinite(u) || std::fabs(u) >= 1.0) throw bad("has a wall velocity that is not finite or not below 1 in magnitude");
+        wall_kind[side] = 2; wall_velocity[side] = u;
+    }
     double reynolds() const {
         if (masked()) return inlet_velocity * mask_frontal_height / nu();
         return inlet_velocity * (2.0 * cylinder_radius * ny) / nu();

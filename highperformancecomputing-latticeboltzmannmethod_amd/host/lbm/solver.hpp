@@ -48,6 +48,8 @@ public:
         if (!opt_.quiet && params_.trt())
             std::printf("  Collision: TRT collision, magic = %g (odd parts relax with 1/(0.5 + magic/(tau - 0.5)); tau sets the viscosity)\n",
                         params_.trt_magic);
+        if (!opt_.quiet && params_.walled())
+            std::printf("  Walls: south %s, north %s\n", params_.wall_banner(0).c_str(), params_.wall_banner(1).c_str());
         if (!opt_.quiet && params_.masked()) {
             std::printf("  Obstacle: %s %s, frontal height D=%d cells\n  Solid cells: %d\n  Plan: %s\n", params_.bodied() ? "bodies" : "mask",
                         params_.bodied() ? params_.obstacle_bodies_file.c_str() : params_.obstacle_mask_file.c_str(),

@@ -23,7 +23,7 @@ static void usage() {
               "           [--gpus N] [--strips N] [--rccl]\n"
               "           [--checkpoint FILE] [--restart FILE] [--obstacle-mask FILE.pgm] [--obstacle-bodies FILE.pgm]\n"
               "           [--inlet-profile parabolic|FILE] [--print-inlet-profile] [--smagorinsky CS] [--trt-magic LAMBDA]\n"
-              "           [--stats-start N]\n"
+              "           [--stats-start N] [--wall-south KIND] [--wall-north KIND] [--walls KIND]\n"
               "           [--frame-stride K] [--probes FILE] [--probe-line x0 y0 x1 y1 n]\n"
               "Defaults are the reference's SimulationParams (LBMConfig.h:37-51). --reynolds sets the inlet velocity\n"
               "from tau and the cylinder diameter so that params.reynolds() equals RE.\n"
@@ -47,6 +47,10 @@ static void usage() {
               "instead of BGK: the even part of each opposite pair of populations relaxes with 1/tau (the viscosity is\n"
               "unchanged), the odd part with 1/(0.5 + LAMBDA/(tau - 0.5)). 0.25 is the most stable choice, 0.1875 (3/16) the\n"
               "most accurate at walls. Needs tau > 0.5; cannot be combined with --smagorinsky.\n"
+              "--wall-south KIND / --wall-north KIND: the bottom (row 0) / top (row ny-1) wall, KIND = no-slip (the default: on-node\n"
+              "bounce-back) | free-slip (specular reflection: no boundary layer, for unconfined flow past a body) | moving:U (a wall\n"
+              "sliding at the tangential velocity U, |U| < 1: Couette flow, a lid, a moving ground). --walls KIND sets both. The\n"
+              "on-node scheme does not make ux on a moving wall's row equal U, and the wall's density is taken as 1.\n"
               "--stats-start N: time-averaged statistics from step N on, sampled on the device every --output-frequency steps;\n"
               "the run ends with mean_fields.vtk and mean_fields.csv (means of rho, ux, uy and the Reynolds stresses). With\n"
               "--checkpoint / --restart the sums travel beside the checkpoint as FILE.stats. --no-final suppresses the two\n"
@@ -112,6 +116,16 @@ int main(int argc, char** argv) {
         else if (k == "--smagorinsky") smagorinsky = val();
         else if (k == "--trt-magic") trt_magic = val();
         else if (k == "--stats-start") stats_start = val();
+        else if (k == "--wall-south" || k == "--wall-north" || k == "--walls") {   // checked here: no device is touched before a bad value exits
+            try {
+                const std::string kind = val();
+                if (k != "--wall-north") params.set_wall(0, k, kind);
+                if (k != "--wall-south") params.set_wall(1, k, kind);
+            } catch (const std::exception& e) {
+                std::fprintf(stderr, "%s\n", e.what());
+                return 2;
+            }
+        }
         else if (k == "--frame-stride") frame_stride = val();
         else if (k == "--probes" || k == "--probe-line") {   // parsed here, in the order given; checked against the lattice below
             try {

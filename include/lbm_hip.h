@@ -289,6 +289,40 @@ int  lbm_set_smagorinsky(lbm_ctx* c, double cs);
  * LBM_ERR_ARG: null context, an initialised context, a value that is not finite, < 0 or > 1, a context whose tau <= 0.5, or a
  * context with a nonzero Smagorinsky constant: the two collisions cannot be combined. */
 int  lbm_set_trt(lbm_ctx* c, double magic);
+/* The two walls: generalises the on-node bounce-back of the bottom and top rows (LBMSolver.h:155-176), a stationary no-slip wall, to a
+ * KIND and a tangential VELOCITY per wall. The south wall is global row 0, the north wall global row ny - 1. On a fluid cell of the
+ * wall's row, after the pull:
+ *     kind                   south wall                          north wall
+ *     LBM_WALL_NOSLIP   0    f2 = f4; f5 = f7;     f6 = f8       f4 = f2; f7 = f5;     f8 = f6        (the reference's; the default)
+ *     LBM_WALL_FREESLIP 1    f2 = f4; f5 = f8;     f6 = f7       f4 = f2; f7 = f6;     f8 = f5        (specular reflection)
+ *     LBM_WALL_MOVING   2    f2 = f4; f5 = f7 + k; f6 = f8 - k   f4 = f2; f7 = f5 - k; f8 = f6 + k    (k = velocity / 6)
+ * k is the momentum correction 6 w_i rho_w (c_i . u_w) of a diagonal population with rho_w = 1, formed once on the host in double and
+ * cast to the element type; each corrected population is ONE IEEE addition, so strict and contracted arithmetic (option "arith") apply
+ * the same bits in the wall rule. Every kind leaves the pair sums, and with them mass, as bounce-back does. Everything else stays the
+ * reference's: the sequential order bottom -> top -> inlet -> outlet on a cell (a corner cell takes the wall rule first, then Zou-He,
+ * which reads the populations the wall has just written); solid cells of a wall row are skipped; the ghost rows keep their permanent
+ * content; the initial state is unchanged (interior cells start at the inlet equilibrium). The snapshot — lbm_get_macros, statistics,
+ * frames, probes — applies the same rule through the same function, and so does the f_current of lbm_get_populations.
+ * Documented, not corrected: the on-node scheme does not make ux on a moving wall's row equal to the wall's velocity (the row's
+ * populations are collided like any other's), and rho_w is 1, not the local density. A free-slip wall grows no boundary layer: a
+ * uniform stream stays uniform (unconfined flow past a body); a moving wall drives Couette flow, a lid, a ground plane.
+ * Call after lbm_create and before lbm_initialise, like lbm_set_inlet_profile: the plan is measured with the walls set. Every strip of
+ * a run is given the same two walls; a strip that holds neither row 0 nor row ny - 1 carries the values and never uses them. The walls
+ * change no launch and no row range: forces, body forces, the halo exchange and the dry-run choreography (lbm_debug_choreography) are
+ * untouched, and with kind 0 on both walls every result, kernel name and checkpoint byte is what it was without this call.
+ * `velocity` is read for LBM_WALL_MOVING only and must be 0 for the other kinds; setting LBM_WALL_NOSLIP clears a wall. Checkpoints
+ * carry both walls where either is not no-slip (lbm_save_state: magic "LBMCKPT3", flag bit 4, four doubles {south kind, south
+ * velocity, north kind, north velocity} behind the collision parameters) and load only into a context with equal walls.
+ * LBM_ERR_ARG (the text names the offender): a null context, an initialised context, side outside 0..1, kind outside 0..2, a
+ * velocity that is not finite or has |velocity| >= 1, a nonzero velocity with kind 0 or 1. */
+#define LBM_WALL_SOUTH 0
+#define LBM_WALL_NORTH 1
+#define LBM_WALL_NOSLIP   0
+#define LBM_WALL_FREESLIP 1
+#define LBM_WALL_MOVING   2
+int  lbm_set_wall(lbm_ctx* c, int side, int kind, double velocity);
+/* The wall of `side` as set (kind 0, velocity 0 on a fresh context); either pointer may be NULL. LBM_ERR_ARG: null context, side outside 0..1. */
+int  lbm_get_wall(const lbm_ctx* c, int side, int* kind, double* velocity);
 
 /* ---- strip halo exchange (replaces Grid::exchange_ghost_cells, LBMGrid.h:249-283) ----
  * Device path: RCCL send/recv of the LBM_HALO_ROWS edge rows per face (one contiguous run in the row-interleaved
@@ -384,8 +418,8 @@ int  lbm_halo_import(lbm_ctx* c, const double* south_in, const double* north_in)
 /* Checkpoint / restart (the reference has none): the strip's post-collision populations and the
  * iteration counter. lbm_load_state needs an initialised context created with the same parameters; the macro /
  * population snapshots become available again after the next lbm_step. A file written with an obstacle mask, an inlet
- * profile, a Smagorinsky constant or a TRT magic parameter loads only into a context with the same mask, profile, constant and
- * parameter (the failure names which one differs). */
+ * profile, a Smagorinsky constant, a TRT magic parameter or a wall that is not no-slip (lbm_set_wall) loads only into a context with
+ * the same mask, profile, constant, parameter and walls (the failure names which one differs). */
 int  lbm_save_state(lbm_ctx* c, const char* path);
 int  lbm_load_state(lbm_ctx* c, const char* path);
 
@@ -456,6 +490,12 @@ const char* lbm_plan_options(const lbm_ctx* c);
  * (csrc/lbm_kernels.hpp strict_div2); this runs it beside the compiler's IEEE divisions: q1,q2 = strict_div2(a1,a2,b), r1,r2 = a1/b,
  * a2/b, n host doubles each. Bit-identical for denominators in [2^-20, 2^20] and numerators 0 or of magnitude in [2^-400, 2^400]. */
 int lbm_debug_strict_div2(const double* a1, const double* a2, const double* b, int n, double* q1, double* q2, double* r1, double* r2);
+/* Test hook, callable without a device: the wall rule of lbm_set_wall on ONE cell — the inline function every step kernel and the
+ * snapshot call (csrc/lbm_kernels.hpp wall_rule), compiled for the host. f_in9 = the cell's nine pulled populations; they are cast to the
+ * element type of `precision`, the rule of wall `side` with `kind` and `velocity` is applied as on a fluid cell of that wall's row, and
+ * the nine results are widened into f_out9. The argument errors of lbm_set_wall, and LBM_ERR_ARG for a null pointer or an unknown
+ * precision. Replaces nothing in the reference (its rule is LBMSolver.h:155-176, kind 0). */
+int lbm_debug_wall_rule(int side, int kind, double velocity, int precision, const double* f_in9, double* f_out9);
 /* Test hook, callable without a device: what the ranks of a strip run agree on before the collective schedule trials of
  * lbm_initialise (csrc/lbm_hip.hip tune_strip_schedule). per_rank7 = nranks x {may tune, overlap pinned, overlap, deep_halo pinned,
  * deep_halo, halo_trim pinned, halo_trim}; agreed7 = the same seven as agreed (-1 where nothing is pinned). LBM_ERR_ARG when the ranks pin different
