@@ -88,6 +88,10 @@ def lib():
         L.lbm_set_wall.argtypes = [vp, C.c_int, C.c_int, C.c_double]
         L.lbm_get_wall.argtypes = [vp, C.c_int, C.POINTER(C.c_int), dp]
         L.lbm_debug_wall_rule.argtypes = [C.c_int, C.c_int, C.c_double, C.c_int, dp, dp]
+        L.lbm_set_inlet_schedule.argtypes = [vp, dp, C.c_int, C.c_int]
+        L.lbm_inlet_schedule_length.argtypes = [vp]
+        L.lbm_get_inlet_scale.argtypes = [vp, C.c_int, dp]
+        L.lbm_debug_inlet_scale.argtypes = [dp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, dp]
         ip = C.POINTER(C.c_int)
         L.lbm_debug_geometry.argtypes = [C.POINTER(C.c_ubyte), C.c_int, C.c_int, C.c_int, C.c_int, ip, C.POINTER(C.c_ulonglong), C.c_long,
                                          ip, C.c_long, ip, C.c_int, ip]
@@ -280,6 +284,57 @@ def scale_inlet_profile(shape, mean):
     return u
 
 
+INLET_MODES = {"hold": 0, "repeat": 1}                         # LBM_INLET_HOLD / LBM_INLET_REPEAT
+INLET_SCHEDULE_MAX = 1048576                                   # LBM_INLET_SCHEDULE_MAX
+
+
+def cosine_ramp(n):
+    """The schedule of lbm_solver --inlet-ramp N (host/lbm/inlet.hpp cosine_ramp, operation by operation): N + 1 factors
+    0.5 * (1 - cos(pi * k / N)), from 0 to 1; used with "hold"."""
+    n = int(n)
+    if n < 1:
+        raise ValueError("a ramp takes at least one step")
+    k = np.arange(n + 1, dtype=np.float64)
+    return 0.5 * (1.0 - np.cos(np.pi * k / n))
+
+
+def sine_pulse(amplitude, period):
+    """The schedule of lbm_solver --inlet-pulse A:P (host/lbm/inlet.hpp sine_pulse, operation by operation): P factors
+    1 + A * sin(2 * pi * k / P); used with "repeat"."""
+    period = int(period)
+    if period < 1:
+        raise ValueError("a pulse has a period of at least one iteration")
+    k = np.arange(period, dtype=np.float64)
+    return 1.0 + float(amplitude) * np.sin(2.0 * np.pi * k / period)
+
+
+def _schedule(spec):
+    """The inlet_schedule= keyword as (float64 table, mode number): a table (hold) or a pair (table, "hold" | "repeat" | 0 | 1)."""
+    mode = 0
+    if isinstance(spec, tuple) and len(spec) == 2 and (isinstance(spec[1], str) or np.ndim(spec[0]) > 0):
+        spec, m = spec
+        if isinstance(m, str):
+            if m not in INLET_MODES:
+                raise ValueError(f"unknown inlet schedule mode {m!r}: one of {sorted(INLET_MODES)}")
+            mode = INLET_MODES[m]
+        else:
+            mode = int(m)
+    return np.ascontiguousarray(np.atleast_1d(spec), dtype=np.float64), mode
+
+
+def debug_inlet_scale(s, mode, t, precision="f64"):
+    """lbm_debug_inlet_scale (no device): the factor (double)(T)s(t) the schedule (s, mode) gives each iteration of `t`, through the
+    index function the kernels call."""
+    a, m = _schedule((np.asarray(s, dtype=np.float64), mode))
+    tt = np.ascontiguousarray(np.atleast_1d(t), dtype=np.int32)
+    out = np.empty(tt.size, dtype=np.float64)
+    rc = lib().lbm_debug_inlet_scale(_dp(a), a.size, m, {"f64": 0, "f32": 1}[precision], tt.ctypes.data_as(C.POINTER(C.c_int)),
+                                     tt.size, _dp(out))
+    if rc < 0:
+        raise LbmError(f"lbm_hip error {rc}: {lib().lbm_last_error().decode()}")
+    return out
+
+
 WALL_SIDES = {"south": 0, "north": 1}                          # LBM_WALL_SOUTH / LBM_WALL_NORTH
 WALL_KINDS = {"no-slip": 0, "free-slip": 1, "moving": 2}       # LBM_WALL_NOSLIP / LBM_WALL_FREESLIP / LBM_WALL_MOVING
 _WALL_NAMES = {v: k for k, v in WALL_KINDS.items()}
@@ -359,12 +414,14 @@ class Context:
     default capacity at the end of initialise(); see frames_begin). probes: optional (n, 2) array of probe points (x, y) in GLOBAL lattice
     coordinates (lbm_probes_begin with a ring of probe_capacity samples at the end of initialise(); see probes_begin). walls: optional
     kinds of the bottom and top walls (lbm_set_wall) in place of the two no-slip walls: "free-slip" (both), or a pair (south, north) whose
-    entries are "no-slip", "free-slip" or ("moving", u_w) with the wall's tangential velocity u_w."""
+    entries are "no-slip", "free-slip" or ("moving", u_w) with the wall's tangential velocity u_w. inlet_schedule: optional table of
+    scale factors of the inflow, one per iteration (lbm_set_inlet_schedule): a table holds its last entry for ever, a pair
+    (table, "repeat") is periodic (see cosine_ramp, sine_pulse)."""
 
     def __init__(self, nx, ny, tau=0.6, inlet_velocity=0.01333, cylinder_x=0.2, cylinder_y=0.5,
                  cylinder_radius=0.05, y_start=0, local_ny=0, precision="f64", device=0, force_log_capacity=0,
                  options=None, solid=None, inlet_profile=None, smagorinsky=None, bodies=None, frames=None, trt_magic=None,
-                 probes=None, probe_capacity=None, walls=None):
+                 probes=None, probe_capacity=None, walls=None, inlet_schedule=None):
         if solid is not None and bodies is not None:
             raise LbmError("solid= and bodies= exclude each other: the body labels are the geometry (solid where nonzero)")
         self.L = lib()
@@ -395,6 +452,8 @@ class Context:
         if walls is not None:
             for side, (kind, u) in zip(("south", "north"), _wall_pair(walls)):
                 self.set_wall(side, kind, u)
+        if inlet_schedule is not None:
+            self.set_inlet_schedule(*_schedule(inlet_schedule))
 
     def _chk(self, rc):
         if rc < 0:
@@ -476,6 +535,22 @@ class Context:
         k, u = C.c_int(), C.c_double()
         self._chk(self.L.lbm_get_wall(self.h, _wall_code(WALL_SIDES, "side", side), C.byref(k), C.byref(u)))
         return _WALL_NAMES[k.value], u.value
+
+    def set_inlet_schedule(self, s, mode="hold"):
+        """lbm_set_inlet_schedule: one scale factor of the inflow per iteration; mode "hold" (the last entry holds for ever) or "repeat"
+        (periodic); an empty table clears the schedule; before initialise()."""
+        a, m = _schedule((np.asarray(s, dtype=np.float64), mode))
+        self._chk(self.L.lbm_set_inlet_schedule(self.h, _dp(a), a.size, m))
+
+    def inlet_schedule_length(self):
+        """Entries of the schedule as set (lbm_inlet_schedule_length); 0 without one."""
+        return self.L.lbm_inlet_schedule_length(self.h)
+
+    def inlet_scale(self, t):
+        """The factor iteration t applies, in the element type (lbm_get_inlet_scale); 1.0 without a schedule."""
+        v = C.c_double()
+        self._chk(self.L.lbm_get_inlet_scale(self.h, int(t), C.byref(v)))
+        return v.value
 
     def walls(self):
         """((south kind, velocity), (north kind, velocity)) as set; (("no-slip", 0.0), ("no-slip", 0.0)) on a fresh context."""
@@ -708,10 +783,11 @@ class Group:
     transport: "peer" (device copies / hipMemcpyPeerAsync) or "rccl" (ncclCommInitAll; distinct devices).
     solid: optional global (ny, nx) obstacle mask, inlet_profile: optional global [ny] inlet velocities, smagorinsky: optional LES
     constant Cs, trt_magic: optional TRT magic parameter, bodies: optional global (ny, nx) body numbers (in place of solid), frames: optional frame stride k, probes / probe_capacity: optional probe points (global coordinates), walls: optional kinds of the
-    bottom and top walls (as Context takes them); all given to every member."""
+    bottom and top walls (as Context takes them), inlet_schedule: optional scale factors of the inflow per iteration (likewise); all given
+    to every member."""
 
     def __init__(self, nx, ny, bounds, devices=None, transport="peer", options=None, solid=None, inlet_profile=None, smagorinsky=None,
-                 bodies=None, frames=None, trt_magic=None, probes=None, probe_capacity=None, walls=None, **kw):
+                 bodies=None, frames=None, trt_magic=None, probes=None, probe_capacity=None, walls=None, inlet_schedule=None, **kw):
         from .strips import partition_rows
         if isinstance(bounds, int):
             bounds = partition_rows(ny, bounds)
@@ -719,7 +795,7 @@ class Group:
         self.nx, self.ny = nx, ny
         self.ctxs = [Context(nx, ny, y_start=y0, local_ny=n, device=d, options=options, solid=solid, inlet_profile=inlet_profile,
                              smagorinsky=smagorinsky, bodies=bodies, frames=frames, trt_magic=trt_magic, probes=probes,
-                             probe_capacity=probe_capacity, walls=walls, **kw)
+                             probe_capacity=probe_capacity, walls=walls, inlet_schedule=inlet_schedule, **kw)
                      for (y0, n), d in zip(bounds, devices)]
         self.L = lib()
         self._arr = (C.c_void_p * len(self.ctxs))(*[c.h for c in self.ctxs])

@@ -335,6 +335,17 @@ struct lbm_ctx {
     bool has_profile = false;
     unsigned long long prof_digest = 0;
     void* d_feqrow = nullptr;
+    // The inlet schedule (lbm_set_inlet_schedule): the table as given and its mode; its device block {n, mode, (T)s[n]} the step kernels
+    // read (KArgs::sched; nullptr without a schedule); the digest checkpoints carry. h_urow is the host's copy of what d_urow holds,
+    // in double: lbm_initialise, which knows both, checks u[y] * s[k] < 1 and forms the initial profile u0[y] = u[y] * s[0] from it —
+    // into d_urow0 (the initial snapshot's ux) and d_feqrow (the initial state).
+    std::vector<double> sched;
+    int sched_mode = 0;
+    unsigned long long sched_digest = 0;
+    void* d_sched = nullptr;
+    void* d_urow0 = nullptr;
+    std::vector<double> h_urow;
+    bool has_sched() const { return !sched.empty(); }
     // The two physical walls (lbm_set_wall), [0] south (global row 0) and [1] north (row ny - 1): kind (lbm_kernels.hpp WallKind) and the
     // tangential velocity of a moving wall, 0 otherwise. Every strip of a run carries both; one that holds neither wall row never uses them.
     int wall_kind[2] = {0, 0};

@@ -77,18 +77,90 @@ int upload_rows(const lbm_ctx* c, void* dst, const double* v, size_t n) {
     }
     return LBM_OK;
 }
+// The initial equilibria f_eq(1, (u[y], 0)) of every global row into d_feqrow (k_init), replacing an earlier table.
+// The tables cover every global row, not only the strip's rows +- GR: the register kernel's garbage cells beyond a partial band
+// may evaluate the inlet of any row of the domain, and a whole table keeps that read in bounds without a test in the kernel.
+int upload_feqrow(lbm_ctx* c, const double* u, int ny) {
+    std::vector<double> feqrow((size_t)ny * Q);
+    for (int y = 0; y < ny; ++y) {
+        double f[Q];
+        feq_inflow(u[y], f);
+        for (int i = 0; i < Q; ++i) feqrow[(size_t)y * Q + i] = f[i];
+    }
+    if (c->d_feqrow) { HIPCHK(hipFree(c->d_feqrow)); c->d_feqrow = nullptr; }
+    HIPCHK(hipMalloc(&c->d_feqrow, feqrow.size() * c->esize));
+    return upload_rows(c, c->d_feqrow, feqrow.data(), feqrow.size());
+}
+
+// ---- the inlet schedule (lbm_set_inlet_schedule) ----
+// the argument checks shared by lbm_set_inlet_schedule and lbm_debug_inlet_scale; the text names the offender
+int check_schedule(const char* who, const double* s, int n, int mode) {
+    if (n < 0 || n > LBM_INLET_SCHEDULE_MAX) return fail(LBM_ERR_ARG, "%s: n = %d (0 .. %d only)", who, n, LBM_INLET_SCHEDULE_MAX);
+    if (n > 0 && !s) return fail(LBM_ERR_ARG, "%s: null table with n = %d", who, n);
+    if (mode != LBM_INLET_HOLD && mode != LBM_INLET_REPEAT) return fail(LBM_ERR_ARG, "%s: mode = %d (0 hold or 1 repeat only)", who, mode);
+    for (int k = 0; k < n; ++k)
+        if (!std::isfinite(s[k])) return fail(LBM_ERR_ARG, "%s: entry %d is %g (finite factors only)", who, k, s[k]);
+    return LBM_OK;
+}
+// FNV-1a over the mode, the length and the bit patterns of the factors: what a checkpoint carries of a schedule
+unsigned long long schedule_digest(const double* s, int n, int mode) {
+    unsigned long long d = 1469598103934665603ull;
+    auto mix = [&](unsigned v) { d ^= v; d *= 1099511628211ull; };
+    mix((unsigned)mode); mix((unsigned)n);
+    for (int k = 0; k < n; ++k) {
+        unsigned long long b;
+        memcpy(&b, &s[k], sizeof(b));
+        mix((unsigned)b); mix((unsigned)(b >> 32));
+    }
+    return d;
+}
+// the device block the kernels read: {n, mode}, then the factors in the element type (lbm_kernels.hpp inlet_sched_at)
+template <typename T>
+int upload_schedule(lbm_ctx* c) {
+    const size_t n = c->sched.size(), bytes = INLET_SCHED_HEAD * sizeof(int) + n * sizeof(T);
+    std::vector<unsigned char> h(bytes);
+    const int head[INLET_SCHED_HEAD] = {(int)n, c->sched_mode};
+    memcpy(h.data(), head, sizeof(head));
+    T* tab = reinterpret_cast<T*>(h.data() + sizeof(head));
+    for (size_t k = 0; k < n; ++k) tab[k] = (T)c->sched[k];
+    HIPCHK(hipMalloc(&c->d_sched, bytes));
+    HIPCHK(hipMemcpy(c->d_sched, h.data(), bytes, hipMemcpyHostToDevice));
+    return LBM_OK;
+}
+// lbm_initialise with a schedule set, where profile and schedule are both known: the inlet divides by 1 - u[y] * s[k]; the initial state
+// is that of the profile u0[y] = u[y] * s[0], formed here in double (d_feqrow for k_init, d_urow0 for the initial snapshot).
+int prepare_schedule(lbm_ctx* c) {
+    const int ny = c->p.ny;
+    double smax = c->sched[0], smin = c->sched[0];
+    for (double v : c->sched) { smax = std::max(smax, v); smin = std::min(smin, v); }
+    for (int y = 0; y < ny; ++y) {
+        const double u = c->h_urow[(size_t)y];
+        if (u * smax < 1.0 && u * smin < 1.0) continue;
+        for (size_t k = 0; k < c->sched.size(); ++k)
+            if (!(u * c->sched[k] < 1.0))
+                return fail(LBM_ERR_ARG, "lbm_initialise: inlet row %d (velocity %g) times schedule entry %d (factor %g) is %g (products below 1 only)",
+                            y, u, (int)k, c->sched[k], u * c->sched[k]);
+    }
+    std::vector<double> u0((size_t)ny);
+    for (int y = 0; y < ny; ++y) u0[(size_t)y] = c->h_urow[(size_t)y] * c->sched[0];
+    if (int rc = upload_feqrow(c, u0.data(), ny)) return rc;
+    if (!c->d_urow0) HIPCHK(hipMalloc(&c->d_urow0, (size_t)ny * c->esize));
+    return upload_rows(c, c->d_urow0, u0.data(), u0.size());
+}
 }  // namespace
 
 // ---- checkpoint / restart (the reference keeps its state in memory only) ------------------------
 // File: CkptHeader; in an "LBMCKPT3" file a 64-bit word of flags; the fields the flags announce, in the order of their bits (bit 0: the
 // obstacle mask's 64-bit digest, bit 1: the inlet profile's, then one double per collision model that has a parameter — ckpt_bit in
 // collision_models, lbm_plan.hpp: bit 2 Cs, bit 3 the TRT magic parameter — then bit 4: the two walls of lbm_set_wall as four doubles,
-// south kind, south velocity, north kind, north velocity, written only where a wall is not no-slip); then the post-collision populations P_{steps_done} of the
+// south kind, south velocity, north kind, north velocity, written only where a wall is not no-slip — then bit 5: the 64-bit digest of the
+// inlet schedule of lbm_set_inlet_schedule, {mode, n, the n doubles}; the iteration counter positions the schedule after a restart); then the post-collision populations P_{steps_done} of the
 // strip's interior, [9][local_ny][nx] in the element type. The state is complete: ghost cells and solid cells are reconstructed by
-// lbm_initialise. A context with neither profile nor collision parameter nor such a wall writes "LBMCKPT2" (header, mask digest, populations) if it has a
+// lbm_initialise. A context with neither profile nor collision parameter nor such a wall nor a schedule writes "LBMCKPT2" (header, mask digest, populations) if it has a
 // mask and "LBMCKPT1" (header, populations) otherwise. A context loads only a file that announces exactly what it has, with equal values.
 namespace {
 constexpr unsigned long long CKPT_WALLS = 16;   // LBMCKPT3 flag bit 4: the two walls follow the collision parameters
+constexpr unsigned long long CKPT_SCHED = 32;   // LBMCKPT3 flag bit 5: the inlet schedule's 64-bit digest follows the walls
 struct CkptHeader {
     char magic[8];
     int nx, ny, y_start, local_ny, precision, steps_done;
@@ -271,8 +343,8 @@ int lbm_create(const lbm_params* p, int device, lbm_ctx** out) {
     }
     HIPTRY(hipMalloc(&c->d_urow, (size_t)p->ny * c->esize));   // the uniform inflow until lbm_set_inlet_profile replaces it
     {
-        const std::vector<double> u((size_t)p->ny, p->inlet_velocity);
-        if (int rc = upload_rows(c, c->d_urow, u.data(), u.size())) return bail(rc);
+        c->h_urow.assign((size_t)p->ny, p->inlet_velocity);
+        if (int rc = upload_rows(c, c->d_urow, c->h_urow.data(), c->h_urow.size())) return bail(rc);
     }
     HIPTRY(c->force_log.alloc(3, c->log_cap, false));
     HIPTRY(hipMalloc(&c->d_halo, 4 * HR1 * Q * sizeof(double) * (size_t)c->nx));
@@ -316,7 +388,7 @@ void lbm_destroy(lbm_ctx* c) {
     c->pool.reset();
     void* ptrs[] = {c->buf[0], c->buf[1], c->scratch, c->d_macro, c->d_maxbits, c->d_unstable, c->d_tbase, c->d_solid_count, c->d_feq,
                     c->d_force_now, c->force_log.d, c->d_halo, c->d_red, (void*)c->mview.bits, (void*)c->mview.sat, c->d_fpart,
-                    c->d_urow, c->d_feqrow, c->d_stats, c->d_labels, c->d_body_box, c->d_body_chunks, c->d_body_first, c->d_body_part,
+                    c->d_urow, c->d_feqrow, c->d_sched, c->d_urow0, c->d_stats, c->d_labels, c->d_body_box, c->d_body_chunks, c->d_body_first, c->d_body_part,
                     c->d_body_now, c->body_log.d, c->frames.d, c->d_probe_table, c->probes.d};
     for (void* q : ptrs)
         if (q) (void)hipFree(q);
@@ -356,6 +428,7 @@ int lbm_initialise(lbm_ctx* c, int* solid_count_out) {
     lbm_trace("initialise", "ctx %p %dx%d rows %d..%d begin", (void*)c, c->nx, c->p.ny, c->p.y_start, c->p.y_start + c->nyl);
     if (int rc = refuse_tall(c->collision, c->deep)) return rc;
     HIPCHK(hipSetDevice(c->device));
+    if (c->has_sched()) { if (int rc = prepare_schedule(c)) return rc; }
     { int wr = wait_stream(c, c->stream, "compute stream (lbm_initialise)"); if (wr) return wr; }        // (re-)initialisation starts from quiet streams
     { int wr = wait_stream(c, c->comm_stream, "exchange stream (lbm_initialise)"); if (wr) return wr; }
     { int wr = wait_stream(c, c->split_stream, "second compute stream (lbm_initialise)"); if (wr) return wr; }
@@ -762,14 +835,6 @@ int lbm_set_inlet_profile(lbm_ctx* c, const double* u, int ny) {
     for (int y = 0; y < ny; ++y)   // the Zou-He inlet divides by 1 - u
         if (!std::isfinite(u[y]) || u[y] >= 1.0)
             return fail(LBM_ERR_ARG, "lbm_set_inlet_profile: row %d has velocity %g (finite values below 1 only)", y, u[y]);
-    // The tables cover every global row, not only the strip's rows +- GR: the register kernel's garbage cells beyond a partial band
-    // may evaluate the inlet of any row of the domain, and a whole table keeps that read in bounds without a test in the kernel.
-    std::vector<double> feqrow((size_t)ny * Q);
-    for (int y = 0; y < ny; ++y) {
-        double f[Q];
-        feq_inflow(u[y], f);
-        for (int i = 0; i < Q; ++i) feqrow[(size_t)y * Q + i] = f[i];
-    }
     unsigned long long d = 1469598103934665603ull;   // FNV-1a over ny and the bit patterns of the velocities
     auto mix = [&](unsigned v) { d ^= v; d *= 1099511628211ull; };
     mix((unsigned)ny);
@@ -780,10 +845,9 @@ int lbm_set_inlet_profile(lbm_ctx* c, const double* u, int ny) {
     }
     HIPCHK(hipSetDevice(c->device));
     c->has_profile = false;
-    if (c->d_feqrow) { HIPCHK(hipFree(c->d_feqrow)); c->d_feqrow = nullptr; }
-    HIPCHK(hipMalloc(&c->d_feqrow, feqrow.size() * c->esize));
-    if (int rc = upload_rows(c, c->d_feqrow, feqrow.data(), feqrow.size())) return rc;
+    if (int rc = upload_feqrow(c, u, ny)) return rc;
     if (int rc = upload_rows(c, c->d_urow, u, (size_t)ny)) return rc;
+    c->h_urow.assign(u, u + ny);
     c->prof_digest = d;
     c->has_profile = true;
     return LBM_OK;
@@ -819,6 +883,33 @@ int lbm_get_wall(const lbm_ctx* c, int side, int* kind, double* velocity) {
     if (side != LBM_WALL_SOUTH && side != LBM_WALL_NORTH) return fail(LBM_ERR_ARG, "lbm_get_wall: side = %d (0 south or 1 north only)", side);
     if (kind) *kind = c->wall_kind[side];
     if (velocity) *velocity = c->wall_u[side];
+    return LBM_OK;
+}
+
+int lbm_set_inlet_schedule(lbm_ctx* c, const double* s, int n, int mode) {
+    if (!c) return fail(LBM_ERR_ARG, "lbm_set_inlet_schedule: null context");
+    if (c->initialised) return fail(LBM_ERR_ARG, "lbm_set_inlet_schedule must be called before lbm_initialise");
+    if (int rc = check_schedule("lbm_set_inlet_schedule", s, n, mode)) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    c->sched.clear();
+    c->sched_mode = LBM_INLET_HOLD;
+    c->sched_digest = 0;
+    if (c->d_sched) { HIPCHK(hipFree(c->d_sched)); c->d_sched = nullptr; }
+    if (n == 0) return LBM_OK;
+    c->sched.assign(s, s + n);
+    c->sched_mode = mode;
+    c->sched_digest = schedule_digest(s, n, mode);
+    const int rc = DISPATCH(c, upload_schedule<double>(c), upload_schedule<float>(c));
+    if (rc) { c->sched.clear(); if (c->d_sched) { (void)hipFree(c->d_sched); c->d_sched = nullptr; } }
+    return rc;
+}
+
+int lbm_inlet_schedule_length(const lbm_ctx* c) { return c ? (int)c->sched.size() : 0; }
+
+int lbm_get_inlet_scale(const lbm_ctx* c, int t, double* s_out) {
+    if (!c || !s_out) return fail(LBM_ERR_ARG, "lbm_get_inlet_scale: null argument");
+    if (t < 0) return fail(LBM_ERR_ARG, "lbm_get_inlet_scale: t = %d (iterations count from 0)", t);
+    *s_out = DISPATCH(c, (double)inlet_scale<double>(c, t), (double)inlet_scale<float>(c, t));
     return LBM_OK;
 }
 
@@ -1001,14 +1092,15 @@ int lbm_save_state(lbm_ctx* c, const char* path) {
     if (!fp) return fail(LBM_ERR_ARG, "cannot open %s for writing", path);
     CkptHeader h{};
     const CollisionModel& cm = collision_model(c->collision);
-    const bool v3 = c->has_profile || cm.ckpt_bit || c->has_walls();
+    const bool v3 = c->has_profile || cm.ckpt_bit || c->has_walls() || c->has_sched();
     memcpy(h.magic, v3 ? "LBMCKPT3" : c->has_mask ? "LBMCKPT2" : "LBMCKPT1", 8);
     h.nx = c->nx; h.ny = c->p.ny; h.y_start = c->p.y_start; h.local_ny = c->nyl; h.precision = c->p.precision;
     h.steps_done = c->steps_done; h.tau = c->p.tau; h.inlet_velocity = c->p.inlet_velocity;
     h.cylinder_x = c->p.cylinder_x; h.cylinder_y = c->p.cylinder_y; h.cylinder_radius = c->p.cylinder_radius;
     int rc = fwrite(&h, sizeof(h), 1, fp) == 1 ? LBM_OK : fail(LBM_ERR_ARG, "short write");
     if (!rc && v3) {   // flags, then what they announce
-        const unsigned long long flags = (c->has_mask ? 1ull : 0ull) | (c->has_profile ? 2ull : 0ull) | cm.ckpt_bit | (c->has_walls() ? CKPT_WALLS : 0ull);
+        const unsigned long long flags = (c->has_mask ? 1ull : 0ull) | (c->has_profile ? 2ull : 0ull) | cm.ckpt_bit | (c->has_walls() ? CKPT_WALLS : 0ull) |
+                                         (c->has_sched() ? CKPT_SCHED : 0ull);
         if (fwrite(&flags, sizeof(flags), 1, fp) != 1) rc = fail(LBM_ERR_ARG, "short write");
     }
     if (!rc && c->has_mask && fwrite(&c->hmask.digest, sizeof(c->hmask.digest), 1, fp) != 1) rc = fail(LBM_ERR_ARG, "short write");
@@ -1018,6 +1110,7 @@ int lbm_save_state(lbm_ctx* c, const char* path) {
         const double w[4] = {(double)c->wall_kind[0], c->wall_u[0], (double)c->wall_kind[1], c->wall_u[1]};
         if (fwrite(w, sizeof(w), 1, fp) != 1) rc = fail(LBM_ERR_ARG, "short write");
     }
+    if (!rc && c->has_sched() && fwrite(&c->sched_digest, sizeof(c->sched_digest), 1, fp) != 1) rc = fail(LBM_ERR_ARG, "short write");
     if (!rc) rc = DISPATCH(c, do_save<double>(c, fp), do_save<float>(c, fp));
     fclose(fp);
     return rc;
@@ -1040,11 +1133,11 @@ int lbm_load_state(lbm_ctx* c, const char* path) {
     if (!fp) return fail(LBM_ERR_ARG, "cannot open %s", path);
     CkptHeader h{};
     int rc = LBM_OK;
-    unsigned long long digest = 0, flags = 0, pdigest = 0;
+    unsigned long long digest = 0, flags = 0, pdigest = 0, sdigest = 0;
     constexpr int NM = (int)std::size(collision_models);
     double param[NM] = {};             // the parameter of each model the file announces
     double walls[4] = {0.0, 0.0, 0.0, 0.0};   // {south kind, south velocity, north kind, north velocity} of the file; none: no-slip
-    unsigned long long known = 3 | CKPT_WALLS;
+    unsigned long long known = 3 | CKPT_WALLS | CKPT_SCHED;
     for (const CollisionModel& m : collision_models) known |= m.ckpt_bit;
     const bool head = fread(&h, sizeof(h), 1, fp) == 1;
     const bool v1 = head && memcmp(h.magic, "LBMCKPT1", 8) == 0;
@@ -1053,7 +1146,8 @@ int lbm_load_state(lbm_ctx* c, const char* path) {
               (!(flags & 1) || fread(&digest, sizeof(digest), 1, fp) == 1) && (!(flags & 2) || fread(&pdigest, sizeof(pdigest), 1, fp) == 1);
     for (int i = 0; i < NM; ++i) v3 = v3 && (!(flags & collision_models[i].ckpt_bit) || fread(&param[i], sizeof(double), 1, fp) == 1);
     v3 = v3 && (!(flags & CKPT_WALLS) || fread(walls, sizeof(walls), 1, fp) == 1);
-    const bool f_mask = v2 || (v3 && (flags & 1)), f_prof = v3 && (flags & 2), f_walls = v3 && (flags & CKPT_WALLS);
+    v3 = v3 && (!(flags & CKPT_SCHED) || fread(&sdigest, sizeof(sdigest), 1, fp) == 1);
+    const bool f_mask = v2 || (v3 && (flags & 1)), f_prof = v3 && (flags & 2), f_walls = v3 && (flags & CKPT_WALLS), f_sched = v3 && (flags & CKPT_SCHED);
     if (!v1 && !v2 && !v3) rc = fail(LBM_ERR_ARG, "%s is not a checkpoint", path);
     else if ((rc = refuse_collision_mismatch(c, path, v3 ? flags : 0, param))) {}
     else if (!f_walls && c->has_walls()) rc = fail(LBM_ERR_ARG, "checkpoint %s was written with two no-slip walls; this context has a %s south wall and a %s north wall",
@@ -1066,6 +1160,9 @@ int lbm_load_state(lbm_ctx* c, const char* path) {
     else if (!f_prof && c->has_profile) rc = fail(LBM_ERR_ARG, "checkpoint %s was written without an inlet profile; this context has one", path);
     else if (f_prof && !c->has_profile) rc = fail(LBM_ERR_ARG, "checkpoint %s was written with an inlet profile; this context has none", path);
     else if (f_prof && pdigest != c->prof_digest) rc = fail(LBM_ERR_ARG, "checkpoint %s was written for a different inlet profile", path);
+    else if (!f_sched && c->has_sched()) rc = fail(LBM_ERR_ARG, "checkpoint %s was written without an inlet schedule; this context has one", path);
+    else if (f_sched && !c->has_sched()) rc = fail(LBM_ERR_ARG, "checkpoint %s was written with an inlet schedule; this context has none", path);
+    else if (f_sched && sdigest != c->sched_digest) rc = fail(LBM_ERR_ARG, "checkpoint %s was written for a different inlet schedule", path);
     else if (!f_mask && c->has_mask) rc = fail(LBM_ERR_ARG, "checkpoint %s was written without an obstacle mask; this context has one", path);
     else if (f_mask && !c->has_mask) rc = fail(LBM_ERR_ARG, "checkpoint %s was written with an obstacle mask; this context has none", path);
     else if (f_mask && digest != c->hmask.digest) rc = fail(LBM_ERR_ARG, "checkpoint %s was written for a different obstacle mask", path);
@@ -1251,6 +1348,21 @@ int lbm_debug_wall_rule(int side, int kind, double velocity, int precision, cons
     if (int rc = check_wall("lbm_debug_wall_rule", side, kind, velocity)) return rc;
     if (precision == LBM_PRECISION_F32) debug_wall_rule<float>(side, kind, velocity, f_in9, f_out9);
     else debug_wall_rule<double>(side, kind, velocity, f_in9, f_out9);
+    return LBM_OK;
+}
+
+/* TEST HOOK (no device needed): the factor (double)(T)s(t) of each of nt iterations, through inlet_sched_index (lbm_kernels.hpp), the function
+ * the kernels and the snapshot call. */
+int lbm_debug_inlet_scale(const double* s, int n, int mode, int precision, const int* t, int nt, double* out) {
+    if (!t || !out || nt < 0) return fail(LBM_ERR_ARG, "lbm_debug_inlet_scale: null pointer or nt < 0");
+    if (precision != LBM_PRECISION_F64 && precision != LBM_PRECISION_F32) return fail(LBM_ERR_ARG, "lbm_debug_inlet_scale: precision = %d", precision);
+    if (int rc = check_schedule("lbm_debug_inlet_scale", s, n, mode)) return rc;
+    if (n == 0) return fail(LBM_ERR_ARG, "lbm_debug_inlet_scale: n = 0 (an empty table has no factor)");
+    for (int i = 0; i < nt; ++i) {
+        if (t[i] < 0) return fail(LBM_ERR_ARG, "lbm_debug_inlet_scale: t[%d] = %d (iterations count from 0)", i, t[i]);
+        const double v = s[inlet_sched_index(t[i], n, mode)];
+        out[i] = precision == LBM_PRECISION_F32 ? (double)(float)v : v;
+    }
     return LBM_OK;
 }
 

@@ -141,7 +141,7 @@ __global__ void __launch_bounds__(NW * 64, (col_min_waves<T, NW, AR>())) k_stepc
                     const long c = (long)(y + GR) * a.pitch + a.xoff + x;
 #pragma unroll
                     for (int i = 0; i < Q; ++i) g[j][i] = a.src[(long)i * a.plane + c - (long)cy(i) * a.pitch - cx(i)];
-                    cell_update_as<T, AR, true>(a, g[j], x, yg, (sbits >> j) & 1u, fr.near_solid, true, bad);
+                    cell_update_as<T, AR, true>(a, g[j], x, yg, 0, (sbits >> j) & 1u, fr.near_solid, true, bad);
                 }
             }
         }
@@ -181,7 +181,7 @@ __global__ void __launch_bounds__(NW * 64, (col_min_waves<T, NW, AR>())) k_stepc
                         for (int i = 0; i < Q; ++i) f[i] = outside_value(e, row_in, col_in, i);
                         store = false;
                     } else {
-                        cell_update_as<T, AR, true>(a, f, x, yg, (sbits >> j) & 1u, fr.near_solid, valid && y <= y_end + HW - L, badl);
+                        cell_update_as<T, AR, true>(a, f, x, yg, L - 1, (sbits >> j) & 1u, fr.near_solid, valid && y <= y_end + HW - L, badl);
                         store = store && y < y_end && !((sbits >> j) & 1u);
                     }
                 }

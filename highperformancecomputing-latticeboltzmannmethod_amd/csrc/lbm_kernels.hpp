@@ -120,9 +120,10 @@ struct KArgs {
     const T* u_row;    // inlet velocity of global row yg at u_row[yg], every row of the domain: inlet_velocity on every row, or the
                        // profile of lbm_set_inlet_profile. Read on the inlet column (x == 0) only, inside apply_bcs
     int* unstable_t;   // device word: first unstable iteration (INT_MAX if none)
-    int t;             // iteration this launch completes, RELATIVE to *t_base (stability bookkeeping only)
+    int t;             // iteration this launch completes, RELATIVE to *t_base (stability bookkeeping; the inlet schedule's entry)
     const int* t_base; // device word: the iteration `t` counts from. A launch replayed from a hipGraph carries a fixed `t`; the
-                       // word is advanced on the device between replays. Read on the (rare) unstable path only.
+                       // word is advanced on the device between replays. Read on the (rare) unstable path, and on the inlet column
+                       // of a context with an inlet schedule (bcs_at), only.
     int y_lo, y_cnt;   // local rows [y_lo, y_lo + y_cnt) covered by this launch
     int y_lo2, y_cnt2; // optional second range [y_lo2, y_lo2 + y_cnt2) of the same launch (both edge bands of a strip
                        // in one grid); y_cnt2 == 0: none
@@ -141,6 +142,9 @@ struct KArgs {
     // operands otherwise). Launch-uniform: read inside the bottom / top branches of apply_bcs only.
     int walls;
     WallK<T> wk;
+    // The inlet schedule (lbm_set_inlet_schedule), appended likewise: the device block {int n; int mode; T s[n]} (inlet_sched_at), nullptr
+    // without one. Launch-uniform: tested and read inside the inlet branch of apply_bcs only.
+    const int* sched;
 };
 
 // Row handled by blockIdx.y. Blocks are dispatched roughly in index order; walking the rows in the opposite
@@ -188,6 +192,21 @@ __device__ __forceinline__ bool tile_near_solid(const KArgs<T>& a, int X0, int Y
            yg0 - ring <= a.cyl_y + r && yg0 + TY - 1 + ring >= a.cyl_y - r;
 }
 
+// The inlet schedule (lbm_set_inlet_schedule): which entry of a table of n scale factors iteration t >= 0 takes. HOLD (mode 0): the last
+// entry holds for ever; REPEAT (mode 1): the table is periodic. The one statement of it: the step kernels, the snapshot's host side
+// (lbm_get_inlet_scale, MacroArgs::in_scale) and lbm_debug_inlet_scale call this function.
+// Unsigned arithmetic: the result lies in [0, n) for every bit pattern of t, so no iteration number can take a read out of the table.
+__host__ __device__ inline int inlet_sched_index(int t, int n, int mode) {
+    const unsigned ut = (unsigned)t, un = (unsigned)n;
+    return (int)(mode == 1 ? ut % un : (ut < un - 1u ? ut : un - 1u));
+}
+// The schedule as the kernels read it: two ints, then the n factors in the element type at byte 8 (aligned for both types).
+constexpr int INLET_SCHED_HEAD = 2;
+template <typename T>
+__device__ __forceinline__ T inlet_sched_at(const int* sched, int t) {
+    return reinterpret_cast<const T*>(sched + INLET_SCHED_HEAD)[inlet_sched_index(t, sched[0], sched[1])];
+}
+
 // The wall rule of ONE cell of global row 0 (bottom) or ny - 1 (top): the reference's on-node bounce-back (:155-163, :168-176) with the
 // wall's kind deciding what the two diagonal populations it writes become:
 //   no-slip    f5 = f7, f6 = f8 (south); f7 = f5, f8 = f6 (north): the reference's
@@ -219,12 +238,15 @@ __host__ __device__ __forceinline__ void wall_rule(T (&f)[Q], bool bottom, bool 
 // of those loops. Returns nothing; rho_bc/u_out are exposed for the macro snapshot kernel.
 // The inlet velocity of global row yg is u_row[yg] (KArgs::u_row): loaded inside the inlet branch only, so no cell off column 0
 // carries its address or value. The two walls are wall_rule above: the one statement of it, for the step kernels and the snapshot.
-template <typename T>
-__device__ __forceinline__ void apply_bcs(T (&f)[Q], bool bottom, bool top, bool inlet, bool outlet, const T* u_row, int yg,
+// `inlet_u` gives the inlet velocity of the cell's row at the iteration served and is called inside the inlet branch only: u_row[yg],
+// times the schedule's factor where there is one — ONE IEEE multiplication in the element type, rounded before the two uses below (the
+// library is built without contraction), so strict and contracted arithmetic apply the same bits here.
+template <typename T, typename U>
+__device__ __forceinline__ void apply_bcs(T (&f)[Q], bool bottom, bool top, bool inlet, bool outlet, U&& inlet_u,
                                           int walls, const WallK<T>& wk, T& rho_bc, T& u_out) {
     wall_rule(f, bottom, top, walls, wk);
     if (inlet) {                                                              // :181-206 (Zou-He velocity)
-        const T u_in = u_row[yg];
+        const T u_in = inlet_u();
         rho_bc = (f[0] + f[2] + f[4] + T(2.0) * (f[3] + f[6] + f[7])) / (T(1.0) - u_in);
         f[1] = f[3] + T(2.0 / 3.0) * rho_bc * u_in;
         f[5] = f[7] - T(0.5) * (f[2] - f[4]) + T(1.0 / 6.0) * rho_bc * u_in;
@@ -238,11 +260,18 @@ __device__ __forceinline__ void apply_bcs(T (&f)[Q], bool bottom, bool top, bool
         f[7] = f[5] + T(0.5) * (f[2] - f[4]) - T(1.0 / 6.0) * rho_out * u_out;
     }
 }
-// apply_bcs at global cell (x, yg) for the step kernels. `a`: any argument block with nx, ny_glob, u_row and the walls (KArgs, MacroArgs).
-template <typename A, typename T>
-__device__ __forceinline__ void bcs_at(const A& a, T (&f)[Q], int x, int yg) {
+// apply_bcs at global cell (x, yg) for the step kernels, at level `lvl` (0-based) of the launch: iteration *t_base + t + lvl, the number
+// the first-unstable bookkeeping forms. The device word is read under the schedule's test only — a captured graph carries a fixed `t` and
+// advances the word itself, so replays take the right entry with no host involvement. Everything the schedule touches is launch- and
+// level-uniform.
+template <typename T>
+__device__ __forceinline__ void bcs_at(const KArgs<T>& a, T (&f)[Q], int x, int yg, int lvl) {
     T rho_bc, u_out;
-    apply_bcs(f, yg == 0, yg == a.ny_glob - 1, x == 0, x == a.nx - 1, a.u_row, yg, a.walls, a.wk, rho_bc, u_out);
+    apply_bcs(f, yg == 0, yg == a.ny_glob - 1, x == 0, x == a.nx - 1, [&]() {
+        T u = a.u_row[yg];
+        if (a.sched) u = u * inlet_sched_at<T>(a.sched, *a.t_base + a.t + lvl);
+        return u;
+    }, a.walls, a.wk, rho_bc, u_out);
 }
 
 // Arithmetic of the collision (the only place the two modes differ):
@@ -541,7 +570,7 @@ __global__ void __launch_bounds__(256) k_step_site(const KArgs<T> a) {
         f[i] = a.src[(long)i * a.plane + c - off];
     }
     const bool solid = solid_at(a, x, yg);
-    if (MODE != MODE_COLLIDE_ONLY && !solid) bcs_at(a, f, x, yg);
+    if (MODE != MODE_COLLIDE_ONLY && !solid) bcs_at(a, f, x, yg, 0);
     if (MODE == MODE_STEP) {
         if (any_unstable(f)) atomicMin(a.unstable_t, *a.t_base + a.t);
     }
@@ -586,13 +615,13 @@ template <typename T> struct K2Extra {
 // (The general nine pulls stay written out in the kernels, and outside_value gives one value, not a cell: a loop over a cell
 // that is unrolled inside a helper before it is inlined compiles differently — two more VGPRs in k_step2_tile fp32.)
 
-// One general cell of a level (any cell of a non-LEAN path): BCs unless solid, the stability test where `count`, the
+// One general cell of level lvl + 1 (any cell of a non-LEAN path): BCs of that level's iteration unless solid, the stability test where `count`, the
 // collision; a solid cell keeps w_i (its collision result is discarded). `near_solid` is block-uniform: tiles far from every
 // solid cell skip the select. BRANCH_FREE: the stability test is unstable_if (k_stepc_col, whose garbage cells are masked).
 template <typename T, int AR, bool BRANCH_FREE = false>
-__device__ __forceinline__ void cell_update_as(const KArgs<T>& a, T (&f)[Q], int x, int yg, bool solid, bool near_solid, bool count,
-                                               bool& bad) {
-    if (!solid) bcs_at(a, f, x, yg);
+__device__ __forceinline__ void cell_update_as(const KArgs<T>& a, T (&f)[Q], int x, int yg, int lvl, bool solid, bool near_solid,
+                                               bool count, bool& bad) {
+    if (!solid) bcs_at(a, f, x, yg, lvl);
     if (BRANCH_FREE) bad |= unstable_if(f, count);
     else if (count) bad |= any_unstable(f);
     collide<T, AR>(f, a);
@@ -603,17 +632,17 @@ __device__ __forceinline__ void cell_update_as(const KArgs<T>& a, T (&f)[Q], int
 }
 // ... with the geometry looked up here (block-uniform branch: only tiles near a solid cell)
 template <typename T, int AR>
-__device__ __forceinline__ void cell_update(const KArgs<T>& a, T (&f)[Q], int x, int yg, bool near_solid, bool count, bool& bad) {
+__device__ __forceinline__ void cell_update(const KArgs<T>& a, T (&f)[Q], int x, int yg, int lvl, bool near_solid, bool count, bool& bad) {
     bool solid = false;
     if (near_solid) solid = solid_at(a, x, yg);
-    cell_update_as<T, AR>(a, f, x, yg, solid, near_solid, count, bad);
+    cell_update_as<T, AR>(a, f, x, yg, lvl, solid, near_solid, count, bad);
 }
 // A general cell of the last level, which stores: every cell is counted, and a solid cell is neither collided nor stored
 // (false: do not store the cell).
 template <typename T, int AR>
-__device__ __forceinline__ bool cell_update_last(const KArgs<T>& a, T (&f)[Q], int x, int yg, bool near_solid, bool& bad) {
+__device__ __forceinline__ bool cell_update_last(const KArgs<T>& a, T (&f)[Q], int x, int yg, int lvl, bool near_solid, bool& bad) {
     const bool solid = near_solid && solid_at(a, x, yg);
-    if (!solid) bcs_at(a, f, x, yg);
+    if (!solid) bcs_at(a, f, x, yg, lvl);
     bad |= any_unstable(f);
     if (solid) return false;
     collide<T, AR>(f, a);
@@ -739,7 +768,7 @@ __global__ void __launch_bounds__(NTH) k_step2_tile(const KArgs<T> a, const K2Ex
             const long c = (long)(y + GR) * a.pitch + a.xoff + x;
 #pragma unroll
             for (int i = 0; i < Q; ++i) f[i] = a.src[(long)i * a.plane + c - (long)cy(i) * a.pitch - cx(i)];
-            cell_update<T, AR>(a, f, x, yg, fr.near_solid, true, bad);
+            cell_update<T, AR>(a, f, x, yg, 0, fr.near_solid, true, bad);
         }
 #pragma unroll
         for (int i = 0; i < Q; ++i) lds[i][ry][rx] = f[i];
@@ -754,7 +783,7 @@ __global__ void __launch_bounds__(NTH) k_step2_tile(const KArgs<T> a, const K2Ex
         T f[Q];
 #pragma unroll
         for (int i = 0; i < Q; ++i) f[i] = lds[i][ly + 1 - cy(i)][lx + 1 - cx(i)];
-        if (cell_update_last<T, AR>(a, f, x, a.y_start + y, fr.near_solid, bad)) store_cell(a, f, x, y, e.nt != 0);
+        if (cell_update_last<T, AR>(a, f, x, a.y_start + y, 1, fr.near_solid, bad)) store_cell(a, f, x, y, e.nt != 0);
     }
     if (bad) atomicMin(a.unstable_t, *a.t_base + a.t + 1);
 }
@@ -798,7 +827,7 @@ __device__ __forceinline__ void step_tile(const KArgs<T>& a, const K2Extra<T>& e
                     const long c = (long)(y + GR) * a.pitch + a.xoff + x;
 #pragma unroll
                     for (int i = 0; i < Q; ++i) f[i] = a.src[(long)i * a.plane + c - (long)cy(i) * a.pitch - cx(i)];
-                    cell_update<T, AR>(a, f, x, yg, fr.near_solid, true, bad);
+                    cell_update<T, AR>(a, f, x, yg, 0, fr.near_solid, true, bad);
                 }
             }
 #pragma unroll
@@ -840,7 +869,7 @@ __device__ __forceinline__ void step_tile(const KArgs<T>& a, const K2Extra<T>& e
                     if (LEAN) {
                         badl |= any_unstable(f);
                         collide<T, AR>(f, a);
-                    } else cell_update<T, AR>(a, f, x, yg, fr.near_solid, y <= y_end + HW - L, badl);
+                    } else cell_update<T, AR>(a, f, x, yg, L - 1, fr.near_solid, y <= y_end + HW - L, badl);
                 }
 #pragma unroll
                 for (int i = 0; i < Q; ++i) lds[i][ry][rx] = f[i];
@@ -861,7 +890,7 @@ __device__ __forceinline__ void step_tile(const KArgs<T>& a, const K2Extra<T>& e
                 bad |= any_unstable(f);
                 collide<T, AR>(f, a);
                 fr.store(f, fr.at(ly, lx), fr.dst_off(a, Y0, X0), e.nt != 0);
-            } else if (cell_update_last<T, AR>(a, f, x, a.y_start + y, fr.near_solid, bad)) store_cell(a, f, x, y, e.nt != 0);
+            } else if (cell_update_last<T, AR>(a, f, x, a.y_start + y, D - 1, fr.near_solid, bad)) store_cell(a, f, x, y, e.nt != 0);
         }
         if (bad) atomicMin(a.unstable_t, *a.t_base + a.t + D - 1);
     };
@@ -968,7 +997,7 @@ __global__ void __launch_bounds__(TX * TY, (deep_waves_per_simd<T, TX, TY, D>())
                     const long c = (long)(y + GR) * a.pitch + a.xoff + x;
 #pragma unroll
                     for (int i = 0; i < Q; ++i) f[i] = a.src[(long)i * a.plane + c - (long)cy(i) * a.pitch - cx(i)];
-                    cell_update<T, AR>(a, f, x, yg, fr.near_solid, true, bad);
+                    cell_update<T, AR>(a, f, x, yg, 0, fr.near_solid, true, bad);
                 }
             }
 #pragma unroll
@@ -1010,7 +1039,7 @@ __global__ void __launch_bounds__(TX * TY, (deep_waves_per_simd<T, TX, TY, D>())
                     if (!(row_in && col_in)) {
 #pragma unroll
                         for (int i = 0; i < Q; ++i) g[k][i] = outside_value(e, row_in, col_in, i);
-                    } else cell_update<T, AR>(a, g[k], x, yg, fr.near_solid, y <= y_end + HW - L, badl);
+                    } else cell_update<T, AR>(a, g[k], x, yg, L - 1, fr.near_solid, y <= y_end + HW - L, badl);
                 }
 #pragma unroll
                 for (int i = 0; i < Q; ++i) lds[i][ry][rx] = g[k][i];
@@ -1033,7 +1062,7 @@ __global__ void __launch_bounds__(TX * TY, (deep_waves_per_simd<T, TX, TY, D>())
                     bad |= any_unstable(f);
                     collide<T, AR>(f, a);
                     fr.store(f, fr.at(ly, lx), fr.dst_off(a, Y0, X0), e.nt != 0);
-                } else if (cell_update_last<T, AR>(a, f, x, a.y_start + y, fr.near_solid, bad)) store_cell(a, f, x, y, e.nt != 0);
+                } else if (cell_update_last<T, AR>(a, f, x, a.y_start + y, D - 1, fr.near_solid, bad)) store_cell(a, f, x, y, e.nt != 0);
             }
         }
         if (bad) atomicMin(a.unstable_t, *a.t_base + a.t + D - 1);
@@ -1105,6 +1134,8 @@ struct MacroArgs {
     double* rho; double* ux; double* uy;   // [ny_loc][nx]
     unsigned long long* max_usq_bits;      // optional running max of ux^2+uy^2 (bit pattern of a double >= 0)
     int walls; WallK<T> wk;                // the two walls, as KArgs carries them (appended: the fields above keep their offsets)
+    T in_scale;                            // the inlet schedule's factor of the iteration this snapshot describes, (T)s(t), formed by the host
+                                           // (lbm_set_inlet_schedule); 1 without a schedule: x * 1 changes no bit, so no branch
 };
 
 // the moments of the nine populations of a fluid cell, in the element type: rho and u = (sum c_i f_i) / rho (one definition for
@@ -1137,10 +1168,10 @@ __device__ __forceinline__ void macro_cell(const MacroArgs<T>& p, int x, int y, 
 #pragma unroll
         for (int i = 0; i < Q; ++i) f[i] = p.old[(long)i * p.plane + c - (long)cy(i) * p.pitch - cx(i)];
         T rho_bc = T(1), u_out = T(0);
-        apply_bcs(f, yg == 0, yg == p.ny_glob - 1, x == 0, x == p.nx - 1, p.u_row, yg, p.walls, p.wk, rho_bc, u_out);
+        apply_bcs(f, yg == 0, yg == p.ny_glob - 1, x == 0, x == p.nx - 1, [&]() { return p.u_row[yg] * p.in_scale; }, p.walls, p.wk, rho_bc, u_out);
         // the outlet loop runs after the inlet loop (only matters for nx == 1)
         if (x == p.nx - 1) { r = 1.0; vx = (double)u_out; vy = 0.0; }
-        else { r = (double)rho_bc; vx = (double)p.u_row[yg]; vy = 0.0; }
+        else { r = (double)rho_bc; vx = (double)(p.u_row[yg] * p.in_scale); vy = 0.0; }
     } else {
         T f[Q];
 #pragma unroll

@@ -8,6 +8,13 @@ void fill_walls(const lbm_ctx* c, A& a) {
     a.wk = wall_ks<T>(c->wall_kind[0], c->wall_u[0], c->wall_kind[1], c->wall_u[1]);
 }
 
+// The inlet schedule's factor of iteration t in the element type, (T)s(t); 1 without a schedule (or before iteration 0).
+template <typename T>
+T inlet_scale(const lbm_ctx* c, int t) {
+    if (!c->has_sched() || t < 0) return T(1);
+    return (T)c->sched[(size_t)inlet_sched_index(t, (int)c->sched.size(), c->sched_mode)];
+}
+
 template <typename T>
 KArgs<T> make_kargs(const lbm_ctx* c, int src, int dst, int t) {
     KArgs<T> a;
@@ -47,6 +54,7 @@ KArgs<T> make_kargs(const lbm_ctx* c, int src, int dst, int t) {
         a.trt_wb = (T)(0.5 * (wp - wm));
     }
     fill_walls<T>(c, a);
+    a.sched = static_cast<const int*>(c->d_sched);
     return a;
 }
 
@@ -146,9 +154,10 @@ int launch_step(lbm_ctx* c, int src, int dst, int t, int mode, hipStream_t s) {
 
 // The snapshot's source as k_macros and k_stats take it: the lattice, the geometry and the inlet profile of this strip, read from
 // `src`. One fill for both launches (do_macros, launch_stats), so that the two snapshots cannot differ in their arguments either.
-// initial = 0 and no outputs: the caller sets what it needs.
+// initial = 0 and no outputs: the caller sets what it needs. t: the iteration whose boundary rules the snapshot applies (`src` = P_t),
+// which selects the inlet schedule's factor.
 template <typename T>
-MacroArgs<T> make_macro_args(const lbm_ctx* c, const void* src) {
+MacroArgs<T> make_macro_args(const lbm_ctx* c, const void* src, int t) {
     MacroArgs<T> m;
     m.old = static_cast<const T*>(src);
     m.plane = (long)c->plane; m.pitch = c->pitch; m.xoff = c->xoff;
@@ -157,6 +166,7 @@ MacroArgs<T> make_macro_args(const lbm_ctx* c, const void* src) {
     if (c->has_mask) m.mv = c->mview;
     m.u_row = static_cast<const T*>(c->d_urow);
     fill_walls<T>(c, m);
+    m.in_scale = inlet_scale<T>(c, t);
     m.initial = 0;
     m.rho = m.ux = m.uy = nullptr; m.max_usq_bits = nullptr;
     return m;
@@ -177,7 +187,7 @@ template <typename T>
 int launch_stats(lbm_ctx* c, int t) {
     if (c->rec) { c->stats_n++; return record_sample(c, ChoreoOp::STATS, t); }
     StatsArgs<T> s;
-    s.m = make_macro_args<T>(c, c->buf[c->cur]);
+    s.m = make_macro_args<T>(c, c->buf[c->cur], t);
     s.acc = c->d_stats; s.cells = (long)c->nx * c->nyl;
     dim3 grid((c->nx + 511) / 512, c->nyl), block(256);
     hipLaunchKernelGGL((k_stats<T>), grid, block, 0, c->stream, s);
@@ -243,7 +253,7 @@ template <typename T>
 int launch_frame_sample(lbm_ctx* c, int t) {
     if (c->rec) return record_sample(c, ChoreoOp::FRAME, t);
     FrameArgs<T> f;
-    f.m = make_macro_args<T>(c, c->buf[c->cur]);
+    f.m = make_macro_args<T>(c, c->buf[c->cur], t);
     f.k = c->frames_k; f.cnx = c->nx / c->frames_k; f.cny = c->nyl / c->frames_k;
     f.out = c->frames.next_slot();
     launch_frame<T>(f, c->stream);
@@ -259,7 +269,7 @@ template <typename T>
 int launch_probe_sample(lbm_ctx* c, int t) {
     if (c->rec) return record_sample(c, ChoreoOp::PROBES, t);
     ProbeArgs<T> a;
-    a.m = make_macro_args<T>(c, c->buf[c->cur]);
+    a.m = make_macro_args<T>(c, c->buf[c->cur], t);
     a.table = static_cast<const ProbeEntry*>(c->d_probe_table);
     a.n = c->probe_n;
     a.out = c->probes.next_slot();

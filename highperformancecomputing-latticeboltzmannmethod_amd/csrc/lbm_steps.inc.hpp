@@ -263,8 +263,9 @@ template <typename T>
 int do_macros(lbm_ctx* c, bool want_max) {
     const size_t n = (size_t)c->nx * c->nyl;
     if (!c->d_macro) HIPCHK(hipMalloc(&c->d_macro, 3 * n * sizeof(double)));
-    MacroArgs<T> m = make_macro_args<T>(c, c->buf[c->cur ^ 1]);
+    MacroArgs<T> m = make_macro_args<T>(c, c->buf[c->cur ^ 1], c->steps_done - 1);
     m.initial = (c->steps_done == 0);
+    if (m.initial && c->has_sched()) m.u_row = static_cast<const T*>(c->d_urow0);   // the initial state's profile, u[y] * s[0]
     m.rho = c->d_macro; m.ux = c->d_macro + n; m.uy = c->d_macro + 2 * n;
     m.max_usq_bits = want_max ? c->d_maxbits : nullptr;
     if (want_max) HIPCHK(hipMemsetAsync(c->d_maxbits, 0, sizeof(unsigned long long), c->stream));
@@ -281,7 +282,7 @@ int do_populations(lbm_ctx* c, int which, double* aos) {
     const bool initial = (c->steps_done == 0);
     if (which == 0 && !initial) {
         if (!c->scratch) HIPCHK(hipMalloc(&c->scratch, buffer_bytes(c)));
-        KArgs<T> a = make_kargs<T>(c, c->cur ^ 1, c->cur ^ 1, 0);
+        KArgs<T> a = make_kargs<T>(c, c->cur ^ 1, c->cur ^ 1, c->steps_done - 1);   // (the iteration whose inlet the snapshot applies)
         a.dst = static_cast<T*>(c->scratch);
         launch_rows<T, MODE_STREAM_ONLY>(c, a, c->stream);
         HIPCHK(hipGetLastError());

@@ -642,7 +642,7 @@ int init_state(lbm_ctx* c) {
     ia.cyl_x = c->cyl_x; ia.cyl_y = c->cyl_y; ia.cyl_r2 = (double)(c->cyl_r * c->cyl_r);
     if (c->has_mask) ia.mv = c->mview;
     for (int i = 0; i < Q; ++i) ia.feq_in[i] = (T)c->feq_in[i];
-    ia.feq_row = c->has_profile ? static_cast<const T*>(c->d_feqrow) : nullptr;
+    ia.feq_row = (c->has_profile || c->has_sched()) ? static_cast<const T*>(c->d_feqrow) : nullptr;
     ia.solid_count = c->d_solid_count;
     HIPCHK(hipMemsetAsync(c->d_solid_count, 0, sizeof(int), c->stream));
     dim3 grid((c->nx + 2 + 255) / 256, c->nyl + 2 * GR), block(256);

@@ -51,6 +51,8 @@ public:
             if (p.bodied()) check(lbm_set_body_labels(c, p.obstacle_mask.data(), p.nx, p.ny), "lbm_set_body_labels");
             else if (p.masked()) check(lbm_set_solid_mask(c, p.obstacle_mask.data(), p.nx, p.ny), "lbm_set_solid_mask");
             if (p.profiled()) check(lbm_set_inlet_profile(c, p.inlet_profile.data(), p.ny), "lbm_set_inlet_profile");
+            if (p.scheduled())   // every strip is given the same schedule: the halo rows a strip recomputes use the same global iteration
+                check(lbm_set_inlet_schedule(c, p.inlet_schedule.data(), (int)p.inlet_schedule.size(), p.inlet_schedule_mode), "lbm_set_inlet_schedule");
             if (p.les()) check(lbm_set_smagorinsky(c, p.smagorinsky_cs), "lbm_set_smagorinsky");
             if (p.trt()) check(lbm_set_trt(c, p.trt_magic), "lbm_set_trt");
             if (p.walled())      // every strip carries both walls; only the strips that hold row 0 / ny - 1 use them

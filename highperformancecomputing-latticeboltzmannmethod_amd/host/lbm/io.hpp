@@ -313,6 +313,7 @@ private:
             f.put("wall_south,"); f.put(p.wall_text(0).c_str()); f.put("\n");
             f.put("wall_north,"); f.put(p.wall_text(1).c_str()); f.put("\n");
         }
+        if (p.scheduled()) { f.put("inlet_schedule,"); f.put(p.inlet_schedule_spec.c_str()); f.put("\n"); }   // (runs with an inlet schedule only; the last line)
         std::printf("  simulation_params.csv written\n");
     }
     // calculate_time_averaged_drag (LBMIO.h:367-413): statistics of the CSV values (8 decimals) for timestep > 1000.

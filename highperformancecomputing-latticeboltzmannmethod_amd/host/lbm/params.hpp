@@ -47,6 +47,13 @@ struct SimulationParams {
     // absolute velocities, row 0 first, whose mean is inlet_velocity (host/lbm/inlet.hpp). Empty: inlet_velocity on every row.
     std::string inlet_profile_spec;
     std::vector<double> inlet_profile;
+    // inlet schedule (lbm_solver --inlet-ramp N | --inlet-pulse A:P | --inlet-schedule FILE [--inlet-schedule-repeat]; not in the
+    // reference, whose inflow is frozen): how it was asked for ("ramp:N", "pulse:A:P", "FILE" or "FILE:repeat"), the scale factor of
+    // the inflow per iteration and the mode (0 hold the last entry, 1 repeat) as lbm_set_inlet_schedule takes them (host/lbm/inlet.hpp).
+    // Empty: the frozen inflow. The moving walls' velocity is not scaled, and Cd / Cl keep referring to inlet_velocity.
+    std::string inlet_schedule_spec;
+    std::vector<double> inlet_schedule;
+    int inlet_schedule_mode = 0;
     // Smagorinsky LES collision (lbm_solver --smagorinsky; not in the reference): the constant Cs, 0 = plain BGK. tau, nu() and
     // reynolds() keep referring to the molecular viscosity.
     double smagorinsky_cs = 0.0;
@@ -75,6 +82,7 @@ struct SimulationParams {
     bool bodied() const { return !obstacle_bodies_file.empty(); }
     int body_count() const { return (int)body_height.size(); }
     bool profiled() const { return !inlet_profile.empty(); }
+    bool scheduled() const { return !inlet_schedule.empty(); }
     bool les() const { return smagorinsky_cs > 0.0; }
     bool trt() const { return trt_magic > 0.0; }
     bool stats() const { return stats_start >= 0; }

@@ -42,6 +42,10 @@ public:
         }
         if (!opt_.quiet && params_.profiled())
             std::printf("  Inlet: profile %s, mean velocity %g (Cd / Cl refer to it)\n", params_.inlet_profile_spec.c_str(), params_.inlet_velocity);
+        if (!opt_.quiet && params_.scheduled())
+            std::printf("  Inlet: schedule %s, %d factors, %s (the inflow of iteration t is scaled by s(t); the walls are not; Cd / Cl refer to the inlet velocity %g)\n",
+                        params_.inlet_schedule_spec.c_str(), (int)params_.inlet_schedule.size(),
+                        params_.inlet_schedule_mode ? "repeated" : "the last one holds", params_.inlet_velocity);
         if (!opt_.quiet && params_.les())
             std::printf("  Collision: Smagorinsky LES, Cs = %g (tau and the Reynolds number refer to the molecular viscosity)\n",
                         params_.smagorinsky_cs);

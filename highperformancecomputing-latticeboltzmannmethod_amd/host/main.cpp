@@ -25,6 +25,7 @@ static void usage() {
               "           [--inlet-profile parabolic|FILE] [--print-inlet-profile] [--smagorinsky CS] [--trt-magic LAMBDA]\n"
               "           [--stats-start N] [--wall-south KIND] [--wall-north KIND] [--walls KIND]\n"
               "           [--frame-stride K] [--probes FILE] [--probe-line x0 y0 x1 y1 n]\n"
+              "           [--inlet-ramp N | --inlet-pulse A:P | --inlet-schedule FILE [--inlet-schedule-repeat]] [--print-inlet-schedule]\n"
               "Defaults are the reference's SimulationParams (LBMConfig.h:37-51). --reynolds sets the inlet velocity\n"
               "from tau and the cylinder diameter so that params.reynolds() equals RE.\n"
               "--gpus N cuts the lattice into N row strips, one per GPU of this node, advanced in lockstep by this process\n"
@@ -40,6 +41,14 @@ static void usage() {
               "allowed), giving the shape. Either is scaled so that its mean over the ny rows is the inlet velocity, which\n"
               "stays the reference velocity: Reynolds number, --reynolds and Cd / Cl refer to the bulk (mean) velocity.\n"
               "--print-inlet-profile: print the ny inlet velocities (row 0 first) and exit without opening a device.\n"
+              "--inlet-ramp N / --inlet-pulse A:P / --inlet-schedule FILE: a time-dependent inflow; the inlet velocity of every row is\n"
+              "multiplied by one factor s(t) per iteration t (counted from the start of the run, across --restart). ramp: the N + 1\n"
+              "factors 0.5 (1 - cos(pi k / N)), from rest to the full inflow, the last one held; pulse: the P factors\n"
+              "1 + A sin(2 pi k / P), repeated; FILE: a text file of up to 1048576 numbers ('#' comments allowed), the last one held,\n"
+              "or repeated with --inlet-schedule-repeat. The three exclude each other. Negative factors reverse the inflow. The\n"
+              "velocity of moving walls is not scaled, and Reynolds number and Cd / Cl keep referring to the inlet velocity. A ramp\n"
+              "should be long against L / c_s: accelerating the channel needs a pressure difference against the outlet's fixed density.\n"
+              "--print-inlet-schedule: print the factors and exit without opening a device.\n"
               "--smagorinsky CS: Smagorinsky LES collision with constant CS in [0, 1] (0: plain BGK) instead of BGK, for\n"
               "higher Reynolds numbers at the same tau. tau, the Reynolds number and --reynolds keep referring to the\n"
               "molecular viscosity (tau - 0.5) / 3; the eddy viscosity of the model is added per cell.\n"
@@ -72,6 +81,8 @@ int main(int argc, char** argv) {
     bool vtk = true, final_results = true;
     std::string restart_from, checkpoint_to;
     bool print_profile = false;
+    bool print_schedule = false, schedule_repeat = false;
+    std::string schedule_option, schedule_file;   // which of the three sources gave the schedule; the FILE of --inlet-schedule
     const char* smagorinsky = nullptr;
     const char* trt_magic = nullptr;
     const char* stats_start = nullptr;
@@ -126,6 +137,22 @@ int main(int argc, char** argv) {
                 return 2;
             }
         }
+        else if (k == "--inlet-ramp" || k == "--inlet-pulse" || k == "--inlet-schedule") {   // parsed here: no device is touched before a bad value exits
+            try {
+                const std::string text = val();
+                if (!schedule_option.empty())
+                    throw std::invalid_argument(k + " cannot be combined with " + schedule_option + " (one inlet schedule at a time)");
+                schedule_option = k;
+                if (k == "--inlet-ramp") { params.inlet_schedule = LBM::parse_inlet_ramp(text); params.inlet_schedule_spec = "ramp:" + text; }
+                else if (k == "--inlet-pulse") { params.inlet_schedule = LBM::parse_inlet_pulse(text); params.inlet_schedule_spec = "pulse:" + text; params.inlet_schedule_mode = 1; }
+                else { params.inlet_schedule = LBM::read_inlet_schedule(text); params.inlet_schedule_spec = schedule_file = text; }
+            } catch (const std::exception& e) {
+                std::fprintf(stderr, "%s\n", e.what());
+                return 2;
+            }
+        }
+        else if (k == "--inlet-schedule-repeat") schedule_repeat = true;
+        else if (k == "--print-inlet-schedule") print_schedule = true;
         else if (k == "--frame-stride") frame_stride = val();
         else if (k == "--probes" || k == "--probe-line") {   // parsed here, in the order given; checked against the lattice below
             try {
@@ -265,6 +292,24 @@ int main(int argc, char** argv) {
         if (!params.profiled()) { std::fprintf(stderr, "--print-inlet-profile needs --inlet-profile\n"); return 2; }
         for (double u : params.inlet_profile) std::printf("%.17g\n", u);
         return 0;
+    }
+    if (schedule_repeat) {   // the mode of --inlet-schedule FILE alone: a ramp holds and a pulse repeats by what they are
+        if (schedule_file.empty()) { std::fprintf(stderr, "--inlet-schedule-repeat needs --inlet-schedule FILE\n"); return 2; }
+        params.inlet_schedule_mode = 1;
+        params.inlet_schedule_spec += ":repeat";
+    }
+    if (print_schedule) {
+        if (!params.scheduled()) { std::fprintf(stderr, "--print-inlet-schedule needs --inlet-ramp, --inlet-pulse or --inlet-schedule\n"); return 2; }
+        for (double s : params.inlet_schedule) std::printf("%.17g\n", s);
+        return 0;
+    }
+    if (params.scheduled()) {   // against the final inlet velocities, checked before any device is touched: the inlet divides by 1 - u s
+        try {
+            LBM::check_inlet_schedule(params.profiled() ? params.inlet_profile : std::vector<double>(1, params.inlet_velocity), params.inlet_schedule);
+        } catch (const std::exception& e) {
+            std::fprintf(stderr, "%s\n", e.what());
+            return 2;
+        }
     }
     try {
         LBM::Solver solver(params, vtk, opt);

@@ -263,6 +263,41 @@ int  lbm_set_solid_mask(lbm_ctx* c, const unsigned char* mask, int nx, int ny);
  * LBM_ERR_ARG: null pointer, ny other than the domain's, an initialised context, or a value that is not finite or is >= 1 (the
  * inlet divides by 1 - u). */
 int  lbm_set_inlet_profile(lbm_ctx* c, const double* u, int ny);
+/* The inflow in time: generalises the Zou-He velocity inlet (LBMSolver.h:181-206), whose velocity is frozen for the whole run, to one
+ * scale factor per iteration. No reference counterpart. A schedule is a table s[0..n) of doubles and a mode; iteration t — the absolute
+ * loop-body number, the t of lbm_steps_done, continuing across checkpoints — takes
+ *     LBM_INLET_HOLD   0   s(t) = s[min(t, n - 1)]   (ramps: the last entry holds for ever)
+ *     LBM_INLET_REPEAT 1   s(t) = s[t mod n]         (periodic forcing)
+ * and the inlet of iteration t imposes u_in = u[y] * s(t) on row y, u[y] being inlet_velocity or the profile of
+ * lbm_set_inlet_profile. The table is cast once to the element type (memory: n elements on the device), and the product is ONE IEEE
+ * multiplication in the element type, rounded before 1 - u_in and rho_bc * u_in use it, so strict and contracted arithmetic (option
+ * "arith") apply the same bits in the inlet rule. Nothing else changes: the order bottom -> top -> inlet -> outlet on a cell stays, solid
+ * inlet cells are skipped. Every fused level of a launch takes the factor of its own iteration, read on the device (a replayed graph
+ * included). Negative factors are allowed: the inlet then acts as an outflow. The moving walls' velocity is not scaled, and a schedule
+ * never differs per row.
+ * Initial state: that of a context whose profile is u0[y] = u[y] * s[0], formed on the host in double — a ramp that starts at 0 starts
+ * from rest, and the initial snapshot reports ux = u0[y]; the ghost frame is what it is with a profile. Snapshots (lbm_get_macros,
+ * statistics, frames, probes, the f_current of lbm_get_populations) apply the inlet of the iteration they describe: a context with
+ * lbm_steps_done == k >= 1 reports (rho_bc, u[y] * s(k - 1), 0) on the inlet column, the sample of output iteration t uses s(t).
+ * Call after lbm_create and before lbm_initialise, in either order with lbm_set_inlet_profile: the plan is measured with the schedule
+ * set. n == 0 clears the schedule. Every strip of a run is given the same schedule. The schedule changes no launch, no row range and no
+ * exchange, and without one every result, kernel name, checkpoint byte and dry-run record is what it was without this call.
+ * Checkpoints of a context with a schedule carry its digest (lbm_save_state: magic "LBMCKPT3", flag bit 5, a 64-bit digest of {mode, n,
+ * the n doubles} behind the walls) and load only into a context with an equal schedule; the iteration counter of the file positions
+ * the schedule after a restart.
+ * LBM_ERR_ARG (the text names the offender, entry index included): a null context, an initialised context, n < 0 or
+ * n > LBM_INLET_SCHEDULE_MAX, a null `s` with n > 0, a mode outside 0..1, an entry that is not finite. lbm_initialise, which knows
+ * profile and schedule, fails with LBM_ERR_ARG naming row and entry unless u[y] * s[k] < 1 for every row and entry (the inlet divides by
+ * 1 - u_in). */
+#define LBM_INLET_HOLD 0
+#define LBM_INLET_REPEAT 1
+#define LBM_INLET_SCHEDULE_MAX 1048576
+int  lbm_set_inlet_schedule(lbm_ctx* c, const double* s, int n, int mode);
+/* The length of the schedule as set; 0 without one (or for a null context). */
+int  lbm_inlet_schedule_length(const lbm_ctx* c);
+/* The factor iteration t applies, as the kernels see it: (double)(T)s(t) in the element type T; 1.0 without a schedule.
+ * LBM_ERR_ARG: null argument, t < 0. */
+int  lbm_get_inlet_scale(const lbm_ctx* c, int t, double* s_out);
 /* The collision: replaces the BGK operator's one global tau (LBMSolver.h:85) by a Smagorinsky subgrid model with constant `cs`. Each
  * fluid cell relaxes with tau_eff = (tau + sqrt(tau^2 + 18 sqrt(2) cs^2 |Pi|/rho)) / 2, where Pi is the non-equilibrium momentum flux
  * of its post-BC populations: the closed form of tau_eff = tau + 3 cs^2 |S|, |S| = sqrt(2 S:S), for cs^2 = 1/3 and dx = dt = 1. This
@@ -418,8 +453,9 @@ int  lbm_halo_import(lbm_ctx* c, const double* south_in, const double* north_in)
 /* Checkpoint / restart (the reference has none): the strip's post-collision populations and the
  * iteration counter. lbm_load_state needs an initialised context created with the same parameters; the macro /
  * population snapshots become available again after the next lbm_step. A file written with an obstacle mask, an inlet
- * profile, a Smagorinsky constant, a TRT magic parameter or a wall that is not no-slip (lbm_set_wall) loads only into a context with
- * the same mask, profile, constant, parameter and walls (the failure names which one differs). */
+ * profile, a Smagorinsky constant, a TRT magic parameter, a wall that is not no-slip (lbm_set_wall) or an inlet schedule
+ * (lbm_set_inlet_schedule) loads only into a context with the same mask, profile, constant, parameter, walls and schedule (the failure
+ * names which one differs). */
 int  lbm_save_state(lbm_ctx* c, const char* path);
 int  lbm_load_state(lbm_ctx* c, const char* path);
 
@@ -496,6 +532,11 @@ int lbm_debug_strict_div2(const double* a1, const double* a2, const double* b, i
  * the nine results are widened into f_out9. The argument errors of lbm_set_wall, and LBM_ERR_ARG for a null pointer or an unknown
  * precision. Replaces nothing in the reference (its rule is LBMSolver.h:155-176, kind 0). */
 int lbm_debug_wall_rule(int side, int kind, double velocity, int precision, const double* f_in9, double* f_out9);
+/* Test hook, callable without a device: the factor the schedule {s, n, mode} of lbm_set_inlet_schedule gives each of the nt iterations
+ * t[i] >= 0, out[i] = (double)(T)s(t[i]) in the element type of `precision` — through the index function the step kernels and the
+ * snapshot call (csrc/lbm_kernels.hpp inlet_sched_index), compiled for the host. The argument errors of lbm_set_inlet_schedule, and
+ * LBM_ERR_ARG for n == 0, a null pointer, an unknown precision or a negative iteration. */
+int lbm_debug_inlet_scale(const double* s, int n, int mode, int precision, const int* t, int nt, double* out);
 /* Test hook, callable without a device: what the ranks of a strip run agree on before the collective schedule trials of
  * lbm_initialise (csrc/lbm_hip.hip tune_strip_schedule). per_rank7 = nranks x {may tune, overlap pinned, overlap, deep_halo pinned,
  * deep_halo, halo_trim pinned, halo_trim}; agreed7 = the same seven as agreed (-1 where nothing is pinned). LBM_ERR_ARG when the ranks pin different
