@@ -1,6 +1,8 @@
-"""What the test modules share (test infrastructure): paths, fixtures, the GPU plan table, masks and files, context runs, case tables.
+"""What the test modules share (test infrastructure): paths, fixtures, the GPU plan table, masks and files, context runs, the check of a
+GPU run against a reference run, case tables.
 
 A fixture is shared by importing it by name into the test module (pytest finds it there like one defined there)."""
+import collections
 import importlib
 import os
 import re
@@ -220,13 +222,26 @@ def whole_run(lbm, nx, ny, plan, steps, of, **kw):
         return whole.macros(), whole.populations("f_next"), whole.drain_force_log()
 
 
+CtxRun = collections.namedtuple("CtxRun", "solid_count f_current f_next macros force_log first_unstable kernel_name plan")
+
+
 def run_ctx(lbm, nx, ny, opts, steps, of, **kw):
     with lbm.Context(nx, ny, options=opts, **kw) as ctx:
         n = ctx.initialise()
         ctx.step(steps, of)
         ctx.step(1, 0)
-        return (n, ctx.populations("f_current"), ctx.populations("f_next"), ctx.macros(), ctx.drain_force_log(),
-                ctx.first_unstable_step())
+        return CtxRun(n, ctx.populations("f_current"), ctx.populations("f_next"), ctx.macros(), ctx.drain_force_log(),
+                      ctx.first_unstable_step(), ctx.kernel_name(), ctx.plan())
+
+
+def assert_same_results(a, b, rows=4):
+    """Two run_ctx results of stable runs are one: the solid count, both population arrays and the macros bit for bit, the force logs
+    equal and `rows` rows long."""
+    assert a.solid_count == b.solid_count and a.first_unstable == b.first_unstable == -1
+    assert np.array_equal(a.f_current, b.f_current) and np.array_equal(a.f_next, b.f_next)
+    for x, y in zip(a.macros, b.macros):
+        assert np.array_equal(x, y)
+    assert a.force_log == b.force_log and len(a.force_log) == rows
 
 
 def host_staged_two_strips(lbm, nx, ny, rounds, steps_per_round, strip_options, **ctx_kw):
@@ -263,6 +278,68 @@ def assert_group_is_whole(group, whole):
     assert [r[0] for r in log] == [r[0] for r in whole[2]]
     for (t, fx, fy), (_, wx, wy) in zip(log, whole[2]):
         assert abs(fx - wx) <= 1e-13 * max(1.0, abs(wx)) and abs(fy - wy) <= 1e-13 * max(1.0, abs(wy))
+
+
+# ---- a GPU run against a reference run (tests/reference.py Run) --------------------------------------------------------------------
+# The velocity bar is the call site's decision. Absolute 1e-10, the contracted bar, where tau is close to 0.5 (LES, TRT, walls): tau
+# 0.51 amplifies — 4.6e-11 measured with LES on the parabolic inlet, where 1e-10 * max|u| would be 1.7e-11. Relative to the largest
+# reference speed (u_bar_rel) in geometry, inlet profile and inlet schedule.
+U_BAR_ABS = 1e-10
+
+
+def u_bar_rel(ref):
+    return 1e-10 * float(np.max(np.sqrt(ref.ux ** 2 + ref.uy ** 2)))
+
+
+def where(a, b):
+    """The first cell (x, y) of the interior at which two ghost-inclusive population arrays differ, for the failure message."""
+    d = np.argwhere(np.any(a != b, axis=-1))
+    return "first differing cell (x, y) = (%d, %d), %d cells differ" % (d[0][1] - 1, d[0][0] - 1, len(d)) if len(d) else "equal"
+
+
+def force_problems(log, ref_forces):
+    """What of a force log misses the reference's rows: the same timesteps, each component within 1e-10 * max(1, |F|)."""
+    if [r[0] for r in log] != [r[0] for r in ref_forces]:
+        return ["force log times %s, reference %s" % ([r[0] for r in log], [r[0] for r in ref_forces])]
+    out = []
+    for (t, fx, fy), (_, rx, ry) in zip(log, ref_forces):
+        if not (abs(fx - rx) <= 1e-10 * max(1.0, abs(rx)) and abs(fy - ry) <= 1e-10 * max(1.0, abs(ry))):
+            out.append("force at t = %d: (%.17g, %.17g), reference (%.17g, %.17g)" % (t, fx, fy, rx, ry))
+    return out
+
+
+def reference_problems(plan, fn, macros, log, ref, u_bar, fast_rho=True):
+    """What of a run misses the reference: the force rows; strict plans f_next bit for bit and rho within 1e-14 (the macro snapshot);
+    contracted plans f_next within 1e-10 max|f_ref| and (fast_rho) rho within 1e-10; both velocity components within u_bar.
+    (Every comparison is written so that a NaN fails it.)"""
+    rho, ux, uy = macros
+    out = force_problems(log, ref.forces)
+    erho = float(np.max(np.abs(rho - ref.rho)))
+    if strict(plan):
+        if not np.array_equal(fn, ref.f_next):
+            out.append("f_next is not the reference's bit for bit: " + where(fn, ref.f_next))
+        if not erho <= 1e-14:
+            out.append("rho off by %.3g" % erho)
+    else:
+        err, scale = float(np.max(np.abs(fn - ref.f_next))), float(np.max(np.abs(ref.f_next)))
+        if not err <= 1e-10 * scale:
+            out.append("f_next off by %.3g (bar %.3g)" % (err, 1e-10 * scale))
+        if fast_rho and not erho <= 1e-10:
+            out.append("rho off by %.3g" % erho)
+    eu = max(float(np.max(np.abs(ux - ref.ux))), float(np.max(np.abs(uy - ref.uy))))
+    if not eu <= u_bar:
+        out.append("u off by %.3g (bar %.3g)" % (eu, u_bar))
+    return out
+
+
+def assert_forces_match(log, ref_forces, what):
+    bad = force_problems(log, ref_forces)
+    assert not bad, "%s: %s" % (what, "; ".join(bad))
+
+
+def assert_matches_reference(plan, fn, macros, log, ref, u_bar, fast_rho=True):
+    bad = reference_problems(plan, fn, macros, log, ref, u_bar, fast_rho)
+    assert not bad, "%s: %s" % (plan, "; ".join(bad))
 
 
 # ---- case tables of the CPU choreography tests -----------------------------------------------------------------------------------

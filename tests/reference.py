@@ -1,9 +1,10 @@
 """The one stepwise reference run of the GPU feature tests (test infrastructure, like oracle/oracle.py).
 
 The C oracle's arrays are writable views, so its loop taken step by step, with a numpy collision operator in place of o.collide()
-and a numpy fix-up of the inlet column, is the reference of every feature the oracle itself does not have. Everything here is fp64,
-IEEE, in the operation order the library's strict arithmetic evaluates: strict plans must match it bit for bit.
-tests/test_reference_cpu.py pins the shared pieces to the unmodified oracle."""
+and a numpy restatement of ALL of lbmo_boundaries (oracle/lbm_oracle.c) in place of o.boundaries(), is the reference of every feature
+the oracle itself does not have: obstacle masks, inlet profiles and schedules, the wall kinds, the collision operators, and any
+combination of them. Everything here is fp64, IEEE, in the operation order the library's strict arithmetic evaluates: strict plans
+must match it bit for bit. tests/test_reference_cpu.py pins the loop and the shared pieces to the unmodified oracle."""
 import collections
 import math
 
@@ -121,54 +122,139 @@ def link_forces(f_next, solid):
     return fx, fy
 
 
+# ---- the boundary step: walls, inlet, outlet, solid cells -----------------------------------------------------------------------
+NOSLIP, FREESLIP = "no-slip", "free-slip"
+OPP = [0, 3, 4, 1, 2, 7, 8, 5, 6]
+HOLD, REPEAT = 0, 1
+
+
+def moving(u_w):
+    return ("moving", float(u_w))
+
+
+def wall_kind_k(wall):
+    """(kind 0 / 1 / 2, k) of a wall given as the binding takes it: k = u_w * (1 / 6), the library's host expression."""
+    if wall == NOSLIP:
+        return 0, 0.0
+    if wall == FREESLIP:
+        return 1, 0.0
+    name, u_w = wall
+    assert name == "moving"
+    return 2, float(u_w) * (1.0 / 6.0)
+
+
+def wall_rule(f, side, kind, k):
+    """The table of include/lbm_hip.h (lbm_set_wall) on cells f[..., 9], in place. side 0: south, 1: north."""
+    if side == 0:
+        f[..., 2] = f[..., 4]
+        if kind == 0:
+            f[..., 5] = f[..., 7]; f[..., 6] = f[..., 8]
+        elif kind == 1:
+            f[..., 5] = f[..., 8]; f[..., 6] = f[..., 7]
+        else:
+            f[..., 5] = f[..., 7] + k; f[..., 6] = f[..., 8] - k
+    else:
+        f[..., 4] = f[..., 2]
+        if kind == 0:
+            f[..., 7] = f[..., 5]; f[..., 8] = f[..., 6]
+        elif kind == 1:
+            f[..., 7] = f[..., 6]; f[..., 8] = f[..., 5]
+        else:
+            f[..., 7] = f[..., 5] - k; f[..., 8] = f[..., 6] + k
+    return f
+
+
+def sched_index(t, n, mode):
+    """Which entry iteration t takes: HOLD s[min(t, n - 1)], REPEAT s[t mod n] (the Python restatement of inlet_sched_index)."""
+    return t % n if mode == REPEAT else min(t, n - 1)
+
+
+def boundaries(o, solid, walls, u):
+    """lbmo_boundaries in numpy, in its sequential order: bottom, top, inlet, outlet, solid cells, with rho / ux / uy on the inlet and
+    outlet columns and zeros on solid cells, operation for operation as the C writes them. walls = (south, north); u = the inlet
+    velocity of every row, [ny]. (A wall rule cannot be patched in around o.boundaries(): the inlet and the outlet read f5..f8 of the
+    corner cells after the wall has rewritten them.)"""
+    fc = o.f_current
+    ny, nx = solid.shape
+    fluid = ~solid
+    # the two walls: fluid cells of row 0 / ny - 1 (ghost-inclusive rows 1 / ny)
+    for side, gy, y in ((0, 1, 0), (1, ny, ny - 1)):
+        kind, k = wall_kind_k(walls[side])
+        cols = np.nonzero(fluid[y])[0] + 1
+        fc[gy, cols, :] = wall_rule(fc[gy, cols, :], side, kind, k)
+    # inlet: fluid cells of column 0, Zou-He velocity with u[y]
+    rows = np.nonzero(fluid[:, 0])[0]
+    ur = u[rows]
+    f = fc[rows + 1, 1, :]
+    rho_bc = (f[:, 0] + f[:, 2] + f[:, 4] + 2.0 * (f[:, 3] + f[:, 6] + f[:, 7])) / (1.0 - ur)
+    f[:, 1] = f[:, 3] + (2.0 / 3.0) * rho_bc * ur
+    f[:, 5] = f[:, 7] - 0.5 * (f[:, 2] - f[:, 4]) + (1.0 / 6.0) * rho_bc * ur
+    f[:, 8] = f[:, 6] + 0.5 * (f[:, 2] - f[:, 4]) + (1.0 / 6.0) * rho_bc * ur
+    fc[rows + 1, 1, :] = f
+    o.rho[rows, 0] = rho_bc; o.ux[rows, 0] = ur; o.uy[rows, 0] = 0.0
+    # outlet: fluid cells of column nx - 1, Zou-He pressure with rho = 1
+    rows = np.nonzero(fluid[:, nx - 1])[0]
+    f = fc[rows + 1, nx, :]
+    rho_out = 1.0
+    u_out = -1.0 + (f[:, 0] + f[:, 2] + f[:, 4] + 2.0 * (f[:, 1] + f[:, 5] + f[:, 8])) / rho_out
+    f[:, 3] = f[:, 1] - (2.0 / 3.0) * rho_out * u_out
+    f[:, 6] = f[:, 8] - 0.5 * (f[:, 2] - f[:, 4]) - (1.0 / 6.0) * rho_out * u_out
+    f[:, 7] = f[:, 5] + 0.5 * (f[:, 2] - f[:, 4]) - (1.0 / 6.0) * rho_out * u_out
+    fc[rows + 1, nx, :] = f
+    o.rho[rows, nx - 1] = rho_out; o.ux[rows, nx - 1] = u_out; o.uy[rows, nx - 1] = 0.0
+    # solid cells: the populations reversed, the velocity zeroed
+    inner = fc[1:-1, 1:-1]
+    inner[solid] = inner[solid][:, OPP]
+    o.ux[solid] = 0.0; o.uy[solid] = 0.0
+
+
 # ---- the loop -------------------------------------------------------------------------------------------------------------------
 Run = collections.namedtuple("Run", "f_next rho ux uy forces first_unstable solid_count tau_max")
 
 
-def oracle_run(nx, ny, steps, of, *, mask=None, u=None, collide=None, **params):
-    """The stepwise oracle: on `mask` (None: the analytic disc of `params`), with the inlet of row y at u[y] (None: the uniform
-    inlet) and with collide(o, tau) in place of its own o.collide() (None: plain BGK). forces are [(t, fx, fy)] by link_forces;
-    tau_max is the largest value the operator returned, None if it returns none."""
+def oracle_run(nx, ny, steps, of, *, mask=None, u=None, walls=(NOSLIP, NOSLIP), schedule=None, collide=None, keep_f_current=False,
+               **params):
+    """The stepwise oracle: on `mask` (None: the analytic disc of `params`); with the inlet of row y at iteration t at u[y] (None: the
+    uniform inlet_velocity of `params`) times, under schedule = (s, HOLD or REPEAT), s[sched_index(t)] — one IEEE multiplication in
+    double, formed before `boundaries` uses it; between walls = (south, north), each "no-slip", "free-slip" or ("moving", u_w), one
+    string meaning both; and with collide(o, tau) in place of its own o.collide() (None: plain BGK). forces are [(t, fx, fy)] by
+    link_forces; tau_max is the largest value the operator returned, None if it returns none. Returns a Run (and, with
+    keep_f_current, f_current beside it)."""
+    if isinstance(walls, str):
+        walls = (walls, walls)
     o = Oracle(make_params(nx, ny, **params))
     if mask is not None:
         o.solid[:] = mask
     o.L.lbmo_initialise(o.h)
     solid = o.solid.astype(bool).copy()
     fluid = ~solid
-    if u is not None:                            # interior fluid cells of row y start at f_eq(1, (u[y], 0))
-        fr = feq_rows(u)
+    u_rows = np.full(ny, o.p.inlet_velocity, dtype=np.float64) if u is None else np.asarray(u, dtype=np.float64)
+    s, mode = (None, HOLD) if schedule is None else (np.asarray(schedule[0], dtype=np.float64), schedule[1])
+    if u is not None or s is not None:           # interior fluid cells of row y start at f_eq(1, (u0[y], 0))
+        u0 = u_rows if s is None else u_rows * s[0]
+        fr = feq_rows(u0)
         for arr in (o.f_current, o.f_next):
             inner = arr[1:-1, 1:-1]
             inner[fluid] = np.broadcast_to(fr[:, None, :], (ny, nx, 9))[fluid]
-        o.ux[fluid] = np.broadcast_to(np.asarray(u)[:, None], (ny, nx))[fluid]
-        rows = np.nonzero(fluid[:, 0])[0]
-        ur = np.asarray(u, dtype=np.float64)[rows]
+        o.ux[fluid] = np.broadcast_to(u0[:, None], (ny, nx))[fluid]
     tau = o.p.tau
     forces, bad, tmax = [], -1, None
     for t in range(steps):
         with np.errstate(all="ignore"):          # (a diverging run reaches Inf / NaN; the stability test then ends it)
             got = o.collide() if collide is None else collide(o, tau)
-        if got is not None:
-            tmax = max(tau if tmax is None else tmax, got)
-        if of and t % of == 0:
-            forces.append((t,) + link_forces(o.f_next, solid))
-        o.exchange_physical()
-        o.stream()
-        o.boundaries()
-        if u is not None:
-            # the inlet again, with u[y]: it reads f0, f2, f3, f4, f6, f7 after the wall conditions (which it leaves alone) and
-            # rewrites f1, f5, f8 (lbm_oracle.c inlet block, same operation order)
-            f = o.f_current[rows + 1, 1, :]
-            rho_bc = (f[:, 0] + f[:, 2] + f[:, 4] + 2.0 * (f[:, 3] + f[:, 6] + f[:, 7])) / (1.0 - ur)
-            f[:, 1] = f[:, 3] + (2.0 / 3.0) * rho_bc * ur
-            f[:, 5] = f[:, 7] - 0.5 * (f[:, 2] - f[:, 4]) + (1.0 / 6.0) * rho_bc * ur
-            f[:, 8] = f[:, 6] + 0.5 * (f[:, 2] - f[:, 4]) + (1.0 / 6.0) * rho_bc * ur
-            o.f_current[rows + 1, 1, :] = f
-            o.rho[rows, 0] = rho_bc
-            o.ux[rows, 0] = ur
+            if got is not None:
+                tmax = max(tau if tmax is None else tmax, got)
+            if of and t % of == 0:
+                forces.append((t,) + link_forces(o.f_next, solid))
+            o.exchange_physical()
+            o.stream()
+            boundaries(o, solid, walls, u_rows if s is None else u_rows * s[sched_index(t, len(s), mode)])
         if not o.stable():
             bad = t
             break
     out = Run(o.f_next.copy(), o.rho.copy(), o.ux.copy(), o.uy.copy(), forces, bad, o.solid_count(), tmax)
+    fcur = o.f_current.copy()
     o.close()
-    return out
+    return (out, fcur) if keep_f_current else out
+
+

@@ -7,8 +7,8 @@ only its lbmo_forces recomputes the disc, so the forces here are recomputed in n
 import numpy as np
 import pytest
 
-from tests.helpers import (ORACLE_PLANS, PLANS, TALL_F32, assert_group_is_whole, disc, host_staged_two_strips, lbm_gpu, masks,  # noqa: F401
-                           read_csv_rows, read_params, run_solver, square, strict, write_pgm)
+from tests.helpers import (ORACLE_PLANS, PLANS, TALL_F32, assert_forces_match, assert_group_is_whole, assert_matches_reference, disc,  # noqa: F401
+                           host_staged_two_strips, lbm_gpu, masks, read_csv_rows, read_params, run_solver, square, strict, u_bar_rel, write_pgm)
 from tests.reference import oracle_run
 
 pytestmark = pytest.mark.gpu
@@ -77,21 +77,11 @@ def test_masks_against_the_oracle(lbm, name):
                 continue
             log = ctx.drain_force_log()
             fn = ctx.populations("f_next")
-            rho, ux, uy = ctx.macros()
-        assert [r[0] for r in log] == [r[0] for r in ref.forces]
-        for (t, fx, fy), (_, rx, ry) in zip(log, ref.forces):
-            assert abs(fx - rx) <= 1e-10 * max(1.0, abs(rx)) and abs(fy - ry) <= 1e-10 * max(1.0, abs(ry)), (plan, t)
+            macros = ctx.macros()
         key = "strict" if strict(plan) else "fast"
         fast.setdefault(key, fn)
         assert np.array_equal(fn, fast[key]), plan      # every plan of one arithmetic mode: the same bits
-        scale = float(np.max(np.abs(ref.f_next)))
-        if key == "strict":
-            assert np.array_equal(fn, ref.f_next), plan
-            assert np.array_equal(rho, ref.rho) or float(np.max(np.abs(rho - ref.rho))) <= 1e-14, plan
-        else:
-            assert float(np.max(np.abs(fn - ref.f_next))) <= 1e-10 * scale, plan
-        uscale = float(np.max(np.sqrt(ref.ux ** 2 + ref.uy ** 2)))
-        assert float(np.max(np.abs(ux - ref.ux))) <= 1e-10 * uscale and float(np.max(np.abs(uy - ref.uy))) <= 1e-10 * uscale, plan
+        assert_matches_reference(plan, fn, macros, log, ref, u_bar_rel(ref), fast_rho=False)
 
 
 def test_whole_domain_mask_forces_in_fixed_chunks(lbm):
@@ -110,9 +100,7 @@ def test_whole_domain_mask_forces_in_fixed_chunks(lbm):
             ctx.step(steps, of)
             logs.append(ctx.drain_force_log())
     assert all(l == logs[0] for l in logs)
-    assert [r[0] for r in logs[0]] == [r[0] for r in ref.forces]
-    for (t, fx, fy), (_, rx, ry) in zip(logs[0], ref.forces):
-        assert abs(fx - rx) <= 1e-10 * max(1.0, abs(rx)) and abs(fy - ry) <= 1e-10 * max(1.0, abs(ry)), t
+    assert_forces_match(logs[0], ref.forces, "every plan")
 
 
 # ---- 3. strips --------------------------------------------------------------------------------------------------------------

@@ -25,7 +25,7 @@ import numpy as np
 import pytest
 
 from oracle.oracle import Oracle, make_params
-from tests.helpers import PKG, PLANS, TALL_F32, lbm_gpu, strict  # noqa: F401
+from tests.helpers import PKG, PLANS, TALL_F32, U_BAR_ABS, lbm_gpu, reference_problems, strict, u_bar_rel, where  # noqa: F401
 from tests.reference import les_collide, oracle_run
 
 gpu = pytest.mark.gpu          # (every test but the guard at the end of the module)
@@ -68,7 +68,7 @@ STRIP_CONFIGS = {
 }
 SITE_F32 = dict(tune=0, layout=1, nt=1, alternate=0, fuse=1)
 
-Ref = collections.namedtuple("Ref", "f rho ux uy forces bad count tmax solid")
+Ref = collections.namedtuple("Ref", "f_next rho ux uy forces bad count tmax solid")
 Run = collections.namedtuple("Run", "count bad log f rho ux uy kernel solid")
 
 
@@ -139,48 +139,15 @@ def run(lbm, opts, mask, nx=NX, ny=NY, bounds=None, **kw):
     return Run(count, bad, log, f, rho, ux, uy, kernel, solid)
 
 
-def where(a, b):
-    """The first cell (x, y) of the interior at which two ghost-inclusive population arrays differ, for the failure message."""
-    d = np.argwhere(np.any(a != b, axis=-1))
-    return "first differing cell (x, y) = (%d, %d), %d cells differ" % (d[0][1] - 1, d[0][0] - 1, len(d)) if len(d) else "equal"
-
-
-def force_problems(log, forces):
-    out = []
-    if [r[0] for r in log] != [r[0] for r in forces]:
-        return ["force log times %s, reference %s" % ([r[0] for r in log], [r[0] for r in forces])]
-    for (t, fx, fy), (_, rx, ry) in zip(log, forces):
-        if not (abs(fx - rx) <= 1e-10 * max(1.0, abs(rx)) and abs(fy - ry) <= 1e-10 * max(1.0, abs(ry))):
-            out.append("force at t = %d: (%.17g, %.17g), reference (%.17g, %.17g)" % (t, fx, fy, rx, ry))
-    return out
-
-
-def oracle_problems(got, ref, is_strict, les=False):
-    """What of a run misses the oracle: strict arithmetic f_next bit for bit, contracted within 1e-10 max|f_ref|; rho and u at the
-    bars of test_masks_against_the_oracle (LES: of test_les_against_the_reference); forces 1e-10 relative; stable; the solid count.
-    (Every comparison is written so that a NaN fails it.)"""
+def oracle_problems(got, ref, plan, les=False):
+    """What of a run misses the oracle: stable; the solid count; then reference_problems of tests/helpers.py — forces, f_next, rho and
+    u at the bars of test_masks_against_the_oracle (LES: of test_les_against_the_reference), contracted rho within 1e-10."""
     out = []
     if got.count != ref.count:
         out.append("solid count %d, reference %d" % (got.count, ref.count))
     if got.bad != -1 or ref.bad != -1:
         out.append("first unstable step %d, reference %d" % (got.bad, ref.bad))
-    out += force_problems(got.log, ref.forces)
-    if is_strict:
-        if not np.array_equal(got.f, ref.f):
-            out.append("f_next is not the oracle's bit for bit: " + where(got.f, ref.f))
-        if not float(np.max(np.abs(got.rho - ref.rho))) <= 1e-14:
-            out.append("rho off by %.3g" % float(np.max(np.abs(got.rho - ref.rho))))
-    else:
-        err, scale = float(np.max(np.abs(got.f - ref.f))), float(np.max(np.abs(ref.f)))
-        if not err <= 1e-10 * scale:
-            out.append("f_next off by %.3g (bar %.3g)" % (err, 1e-10 * scale))
-        if not float(np.max(np.abs(got.rho - ref.rho))) <= 1e-10:
-            out.append("rho off by %.3g" % float(np.max(np.abs(got.rho - ref.rho))))
-    ubar = 1e-10 if les else 1e-10 * float(np.max(np.sqrt(ref.ux ** 2 + ref.uy ** 2)))
-    eu = max(float(np.max(np.abs(got.ux - ref.ux))), float(np.max(np.abs(got.uy - ref.uy))))
-    if not eu <= ubar:
-        out.append("u off by %.3g (bar %.3g)" % (eu, ubar))
-    return out
+    return out + reference_problems(plan, got.f, (got.rho, got.ux, got.uy), got.log, ref, U_BAR_ABS if les else u_bar_rel(ref))
 
 
 def site_problems(got, ref):
@@ -214,7 +181,7 @@ def test_one_cell_swept_across_tiles(lbm, line, plan):
     for x, y in LINES[line]:
         mask = one_cell(x, y)
         got = run(lbm, PLANS[plan], mask, **KW)
-        bad = oracle_problems(got, reference("bgk", x, y), strict(plan))
+        bad = oracle_problems(got, reference("bgk", x, y), plan)
         if not got.kernel.replace(" ", "").startswith(FAMILY[family(plan)]):
             bad.append("kernel " + got.kernel)
         if not np.array_equal(got.solid, mask):
@@ -248,7 +215,7 @@ def test_one_cell_swept_across_tiles_les(lbm, plan):
     for x, y in LINES["horizontal"]:
         ref = reference("les", x, y)
         got = run(lbm, PLANS[plan], one_cell(x, y), smagorinsky=CS, **KW_LES)
-        bad = oracle_problems(got, ref, strict(plan), les=True)
+        bad = oracle_problems(got, ref, plan, les=True)
         if not got.kernel.endswith((",2>", ",3>")):
             bad.append("kernel " + got.kernel)
         if not ref.tmax > KW_LES["tau"]:       # the model is active
@@ -269,7 +236,7 @@ def test_one_cell_swept_across_strip_faces(lbm, column, config):
     failures = []
     for x, y in FACE_COLUMNS[column]:
         got = run(lbm, dict(PLANS[plan], **extra), one_cell(x, y), bounds=BOUNDS, **KW)
-        failures += [(x, y, b) for b in oracle_problems(got, reference("bgk", x, y), strict(plan))]
+        failures += [(x, y, b) for b in oracle_problems(got, reference("bgk", x, y), plan)]
     report(failures, len(FACE_COLUMNS[column]))
 
 
@@ -285,7 +252,7 @@ def test_smallest_discs_swept_across_tiles(lbm, line, r, plan):
     for x, y in LINES[line]:
         ref = reference("disc", x, y, r)
         got = run(lbm, PLANS[plan], None, **KW, **disc_params(x, y, r))
-        bad = oracle_problems(got, ref, strict(plan))
+        bad = oracle_problems(got, ref, plan)
         if ref.count != DISC_RADII[r]:
             bad.append("the oracle's disc has %d cells" % ref.count)
         if not np.array_equal(got.solid, ref.solid):
@@ -303,10 +270,10 @@ def test_one_cell_in_corners_and_on_walls(lbm, plan):
     failures = []
     for x, y in CORNERS:
         got = run(lbm, PLANS[plan], one_cell(x, y), **KW)
-        failures += [(x, y, b) for b in oracle_problems(got, reference("bgk", x, y), strict(plan))]
+        failures += [(x, y, b) for b in oracle_problems(got, reference("bgk", x, y), plan)]
     for x, y in INLET_CELLS:
         got = run(lbm, PLANS[plan], one_cell(x, y), inlet_profile=parabolic(), **KW)
-        failures += [(x, y, "parabolic inlet: " + b) for b in oracle_problems(got, reference("profile", x, y), strict(plan))]
+        failures += [(x, y, "parabolic inlet: " + b) for b in oracle_problems(got, reference("profile", x, y), plan)]
     report(failures, len(CORNERS) + len(INLET_CELLS))
 
 
@@ -357,7 +324,7 @@ def test_the_oracle_is_stable_at_every_position(name):
     for x, y in cells:
         ref = reference("bgk", x, y)
         assert ref.bad == -1 and ref.count == 1 and [r[0] for r in ref.forces] == [0, 16], (x, y)
-        assert np.all(np.isfinite(ref.f))
+        assert np.all(np.isfinite(ref.f_next))
     if name == "corners":
         for x, y in INLET_CELLS:
             assert reference("profile", x, y).bad == -1, (x, y)

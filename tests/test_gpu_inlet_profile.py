@@ -1,15 +1,16 @@
 """Per-row inlet velocity profiles (lbm_set_inlet_profile, Context/Group(inlet_profile=...), lbm_solver --inlet-profile) on the GPU.
 
 The reference's Zou-He inlet with u_in replaced by u[y] on row y, and an initial state of f_eq(1, (u[y], 0)) per row. The oracle
-imposes one velocity; its arrays are writable views, so the stepwise oracle plus a numpy fix-up of the inlet column (in the
-oracle's operation order) is the per-row reference: strict plans must match it bit for bit."""
+imposes one velocity; its arrays are writable views, so the stepwise oracle with the numpy boundary step (oracle_run(u=...) of
+tests/reference.py, in the oracle's operation order) is the per-row reference: strict plans must match it bit for bit."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
-from tests.helpers import (ORACLE_PLANS, PLANS, TALL_F32, assert_group_is_whole, host_staged_two_strips, lbm_gpu, masks, read_csv_rows,  # noqa: F401
-                           read_params, read_velocity_field, record, run_ctx, run_solver, square, strict, whole_run, write_pgm)
+from tests.helpers import (ORACLE_PLANS, PLANS, TALL_F32, assert_group_is_whole, assert_matches_reference, assert_same_results,  # noqa: F401
+                           host_staged_two_strips, lbm_gpu, masks, read_csv_rows, read_params, read_velocity_field, record, run_ctx, run_solver,
+                           square, strict, u_bar_rel, whole_run, write_pgm)
 from tests.reference import oracle_run
 
 pytestmark = pytest.mark.gpu
@@ -41,11 +42,7 @@ def test_constant_profile_is_the_uniform_inlet(lbm, plan, precision, mask):
     solid = square(nx, ny) if mask else None
     a = run_ctx(lbm, nx, ny, opts, steps, of, solid=solid, **kw)
     b = run_ctx(lbm, nx, ny, opts, steps, of, solid=solid, inlet_profile=np.full(ny, u0), **kw)
-    assert a[0] == b[0] and a[5] == b[5] == -1
-    assert np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2])
-    for x, y in zip(a[3], b[3]):
-        assert np.array_equal(x, y)
-    assert a[4] == b[4] and len(a[4]) == 4
+    assert_same_results(a, b)
 
 
 # ---- 2. non-uniform profiles against the oracle ------------------------------------------------------------------------------
@@ -77,22 +74,12 @@ def test_profiles_against_the_oracle(lbm, name):
             assert ctx.first_unstable_step() == -1
             log = ctx.drain_force_log()
             fn = ctx.populations("f_next")
-            rho, ux, uy = ctx.macros()
-        assert np.array_equal(ux[fluid0, 0], u[fluid0]), plan       # the inlet column reports u[y]
-        assert [r[0] for r in log] == [r[0] for r in ref.forces]
-        for (t, fx, fy), (_, rx, ry) in zip(log, ref.forces):
-            assert abs(fx - rx) <= 1e-10 * max(1.0, abs(rx)) and abs(fy - ry) <= 1e-10 * max(1.0, abs(ry)), (plan, t)
+            macros = ctx.macros()
+        assert np.array_equal(macros[1][fluid0, 0], u[fluid0]), plan       # the inlet column reports u[y]
         key = "strict" if strict(plan) else "fast"
         seen.setdefault(key, fn)
         assert np.array_equal(fn, seen[key]), plan      # every plan of one arithmetic mode: the same bits
-        scale = float(np.max(np.abs(ref.f_next)))
-        if key == "strict":
-            assert np.array_equal(fn, ref.f_next), plan
-            assert float(np.max(np.abs(rho - ref.rho))) <= 1e-14, plan
-        else:
-            assert float(np.max(np.abs(fn - ref.f_next))) <= 1e-10 * scale, plan
-        uscale = float(np.max(np.sqrt(ref.ux ** 2 + ref.uy ** 2)))
-        assert float(np.max(np.abs(ux - ref.ux))) <= 1e-10 * uscale and float(np.max(np.abs(uy - ref.uy))) <= 1e-10 * uscale, plan
+        assert_matches_reference(plan, fn, macros, log, ref, u_bar_rel(ref), fast_rho=False)
 
 
 # ---- 3. strips ---------------------------------------------------------------------------------------------------------------

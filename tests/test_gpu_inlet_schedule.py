@@ -2,38 +2,21 @@
 --inlet-schedule) on the GPU.
 
 The Zou-He inlet of iteration t imposes u[y] * s(t), one IEEE multiplication in the element type; every fused level of a launch takes
-the factor of its own iteration, and so does a launch replayed from a graph. The reference is tests/inlet_schedule_reference.py (the
-stepwise oracle with the scaled inlet fix-up): strict fp64 plans must match it bit for bit."""
+the factor of its own iteration, and so does a launch replayed from a graph. The reference is oracle_run(schedule=...) of
+tests/reference.py (the stepwise oracle, whose boundary step takes the scaled inlet): strict fp64 plans must match it bit for bit."""
 import ctypes as C
 import struct
 
 import numpy as np
 import pytest
 
-from tests.helpers import (ORACLE_PLANS, PLANS, TALL_F32, assert_group_is_whole, host_staged_two_strips, lbm_gpu, masks, read_csv_rows,  # noqa: F401
-                           read_params, read_velocity_field, record, run_solver, solver, square, strict, whole_run, write_pgm)
-from tests.inlet_schedule_reference import HOLD, REPEAT, sched_index, schedule_run
+from tests.helpers import (ORACLE_PLANS, PLANS, TALL_F32, assert_group_is_whole, assert_matches_reference, assert_same_results,  # noqa: F401
+                           host_staged_two_strips, lbm_gpu, masks, read_csv_rows, read_params, read_velocity_field, record, run_ctx, run_solver,
+                           solver, square, strict, u_bar_rel, whole_run, write_pgm)
+from tests.reference import HOLD, REPEAT, oracle_run, sched_index
 from tests.test_gpu_inlet_profile import CONST_CASES, shear, wavy
 
 pytestmark = pytest.mark.gpu
-
-
-def run_all(lbm, nx, ny, opts, steps, of, **kw):
-    """run_ctx of tests/helpers.py plus the kernel's name and the plan."""
-    with lbm.Context(nx, ny, options=opts, **kw) as ctx:
-        n = ctx.initialise()
-        ctx.step(steps, of)
-        ctx.step(1, 0)
-        return (n, ctx.populations("f_current"), ctx.populations("f_next"), ctx.macros(), ctx.drain_force_log(),
-                ctx.first_unstable_step(), ctx.kernel_name(), ctx.plan())
-
-
-def same_results(a, b):
-    assert a[0] == b[0] and a[5] == b[5] == -1
-    assert np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2])
-    for x, y in zip(a[3], b[3]):
-        assert np.array_equal(x, y)
-    assert a[4] == b[4] and len(a[4]) == 4
 
 
 # ---- 1. the schedule [1.0] is no schedule, bit for bit ---------------------------------------------------------------------------
@@ -43,13 +26,13 @@ def test_the_schedule_of_ones_is_no_schedule(lbm, plan, precision, mask):
     kw = dict(inlet_velocity=0.05, cylinder_radius=0.08, precision=precision)
     opts = TALL_F32 if plan == "tall-f32" else PLANS["rowil-col5-nt"] if plan == "col5-f32" else PLANS[plan]
     solid = square(nx, ny) if mask else None
-    a = run_all(lbm, nx, ny, opts, steps, of, solid=solid, **kw)
-    b = run_all(lbm, nx, ny, opts, steps, of, solid=solid, inlet_schedule=[1.0], **kw)
-    same_results(a, b)
+    a = run_ctx(lbm, nx, ny, opts, steps, of, solid=solid, **kw)
+    b = run_ctx(lbm, nx, ny, opts, steps, of, solid=solid, inlet_schedule=[1.0], **kw)
+    assert_same_results(a, b)
     # The schedule changes no launch, so a pinned plan names the same kernel. A measured plan (tune: "auto", "fast-auto") names the
     # kernel its own timing picked: the names are compared where both measurements picked the same plan.
-    if (opts and opts.get("tune") == 0) or a[7] == b[7]:
-        assert a[6] == b[6], (a[6], b[6])
+    if (opts and opts.get("tune") == 0) or a.plan == b.plan:
+        assert a.kernel_name == b.kernel_name, (a.kernel_name, b.kernel_name)
 
 
 @pytest.mark.parametrize("plan", ["rowil-site-nt", "rowil-col5-nt", "planar-deep7-alt", "fast-rowil-col6"])
@@ -57,10 +40,10 @@ def test_a_constant_schedule_is_the_scaled_profile(lbm, plan):
     nx, ny, steps, of = 1000, 200, 23, 7
     kw = dict(inlet_velocity=0.05, cylinder_radius=0.08)
     u = shear(ny, 0.05)
-    a = run_all(lbm, nx, ny, PLANS[plan], steps, of, inlet_profile=0.7 * u, **kw)
-    b = run_all(lbm, nx, ny, PLANS[plan], steps, of, inlet_profile=u, inlet_schedule=[0.7], **kw)
-    same_results(a, b)
-    assert a[6] == b[6]
+    a = run_ctx(lbm, nx, ny, PLANS[plan], steps, of, inlet_profile=0.7 * u, **kw)
+    b = run_ctx(lbm, nx, ny, PLANS[plan], steps, of, inlet_profile=u, inlet_schedule=[0.7], **kw)
+    assert_same_results(a, b)
+    assert a.kernel_name == b.kernel_name
 
 
 # ---- 2. schedules against the reference -------------------------------------------------------------------------------------------
@@ -79,7 +62,7 @@ def test_schedules_against_the_reference(lbm, name):
     nx, ny, steps, of = 200, 64, 60, 20        # (200 % 64 != 0: a ragged last tile column)
     kw = dict(inlet_velocity=0.05)
     u, mask, s, mode = oracle_case(lbm, name, nx, ny)
-    ref = schedule_run(nx, ny, steps, of, s=s, mode=mode, mask=mask, u=u, **kw)
+    ref = oracle_run(nx, ny, steps, of, schedule=(s, mode), mask=mask, u=u, **kw)
     assert ref.first_unstable == -1
     if name == "reversing11":
         assert np.min(s) < 0
@@ -97,24 +80,15 @@ def test_schedules_against_the_reference(lbm, name):
                     ctx.step(n, of)
                 assert ctx.first_unstable_step() == -1 and ctx.steps_done == steps
                 out.append((ctx.populations("f_next"), ctx.drain_force_log(), ctx.macros()))
-        fn, log, (rho, ux, uy) = out[0]
+        fn, log, macros = out[0]
         assert np.array_equal(out[1][0], fn) and out[1][1] == log, plan
-        for x, y in zip(out[1][2], out[0][2]):
+        for x, y in zip(out[1][2], macros):
             assert np.array_equal(x, y), plan
-        assert np.array_equal(ux[fluid0, 0], last[fluid0]), plan       # the inlet column reports u[y] * s(steps - 1)
-        assert [r[0] for r in log] == [r[0] for r in ref.forces]
-        for (t, fx, fy), (_, rx, ry) in zip(log, ref.forces):
-            assert abs(fx - rx) <= 1e-10 * max(1.0, abs(rx)) and abs(fy - ry) <= 1e-10 * max(1.0, abs(ry)), (plan, t)
+        assert np.array_equal(macros[1][fluid0, 0], last[fluid0]), plan       # the inlet column reports u[y] * s(steps - 1)
         key = "strict" if strict(plan) else "fast"
         seen.setdefault(key, fn)
         assert np.array_equal(fn, seen[key]), plan      # every plan of one arithmetic mode: the same bits
-        scale = float(np.max(np.abs(ref.f_next)))
-        if key == "strict":
-            assert np.array_equal(fn, ref.f_next), plan
-        else:
-            assert float(np.max(np.abs(fn - ref.f_next))) <= 1e-10 * scale, plan
-        uscale = float(np.max(np.sqrt(ref.ux ** 2 + ref.uy ** 2)))
-        assert float(np.max(np.abs(ux - ref.ux))) <= 1e-10 * uscale and float(np.max(np.abs(uy - ref.uy))) <= 1e-10 * uscale, plan
+        assert_matches_reference(plan, fn, macros, log, ref, u_bar_rel(ref), fast_rho=False)     # (strict rho at 1e-14 too)
 
 
 # ---- 3. the inlet column through every reporter ----------------------------------------------------------------------------------

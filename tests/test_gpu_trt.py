@@ -11,8 +11,8 @@ import struct
 import numpy as np
 import pytest
 
-from tests.helpers import (ORACLE_PLANS, PKG, PLANS, assert_group_is_whole, host_staged_two_strips, lbm_gpu, read_csv_rows, read_params,  # noqa: F401
-                           read_velocity_field, record, run_solver, square, strict, whole_run)
+from tests.helpers import (ORACLE_PLANS, PKG, PLANS, U_BAR_ABS, assert_group_is_whole, assert_matches_reference, host_staged_two_strips,  # noqa: F401
+                           lbm_gpu, read_csv_rows, read_params, read_velocity_field, record, run_solver, square, whole_run)
 from tests.reference import oracle_run, trt_collide
 
 pytestmark = pytest.mark.gpu
@@ -56,19 +56,9 @@ def test_trt_against_the_reference(lbm, name, plan):
         assert ctx.first_unstable_step() == ref.first_unstable
         log = ctx.drain_force_log()
         fn = ctx.populations("f_next")
-        rho, ux, uy = ctx.macros()
+        macros = ctx.macros()
         assert ctx.kernel_name().endswith((",4>", ",5>")), ctx.kernel_name()
-    assert [r[0] for r in log] == [r[0] for r in ref.forces]
-    if strict(plan):
-        assert np.array_equal(fn, ref.f_next), plan
-        assert float(np.max(np.abs(rho - ref.rho))) <= 1e-14, plan
-    else:
-        scale = float(np.max(np.abs(ref.f_next)))
-        assert float(np.max(np.abs(fn - ref.f_next))) <= 1e-10 * scale, plan
-        assert float(np.max(np.abs(rho - ref.rho))) <= 1e-10, plan
-    assert float(np.max(np.abs(ux - ref.ux))) <= 1e-10 and float(np.max(np.abs(uy - ref.uy))) <= 1e-10, plan
-    for (t, fx, fy), (_, rx, ry) in zip(log, ref.forces):
-        assert abs(fx - rx) <= 1e-10 * max(1.0, abs(rx)) and abs(fy - ry) <= 1e-10 * max(1.0, abs(ry)), (plan, t)
+    assert_matches_reference(plan, fn, macros, log, ref, U_BAR_ABS)
 
 
 # ---- 2. degenerate magic parameter: the two rates coincide, BGK up to rounding ----------------------------------------------------

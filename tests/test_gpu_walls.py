@@ -1,9 +1,9 @@
 """Free-slip and moving top / bottom walls (lbm_set_wall, Context/Group(walls=...), lbm_solver --wall-south / --wall-north / --walls) on the GPU.
 
-The reference is walls_run of tests/walls_reference.py: the stepwise oracle loop with a numpy restatement of all of lbmo_boundaries, the
-two walls with their kind and k = u_w / 6 first. fp64, IEEE, in the operation order of the library's strict arithmetic: strict plans must
-match it bit for bit, contracted ones within 1e-10 (the bars of the TRT and LES tests). tests/test_walls_cpu.py pins the reference, with
-two no-slip walls, to the unmodified oracle."""
+The reference is oracle_run(walls=...) of tests/reference.py: the stepwise oracle loop, whose boundary step is a numpy restatement of all
+of lbmo_boundaries, the two walls with their kind and k = u_w / 6 first. fp64, IEEE, in the operation order of the library's strict
+arithmetic: strict plans must match it bit for bit, contracted ones within 1e-10 (the bars of the TRT and LES tests).
+tests/test_reference_cpu.py pins the loop, with two no-slip walls, to the unmodified oracle."""
 import functools
 import importlib
 import struct
@@ -11,10 +11,9 @@ import struct
 import numpy as np
 import pytest
 
-from tests.helpers import (ORACLE_PLANS, PKG, PLANS, assert_group_is_whole, host_staged_two_strips, lbm_gpu, read_csv_rows, read_params,  # noqa: F401
-                           read_velocity_field, record, run_solver, square, strict, whole_run)
-from tests.reference import trt_collide
-from tests.walls_reference import FREESLIP, NOSLIP, moving, walls_run
+from tests.helpers import (ORACLE_PLANS, PKG, PLANS, U_BAR_ABS, assert_group_is_whole, assert_matches_reference, host_staged_two_strips,  # noqa: F401
+                           lbm_gpu, read_csv_rows, read_params, read_velocity_field, record, run_solver, square, whole_run)
+from tests.reference import FREESLIP, NOSLIP, REPEAT, moving, oracle_run, trt_collide
 
 pytestmark = pytest.mark.gpu
 
@@ -46,8 +45,8 @@ def reference(name):
     """(the reference run of the case, max |f_next - f_next of the same case between two no-slip walls|); on the CPU, once."""
     lbm = importlib.import_module(PKG)
     walls, mask, u = case_inputs(name, lbm)
-    ref = walls_run(NX, NY, STEPS, OF, walls=walls, mask=mask, u=u, **KW)
-    plain = walls_run(NX, NY, STEPS, OF, mask=mask, u=u, **KW)
+    ref = oracle_run(NX, NY, STEPS, OF, walls=walls, mask=mask, u=u, **KW)
+    plain = oracle_run(NX, NY, STEPS, OF, mask=mask, u=u, **KW)
     return ref, float(np.max(np.abs(ref.f_next - plain.f_next)))
 
 
@@ -66,18 +65,8 @@ def test_walls_against_the_reference(lbm, name, plan):
         assert ctx.first_unstable_step() == ref.first_unstable
         log = ctx.drain_force_log()
         fn = ctx.populations("f_next")
-        rho, ux, uy = ctx.macros()
-    assert [r[0] for r in log] == [r[0] for r in ref.forces]
-    if strict(plan):
-        assert np.array_equal(fn, ref.f_next), plan
-        assert float(np.max(np.abs(rho - ref.rho))) <= 1e-14, plan
-    else:
-        scale = float(np.max(np.abs(ref.f_next)))
-        assert float(np.max(np.abs(fn - ref.f_next))) <= 1e-10 * scale, plan
-        assert float(np.max(np.abs(rho - ref.rho))) <= 1e-10, plan
-    assert float(np.max(np.abs(ux - ref.ux))) <= 1e-10 and float(np.max(np.abs(uy - ref.uy))) <= 1e-10, plan
-    for (t, fx, fy), (_, rx, ry) in zip(log, ref.forces):
-        assert abs(fx - rx) <= 1e-10 * max(1.0, abs(rx)) and abs(fy - ry) <= 1e-10 * max(1.0, abs(ry)), (plan, t)
+        macros = ctx.macros()
+    assert_matches_reference(plan, fn, macros, log, ref, U_BAR_ABS)
 
 
 # ---- 1b. a second collision operator under the walls: TRT against the reference loop with trt_collide -----------------------------
@@ -86,8 +75,8 @@ TRT_MAGIC, TRT_WALLS = 3.0 / 16.0, (moving(0.05), FREESLIP)
 
 @functools.lru_cache(maxsize=None)
 def trt_reference():
-    ref = walls_run(NX, NY, STEPS, OF, walls=TRT_WALLS, collide=functools.partial(trt_collide, magic=TRT_MAGIC), **KW)
-    plain = walls_run(NX, NY, STEPS, OF, collide=functools.partial(trt_collide, magic=TRT_MAGIC), **KW)
+    ref = oracle_run(NX, NY, STEPS, OF, walls=TRT_WALLS, collide=functools.partial(trt_collide, magic=TRT_MAGIC), **KW)
+    plain = oracle_run(NX, NY, STEPS, OF, collide=functools.partial(trt_collide, magic=TRT_MAGIC), **KW)
     return ref, float(np.max(np.abs(ref.f_next - plain.f_next)))
 
 
@@ -101,17 +90,37 @@ def test_trt_with_walls_against_the_reference(lbm, plan):
         assert ctx.first_unstable_step() == -1 and ctx.kernel_name().endswith((",4>", ",5>"))
         log = ctx.drain_force_log()
         fn = ctx.populations("f_next")
-        rho, ux, uy = ctx.macros()
-    assert [r[0] for r in log] == [r[0] for r in ref.forces]
-    if strict(plan):
-        assert np.array_equal(fn, ref.f_next), plan
-        assert float(np.max(np.abs(rho - ref.rho))) <= 1e-14, plan
-    else:
-        assert float(np.max(np.abs(fn - ref.f_next))) <= 1e-10 * float(np.max(np.abs(ref.f_next))), plan
-        assert float(np.max(np.abs(rho - ref.rho))) <= 1e-10, plan
-    assert float(np.max(np.abs(ux - ref.ux))) <= 1e-10 and float(np.max(np.abs(uy - ref.uy))) <= 1e-10, plan
-    for (t, fx, fy), (_, rx, ry) in zip(log, ref.forces):
-        assert abs(fx - rx) <= 1e-10 * max(1.0, abs(rx)) and abs(fy - ry) <= 1e-10 * max(1.0, abs(ry)), (plan, t)
+        macros = ctx.macros()
+    assert_matches_reference(plan, fn, macros, log, ref, U_BAR_ABS)
+
+
+# ---- 1c. every feature of the boundary step at once: an inlet schedule on a profile, TRT, both walls, a mask -------------------------
+@functools.lru_cache(maxsize=None)
+def cross_reference():
+    """(the reference run, [max |f_next - f_next of the same case with one feature switched off|: walls, schedule, TRT]); on the CPU,
+    once. The pulse's period 7 is coprime to every launch depth."""
+    lbm = importlib.import_module(PKG)
+    on = dict(mask=square(NX, NY), u=lbm.parabolic_profile(NY, KW["inlet_velocity"]), walls=TRT_WALLS,
+              schedule=(lbm.sine_pulse(0.3, 7), REPEAT), collide=functools.partial(trt_collide, magic=TRT_MAGIC))
+    ref = oracle_run(NX, NY, STEPS, OF, **on, **KW)
+    away = [float(np.max(np.abs(ref.f_next - oracle_run(NX, NY, STEPS, OF, **dict(on, **off), **KW).f_next)))
+            for off in (dict(walls=NOSLIP), dict(schedule=None), dict(collide=None))]
+    return ref, on, away
+
+
+@pytest.mark.parametrize("plan", ORACLE_PLANS)
+def test_schedule_with_trt_and_walls_against_the_reference(lbm, plan):
+    ref, on, away = cross_reference()
+    assert ref.first_unstable == -1 and min(away) > 1e-3, away     # on the CPU, before the GPU run: stable, and each feature is active
+    with lbm.Context(NX, NY, options=PLANS[plan], solid=on["mask"], inlet_profile=on["u"], inlet_schedule=(on["schedule"][0], "repeat"),
+                     trt_magic=TRT_MAGIC, walls=TRT_WALLS, **KW) as ctx:
+        ctx.initialise()
+        ctx.step(STEPS, OF)
+        assert ctx.first_unstable_step() == -1 and ctx.kernel_name().endswith((",4>", ",5>"))
+        log = ctx.drain_force_log()
+        fn = ctx.populations("f_next")
+        macros = ctx.macros()
+    assert_matches_reference(plan, fn, macros, log, ref, U_BAR_ABS)
 
 
 # ---- 2. free-slip keeps a uniform stream uniform ----------------------------------------------------------------------------------
@@ -123,9 +132,9 @@ def test_free_slip_keeps_a_uniform_stream_uniform(lbm):
     nx, ny, steps, u0 = 160, 48, 600, 0.08
     kw = dict(tau=0.55, inlet_velocity=u0)
     empty = np.zeros((ny, nx), np.uint8)
-    plain = walls_run(nx, ny, steps, 0, mask=empty, **kw)          # precondition, on the CPU: no-slip walls do disturb the stream
+    plain = oracle_run(nx, ny, steps, 0, mask=empty, **kw)          # precondition, on the CPU: no-slip walls do disturb the stream
     assert plain.first_unstable == -1 and max(uniformity(plain.rho, plain.ux, plain.uy, u0)) > 1e-2
-    ref = walls_run(nx, ny, steps, 0, walls=FREESLIP, mask=empty, **kw)
+    ref = oracle_run(nx, ny, steps, 0, walls=FREESLIP, mask=empty, **kw)
     record("walls_uniform_stream_reference", err=uniformity(ref.rho, ref.ux, ref.uy, u0))
     with lbm.Context(nx, ny, solid=empty, walls="free-slip", options=dict(arith=0), **kw) as ctx:
         ctx.initialise()
@@ -197,7 +206,7 @@ def test_host_staged_strips_with_walls(lbm):
 @pytest.mark.parametrize("walls", [NOSLIP, FREESLIP])
 def test_stability_follows_the_reference(lbm, walls):
     stab = dict(tau=0.505, inlet_velocity=0.1)
-    want = walls_run(400, 100, 4000, 0, walls=walls, **stab).first_unstable
+    want = oracle_run(400, 100, 4000, 0, walls=walls, **stab).first_unstable
     with lbm.Context(400, 100, options=dict(arith=0), walls=(walls, walls), **stab) as ctx:
         ctx.initialise()
         ctx.step(4000, 0)

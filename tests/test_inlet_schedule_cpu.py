@@ -1,4 +1,4 @@
-"""The inlet schedule of lbm_set_inlet_schedule without a GPU: the reference of the schedule tests pinned to oracle_run, the index
+"""The inlet schedule of lbm_set_inlet_schedule without a GPU: oracle_run(schedule=...) pinned to oracle_run(u=...), the index
 function the kernels call (lbm_debug_inlet_scale: compiled for the host) against a Python restatement, the argument errors that need
 no device (the library's and lbm_solver's), and the C++ builders of --inlet-ramp / --inlet-pulse against the Python helpers."""
 import ctypes as C
@@ -8,8 +8,7 @@ import numpy as np
 import pytest
 
 from tests.helpers import lbm_cpu, masks, solver  # noqa: F401
-from tests.inlet_schedule_reference import HOLD, REPEAT, sched_index, schedule_run
-from tests.reference import oracle_run
+from tests.reference import HOLD, REPEAT, oracle_run, sched_index
 
 MAX = 1048576       # LBM_INLET_SCHEDULE_MAX
 
@@ -21,7 +20,7 @@ def same_run(a, b):
     assert a.forces == b.forces
 
 
-# ---- the reference is oracle_run -------------------------------------------------------------------------------------------------
+# ---- schedule= against u= --------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("c", [1.0, 0.7, -0.4])
 def test_a_constant_schedule_is_the_scaled_profile_bit_for_bit(c):
     nx, ny, steps, of = 96, 40, 45, 10
@@ -30,16 +29,16 @@ def test_a_constant_schedule_is_the_scaled_profile_bit_for_bit(c):
     u = 0.3 * y * (1 - y) * (1.0 + 0.3 * np.sin(1.7 * np.arange(ny)))
     mask = masks(200, 64)["inlet-outlet"][:ny, :nx]
     for mode in (HOLD, REPEAT):
-        same_run(schedule_run(nx, ny, steps, of, s=[c], mode=mode, mask=mask, u=u, **kw), oracle_run(nx, ny, steps, of, mask=mask, u=c * u, **kw))
+        same_run(oracle_run(nx, ny, steps, of, schedule=([c], mode), mask=mask, u=u, **kw), oracle_run(nx, ny, steps, of, mask=mask, u=c * u, **kw))
     # without a profile: the uniform inlet_velocity on every row
-    same_run(schedule_run(nx, ny, steps, of, s=[c, c, c], **kw), oracle_run(nx, ny, steps, of, u=c * np.full(ny, 0.05), **kw))
+    same_run(oracle_run(nx, ny, steps, of, schedule=([c, c, c], HOLD), **kw), oracle_run(nx, ny, steps, of, u=c * np.full(ny, 0.05), **kw))
 
 
 def test_a_varying_schedule_changes_the_run_and_reports_the_last_factor():
     nx, ny, steps = 96, 40, 23
     u = np.full(ny, 0.05)
     s = 1.0 + 0.5 * np.sin(2 * np.pi * np.arange(7) / 7)
-    a = schedule_run(nx, ny, steps, 0, s=s, mode=REPEAT, inlet_velocity=0.05)
+    a = oracle_run(nx, ny, steps, 0, schedule=(s, REPEAT), inlet_velocity=0.05)
     b = oracle_run(nx, ny, steps, 0, u=u, inlet_velocity=0.05)
     assert not np.array_equal(a.f_next, b.f_next)
     assert np.array_equal(a.ux[:, 0], u * s[(steps - 1) % 7])

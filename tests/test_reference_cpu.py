@@ -1,14 +1,15 @@
 """tests/reference.py against the unmodified C oracle (no GPU): each shared piece, switched on in a way that must change nothing, gives
-the plain run's bits, and the stepwise loop gives those of Oracle.run. A later edit of the shared moment, equilibrium, inlet or loop
-code therefore cannot move every feature's reference at once without failing here."""
+the plain run's bits — also under another feature — and the stepwise loop, whose boundary step is numpy, gives those of Oracle.run. A
+later edit of the shared moment, equilibrium, boundary or loop code therefore cannot move every feature's reference at once without
+failing here."""
 import functools
 
 import numpy as np
 import pytest
 
 from oracle.oracle import Oracle, make_params
-from tests.helpers import square
-from tests.reference import les_collide, oracle_run
+from tests.helpers import assert_forces_match, square
+from tests.reference import FREESLIP, HOLD, NOSLIP, les_collide, moving, oracle_run, trt_collide
 
 NX, NY, STEPS, OF = 160, 48, 120, 30
 KW = dict(tau=0.55, inlet_velocity=0.08, cylinder_radius=0.1)
@@ -80,4 +81,40 @@ def test_the_stepwise_loop_is_oracle_run(geometry):
     if geometry == "disc":
         for (t, fx, fy, _, _), (_, rx, ry) in zip(rows, want.forces):
             print(f"t={t}: lbmo_forces ({fx:.17g}, {fy:.17g}) link_forces ({rx:.17g}, {ry:.17g}) diff ({abs(fx - rx):.2e}, {abs(fy - ry):.2e})")
-            assert abs(fx - rx) <= 1e-10 * max(1.0, abs(rx)) and abs(fy - ry) <= 1e-10 * max(1.0, abs(ry)), t
+        assert_forces_match([r[:3] for r in rows], want.forces, "lbmo_forces against link_forces")
+
+
+@pytest.mark.parametrize("geometry", GEOMETRIES)
+def test_no_slip_reference_is_the_oracle_bit_for_bit(geometry):
+    """The loop every feature uses, its numpy boundary step included, with two no-slip walls named: f_current too, over 240 steps."""
+    steps = 240
+    ref, fcur = oracle_run(NX, NY, steps, 0, mask=mask_of(geometry), walls=(NOSLIP, NOSLIP), keep_f_current=True, **KW)
+    o = Oracle(make_params(NX, NY, **KW))
+    if geometry == "square":
+        o.solid[:] = square(NX, NY)
+        o.L.lbmo_initialise(o.h)
+    assert o.run(steps) == -1 and ref.first_unstable == -1
+    for name, got, want in (("f_current", fcur, o.f_current), ("f_next", ref.f_next, o.f_next), ("rho", ref.rho, o.rho),
+                            ("ux", ref.ux, o.ux), ("uy", ref.uy, o.uy)):
+        assert np.array_equal(got, want), name
+    assert ref.solid_count == o.solid_count()
+    o.close()
+
+
+# ---- feature crosses: one feature, switched on in a way that must change nothing, under another -------------------------------------
+def test_a_constant_schedule_under_walls_is_the_scaled_profile():
+    c, walls = 0.7, (moving(0.05), FREESLIP)
+    u = 0.1 * (np.arange(NY) + 1.0) / NY
+    got = oracle_run(NX, NY, STEPS, OF, mask=square(NX, NY), u=u, walls=walls, schedule=([c], HOLD), **KW)
+    want = oracle_run(NX, NY, STEPS, OF, mask=square(NX, NY), u=c * u, walls=walls, **KW)
+    assert_same_run(got, want)
+    away = oracle_run(NX, NY, STEPS, OF, mask=square(NX, NY), u=c * u, **KW)           # ... and the walls were active in both
+    assert float(np.max(np.abs(want.f_next - away.f_next))) > 1e-3
+
+
+def test_the_schedule_of_one_under_trt_is_no_schedule():
+    trt = functools.partial(trt_collide, magic=3.0 / 16.0)
+    got = oracle_run(NX, NY, STEPS, OF, collide=trt, schedule=([1.0], HOLD), **KW)
+    want = oracle_run(NX, NY, STEPS, OF, collide=trt, **KW)
+    assert_same_run(got, want)
+    assert not np.array_equal(want.f_next, plain("disc").f_next)                      # ... and TRT was active in both

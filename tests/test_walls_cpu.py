@@ -1,28 +1,14 @@
-"""The walls of lbm_set_wall without a GPU: the numpy reference of the wall tests against the unmodified oracle, the kernels' wall rule
-(lbm_debug_wall_rule: the very inline function, compiled for the host) against the table of include/lbm_hip.h, and the argument errors
-that need no device (the library's and lbm_solver's)."""
+"""The walls of lbm_set_wall without a GPU: the kernels' wall rule (lbm_debug_wall_rule: the very inline function, compiled for the
+host) against the table of include/lbm_hip.h, and the argument errors that need no device (the library's and lbm_solver's). (The
+reference loop with two no-slip walls is pinned to the unmodified oracle in tests/test_reference_cpu.py.)"""
 import ctypes as C
 import subprocess
 
 import numpy as np
 import pytest
 
-from oracle.oracle import Oracle, make_params
 from tests.helpers import lbm_cpu, solver  # noqa: F401
-from tests.walls_reference import FREESLIP, NOSLIP, moving, wall_kind_k, wall_rule, walls_run
-
-
-def test_no_slip_reference_is_the_oracle_bit_for_bit():
-    nx, ny, steps = 160, 48, 240
-    kw = dict(tau=0.55, inlet_velocity=0.08, cylinder_radius=0.1)
-    ref, fcur = walls_run(nx, ny, steps, 0, walls=(NOSLIP, NOSLIP), keep_f_current=True, **kw)
-    o = Oracle(make_params(nx, ny, **kw))
-    assert o.run(steps) == -1 and ref.first_unstable == -1
-    for name, got, want in (("f_current", fcur, o.f_current), ("f_next", ref.f_next, o.f_next), ("rho", ref.rho, o.rho),
-                            ("ux", ref.ux, o.ux), ("uy", ref.uy, o.uy)):
-        assert np.array_equal(got, want), name
-    assert ref.solid_count == o.solid_count()
-    o.close()
+from tests.reference import FREESLIP, NOSLIP, moving, wall_kind_k, wall_rule
 
 
 @pytest.mark.parametrize("precision", ["f64", "f32"])
