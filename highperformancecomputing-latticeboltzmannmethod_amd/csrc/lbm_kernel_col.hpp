@@ -84,6 +84,7 @@ __global__ void __launch_bounds__(NW * 64, (col_min_waves<T, NW, AR>())) k_stepc
     // that are garbage anyway: round 4 dropped the two phantom slots, 63 -> 51 KB at 8 fp64 waves, so that 12 waves fit two
     // blocks per CU); one pad column on each side for the diagonal reads at lane -/+ 1
     __shared__ T xbuf[2][NW][6][LW];
+    __shared__ T u_sh[NW][R];                              // (general tiles with column 0) the inlet velocity of every wave's rows
     const int lane = (int)threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
     const int nbx = (a.nx + OW - 1) / OW, nby = (a.y_cnt + OH - 1) / OH + (a.y_cnt2 + OH - 1) / OH, nb = nbx * nby;
@@ -107,12 +108,44 @@ __global__ void __launch_bounds__(NW * 64, (col_min_waves<T, NW, AR>())) k_stepc
         // bit j: the thread's cell of row j is solid. The thread <-> cell map is fixed for all D levels, so the geometry is looked
         // up once, here, and serves every level and the store predicate (block-uniform branch: only tiles near a solid cell)
         unsigned sbits = 0;
-        if (!LEAN && fr.near_solid && col_in) {
+        // The general path fetches once what no level of a launch changes, and every read of level 1 goes out before the first value is
+        // looked at (one exposed round trip per wave, like the lean path's; the per-row and per-level reads it had cost one each):
+        //   mw    the mask words of the thread's R cells (a masked context near a solid cell; the disc is arithmetic), looked at once the
+        //         lattice loads are out
+        //   u_sh  the inlet velocity of the wave's R rows (tiles with column 0): lane j fetches row j's, the wave keeps them in its own
+        //         slot of shared memory (no other wave reads it: no barrier) and the inlet branch of every level reads them there. Held
+        //         in scalar registers they cost the TRT and LES kernels their occupancy step (profiles/boundary_tiles/README.md)
+        //   the ghost constants e.feq_in are read at level 1 only: a cell outside the domain takes its permanent value there and keeps
+        //   it, levels 2..D skip it
+        // Every address is one that the per-level reads took before, under the same test.
+        // The tests on a row are wave-uniform and the same at every level; they are made once and kept as two words of R bits (bit j:
+        // row j): rin, the row lies inside the domain; rld, level 1 loads it (inside, and not beyond what the band's outputs need).
+        // Written out at every use, each comparison stayed live from level 1 to level D as a 64-bit lane mask of its own (scalar spills).
+        unsigned long long mw[R];
+        unsigned rin = 0, rld = 0;
+        const bool masked = !LEAN && fr.near_solid && a.mv.bits != nullptr;                     // (block-uniform)
+        if (!LEAN) {
 #pragma unroll
             for (int j = 0; j < R; ++j) {
-                const int yg = a.y_start + Yr + ry0 + j;
-                if (yg >= 0 && yg < a.ny_glob && solid_at(a, x, yg)) sbits |= 1u << j;
+                const int y = Yr + ry0 + j, yg = a.y_start + y;
+                mw[j] = 0;
+                if (yg >= 0 && yg < a.ny_glob) { rin |= 1u << j; if (y <= y_end + HW - 1) rld |= 1u << j; }
             }
+            if (fr.near_solid && col_in) {
+#pragma unroll
+                for (int j = 0; j < R; ++j) {
+                    const int yg = a.y_start + Yr + ry0 + j;
+                    if ((rin >> j) & 1u) {
+                        if (masked) mw[j] = mask_word(a.mv, x, yg);
+                        else if (is_solid_cell(x, yg, a.cyl_x, a.cyl_y, a.cyl_r2)) sbits |= 1u << j;
+                    }
+                }
+            }
+            if (bx == 0 && lane < R) {
+                const int yg = a.y_start + Yr + ry0 + lane;
+                u_sh[w][lane] = (yg >= 0 && yg < a.ny_glob) ? a.u_row[yg] : T(0);
+            }
+            __builtin_amdgcn_wave_barrier();                       // (other lanes of this wave read the slot: no instruction, an order)
         }
         LBM_PROF_IDS(b, NW, w);
         LBM_PROF(b, NW, w, 0);
@@ -130,18 +163,51 @@ __global__ void __launch_bounds__(NW * 64, (col_min_waves<T, NW, AR>())) k_stepc
                 collide<T, AR>(g[j], a);
             }
         } else {
+            // rows outside the domain, or beyond what the band's outputs need (wave-uniform): outside_value. The nine constants come by
+            // VECTOR loads straight into the row's registers, like the lattice loads below and waited for with them: the address is
+            // uniform, and left to itself the compiler fetches them into 9 / 18 scalar registers, which this kernel does not have
+            // (scalar spills in the TRT kernels)
 #pragma unroll
             for (int j = 0; j < R; ++j) {
-                const int y = Yr + ry0 + j, yg = a.y_start + y;
-                const bool row_in = (yg >= 0 && yg < a.ny_glob);
-                if (!(row_in && col_in) || y > y_end + HW - 1) {
+                const bool row_in = (rin >> j) & 1u;
+                if (!((rld >> j) & 1u)) {
+                    const T* fq = e.feq_in;
+                    asm volatile("" : "+v"(fq));                                     // (a vector register: the loads below are vector loads)
 #pragma unroll
-                    for (int i = 0; i < Q; ++i) g[j][i] = outside_value(e, row_in, col_in, i);
-                } else {
-                    const long c = (long)(y + GR) * a.pitch + a.xoff + x;
+                    for (int i = 0; i < Q; ++i) g[j][i] = T(0);
+                    if (!(row_in && !col_in)) {
 #pragma unroll
-                    for (int i = 0; i < Q; ++i) g[j][i] = a.src[(long)i * a.plane + c - (long)cy(i) * a.pitch - cx(i)];
-                    cell_update_as<T, AR, true>(a, g[j], x, yg, 0, (sbits >> j) & 1u, fr.near_solid, true, bad);
+                        for (int i = 0; i < Q; ++i) g[j][i] = fq[i];
+                    }
+                }
+            }
+            // the loads of all other rows, each under the test it always had (a lane without a column: outside_value's zero) ...
+#pragma unroll
+            for (int j = 0; j < R; ++j) {
+                const int y = Yr + ry0 + j;
+                if ((rld >> j) & 1u) {
+#pragma unroll
+                    for (int i = 0; i < Q; ++i) g[j][i] = T(0);
+                    if (col_in) {
+                        const long c = (long)(y + GR) * a.pitch + a.xoff + x;
+#pragma unroll
+                        for (int i = 0; i < Q; ++i) g[j][i] = a.src[(long)i * a.plane + c - (long)cy(i) * a.pitch - cx(i)];
+                    }
+                }
+            }
+            if (masked) {
+#pragma unroll
+                for (int j = 0; j < R; ++j) sbits |= (unsigned)((mw[j] >> (x & 63)) & 1ull) << j;
+            }
+            // ... then the updates. A lane without a column computes on zeros, is not counted and takes its zeros back: a select, no
+            // branch (a block-uniform flag around it, for the tiles that have such lanes, cost scalar spills in the fp64 TRT kernels)
+#pragma unroll
+            for (int j = 0; j < R; ++j) {
+                const int yg = a.y_start + Yr + ry0 + j;
+                if ((rld >> j) & 1u) {
+                    cell_update_with<T, AR, true>(a, g[j], x, yg, 0, (sbits >> j) & 1u, fr.near_solid, col_in, bad, [&]() { return u_sh[w][j]; });
+#pragma unroll
+                    for (int i = 0; i < Q; ++i) g[j][i] = col_in ? g[j][i] : T(0);
                 }
             }
         }
@@ -162,28 +228,27 @@ __global__ void __launch_bounds__(NW * 64, (col_min_waves<T, NW, AR>())) k_stepc
             for (int j = 0; j < R; ++j) {
                 const int ry = ry0 + j;
                 const T n2 = g[j][2], n5 = g[j][5], n6 = g[j][6];       // this row's north-going values, for row j+1
-                if (ry >= L - 1 && ry <= H - L) {                       // (wave-uniform) rows outside hold garbage from here on
+                const int y = Yr + ry, yg = a.y_start + y;
+                // (wave-uniform) rows outside the level's window hold garbage from here on; a row outside the domain keeps the ghost
+                // values that level 1 gave it
+                if (ry >= L - 1 && ry <= H - L && (LEAN || ((rin >> j) & 1u))) {
                 T f[Q];
                 f[0] = g[j][0]; f[1] = from_left(g[j][1]); f[3] = from_right(g[j][3]);
                 f[2] = p2; f[5] = p5; f[6] = p6;
                 if (j < R - 1) { f[4] = g[j + 1][4]; f[7] = from_right(g[j + 1][7]); f[8] = from_left(g[j + 1][8]); }
                 else { f[4] = xb[wa][3][1 + lane]; f[7] = xb[wa][4][2 + lane]; f[8] = xb[wa][5][lane]; }   // (read here, not after the barrier: six registers fewer are live across the rows below; the buffer is not rewritten before this wave has passed the next barrier)
                 const bool valid = lane_ok;
-                const int y = Yr + ry, yg = a.y_start + y;
                 bool store = L == D && lane >= HW && lane < 64 - HW && ry >= HW && ry < H - HW;
                 if (LEAN) {
                     badl |= unstable_if(f, valid);
                     collide<T, AR>(f, a);
                 } else {
-                    const bool row_in = (yg >= 0 && yg < a.ny_glob);
-                    if (!(row_in && col_in)) {
+                    // (a lane without a column: as at level 1 — not counted, not stored, its zeros back)
+                    cell_update_with<T, AR, true>(a, f, x, yg, L - 1, (sbits >> j) & 1u, fr.near_solid,
+                                                  valid && col_in && y <= y_end + HW - L, badl, [&]() { return u_sh[w][j]; });
 #pragma unroll
-                        for (int i = 0; i < Q; ++i) f[i] = outside_value(e, row_in, col_in, i);
-                        store = false;
-                    } else {
-                        cell_update_as<T, AR, true>(a, f, x, yg, L - 1, (sbits >> j) & 1u, fr.near_solid, valid && y <= y_end + HW - L, badl);
-                        store = store && y < y_end && !((sbits >> j) & 1u);
-                    }
+                    for (int i = 0; i < Q; ++i) f[i] = col_in ? f[i] : T(0);
+                    store = store && col_in && y < y_end && !((sbits >> j) & 1u);
                 }
                 if (L < D) {
 #pragma unroll

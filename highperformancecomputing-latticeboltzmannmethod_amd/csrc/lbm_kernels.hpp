@@ -73,6 +73,12 @@ __host__ __device__ inline bool mask_cell(const MaskView& m, int x, int yg) {   
     if (r < 0 || r >= m.rows) return false;
     return (m.bits[(long)r * m.words + (x >> 6)] >> (x & 63)) & 1ull;
 }
+// the word of mask_cell's bit, 0 where mask_cell answers false without a read: the same address under the same test, for a caller that
+// issues the read early and looks at bit x & 63 later (k_stepc_col)
+__device__ __forceinline__ unsigned long long mask_word(const MaskView& m, int x, int yg) {
+    const int r = yg - m.y0;
+    return (r < 0 || r >= m.rows) ? 0ull : m.bits[(long)r * m.words + (x >> 6)];
+}
 // any solid cell in [x0, x1] x [yg0, yg1] (global, inclusive)? Exact at block granularity, so a superset of the cell test: it never
 // answers false where a solid cell lies in the box.
 __host__ __device__ inline bool mask_box_any(const MaskView& m, int x0, int x1, int yg0, int yg1) {
@@ -264,14 +270,21 @@ __device__ __forceinline__ void apply_bcs(T (&f)[Q], bool bottom, bool top, bool
 // the first-unstable bookkeeping forms. The device word is read under the schedule's test only — a captured graph carries a fixed `t` and
 // advances the word itself, so replays take the right entry with no host involvement. Everything the schedule touches is launch- and
 // level-uniform.
-template <typename T>
-__device__ __forceinline__ void bcs_at(const KArgs<T>& a, T (&f)[Q], int x, int yg, int lvl) {
+// `row_u` gives u_row[yg]: the load itself (bcs_at), or a value that the caller fetched once for all levels of a launch (k_stepc_col,
+// whose threads keep their rows: the velocity of a row is wave-uniform there and never changes inside a launch; the schedule's factor does,
+// from level to level, and stays here).
+template <typename T, typename U>
+__device__ __forceinline__ void bcs_at_with(const KArgs<T>& a, T (&f)[Q], int x, int yg, int lvl, U&& row_u) {
     T rho_bc, u_out;
     apply_bcs(f, yg == 0, yg == a.ny_glob - 1, x == 0, x == a.nx - 1, [&]() {
-        T u = a.u_row[yg];
+        T u = row_u();
         if (a.sched) u = u * inlet_sched_at<T>(a.sched, *a.t_base + a.t + lvl);
         return u;
     }, a.walls, a.wk, rho_bc, u_out);
+}
+template <typename T>
+__device__ __forceinline__ void bcs_at(const KArgs<T>& a, T (&f)[Q], int x, int yg, int lvl) {
+    bcs_at_with(a, f, x, yg, lvl, [&]() { return a.u_row[yg]; });
 }
 
 // Arithmetic of the collision (the only place the two modes differ):
@@ -618,10 +631,11 @@ template <typename T> struct K2Extra {
 // One general cell of level lvl + 1 (any cell of a non-LEAN path): BCs of that level's iteration unless solid, the stability test where `count`, the
 // collision; a solid cell keeps w_i (its collision result is discarded). `near_solid` is block-uniform: tiles far from every
 // solid cell skip the select. BRANCH_FREE: the stability test is unstable_if (k_stepc_col, whose garbage cells are masked).
-template <typename T, int AR, bool BRANCH_FREE = false>
-__device__ __forceinline__ void cell_update_as(const KArgs<T>& a, T (&f)[Q], int x, int yg, int lvl, bool solid, bool near_solid,
-                                               bool count, bool& bad) {
-    if (!solid) bcs_at(a, f, x, yg, lvl);
+// cell_update_with: the same with the row's inlet velocity from `row_u` (bcs_at_with).
+template <typename T, int AR, bool BRANCH_FREE = false, typename U>
+__device__ __forceinline__ void cell_update_with(const KArgs<T>& a, T (&f)[Q], int x, int yg, int lvl, bool solid, bool near_solid,
+                                                 bool count, bool& bad, U&& row_u) {
+    if (!solid) bcs_at_with(a, f, x, yg, lvl, row_u);
     if (BRANCH_FREE) bad |= unstable_if(f, count);
     else if (count) bad |= any_unstable(f);
     collide<T, AR>(f, a);
@@ -629,6 +643,11 @@ __device__ __forceinline__ void cell_update_as(const KArgs<T>& a, T (&f)[Q], int
 #pragma unroll
         for (int i = 0; i < Q; ++i) f[i] = solid ? wgt<T>(i) : f[i];
     }
+}
+template <typename T, int AR, bool BRANCH_FREE = false>
+__device__ __forceinline__ void cell_update_as(const KArgs<T>& a, T (&f)[Q], int x, int yg, int lvl, bool solid, bool near_solid,
+                                               bool count, bool& bad) {
+    cell_update_with<T, AR, BRANCH_FREE>(a, f, x, yg, lvl, solid, near_solid, count, bad, [&]() { return a.u_row[yg]; });
 }
 // ... with the geometry looked up here (block-uniform branch: only tiles near a solid cell)
 template <typename T, int AR>

@@ -15,6 +15,31 @@ def load(path):
     launch_us = float(head.split("launch_us=")[1])
     return head, launch_us, cols, data
 
+def tile_classes(head, blocks):
+    """Of every block index (the tile index the kernel records): True where the tile takes the lean path. The predicate is
+    TileFrame::lean (csrc/lbm_kernels.hpp) on the lattice tools/colbench.hip builds: one whole-domain launch of the fp64 register kernel,
+    the disc at (0.2 nx, 0.5 ny) with radius 0.05 ny. None where the header names no register kernel."""
+    import re
+    m = re.search(r"col R=(\d+) NW=(\d+) D=(\d+) (..) (alt)? *p\d+ (\d+)x(\d+) ", head)
+    if not m:
+        return None
+    R, NW, D = int(m.group(1)), int(m.group(2)), int(m.group(3))
+    nx, ny = int(m.group(6)), int(m.group(7))
+    HW = D - 1
+    OW, OH = 64 - 2 * HW, R * NW - 2 * HW
+    nbx, nby = -(-nx // OW), -(-ny // OH)
+    cx, cy, r = int(0.2 * nx), int(0.5 * ny), int(0.05 * ny) + 1
+    pitch0 = -(-(16 + nx + 1) // 16) * 16                       # (Lattice<double>: 128-byte sub-rows, twelve ghost rows on each side)
+    small = 9 * pitch0 * (ny + 24) * 8 + 4096 < 2 ** 32
+    out = {}
+    for b in blocks:
+        by, bx = divmod(int(b), nbx)
+        X0, Y0 = bx * OW, by * OH
+        near = X0 - HW <= cx + r and X0 + OW - 1 + HW >= cx - r and Y0 - HW <= cy + r and Y0 + OH - 1 + HW >= cy - r
+        out[b] = (not near and X0 >= HW + 1 and X0 + OW + HW <= nx - 1 and Y0 >= HW + 1 and Y0 + OH + HW <= ny - 1
+                  and Y0 + OH <= ny and small and by < nby)
+    return out
+
 def describe(path, show_cu=None):
     head, launch_us, cols, d = load(path)
     t = d[:, 5:].astype(np.float64)
@@ -60,6 +85,33 @@ def describe(path, show_cu=None):
     life = last - first
     print(f"   block lifetime us: median {np.median(life):.2f}, p10 {np.percentile(life,10):.2f}, p90 {np.percentile(life,90):.2f}; "
           f"first starts: {np.sort(first)[:3].round(2)}, last start {first.max():.2f}, last end {last.max():.2f}")
+    # block lifetime by tile class (first mark of wave 0 -> last mark of any wave of the block), lean against general
+    lean = tile_classes(head, blocks)
+    allfirst = np.where(used, t, np.inf).min(axis=1); alllast = np.where(used, t, -np.inf).max(axis=1)
+    if lean is not None:
+        bl = np.array([bix[b] for b in d[:, 0].tolist()])
+        bfirst = np.full(len(blocks), np.inf); blast = np.full(len(blocks), -np.inf)
+        np.minimum.at(bfirst, bl, allfirst); np.maximum.at(blast, bl, alllast)
+        blife = blast - bfirst
+        is_lean = np.array([lean[b] for b in blocks])
+        for name, sel in (("lean", is_lean), ("general", ~is_lean)):
+            if sel.sum():
+                v = blife[sel]
+                print(f"   {name:7s} blocks: {int(sel.sum()):5d}, lifetime us (all waves): median {np.median(v):.2f}, p10 {np.percentile(v,10):.2f}, "
+                      f"p90 {np.percentile(v,90):.2f}")
+        if is_lean.sum() and (~is_lean).sum():
+            print(f"   general / lean median lifetime: {np.median(blife[~is_lean]) / np.median(blife[is_lean]):.3f}")
+    # per XCD: when its last block ends, relative to the launch's end (the last mark of all)
+    xall = d[:, 2] & 0xf
+    end = alllast.max(); start = allfirst.min()
+    ends = {int(k): float(alllast[xall == k].max()) for k in sorted(set(xall.tolist()))}
+    med = float(np.median(list(ends.values())))
+    print("   per XCD: last block's end before the launch's end, us: " + " ".join(f"x{k}:{end - v:.2f}" for k, v in ends.items()))
+    print(f"   slowest XCD ends {max(ends.values()) - med:.2f} us after the median XCD: {100 * (max(ends.values()) - med) / (end - start):.2f} % of the "
+          f"launch ({end - start:.1f} us, first mark to last)")
+    if lean is not None:
+        print("   general blocks per XCD: " + " ".join(f"x{k}:{len(set(d[(xall == k) & ~np.array([lean[b] for b in d[:, 0].tolist()]), 0].tolist()))}"
+                                                       for k in ends))
     # residency per CU
     hw = d[w0, 3]; xcc = d[w0, 2] & 0xf
     cu = ((hw >> 8) & 0xf); sh = (hw >> 12) & 1; se = (hw >> 13) & 0x7
