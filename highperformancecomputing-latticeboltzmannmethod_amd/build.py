@@ -44,6 +44,8 @@ def embedded_id(path=LIB):
 
 # the Arith bases of the collision models (csrc/lbm_plan.hpp collision_models): BGK, Smagorinsky (LES), two relaxation times (TRT)
 COLLISION_BASES = (0, 2, 4)
+# ... and those whose row says `park`: the tall fp64 regions (64x40) are built for them
+PARK_BASES = (0, 2, 4)
 
 
 def units(build_id):
@@ -58,6 +60,8 @@ def units(build_id):
     # the tall fp32 regions (BGK only), the frame kernel (lbm_frames_begin), the probe kernel (lbm_probes_begin)
     out += [("lbm_col.hip", ["-DLBM_COL_TALL=1"], "lbm_col_tall_c.o"), ("lbm_col.hip", ["-DLBM_COL_TALL=0"], "lbm_col_tall_s.o"),
             ("lbm_frames.hip", [], "lbm_frames.o"), ("lbm_probes.hip", [], "lbm_probes.o")]
+    # the tall fp64 regions (64x40, contracted arithmetic), one object per model that has them
+    out += [("lbm_col.hip", ["-DLBM_COL_PARK=%d" % base], "lbm_col_park_ar%d.o" % base) for base in PARK_BASES]
     return out
 
 

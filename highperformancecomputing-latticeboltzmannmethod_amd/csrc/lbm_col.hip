@@ -1,7 +1,8 @@
 // csrc/lbm_col.hip — the translation unit(s) of k_stepc_col (lbm_kernel_col.hpp) and the launchers lbm_hip.hip calls (lbm_col_api.hpp).
 // -DLBM_COL_T=<element type> -DLBM_AR_BASE=<a collision model's Arith base>: the ten instantiations of that type and model on 64 x 32
 // regions (five / six iterations x store policy + seven iterations, x arithmetic); -DLBM_COL_TALL=1 / 0: the three tall fp32 ones of
-// one arithmetic mode, BGK only. One object each (build.py).
+// one arithmetic mode, BGK only; -DLBM_COL_PARK=<base>: the five of the tall fp64 regions (64 x 40, contracted) of one model. One object
+// each (build.py).
 #include "lbm_kernel_col.hpp"
 #include "lbm_col_api.hpp"
 
@@ -39,8 +40,17 @@ void launch_col_tall_strict(const KArgs<float>& a, const K2Extra<float>& e, int 
 #endif
     if (depth == 6) LBM_KC(float, 6, R, W, false, AR); else if (depth == 8) LBM_KC(float, 8, R, W, false, AR); else LBM_KC(float, 7, R, W, false, AR);
 }
+#elif defined(LBM_COL_PARK)  // the tall fp64 regions (64 x 40, eight waves x five rows, the top row parked in LDS), contracted, of one model
+template <int ARB>
+void launch_col_park(const KArgs<double>& a, const K2Extra<double>& e, int depth, bool nt, hipStream_t s) {
+    constexpr int R = col_rows_per_thread(8, false, true), W = col_waves(8, false, true), AR = ARB | 1;
+    if (depth == 5) { if (nt) LBM_KC(double, 5, R, W, true, AR); else LBM_KC(double, 5, R, W, false, AR); }
+    else if (depth == 7) LBM_KC(double, 7, R, W, false, AR);
+    else { if (nt) LBM_KC(double, 6, R, W, true, AR); else LBM_KC(double, 6, R, W, false, AR); }
+}
+template void launch_col_park<LBM_COL_PARK>(const KArgs<double>&, const K2Extra<double>&, int, bool, hipStream_t);
 #else
-#error "compile with -DLBM_COL_T=double or float and -DLBM_AR_BASE=0, 2 or 4 (a collision model's Arith base), or with -DLBM_COL_TALL=1 or 0"
+#error "compile with -DLBM_COL_T=double or float and -DLBM_AR_BASE=0, 2 or 4 (a collision model's Arith base), with -DLBM_COL_TALL=1 or 0, or with -DLBM_COL_PARK=<base>"
 #endif
 #undef LBM_KC
 

@@ -22,8 +22,11 @@ constexpr int col_waves(int esize, bool strict, bool tall = false) {
 // 4096x1024 262 against 260; a 16384x512 strip 259 against 246-260. The first tall shape of the round, 8 waves x 8 rows = 64 x 64
 // (121-127 VGPRs, 12 B of scratch), read 310 at 16384x4096 and lost elsewhere (216 at 4096x1024, 209 on the strip): replaced.
 constexpr int col_rows_per_thread(int esize, bool strict, bool tall = false) {
-    return tall && esize == 4 ? (strict ? 6 : 4) : (esize == 8 && strict) ? 2 : 4;
+    return tall && esize == 4 ? (strict ? 6 : 4) : (tall && esize == 8 && !strict) ? 5 : (esize == 8 && strict) ? 2 : 4;
 }
+// TALL, fp64 contracted: a 64 x 40 region — 8 waves x 5 rows, the top row of every thread parked in LDS between levels
+// (lbm_kernel_col.hpp "Parked top row": 120-124 VGPRs, no scratch, 76 352 B of LDS per block = two blocks per CU). At seven iterations
+// it stores 52 x 28 of its 64 x 40 cells. Whole domains only; strict arithmetic keeps 12 waves x 2 rows.
 // output tile of a launch of `depth` iterations
 constexpr int col_tile_w(int depth) { return 64 - 2 * (depth - 1); }
 constexpr int col_tile_h(int depth, int rows_per_thread, int waves) { return rows_per_thread * waves - 2 * (depth - 1); }
@@ -41,5 +44,9 @@ void launch_col(const KArgs<T>& a, const K2Extra<T>& e, int depth, bool nt, bool
 // arithmetic mode, BGK only (lbm_col.hip -DLBM_COL_TALL=1 contracted / 0 strict: eight unrolled rows x up to eight levels compile slowly)
 void launch_col_tall_contracted(const KArgs<float>& a, const K2Extra<float>& e, int depth, hipStream_t s);
 void launch_col_tall_strict(const KArgs<float>& a, const K2Extra<float>& e, int depth, hipStream_t s);
+// ... and on the tall fp64 regions (64 x 40, contracted arithmetic of one collision model), depth 5, 6 or 7, non-temporal stores at
+// five and six; one object file per model (lbm_col.hip -DLBM_COL_PARK=<base>)
+template <int ARB>
+void launch_col_park(const KArgs<double>& a, const K2Extra<double>& e, int depth, bool nt, hipStream_t s);
 
 }  // namespace lbmk

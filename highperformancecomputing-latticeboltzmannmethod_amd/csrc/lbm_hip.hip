@@ -406,7 +406,8 @@ namespace {
 // the tall fp32 regions (deep 8) exist for the models whose row says so
 int refuse_tall(int collision, int deep) {
     const CollisionModel& m = collision_model(collision);
-    if (deep_is_tall(deep) && !m.tall) return fail(LBM_ERR_ARG, "deep 8 (64x48 regions in registers) has no %s kernel", m.noun);
+    if (deep == 8 && !m.tall) return fail(LBM_ERR_ARG, "deep 8 (64x48 regions in registers) has no %s kernel", m.noun);
+    if (deep_is_park(deep) && !m.park) return fail(LBM_ERR_ARG, "deep %d (64x40 regions in registers) has no %s kernel", deep, m.noun);
     return LBM_OK;
 }
 // What the setters of the collision models share once the value is accepted. value > 0: the model `base` with that parameter, unless
@@ -427,6 +428,9 @@ int lbm_initialise(lbm_ctx* c, int* solid_count_out) {
     if (!c) return fail(LBM_ERR_ARG, "null context");
     lbm_trace("initialise", "ctx %p %dx%d rows %d..%d begin", (void*)c, c->nx, c->p.ny, c->p.y_start, c->p.y_start + c->nyl);
     if (int rc = refuse_tall(c->collision, c->deep)) return rc;
+    // (the arithmetic and the strip options may follow `deep`: looked at here)
+    if (deep_is_park(c->deep) && (c->arith != AR_CONTRACTED || (c->comm && c->nranks > 1) || c->group_n > 1 || c->loopback || c->nyl != c->p.ny))
+        return fail(LBM_ERR_ARG, "deep %d (64x40 regions in registers) exists for contracted arithmetic on whole domains only", c->deep);
     HIPCHK(hipSetDevice(c->device));
     if (c->has_sched()) { if (int rc = prepare_schedule(c)) return rc; }
     { int wr = wait_stream(c, c->stream, "compute stream (lbm_initialise)"); if (wr) return wr; }        // (re-)initialisation starts from quiet streams
@@ -1193,9 +1197,11 @@ int lbm_set_option(lbm_ctx* c, const char* key, long value) {
     else if (k == "ntl") c->use_ntl = (int)value ? 1 : 0;
     else if (k == "fuse") { if (value < 1 || value > 4) return fail(LBM_ERR_ARG, "fuse must be 1, 2, 3 or 4 (4: tile kernel, no strip faces)"); c->fuse = (int)value; c->deep = 0; }
     else if (k == "deep") {     // k_stepd_tile: 1: 6 iterations on 64x16 tiles, 2: 7 on 64x16, 3: 8 on 32x32 (1024 threads);
-                                // k_stepc_col (registers): 6 / 7 / 9: 5 / 6 / 7 iterations on 64x32 regions; 8 (fp32): 7 iterations on 64x48 regions.
-        if (!deep_valid((int)value)) return fail(LBM_ERR_ARG, "deep must be 0..3 or 6..9 (4 / 5, round 2's 32x16 LDS tiles, are retired)");
-        if (deep_is_tall((int)value) && c->esize != 4) return fail(LBM_ERR_ARG, "deep 8 (64x48 regions in registers, twelve waves x four rows) exists in fp32 only");
+                                // k_stepc_col (registers): 6 / 7 / 9: 5 / 6 / 7 iterations on 64x32 regions; 8 (fp32): 7 iterations on 64x48 regions;
+                                // 10 / 11 (fp64 contracted, whole domains): 6 / 7 iterations on 64x40 regions.
+        if (!deep_valid((int)value)) return fail(LBM_ERR_ARG, "deep must be 0..3 or 6..11 (4 / 5, round 2's 32x16 LDS tiles, are retired)");
+        if (deep_is_park((int)value) && c->esize != 8) return fail(LBM_ERR_ARG, "deep 10 / 11 (64x40 regions in registers, eight waves x five rows) exist in fp64 only");
+        if (value == 8 && c->esize != 4) return fail(LBM_ERR_ARG, "deep 8 (64x48 regions in registers, twelve waves x four rows) exists in fp32 only");
         if (int rc = refuse_tall(c->collision, (int)value)) return rc;
         c->deep = (int)value;
         if (c->deep) c->fuse = deep_depth(c->deep);
@@ -1329,6 +1335,7 @@ int lbm_debug_plan_candidates(int nx, int ny, int precision, int arith, int num_
     PlanQuery q;
     q.nx = nx; q.nyl = ny; q.ny_glob = ny; q.esize = precision == LBM_PRECISION_F32 ? 4 : 8; q.num_cus = num_cus > 0 ? num_cus : 256;
     q.no_tall = !collision_model(arith).tall;
+    q.park = (arith & 1) && collision_model(arith).park;
     const Plan none{};
     std::string text;
     for (const Plan& pl : plan_candidates(q, none)) {

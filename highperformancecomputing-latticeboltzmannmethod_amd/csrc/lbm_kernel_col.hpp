@@ -22,6 +22,28 @@
 // kernel => bit-identical results (tests).
 // Redundant collisions: x 64/56, y (H + .. + H-8)/(5 (H-8)) at D = 5: 1.33x at H = 32. HBM traffic per update at D = 5,
 // H = 32: (2048 + 1344) * 72 B / (1344 * 5) = 36 B before L2 absorbs the overlap, like the 32x16 LDS tile.
+//
+// Parked top row (PARK: fp64 with R = 5, a 64x40 region on eight waves). Five fp64 rows are 90 state registers, one row more than 128
+// VGPRs hold beside a collision (unparked: 128 VGPRs, 19 spilled). Rows 0..R-2 stay in registers; row R-1 lives in LDS between levels:
+//   pbuf[w][0..5]        populations 0, 1, 3, 4, 7, 8 of wave w's top row (pad columns as in xbuf; one buffer; only wave w touches it)
+//   xbuf[.][w][0..2]     its north-going 2, 5, 6, which only the wave above needs: the owner's pull takes 2, 5, 6 from row R-2
+//   level 1              loads all rows, updates the top row first and parks it: pbuf, and xbuf[0], which level 2 reads
+//   level L, before the barrier   writes only the bottom row's 4, 7, 8 into xbuf[L&1]
+//   level L, row R-2     takes 4, 7, 8 from pbuf at lane 0, +1, -1 (no DPP)
+//   level L, row R-1     takes 0, 1, 3 from pbuf at lane 0, -1, +1; 2, 5, 6 from row R-2 and 4, 7, 8 from the wave above, as every form does;
+//                        its new values go to pbuf and xbuf[(L+1)&1] (L < D) or to the lattice (L = D)
+// Order inside pbuf: the LDS operations of one wave execute in program order, the reads of a level stand in front of its writes (the
+// writes depend on them through the collision), and the barrier of level L+1 stands between the writes of level L and the next reads.
+// Reuse of xbuf: xbuf[(L+1)&1] was last read during level L-1 (three reads behind barrier L-1, three in front of that level's last
+// row); a wave that writes it during level L has passed barrier L, so every wave has finished level L-1. One barrier per level stays.
+// Skipped top rows. A row outside the level's window is not updated and so writes nothing: xbuf[(L+1)&1][w][0..2] then holds what level
+// L-2 or level 1 left there. The only reader is row ry+1 of the wave above at level L+1. If row ry was updated at level L-1 but not at L
+// (ry = L-2 or ry = H-L+1), its values of level L-1 stand in xbuf[L&1], written then, and level L reads exactly those. If it was not
+// updated at level L-1 either (ry < L-2 or ry > H-L+1), the reader is outside its own window (ry+1 < L-1 or ry+1 > H-L): garbage reads
+// garbage, as in the unparked form, where the stale registers are rewritten into xbuf at every level.
+// Ghost rows (general path): a top row outside the domain takes its ghost values at level 1, is skipped at levels 2..D and is read at
+// every one of them, from both parities of xbuf: level 1 writes its three into both. pbuf keeps its other six untouched.
+// A lane that reads a pad column of pbuf (lane 0 at x-1, lane 63 at x+1) is outside every window from level 2 on, as for xbuf.
 #pragma once
 #include "lbm_kernels.hpp"
 
@@ -84,6 +106,14 @@ __global__ void __launch_bounds__(NW * 64, (col_min_waves<T, NW, AR>())) k_stepc
     // that are garbage anyway: round 4 dropped the two phantom slots, 63 -> 51 KB at 8 fp64 waves, so that 12 waves fit two
     // blocks per CU); one pad column on each side for the diagonal reads at lane -/+ 1
     __shared__ T xbuf[2][NW][6][LW];
+    // the parked form (header: "Parked top row"): per wave, populations 0, 1, 3, 4, 7, 8 of its top row; pad columns as in xbuf
+    constexpr bool PARK = sizeof(T) == 8 && R == 5;
+    // the rows of a level in front of which the parked row's reads are issued: row R-2's three and row R-1's three. Two rows ahead where the
+    // registers allow it (BGK 120 VGPRs, TRT 124); the Smagorinsky collision holds more live values, and with all six reads in front of row
+    // R-3 its kernels take 128 VGPRs and spill four: row R-1's three wait one row longer there (126 VGPRs, no scratch)
+    constexpr bool PARK_LATE = AR == AR_STRICT_LES || AR == AR_CONTRACTED_LES;
+    constexpr int PARK_AT = R >= 3 ? R - 3 : 0, PARK_AT1 = R >= 3 ? (PARK_LATE ? R - 2 : R - 3) : 0;
+    __shared__ T pbuf[PARK ? NW : 1][6][LW];
     __shared__ T u_sh[NW][R];                              // (general tiles with column 0) the inlet velocity of every wave's rows
     const int lane = (int)threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
@@ -104,6 +134,15 @@ __global__ void __launch_bounds__(NW * 64, (col_min_waves<T, NW, AR>())) k_stepc
     auto run = [&]<bool LEAN>() {
         T g[R][Q];
         bool bad = false;
+        // (parked form) the top row's new values of level L: six parked, the north-going three into the exchange buffer that level L + 1
+        // reads (last read during level L - 1, and this wave has passed barrier L: every wave has finished level L - 1)
+        auto park = [&](const T (&f)[Q], int par) {
+            pbuf[w][0][1 + lane] = f[0]; pbuf[w][1][1 + lane] = f[1]; pbuf[w][2][1 + lane] = f[3];
+            pbuf[w][3][1 + lane] = f[4]; pbuf[w][4][1 + lane] = f[7]; pbuf[w][5][1 + lane] = f[8];
+            xbuf[par][w][0][1 + lane] = f[2]; xbuf[par][w][1][1 + lane] = f[5]; xbuf[par][w][2][1 + lane] = f[6];
+        };
+        // level 1 of the parked form takes the top row first and parks it: the other rows' collisions then run over R - 1 rows of state
+        auto first_top = [](int jj) { return PARK ? (jj == 0 ? R - 1 : jj - 1) : jj; };
         const bool col_in = (x >= 0 && x < a.nx);
         // bit j: the thread's cell of row j is solid. The thread <-> cell map is fixed for all D levels, so the geometry is looked
         // up once, here, and serves every level and the store predicate (block-uniform branch: only tiles near a solid cell)
@@ -154,13 +193,15 @@ __global__ void __launch_bounds__(NW * 64, (col_min_waves<T, NW, AR>())) k_stepc
             const unsigned ub = fr.src_off(a, Yr + ry0, X0), voff = (unsigned)lane * (unsigned)sizeof(T);   // wave-uniform, lane
             auto load_all = [&]<int AUX>() {
 #pragma unroll
-                for (int j = 0; j < R; ++j) fr.template load<AUX>(g[j], voff, ub + (unsigned)j * fr.pitchB);
+                for (int jj = 0; jj < R; ++jj) { const int j = first_top(jj); fr.template load<AUX>(g[j], voff, ub + (unsigned)j * fr.pitchB); }
             };
             if (e.ntl) load_all.template operator()<2>(); else load_all.template operator()<0>();      // (block-uniform)
 #pragma unroll
-            for (int j = 0; j < R; ++j) {
+            for (int jj = 0; jj < R; ++jj) {
+                const int j = first_top(jj);
                 bad |= any_unstable(g[j]);
                 collide<T, AR>(g[j], a);
+                if constexpr (PARK) if (jj == 0) park(g[j], 0);
             }
         } else {
             // rows outside the domain, or beyond what the band's outputs need (wave-uniform): outside_value. The nine constants come by
@@ -202,13 +243,17 @@ __global__ void __launch_bounds__(NW * 64, (col_min_waves<T, NW, AR>())) k_stepc
             // ... then the updates. A lane without a column computes on zeros, is not counted and takes its zeros back: a select, no
             // branch (a block-uniform flag around it, for the tiles that have such lanes, cost scalar spills in the fp64 TRT kernels)
 #pragma unroll
-            for (int j = 0; j < R; ++j) {
+            for (int jj = 0; jj < R; ++jj) {
+                const int j = first_top(jj);
                 const int yg = a.y_start + Yr + ry0 + j;
                 if ((rld >> j) & 1u) {
                     cell_update_with<T, AR, true>(a, g[j], x, yg, 0, (sbits >> j) & 1u, fr.near_solid, col_in, bad, [&]() { return u_sh[w][j]; });
 #pragma unroll
                     for (int i = 0; i < Q; ++i) g[j][i] = col_in ? g[j][i] : T(0);
                 }
+                // (parked form) loaded or ghost, the row is parked; a ghost row is never written again, so its north-going three go into
+                // both exchange buffers
+                if constexpr (PARK) if (jj == 0) { park(g[j], 0); park(g[j], 1); }
             }
         }
         if (bad) atomicMin(a.unstable_t, *a.t_base + a.t);
@@ -217,25 +262,32 @@ __global__ void __launch_bounds__(NW * 64, (col_min_waves<T, NW, AR>())) k_stepc
         auto level = [&]<int L>() {
             T (*xb)[6][LW] = xbuf[L & 1];
             const int wb = w > 0 ? w - 1 : 0, wa = w + 1 < NW ? w + 1 : NW - 1;
-            xb[w][0][1 + lane] = g[R - 1][2]; xb[w][1][1 + lane] = g[R - 1][5]; xb[w][2][1 + lane] = g[R - 1][6];
+            if constexpr (!PARK) { xb[w][0][1 + lane] = g[R - 1][2]; xb[w][1][1 + lane] = g[R - 1][5]; xb[w][2][1 + lane] = g[R - 1][6]; }
             xb[w][3][1 + lane] = g[0][4];     xb[w][4][1 + lane] = g[0][7];     xb[w][5][1 + lane] = g[0][8];
             __syncthreads();
             // from the wave below (its top row): f2 at x, f5 at x-1, f6 at x+1; from the wave above (its bottom row): f4, f7 at x+1, f8 at x-1
             T p2 = xb[wb][0][1 + lane], p5 = xb[wb][1][lane], p6 = xb[wb][2][2 + lane];
             bool badl = false;
             const bool lane_ok = lane >= L - 1 && lane <= 64 - L;
+            T q[6];                                                     // (parked form) the parked row as its two readers pull it
 #pragma unroll
             for (int j = 0; j < R; ++j) {
                 const int ry = ry0 + j;
+                if constexpr (PARK) {
+                    if (j == PARK_AT) { q[3] = pbuf[w][3][1 + lane]; q[4] = pbuf[w][4][2 + lane]; q[5] = pbuf[w][5][lane]; }     // row R-2: f4, f7 from x+1, f8 from x-1
+                    if (j == PARK_AT1) { q[0] = pbuf[w][0][1 + lane]; q[1] = pbuf[w][1][lane]; q[2] = pbuf[w][2][2 + lane]; }    // row R-1: f0, f1 from x-1, f3 from x+1
+                }
                 const T n2 = g[j][2], n5 = g[j][5], n6 = g[j][6];       // this row's north-going values, for row j+1
                 const int y = Yr + ry, yg = a.y_start + y;
                 // (wave-uniform) rows outside the level's window hold garbage from here on; a row outside the domain keeps the ghost
                 // values that level 1 gave it
                 if (ry >= L - 1 && ry <= H - L && (LEAN || ((rin >> j) & 1u))) {
                 T f[Q];
-                f[0] = g[j][0]; f[1] = from_left(g[j][1]); f[3] = from_right(g[j][3]);
+                if (PARK && j == R - 1) { f[0] = q[0]; f[1] = q[1]; f[3] = q[2]; }
+                else { f[0] = g[j][0]; f[1] = from_left(g[j][1]); f[3] = from_right(g[j][3]); }
                 f[2] = p2; f[5] = p5; f[6] = p6;
-                if (j < R - 1) { f[4] = g[j + 1][4]; f[7] = from_right(g[j + 1][7]); f[8] = from_left(g[j + 1][8]); }
+                if (PARK && j == R - 2) { f[4] = q[3]; f[7] = q[4]; f[8] = q[5]; }
+                else if (j < R - 1) { f[4] = g[j + 1][4]; f[7] = from_right(g[j + 1][7]); f[8] = from_left(g[j + 1][8]); }
                 else { f[4] = xb[wa][3][1 + lane]; f[7] = xb[wa][4][2 + lane]; f[8] = xb[wa][5][lane]; }   // (read here, not after the barrier: six registers fewer are live across the rows below; the buffer is not rewritten before this wave has passed the next barrier)
                 const bool valid = lane_ok;
                 bool store = L == D && lane >= HW && lane < 64 - HW && ry >= HW && ry < H - HW;
@@ -251,8 +303,11 @@ __global__ void __launch_bounds__(NW * 64, (col_min_waves<T, NW, AR>())) k_stepc
                     store = store && col_in && y < y_end && !((sbits >> j) & 1u);
                 }
                 if (L < D) {
+                    if (PARK && j == R - 1) park(f, (L + 1) & 1);
+                    else {
 #pragma unroll
                     for (int i = 0; i < Q; ++i) g[j][i] = f[i];
+                    }
                 } else if (store) {
                     if (LEAN) fr.template store<NT>(f, (unsigned)lane * (unsigned)sizeof(T), fr.dst_off(a, y, X0));
                     else store_cell<NT>(a, f, x, y);

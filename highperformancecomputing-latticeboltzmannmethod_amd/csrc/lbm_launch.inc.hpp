@@ -102,7 +102,8 @@ void launch_rows(const lbm_ctx* c, const KArgs<T>& a, hipStream_t s) {
 // a plan of either uses both depths, and on a context without strip faces seven iterations too, for what a segment leaves
 // over (20 = 7 + 7 + 6; at 4096x1024 fp64 seven iterations run at 160.6 GLUPS against 161.7 for six — eight, 154.3, are
 // not built); 9: the same family with seven iterations as the plan's depth (8192x2048 fp64: 175.9 against 169.9); 8: fp32 only, the same kernel on TALL 64 x 48 regions (twelve waves x four rows) with seven iterations, six / eight for
-// what a segment leaves over. Ids 4 / 5 were round 2's 32x16 LDS tiles: retired.
+// what a segment leaves over; 10 / 11: fp64 contracted on whole domains only, the same kernel on TALL 64 x 40 regions (eight waves x five rows, the fifth
+// parked in LDS) with six / seven iterations, five to seven for what a segment leaves over. Ids 4 / 5 were round 2's 32x16 LDS tiles: retired.
 // rows of one band of tiles of a launch of `depth` iterations (the edge bands of a strip are one band each)
 inline int deep_rows(const lbm_ctx* c, int id, int depth) {
     if (deep_is_col(id)) return col_tile_h(depth, (int)c->esize, c->arith == 0, deep_is_tall(id));
@@ -123,6 +124,14 @@ void launch_fused_rows(const lbm_ctx* c, const KArgs<T>& a, int depth, hipStream
         if constexpr (sizeof(T) == 4) {
             if (deep_is_tall(shape)) {
                 if (fast) launch_col_tall_contracted(a, e, depth, s); else launch_col_tall_strict(a, e, depth, s);
+                return;
+            }
+        }
+        if constexpr (sizeof(T) == 8) {
+            if (deep_is_park(shape)) {        // (contracted arithmetic of a model that has them: refuse_tall)
+                with_collision_base(c->collision, [&](auto arb) {
+                    if constexpr (collision_model(arb()).park) launch_col_park<arb()>(a, e, depth, c->use_nt != 0, s);
+                });
                 return;
             }
         }

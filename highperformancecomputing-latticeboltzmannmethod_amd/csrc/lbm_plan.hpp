@@ -16,16 +16,18 @@ namespace lbmk {
 // ty: tile height of the two- / three-iteration tile kernels (8 or 12); xcd: XCD-aware tile walk; deep: 0, or the deep shape
 // (1..3: k_stepd_tile six / seven / eight iterations; 6 / 7: k_stepc_col five / six iterations in registers on 64x32 regions;
 // 9: the same kernel with SEVEN iterations as the plan's depth — the largest grids; 8: fp32 only, k_stepc_col seven iterations
-// on TALL 64x48 regions — lbm_col_api.hpp); ntl: the register kernel's level-1 loads
+// on TALL 64x48 regions — lbm_col_api.hpp; 10 / 11: fp64 contracted only, whole domains only, k_stepc_col six / seven iterations on
+// TALL 64x40 regions, the top row of every thread parked in LDS); ntl: the register kernel's level-1 loads
 // are non-temporal
 struct Plan { int layout, nt, alternate, fuse, ty, xcd; std::string name; int deep = 0; int ntl = 0; };
 
-inline bool deep_is_col(int id) { return id >= 6 && id <= 9; }
-inline bool deep_is_tall(int id) { return id == 8; }
+inline bool deep_is_col(int id) { return id >= 6 && id <= 11; }
+inline bool deep_is_park(int id) { return id == 10 || id == 11; }         // the tall fp64 regions (64x40)
+inline bool deep_is_tall(int id) { return id == 8 || deep_is_park(id); }  // (8: the tall fp32 regions, 64x48)
 inline bool deep_valid(int id) { return id == 0 || (id >= 1 && id <= 3) || deep_is_col(id); }
 inline int deep_depth(int id) {
-    static const int d[10] = {0, 6, 7, 8, 0, 0, 5, 6, 7, 7};
-    return id >= 0 && id <= 9 ? d[id] : 0;
+    static const int d[12] = {0, 6, 7, 8, 0, 0, 5, 6, 7, 7, 6, 7};
+    return id >= 0 && id <= 11 ? d[id] : 0;
 }
 inline const char* deep_tile(int id) {
     static const char* t[4] = {"", "64,16", "64,16", "32,32"};
@@ -34,14 +36,17 @@ inline const char* deep_tile(int id) {
 
 // The collision models, one row each: everything the host knows about a model beyond its C-ABI setter. `base` is the model's strict
 // Arith value (lbm_kernels.hpp; base | 1: its contracted one) and what lbm_ctx::collision holds; `noun` names it in messages;
-// `tall`: the tall fp32 regions (deep 8) are instantiated for it; `ckpt_bit`: the LBMCKPT3 flag that announces its parameter (0: none —
+// `tall`: the tall fp32 regions (deep 8) are instantiated for it; `park`: so are the tall fp64 ones (deep 10 / 11); `ckpt_bit`: the LBMCKPT3 flag that announces its parameter (0: none —
 // rows in ascending order of this bit, the order the parameters stand in the file); the last three are the words checkpoints and
 // setters use for the parameter, its value and a context without it.
-struct CollisionModel { int base; const char* noun; bool tall; unsigned long long ckpt_bit; const char *param, *value, *none; };
+// the models whose contracted kernels on the tall fp64 regions keep four waves per SIMD without scratch: BGK 120 VGPRs, TRT 124,
+// Smagorinsky 126 with three of the parked row's reads issued a row later (profiles/col_parked/README.md; build.py PARK_BASES)
+constexpr bool PARK_LES = true, PARK_TRT = true;
+struct CollisionModel { int base; const char* noun; bool tall, park; unsigned long long ckpt_bit; const char *param, *value, *none; };
 constexpr CollisionModel collision_models[] = {
-    {AR_STRICT, "BGK", true, 0, "", "", ""},
-    {AR_STRICT_LES, "Smagorinsky (LES)", false, 4, "Smagorinsky constant", "Cs = ", " (BGK)"},
-    {AR_STRICT_TRT, "two-relaxation-time (TRT)", false, 8, "TRT magic parameter", "", ""},
+    {AR_STRICT, "BGK", true, true, 0, "", "", ""},
+    {AR_STRICT_LES, "Smagorinsky (LES)", false, PARK_LES, 4, "Smagorinsky constant", "Cs = ", " (BGK)"},
+    {AR_STRICT_TRT, "two-relaxation-time (TRT)", false, PARK_TRT, 8, "TRT magic parameter", "", ""},
 };
 // the row of an Arith value, strict or contracted
 constexpr const CollisionModel& collision_model(int arith) {
@@ -59,6 +64,7 @@ struct PlanQuery {
     bool faces = false;                 // ... and at least one of them is an internal face
     bool tune = true, can_tune = true;  // option "tune"; the grid is neither too small nor too large to measure
     bool no_tall = false;               // the collision model has no tall fp32 regions (collision_models: no such instantiation of them)
+    bool park = false;                  // contracted arithmetic of a model that has the tall fp64 regions (collision_models)
 };
 
 // The strip rule: 0: three iterations on 64x12 LDS tiles in pairs between exchanges; 1: six iterations on 64x16 LDS tiles of
@@ -124,6 +130,19 @@ inline std::vector<Plan> plan_candidates(const PlanQuery& q, const Plan& fixed) 
         cand.push_back({1, 0, 0, 7, 12, 1, "row-interleaved/7-step 64x48 in registers/xcd", 8});
         cand.push_back({1, 0, 1, 7, 12, 1, "row-interleaved/7-step 64x48 in registers/alternate/xcd", 8});
     }
+    // (fp64 contracted: 64x40 regions, the fifth row parked in LDS. tools/colbench, 4096x1024: seven iterations with non-temporal loads
+    // 24.8 us per iteration against 26.0 for the best 64x32 form; six iterations LOSE there, 26.2-27.5 against 26.0, a launch being 5.2
+    // rounds of blocks — they are measured because "split" hides a short last round; profiles/col_parked/README.md. Where a six-iteration
+    // launch on 64x32 regions is at least six rounds of blocks, two per CU.)
+    if (q.esize == 8 && q.park && (long)((q.nx + 53) / 54) * ((q.nyl + 21) / 22) >= 6L * 2 * q.num_cus) {
+        cand.push_back({1, 0, 1, 6, 12, 1, "row-interleaved/6-step 64x40 in registers/nt-load/alternate/xcd", 10, 1});
+        cand.push_back({1, 0, 0, 6, 12, 1, "row-interleaved/6-step 64x40 in registers/nt-load/xcd", 10, 1});
+        cand.push_back({1, 0, 1, 6, 12, 1, "row-interleaved/6-step 64x40 in registers/alternate/xcd", 10});
+        cand.push_back({1, 1, 0, 6, 12, 1, "row-interleaved/6-step 64x40 in registers/nt-store/xcd", 10});
+        cand.push_back({1, 0, 1, 7, 12, 1, "row-interleaved/7-step 64x40 in registers/alternate/xcd", 11});
+        cand.push_back({1, 0, 0, 7, 12, 1, "row-interleaved/7-step 64x40 in registers/nt-load/xcd", 11, 1});
+        cand.push_back({1, 0, 1, 7, 12, 1, "row-interleaved/7-step 64x40 in registers/nt-load/alternate/xcd", 11, 1});
+    }
     cand.push_back({1, 1, 0, 6, 12, 1, "row-interleaved/6-step 64x16/nt-store/xcd", 1});
     if (small_grid && !q.faces) {   // one round of LDS-filling tiles: a launch's load and store phases are paid once per 7-8 iterations
         cand.push_back({1, 1, 0, 7, 12, 1, "row-interleaved/7-step 64x16/nt-store/xcd", 2});
@@ -150,8 +169,8 @@ inline std::vector<Plan> plan_candidates(const PlanQuery& q, const Plan& fixed) 
 inline std::string plan_kernel_name(int fuse, int deep, int pair_ty, int nt, int arith, int esize) {
     char name[96];
     const char* t = esize == 4 ? "float" : "double";
-    const bool tall = deep_is_tall(deep) && esize == 4;      // (tall regions and seven-iteration launches: plain stores only)
-    const char* nts = nt && !tall && !(deep_is_col(deep) && deep_depth(deep) == 7) ? "true" : "false";
+    const bool tall = esize == 4 ? deep == 8 : deep_is_park(deep);      // (tall fp32 regions and seven-iteration launches: plain stores only)
+    const char* nts = nt && !(tall && esize == 4) && !(deep_is_col(deep) && deep_depth(deep) == 7) ? "true" : "false";
     if (fuse > 2 && deep_is_col(deep)) snprintf(name, sizeof(name), "k_stepc_col<%s,%d,%d,%d,%s,%d>", t, col_rows_per_thread(esize, (arith & 1) == 0, tall), col_waves(esize, (arith & 1) == 0, tall), deep_depth(deep), nts, arith);
     else if (fuse > 2 && deep) snprintf(name, sizeof(name), "k_stepd_tile<%s,%s,%d,%d>", t, deep_tile(deep), deep_depth(deep), arith);
     else if (fuse == 4) snprintf(name, sizeof(name), "k_step4_tile<%s,8,%d,%d>", t, esize == 8 ? 1024 : 512, arith);

@@ -71,6 +71,7 @@ int choose_plan(lbm_ctx* c) {
     q.nx = c->nx; q.nyl = c->nyl; q.ny_glob = c->p.ny; q.esize = (int)c->esize; q.num_cus = c->num_cus; q.nstrips = nstrips; q.strips = strips;
     q.tune = c->tune != 0; q.can_tune = can_tune; q.faces = face_south(c) || face_north(c);
     q.no_tall = !collision_model(c->collision).tall;
+    q.park = c->arith == AR_CONTRACTED && collision_model(c->collision).park && !strips && c->nyl == c->p.ny;
     const std::vector<Plan> cand = plan_candidates(q, fixed);
     free_buffers(c);                                // a second lbm_initialise starts from no population buffers
     // First round: every candidate once; the three fastest keep their allocations. Final round: those three again with
@@ -84,7 +85,9 @@ int choose_plan(lbm_ctx* c) {
     auto split_worth_trying = [&](const Plan& pl) {
         if (c->split_pinned || !deep_is_col(pl.deep)) return false;
         const int d = deep_depth(pl.deep), OW = col_tile_w(d), OH = deep_rows(c, pl.deep, d);
-        const long tiles = (long)((c->nx + OW - 1) / OW) * ((c->nyl + OH - 1) / OH);
+        // (a 64x40 region is a quarter more work than the 64x32 one the six rounds were counted in: a seven-iteration launch of them at
+        // 4096x1024 is 5.7 rounds of blocks and gains more from the ranges than any, 153.8 -> 165.0 GLUPS, profiles/col_parked/README.md)
+        const long tiles = (long)((c->nx + OW - 1) / OW) * ((c->nyl + OH - 1) / OH) * (deep_is_park(pl.deep) ? 5 : 4) / 4;
         int cut[5];
         c->split = 3;
         const bool ok = split_possible(c) && split_ranges(c, d, cut) && tiles >= 6L * 2 * c->num_cus;
