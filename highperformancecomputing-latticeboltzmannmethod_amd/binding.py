@@ -85,6 +85,8 @@ def lib():
         L.lbm_set_inlet_profile.argtypes = [vp, dp, C.c_int]
         L.lbm_set_smagorinsky.argtypes = [vp, C.c_double]
         L.lbm_set_trt.argtypes = [vp, C.c_double]
+        L.lbm_set_forcing.argtypes = [vp, C.c_double, C.c_double]
+        L.lbm_get_forcing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.lbm_set_wall.argtypes = [vp, C.c_int, C.c_int, C.c_double]
         L.lbm_get_wall.argtypes = [vp, C.c_int, C.POINTER(C.c_int), dp]
         L.lbm_debug_wall_rule.argtypes = [C.c_int, C.c_int, C.c_double, C.c_int, dp, dp]
@@ -416,12 +418,13 @@ class Context:
     kinds of the bottom and top walls (lbm_set_wall) in place of the two no-slip walls: "free-slip" (both), or a pair (south, north) whose
     entries are "no-slip", "free-slip" or ("moving", u_w) with the wall's tangential velocity u_w. inlet_schedule: optional table of
     scale factors of the inflow, one per iteration (lbm_set_inlet_schedule): a table holds its last entry for ever, a pair
-    (table, "repeat") is periodic (see cosine_ramp, sine_pulse)."""
+    (table, "repeat") is periodic (see cosine_ramp, sine_pulse). forcing: optional pair (fx, fy), a uniform driving force density in
+    lattice units on every fluid cell (lbm_set_forcing, Guo's scheme on BGK); (0, 0) / None: none; not with smagorinsky or trt_magic."""
 
     def __init__(self, nx, ny, tau=0.6, inlet_velocity=0.01333, cylinder_x=0.2, cylinder_y=0.5,
                  cylinder_radius=0.05, y_start=0, local_ny=0, precision="f64", device=0, force_log_capacity=0,
                  options=None, solid=None, inlet_profile=None, smagorinsky=None, bodies=None, frames=None, trt_magic=None,
-                 probes=None, probe_capacity=None, walls=None, inlet_schedule=None):
+                 probes=None, probe_capacity=None, walls=None, inlet_schedule=None, forcing=None):
         if solid is not None and bodies is not None:
             raise LbmError("solid= and bodies= exclude each other: the body labels are the geometry (solid where nonzero)")
         self.L = lib()
@@ -454,6 +457,8 @@ class Context:
                 self.set_wall(side, kind, u)
         if inlet_schedule is not None:
             self.set_inlet_schedule(*_schedule(inlet_schedule))
+        if forcing is not None:
+            self.set_forcing(*forcing)
 
     def _chk(self, rc):
         if rc < 0:
@@ -524,6 +529,16 @@ class Context:
     def set_trt(self, magic):
         """lbm_set_trt: the TRT magic parameter (tau - 1/2)(tau_minus - 1/2) in [0, 1] (0: plain BGK); before initialise()."""
         self._chk(self.L.lbm_set_trt(self.h, float(magic)))
+
+    def set_forcing(self, fx, fy):
+        """lbm_set_forcing: the uniform driving force density (fx, fy), each of magnitude below 1 ((0, 0): none); before initialise()."""
+        self._chk(self.L.lbm_set_forcing(self.h, float(fx), float(fy)))
+
+    def forcing(self):
+        """(fx, fy) as set (lbm_get_forcing); (0.0, 0.0) without a force."""
+        fx, fy = C.c_double(), C.c_double()
+        self._chk(self.L.lbm_get_forcing(self.h, C.byref(fx), C.byref(fy)))
+        return fx.value, fy.value
 
     def set_wall(self, side, kind, velocity=0.0):
         """lbm_set_wall: side "south" (row 0) / "north" (row ny - 1); kind "no-slip" / "free-slip" / "moving" with the wall's tangential
@@ -783,11 +798,12 @@ class Group:
     transport: "peer" (device copies / hipMemcpyPeerAsync) or "rccl" (ncclCommInitAll; distinct devices).
     solid: optional global (ny, nx) obstacle mask, inlet_profile: optional global [ny] inlet velocities, smagorinsky: optional LES
     constant Cs, trt_magic: optional TRT magic parameter, bodies: optional global (ny, nx) body numbers (in place of solid), frames: optional frame stride k, probes / probe_capacity: optional probe points (global coordinates), walls: optional kinds of the
-    bottom and top walls (as Context takes them), inlet_schedule: optional scale factors of the inflow per iteration (likewise); all given
-    to every member."""
+    bottom and top walls (as Context takes them), inlet_schedule: optional scale factors of the inflow per iteration (likewise), forcing:
+    optional driving force (fx, fy); all given to every member."""
 
     def __init__(self, nx, ny, bounds, devices=None, transport="peer", options=None, solid=None, inlet_profile=None, smagorinsky=None,
-                 bodies=None, frames=None, trt_magic=None, probes=None, probe_capacity=None, walls=None, inlet_schedule=None, **kw):
+                 bodies=None, frames=None, trt_magic=None, probes=None, probe_capacity=None, walls=None, inlet_schedule=None, forcing=None,
+                 **kw):
         from .strips import partition_rows
         if isinstance(bounds, int):
             bounds = partition_rows(ny, bounds)
@@ -795,7 +811,7 @@ class Group:
         self.nx, self.ny = nx, ny
         self.ctxs = [Context(nx, ny, y_start=y0, local_ny=n, device=d, options=options, solid=solid, inlet_profile=inlet_profile,
                              smagorinsky=smagorinsky, bodies=bodies, frames=frames, trt_magic=trt_magic, probes=probes,
-                             probe_capacity=probe_capacity, walls=walls, inlet_schedule=inlet_schedule, **kw)
+                             probe_capacity=probe_capacity, walls=walls, inlet_schedule=inlet_schedule, forcing=forcing, **kw)
                      for (y0, n), d in zip(bounds, devices)]
         self.L = lib()
         self._arr = (C.c_void_p * len(self.ctxs))(*[c.h for c in self.ctxs])

@@ -46,6 +46,10 @@ def embedded_id(path=LIB):
 COLLISION_BASES = (0, 2, 4)
 # ... and those whose row says `park`: the tall fp64 regions (64x40) are built for them
 PARK_BASES = (0, 2, 4)
+# BGK under a driving force (lbm_set_forcing), enumerated on its own and named to the sources by flags of its own (-DLBM_AR_FORCED_BASE,
+# -DLBM_COL_FORCED_PARK), which they map to the base: the same three kinds of unit as a base above, and the tall fp64 regions if its row says so
+FORCED_BASES = (8,)
+FORCED_PARK_BASES = (8,)
 
 
 def units(build_id):
@@ -62,6 +66,12 @@ def units(build_id):
             ("lbm_frames.hip", [], "lbm_frames.o"), ("lbm_probes.hip", [], "lbm_probes.o")]
     # the tall fp64 regions (64x40, contracted arithmetic), one object per model that has them
     out += [("lbm_col.hip", ["-DLBM_COL_PARK=%d" % base], "lbm_col_park_ar%d.o" % base) for base in PARK_BASES]
+    for base in FORCED_BASES:
+        ar = "-DLBM_AR_FORCED_BASE=%d" % base
+        out += [("lbm_col.hip", ["-DLBM_COL_T=double", ar], "lbm_col_ar%d_f64.o" % base),
+                ("lbm_col.hip", ["-DLBM_COL_T=float", ar], "lbm_col_ar%d_f32.o" % base),
+                ("lbm_step_k.hip", [ar], "lbm_step_k_ar%d.o" % base)]
+    out += [("lbm_col.hip", ["-DLBM_COL_FORCED_PARK=%d" % base], "lbm_col_park_ar%d.o" % base) for base in FORCED_PARK_BASES]
     return out
 
 

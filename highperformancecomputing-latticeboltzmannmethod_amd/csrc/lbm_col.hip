@@ -2,9 +2,16 @@
 // -DLBM_COL_T=<element type> -DLBM_AR_BASE=<a collision model's Arith base>: the ten instantiations of that type and model on 64 x 32
 // regions (five / six iterations x store policy + seven iterations, x arithmetic); -DLBM_COL_TALL=1 / 0: the three tall fp32 ones of
 // one arithmetic mode, BGK only; -DLBM_COL_PARK=<base>: the five of the tall fp64 regions (64 x 40, contracted) of one model. One object
-// each (build.py).
+// each (build.py). The forced model (base 8) is named by -DLBM_AR_FORCED_BASE=8 / -DLBM_COL_FORCED_PARK=8 instead.
 #include "lbm_kernel_col.hpp"
 #include "lbm_col_api.hpp"
+
+#if !defined(LBM_AR_BASE) && defined(LBM_AR_FORCED_BASE)    // the forced model's objects carry flags of their own (build.py FORCED_BASES)
+#define LBM_AR_BASE LBM_AR_FORCED_BASE
+#endif
+#if !defined(LBM_COL_PARK) && defined(LBM_COL_FORCED_PARK)
+#define LBM_COL_PARK LBM_COL_FORCED_PARK
+#endif
 
 namespace lbmk {
 

@@ -49,7 +49,7 @@ __global__ void __launch_bounds__(FRAME_THREADS) k_frame(const FrameArgs<T> p) {
         r = 0.0; vx = 0.0; vy = 0.0;
         if (!have) return;
         if (edge) { macro_cell<T>(a, x, y, r, vx, vy); return; }
-        macro_moments<T>(f, r, vx, vy);
+        macro_moments<T>(a, f, r, vx, vy);
         if (solid_at(a, x, a.y_start + y)) { r = 1.0; vx = 0.0; vy = 0.0; }
     };
 

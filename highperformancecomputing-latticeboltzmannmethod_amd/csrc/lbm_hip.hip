@@ -152,7 +152,7 @@ int prepare_schedule(lbm_ctx* c) {
 // ---- checkpoint / restart (the reference keeps its state in memory only) ------------------------
 // File: CkptHeader; in an "LBMCKPT3" file a 64-bit word of flags; the fields the flags announce, in the order of their bits (bit 0: the
 // obstacle mask's 64-bit digest, bit 1: the inlet profile's, then one double per collision model that has a parameter — ckpt_bit in
-// collision_models, lbm_plan.hpp: bit 2 Cs, bit 3 the TRT magic parameter — then bit 4: the two walls of lbm_set_wall as four doubles,
+// collision_models, lbm_plan.hpp: bit 2 Cs, bit 3 the TRT magic parameter (and, behind everything the lower bits carry, bit 6: the two doubles {fx, fy} of lbm_set_forcing) — then bit 4: the two walls of lbm_set_wall as four doubles,
 // south kind, south velocity, north kind, north velocity, written only where a wall is not no-slip — then bit 5: the 64-bit digest of the
 // inlet schedule of lbm_set_inlet_schedule, {mode, n, the n doubles}; the iteration counter positions the schedule after a restart); then the post-collision populations P_{steps_done} of the
 // strip's interior, [9][local_ny][nx] in the element type. The state is complete: ghost cells and solid cells are reconstructed by
@@ -167,16 +167,25 @@ struct CkptHeader {
     double tau, inlet_velocity, cylinder_x, cylinder_y, cylinder_radius;
 };
 
+// a model's parameter as messages print it: one number, or the pair of a model with two (collision_models: nparam)
+std::string param_text(const CollisionModel& m, double v, double v2, const char* fmt = "%g") {
+    char a[40], b[40];
+    snprintf(a, sizeof(a), fmt, v); snprintf(b, sizeof(b), fmt, v2);
+    return m.nparam == 2 ? std::string("(") + a + ", " + b + ")" : std::string(a);
+}
+
 // lbm_load_state: the collision parameters a file announces (param: one slot per row of collision_models) against the context's; the last
 // model first, the order mismatches have always been reported in
-int refuse_collision_mismatch(const lbm_ctx* c, const char* path, unsigned long long flags, const double* param) {
-    const double mine = c->collision_param;
+int refuse_collision_mismatch(const lbm_ctx* c, const char* path, unsigned long long flags, const double (*param)[2]) {
+    const double mine = c->collision_param, mine2 = c->collision_param2;
     for (int i = (int)std::size(collision_models) - 1; i >= 0; --i) {
         const CollisionModel& m = collision_models[i];
         const bool in_file = flags & m.ckpt_bit, here = m.ckpt_bit && c->collision == m.base;
-        if (!in_file && here) return fail(LBM_ERR_ARG, "checkpoint %s was written without a %s%s; this context has %s%g", path, m.param, m.none, m.value, mine);
-        if (in_file && !here) return fail(LBM_ERR_ARG, "checkpoint %s was written with %s %s%g; this context has none%s", path, m.param, m.value, param[i], m.none);
-        if (in_file && param[i] != mine) return fail(LBM_ERR_ARG, "checkpoint %s was written with %s %s%.17g; this context has %s%.17g", path, m.param, m.value, param[i], m.value, mine);
+        if (!in_file && here) return fail(LBM_ERR_ARG, "checkpoint %s was written without a %s%s; this context has %s%s", path, m.param, m.none, m.value, param_text(m, mine, mine2).c_str());
+        if (in_file && !here) return fail(LBM_ERR_ARG, "checkpoint %s was written with %s %s%s; this context has none%s", path, m.param, m.value, param_text(m, param[i][0], param[i][1]).c_str(), m.none);
+        if (in_file && (param[i][0] != mine || (m.nparam == 2 && param[i][1] != mine2)))
+            return fail(LBM_ERR_ARG, "checkpoint %s was written with %s %s%s; this context has %s%s", path, m.param, m.value, param_text(m, param[i][0], param[i][1], "%.17g").c_str(),
+                        m.value, param_text(m, mine, mine2, "%.17g").c_str());
     }
     return LBM_OK;
 }
@@ -410,16 +419,19 @@ int refuse_tall(int collision, int deep) {
     if (deep_is_park(deep) && !m.park) return fail(LBM_ERR_ARG, "deep %d (64x40 regions in registers) has no %s kernel", deep, m.noun);
     return LBM_OK;
 }
-// What the setters of the collision models share once the value is accepted. value > 0: the model `base` with that parameter, unless
+// What the setters of the collision models share once the value is accepted. A nonzero value (value2: the second one of a model with
+// two, the force's Fy): the model `base` with that parameter, unless
 // the context has another model (`what`: the caller's name and its word for the value) or, where the setter checks it (`tall_now`), is
-// pinned to tall regions the model lacks; 0: that model off, the BGK kernels.
-int set_collision(lbm_ctx* c, int base, double value, const char* what, bool tall_now) {
+// pinned to tall regions the model lacks; 0 (both): that model off, the BGK kernels.
+int set_collision(lbm_ctx* c, int base, double value, const char* what, bool tall_now, double value2 = 0.0) {
     const CollisionModel& cur = collision_model(c->collision);
-    if (value > 0.0 && c->collision != base && c->collision != AR_STRICT)
-        return fail(LBM_ERR_ARG, "%s %g on a context with %s %s%g (the two collisions cannot be combined)", what, value, cur.param, cur.value, c->collision_param);
-    if (value > 0.0 && tall_now) { if (int rc = refuse_tall(base, c->deep)) return rc; }
-    if (value > 0.0) { c->collision = base; c->collision_param = value; }
-    else if (c->collision == base) { c->collision = AR_STRICT; c->collision_param = 0.0; }
+    const bool on = value != 0.0 || value2 != 0.0;      // (Cs and the magic parameter are never negative: their setters refuse that)
+    if (on && c->collision != base && c->collision != AR_STRICT)
+        return fail(LBM_ERR_ARG, "%s %s on a context with %s %s%s (the two collisions cannot be combined)", what, param_text(collision_model(base), value, value2).c_str(),
+                    cur.param, cur.value, param_text(cur, c->collision_param, c->collision_param2).c_str());
+    if (on && tall_now) { if (int rc = refuse_tall(base, c->deep)) return rc; }
+    if (on) { c->collision = base; c->collision_param = value; c->collision_param2 = value2; }
+    else if (c->collision == base) { c->collision = AR_STRICT; c->collision_param = 0.0; c->collision_param2 = 0.0; }
     return LBM_OK;
 }
 }  // namespace
@@ -873,6 +885,22 @@ int lbm_set_trt(lbm_ctx* c, double magic) {
     return set_collision(c, AR_STRICT_TRT, magic, "lbm_set_trt: magic parameter", true);
 }
 
+int lbm_set_forcing(lbm_ctx* c, double fx, double fy) {
+    if (!c) return fail(LBM_ERR_ARG, "lbm_set_forcing: null context");
+    if (c->initialised) return fail(LBM_ERR_ARG, "lbm_set_forcing must be called before lbm_initialise");
+    if (!std::isfinite(fx) || !(std::fabs(fx) < 1.0)) return fail(LBM_ERR_ARG, "lbm_set_forcing: fx = %g (finite values of magnitude below 1 only)", fx);
+    if (!std::isfinite(fy) || !(std::fabs(fy) < 1.0)) return fail(LBM_ERR_ARG, "lbm_set_forcing: fy = %g (finite values of magnitude below 1 only)", fy);
+    return set_collision(c, AR_STRICT_FORCED, fx, "lbm_set_forcing: force", true, fy);
+}
+
+int lbm_get_forcing(const lbm_ctx* c, double* fx, double* fy) {
+    if (!c) return fail(LBM_ERR_ARG, "lbm_get_forcing: null context");
+    const bool on = c->collision == AR_STRICT_FORCED;
+    if (fx) *fx = on ? c->collision_param : 0.0;
+    if (fy) *fy = on ? c->collision_param2 : 0.0;
+    return LBM_OK;
+}
+
 int lbm_set_wall(lbm_ctx* c, int side, int kind, double velocity) {
     if (!c) return fail(LBM_ERR_ARG, "lbm_set_wall: null context");
     if (c->initialised) return fail(LBM_ERR_ARG, "lbm_set_wall must be called before lbm_initialise");
@@ -1109,12 +1137,15 @@ int lbm_save_state(lbm_ctx* c, const char* path) {
     }
     if (!rc && c->has_mask && fwrite(&c->hmask.digest, sizeof(c->hmask.digest), 1, fp) != 1) rc = fail(LBM_ERR_ARG, "short write");
     if (!rc && c->has_profile && fwrite(&c->prof_digest, sizeof(c->prof_digest), 1, fp) != 1) rc = fail(LBM_ERR_ARG, "short write");
-    if (!rc && cm.ckpt_bit && fwrite(&c->collision_param, sizeof(c->collision_param), 1, fp) != 1) rc = fail(LBM_ERR_ARG, "short write");
+    const double cparam[2] = {c->collision_param, c->collision_param2};
+    const bool cm_late = cm.ckpt_bit > CKPT_SCHED;      // (a model whose bit lies above the schedule's: behind everything the lower bits carry)
+    if (!rc && cm.ckpt_bit && !cm_late && fwrite(cparam, sizeof(double), (size_t)cm.nparam, fp) != (size_t)cm.nparam) rc = fail(LBM_ERR_ARG, "short write");
     if (!rc && c->has_walls()) {
         const double w[4] = {(double)c->wall_kind[0], c->wall_u[0], (double)c->wall_kind[1], c->wall_u[1]};
         if (fwrite(w, sizeof(w), 1, fp) != 1) rc = fail(LBM_ERR_ARG, "short write");
     }
     if (!rc && c->has_sched() && fwrite(&c->sched_digest, sizeof(c->sched_digest), 1, fp) != 1) rc = fail(LBM_ERR_ARG, "short write");
+    if (!rc && cm_late && fwrite(cparam, sizeof(double), (size_t)cm.nparam, fp) != (size_t)cm.nparam) rc = fail(LBM_ERR_ARG, "short write");
     if (!rc) rc = DISPATCH(c, do_save<double>(c, fp), do_save<float>(c, fp));
     fclose(fp);
     return rc;
@@ -1139,7 +1170,7 @@ int lbm_load_state(lbm_ctx* c, const char* path) {
     int rc = LBM_OK;
     unsigned long long digest = 0, flags = 0, pdigest = 0, sdigest = 0;
     constexpr int NM = (int)std::size(collision_models);
-    double param[NM] = {};             // the parameter of each model the file announces
+    double param[NM][2] = {};          // the parameter of each model the file announces
     double walls[4] = {0.0, 0.0, 0.0, 0.0};   // {south kind, south velocity, north kind, north velocity} of the file; none: no-slip
     unsigned long long known = 3 | CKPT_WALLS | CKPT_SCHED;
     for (const CollisionModel& m : collision_models) known |= m.ckpt_bit;
@@ -1148,9 +1179,17 @@ int lbm_load_state(lbm_ctx* c, const char* path) {
     const bool v2 = head && memcmp(h.magic, "LBMCKPT2", 8) == 0 && fread(&digest, sizeof(digest), 1, fp) == 1;
     bool v3 = head && memcmp(h.magic, "LBMCKPT3", 8) == 0 && fread(&flags, sizeof(flags), 1, fp) == 1 && (flags & ~known) == 0 &&
               (!(flags & 1) || fread(&digest, sizeof(digest), 1, fp) == 1) && (!(flags & 2) || fread(&pdigest, sizeof(pdigest), 1, fp) == 1);
-    for (int i = 0; i < NM; ++i) v3 = v3 && (!(flags & collision_models[i].ckpt_bit) || fread(&param[i], sizeof(double), 1, fp) == 1);
+    // (the parameters stand in the order of their bits: the models below the walls' bit, the walls, the schedule, then the models above)
+    auto read_params = [&](bool late) {
+        for (int i = 0; i < NM; ++i) {
+            const CollisionModel& m = collision_models[i];
+            if ((m.ckpt_bit > CKPT_SCHED) == late && (flags & m.ckpt_bit)) v3 = v3 && fread(param[i], sizeof(double), (size_t)m.nparam, fp) == (size_t)m.nparam;
+        }
+    };
+    read_params(false);
     v3 = v3 && (!(flags & CKPT_WALLS) || fread(walls, sizeof(walls), 1, fp) == 1);
     v3 = v3 && (!(flags & CKPT_SCHED) || fread(&sdigest, sizeof(sdigest), 1, fp) == 1);
+    read_params(true);
     const bool f_mask = v2 || (v3 && (flags & 1)), f_prof = v3 && (flags & 2), f_walls = v3 && (flags & CKPT_WALLS), f_sched = v3 && (flags & CKPT_SCHED);
     if (!v1 && !v2 && !v3) rc = fail(LBM_ERR_ARG, "%s is not a checkpoint", path);
     else if ((rc = refuse_collision_mismatch(c, path, v3 ? flags : 0, param))) {}
@@ -1329,7 +1368,8 @@ int lbm_debug_body_chunks(const unsigned char* labels, int nx, int ny, int y_sta
 }
 
 /* TEST HOOK (no device needed): the candidates lbm_initialise would time for a whole-domain context of this grid, one per line:
- * "name|lbm_set_option pairs|dominant kernel|iterations per launch". arith: 0 / 1, 2 / 3 for a Smagorinsky (LES) context, 4 / 5 for a TRT one. */
+ * "name|lbm_set_option pairs|dominant kernel|iterations per launch". arith: 0 / 1, 2 / 3 for a Smagorinsky (LES) context, 4 / 5 for a TRT one,
+ * 8 / 9 for one with a driving force (lbm_set_forcing). */
 int lbm_debug_plan_candidates(int nx, int ny, int precision, int arith, int num_cus, char* out, int cap) {
     if (!out || cap < 1 || nx < 1 || ny < 1) return fail(LBM_ERR_ARG, "bad argument");
     PlanQuery q;

@@ -111,6 +111,16 @@ inline WallK<T> wall_ks(int south, double u_south, int north, double u_north) {
 
 template <typename T>
 struct KArgs {
+    // The uniform driving force (lbm_set_forcing; Guo, Zheng and Shi 2002): g = (1 - 1/(2 tau)) F, the factor of the source term, and
+    // h = F/2, what the velocity of the equilibrium adds to the momentum, each formed on the host in double and cast once. Read only by
+    // the forced instantiations (AR_STRICT_FORCED / AR_CONTRACTED_FORCED): a slot of their own, four values where the union below has
+    // three. A block of exactly 64 bytes IN FRONT of everything else, not behind it like the additions below: the fused kernels' second
+    // argument block (K2Extra) follows this struct in the kernel-argument segment, and the compiler merges the scalar loads of adjacent
+    // fields across the two by their alignment, up to 64 bytes. Four values behind `sched` part the two blocks and 26 earlier
+    // instantiations came out with other scalar spills or vector register counts; with every field moved by 64 bytes, K2Extra's
+    // included, each of them keeps its loads and its register allocation (profiles/forcing/README.md).
+    T frc_gx, frc_gy, frc_hx, frc_hy;
+    char frc_pad[64 - 4 * sizeof(T)];
     const T* src;      // plane 0 of the buffer read  (P_t)
     T* dst;            // plane 0 of the buffer written (P_{t+1})
     long plane;        // elements per plane
@@ -299,10 +309,16 @@ __device__ __forceinline__ void bcs_at(const KArgs<T>& a, T (&f)[Q], int x, int 
 //   AR_STRICT_TRT / AR_CONTRACTED_TRT  the same two arithmetic modes with the two-relaxation-time operator (lbm_set_trt): the even
 //                 part of each opposite pair relaxes with 1/tau, the odd part with the launch-uniform second rate trt_wm. Separate
 //                 instantiations for the same reason. TRT and LES exclude each other: there are no values 6 and 7.
-enum Arith { AR_STRICT = 0, AR_CONTRACTED = 1, AR_STRICT_LES = 2, AR_CONTRACTED_LES = 3, AR_STRICT_TRT = 4, AR_CONTRACTED_TRT = 5 };
+//   AR_STRICT_FORCED / AR_CONTRACTED_FORCED  BGK under a uniform force density F (lbm_set_forcing), Guo's scheme: the equilibrium is
+//                 taken at u = (sum c f + F/2) / rho and the source S_i = (1 - 1/(2 tau)) w_i [3 (c_i - u) + 9 (c_i.u) c_i] . F is added
+//                 to the relaxed populations. Separate instantiations for the same reason. Forcing excludes LES and TRT: there are no
+//                 values 10 to 13.
+enum Arith { AR_STRICT = 0, AR_CONTRACTED = 1, AR_STRICT_LES = 2, AR_CONTRACTED_LES = 3, AR_STRICT_TRT = 4, AR_CONTRACTED_TRT = 5,
+             AR_STRICT_FORCED = 8, AR_CONTRACTED_FORCED = 9 };
 constexpr bool ar_contracted(int ar) { return (ar & 1) != 0; }
 constexpr bool ar_les(int ar) { return (ar & 2) != 0; }
 constexpr bool ar_trt(int ar) { return (ar & 4) != 0; }
+constexpr bool ar_forced(int ar) { return (ar & 8) != 0; }
 constexpr int ar_of(bool contracted, bool les, bool trt = false) { return (contracted ? 1 : 0) | (les ? 2 : 0) | (trt ? 4 : 0); }
 
 __device__ __forceinline__ double fma_t(double a, double b, double c) { return __builtin_fma(a, b, c); }
@@ -407,8 +423,9 @@ __device__ __forceinline__ T les_tau_inv_strict(const T (&f)[Q], T rho, T ux, T 
 // collision_step for one cell, LBMSolver.h:101-123 (moments i = 0..8 ascending from 0, N7). LES modes: tau_inv is ignored and the
 // relaxation rate of the cell comes from les_tau / les_tau2 / les_c (KArgs); BGK modes never read those three. TRT modes: tau_inv
 // relaxes the even part of each opposite pair (and the rest population), `les_tau` carries the rate of the odd part, wm = 1/tau_minus, and les_tau2 / les_c the folded rates (wp + wm)/2, (wp - wm)/2.
+// FORCED modes: tau_inv is BGK's, and the four values carry gx, gy, hx, hy (KArgs::frc_*): g = (1 - wp/2) F, h = F/2.
 template <typename T, int AR = AR_STRICT>
-__device__ __forceinline__ void bgk_collide(T (&f)[Q], T tau_inv, T les_tau = T(0), T les_tau2 = T(0), T les_c = T(0)) {
+__device__ __forceinline__ void bgk_collide(T (&f)[Q], T tau_inv, T les_tau = T(0), T les_tau2 = T(0), T les_c = T(0), T frc_hy = T(0)) {
     T rho = T(0), ux = T(0), uy = T(0);
     if constexpr (ar_contracted(AR)) {
         // moments as short trees over opposite pairs (depth 4 / 3 instead of chains of 9 / 6 dependent additions)
@@ -417,6 +434,7 @@ __device__ __forceinline__ void bgk_collide(T (&f)[Q], T tau_inv, T les_tau = T(
         rho = ((f[0] + a13) + (a24 + a57)) + a68;
         ux = (d13 + d57) - d68;
         uy = (d24 + d57) + d68;
+        if constexpr (ar_forced(AR)) { ux = ux + les_c; uy = uy + frc_hy; }      // Guo: the momenta take h = F/2, so v below is 3u of the forced velocity
         // v = 3u. 1 + 3cu + 4.5cu^2 - 1.5u^2 = base + cv*(1 + 0.5cv) with cv = c.v and base = 1 - v^2/6: the inner bracket
         // is one FMA with INLINE constants (0.5, 1.0). gfx950 VALU instructions take one SGPR/literal operand at most, so
         // fma(4.5, cu, 3.0) cost two v_mov per direction to build the 3.0 — 16 of ~100 vector instructions per cell.
@@ -468,6 +486,27 @@ __device__ __forceinline__ void bgk_collide(T (&f)[Q], T tau_inv, T les_tau = T(
             const T wr = i == 0 ? wr0 : (i < 5 ? wr1 : wr5);
             f[i] = fma_t(tau_inv, fma_t(wr, t, -f[i]), f[i]);     // f - (f - feq)/tau = f + (feq - f)/tau
         }
+        if constexpr (ar_forced(AR)) {
+            // Guo's source, added once BGK's chain above has finished. With cg = c_i.g and cv = c_i.v:
+            //     S_i = w_i (3 cg - 3 u.g + 9 (c_i.u) cg) = 3 w_i ((cg cv - u.g) + cg),   the opposite direction 3 w_i ((cg cv - u.g) - cg)
+            // so a pair shares m = cg cv - u.g, and gx, gy enter as scalar operands only (no uniform value is formed in a vector register).
+            // A phase of its own behind an empty asm statement that "rewrites" its inputs: base and the three w rho are dead by now and
+            // u.g is not yet alive, so the kernel holds no more values at once than BGK's does (folded into the relaxation, the
+            // register kernels of fp64 spilled: profiles/forcing/README.md).
+            const T gx = les_tau, gy = les_tau2;
+            T sx = vx, sy = vy;
+            asm volatile("" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]), "+v"(f[4]), "+v"(f[5]), "+v"(f[6]), "+v"(f[7]), "+v"(f[8]), "+v"(sx), "+v"(sy));
+            const T ug = fma_t(sx, gx, sy * gy) * T(1.0 / 3.0);      // u.g
+            f[0] = fma_t(T(-4.0 / 3.0), ug, f[0]);                  // S_0 = -3 w_0 u.g
+            auto source = [&](int i, int ib, T w3, T mi, T mb) {     // mi = m + cg, mb = m - cg; w3 = 3 w_i
+                f[i] = fma_t(w3, mi, f[i]);
+                f[ib] = fma_t(w3, mb, f[ib]);
+            };
+            {   const T m = fma_t(gx, sx, -ug); source(1, 3, T(1.0 / 3.0), m + gx, m - gx); }
+            {   const T m = fma_t(gy, sy, -ug); source(2, 4, T(1.0 / 3.0), m + gy, m - gy); }
+            {   const T cv = sx + sy, m = fma_t(gx, cv, fma_t(gy, cv, -ug)); source(5, 7, T(1.0 / 12.0), (m + gx) + gy, (m - gx) - gy); }
+            {   const T cv = sx - sy, m = fma_t(gx, cv, fma_t(-gy, cv, -ug)); source(8, 6, T(1.0 / 12.0), (m + gx) - gy, (m - gx) + gy); }
+        }
         return;
     }
 #pragma unroll
@@ -476,6 +515,7 @@ __device__ __forceinline__ void bgk_collide(T (&f)[Q], T tau_inv, T les_tau = T(
         if (cx(i) != 0) ux += T(cx(i)) * f[i];
         if (cy(i) != 0) uy += T(cy(i)) * f[i];
     }
+    if constexpr (ar_forced(AR)) { ux = ux + les_c; uy = uy + frc_hy; }      // Guo: the momenta take h = F/2 before the divisions
     strict_div2(ux, uy, rho);
     if constexpr (ar_les(AR)) tau_inv = les_tau_inv_strict(f, rho, ux, uy, les_tau, les_tau2, les_c);
     const T usq = ux * ux + uy * uy;
@@ -515,6 +555,24 @@ __device__ __forceinline__ void bgk_collide(T (&f)[Q], T tau_inv, T les_tau = T(
     pair(2, 4, uy, wr1);              // c2 = (0,1),  c4 = (0,-1)
     pair(5, 7, ux + uy, wr5);         // c5 = (1,1),  c7 = (-1,-1)
     pair(8, 6, ux - uy, wr5);         // c8 = (1,-1), c6 = (-1,1): 1*ux + (-1)*uy == ux - uy
+    if constexpr (ar_forced(AR)) {
+        // Guo's source (tests/forcing_reference.py guo_collide, operation by operation), added to BGK's relaxed populations:
+        //     S_i = w_i * ((3 cg - u3) + (9 cu) cg),  u3 = 3 (ux gx + uy gy),  cg = c_i.g; the opposite direction negates 3 cg and keeps the product.
+        // A phase of its own behind an empty asm statement, as in the contracted branch: what the relaxation held is dead by now.
+        const T gx = les_tau, gy = les_tau2;
+        asm volatile("" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]), "+v"(f[4]), "+v"(f[5]), "+v"(f[6]), "+v"(f[7]), "+v"(f[8]), "+v"(ux), "+v"(uy));
+        const T u3 = T(3.0) * (ux * gx + uy * gy);
+        f[0] = f[0] + wgt<T>(0) * (T(0.0) - u3);
+        auto source = [&](int i, int ib, T cu, T cg, T w) {
+            const T sa = T(3.0) * cg, sb = (T(9.0) * cu) * cg;
+            f[i] = f[i] + w * ((sa - u3) + sb);
+            f[ib] = f[ib] + w * (((-sa) - u3) + sb);
+        };
+        source(1, 3, ux, gx, wgt<T>(1));
+        source(2, 4, uy, gy, wgt<T>(1));
+        source(5, 7, ux + uy, gx + gy, wgt<T>(5));
+        source(8, 6, ux - uy, gx - gy, wgt<T>(5));
+    }
 }
 
 // The collision of the step kernels: BGK with the global 1/tau, (LES modes) the Smagorinsky rate of each cell, or (TRT modes) 1/tau
@@ -522,7 +580,9 @@ __device__ __forceinline__ void bgk_collide(T (&f)[Q], T tau_inv, T les_tau = T(
 template <typename T, int AR>
 __device__ __forceinline__ void collide(T (&f)[Q], const KArgs<T>& a) {
     static_assert(!(ar_les(AR) && ar_trt(AR)), "TRT and LES exclude each other");
-    if constexpr (ar_trt(AR)) bgk_collide<T, AR>(f, a.tau_inv, a.trt_wm, a.trt_wa, a.trt_wb);
+    static_assert(!(ar_forced(AR) && (ar_les(AR) || ar_trt(AR))), "forcing excludes LES and TRT");
+    if constexpr (ar_forced(AR)) bgk_collide<T, AR>(f, a.tau_inv, a.frc_gx, a.frc_gy, a.frc_hx, a.frc_hy);
+    else if constexpr (ar_trt(AR)) bgk_collide<T, AR>(f, a.tau_inv, a.trt_wm, a.trt_wa, a.trt_wb);
     else if constexpr (ar_les(AR)) bgk_collide<T, AR>(f, T(0), a.les_tau, a.les_tau2, a.les_c);
     else bgk_collide<T, AR>(f, a.tau_inv);
 }
@@ -1155,12 +1215,18 @@ struct MacroArgs {
     int walls; WallK<T> wk;                // the two walls, as KArgs carries them (appended: the fields above keep their offsets)
     T in_scale;                            // the inlet schedule's factor of the iteration this snapshot describes, (T)s(t), formed by the host
                                            // (lbm_set_inlet_schedule); 1 without a schedule: x * 1 changes no bit, so no branch
+    T frc_hx, frc_hy;                      // a context with a driving force (lbm_set_forcing): h = F/2, as KArgs carries it, which the fluid cells'
+    int forced;                            // velocity takes off the momentum of the populations read (macro_moments) where `forced` is set
+    char frc_pad[64 - 2 * sizeof(T) - sizeof(int)];   // (64 bytes in all: what follows this struct in FrameArgs, ProbeArgs, StatsArgs keeps its alignment)
 };
 
 // the moments of the nine populations of a fluid cell, in the element type: rho and u = (sum c_i f_i) / rho (one definition for
-// k_macros and k_stats: the two must agree to the bit)
+// k_macros, k_stats, k_frame and k_probes: they must agree to the bit).
+// Under a driving force (lbm_set_forcing) the velocity is Guo's, u = (sum c f_pre + F/2) / rho of the collision that wrote the
+// populations read here. Those are POST-collision ones, whose momentum is the pre-collision one plus F, so h = F/2 is taken off: one
+// IEEE subtraction per component before the division. A launch-uniform branch, taken with a force set only: without one no bit changes.
 template <typename T>
-__device__ __forceinline__ void macro_moments(const T (&f)[Q], double& r, double& vx, double& vy) {
+__device__ __forceinline__ void macro_moments(const MacroArgs<T>& p, const T (&f)[Q], double& r, double& vx, double& vy) {
     T rr = T(0), sx = T(0), sy = T(0);
 #pragma unroll
     for (int i = 0; i < Q; ++i) {
@@ -1169,6 +1235,7 @@ __device__ __forceinline__ void macro_moments(const T (&f)[Q], double& r, double
         if (cx(i) != 0) sx += T(cx(i)) * v;
         if (cy(i) != 0) sy += T(cy(i)) * v;
     }
+    if (p.forced) { sx = sx - p.frc_hx; sy = sy - p.frc_hy; }
     sx /= rr; sy /= rr;
     r = (double)rr; vx = (double)sx; vy = (double)sy;
 }
@@ -1195,7 +1262,7 @@ __device__ __forceinline__ void macro_cell(const MacroArgs<T>& p, int x, int y, 
         T f[Q];
 #pragma unroll
         for (int i = 0; i < Q; ++i) f[i] = p.old[(long)i * p.plane + c];
-        macro_moments<T>(f, r, vx, vy);
+        macro_moments<T>(p, f, r, vx, vy);
     }
 }
 
@@ -1263,8 +1330,8 @@ __global__ void __launch_bounds__(256) k_stats(const StatsArgs<T> p) {
             const T2 v = *reinterpret_cast<const T2*>(a.old + (long)i * a.plane + c);
             f0[i] = v.x; f1[i] = v.y;
         }
-        macro_moments<T>(f0, r[0], vx[0], vy[0]);
-        macro_moments<T>(f1, r[1], vx[1], vy[1]);
+        macro_moments<T>(a, f0, r[0], vx[0], vy[0]);
+        macro_moments<T>(a, f1, r[1], vx[1], vy[1]);
         const int yg = a.y_start + y;
         if (solid_at(a, x0, yg)) { r[0] = 1.0; vx[0] = 0.0; vy[0] = 0.0; }
         if (solid_at(a, x0 + 1, yg)) { r[1] = 1.0; vx[1] = 0.0; vy[1] = 0.0; }

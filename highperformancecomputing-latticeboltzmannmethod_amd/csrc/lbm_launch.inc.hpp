@@ -8,6 +8,26 @@ void fill_walls(const lbm_ctx* c, A& a) {
     a.wk = wall_ks<T>(c->wall_kind[0], c->wall_u[0], c->wall_kind[1], c->wall_u[1]);
 }
 
+// The driving force (lbm_set_forcing) as the argument blocks carry it: h = F/2 (KArgs and MacroArgs) and g = (1 - wp/2) F with wp = 1/tau
+// as tau_inv is formed (KArgs), each formed in double and cast once. Zeros on every other context, whose kernels never read them.
+struct ForcingK { double gx, gy, hx, hy; };
+inline ForcingK forcing_ks(const lbm_ctx* c) {
+    if (c->collision != AR_STRICT_FORCED) return {0.0, 0.0, 0.0, 0.0};
+    const double wp = 1.0 / c->p.tau, k = 1.0 - 0.5 * wp;
+    return {k * c->collision_param, k * c->collision_param2, 0.5 * c->collision_param, 0.5 * c->collision_param2};
+}
+template <typename T>
+void fill_forcing(const lbm_ctx* c, KArgs<T>& a) {
+    const ForcingK k = forcing_ks(c);
+    a.frc_gx = (T)k.gx; a.frc_gy = (T)k.gy; a.frc_hx = (T)k.hx; a.frc_hy = (T)k.hy;
+}
+template <typename T>
+void fill_forcing(const lbm_ctx* c, MacroArgs<T>& m) {
+    const ForcingK k = forcing_ks(c);
+    m.forced = c->collision == AR_STRICT_FORCED ? 1 : 0;
+    m.frc_hx = (T)k.hx; m.frc_hy = (T)k.hy;
+}
+
 // The inlet schedule's factor of iteration t in the element type, (T)s(t); 1 without a schedule (or before iteration 0).
 template <typename T>
 T inlet_scale(const lbm_ctx* c, int t) {
@@ -55,6 +75,7 @@ KArgs<T> make_kargs(const lbm_ctx* c, int src, int dst, int t) {
     }
     fill_walls<T>(c, a);
     a.sched = static_cast<const int*>(c->d_sched);
+    fill_forcing<T>(c, a);
     return a;
 }
 
@@ -176,6 +197,7 @@ MacroArgs<T> make_macro_args(const lbm_ctx* c, const void* src, int t) {
     m.u_row = static_cast<const T*>(c->d_urow);
     fill_walls<T>(c, m);
     m.in_scale = inlet_scale<T>(c, t);
+    fill_forcing<T>(c, m);
     m.initial = 0;
     m.rho = m.ux = m.uy = nullptr; m.max_usq_bits = nullptr;
     return m;

@@ -42,11 +42,18 @@ inline const char* deep_tile(int id) {
 // the models whose contracted kernels on the tall fp64 regions keep four waves per SIMD without scratch: BGK 120 VGPRs, TRT 124,
 // Smagorinsky 126 with three of the parked row's reads issued a row later (profiles/col_parked/README.md; build.py PARK_BASES)
 constexpr bool PARK_LES = true, PARK_TRT = true;
-struct CollisionModel { int base; const char* noun; bool tall, park; unsigned long long ckpt_bit; const char *param, *value, *none; };
+// BGK under a driving force (lbm_set_forcing): its contracted kernels on the tall fp64 regions take 122-123 VGPRs, no scratch, four waves
+// per SIMD like BGK's 120 (profiles/forcing/README.md; build.py FORCED_PARK_BASES). Like LES and TRT it has no tall fp32 regions: their
+// two objects are BGK's alone (lbm_col.hip -DLBM_COL_TALL), so no forced instantiation of them exists to meet the bar.
+constexpr bool PARK_FORCED = true;
+// `nparam`: the doubles of the model's parameter (the force has two components; lbm_ctx::collision_param, collision_param2). A model whose
+// ckpt_bit lies above the bits of the walls and the inlet schedule stands behind them in a checkpoint, as its bit says.
+struct CollisionModel { int base; const char* noun; bool tall, park; unsigned long long ckpt_bit; const char *param, *value, *none; int nparam = 1; };
 constexpr CollisionModel collision_models[] = {
     {AR_STRICT, "BGK", true, true, 0, "", "", ""},
     {AR_STRICT_LES, "Smagorinsky (LES)", false, PARK_LES, 4, "Smagorinsky constant", "Cs = ", " (BGK)"},
     {AR_STRICT_TRT, "two-relaxation-time (TRT)", false, PARK_TRT, 8, "TRT magic parameter", "", ""},
+    {AR_STRICT_FORCED, "forced BGK (Guo forcing)", false, PARK_FORCED, 64, "forcing", "F = ", "", 2},
 };
 // the row of an Arith value, strict or contracted
 constexpr const CollisionModel& collision_model(int arith) {
@@ -165,7 +172,7 @@ inline std::vector<Plan> plan_candidates(const PlanQuery& q, const Plan& fixed) 
 }
 
 // the dominant kernel of a plan, as rocprofv3 names it (minus "lbmk::" and blanks)
-// (arith: the kernels' Arith value, 0..5; the region shapes follow its strict / contracted half)
+// (arith: the kernels' Arith value, 0..5, 8, 9; the region shapes follow its strict / contracted half)
 inline std::string plan_kernel_name(int fuse, int deep, int pair_ty, int nt, int arith, int esize) {
     char name[96];
     const char* t = esize == 4 ? "float" : "double";

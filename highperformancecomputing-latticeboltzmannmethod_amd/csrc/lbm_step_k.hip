@@ -1,10 +1,13 @@
 // csrc/lbm_step_k.hip — the single-iteration and fused tile kernel families (k_step_site, k_step2/3/4_tile, k_stepd_tile) of ONE collision
 // model and their launchers (lbm_launch_k.hpp), for both element types: compiled once per model with -DLBM_AR_BASE=<the model's Arith
-// base> (build.py), side by side with the host translation unit. MODE_STREAM_ONLY has no collision in it: base 0 alone holds it.
+// base> (-DLBM_AR_FORCED_BASE=8 for the forced one; build.py), side by side with the host translation unit. MODE_STREAM_ONLY has no collision in it: base 0 alone holds it.
 #include "lbm_launch_k.hpp"
 
+#if !defined(LBM_AR_BASE) && defined(LBM_AR_FORCED_BASE)   // the forced model's objects carry a flag of their own (build.py FORCED_BASES)
+#define LBM_AR_BASE LBM_AR_FORCED_BASE
+#endif
 #ifndef LBM_AR_BASE
-#error "compile with -DLBM_AR_BASE=<Arith base of a collision model: 0, 2 or 4>"
+#error "compile with -DLBM_AR_BASE=<Arith base of a collision model: 0, 2 or 4> or -DLBM_AR_FORCED_BASE=8"
 #endif
 
 namespace lbmk {

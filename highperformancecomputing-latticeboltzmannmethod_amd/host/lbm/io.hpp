@@ -313,7 +313,11 @@ private:
             f.put("wall_south,"); f.put(p.wall_text(0).c_str()); f.put("\n");
             f.put("wall_north,"); f.put(p.wall_text(1).c_str()); f.put("\n");
         }
-        if (p.scheduled()) { f.put("inlet_schedule,"); f.put(p.inlet_schedule_spec.c_str()); f.put("\n"); }   // (runs with an inlet schedule only; the last line)
+        if (p.scheduled()) { f.put("inlet_schedule,"); f.put(p.inlet_schedule_spec.c_str()); f.put("\n"); }   // (runs with an inlet schedule only)
+        if (p.forced()) {                                                                                  // (runs with a driving force only; the last lines)
+            f.put("forcing_x,"); f.put(SimulationParams::shortest_text(p.forcing_x).c_str()); f.put("\n");
+            f.put("forcing_y,"); f.put(SimulationParams::shortest_text(p.forcing_y).c_str()); f.put("\n");
+        }
         std::printf("  simulation_params.csv written\n");
     }
     // calculate_time_averaged_drag (LBMIO.h:367-413): statistics of the CSV values (8 decimals) for timestep > 1000.

@@ -3,6 +3,7 @@
 // surface a caller of the reference touches: LBMConfig.h:9-34 constants, :36-66 SimulationParams).
 #pragma once
 #include <array>
+#include <cctype>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -60,6 +61,9 @@ struct SimulationParams {
     // Two-relaxation-time collision (lbm_solver --trt-magic; not in the reference): the magic parameter, 0 = plain BGK. Never
     // together with smagorinsky_cs. tau keeps setting the viscosity.
     double trt_magic = 0.0;
+    // Uniform driving force (lbm_solver --forcing FX,FY; not in the reference): a constant force density in lattice units on every
+    // fluid cell, Guo's scheme on the BGK collision (lbm_set_forcing). (0, 0) = none. Never together with smagorinsky_cs or trt_magic.
+    double forcing_x = 0.0, forcing_y = 0.0;
     // time-averaged statistics (lbm_solver --stats-start; not in the reference): the first step sampled, -1 = off. Samples are taken on
     // the device at the output_frequency cadence (lbm_stats_begin); the run ends with mean_fields.vtk / mean_fields.csv.
     int stats_start = -1;
@@ -85,19 +89,40 @@ struct SimulationParams {
     bool scheduled() const { return !inlet_schedule.empty(); }
     bool les() const { return smagorinsky_cs > 0.0; }
     bool trt() const { return trt_magic > 0.0; }
+    bool forced() const { return forcing_x != 0.0 || forcing_y != 0.0; }
     bool stats() const { return stats_start >= 0; }
     bool frames() const { return frame_stride > 0; }
     bool probes() const { return !probe_xy.empty(); }
     int probe_count() const { return (int)(probe_xy.size() / 2); }
     bool walled() const { return wall_kind[0] != 0 || wall_kind[1] != 0; }
-    // the velocity of wall `side` with the fewest digits that read back exactly
-    std::string wall_velocity_text(int side) const {
+    // a number with the fewest digits that read back exactly
+    static std::string shortest_text(double v) {
         char b[64];
         for (int digits = 1; digits <= 17; ++digits) {
-            std::snprintf(b, sizeof(b), "%.*g", digits, wall_velocity[side]);
-            if (std::strtod(b, nullptr) == wall_velocity[side]) break;
+            std::snprintf(b, sizeof(b), "%.*g", digits, v);
+            if (std::strtod(b, nullptr) == v) break;
         }
         return b;
+    }
+    // the velocity of wall `side` in that form
+    std::string wall_velocity_text(int side) const { return shortest_text(wall_velocity[side]); }
+    // FX,FY of --forcing: one token, two finite numbers of magnitude below 1, each parsed whole (std::invalid_argument with the one-line
+    // message otherwise)
+    void set_forcing(const std::string& text) {
+        const auto bad = [&](const char* why) {
+            return std::invalid_argument("--forcing: '" + text + "' " + why + " (FX,FY: two numbers of magnitude below 1)");
+        };
+        const size_t comma = text.find(',');
+        if (comma == std::string::npos || text.find(',', comma + 1) != std::string::npos) throw bad("is not a pair FX,FY");
+        const std::string part[2] = {text.substr(0, comma), text.substr(comma + 1)};
+        double v[2];
+        for (int k = 0; k < 2; ++k) {
+            char* end = nullptr;
+            v[k] = std::strtod(part[k].c_str(), &end);
+            if (part[k].empty() || std::isspace((unsigned char)part[k][0]) || end == part[k].c_str() || *end != '\0') throw bad(k ? "has no number FY" : "has no number FX");
+            if (!std::isfinite(v[k]) || std::fabs(v[k]) >= 1.0) throw bad("has a component that is not finite or not below 1 in magnitude");
+        }
+        forcing_x = v[0]; forcing_y = v[1];
     }
     // a wall as the command line names it: "no-slip", "free-slip" or "moving:U"
     std::string wall_text(int side) const {

@@ -52,6 +52,9 @@ public:
         if (!opt_.quiet && params_.trt())
             std::printf("  Collision: TRT collision, magic = %g (odd parts relax with 1/(0.5 + magic/(tau - 0.5)); tau sets the viscosity)\n",
                         params_.trt_magic);
+        if (!opt_.quiet && params_.forced())
+            std::printf("  driving force (Guo): Fx = %s, Fy = %s\n", SimulationParams::shortest_text(params_.forcing_x).c_str(),
+                        SimulationParams::shortest_text(params_.forcing_y).c_str());
         if (!opt_.quiet && params_.walled())
             std::printf("  Walls: south %s, north %s\n", params_.wall_banner(0).c_str(), params_.wall_banner(1).c_str());
         if (!opt_.quiet && params_.masked()) {

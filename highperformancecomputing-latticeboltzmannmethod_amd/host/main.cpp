@@ -23,6 +23,7 @@ static void usage() {
               "           [--gpus N] [--strips N] [--rccl]\n"
               "           [--checkpoint FILE] [--restart FILE] [--obstacle-mask FILE.pgm] [--obstacle-bodies FILE.pgm]\n"
               "           [--inlet-profile parabolic|FILE] [--print-inlet-profile] [--smagorinsky CS] [--trt-magic LAMBDA]\n"
+              "           [--forcing FX,FY]\n"
               "           [--stats-start N] [--wall-south KIND] [--wall-north KIND] [--walls KIND]\n"
               "           [--frame-stride K] [--probes FILE] [--probe-line x0 y0 x1 y1 n]\n"
               "           [--inlet-ramp N | --inlet-pulse A:P | --inlet-schedule FILE [--inlet-schedule-repeat]] [--print-inlet-schedule]\n"
@@ -56,6 +57,11 @@ static void usage() {
               "instead of BGK: the even part of each opposite pair of populations relaxes with 1/tau (the viscosity is\n"
               "unchanged), the odd part with 1/(0.5 + LAMBDA/(tau - 0.5)). 0.25 is the most stable choice, 0.1875 (3/16) the\n"
               "most accurate at walls. Needs tau > 0.5; cannot be combined with --smagorinsky.\n"
+              "--forcing FX,FY: a uniform driving force density (FX, FY) in lattice units on every fluid cell and iteration (one token;\n"
+              "either number may be negative, each of magnitude below 1): a pressure-gradient-equivalent drive, gravity, a cross-stream\n"
+              "force. Guo's scheme on the BGK collision: the velocity of the equilibrium and of every output is (sum c f + F/2) / rho.\n"
+              "A channel of H rows between the walls carries the parabola of peak u_max under FX = 8 nu u_max / H^2. The inlet, the outlet\n"
+              "and the walls do not know about the force. Cannot be combined with --smagorinsky or --trt-magic.\n"
               "--wall-south KIND / --wall-north KIND: the bottom (row 0) / top (row ny-1) wall, KIND = no-slip (the default: on-node\n"
               "bounce-back) | free-slip (specular reflection: no boundary layer, for unconfined flow past a body) | moving:U (a wall\n"
               "sliding at the tangential velocity U, |U| < 1: Couette flow, a lid, a moving ground). --walls KIND sets both. The\n"
@@ -85,6 +91,7 @@ int main(int argc, char** argv) {
     std::string schedule_option, schedule_file;   // which of the three sources gave the schedule; the FILE of --inlet-schedule
     const char* smagorinsky = nullptr;
     const char* trt_magic = nullptr;
+    const char* forcing = nullptr;
     const char* stats_start = nullptr;
     const char* frame_stride = nullptr;
     std::vector<LBM::ProbePoint> probe_points;
@@ -126,6 +133,7 @@ int main(int argc, char** argv) {
         else if (k == "--print-inlet-profile") print_profile = true;
         else if (k == "--smagorinsky") smagorinsky = val();
         else if (k == "--trt-magic") trt_magic = val();
+        else if (k == "--forcing") forcing = val();
         else if (k == "--stats-start") stats_start = val();
         else if (k == "--wall-south" || k == "--wall-north" || k == "--walls") {   // checked here: no device is touched before a bad value exits
             try {
@@ -198,6 +206,18 @@ int main(int argc, char** argv) {
             return 2;
         }
         params.trt_magic = magic;
+    }
+    if (forcing) {       // likewise: FX,FY parsed whole, and no second collision model
+        try {
+            params.set_forcing(forcing);
+        } catch (const std::exception& e) {
+            std::fprintf(stderr, "%s\n", e.what());
+            return 2;
+        }
+        if (params.forced() && (params.smagorinsky_cs > 0.0 || params.trt_magic > 0.0)) {
+            std::fprintf(stderr, "--forcing cannot be combined with %s (one collision model at a time)\n", params.smagorinsky_cs > 0.0 ? "--smagorinsky" : "--trt-magic");
+            return 2;
+        }
     }
     if (stats_start) {   // checked before any device is touched: a whole number >= 0, and a cadence to sample at
         char* end = nullptr;

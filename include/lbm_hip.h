@@ -324,6 +324,37 @@ int  lbm_set_smagorinsky(lbm_ctx* c, double cs);
  * LBM_ERR_ARG: null context, an initialised context, a value that is not finite, < 0 or > 1, a context whose tau <= 0.5, or a
  * context with a nonzero Smagorinsky constant: the two collisions cannot be combined. */
 int  lbm_set_trt(lbm_ctx* c, double magic);
+/* The collision: a uniform driving force. A constant force density F = (fx, fy) in lattice units acts on every fluid cell at every
+ * iteration: the pressure-gradient-equivalent drive of a channel, gravity, a cross-stream force on a wake. ("Forcing", because "body
+ * forces" are the momentum-exchange forces on obstacles: lbm_get_body_forces.) The scheme is Guo, Zheng and Shi (2002) on the BGK
+ * operator: the equilibrium is taken at the velocity u = (sum_i c_i f_i + F/2) / rho, and the source
+ *     S_i = (1 - 1/(2 tau)) w_i [3 (c_i - u) + 9 (c_i . u) c_i] . F
+ * is added to the relaxed populations, f_i' = (f_i - (f_i - feq_i(rho, u)) / tau) + S_i. The host forms the launch-uniform values in
+ * double and casts each once to the element type: wp = 1/tau, g = (1 - wp/2) F, h = F/2. Strict arithmetic (option arith=0) evaluates,
+ * one IEEE operation at a time with no contraction: the sums rho, jx, jy of BGK; jx + hx, jy + hy; the two divisions by rho; feq_i as
+ * BGK forms it from these ux, uy; u3 = 3 (ux gx + uy gy); S_0 = w_0 (0 - u3); and per opposite pair (i, ib) of (1,3), (2,4), (5,7),
+ * (8,6), with cu as BGK's and cg = gx, gy, gx + gy, gx - gy: a = 3 cg, b = (9 cu) cg, S_i = w_i ((a - u3) + b),
+ * S_ib = w_i ((-a - u3) + b). Contracted arithmetic (arith=1) folds the source into its FMA chain. The sum of the S_i is zero (mass is
+ * kept) and a collision adds exactly F to a cell's momentum. No extra memory traffic.
+ * Every cell that collides today takes the force: the cells of the wall rows and of the inlet and outlet columns included.
+ * The snapshot — lbm_get_macros, statistics, frames, probes — reports Guo's velocity on the interior fluid cells of a forced context,
+ * through the one function they share: the populations it reads are post-collision ones, whose momentum is the pre-collision one plus
+ * F, so it forms (sum_i c_i f_i - F/2) / rho, one IEEE subtraction per component before the division. The inlet and outlet columns,
+ * solid cells and the initial snapshot report what they report without a force.
+ * Unchanged: the momentum-exchange forces on obstacles, the stability scan, the halo exchange, every launch and row range and the
+ * dry-run choreography (lbm_debug_choreography); with (0, 0) every result, kernel name and checkpoint byte is what it was without this
+ * call. Documented, not corrected: the Zou-He inlet and outlet, the wall rules and the solid cells do not know about the force (the
+ * boundary rules prescribe their velocity and density as they do without one, and bounce-back is not force-corrected).
+ * Call after lbm_create and before lbm_initialise, like lbm_set_trt: the plan is then measured on the forced kernels (Arith values
+ * 8 / 9; no fp32 deep=8 plan: pinning it fails). Every strip of a run is given the same values. (0, 0) clears the model (the BGK
+ * kernels). Checkpoints carry the force (lbm_save_state: magic "LBMCKPT3", flag bit 6, two doubles {fx, fy} behind everything the
+ * lower bits carry) and load only into a context with an equal one.
+ * LBM_ERR_ARG (the text names the offender): a null context, an initialised context, a component that is not finite or has
+ * magnitude >= 1, or a nonzero force on a context with a Smagorinsky constant or a TRT magic parameter — and either of those on a
+ * context with a force: the collisions cannot be combined. */
+int  lbm_set_forcing(lbm_ctx* c, double fx, double fy);
+/* The force as set, (0, 0) on a context without one; either pointer may be NULL. LBM_ERR_ARG: null context. */
+int  lbm_get_forcing(const lbm_ctx* c, double* fx, double* fy);
 /* The two walls: generalises the on-node bounce-back of the bottom and top rows (LBMSolver.h:155-176), a stationary no-slip wall, to a
  * KIND and a tangential VELOCITY per wall. The south wall is global row 0, the north wall global row ny - 1. On a fluid cell of the
  * wall's row, after the pull:
