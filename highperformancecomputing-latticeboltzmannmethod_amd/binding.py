@@ -28,6 +28,18 @@ class BodyForceRow(C.Structure):
     _fields_ = [("timestep", C.c_int), ("body", C.c_int), ("fx", C.c_double), ("fy", C.c_double)]
 
 
+class CkptHead(C.Structure):
+    """struct lbm_ckpt_head (include/lbm_hip.h): what the head of a checkpoint says about a run."""
+    _fields_ = [("nx", C.c_int), ("ny", C.c_int), ("y_start", C.c_int), ("local_ny", C.c_int), ("precision", C.c_int), ("steps_done", C.c_int),
+                ("tau", C.c_double), ("inlet_velocity", C.c_double), ("cylinder_x", C.c_double), ("cylinder_y", C.c_double),
+                ("cylinder_radius", C.c_double),
+                ("has_mask", C.c_int), ("has_profile", C.c_int), ("collision", C.c_int), ("has_walls", C.c_int), ("has_sched", C.c_int),
+                ("mask_digest", C.c_ulonglong), ("profile_digest", C.c_ulonglong), ("sched_digest", C.c_ulonglong),
+                ("collision_param", C.c_double * 2), ("walls", C.c_double * 4)]
+
+
+CKPT_HEAD_MAX = 176                                            # LBM_CKPT_HEAD_MAX
+
 _lib = None
 
 
@@ -127,6 +139,8 @@ def lib():
         L.lbm_set_option.argtypes = [vp, C.c_char_p, C.c_long]
         L.lbm_save_state.argtypes = [vp, C.c_char_p]
         L.lbm_load_state.argtypes = [vp, C.c_char_p]
+        L.lbm_debug_ckpt_save.argtypes = [C.POINTER(CkptHead), C.POINTER(C.c_ubyte), dp, dp, C.c_int, C.c_int, C.c_char_p, C.c_int]
+        L.lbm_debug_ckpt_load.argtypes = [C.c_char_p, C.c_int, C.POINTER(CkptHead), C.c_char_p, ip]
         L.lbm_last_step_kernel_ms.argtypes = [vp, dp]
         L.lbm_last_step_stats.argtypes = [vp, dp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.lbm_last_step_dispatches.argtypes = [vp]
@@ -224,6 +238,33 @@ def debug_gather(what, bounds, nx, ny, parts, whole, k=1, planes=1):
     code = {"stack": 0, "unstack": 1, "stack_f32": 2, "populations": 3, "sum": 4}[what]
     if lib().lbm_debug_gather(code, len(parts), b.ctypes.data_as(C.POINTER(C.c_int)), nx, ny, k, planes, ptrs, whole.ctypes.data) < 0:
         raise LbmError(lib().lbm_last_error().decode())
+
+
+def debug_ckpt_save(head, mask=None, profile=None, schedule=None):
+    """lbm_debug_ckpt_save (no device): the bytes of the head lbm_save_state writes for a context that `head` (a CkptHead) describes.
+    mask ((ny, nx)), profile ((ny,)) or schedule (inlet_schedule= form): that field is marked present in `head` and its digest is formed
+    from the data as the setter forms it, and left in `head`."""
+    m = _mask_bytes(mask, head.nx, head.ny) if mask is not None else None
+    u = np.ascontiguousarray(profile, dtype=np.float64) if profile is not None else None
+    if u is not None and u.shape != (head.ny,):
+        raise ValueError(f"an inlet profile has one velocity per row: shape {u.shape}, the domain has {head.ny} rows")
+    s, mode = _schedule(schedule) if schedule is not None else (None, 0)
+    out = C.create_string_buffer(CKPT_HEAD_MAX)
+    n = lib().lbm_debug_ckpt_save(C.byref(head), m.ctypes.data_as(C.POINTER(C.c_ubyte)) if m is not None else None, _dp(u), _dp(s),
+                                  s.size if s is not None else 0, mode, out, CKPT_HEAD_MAX)
+    if n < 0:
+        raise LbmError(f"lbm_hip error {n}: {lib().lbm_last_error().decode()}")
+    return out.raw[:n]
+
+
+def debug_ckpt_load(data, head, path="x.ckpt"):
+    """lbm_debug_ckpt_load (no device): what lbm_load_state decides about a file `path` that begins with the bytes `data`, on a context that
+    `head` (a CkptHead) describes: the bytes of the file's head, behind which the populations stand; LbmError with lbm_load_state's text."""
+    used = C.c_int()
+    rc = lib().lbm_debug_ckpt_load(bytes(data), len(data), C.byref(head), path.encode(), C.byref(used))
+    if rc < 0:
+        raise LbmError(lib().lbm_last_error().decode())
+    return used.value
 
 
 def _label_bytes(labels, nx, ny):

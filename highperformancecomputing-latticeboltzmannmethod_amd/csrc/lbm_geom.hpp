@@ -4,6 +4,7 @@
 // 8x8-cell blocks of the same window. Plus what the host needs: the mask's bounding box (force box) and a digest (checkpoints).
 #pragma once
 #include "lbm_kernels.hpp"
+#include "lbm_ckpt.hpp"
 
 #include <cstdint>
 #include <cstring>
@@ -16,7 +17,7 @@ struct HostMask {
     std::vector<int> sat;                   // [nby + 1][nbx + 1]
     int y0 = 0, rows = 0, words = 0, nbx = 0, nby = 0;
     int bx0 = 0, bx1 = -1, by0 = 0, by1 = -1;   // bounding box of the solid cells of the WHOLE mask (global, inclusive; empty: x1 < x0)
-    unsigned long long digest = 0;              // FNV-1a over nx, ny and the 0/1 cells of the whole mask
+    unsigned long long digest = 0;              // of the whole mask (lbm_ckpt.hpp mask_digest)
     MaskView view() const {                     // (host pointers: for the host-side queries and the test hook)
         MaskView m;
         m.bits = bits.data(); m.sat = sat.data();
@@ -47,21 +48,15 @@ inline HostMask pack_mask(const unsigned char* mask, int nx, int ny, int y_start
         for (int c = 0; c < h.nbx; ++c)
             h.sat[(size_t)(b + 1) * W + c + 1] = blocks[(size_t)b * h.nbx + c] + h.sat[(size_t)b * W + c + 1] +
                                                  h.sat[(size_t)(b + 1) * W + c] - h.sat[(size_t)b * W + c];
-    unsigned long long d = 1469598103934665603ull;
-    auto mix = [&](unsigned v) { d ^= v; d *= 1099511628211ull; };
-    mix((unsigned)nx); mix((unsigned)ny);
     h.bx0 = nx; h.by0 = ny;
     for (int y = 0; y < ny; ++y)
-        for (int x = 0; x < nx; ++x) {
-            const bool s = mask[(size_t)y * nx + x] != 0;
-            mix(s ? 1u : 0u);
-            if (s) {
+        for (int x = 0; x < nx; ++x)
+            if (mask[(size_t)y * nx + x]) {
                 h.bx0 = x < h.bx0 ? x : h.bx0; h.bx1 = x > h.bx1 ? x : h.bx1;
                 h.by0 = y < h.by0 ? y : h.by0; h.by1 = y > h.by1 ? y : h.by1;
             }
-        }
     if (h.bx1 < 0) { h.bx0 = 0; h.by0 = 0; }
-    h.digest = d;
+    h.digest = mask_digest(mask, nx, ny);
     return h;
 }
 

@@ -8,6 +8,7 @@
 #include "lbm_plan.hpp"
 #include "lbm_gather.hpp"
 #include "lbm_geom.hpp"
+#include "lbm_ckpt.hpp"
 #include "../../include/lbm_hip.h"
 
 #include <rccl/rccl.h>
@@ -102,18 +103,6 @@ int check_schedule(const char* who, const double* s, int n, int mode) {
         if (!std::isfinite(s[k])) return fail(LBM_ERR_ARG, "%s: entry %d is %g (finite factors only)", who, k, s[k]);
     return LBM_OK;
 }
-// FNV-1a over the mode, the length and the bit patterns of the factors: what a checkpoint carries of a schedule
-unsigned long long schedule_digest(const double* s, int n, int mode) {
-    unsigned long long d = 1469598103934665603ull;
-    auto mix = [&](unsigned v) { d ^= v; d *= 1099511628211ull; };
-    mix((unsigned)mode); mix((unsigned)n);
-    for (int k = 0; k < n; ++k) {
-        unsigned long long b;
-        memcpy(&b, &s[k], sizeof(b));
-        mix((unsigned)b); mix((unsigned)(b >> 32));
-    }
-    return d;
-}
 // the device block the kernels read: {n, mode}, then the factors in the element type (lbm_kernels.hpp inlet_sched_at)
 template <typename T>
 int upload_schedule(lbm_ctx* c) {
@@ -149,77 +138,49 @@ int prepare_schedule(lbm_ctx* c) {
 }
 }  // namespace
 
-// ---- checkpoint / restart (the reference keeps its state in memory only) ------------------------
-// File: CkptHeader; in an "LBMCKPT3" file a 64-bit word of flags; the fields the flags announce, in the order of their bits (bit 0: the
-// obstacle mask's 64-bit digest, bit 1: the inlet profile's, then one double per collision model that has a parameter — ckpt_bit in
-// collision_models, lbm_plan.hpp: bit 2 Cs, bit 3 the TRT magic parameter (and, behind everything the lower bits carry, bit 6: the two doubles {fx, fy} of lbm_set_forcing) — then bit 4: the two walls of lbm_set_wall as four doubles,
-// south kind, south velocity, north kind, north velocity, written only where a wall is not no-slip — then bit 5: the 64-bit digest of the
-// inlet schedule of lbm_set_inlet_schedule, {mode, n, the n doubles}; the iteration counter positions the schedule after a restart); then the post-collision populations P_{steps_done} of the
-// strip's interior, [9][local_ny][nx] in the element type. The state is complete: ghost cells and solid cells are reconstructed by
-// lbm_initialise. A context with neither profile nor collision parameter nor such a wall nor a schedule writes "LBMCKPT2" (header, mask digest, populations) if it has a
-// mask and "LBMCKPT1" (header, populations) otherwise. A context loads only a file that announces exactly what it has, with equal values.
+// ---- checkpoint / restart: the format, the table of its optional fields and the refusals are lbm_ckpt.hpp ----
 namespace {
-constexpr unsigned long long CKPT_WALLS = 16;   // LBMCKPT3 flag bit 4: the two walls follow the collision parameters
-constexpr unsigned long long CKPT_SCHED = 32;   // LBMCKPT3 flag bit 5: the inlet schedule's 64-bit digest follows the walls
-struct CkptHeader {
-    char magic[8];
-    int nx, ny, y_start, local_ny, precision, steps_done;
-    double tau, inlet_velocity, cylinder_x, cylinder_y, cylinder_radius;
-};
-
-// a model's parameter as messages print it: one number, or the pair of a model with two (collision_models: nparam)
-std::string param_text(const CollisionModel& m, double v, double v2, const char* fmt = "%g") {
-    char a[40], b[40];
-    snprintf(a, sizeof(a), fmt, v); snprintf(b, sizeof(b), fmt, v2);
-    return m.nparam == 2 ? std::string("(") + a + ", " + b + ")" : std::string(a);
+// what a checkpoint of this context says in its head, and what the head of a file it loads must say
+lbm_ckpt_head ckpt_head_of(const lbm_ctx* c) {
+    lbm_ckpt_head h{};
+    h.nx = c->nx; h.ny = c->p.ny; h.y_start = c->p.y_start; h.local_ny = c->nyl; h.precision = c->p.precision;
+    h.steps_done = c->steps_done; h.tau = c->p.tau; h.inlet_velocity = c->p.inlet_velocity;
+    h.cylinder_x = c->p.cylinder_x; h.cylinder_y = c->p.cylinder_y; h.cylinder_radius = c->p.cylinder_radius;
+    h.has_mask = c->has_mask; h.mask_digest = c->hmask.digest;
+    h.has_profile = c->has_profile; h.profile_digest = c->prof_digest;
+    h.collision = c->collision; h.collision_param[0] = c->collision_param; h.collision_param[1] = c->collision_param2;
+    h.has_walls = c->has_walls();
+    h.walls[0] = (double)c->wall_kind[0]; h.walls[1] = c->wall_u[0]; h.walls[2] = (double)c->wall_kind[1]; h.walls[3] = c->wall_u[1];
+    h.has_sched = c->has_sched(); h.sched_digest = c->sched_digest;
+    return h;
+}
+// lbm_load_state and lbm_debug_ckpt_load: the head in the first n bytes of `path` against the loading context's: the bytes it takes and
+// what it says, or the refusal
+int accept_head(const char* path, const unsigned char* bytes, int n, const lbm_ckpt_head& here, lbm_ckpt_head* file) {
+    const int used = ckpt_parse(bytes, n, file);
+    if (!used) return fail(LBM_ERR_ARG, "%s is not a checkpoint", path);
+    const std::string why = ckpt_refusal(*file, here);
+    if (!why.empty()) return fail(LBM_ERR_ARG, "checkpoint %s was written %s", path, why.c_str());
+    return used;
 }
 
-// lbm_load_state: the collision parameters a file announces (param: one slot per row of collision_models) against the context's; the last
-// model first, the order mismatches have always been reported in
-int refuse_collision_mismatch(const lbm_ctx* c, const char* path, unsigned long long flags, const double (*param)[2]) {
-    const double mine = c->collision_param, mine2 = c->collision_param2;
-    for (int i = (int)std::size(collision_models) - 1; i >= 0; --i) {
-        const CollisionModel& m = collision_models[i];
-        const bool in_file = flags & m.ckpt_bit, here = m.ckpt_bit && c->collision == m.base;
-        if (!in_file && here) return fail(LBM_ERR_ARG, "checkpoint %s was written without a %s%s; this context has %s%s", path, m.param, m.none, m.value, param_text(m, mine, mine2).c_str());
-        if (in_file && !here) return fail(LBM_ERR_ARG, "checkpoint %s was written with %s %s%s; this context has none%s", path, m.param, m.value, param_text(m, param[i][0], param[i][1]).c_str(), m.none);
-        if (in_file && (param[i][0] != mine || (m.nparam == 2 && param[i][1] != mine2)))
-            return fail(LBM_ERR_ARG, "checkpoint %s was written with %s %s%s; this context has %s%s", path, m.param, m.value, param_text(m, param[i][0], param[i][1], "%.17g").c_str(),
-                        m.value, param_text(m, mine, mine2, "%.17g").c_str());
-    }
-    return LBM_OK;
-}
-
+// The populations of a checkpoint, the interior rows of buf[cur] as [9][local_ny][nx]: written to fp, or (load) read from it. buf[cur]
+// comes down whole first: on a load it already holds P_0 with all ghost / solid constants in place and only its interior is overwritten
+// (the previous-iteration buffer's ghost frame is not needed: it is only read by snapshots after the next step).
 template <typename T>
-int do_save(lbm_ctx* c, FILE* fp) {
-    std::vector<T> row((size_t)c->nx);
+int transfer_interior(lbm_ctx* c, FILE* fp, bool load) {
     std::vector<T> host(c->total);
     HIPCHK(hipMemcpyAsync(host.data(), c->buf[c->cur], c->total * c->esize, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
+    const size_t nx = (size_t)c->nx;
     for (int i = 0; i < Q; ++i)
         for (int y = 0; y < c->nyl; ++y) {
-            const T* src = host.data() + (size_t)i * c->plane + (size_t)(y + GR) * c->pitch + c->xoff;
-            if (fwrite(src, sizeof(T), (size_t)c->nx, fp) != (size_t)c->nx) return fail(LBM_ERR_ARG, "short write");
+            T* row = host.data() + (size_t)i * c->plane + (size_t)(y + GR) * c->pitch + c->xoff;
+            if ((load ? fread(row, sizeof(T), nx, fp) : fwrite(row, sizeof(T), nx, fp)) != nx) return fail(LBM_ERR_ARG, load ? "short read" : "short write");
         }
-    return LBM_OK;
-}
-
-template <typename T>
-int do_load(lbm_ctx* c, FILE* fp, int steps_done) {
-    // buf[cur] already holds P_0 with all ghost/solid constants in place: overwrite the interior, then rebuild the
-    // previous-iteration buffer's ghost frame is not needed (it is only read by snapshots after the next step).
-    std::vector<T> host(c->total);
-    HIPCHK(hipMemcpyAsync(host.data(), c->buf[c->cur], c->total * c->esize, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    for (int i = 0; i < Q; ++i)
-        for (int y = 0; y < c->nyl; ++y) {
-            T* dst = host.data() + (size_t)i * c->plane + (size_t)(y + GR) * c->pitch + c->xoff;
-            if (fread(dst, sizeof(T), (size_t)c->nx, fp) != (size_t)c->nx) return fail(LBM_ERR_ARG, "short read");
-        }
+    if (!load) return LBM_OK;
     HIPCHK(hipMemcpyAsync(c->buf[c->cur], host.data(), c->total * c->esize, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    c->steps_done = steps_done;
-    c->restored = true;
     return LBM_OK;
 }
 
@@ -241,7 +202,6 @@ int drain_force_rows(lbm_ctx* c, DeviceRing<double>& log, int B, Row* rows, int 
 
 // ---- the two walls (lbm_set_wall) ----
 namespace {
-const char* wall_kind_name(int kind) { return kind == LBM_WALL_NOSLIP ? "no-slip" : kind == LBM_WALL_FREESLIP ? "free-slip" : "moving"; }
 // the argument checks shared by lbm_set_wall and lbm_debug_wall_rule; the text names the offender
 int check_wall(const char* who, int side, int kind, double velocity) {
     if (side != LBM_WALL_SOUTH && side != LBM_WALL_NORTH) return fail(LBM_ERR_ARG, "%s: side = %d (0 south or 1 north only)", who, side);
@@ -851,20 +811,12 @@ int lbm_set_inlet_profile(lbm_ctx* c, const double* u, int ny) {
     for (int y = 0; y < ny; ++y)   // the Zou-He inlet divides by 1 - u
         if (!std::isfinite(u[y]) || u[y] >= 1.0)
             return fail(LBM_ERR_ARG, "lbm_set_inlet_profile: row %d has velocity %g (finite values below 1 only)", y, u[y]);
-    unsigned long long d = 1469598103934665603ull;   // FNV-1a over ny and the bit patterns of the velocities
-    auto mix = [&](unsigned v) { d ^= v; d *= 1099511628211ull; };
-    mix((unsigned)ny);
-    for (int y = 0; y < ny; ++y) {
-        unsigned long long b;
-        memcpy(&b, &u[y], sizeof(b));
-        mix((unsigned)b); mix((unsigned)(b >> 32));
-    }
     HIPCHK(hipSetDevice(c->device));
     c->has_profile = false;
     if (int rc = upload_feqrow(c, u, ny)) return rc;
     if (int rc = upload_rows(c, c->d_urow, u, (size_t)ny)) return rc;
     c->h_urow.assign(u, u + ny);
-    c->prof_digest = d;
+    c->prof_digest = profile_digest(u, ny);
     c->has_profile = true;
     return LBM_OK;
 }
@@ -1122,31 +1074,10 @@ int lbm_save_state(lbm_ctx* c, const char* path) {
     { int jr = join_comm(c); if (jr) return jr; }
     FILE* fp = fopen(path, "wb");
     if (!fp) return fail(LBM_ERR_ARG, "cannot open %s for writing", path);
-    CkptHeader h{};
-    const CollisionModel& cm = collision_model(c->collision);
-    const bool v3 = c->has_profile || cm.ckpt_bit || c->has_walls() || c->has_sched();
-    memcpy(h.magic, v3 ? "LBMCKPT3" : c->has_mask ? "LBMCKPT2" : "LBMCKPT1", 8);
-    h.nx = c->nx; h.ny = c->p.ny; h.y_start = c->p.y_start; h.local_ny = c->nyl; h.precision = c->p.precision;
-    h.steps_done = c->steps_done; h.tau = c->p.tau; h.inlet_velocity = c->p.inlet_velocity;
-    h.cylinder_x = c->p.cylinder_x; h.cylinder_y = c->p.cylinder_y; h.cylinder_radius = c->p.cylinder_radius;
-    int rc = fwrite(&h, sizeof(h), 1, fp) == 1 ? LBM_OK : fail(LBM_ERR_ARG, "short write");
-    if (!rc && v3) {   // flags, then what they announce
-        const unsigned long long flags = (c->has_mask ? 1ull : 0ull) | (c->has_profile ? 2ull : 0ull) | cm.ckpt_bit | (c->has_walls() ? CKPT_WALLS : 0ull) |
-                                         (c->has_sched() ? CKPT_SCHED : 0ull);
-        if (fwrite(&flags, sizeof(flags), 1, fp) != 1) rc = fail(LBM_ERR_ARG, "short write");
-    }
-    if (!rc && c->has_mask && fwrite(&c->hmask.digest, sizeof(c->hmask.digest), 1, fp) != 1) rc = fail(LBM_ERR_ARG, "short write");
-    if (!rc && c->has_profile && fwrite(&c->prof_digest, sizeof(c->prof_digest), 1, fp) != 1) rc = fail(LBM_ERR_ARG, "short write");
-    const double cparam[2] = {c->collision_param, c->collision_param2};
-    const bool cm_late = cm.ckpt_bit > CKPT_SCHED;      // (a model whose bit lies above the schedule's: behind everything the lower bits carry)
-    if (!rc && cm.ckpt_bit && !cm_late && fwrite(cparam, sizeof(double), (size_t)cm.nparam, fp) != (size_t)cm.nparam) rc = fail(LBM_ERR_ARG, "short write");
-    if (!rc && c->has_walls()) {
-        const double w[4] = {(double)c->wall_kind[0], c->wall_u[0], (double)c->wall_kind[1], c->wall_u[1]};
-        if (fwrite(w, sizeof(w), 1, fp) != 1) rc = fail(LBM_ERR_ARG, "short write");
-    }
-    if (!rc && c->has_sched() && fwrite(&c->sched_digest, sizeof(c->sched_digest), 1, fp) != 1) rc = fail(LBM_ERR_ARG, "short write");
-    if (!rc && cm_late && fwrite(cparam, sizeof(double), (size_t)cm.nparam, fp) != (size_t)cm.nparam) rc = fail(LBM_ERR_ARG, "short write");
-    if (!rc) rc = DISPATCH(c, do_save<double>(c, fp), do_save<float>(c, fp));
+    unsigned char head[LBM_CKPT_HEAD_MAX];
+    const size_t n = (size_t)ckpt_serialise(ckpt_head_of(c), head);
+    int rc = fwrite(head, 1, n, fp) == n ? LBM_OK : fail(LBM_ERR_ARG, "short write");
+    if (!rc) rc = DISPATCH(c, transfer_interior<double>(c, fp, false), transfer_interior<float>(c, fp, false));
     fclose(fp);
     return rc;
 }
@@ -1166,62 +1097,38 @@ int lbm_load_state(lbm_ctx* c, const char* path) {
     }
     FILE* fp = fopen(path, "rb");
     if (!fp) return fail(LBM_ERR_ARG, "cannot open %s", path);
-    CkptHeader h{};
-    int rc = LBM_OK;
-    unsigned long long digest = 0, flags = 0, pdigest = 0, sdigest = 0;
-    constexpr int NM = (int)std::size(collision_models);
-    double param[NM][2] = {};          // the parameter of each model the file announces
-    double walls[4] = {0.0, 0.0, 0.0, 0.0};   // {south kind, south velocity, north kind, north velocity} of the file; none: no-slip
-    unsigned long long known = 3 | CKPT_WALLS | CKPT_SCHED;
-    for (const CollisionModel& m : collision_models) known |= m.ckpt_bit;
-    const bool head = fread(&h, sizeof(h), 1, fp) == 1;
-    const bool v1 = head && memcmp(h.magic, "LBMCKPT1", 8) == 0;
-    const bool v2 = head && memcmp(h.magic, "LBMCKPT2", 8) == 0 && fread(&digest, sizeof(digest), 1, fp) == 1;
-    bool v3 = head && memcmp(h.magic, "LBMCKPT3", 8) == 0 && fread(&flags, sizeof(flags), 1, fp) == 1 && (flags & ~known) == 0 &&
-              (!(flags & 1) || fread(&digest, sizeof(digest), 1, fp) == 1) && (!(flags & 2) || fread(&pdigest, sizeof(pdigest), 1, fp) == 1);
-    // (the parameters stand in the order of their bits: the models below the walls' bit, the walls, the schedule, then the models above)
-    auto read_params = [&](bool late) {
-        for (int i = 0; i < NM; ++i) {
-            const CollisionModel& m = collision_models[i];
-            if ((m.ckpt_bit > CKPT_SCHED) == late && (flags & m.ckpt_bit)) v3 = v3 && fread(param[i], sizeof(double), (size_t)m.nparam, fp) == (size_t)m.nparam;
-        }
-    };
-    read_params(false);
-    v3 = v3 && (!(flags & CKPT_WALLS) || fread(walls, sizeof(walls), 1, fp) == 1);
-    v3 = v3 && (!(flags & CKPT_SCHED) || fread(&sdigest, sizeof(sdigest), 1, fp) == 1);
-    read_params(true);
-    const bool f_mask = v2 || (v3 && (flags & 1)), f_prof = v3 && (flags & 2), f_walls = v3 && (flags & CKPT_WALLS), f_sched = v3 && (flags & CKPT_SCHED);
-    if (!v1 && !v2 && !v3) rc = fail(LBM_ERR_ARG, "%s is not a checkpoint", path);
-    else if ((rc = refuse_collision_mismatch(c, path, v3 ? flags : 0, param))) {}
-    else if (!f_walls && c->has_walls()) rc = fail(LBM_ERR_ARG, "checkpoint %s was written with two no-slip walls; this context has a %s south wall and a %s north wall",
-                                                   path, wall_kind_name(c->wall_kind[0]), wall_kind_name(c->wall_kind[1]));
-    else if (f_walls && !c->has_walls()) rc = fail(LBM_ERR_ARG, "checkpoint %s was written with wall kinds %g (south) and %g (north); this context has two no-slip walls",
-                                                   path, walls[0], walls[2]);
-    else if (f_walls && (walls[0] != (double)c->wall_kind[0] || walls[1] != c->wall_u[0] || walls[2] != (double)c->wall_kind[1] || walls[3] != c->wall_u[1]))
-        rc = fail(LBM_ERR_ARG, "checkpoint %s was written for different walls: south kind %g u = %.17g, north kind %g u = %.17g; this context has south kind %d u = %.17g, north kind %d u = %.17g",
-                  path, walls[0], walls[1], walls[2], walls[3], c->wall_kind[0], c->wall_u[0], c->wall_kind[1], c->wall_u[1]);
-    else if (!f_prof && c->has_profile) rc = fail(LBM_ERR_ARG, "checkpoint %s was written without an inlet profile; this context has one", path);
-    else if (f_prof && !c->has_profile) rc = fail(LBM_ERR_ARG, "checkpoint %s was written with an inlet profile; this context has none", path);
-    else if (f_prof && pdigest != c->prof_digest) rc = fail(LBM_ERR_ARG, "checkpoint %s was written for a different inlet profile", path);
-    else if (!f_sched && c->has_sched()) rc = fail(LBM_ERR_ARG, "checkpoint %s was written without an inlet schedule; this context has one", path);
-    else if (f_sched && !c->has_sched()) rc = fail(LBM_ERR_ARG, "checkpoint %s was written with an inlet schedule; this context has none", path);
-    else if (f_sched && sdigest != c->sched_digest) rc = fail(LBM_ERR_ARG, "checkpoint %s was written for a different inlet schedule", path);
-    else if (!f_mask && c->has_mask) rc = fail(LBM_ERR_ARG, "checkpoint %s was written without an obstacle mask; this context has one", path);
-    else if (f_mask && !c->has_mask) rc = fail(LBM_ERR_ARG, "checkpoint %s was written with an obstacle mask; this context has none", path);
-    else if (f_mask && digest != c->hmask.digest) rc = fail(LBM_ERR_ARG, "checkpoint %s was written for a different obstacle mask", path);
-    else if (h.nx != c->nx || h.ny != c->p.ny || h.y_start != c->p.y_start || h.local_ny != c->nyl ||
-             h.precision != c->p.precision || h.tau != c->p.tau || h.inlet_velocity != c->p.inlet_velocity ||
-             h.cylinder_x != c->p.cylinder_x || h.cylinder_y != c->p.cylinder_y || h.cylinder_radius != c->p.cylinder_radius)
-        rc = fail(LBM_ERR_ARG, "checkpoint %s was written for different parameters", path);
-    if (!rc) rc = DISPATCH(c, do_load<double>(c, fp, h.steps_done), do_load<float>(c, fp, h.steps_done));
+    unsigned char head[LBM_CKPT_HEAD_MAX];
+    lbm_ckpt_head file{};
+    int rc = accept_head(path, head, (int)fread(head, 1, sizeof(head), fp), ckpt_head_of(c), &file);      // (> 0: the bytes of the head)
+    if (rc > 0) rc = fseek(fp, rc, SEEK_SET) ? fail(LBM_ERR_ARG, "short read") : DISPATCH(c, transfer_interior<double>(c, fp, true), transfer_interior<float>(c, fp, true));
     fclose(fp);
     if (rc) return rc;
+    c->steps_done = file.steps_done;
+    c->restored = true;
     c->force_log.ix.reset(); c->body_log.ix.reset();
     c->last_was_pair = false;
     c->mid_pair = false;
     if ((c->comm || c->loopback) && c->group_n <= 1)   // (a group: lbm_group_refresh_halos once every member is restored)
         rc = DISPATCH(c, exchange_rccl<double>(c, c->cur, c->stream), exchange_rccl<float>(c, c->cur, c->stream));
     return rc;
+}
+
+int lbm_debug_ckpt_save(lbm_ckpt_head* h, const unsigned char* mask, const double* profile, const double* sched, int sched_n, int sched_mode,
+                        unsigned char* out, int cap) {
+    if (!h || !out || cap < LBM_CKPT_HEAD_MAX) return fail(LBM_ERR_ARG, "lbm_debug_ckpt_save: a head and %d bytes for it", LBM_CKPT_HEAD_MAX);
+    if ((mask && (h->nx < 1 || h->ny < 1)) || (profile && h->ny < 1) || (sched && sched_n < 1)) return fail(LBM_ERR_ARG, "lbm_debug_ckpt_save: data without a size");
+    if (mask) { h->has_mask = 1; h->mask_digest = mask_digest(mask, h->nx, h->ny); }
+    if (profile) { h->has_profile = 1; h->profile_digest = profile_digest(profile, h->ny); }
+    if (sched) { h->has_sched = 1; h->sched_digest = schedule_digest(sched, sched_n, sched_mode); }
+    return ckpt_serialise(*h, out);
+}
+
+int lbm_debug_ckpt_load(const unsigned char* bytes, int n, const lbm_ckpt_head* here, const char* path, int* consumed_out) {
+    if (!bytes || n < 0 || !here || !path) return fail(LBM_ERR_ARG, "lbm_debug_ckpt_load: null argument");
+    lbm_ckpt_head file{};
+    const int rc = accept_head(path, bytes, n, *here, &file);
+    if (consumed_out) *consumed_out = rc > 0 ? rc : 0;
+    return rc > 0 ? LBM_OK : rc;
 }
 
 int lbm_set_option(lbm_ctx* c, const char* key, long value) {

@@ -47,7 +47,8 @@ constexpr bool PARK_LES = true, PARK_TRT = true;
 // two objects are BGK's alone (lbm_col.hip -DLBM_COL_TALL), so no forced instantiation of them exists to meet the bar.
 constexpr bool PARK_FORCED = true;
 // `nparam`: the doubles of the model's parameter (the force has two components; lbm_ctx::collision_param, collision_param2). A model whose
-// ckpt_bit lies above the bits of the walls and the inlet schedule stands behind them in a checkpoint, as its bit says.
+// ckpt_bit lies above the bits of the walls and the inlet schedule stands behind them in a checkpoint, as its bit says
+// (lbm_ckpt.hpp makes one row of its field table from each model that has a bit).
 struct CollisionModel { int base; const char* noun; bool tall, park; unsigned long long ckpt_bit; const char *param, *value, *none; int nparam = 1; };
 constexpr CollisionModel collision_models[] = {
     {AR_STRICT, "BGK", true, true, 0, "", "", ""},
@@ -60,6 +61,12 @@ constexpr const CollisionModel& collision_model(int arith) {
     for (const CollisionModel& m : collision_models)
         if (m.base == (arith & ~1)) return m;
     return collision_models[0];
+}
+// a model's parameter as messages print it: one number, or the pair of a model with two (nparam)
+inline std::string param_text(const CollisionModel& m, double v, double v2, const char* fmt = "%g") {
+    char a[40], b[40];
+    snprintf(a, sizeof(a), fmt, v); snprintf(b, sizeof(b), fmt, v2);
+    return m.nparam == 2 ? std::string("(") + a + ", " + b + ")" : std::string(a);
 }
 
 struct PlanQuery {

@@ -259,7 +259,7 @@ int  lbm_set_solid_mask(lbm_ctx* c, const unsigned char* mask, int nx, int ny);
  * then the inlet; solid inlet cells are skipped; interior fluid cells of row y start at f_eq(1, (u[y], 0)) (evaluated on the host in
  * double, in the reference's bracket order), solid cells and the ghost frame as before; lbm_get_macros reports (rho_bc, u[y], 0) on
  * the inlet column and ux = u[y] in the initial snapshot. inlet_velocity then only names the run (checkpoint header, the
- * caller's Reynolds number). Checkpoints carry the profile's digest (lbm_save_state: magic "LBMCKPT3").
+ * caller's Reynolds number). Checkpoints carry the profile's digest (lbm_save_state: magic "LBMCKPT3", flag bit 1).
  * LBM_ERR_ARG: null pointer, ny other than the domain's, an initialised context, or a value that is not finite or is >= 1 (the
  * inlet divides by 1 - u). */
 int  lbm_set_inlet_profile(lbm_ctx* c, const double* u, int ny);
@@ -282,9 +282,8 @@ int  lbm_set_inlet_profile(lbm_ctx* c, const double* u, int ny);
  * Call after lbm_create and before lbm_initialise, in either order with lbm_set_inlet_profile: the plan is measured with the schedule
  * set. n == 0 clears the schedule. Every strip of a run is given the same schedule. The schedule changes no launch, no row range and no
  * exchange, and without one every result, kernel name, checkpoint byte and dry-run record is what it was without this call.
- * Checkpoints of a context with a schedule carry its digest (lbm_save_state: magic "LBMCKPT3", flag bit 5, a 64-bit digest of {mode, n,
- * the n doubles} behind the walls) and load only into a context with an equal schedule; the iteration counter of the file positions
- * the schedule after a restart.
+ * Checkpoints of a context with a schedule carry its digest (lbm_save_state: magic "LBMCKPT3", flag bit 5) and load only into
+ * a context with an equal schedule; the iteration counter of the file positions the schedule after a restart.
  * LBM_ERR_ARG (the text names the offender, entry index included): a null context, an initialised context, n < 0 or
  * n > LBM_INLET_SCHEDULE_MAX, a null `s` with n > 0, a mode outside 0..1, an entry that is not finite. lbm_initialise, which knows
  * profile and schedule, fails with LBM_ERR_ARG naming row and entry unless u[y] * s[k] < 1 for every row and entry (the inlet divides by
@@ -347,8 +346,8 @@ int  lbm_set_trt(lbm_ctx* c, double magic);
  * boundary rules prescribe their velocity and density as they do without one, and bounce-back is not force-corrected).
  * Call after lbm_create and before lbm_initialise, like lbm_set_trt: the plan is then measured on the forced kernels (Arith values
  * 8 / 9; no fp32 deep=8 plan: pinning it fails). Every strip of a run is given the same values. (0, 0) clears the model (the BGK
- * kernels). Checkpoints carry the force (lbm_save_state: magic "LBMCKPT3", flag bit 6, two doubles {fx, fy} behind everything the
- * lower bits carry) and load only into a context with an equal one.
+ * kernels). Checkpoints carry the force (lbm_save_state: magic "LBMCKPT3", flag bit 6) and load only into a context with an
+ * equal one.
  * LBM_ERR_ARG (the text names the offender): a null context, an initialised context, a component that is not finite or has
  * magnitude >= 1, or a nonzero force on a context with a Smagorinsky constant or a TRT magic parameter — and either of those on a
  * context with a force: the collisions cannot be combined. */
@@ -377,8 +376,8 @@ int  lbm_get_forcing(const lbm_ctx* c, double* fx, double* fy);
  * change no launch and no row range: forces, body forces, the halo exchange and the dry-run choreography (lbm_debug_choreography) are
  * untouched, and with kind 0 on both walls every result, kernel name and checkpoint byte is what it was without this call.
  * `velocity` is read for LBM_WALL_MOVING only and must be 0 for the other kinds; setting LBM_WALL_NOSLIP clears a wall. Checkpoints
- * carry both walls where either is not no-slip (lbm_save_state: magic "LBMCKPT3", flag bit 4, four doubles {south kind, south
- * velocity, north kind, north velocity} behind the collision parameters) and load only into a context with equal walls.
+ * carry both walls where either is not no-slip (lbm_save_state: magic "LBMCKPT3", flag bit 4) and load only into a context with equal
+ * walls.
  * LBM_ERR_ARG (the text names the offender): a null context, an initialised context, side outside 0..1, kind outside 0..2, a
  * velocity that is not finite or has |velocity| >= 1, a nonzero velocity with kind 0 or 1. */
 #define LBM_WALL_SOUTH 0
@@ -484,9 +483,10 @@ int  lbm_halo_import(lbm_ctx* c, const double* south_in, const double* north_in)
 /* Checkpoint / restart (the reference has none): the strip's post-collision populations and the
  * iteration counter. lbm_load_state needs an initialised context created with the same parameters; the macro /
  * population snapshots become available again after the next lbm_step. A file written with an obstacle mask, an inlet
- * profile, a Smagorinsky constant, a TRT magic parameter, a wall that is not no-slip (lbm_set_wall) or an inlet schedule
- * (lbm_set_inlet_schedule) loads only into a context with the same mask, profile, constant, parameter, walls and schedule (the failure
- * names which one differs). */
+ * profile, a Smagorinsky constant, a TRT magic parameter, a force (lbm_set_forcing), a wall that is not no-slip (lbm_set_wall) or an
+ * inlet schedule (lbm_set_inlet_schedule) loads only into a context with the same mask, profile, constant, parameter, force, walls and
+ * schedule (the failure names which one differs). The file format, and the order in which differences are named: the comment at the
+ * head of csrc/lbm_ckpt.hpp. */
 int  lbm_save_state(lbm_ctx* c, const char* path);
 int  lbm_load_state(lbm_ctx* c, const char* path);
 
@@ -571,6 +571,28 @@ int lbm_debug_wall_rule(int side, int kind, double velocity, int precision, cons
  * snapshot call (csrc/lbm_kernels.hpp inlet_sched_index), compiled for the host. The argument errors of lbm_set_inlet_schedule, and
  * LBM_ERR_ARG for n == 0, a null pointer, an unknown precision or a negative iteration. */
 int lbm_debug_inlet_scale(const double* s, int n, int mode, int precision, const int* t, int nt, double* out);
+/* What the head of a checkpoint says about a run (csrc/lbm_ckpt.hpp, which also describes the file): the fixed header, then for each
+ * optional field whether the run has it and its value. has_*: 0 or 1; collision: 0, or the setter's model as lbm_ctx holds it (2 Smagorinsky,
+ * 4 TRT, 8 forcing) with collision_param = {Cs}, {magic} or {fx, fy}; walls = {south kind, south velocity, north kind, north velocity}. */
+typedef struct lbm_ckpt_head {
+    int nx, ny, y_start, local_ny, precision, steps_done;
+    double tau, inlet_velocity, cylinder_x, cylinder_y, cylinder_radius;
+    int has_mask, has_profile, collision, has_walls, has_sched;
+    unsigned long long mask_digest, profile_digest, sched_digest;
+    double collision_param[2];
+    double walls[4];
+} lbm_ckpt_head;
+#define LBM_CKPT_HEAD_MAX 176   /* bytes: no head is longer */
+/* Test hook, callable without a device: the head lbm_save_state writes for a context that *h describes, through the function it calls,
+ * into out (cap >= LBM_CKPT_HEAD_MAX); returns its length. Where mask ([h->ny][h->nx] bytes), profile (h->ny doubles) or sched (sched_n
+ * doubles, sched_mode) is not NULL, that field is marked present and its digest is formed as lbm_set_solid_mask, lbm_set_inlet_profile,
+ * lbm_set_inlet_schedule form it, and left in *h. LBM_ERR_ARG: a null head or buffer, cap too small, data without a size. */
+int lbm_debug_ckpt_save(lbm_ckpt_head* h, const unsigned char* mask, const double* profile, const double* sched, int sched_n, int sched_mode,
+                        unsigned char* out, int cap);
+/* Test hook, callable without a device: what lbm_load_state decides, through the functions it calls, about a file `path` that begins with
+ * the n bytes `bytes`, on a context that *here describes: LBM_OK and in *consumed_out (nullable) the bytes of the head, behind which the
+ * populations stand; or LBM_ERR_ARG with lbm_last_error() as lbm_load_state words it: "<path> is not a checkpoint", or the refusal. */
+int lbm_debug_ckpt_load(const unsigned char* bytes, int n, const lbm_ckpt_head* here, const char* path, int* consumed_out);
 /* Test hook, callable without a device: what the ranks of a strip run agree on before the collective schedule trials of
  * lbm_initialise (csrc/lbm_hip.hip tune_strip_schedule). per_rank7 = nranks x {may tune, overlap pinned, overlap, deep_halo pinned,
  * deep_halo, halo_trim pinned, halo_trim}; agreed7 = the same seven as agreed (-1 where nothing is pinned). LBM_ERR_ARG when the ranks pin different

@@ -1,10 +1,11 @@
 // tools/sanitize_driver.cpp — the host-side logic that runs WITHOUT a GPU (the group threads' rendezvous with its error and time-out paths,
-// the dry run of the strip choreography and its checker, the stacking arithmetic of the group gathers) under ThreadSanitizer and AddressSanitizer + UBSan: tools/sanitize_host.sh.
+// the dry run of the strip choreography and its checker, the stacking arithmetic of the group gathers, the parser of the checkpoint head) under ThreadSanitizer and AddressSanitizer + UBSan: tools/sanitize_host.sh.
 // (GPU AddressSanitizer is not available on this pool; the device code is covered by the parity tests.)
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
 #include <vector>
+#include "../include/lbm_hip.h"      // (lbm_ckpt_head and its two hooks)
 extern "C" {
 int lbm_debug_group_pool(int n, int rounds, int fail_strip, int fail_round, int stall_strip, int stall_round, int stall_ms, long timeout_ms, int repeat, int* rendezvous_out);
 int lbm_debug_choreography(int nx, int ny, const int* bounds2, int nstrips, int precision, int transport, const char* options, const int* calls2, int ncalls, int dump, char* out, int cap);
@@ -46,6 +47,51 @@ static int gather_cases() {
     run(4, 3, ny, 1, 5, (size_t)nx * 5, 0, 0.0);
     return bad;
 }
+// The head of a checkpoint (csrc/lbm_ckpt.hpp) through lbm_debug_ckpt_save / lbm_debug_ckpt_load, every input an exactly-sized heap copy (a
+// read past a truncated head is a heap-buffer-overflow): the 64 described runs — mask x profile x walls x schedule x {BGK, LES, TRT,
+// forced}. Each head must load into its own description and take all its bytes; cut at every shorter length it must be refused with
+// nothing taken; with any byte of its flag word set to any other value (fields announced that the bytes do not hold, unknown bits, two
+// collision models) it must be refused. Then the digests from exactly-sized data. Returns the cases whose result is wrong.
+static int ckpt_cases(int* cases_out) {
+    int bad = 0, cases = 0;
+    const int bases[4] = {0, 2, 4, 8};
+    for (int k = 0; k < 64; ++k) {
+        lbm_ckpt_head h{};
+        h.nx = 128; h.ny = 32; h.local_ny = 32; h.steps_done = 11; h.tau = 0.6; h.inlet_velocity = 0.05;
+        h.cylinder_x = 0.2; h.cylinder_y = 0.5; h.cylinder_radius = 0.125;
+        h.has_mask = k & 1; h.has_profile = (k >> 1) & 1; h.has_walls = (k >> 2) & 1; h.has_sched = (k >> 3) & 1; h.collision = bases[k >> 4];
+        h.mask_digest = 0x0123456789abcdefull; h.profile_digest = 0xfedcba9876543210ull; h.sched_digest = 0x0f1e2d3c4b5a6978ull;
+        h.collision_param[0] = 0.17; h.collision_param[1] = -2.5e-6;
+        h.walls[0] = 2.0; h.walls[1] = 0.05; h.walls[2] = 1.0;
+        unsigned char full[LBM_CKPT_HEAD_MAX];
+        const int n = lbm_debug_ckpt_save(&h, nullptr, nullptr, nullptr, 0, 0, full, (int)sizeof(full));
+        if (n < 72) { ++bad; continue; }
+        for (int len = 1; len <= n; ++len, ++cases) {
+            const std::vector<unsigned char> cut(full, full + len);
+            int used = -1;
+            const int rc = lbm_debug_ckpt_load(cut.data(), len, &h, "x.ckpt", &used);
+            if (len == n ? (rc != 0 || used != n) : (rc != -1 || used != 0 || !strstr(lbm_last_error(), "is not a checkpoint"))) ++bad;
+        }
+        for (int b = 72; full[7] == '3' && b < 80; ++b)
+            for (int v = 0; v < 256; ++v) {
+                if (full[b] == v) continue;
+                std::vector<unsigned char> p(full, full + n);
+                p[b] = (unsigned char)v;
+                ++cases;
+                if (lbm_debug_ckpt_load(p.data(), n, &h, "x.ckpt", nullptr) != -1) ++bad;
+            }
+    }
+    lbm_ckpt_head h{};
+    h.nx = 7; h.ny = 5; h.local_ny = 5;
+    const std::vector<unsigned char> mask(35, 1);
+    const std::vector<double> profile(5, 0.03), sched(3, 0.5);
+    std::vector<unsigned char> out(LBM_CKPT_HEAD_MAX);
+    const int n = lbm_debug_ckpt_save(&h, mask.data(), profile.data(), sched.data(), 3, 1, out.data(), (int)out.size());
+    bad += n != 72 + 8 + 3 * 8 || !h.has_mask || !h.has_profile || !h.has_sched;
+    bad += lbm_debug_ckpt_save(&h, nullptr, nullptr, nullptr, 0, 0, out.data(), (int)out.size() - 1) != -1;      // a buffer too small is refused
+    *cases_out = cases + 2;
+    return bad;
+}
 int main() {
     int passed = 0;
     int rc = lbm_debug_group_pool(8, 2000, -1, -1, -1, -1, 0, 0, 3, &passed);
@@ -79,5 +125,8 @@ int main() {
         }
     printf("p2p matching: %d eight-rank dry runs, %d mismatching or failed\n", runs2, bad2);
     printf("group gathers: 6 cases through lbm_debug_gather, %d wrong\n", gather_cases());
-    return 0;
+    int ncases = 0;
+    const int wrong = ckpt_cases(&ncases);
+    printf("checkpoint heads: %d cases through lbm_debug_ckpt_save / lbm_debug_ckpt_load, %d wrong\n", ncases, wrong);
+    return wrong != 0;      // (the script fails on a nonzero exit code)
 }

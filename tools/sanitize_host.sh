@@ -1,8 +1,8 @@
 #!/bin/bash
 # Usage (CPU only, from the repo root): tools/sanitize_host.sh OUTFILE
 # Builds the host translation unit of the library with -fsanitize=thread and with -fsanitize=address,undefined (host code only: -Xarch_host)
-# and runs tools/sanitize_driver.cpp against each: the GroupPool rendezvous (clean, injected error, time-out) and a sample of choreography
-# dry runs. Any sanitizer report fails the run. ~4 minutes (two extra builds of lbm_hip.hip + every kernel object of build.py's unit list).
+# and runs tools/sanitize_driver.cpp against each: the GroupPool rendezvous (clean, injected error, time-out) a sample of choreography
+# dry runs, the group gathers and the checkpoint head (every head cut at every length, every flag byte perturbed). Any sanitizer report fails the run. ~4 minutes (two extra builds of lbm_hip.hip + every kernel object of build.py's unit list).
 set -e
 ROOT=$PWD
 PKG=$ROOT/highperformancecomputing-latticeboltzmannmethod_amd
