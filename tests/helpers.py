@@ -132,8 +132,9 @@ ORACLE_PLANS = ["rowil-site-nt", "planar-fuse3-8", "rowil-deep6-nt", "rowil-col5
 
 
 def strict(plan):
-    """True when the plan evaluates the oracle's operation sequence (populations bit-identical to it)."""
-    return plan not in FAST
+    """True when the plan evaluates the oracle's operation sequence (populations bit-identical to it). `plan`: a key of PLANS, or,
+    for a pinned plan that is none, its arithmetic mode (option "arith": 0 strict, 1 contracted)."""
+    return plan == 0 if isinstance(plan, int) else plan not in FAST
 
 
 # ---- masks and files -------------------------------------------------------------------------------------------------------------
@@ -162,6 +163,15 @@ def masks(nx, ny):
     out["ragged-last-column"] = m
     out["random20"] = (np.random.default_rng(1234).random((ny, nx)) < 0.2).astype(np.uint8)
     return out
+
+
+def every_row_differs(ny, mean):
+    """An inlet profile with a different velocity on every row, of mean `mean`."""
+    y = np.arange(ny)
+    s = (y + 0.5) / ny
+    u = (0.4 + s * (1 - s)) * (1.0 + 0.3 * np.sin(1.7 * y))
+    assert len(set(u.tolist())) == ny
+    return u * (mean / np.mean(u))
 
 
 def write_pgm(path, cells, maxval=255):

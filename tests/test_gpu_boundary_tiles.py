@@ -21,7 +21,8 @@ import functools
 import numpy as np
 import pytest
 
-from tests.helpers import (CtxRun, assert_group_is_whole, assert_same_results, golden_params, lbm_gpu, load_golden, masks)  # noqa: F401
+from tests.helpers import (CtxRun, assert_group_is_whole, assert_same_results, every_row_differs, golden_params, lbm_gpu, load_golden,  # noqa: F401
+                           masks)
 from tests.reference import FREESLIP, moving
 
 pytestmark = pytest.mark.gpu
@@ -42,14 +43,6 @@ def corners_and_edges(nx, ny):
         out[oh - 1:oh + 1, ow - 1:ow + 1] = 1
         out[2 * oh - 1:2 * oh + 1, 3 * ow - 1] = 1
     return out
-
-
-def every_row_differs(ny, mean):
-    y = np.arange(ny)
-    s = (y + 0.5) / ny
-    u = (0.4 + s * (1 - s)) * (1.0 + 0.3 * np.sin(1.7 * y))
-    assert len(set(u.tolist())) == ny
-    return u * (mean / np.mean(u))
 
 
 def case_kw(name):

@@ -20,7 +20,7 @@ import functools
 import numpy as np
 import pytest
 
-from tests.helpers import CtxRun, lbm_gpu  # noqa: F401
+from tests.helpers import CtxRun, every_row_differs, lbm_gpu  # noqa: F401
 from tests.reference import FREESLIP, moving
 
 pytestmark = pytest.mark.gpu
@@ -31,13 +31,6 @@ IDS = (10, 11)
 WALKS = (dict(nt=1, ntl=0, alternate=0, split=0), dict(nt=0, ntl=1, alternate=1, split=3, split_min=1))
 CALLS = ((20, 0), (13, 5))
 KERNEL = "k_stepc_col<double,5,8,"
-
-
-def every_row_differs(ny, mean):
-    y = np.arange(ny)
-    s = (y + 0.5) / ny
-    u = (0.4 + s * (1 - s)) * (1.0 + 0.3 * np.sin(1.7 * y))
-    return u * (mean / np.mean(u))
 
 
 def single_cells(nx, ny):
