@@ -29,7 +29,7 @@
 //                                registers: the production kernel of large grids and tall strips
 //   k_init, k_macros, k_forces, k_halo_pack/unpack   set-up and the output cadence
 // The fused kernels share the per-cell rule (cell_update / cell_update_last over bcs_at) and the block prologue (TileFrame);
-// k_step3_tile and k_step4_tile are one body (step_tile) at depth 3 and 4.
+// k_step3_tile, k_step4_tile and k_stepd_tile are one body (step_tile) at depth 3, 4 and 6..8.
 // Arithmetic modes of the collision (enum Arith): strict IEEE operation by operation (bit-identical to the CPU oracle)
 // or FMA-contracted with one reciprocal (what the reference's -ffast-math -mfma build permits; <= 1e-10).
 //
@@ -867,120 +867,6 @@ __global__ void __launch_bounds__(NTH) k_step2_tile(const KArgs<T> a, const K2Ex
     if (bad) atomicMin(a.unstable_t, *a.t_base + a.t + 1);
 }
 
-// Three / four iterations per launch (D = 3 / 4): the same idea one / two levels deeper, the LDS image reused in place:
-//   level 1      region 1 = tile + HW = D-1 rings: P_{t+1} from global P_t into LDS (9*(TY+2HW)*(TX+2HW)*sizeof(T): 78 KB at
-//                64x12 fp64 for D = 3, two blocks of 1024 threads per CU = all 32 wave slots, the lean path needs 48 VGPRs; 70.5 KB at 64x8 fp64, 35 KB fp32 for D = 4);
-//   levels 2..D-1  region L = region 1 shrunk by L-1 rings, in place: every thread first pulls its (<= 2) cells' nine values
-//                from LDS into registers, barrier, then computes the next state and writes it IN PLACE (no second LDS image);
-//   level D      the tile: pull from LDS, BCs, collide, store P_{t+D}.
-// HBM traffic per update ~ (1 + (TX+2HW)(TY+2HW)/(TX TY)) * 72/D B (fp64: 58 B at 64x12, D = 3); redundant collisions 1.21x
-// (64x12, D = 3) / 1.45x (64x8, D = 4) — D = 4 is worth it where the three-iteration kernel is close to the memory roof (fp32).
-// Bit-identical to D single launches (tests). Rows of neighbouring strips must be present D deep beyond the rows written, so
-// strips (six rows per exchange = 2 x 3) never use D = 4; the plan measurement decides elsewhere.
-template <typename T, int TY, int NTH, int D, int AR>
-__device__ __forceinline__ void step_tile(const KArgs<T>& a, const K2Extra<T>& e) {
-    constexpr int TX = 64, HW = D - 1, R1W = TX + 2 * HW, R1H = TY + 2 * HW, LP = R1W;
-    static_assert((R1W - 2) * (R1H - 2) <= 2 * NTH, "two cells per thread at most in the in-place levels");
-    __shared__ T lds[Q][R1H][LP];
-    const TileFrame<T> fr = tile_frame(a, e, TX, TY, HW);
-    const int X0 = fr.X0, Y0 = fr.Y0, y_end = fr.y_end;
-    // The whole tile twice: LEAN (fr.lean) or general; a block takes one of the two (block-uniform)
-    auto run = [&]<bool LEAN>() {
-        bool bad = false;
-#pragma unroll
-        for (int r = threadIdx.x; r < R1W * R1H; r += NTH) {                 // level 1 on region 1: iteration t
-            const int ry = r / R1W, rx = r - ry * R1W;
-            T f[Q];
-            if (LEAN) {
-                fr.load(f, fr.at(ry, rx), fr.src_off(a, Y0 - HW, X0 - HW));
-                bad |= any_unstable(f);
-                collide<T, AR>(f, a);
-            } else {
-                const int x = X0 + rx - HW, y = Y0 + ry - HW;
-                const int yg = a.y_start + y;
-                const bool row_in = (yg >= 0 && yg < a.ny_glob), col_in = (x >= 0 && x < a.nx);
-                if (!(row_in && col_in) || y > y_end + HW - 1) {
-#pragma unroll
-                    for (int i = 0; i < Q; ++i) f[i] = outside_value(e, row_in, col_in, i);
-                } else {
-                    const long c = (long)(y + GR) * a.pitch + a.xoff + x;
-#pragma unroll
-                    for (int i = 0; i < Q; ++i) f[i] = a.src[(long)i * a.plane + c - (long)cy(i) * a.pitch - cx(i)];
-                    cell_update<T, AR>(a, f, x, yg, 0, fr.near_solid, true, bad);
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < Q; ++i) lds[i][ry][rx] = f[i];
-        }
-        if (bad) atomicMin(a.unstable_t, *a.t_base + a.t);
-        __syncthreads();
-        auto in_place = [&]<int L>() {                                        // level L on region L, in place
-            constexpr int O = L - 1, RW = R1W - 2 * O, RH = R1H - 2 * O;
-            T g[2][Q];
-            int cell[2];
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                const int r = (int)threadIdx.x + k * NTH;
-                cell[k] = (r < RW * RH) ? r : -1;
-                if (cell[k] >= 0) {
-                    const int ry = r / RW + O, rx = r - (r / RW) * RW + O;    // LDS coordinates of the cell
-#pragma unroll
-                    for (int i = 0; i < Q; ++i) g[k][i] = lds[i][ry - cy(i)][rx - cx(i)];
-                }
-            }
-            __syncthreads();
-            bool badl = false;
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                if (cell[k] < 0) continue;
-                const int r = cell[k];
-                const int ry = r / RW + O, rx = r - (r / RW) * RW + O;
-                const int x = X0 + rx - HW, y = Y0 + ry - HW;
-                const int yg = a.y_start + y;
-                const bool row_in = (yg >= 0 && yg < a.ny_glob), col_in = (x >= 0 && x < a.nx);
-                T f[Q];
-                if (!LEAN && !(row_in && col_in)) {
-#pragma unroll
-                    for (int i = 0; i < Q; ++i) f[i] = outside_value(e, row_in, col_in, i);
-                } else {
-#pragma unroll
-                    for (int i = 0; i < Q; ++i) f[i] = g[k][i];
-                    if (LEAN) {
-                        badl |= any_unstable(f);
-                        collide<T, AR>(f, a);
-                    } else cell_update<T, AR>(a, f, x, yg, L - 1, fr.near_solid, y <= y_end + HW - L, badl);
-                }
-#pragma unroll
-                for (int i = 0; i < Q; ++i) lds[i][ry][rx] = f[i];
-            }
-            if (badl) atomicMin(a.unstable_t, *a.t_base + a.t + L - 1);
-            __syncthreads();
-        };
-        [&]<int... Ls>(std::integer_sequence<int, Ls...>) { (in_place.template operator()<Ls + 2>(), ...); }(std::make_integer_sequence<int, D - 2>{});
-        bad = false;
-        for (int o = threadIdx.x; o < TX * TY; o += NTH) {                    // level D on the tile: iteration t+D-1
-            const int ly = o / TX, lx = o - ly * TX;
-            const int x = X0 + lx, y = Y0 + ly;
-            if (!LEAN && (y >= y_end || x >= a.nx)) continue;
-            T f[Q];
-#pragma unroll
-            for (int i = 0; i < Q; ++i) f[i] = lds[i][ly + HW - cy(i)][lx + HW - cx(i)];
-            if (LEAN) {
-                bad |= any_unstable(f);
-                collide<T, AR>(f, a);
-                fr.store(f, fr.at(ly, lx), fr.dst_off(a, Y0, X0), e.nt != 0);
-            } else if (cell_update_last<T, AR>(a, f, x, a.y_start + y, D - 1, fr.near_solid, bad)) store_cell(a, f, x, y, e.nt != 0);
-        }
-        if (bad) atomicMin(a.unstable_t, *a.t_base + a.t + D - 1);
-    };
-    if (fr.lean) run.template operator()<true>();
-    else run.template operator()<false>();
-}
-template <typename T, int TY, int NTH, int AR = AR_STRICT>
-__global__ void __launch_bounds__(NTH, (2 * NTH / 256)) k_step3_tile(const KArgs<T> a, const K2Extra<T> e) { step_tile<T, TY, NTH, 3, AR>(a, e); }
-template <typename T, int TY, int NTH, int AR = AR_STRICT>
-__global__ void __launch_bounds__(NTH, (2 * NTH / 256)) k_step4_tile(const KArgs<T> a, const K2Extra<T> e) { step_tile<T, TY, NTH, 4, AR>(a, e); }
-
 // In-kernel phase record (tools/colbench -DLBM_COL_PROF only; never in the library): lane 0 of every wave writes the 100 MHz
 // real-time counter at the marks below, plus HW_ID / XCC_ID, so that the host can lay the blocks of one CU side by side (profiles/r04).
 #ifdef LBM_COL_PROF
@@ -1011,40 +897,41 @@ __device__ __forceinline__ void prof_ids(int blk, int nw, int w) {
 #define LBM_PROF_IDS(blk, nw, w) do {} while (0)
 #endif
 
-// D iterations per launch (D = 6..8) on a TX x TY tile: k_step4_tile generalised — level 1 from HBM into an LDS image of the
-// (TX + 2(D-1)) x (TY + 2(D-1)) region, levels 2..D-1 in place (pull into registers, barrier, compute, overwrite, barrier),
-// level D the tile -> HBM, on 64x16 / 32x32 tiles of 1024 threads: for grids so small that one launch is a single round of
-// blocks. There the chip runs load -> compute -> store in lockstep, so the two memory phases are paid per LAUNCH: fusing more
-// iterations divides them, at the price of ~1.5x redundant collisions that such a grid has VALU time to spare for.
-// (Round 2's production shape — 32x16 tiles, 512 threads, D = 5/6, two blocks per CU: 125-130 GLUPS at 4096x1024 fp64 — is
-// superseded by k_stepc_col, which keeps the same region in registers instead of LDS, and is no longer built.)
-// Whole-domain launches only (rows outside the domain hold the permanent ghost values; a strip is refreshed six rows deep per single launch).
-// waves per SIMD the register allocation may assume: as many blocks as the LDS image allows on a CU (at most 32 waves)
-template <typename T, int TX, int TY, int D>
-constexpr int deep_waves_per_simd() {
-    const int lds = (int)sizeof(T) * Q * (TX + 2 * (D - 1)) * (TY + 2 * (D - 1)), waves = TX * TY / 64;
-    int blocks = 160 * 1024 / lds;
-    if (blocks * waves > 32) blocks = 32 / waves;
-    return (blocks * waves) / 4 > 0 ? (blocks * waves) / 4 : 1;
-}
-template <typename T, int TX, int TY, int D, int AR = AR_STRICT>
-__global__ void __launch_bounds__(TX * TY, (deep_waves_per_simd<T, TX, TY, D>())) k_stepd_tile(const KArgs<T> a, const K2Extra<T> e) {
-    constexpr int NTH = TX * TY, HW = D - 1, R1W = TX + 2 * HW, R1H = TY + 2 * HW, LP = R1W;
-    static_assert(D >= 3 && (NTH == 1024 || NTH == 512 || NTH == 256), "one tile cell per thread at the last level");
-    static_assert((TX & (TX - 1)) == 0, "cell_xy splits an index with a mask");
+// D >= 3 iterations per launch on a TX x TY tile of NTH threads: k_step2_tile's idea D - 2 levels deeper, the LDS image reused in place.
+// One body for k_step3_tile, k_step4_tile and k_stepd_tile (below, each with its shapes and what was measured on them):
+//   level 1        region 1 = tile + HW = D-1 rings: P_{t+1} from global P_t into an LDS image of (TX+2HW) x (TY+2HW) cells;
+//   levels 2..D-1  region L = region 1 shrunk by L-1 rings, in place: every thread first pulls the nine values of its cells
+//                  (ceil(cells / NTH) of them) from LDS into registers, barrier, then computes the next state and writes it
+//                  IN PLACE (no second LDS image), barrier;
+//   level D        the tile: pull from LDS, BCs, collide, store P_{t+D}.
+// A region cell outside the domain, or in a row that no output of this launch needs (beyond y_end + HW - L at level L), takes or
+// keeps a ghost value and is not counted by the stability test. A block runs the whole tile either LEAN (TileFrame) or general.
+// HBM traffic per update ~ (1 + (TX+2HW)(TY+2HW)/(TX TY)) * 72/D B (fp64). Bit-identical to D single launches (tests). Rows of
+// neighbouring strips must be present D deep beyond the rows written.
+// TILE_FIRST chooses how the cells of a region are dealt to the threads (cell_xy).
+template <typename T, int TX, int TY, int NTH, int D, int AR, bool TILE_FIRST>
+__device__ __forceinline__ void step_tile(const KArgs<T>& a, const K2Extra<T>& e) {
+    constexpr int HW = D - 1, R1W = TX + 2 * HW, R1H = TY + 2 * HW, LP = R1W;
+    static_assert(D >= 3, "level 1, at least one in-place level, the last level");
+    static_assert(!TILE_FIRST || (TX & (TX - 1)) == 0, "the tile-first cell_xy splits an index with a mask");
     static_assert((size_t)Q * R1H * LP * sizeof(T) <= 160 * 1024, "level-1 region must fit the CU's LDS");
     __shared__ T lds[Q][R1H][LP];
-    // Cell r of the region at ring offset O (rows and columns [O, R1 - O) of the LDS image) -> its LDS coordinates. The TX
-    // columns above the tile come first, row by row: a half-wave then covers one aligned run of 32 cells (no LDS bank
-    // conflict, whole cache lines at level 1) instead of a region row that wraps somewhere inside it; the 2 x (HW - O) halo
-    // columns of every row follow.
+    // Cell r of the region at ring offset O (rows and columns [O, R1 - O) of the LDS image) -> its LDS coordinates.
     auto cell_xy = [&]<int O>(int r, int& ry, int& rx) {
-        constexpr int RH = R1H - 2 * O, HALO = HW - O, NC = RH * TX;
-        if (HALO == 0 || r < NC) { ry = O + r / TX; rx = HW + (r & (TX - 1)); }
-        else {
-            const int h = r - NC, q = h / (2 * HALO), c = h - q * (2 * HALO);
-            ry = O + q;
-            rx = c < HALO ? O + c : HW + TX + (c - HALO);
+        if constexpr (!TILE_FIRST) {                      // row-major over the region
+            constexpr int RW = R1W - 2 * O;
+            ry = O + r / RW; rx = O + r - (r / RW) * RW;
+        } else {
+            // The TX columns above the tile come first, row by row: a half-wave then covers one aligned run of 32 cells (no LDS
+            // bank conflict, whole cache lines at level 1) instead of a region row that wraps somewhere inside it; the
+            // 2 x (HW - O) halo columns of every row follow.
+            constexpr int RH = R1H - 2 * O, HALO = HW - O, NC = RH * TX;
+            if (HALO == 0 || r < NC) { ry = O + r / TX; rx = HW + (r & (TX - 1)); }
+            else {
+                const int h = r - NC, q = h / (2 * HALO), c = h - q * (2 * HALO);
+                ry = O + q;
+                rx = c < HALO ? O + c : HW + TX + (c - HALO);
+            }
         }
     };
     const TileFrame<T> fr = tile_frame(a, e, TX, TY, HW);
@@ -1085,8 +972,12 @@ __global__ void __launch_bounds__(TX * TY, (deep_waves_per_simd<T, TX, TY, D>())
         if (bad) atomicMin(a.unstable_t, *a.t_base + a.t);
         LBM_PROF(pb, NTH / 64, pw, 1);
         __syncthreads();
-        auto in_place = [&]<int L>() {                                        // level L on region L = region 1 shrunk by L-1 rings
-            constexpr int O = L - 1, RW = R1W - 2 * O, RH = R1H - 2 * O, CPT = (RW * RH + NTH - 1) / NTH;
+        auto in_place = [&]<int L>() {                                        // level L on region L, in place
+            constexpr int O = L - 1, RW = R1W - 2 * O, RH = R1H - 2 * O;
+            // cells per thread, at least two: where one would do, the second folds away (its index is past the region for every
+            // thread), but with arrays of one element the compiler keeps the test against -1 and divides the cell index in 32 bits
+            // (k_step3_tile<float,12,1024,0>: -0.9 % at 4096x1024, profiles/lds_tile_body)
+            constexpr int CPT = (RW * RH + NTH - 1) / NTH > 2 ? (RW * RH + NTH - 1) / NTH : 2;
             T g[CPT][Q];
             int cell[CPT];
 #pragma unroll
@@ -1108,20 +999,37 @@ __global__ void __launch_bounds__(TX * TY, (deep_waves_per_simd<T, TX, TY, D>())
                 const int r = cell[k];
                 int ry, rx;
                 cell_xy.template operator()<O>(r, ry, rx);
+                // f, the cell being updated: the registers it was pulled into, or (COPY) a copy filled only where the pulled values
+                // are used. No one form serves both maps (profiles/lds_tile_body): the copy costs k_stepd_tile<float,32,32,8,0> six
+                // SGPR spills and a VGPR, its absence k_step4_tile<double,8,1024,0> nineteen SGPR spills (4 -> 23). The two copies
+                // stay written out: behind a lambda the compiler forms the other variant.
+                constexpr bool COPY = !TILE_FIRST;
+                T copy[Q];
+                T (&f)[Q] = COPY ? copy : g[k];
                 if (LEAN) {
-                    badl |= any_unstable(g[k]);
-                    collide<T, AR>(g[k], a);
+                    if constexpr (COPY) {
+#pragma unroll
+                        for (int i = 0; i < Q; ++i) f[i] = g[k][i];
+                    }
+                    badl |= any_unstable(f);
+                    collide<T, AR>(f, a);
                 } else {
                     const int x = X0 + rx - HW, y = Y0 + ry - HW;
                     const int yg = a.y_start + y;
                     const bool row_in = (yg >= 0 && yg < a.ny_glob), col_in = (x >= 0 && x < a.nx);
                     if (!(row_in && col_in)) {
 #pragma unroll
-                        for (int i = 0; i < Q; ++i) g[k][i] = outside_value(e, row_in, col_in, i);
-                    } else cell_update<T, AR>(a, g[k], x, yg, L - 1, fr.near_solid, y <= y_end + HW - L, badl);
+                        for (int i = 0; i < Q; ++i) f[i] = outside_value(e, row_in, col_in, i);
+                    } else {
+                        if constexpr (COPY) {
+#pragma unroll
+                            for (int i = 0; i < Q; ++i) f[i] = g[k][i];
+                        }
+                        cell_update<T, AR>(a, f, x, yg, L - 1, fr.near_solid, y <= y_end + HW - L, badl);
+                    }
                 }
 #pragma unroll
-                for (int i = 0; i < Q; ++i) lds[i][ry][rx] = g[k][i];
+                for (int i = 0; i < Q; ++i) lds[i][ry][rx] = f[i];
             }
             if (badl) atomicMin(a.unstable_t, *a.t_base + a.t + L - 1);
             __syncthreads();
@@ -1129,20 +1037,18 @@ __global__ void __launch_bounds__(TX * TY, (deep_waves_per_simd<T, TX, TY, D>())
         };
         [&]<int... Ls>(std::integer_sequence<int, Ls...>) { (in_place.template operator()<Ls + 2>(), ...); }(std::make_integer_sequence<int, D - 2>{});
         bad = false;
-        {                                                                     // level D on the tile: iteration t+D-1
-            const int o = threadIdx.x;
-            const int ly = o / TX, lx = o - ly * TX;
+        for (int o = threadIdx.x; o < TX * TY; o += NTH) {                    // level D on the tile: iteration t+D-1
+            const int ly = o / TX, lx = o - ly * TX;                          // (one cell per thread where NTH == TX * TY)
             const int x = X0 + lx, y = Y0 + ly;
-            if (LEAN || (y < y_end && x < a.nx)) {
-                T f[Q];
+            if (!LEAN && (y >= y_end || x >= a.nx)) continue;                 // partial tiles at the right / top edge
+            T f[Q];
 #pragma unroll
-                for (int i = 0; i < Q; ++i) f[i] = lds[i][ly + HW - cy(i)][lx + HW - cx(i)];
-                if (LEAN) {
-                    bad |= any_unstable(f);
-                    collide<T, AR>(f, a);
-                    fr.store(f, fr.at(ly, lx), fr.dst_off(a, Y0, X0), e.nt != 0);
-                } else if (cell_update_last<T, AR>(a, f, x, a.y_start + y, D - 1, fr.near_solid, bad)) store_cell(a, f, x, y, e.nt != 0);
-            }
+            for (int i = 0; i < Q; ++i) f[i] = lds[i][ly + HW - cy(i)][lx + HW - cx(i)];
+            if (LEAN) {
+                bad |= any_unstable(f);
+                collide<T, AR>(f, a);
+                fr.store(f, fr.at(ly, lx), fr.dst_off(a, Y0, X0), e.nt != 0);
+            } else if (cell_update_last<T, AR>(a, f, x, a.y_start + y, D - 1, fr.near_solid, bad)) store_cell(a, f, x, y, e.nt != 0);
         }
         if (bad) atomicMin(a.unstable_t, *a.t_base + a.t + D - 1);
         LBM_PROF(pb, NTH / 64, pw, D);                  // stores issued
@@ -1154,6 +1060,34 @@ __global__ void __launch_bounds__(TX * TY, (deep_waves_per_simd<T, TX, TY, D>())
     if (fr.lean) run.template operator()<true>();
     else run.template operator()<false>();
 }
+
+// Three / four iterations per launch (D = 3 / 4) over 64 x TY tiles, regions dealt row-major. LDS 9*(TY+2HW)*(64+2HW)*sizeof(T):
+// 78 KB at 64x12 fp64 for D = 3, two blocks of 1024 threads per CU = all 32 wave slots, the lean path needs 48 VGPRs; 70.5 KB at
+// 64x8 fp64, 35 KB fp32 for D = 4. At most two cells per thread in the in-place levels. fp64 traffic 58 B per update at 64x12,
+// D = 3; redundant collisions 1.21x (64x12, D = 3) / 1.45x (64x8, D = 4) — D = 4 is worth it where the three-iteration kernel is
+// close to the memory roof (fp32). Strips (six rows per exchange = 2 x 3) never use D = 4; the plan measurement decides elsewhere.
+template <typename T, int TY, int NTH, int AR = AR_STRICT>
+__global__ void __launch_bounds__(NTH, (2 * NTH / 256)) k_step3_tile(const KArgs<T> a, const K2Extra<T> e) { step_tile<T, 64, TY, NTH, 3, AR, false>(a, e); }
+template <typename T, int TY, int NTH, int AR = AR_STRICT>
+__global__ void __launch_bounds__(NTH, (2 * NTH / 256)) k_step4_tile(const KArgs<T> a, const K2Extra<T> e) { step_tile<T, 64, TY, NTH, 4, AR, false>(a, e); }
+
+// D = 6..8 on 64x16 / 32x32 tiles of 1024 threads, one thread per tile cell, regions dealt tile columns first: for grids so
+// small that one launch is a single round of blocks. There the chip runs load -> compute -> store in lockstep, so the two memory
+// phases are paid per LAUNCH: fusing more iterations divides them, at the price of ~1.5x redundant collisions that such a grid
+// has VALU time to spare for.
+// (Round 2's production shape — 32x16 tiles, 512 threads, D = 5/6, two blocks per CU: 125-130 GLUPS at 4096x1024 fp64 — is
+// superseded by k_stepc_col, which keeps the same region in registers instead of LDS, and is no longer built.)
+// Whole-domain launches only (rows outside the domain hold the permanent ghost values; a strip is refreshed six rows deep per single launch).
+// waves per SIMD the register allocation may assume: as many blocks as the LDS image allows on a CU (at most 32 waves)
+template <typename T, int TX, int TY, int D>
+constexpr int deep_waves_per_simd() {
+    const int lds = (int)sizeof(T) * Q * (TX + 2 * (D - 1)) * (TY + 2 * (D - 1)), waves = TX * TY / 64;
+    int blocks = 160 * 1024 / lds;
+    if (blocks * waves > 32) blocks = 32 / waves;
+    return (blocks * waves) / 4 > 0 ? (blocks * waves) / 4 : 1;
+}
+template <typename T, int TX, int TY, int D, int AR = AR_STRICT>
+__global__ void __launch_bounds__(TX * TY, (deep_waves_per_simd<T, TX, TY, D>())) k_stepd_tile(const KArgs<T> a, const K2Extra<T> e) { step_tile<T, TX, TY, TX * TY, D, AR, true>(a, e); }
 
 // ---------------------------------------------------------------------------------------------------------
 // Initialisation: Grid::initialise (LBMGrid.h:185-246) written into BOTH buffers, plus the permanent ghost
