@@ -42,14 +42,10 @@ def embedded_id(path=LIB):
     return m.group(1).decode() if m else None
 
 
-# the Arith bases of the collision models (csrc/lbm_plan.hpp collision_models): BGK, Smagorinsky (LES), two relaxation times (TRT)
-COLLISION_BASES = (0, 2, 4)
-# ... and those whose row says `park`: the tall fp64 regions (64x40) are built for them
-PARK_BASES = (0, 2, 4)
-# BGK under a driving force (lbm_set_forcing), enumerated on its own and named to the sources by flags of its own (-DLBM_AR_FORCED_BASE,
-# -DLBM_COL_FORCED_PARK), which they map to the base: the same three kinds of unit as a base above, and the tall fp64 regions if its row says so
-FORCED_BASES = (8,)
-FORCED_PARK_BASES = (8,)
+# the collision models (csrc/lbm_plan.hpp collision_models) as (Arith base, `park`: the fp64 64x40 regions are built for it): BGK,
+# Smagorinsky (LES), two relaxation times (TRT), BGK under a driving force (lbm_set_forcing)
+COLLISION_MODELS = ((0, True), (2, True), (4, True), (8, True))
+COLLISION_BASES = tuple(base for base, _ in COLLISION_MODELS)
 
 
 def units(build_id):
@@ -61,17 +57,11 @@ def units(build_id):
         out += [("lbm_col.hip", ["-DLBM_COL_T=double", ar], "lbm_col_ar%d_f64.o" % base),
                 ("lbm_col.hip", ["-DLBM_COL_T=float", ar], "lbm_col_ar%d_f32.o" % base),
                 ("lbm_step_k.hip", [ar], "lbm_step_k_ar%d.o" % base)]
-    # the tall fp32 regions (BGK only), the frame kernel (lbm_frames_begin), the probe kernel (lbm_probes_begin)
+    # the fp32 64x48 regions (BGK only), the frame kernel (lbm_frames_begin), the probe kernel (lbm_probes_begin)
     out += [("lbm_col.hip", ["-DLBM_COL_TALL=1"], "lbm_col_tall_c.o"), ("lbm_col.hip", ["-DLBM_COL_TALL=0"], "lbm_col_tall_s.o"),
             ("lbm_frames.hip", [], "lbm_frames.o"), ("lbm_probes.hip", [], "lbm_probes.o")]
-    # the tall fp64 regions (64x40, contracted arithmetic), one object per model that has them
-    out += [("lbm_col.hip", ["-DLBM_COL_PARK=%d" % base], "lbm_col_park_ar%d.o" % base) for base in PARK_BASES]
-    for base in FORCED_BASES:
-        ar = "-DLBM_AR_FORCED_BASE=%d" % base
-        out += [("lbm_col.hip", ["-DLBM_COL_T=double", ar], "lbm_col_ar%d_f64.o" % base),
-                ("lbm_col.hip", ["-DLBM_COL_T=float", ar], "lbm_col_ar%d_f32.o" % base),
-                ("lbm_step_k.hip", [ar], "lbm_step_k_ar%d.o" % base)]
-    out += [("lbm_col.hip", ["-DLBM_COL_FORCED_PARK=%d" % base], "lbm_col_park_ar%d.o" % base) for base in FORCED_PARK_BASES]
+    # the fp64 64x40 regions (contracted arithmetic), one object per model that has them
+    out += [("lbm_col.hip", ["-DLBM_COL_PARK=%d" % base], "lbm_col_park_ar%d.o" % base) for base, park in COLLISION_MODELS if park]
     return out
 
 

@@ -359,7 +359,7 @@ struct lbm_ctx {
     int pair_ty = 8;     // tile height of the fused kernels (8 or 12)
     int xcd = 0;         // fused kernels: remap blocks so that each XCD walks a contiguous run of tiles
     bool deep_now = false;   // the launch being issued is the plan's deep launch (set by plan_launch)
-    int deep = 0;        // 1..3: k_stepd_tile shape (6/7/8 iterations per launch on an LDS-filling tile); 6/7: k_stepc_col (registers)
+    int deep = 0;        // 0, or the id of a row of deep_shapes (lbm_plan.hpp): an LDS-filling tile of k_stepd_tile or regions of k_stepc_col (registers)
     int arith = 0;       // collision arithmetic: 0 strict IEEE op-by-op (bit-identical to the oracle), 1 contracted (FMA +
                          // one reciprocal, as the reference's -ffast-math -mfma build permits); see lbm_kernels.hpp Arith
     int collision = 0;   // the collision model, the `base` of its row in collision_models (lbm_plan.hpp): 0 BGK, AR_STRICT_LES (lbm_set_smagorinsky),

@@ -372,12 +372,12 @@ void lbm_destroy(lbm_ctx* c) {
 }
 
 namespace {
-// the tall fp32 regions (deep 8) exist for the models whose row says so
-int refuse_tall(int collision, int deep) {
-    const CollisionModel& m = collision_model(collision);
-    if (deep == 8 && !m.tall) return fail(LBM_ERR_ARG, "deep 8 (64x48 regions in registers) has no %s kernel", m.noun);
-    if (deep_is_park(deep) && !m.park) return fail(LBM_ERR_ARG, "deep %d (64x40 regions in registers) has no %s kernel", deep, m.noun);
-    return LBM_OK;
+// May this context run deep shape `deep` under collision model `collision` (deep_refusal, lbm_plan.hpp)? `settled`: its arithmetic mode
+// and its extent count too (lbm_initialise: the arithmetic and the strip options may follow `deep`).
+int refuse_deep(const lbm_ctx* c, int collision, int deep, bool settled) {
+    const bool whole = !((c->comm && c->nranks > 1) || c->group_n > 1 || c->loopback || c->nyl != c->p.ny);
+    const std::string why = deep_refusal(deep, (int)c->esize, collision_model(collision), settled, c->arith == AR_CONTRACTED, whole);
+    return why.empty() ? LBM_OK : fail(LBM_ERR_ARG, "%s", why.c_str());
 }
 // What the setters of the collision models share once the value is accepted. A nonzero value (value2: the second one of a model with
 // two, the force's Fy): the model `base` with that parameter, unless
@@ -389,7 +389,7 @@ int set_collision(lbm_ctx* c, int base, double value, const char* what, bool tal
     if (on && c->collision != base && c->collision != AR_STRICT)
         return fail(LBM_ERR_ARG, "%s %s on a context with %s %s%s (the two collisions cannot be combined)", what, param_text(collision_model(base), value, value2).c_str(),
                     cur.param, cur.value, param_text(cur, c->collision_param, c->collision_param2).c_str());
-    if (on && tall_now) { if (int rc = refuse_tall(base, c->deep)) return rc; }
+    if (on && tall_now) { if (int rc = refuse_deep(c, base, c->deep, false)) return rc; }
     if (on) { c->collision = base; c->collision_param = value; c->collision_param2 = value2; }
     else if (c->collision == base) { c->collision = AR_STRICT; c->collision_param = 0.0; c->collision_param2 = 0.0; }
     return LBM_OK;
@@ -399,10 +399,7 @@ int set_collision(lbm_ctx* c, int base, double value, const char* what, bool tal
 int lbm_initialise(lbm_ctx* c, int* solid_count_out) {
     if (!c) return fail(LBM_ERR_ARG, "null context");
     lbm_trace("initialise", "ctx %p %dx%d rows %d..%d begin", (void*)c, c->nx, c->p.ny, c->p.y_start, c->p.y_start + c->nyl);
-    if (int rc = refuse_tall(c->collision, c->deep)) return rc;
-    // (the arithmetic and the strip options may follow `deep`: looked at here)
-    if (deep_is_park(c->deep) && (c->arith != AR_CONTRACTED || (c->comm && c->nranks > 1) || c->group_n > 1 || c->loopback || c->nyl != c->p.ny))
-        return fail(LBM_ERR_ARG, "deep %d (64x40 regions in registers) exists for contracted arithmetic on whole domains only", c->deep);
+    if (int rc = refuse_deep(c, c->collision, c->deep, true)) return rc;
     HIPCHK(hipSetDevice(c->device));
     if (c->has_sched()) { if (int rc = prepare_schedule(c)) return rc; }
     { int wr = wait_stream(c, c->stream, "compute stream (lbm_initialise)"); if (wr) return wr; }        // (re-)initialisation starts from quiet streams
@@ -1142,13 +1139,8 @@ int lbm_set_option(lbm_ctx* c, const char* key, long value) {
     else if (k == "nt") c->use_nt = (int)value ? 1 : 0;
     else if (k == "ntl") c->use_ntl = (int)value ? 1 : 0;
     else if (k == "fuse") { if (value < 1 || value > 4) return fail(LBM_ERR_ARG, "fuse must be 1, 2, 3 or 4 (4: tile kernel, no strip faces)"); c->fuse = (int)value; c->deep = 0; }
-    else if (k == "deep") {     // k_stepd_tile: 1: 6 iterations on 64x16 tiles, 2: 7 on 64x16, 3: 8 on 32x32 (1024 threads);
-                                // k_stepc_col (registers): 6 / 7 / 9: 5 / 6 / 7 iterations on 64x32 regions; 8 (fp32): 7 iterations on 64x48 regions;
-                                // 10 / 11 (fp64 contracted, whole domains): 6 / 7 iterations on 64x40 regions.
-        if (!deep_valid((int)value)) return fail(LBM_ERR_ARG, "deep must be 0..3 or 6..11 (4 / 5, round 2's 32x16 LDS tiles, are retired)");
-        if (deep_is_park((int)value) && c->esize != 8) return fail(LBM_ERR_ARG, "deep 10 / 11 (64x40 regions in registers, eight waves x five rows) exist in fp64 only");
-        if (value == 8 && c->esize != 4) return fail(LBM_ERR_ARG, "deep 8 (64x48 regions in registers, twelve waves x four rows) exists in fp32 only");
-        if (int rc = refuse_tall(c->collision, (int)value)) return rc;
+    else if (k == "deep") {     // the id of a row of deep_shapes (lbm_plan.hpp)
+        if (int rc = refuse_deep(c, c->collision, (int)value, false)) return rc;
         c->deep = (int)value;
         if (c->deep) c->fuse = deep_depth(c->deep);
     }
@@ -1290,6 +1282,33 @@ int lbm_debug_plan_candidates(int nx, int ny, int precision, int arith, int num_
         text += pl.name + "|" + plan_option_string(pl.layout, pl.nt, pl.alternate, pl.ty, pl.xcd, fuse, pl.deep, pl.ntl) + "|" +
                 plan_kernel_name(fuse, pl.deep, pl.ty ? pl.ty : 8, pl.nt, arith, q.esize) + "|" + std::to_string(pl.deep ? deep_depth(pl.deep) : fuse) + "\n";
     }
+    if ((int)text.size() + 1 > cap) return fail(LBM_ERR_ARG, "buffer too small (%zu bytes needed)", text.size() + 1);
+    memcpy(out, text.c_str(), text.size() + 1);
+    return LBM_OK;
+}
+
+/* TEST HOOK (no device needed): the deep launch shapes (deep_shapes and region_kinds, lbm_plan.hpp), one line per id, precision and
+ * arithmetic mode that exists: see include/lbm_hip.h. */
+int lbm_debug_deep_shapes(char* out, int cap) {
+    if (!out || cap < 1) return fail(LBM_ERR_ARG, "bad argument");
+    std::string text;
+    char b[160];
+    for (const DeepShape& s : deep_shapes)
+        for (int esize : {8, 4})
+            for (int contracted : {0, 1}) {
+                const RegionKind* k = deep_kind(s.id);
+                const RowsWaves rw = k ? col_rw(*k, esize, contracted) : RowsWaves{1, s.tile_w * s.tile_h / 64};     // (an LDS tile: a cell per thread)
+                if (!rw.rows) continue;
+                snprintf(b, sizeof(b), "%d|%s|%s|%s|%d|%d|%d|%d|%d|", s.id, esize == 8 ? "f64" : "f32", contracted ? "contracted" : "strict", k ? "registers" : "lds",
+                         s.depth, k ? 64 : s.tile_w, k ? rw.rows * rw.waves : s.tile_h, rw.rows, rw.waves);
+                text += b;
+                if (!k) text += std::to_string(s.depth);
+                else for (const ColDepth& d : k->depths)
+                    text += (&d == k->depths ? "" : " ") + std::to_string(d.depth) + (d.nt ? ":nt+plain" : ":plain") + (d.no_face ? ":no-face" : "");
+                const bool one = k && !k->rw[esize != 4][0].rows && !k->rw[esize != 4][1].rows;       // (the other precision has none)
+                text += std::string("|") + (one ? (esize == 8 ? "fp64 only" : "fp32 only") : "") + (k && k->only ? std::string(", ") + k->only : "") +
+                        (k && k->needs ? (k->needs == &CollisionModel::tall ? ", model flag tall" : ", model flag park") : "") + "\n";
+            }
     if ((int)text.size() + 1 > cap) return fail(LBM_ERR_ARG, "buffer too small (%zu bytes needed)", text.size() + 1);
     memcpy(out, text.c_str(), text.size() + 1);
     return LBM_OK;
@@ -1443,6 +1462,7 @@ int lbm_debug_choreography(int nx, int ny, const int* bounds2, int nstrips, int 
             c->nranks = 1 + (s_face ? 1 : 0) + (n_face ? 1 : 0);
             c->rank = s_face ? 1 : 0;
         } else if (transport == 3) c->loopback = 1;
+        if (int rc = refuse_deep(c, c->collision, c->deep, true)) { cleanup(); return rc; }       // (as lbm_initialise does)
         c->initialised = true;
         c->cur = 1;
         if (c->stats_opt >= 0) { c->stats_active = true; c->stats_from = c->stats_opt; }      // (no accumulators: nothing is launched)

@@ -117,22 +117,16 @@ void launch_rows(const lbm_ctx* c, const KArgs<T>& a, hipStream_t s) {
     with_collision_base(MODE == MODE_STREAM_ONLY ? (int)AR_STRICT : c->collision, [&](auto arb) { launch_site<T, arb()>(a, MODE, nt, fast, s); });
 }
 
-// "deep" plans: shape id -> iterations per launch and tile. 1..3: LDS-image tiles (k_stepd_tile: six / seven iterations on
-// 64x16 tiles, eight on 32x32; what a grid of a single round of blocks picks); 6 / 7: the register-resident column kernel
-// (k_stepc_col, R = 4 rows per thread x 8 waves = a 64 x 32 region per block, two blocks per CU; fp64 strict: 2 rows x 12 waves = 64 x 24) with five / six iterations —
-// a plan of either uses both depths, and on a context without strip faces seven iterations too, for what a segment leaves
-// over (20 = 7 + 7 + 6; at 4096x1024 fp64 seven iterations run at 160.6 GLUPS against 161.7 for six — eight, 154.3, are
-// not built); 9: the same family with seven iterations as the plan's depth (8192x2048 fp64: 175.9 against 169.9); 8: fp32 only, the same kernel on TALL 64 x 48 regions (twelve waves x four rows) with seven iterations, six / eight for
-// what a segment leaves over; 10 / 11: fp64 contracted on whole domains only, the same kernel on TALL 64 x 40 regions (eight waves x five rows, the fifth
-// parked in LDS) with six / seven iterations, five to seven for what a segment leaves over. Ids 4 / 5 were round 2's 32x16 LDS tiles: retired.
-// rows of one band of tiles of a launch of `depth` iterations (the edge bands of a strip are one band each)
+// "deep" plans (deep_shapes, lbm_plan.hpp): rows of one band of tiles of a launch of `depth` iterations (the edge bands of a strip are
+// one band each)
 inline int deep_rows(const lbm_ctx* c, int id, int depth) {
-    if (deep_is_col(id)) return col_tile_h(depth, (int)c->esize, c->arith == 0, deep_is_tall(id));
-    return id == 3 ? 32 : 16;
+    const RegionKind* k = deep_kind(id);
+    return k ? col_tile_h(depth, col_rw(*k, (int)c->esize, c->arith != 0)) : deep_shape(id)->tile_h;
 }
-// A fused kernel over the local rows [a.y_lo, a.y_lo + a.y_cnt): iterations a.t .. a.t + depth - 1 (depth 2..8).
+// A fused kernel over the local rows [a.y_lo, a.y_lo + a.y_cnt): iterations a.t .. a.t + depth - 1 (depth 2..8). LBM_ERR_ARG, and
+// nothing queued: a deep launch of a depth the shape's row does not list (plan_launch reads the same row: it asks for none).
 template <typename T>
-void launch_fused_rows(const lbm_ctx* c, const KArgs<T>& a, int depth, hipStream_t s) {
+int launch_fused_rows(const lbm_ctx* c, const KArgs<T>& a, int depth, hipStream_t s) {
     const int shape = c->deep;
     K2Extra<T> e;
     e.feq_in = static_cast<const T*>(c->d_feq);
@@ -141,29 +135,19 @@ void launch_fused_rows(const lbm_ctx* c, const KArgs<T>& a, int depth, hipStream
     e.nt = c->use_nt;
     e.ntl = c->use_ntl;
     const bool fast = c->arith == AR_CONTRACTED;
-    if (c->deep_now && deep_is_col(shape)) {    // D iterations with the lattice in registers (k_stepc_col, lbm_col.hip)
-        if constexpr (sizeof(T) == 4) {
-            if (deep_is_tall(shape)) {
-                if (fast) launch_col_tall_contracted(a, e, depth, s); else launch_col_tall_strict(a, e, depth, s);
-                return;
-            }
-        }
-        if constexpr (sizeof(T) == 8) {
-            if (deep_is_park(shape)) {        // (contracted arithmetic of a model that has them: refuse_tall)
-                with_collision_base(c->collision, [&](auto arb) {
-                    if constexpr (collision_model(arb()).park) launch_col_park<arb()>(a, e, depth, c->use_nt != 0, s);
-                });
-                return;
-            }
-        }
-        // (no tall regions but BGK's: lbm_set_option / plan_candidates)
-        with_collision_base(c->collision, [&](auto arb) { launch_col<T, arb()>(a, e, depth, c->use_nt != 0, fast, s); });
-        return;
-    }
+    bool ok = false;
     with_collision_base(c->collision, [&](auto arb) {
-        if (c->deep_now) launch_deep<T, arb()>(a, e, shape, fast, s);    // D iterations on a deep LDS tile (k_stepd_tile; whole-domain launches of small grids)
-        else launch_tile<T, arb()>(a, e, depth, c->pair_ty, fast, s);
+        if (!c->deep_now) { launch_tile<T, arb()>(a, e, depth, c->pair_ty, fast, s); ok = true; }
+        // D iterations on a deep LDS tile (k_stepd_tile; whole-domain launches of small grids)
+        else if (!deep_is_col(shape)) ok = depth == deep_depth(shape) && launch_deep<T, arb()>(a, e, shape, fast, s);
+        // ... or with the lattice in registers (k_stepc_col, lbm_col.hip), on the shape's kind of region: an instantiation that is
+        // not built is one refuse_deep has refused
+        else with_row<std::size(region_kinds)>([&](size_t i) { return &region_kinds[i] == deep_kind(shape); }, [&](auto kind) {
+            if constexpr (col_built<T, kind(), arb() | 1>()) { if (fast) ok = launch_col<T, kind(), arb() | 1>(a, e, depth, c->use_nt != 0, s); }
+            if constexpr (col_built<T, kind(), arb()>()) { if (!fast) ok = launch_col<T, kind(), arb()>(a, e, depth, c->use_nt != 0, s); }
+        });
     });
+    return ok ? LBM_OK : fail(LBM_ERR_ARG, "deep %d has no launch of %d iterations here", shape, depth);
 }
 inline bool pair_possible(const lbm_ctx*) { return true; }   // partial tiles cover any nx
 template <typename T>
@@ -172,9 +156,7 @@ int launch_step(lbm_ctx* c, int src, int dst, int t, int mode, hipStream_t s) {
     a.reverse = ((mode == MODE_STEP || mode >= 100) && c->alternate && (c->launches_total & 1)) ? 1 : 0;
     switch (mode) {
         case MODE_STEP: launch_rows<T, MODE_STEP>(c, a, s); break;
-        case 102: launch_fused_rows<T>(c, a, 2, s); break;     // iterations t, t+1
-        case 103: launch_fused_rows<T>(c, a, 3, s); break;     // iterations t, t+1, t+2
-        case 104: launch_fused_rows<T>(c, a, 4, s); break;     // iterations t .. t+3 (k_step4_tile, no strip faces)
+        case 102: case 103: case 104: if (int rc = launch_fused_rows<T>(c, a, mode - 100, s)) return rc; break;     // iterations t .. t+1 / t+2 / t+3 (four: k_step4_tile, no strip faces)
         case MODE_COLLIDE_ONLY: launch_rows<T, MODE_COLLIDE_ONLY>(c, a, s); break;
         default: break;
     }

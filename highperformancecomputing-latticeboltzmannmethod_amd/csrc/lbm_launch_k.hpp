@@ -3,7 +3,7 @@
 // or ARB | 1 contracted). Declared only: lbm_step_k.hip defines them and instantiates them explicitly, once per base (-DLBM_AR_BASE,
 // build.py), so no other translation unit can instantiate a step kernel.
 #pragma once
-#include "lbm_kernels.hpp"
+#include "lbm_plan.hpp"
 
 namespace lbmk {
 
@@ -11,9 +11,9 @@ namespace lbmk {
 // AR_STRICT alone MODE_STREAM_ONLY (no collision in it)
 template <typename T, int ARB>
 void launch_site(const KArgs<T>& a, int mode, bool nt, bool fast, hipStream_t s);
-// k_stepd_tile on LDS shape `shape` (1: 64x16 six iterations, 2: 64x16 seven, 3: 32x32 eight)
+// k_stepd_tile on the tile and with the depth of the LDS row `shape` of deep_shapes (lbm_plan.hpp); false, and nothing queued: no such row
 template <typename T, int ARB>
-void launch_deep(const KArgs<T>& a, const K2Extra<T>& e, int shape, bool fast, hipStream_t s);
+bool launch_deep(const KArgs<T>& a, const K2Extra<T>& e, int shape, bool fast, hipStream_t s);
 // k_step2/3/4_tile: `depth` iterations on bands of `ty` rows (depth 4: 64x8 tiles only)
 template <typename T, int ARB>
 void launch_tile(const KArgs<T>& a, const K2Extra<T>& e, int depth, int ty, bool fast, hipStream_t s);

@@ -4,46 +4,31 @@
 // (tests/test_bench_cpu.py: every fused candidate of every BASELINE.json grid has a committed counter pass).
 #pragma once
 #include <cstdio>
+#include <iterator>
 #include <string>
+#include <utility>
 #include <vector>
 
-#include "lbm_col_api.hpp"
+#include "lbm_kernels.hpp"
 
 namespace lbmk {
 
 // layout 0 planar / 1 row-interleaved; nt: non-temporal stores;
 // alternate: walk direction alternates per launch; fuse: iterations per launch of the tile kernels (1..4) or of the deep shape;
-// ty: tile height of the two- / three-iteration tile kernels (8 or 12); xcd: XCD-aware tile walk; deep: 0, or the deep shape
-// (1..3: k_stepd_tile six / seven / eight iterations; 6 / 7: k_stepc_col five / six iterations in registers on 64x32 regions;
-// 9: the same kernel with SEVEN iterations as the plan's depth — the largest grids; 8: fp32 only, k_stepc_col seven iterations
-// on TALL 64x48 regions — lbm_col_api.hpp; 10 / 11: fp64 contracted only, whole domains only, k_stepc_col six / seven iterations on
-// TALL 64x40 regions, the top row of every thread parked in LDS); ntl: the register kernel's level-1 loads
-// are non-temporal
+// ty: tile height of the two- / three-iteration tile kernels (8 or 12); xcd: XCD-aware tile walk; deep: 0, or the id of a row of
+// deep_shapes (below); ntl: the register kernel's level-1 loads are non-temporal
 struct Plan { int layout, nt, alternate, fuse, ty, xcd; std::string name; int deep = 0; int ntl = 0; };
-
-inline bool deep_is_col(int id) { return id >= 6 && id <= 11; }
-inline bool deep_is_park(int id) { return id == 10 || id == 11; }         // the tall fp64 regions (64x40)
-inline bool deep_is_tall(int id) { return id == 8 || deep_is_park(id); }  // (8: the tall fp32 regions, 64x48)
-inline bool deep_valid(int id) { return id == 0 || (id >= 1 && id <= 3) || deep_is_col(id); }
-inline int deep_depth(int id) {
-    static const int d[12] = {0, 6, 7, 8, 0, 0, 5, 6, 7, 7, 6, 7};
-    return id >= 0 && id <= 11 ? d[id] : 0;
-}
-inline const char* deep_tile(int id) {
-    static const char* t[4] = {"", "64,16", "64,16", "32,32"};
-    return id >= 0 && id <= 3 ? t[id] : "";
-}
 
 // The collision models, one row each: everything the host knows about a model beyond its C-ABI setter. `base` is the model's strict
 // Arith value (lbm_kernels.hpp; base | 1: its contracted one) and what lbm_ctx::collision holds; `noun` names it in messages;
-// `tall`: the tall fp32 regions (deep 8) are instantiated for it; `park`: so are the tall fp64 ones (deep 10 / 11); `ckpt_bit`: the LBMCKPT3 flag that announces its parameter (0: none —
+// `tall`, `park`: the 64x48 fp32 and the 64x40 fp64 regions (region_kinds, below) are instantiated for it; `ckpt_bit`: the LBMCKPT3 flag that announces its parameter (0: none —
 // rows in ascending order of this bit, the order the parameters stand in the file); the last three are the words checkpoints and
 // setters use for the parameter, its value and a context without it.
 // the models whose contracted kernels on the tall fp64 regions keep four waves per SIMD without scratch: BGK 120 VGPRs, TRT 124,
-// Smagorinsky 126 with three of the parked row's reads issued a row later (profiles/col_parked/README.md; build.py PARK_BASES)
+// Smagorinsky 126 with three of the parked row's reads issued a row later (profiles/col_parked/README.md; build.py COLLISION_MODELS)
 constexpr bool PARK_LES = true, PARK_TRT = true;
 // BGK under a driving force (lbm_set_forcing): its contracted kernels on the tall fp64 regions take 122-123 VGPRs, no scratch, four waves
-// per SIMD like BGK's 120 (profiles/forcing/README.md; build.py FORCED_PARK_BASES). Like LES and TRT it has no tall fp32 regions: their
+// per SIMD like BGK's 120 (profiles/forcing/README.md). Like LES and TRT it has no tall fp32 regions: their
 // two objects are BGK's alone (lbm_col.hip -DLBM_COL_TALL), so no forced instantiation of them exists to meet the bar.
 constexpr bool PARK_FORCED = true;
 // `nparam`: the doubles of the model's parameter (the force has two components; lbm_ctx::collision_param, collision_param2). A model whose
@@ -69,6 +54,77 @@ inline std::string param_text(const CollisionModel& m, double v, double v2, cons
     return m.nparam == 2 ? std::string("(") + a + ", " + b + ")" : std::string(a);
 }
 
+// ---- the deep launch shapes: one table of region kinds, one of ids. Launchers, plan_launch, names, messages and refusals read them ----
+// A region of the register kernel (k_stepc_col) is 64 columns x rows per thread * waves; {0, 0}: that precision and arithmetic is not built.
+struct RowsWaves { int rows, waves; };
+// a launch depth a kind offers; nt: a non-temporal-store instantiation exists beside the plain one (they cost 14 % on the fp32 64x48
+// regions, and seven iterations are the depth of remainders and of plans that all store plainly); no_face: not on a context with a
+// physical strip face (its ghost rows go six deep, seven where a plan of that depth exchanges seven)
+struct ColDepth { int depth; bool nt, no_face; };
+struct RegionKind {
+    const char* name;
+    RowsWaves rw[2][2];                 // [fp64, fp32][strict, contracted]
+    ColDepth depths[3];
+    bool CollisionModel::*needs;        // the flag of the model's row that grants the kind (nullptr: every model has it)
+    const char* only;                   // what else a context must be, as messages say it (checked by lbm_initialise); nullptr: nothing
+};
+enum { RK_STD, RK_TALL, RK_PARK };
+constexpr RegionKind region_kinds[] = {
+    // 8 waves x 4 rows, two blocks per CU — except fp64 STRICT arithmetic, whose collision needs a dozen more live registers than 128
+    // VGPRs leave beside 4 x 9 fp64 populations: 12 waves x 2 rows = 64x24, 70 VGPRs = six waves per SIMD, 135.7 against 127.3 GLUPS on
+    // 8 x 3 (tools/colbench --strict); contracted arithmetic is fastest on 8 x 4 (64x24 on 24 waves: 157-159 against 158-162)
+    {"64x32", {{{2, 12}, {4, 8}}, {{4, 8}, {4, 8}}}, {{5, true, false}, {6, true, false}, {7, false, true}}, nullptr, nullptr},
+    // fp32 (round 4): contracted 76 VGPRs = two blocks of twelve waves, strict 112-116 VGPRs. At seven iterations it stores 52x36 of
+    // its cells where 64x32 stores 54x22 at six: 1.33 x instead of 1.45 x the lattice read per launch; 16384x4096: 320 GLUPS against 289-298
+    {"64x48", {{{0, 0}, {0, 0}}, {{6, 8}, {4, 12}}}, {{6, false, false}, {7, false, false}, {8, false, true}}, &CollisionModel::tall, nullptr},
+    // fp64 contracted: the top row of every thread parked in LDS between levels (lbm_kernel_col.hpp "Parked top row": 120-124 VGPRs, no
+    // scratch, 76 352 B of LDS per block = two blocks per CU); strict arithmetic keeps 12 waves x 2 rows
+    {"64x40", {{{0, 0}, {5, 8}}, {{0, 0}, {0, 0}}}, {{5, true, false}, {6, true, false}, {7, false, false}}, &CollisionModel::park, "contracted arithmetic on whole domains"},
+};
+// Option "deep" = the id of a row. LDS rows (k_stepd_tile) launch their own depth on their tile only; register rows launch their depth
+// while it fits a segment and any depth their kind offers for what the segment leaves over (20 = 7 + 7 + 6). Ids 4 / 5 were round 2's
+// 32x16 LDS tiles: retired. The strip rule and the strip tuner name the ids they pick.
+enum { DEEP_LDS6 = 1, DEEP_LDS7 = 2, DEEP_LDS8 = 3, DEEP_COL5 = 6, DEEP_COL6 = 7, DEEP_TALL7 = 8, DEEP_COL7 = 9, DEEP_PARK6 = 10, DEEP_PARK7 = 11 };
+struct DeepShape { int id, depth, kind, tile_w, tile_h; };      // kind: a row of region_kinds, or -1: an LDS tile of tile_w x tile_h
+constexpr DeepShape deep_shapes[] = {
+    {DEEP_LDS6, 6, -1, 64, 16}, {DEEP_LDS7, 7, -1, 64, 16}, {DEEP_LDS8, 8, -1, 32, 32},
+    {DEEP_COL5, 5, RK_STD, 0, 0}, {DEEP_COL6, 6, RK_STD, 0, 0}, {DEEP_COL7, 7, RK_STD, 0, 0},
+    {DEEP_TALL7, 7, RK_TALL, 0, 0}, {DEEP_PARK6, 6, RK_PARK, 0, 0}, {DEEP_PARK7, 7, RK_PARK, 0, 0},
+};
+constexpr const DeepShape* deep_shape(int id) {
+    for (const DeepShape& s : deep_shapes) if (s.id == id) return &s;
+    return nullptr;
+}
+constexpr int deep_depth(int id) { return deep_shape(id) ? deep_shape(id)->depth : 0; }
+constexpr const RegionKind* deep_kind(int id) { return deep_shape(id) && deep_shape(id)->kind >= 0 ? &region_kinds[deep_shape(id)->kind] : nullptr; }
+constexpr bool deep_is_col(int id) { return deep_kind(id) != nullptr; }
+constexpr RowsWaves col_rw(const RegionKind& k, int esize, bool contracted) { return k.rw[esize == 4][contracted]; }
+constexpr const ColDepth* col_depth(const RegionKind& k, int depth) {
+    for (const ColDepth& d : k.depths) if (d.depth == depth) return &d;
+    return nullptr;
+}
+// output tile of a register launch of `depth` iterations
+constexpr int col_tile_w(int depth) { return 64 - 2 * (depth - 1); }
+constexpr int col_tile_h(int depth, RowsWaves rw) { return rw.rows * rw.waves - 2 * (depth - 1); }
+// f(std::integral_constant<size_t, I>) for the first I < N that pred(I) accepts; false: none does. How a table row becomes template
+// arguments (the launchers of lbm_col.hip and lbm_step_k.hip), in the style of with_collision_base (lbm_launch.inc.hpp).
+template <size_t N, typename P, typename F>
+bool with_row(P&& pred, F&& f) {
+    return [&]<size_t... I>(std::index_sequence<I...>) { return ((pred(I) && (f(std::integral_constant<size_t, I>{}), true)) || ...); }(std::make_index_sequence<N>{});
+}
+// Why a context of this element size and collision model may not run deep shape `id` ("": it may). The arithmetic mode and the extent
+// count once they are `settled` only: options may follow `deep`, so lbm_set_option and the models' setters ask before, lbm_initialise after.
+inline std::string deep_refusal(int id, int esize, const CollisionModel& m, bool settled, bool contracted, bool whole_domain) {
+    if (id && !deep_shape(id)) return "deep must be 0..3 or 6..11 (4 / 5, round 2's 32x16 LDS tiles, are retired)";
+    const RegionKind* k = deep_kind(id);
+    if (!k) return "";
+    const std::string what = "deep " + std::to_string(id) + " (" + k->name + " regions in registers)";     // (as plan names call them)
+    if (!k->rw[esize == 4][0].rows && !k->rw[esize == 4][1].rows) return what + " exists in " + (esize == 4 ? "fp64" : "fp32") + " only";
+    if (k->needs && !(m.*k->needs)) return what + " has no " + m.noun + " kernel";
+    if (settled && k->only && !(col_rw(*k, esize, contracted).rows && whole_domain)) return what + " exists for " + k->only + " only";
+    return "";
+}
+
 struct PlanQuery {
     int nx = 0, nyl = 0, ny_glob = 0;   // columns, rows of this strip, rows of the lattice
     int esize = 8;                      // bytes per element
@@ -89,7 +145,7 @@ struct PlanQuery {
 // the number of strips only: every rank — measuring or not — issues the same launch depths.
 inline int strip_rule_deep(bool strips, int ny_glob, int nstrips) {
     const int strip_rows = ny_glob / (nstrips > 0 ? nstrips : 1);
-    return !strips ? 0 : strip_rows >= 192 ? 7 : strip_rows >= 64 ? 1 : 0;
+    return !strips ? 0 : strip_rows >= 192 ? DEEP_COL6 : strip_rows >= 64 ? DEEP_LDS6 : 0;
 }
 
 // Every candidate lbm_initialise times for this context (one entry: nothing is measured). `fixed` = the plan the options pin.
@@ -98,7 +154,7 @@ inline std::vector<Plan> plan_candidates(const PlanQuery& q, const Plan& fixed) 
     // "small": 1024-cell tiles make at most two rounds of one block per CU (fp32: two blocks per CU)
     const bool small_grid = (size_t)q.nx * q.nyl <= (size_t)2048 * q.num_cus * (q.esize == 4 ? 2 : 1);
     const int strip_deep = strip_rule_deep(q.strips, q.ny_glob, q.nstrips);
-    const std::string deep_name = strip_deep == 7 ? "row-interleaved/6-step 64x32 in registers" : "row-interleaved/6-step 64x16";
+    const std::string deep_name = deep_is_col(strip_deep) ? "row-interleaved/6-step 64x32 in registers" : "row-interleaved/6-step 64x16";
     if (!q.tune) { cand.push_back(fixed); return cand; }
     if (!q.can_tune) {
         if (strip_deep) cand.push_back({1, 1, 0, 6, 12, 1, deep_name + " (default, not measured)", strip_deep});
@@ -112,7 +168,7 @@ inline std::vector<Plan> plan_candidates(const PlanQuery& q, const Plan& fixed) 
     if (strip_deep) {
         cand.push_back({1, 1, 0, 6, 12, 1, deep_name + "/nt-store/xcd", strip_deep});
         cand.push_back({1, 0, 0, 6, 12, 1, deep_name + "/xcd", strip_deep});
-        if (strip_deep == 7) cand.push_back({1, 0, 0, 6, 12, 1, deep_name + "/nt-load/xcd", strip_deep, 1});
+        if (deep_is_col(strip_deep)) cand.push_back({1, 0, 0, 6, 12, 1, deep_name + "/nt-load/xcd", strip_deep, 1});
         return cand;
     }
     if (q.strips) {
@@ -179,14 +235,15 @@ inline std::vector<Plan> plan_candidates(const PlanQuery& q, const Plan& fixed) 
 }
 
 // the dominant kernel of a plan, as rocprofv3 names it (minus "lbmk::" and blanks)
-// (arith: the kernels' Arith value, 0..5, 8, 9; the region shapes follow its strict / contracted half)
+// (arith: the kernels' Arith value, 0..5, 8, 9; the region shapes follow its strict / contracted half; the store policy is the row's)
 inline std::string plan_kernel_name(int fuse, int deep, int pair_ty, int nt, int arith, int esize) {
     char name[96];
     const char* t = esize == 4 ? "float" : "double";
-    const bool tall = esize == 4 ? deep == 8 : deep_is_park(deep);      // (tall fp32 regions and seven-iteration launches: plain stores only)
-    const char* nts = nt && !(tall && esize == 4) && !(deep_is_col(deep) && deep_depth(deep) == 7) ? "true" : "false";
-    if (fuse > 2 && deep_is_col(deep)) snprintf(name, sizeof(name), "k_stepc_col<%s,%d,%d,%d,%s,%d>", t, col_rows_per_thread(esize, (arith & 1) == 0, tall), col_waves(esize, (arith & 1) == 0, tall), deep_depth(deep), nts, arith);
-    else if (fuse > 2 && deep) snprintf(name, sizeof(name), "k_stepd_tile<%s,%s,%d,%d>", t, deep_tile(deep), deep_depth(deep), arith);
+    const RegionKind* k = deep_kind(deep);
+    const RowsWaves rw = k ? col_rw(*k, esize, arith & 1) : RowsWaves{};
+    const char* nts = nt && (!k || col_depth(*k, deep_depth(deep))->nt) ? "true" : "false";
+    if (fuse > 2 && k) snprintf(name, sizeof(name), "k_stepc_col<%s,%d,%d,%d,%s,%d>", t, rw.rows, rw.waves, deep_depth(deep), nts, arith);
+    else if (fuse > 2 && deep) snprintf(name, sizeof(name), "k_stepd_tile<%s,%d,%d,%d,%d>", t, deep_shape(deep)->tile_w, deep_shape(deep)->tile_h, deep_depth(deep), arith);
     else if (fuse == 4) snprintf(name, sizeof(name), "k_step4_tile<%s,8,%d,%d>", t, esize == 8 ? 1024 : 512, arith);
     else if (fuse > 1) snprintf(name, sizeof(name), "k_step%d_tile<%s,%d,%d,%d>", fuse, t, pair_ty, pair_ty == 12 ? (fuse == 3 ? 1024 : 768) : 512, arith);
     else snprintf(name, sizeof(name), "k_step_site<%s,0,%s,%d>", t, nts, arith);

@@ -1,13 +1,10 @@
 // csrc/lbm_step_k.hip — the single-iteration and fused tile kernel families (k_step_site, k_step2/3/4_tile, k_stepd_tile) of ONE collision
 // model and their launchers (lbm_launch_k.hpp), for both element types: compiled once per model with -DLBM_AR_BASE=<the model's Arith
-// base> (-DLBM_AR_FORCED_BASE=8 for the forced one; build.py), side by side with the host translation unit. MODE_STREAM_ONLY has no collision in it: base 0 alone holds it.
+// base> (build.py), side by side with the host translation unit. MODE_STREAM_ONLY has no collision in it: base 0 alone holds it.
 #include "lbm_launch_k.hpp"
 
-#if !defined(LBM_AR_BASE) && defined(LBM_AR_FORCED_BASE)   // the forced model's objects carry a flag of their own (build.py FORCED_BASES)
-#define LBM_AR_BASE LBM_AR_FORCED_BASE
-#endif
 #ifndef LBM_AR_BASE
-#error "compile with -DLBM_AR_BASE=<Arith base of a collision model: 0, 2 or 4> or -DLBM_AR_FORCED_BASE=8"
+#error "compile with -DLBM_AR_BASE=<Arith base of a collision model: 0, 2, 4 or 8>"
 #endif
 
 namespace lbmk {
@@ -29,18 +26,16 @@ void launch_site(const KArgs<T>& a, int mode, bool nt, bool fast, hipStream_t s)
 }
 
 template <typename T, int ARB>
-void launch_deep(const KArgs<T>& a, const K2Extra<T>& e, int shape, bool fast, hipStream_t s) {
-    constexpr int ARS = ARB, ARC = ARB | 1;
-#define LBM_KD(TX_, TY_, D_) do { \
-        dim3 gridd((a.nx + TX_ - 1) / TX_, (a.y_cnt + TY_ - 1) / TY_ + (a.y_cnt2 + TY_ - 1) / TY_); \
-        if (fast) hipLaunchKernelGGL((k_stepd_tile<T, TX_, TY_, D_, ARC>), gridd, dim3(TX_ * TY_), 0, s, a, e); \
-        else hipLaunchKernelGGL((k_stepd_tile<T, TX_, TY_, D_, ARS>), gridd, dim3(TX_ * TY_), 0, s, a, e); } while (0)
-    switch (shape) {
-        case 1: LBM_KD(64, 16, 6); break;
-        case 2: LBM_KD(64, 16, 7); break;
-        default: LBM_KD(32, 32, 8); break;
-    }
-#undef LBM_KD
+bool launch_deep(const KArgs<T>& a, const K2Extra<T>& e, int shape, bool fast, hipStream_t s) {
+    return with_row<std::size(deep_shapes)>([&](size_t i) { return deep_shapes[i].id == shape && deep_shapes[i].kind < 0; }, [&](auto i) {
+        constexpr DeepShape S = deep_shapes[i()];
+        if constexpr (S.kind < 0) {
+            constexpr int TX = S.tile_w, TY = S.tile_h;
+            dim3 gridd((a.nx + TX - 1) / TX, (a.y_cnt + TY - 1) / TY + (a.y_cnt2 + TY - 1) / TY);
+            if (fast) hipLaunchKernelGGL((k_stepd_tile<T, TX, TY, S.depth, ARB | 1>), gridd, dim3(TX * TY), 0, s, a, e);
+            else hipLaunchKernelGGL((k_stepd_tile<T, TX, TY, S.depth, ARB>), gridd, dim3(TX * TY), 0, s, a, e);
+        }
+    });
 }
 
 template <typename T, int ARB>
@@ -65,7 +60,7 @@ void launch_tile(const KArgs<T>& a, const K2Extra<T>& e, int depth, int ty, bool
 
 #define LBM_STEP_K_INST(T_) \
     template void launch_site<T_, LBM_AR_BASE>(const KArgs<T_>&, int, bool, bool, hipStream_t); \
-    template void launch_deep<T_, LBM_AR_BASE>(const KArgs<T_>&, const K2Extra<T_>&, int, bool, hipStream_t); \
+    template bool launch_deep<T_, LBM_AR_BASE>(const KArgs<T_>&, const K2Extra<T_>&, int, bool, hipStream_t); \
     template void launch_tile<T_, LBM_AR_BASE>(const KArgs<T_>&, const K2Extra<T_>&, int, int, bool, hipStream_t);
 LBM_STEP_K_INST(double)
 LBM_STEP_K_INST(float)

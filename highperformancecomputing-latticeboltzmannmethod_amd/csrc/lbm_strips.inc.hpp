@@ -278,16 +278,17 @@ inline bool face_south(const lbm_ctx* c) { return c->p.y_start > 0 || c->loopbac
 inline bool face_north(const lbm_ctx* c) { return c->p.y_start + c->nyl < c->p.ny || c->loopback; }
 
 template <typename T>
-void launch_depth(const lbm_ctx* c, const KArgs<T>& a, int depth, hipStream_t s) {
+int launch_depth(const lbm_ctx* c, const KArgs<T>& a, int depth, hipStream_t s) {
     if (c->rec) {
         ChoreoOp o; o.kind = ChoreoOp::KERNEL; o.strip = c->group_k; o.stream = stream_id(c, s); o.buf = a.dst == c->buf[0] ? 0 : 1;
         o.t = a.t; o.depth = depth;
         o.w0[0] = a.y_lo; o.w1[0] = a.y_lo + a.y_cnt; o.w0[1] = a.y_lo2; o.w1[1] = a.y_lo2 + a.y_cnt2;
         c->rec->ops.push_back(o);
-        return;
+        return LBM_OK;
     }
-    if (depth > 1) launch_fused_rows<T>(c, a, depth, s);
-    else launch_rows<T, MODE_STEP>(c, a, s);
+    if (depth > 1) return launch_fused_rows<T>(c, a, depth, s);
+    launch_rows<T, MODE_STEP>(c, a, s);
+    return LBM_OK;
 }
 
 // Decide the next launch of a context that still has `remaining` iterations to go in this call. Fusion: d iterations are
@@ -330,14 +331,12 @@ inline int plan_launch(lbm_ctx* c, int remaining, int of, bool transport, bool s
             // of a few launches never earns back — the driver's 20-step window, three launches, ran 15 % slower split than whole. A
             // sequence of range launches starts only with "split_min" launches ahead, and then runs to the segment's end.)
             c->split_now = c->split_i > 0 || seg >= c->split_min * deep;
-            // depths the plan's kernel family offers: the register kernel five and six iterations anywhere, seven on a
-            // context without strip faces (a strip's ghost rows go six deep); the LDS shapes their own depth only
+            // depths the plan's kernel family offers: its own, and what the region kind of a register shape lists (region_kinds: some
+            // not on a context with strip faces, whose ghost rows go six deep); the LDS shapes their own depth only
             auto in_family = [&](int d) {
                 if (d == deep) return true;
-                if (!deep_is_col(c->deep)) return false;
-                if (deep_is_park(c->deep)) return d == 5 || d == 6 || d == 7;            // (whole domains only)
-                if (deep_is_tall(c->deep)) return d == 6 || (d == 8 && !phys_face);       // (a strip exchanges seven rows on this plan)
-                return d == 5 || d == 6 || (d == 7 && !phys_face);
+                const ColDepth* o = deep_is_col(c->deep) ? col_depth(*deep_kind(c->deep), d) : nullptr;
+                return o && !(o->no_face && phys_face);
             };
             int fam_min = deep;
             for (int d = 2; d < deep; ++d) if (in_family(d)) { fam_min = d; break; }
@@ -474,7 +473,7 @@ int issue_split(lbm_ctx* c, KArgs<T> a, const Launch& L, int n, const int* cut_r
         if (i == 1) QCHK(q_wait(c, s, c, ev[1]));
         else if (i >= 3 && !c->debug_skip_split_wait) QCHK(q_wait(c, s, c, ev[i % 3]));      // (TEST ONLY: the checker must name the race)
         a.y_lo = cut[j]; a.y_cnt = cut[j + 1] - cut[j];
-        launch_depth<T>(c, a, L.depth, s);
+        QCHK(launch_depth<T>(c, a, L.depth, s));
         LAUNCHED(c);
         QCHK(q_record(c, ev[i % 3], s));
         c->split_i = i + 1 < 18 ? i + 1 : i + 1 - 6;      // (parity and residue mod 3 are all that matter past the first three)
@@ -496,7 +495,7 @@ int issue_before(lbm_ctx* c, const Launch& L) {
         const int n = (c->deep_now && c->split_now && split_possible(c)) ? split_ranges(c, L.depth, cut) : 0;
         if (n) return issue_split<T>(c, a, L, n, cut);
         QCHK(split_join(c));
-        launch_depth<T>(c, a, L.depth, c->stream);
+        QCHK(launch_depth<T>(c, a, L.depth, c->stream));
         LAUNCHED(c);
         return LBM_OK;
     }
@@ -514,12 +513,12 @@ int issue_before(lbm_ctx* c, const Launch& L) {
             // that do not depend on it start now on the main stream; the bands next to the faces (and the extension)
             // follow the exchange on the side stream. The next launch waits for ev_edge.
             a.y_lo = e0; a.y_cnt = c->nyl - e0 - e1; a.reverse = rev;
-            launch_depth<T>(c, a, L.depth, c->stream);
+            QCHK(launch_depth<T>(c, a, L.depth, c->stream));
             LAUNCHED(c);
             KArgs<T> b = make_kargs<T>(c, L.src, L.dst, L.t);
             b.y_lo = -es; b.y_cnt = e0 + es; b.y_lo2 = c->nyl - e1; b.y_cnt2 = e1 + en;
             if (b.y_cnt == 0) { b.y_lo = b.y_lo2; b.y_cnt = b.y_cnt2; b.y_cnt2 = 0; }
-            launch_depth<T>(c, b, L.depth, c->comm_stream);
+            QCHK(launch_depth<T>(c, b, L.depth, c->comm_stream));
             LAUNCHED(c);
             QCHK(q_record(c, c->ev_edge, c->comm_stream));
             c->ext_split_pending = true;
@@ -530,7 +529,7 @@ int issue_before(lbm_ctx* c, const Launch& L) {
         a.y_lo = -es;
         a.y_cnt = c->nyl + es + en;
         a.reverse = rev;
-        launch_depth<T>(c, a, L.depth, c->stream);
+        QCHK(launch_depth<T>(c, a, L.depth, c->stream));
         LAUNCHED(c);
         return LBM_OK;
     }
@@ -549,7 +548,7 @@ int issue_before(lbm_ctx* c, const Launch& L) {
         rc = wait_for_neighbour_pulls(c->stream);
         if (rc) return rc;
         a.reverse = rev;
-        launch_depth<T>(c, a, L.depth, c->stream);
+        QCHK(launch_depth<T>(c, a, L.depth, c->stream));
         LAUNCHED(c);
         QCHK(q_record(c, c->ev_edge, c->stream));
         if (c->overlap == 2) {
@@ -572,7 +571,7 @@ int issue_before(lbm_ctx* c, const Launch& L) {
     a.reverse = 0;
     a.y_lo = 0; a.y_cnt = e0; a.y_lo2 = c->nyl - e1; a.y_cnt2 = e1;
     if (e0 == 0) { a.y_lo = a.y_lo2; a.y_cnt = e1; a.y_cnt2 = 0; }
-    launch_depth<T>(c, a, L.depth, c->comm_stream);
+    QCHK(launch_depth<T>(c, a, L.depth, c->comm_stream));
     LAUNCHED(c);
     QCHK(q_record(c, c->ev_edge, c->comm_stream));
     c->edge_rows[0] = e0; c->edge_rows[1] = e1;
@@ -591,7 +590,7 @@ int issue_after(lbm_ctx* c, const Launch& L) {
                 KArgs<T> a = make_kargs<T>(c, L.src, L.dst, L.t);
                 a.y_lo = e0; a.y_cnt = c->nyl - e0 - e1;
                 a.reverse = (c->alternate && (c->launches_total & 1)) ? 1 : 0;
-                launch_depth<T>(c, a, L.depth, c->stream);
+                QCHK(launch_depth<T>(c, a, L.depth, c->stream));
                 LAUNCHED(c);
             }
         }

@@ -85,9 +85,9 @@ int choose_plan(lbm_ctx* c) {
     auto split_worth_trying = [&](const Plan& pl) {
         if (c->split_pinned || !deep_is_col(pl.deep)) return false;
         const int d = deep_depth(pl.deep), OW = col_tile_w(d), OH = deep_rows(c, pl.deep, d);
-        // (a 64x40 region is a quarter more work than the 64x32 one the six rounds were counted in: a seven-iteration launch of them at
+        // (rows per thread over the 64x32 kind's: a 64x40 region is a quarter more work than the 64x32 one the six rounds were counted in: a seven-iteration launch of them at
         // 4096x1024 is 5.7 rounds of blocks and gains more from the ranges than any, 153.8 -> 165.0 GLUPS, profiles/col_parked/README.md)
-        const long tiles = (long)((c->nx + OW - 1) / OW) * ((c->nyl + OH - 1) / OH) * (deep_is_park(pl.deep) ? 5 : 4) / 4;
+        const long tiles = (long)((c->nx + OW - 1) / OW) * ((c->nyl + OH - 1) / OH) * col_rw(*deep_kind(pl.deep), (int)c->esize, c->arith != 0).rows / col_rw(region_kinds[RK_STD], (int)c->esize, c->arith != 0).rows;
         int cut[5];
         c->split = 3;
         const bool ok = split_possible(c) && split_ranges(c, d, cut) && tiles >= 6L * 2 * c->num_cus;
@@ -343,9 +343,9 @@ int tune_strip_schedule(lbm_ctx* c) {
     // on strips too; which of the two is faster is a COLLECTIVE measurement like the schedule — the launch depth must be the same
     // on every rank, and the reduced timings are (one rank of eight exchanging with itself, 4096x128: 7.36 -> 6.78 us per iteration).
     std::string depth_note;
-    if (!res.empty() && c->deep == 1) {
+    if (!res.empty() && c->deep == DEEP_LDS6) {
         Res best8{1, 1, 1e30};      // (an eight-iteration launch refreshes eight rows after every launch: deep_halo has no say)
-        c->deep = 3; c->fuse = deep_depth(3);
+        c->deep = DEEP_LDS8; c->fuse = deep_depth(DEEP_LDS8);
         for (int o = 1; o >= 0; --o) {
             if (c->overlap_pinned && o != c->overlap) continue;
             double a = 0.0, b = 0.0;
@@ -362,7 +362,7 @@ int tune_strip_schedule(lbm_ctx* c) {
             res[0] = best8;
             snprintf(c->plan_desc, sizeof(c->plan_desc), "row-interleaved/8-step 32x32%s/xcd (strip depth measured over the ranks)", c->use_nt ? "/nt-store" : "");
         } else {
-            c->deep = 1; c->fuse = deep_depth(1);
+            c->deep = DEEP_LDS6; c->fuse = deep_depth(DEEP_LDS6);
         }
         snprintf(c->plan_opts, sizeof(c->plan_opts), "%s", plan_option_string(c->layout, c->use_nt, c->alternate, c->pair_ty, c->xcd, c->fuse, c->deep, c->use_ntl).c_str());
     }

@@ -612,6 +612,12 @@ int lbm_debug_ring(int capacity, const int* ops, int nops, int* out3);
 /* Test hook, callable without a device: the candidate plans lbm_initialise would time on a whole-domain context of this grid
  * (csrc/lbm_plan.hpp), one per line: "name|lbm_set_option pairs|dominant kernel|iterations per launch". */
 int lbm_debug_plan_candidates(int nx, int ny, int precision, int arith, int num_cus, char* out, int cap);
+/* Test hook, callable without a device: the table behind option "deep" (csrc/lbm_plan.hpp deep_shapes, region_kinds), one line per id,
+ * precision and arithmetic mode that exists: "id|f64 or f32|strict or contracted|lds or registers|iterations per launch|width|height of
+ * the tile or region|rows per thread|waves|offered depths|restrictions". An offered depth of a register shape reads
+ * "depth:nt+plain" or "depth:plain" (the store policies instantiated), with ":no-face" where a context with a strip face may not
+ * launch it. LBM_ERR_ARG: a null pointer or a buffer too small. */
+int lbm_debug_deep_shapes(char* out, int cap);
 /* Test hook, callable without a device: the host threads that drive the strips of an in-process group (csrc/lbm_ctx.hpp GroupPool) on a
  * dummy job of `rounds` rounds with one rendezvous each, `repeat` times on one pool; in the last run strip `fail_strip` reports an
  * injected error in round `fail_round` and strip `stall_strip` sleeps `stall_ms` before the rendezvous of round `stall_round` (-1:

@@ -3,6 +3,7 @@ GPU run against a reference run, case tables.
 
 A fixture is shared by importing it by name into the test module (pytest finds it there like one defined there)."""
 import collections
+import functools
 import importlib
 import os
 import re
@@ -34,6 +35,28 @@ def lbm_cpu():
 def solver():
     subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, PKG, "host")])
     return EXE
+
+
+# ---- the deep launch shapes ------------------------------------------------------------------------------------------------------
+DeepRow = collections.namedtuple("DeepRow", "id precision arith family depth w h rows waves offered only")
+
+
+@functools.lru_cache(maxsize=None)
+def deep_shapes():
+    """The library's table behind option "deep" (lbm_debug_deep_shapes, csrc/lbm_plan.hpp; no device needed): {(id, "f64" | "f32",
+    contracted 0 | 1): DeepRow}. `offered`: ((depth, "nt+plain" | "plain", barred with a strip face), ...) of a register shape."""
+    import ctypes
+    pkg = importlib.import_module(PKG)
+    pkg.build_all()
+    L = ctypes.CDLL(pkg.lib_path())
+    buf = ctypes.create_string_buffer(1 << 14)
+    assert L.lbm_debug_deep_shapes(buf, len(buf)) == 0
+    rows = {}
+    for line in buf.value.decode().splitlines():
+        i, precision, arith, family, depth, w, h, r, nw, offered, only = line.split("|")
+        off = tuple((int(o.split(":")[0]), o.split(":")[1], o.endswith(":no-face")) for o in offered.split()) if family == "registers" else ((int(offered), "", False),)
+        rows[int(i), precision, int(arith == "contracted")] = DeepRow(int(i), precision, arith, family, int(depth), int(w), int(h), int(r), int(nw), off, only)
+    return rows
 
 
 # ---- golden fixtures and error norms ---------------------------------------------------------------------------------------------

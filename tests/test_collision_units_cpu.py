@@ -31,6 +31,6 @@ def test_every_collision_base_has_the_same_units(build):
         if base:
             rest = tuple(f for f in flags if f not in base)
             kinds.setdefault(int(base[0].split("=")[1]), set()).add((src, rest, re.sub(r"_ar\d+", "", obj)))
-    assert sorted(kinds) == sorted(build.COLLISION_BASES) == [0, 2, 4]
-    assert kinds[0] == kinds[2] == kinds[4] and len(kinds[0]) == 3
+    assert sorted(kinds) == sorted(build.COLLISION_BASES) == [0, 2, 4, 8]
+    assert kinds[0] == kinds[2] == kinds[4] == kinds[8] and len(kinds[0]) == 3
     assert {src for src, _, _ in kinds[0]} == {"lbm_step_k.hip", "lbm_col.hip"}

@@ -10,7 +10,7 @@ import pytest
 
 from oracle.oracle import Oracle, make_params
 from tests import feature_cases as fc
-from tests.helpers import PKG, PLANS, ROOT
+from tests.helpers import PKG, PLANS, ROOT, deep_shapes
 from tests.reference import FREESLIP, NOSLIP, oracle_run
 
 ALL = fc.fp64_cases() + fc.fp32_cases()
@@ -143,29 +143,23 @@ def test_the_lean_cases_feel_their_model_and_walls(model):
 
 
 # ---- the lean tiles ------------------------------------------------------------------------------------------------------------------
-DEPTH = {1: 6, 2: 7, 3: 8, 6: 5, 7: 6, 8: 7, 9: 7, 10: 6, 11: 7}       # deep_depth (csrc/lbm_plan.hpp)
-
-
 def region_height(precision, strict, tall):
-    """col_rows_per_thread * col_waves (csrc/lbm_col_api.hpp): 24 strict fp64, 32 contracted fp64, 40 parked, 32 fp32, 48 tall fp32."""
-    f64 = precision == "f64"
-    rows = (6 if strict else 4) if tall and not f64 else 5 if tall and f64 and not strict else 2 if f64 and strict else 4
-    waves = 12 if (f64 and strict and not tall) or (not f64 and tall and not strict) else 8
-    return rows * waves
+    """Rows per thread * waves of the register kernel's regions as the library's table has them (csrc/lbm_plan.hpp region_kinds): 24 strict
+    fp64, 32 contracted fp64, 40 parked, 32 fp32, 48 tall fp32. `tall`: the kind of deep 8 (fp32) / deep 10 (fp64), else that of deep 7."""
+    return deep_shapes()[(7 if not tall else 10 if precision == "f64" else 8), precision, int(not strict)].h
 
 
 def tile_shape(plan, precision):
     """(OW, OH, HW) of the fused kernel the plan pins: its output tile and the rings its first level reaches beyond it, HW = D - 1.
     The register kernel (k_stepc_col): OW = 64 - 2 HW, OH = region height - 2 HW. The LDS tile families hand the same TileFrame their
-    tile: 64x16 (32x32 at eight iterations) for k_stepd_tile (deep_tile, csrc/lbm_plan.hpp), 64 x pair_ty (64x8 at four) for
+    tile: 64x16 (32x32 at eight iterations) for k_stepd_tile (deep_shapes, csrc/lbm_plan.hpp), 64 x pair_ty (64x8 at four) for
     k_step3_tile / k_step4_tile. None: one or two iterations per launch (k_step_site, k_step2_tile), which have no LEAN path."""
     o = fc.plan_options(plan)
     deep, strict = o.get("deep", 0), not o.get("arith", 0)
-    if deep >= 6:
-        hw = DEPTH[deep] - 1
-        return 64 - 2 * hw, region_height(precision, strict, deep in (8, 10, 11)) - 2 * hw, hw
     if deep:
-        return (32, 32, 7) if deep == 3 else (64, 16, DEPTH[deep] - 1)
+        row = deep_shapes()[deep, precision, int(not strict)]
+        hw = row.depth - 1
+        return (row.w - 2 * hw, row.h - 2 * hw, hw) if row.family == "registers" else (row.w, row.h, hw)
     fuse = o.get("fuse", 1)
     return (64, 8 if fuse == 4 else o["pair_ty"], fuse - 1) if fuse in (3, 4) and not o.get("pair") else None
 

@@ -73,7 +73,7 @@ def forced_row(lbm):
 
 def test_forced_model_has_the_units_of_base_0(lbm):
     build = __import__(PKG + ".build", fromlist=["build"])
-    assert build.FORCED_BASES == (8,) and build.COLLISION_BASES == (0, 2, 4)
+    assert 8 in build.COLLISION_BASES
     units = build.units("0123456789abcdef")
     assert len({obj for _, _, obj in units}) == len(units)
 
@@ -83,13 +83,12 @@ def test_forced_model_has_the_units_of_base_0(lbm):
             if "%s=%d" % (flag, base) in flags:
                 out.add((src, tuple(f for f in flags if not f.startswith(flag + "=")), re.sub(r"_ar\d+", "", obj)))
         return out
-    forced, bgk = kinds("-DLBM_AR_FORCED_BASE", 8), kinds("-DLBM_AR_BASE", 0)
+    forced, bgk = kinds("-DLBM_AR_BASE", 8), kinds("-DLBM_AR_BASE", 0)
     assert forced == bgk and len(forced) == 3
     assert {src for src, _, _ in forced} == {"lbm_step_k.hip", "lbm_col.hip"}
-    assert not kinds("-DLBM_AR_BASE", 8)                       # named by the flag of its own only
     tall, park = forced_row(lbm)
-    assert kinds("-DLBM_COL_FORCED_PARK", 8) == ({("lbm_col.hip", (), "lbm_col_park.o")} if park else set())
-    assert tuple(build.FORCED_PARK_BASES) == ((8,) if park else ())
+    assert kinds("-DLBM_COL_PARK", 8) == ({("lbm_col.hip", (), "lbm_col_park.o")} if park else set())
+    assert dict(build.COLLISION_MODELS)[8] == park
     # the tall fp32 objects are BGK's two alone, whatever the models: a row that granted them to the forced model would need a third
     assert not tall
     assert sorted(obj for _, flags, obj in units if any(f.startswith("-DLBM_COL_TALL=") for f in flags)) == ["lbm_col_tall_c.o", "lbm_col_tall_s.o"]
