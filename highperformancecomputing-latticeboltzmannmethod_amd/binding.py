@@ -35,10 +35,10 @@ class CkptHead(C.Structure):
                 ("cylinder_radius", C.c_double),
                 ("has_mask", C.c_int), ("has_profile", C.c_int), ("collision", C.c_int), ("has_walls", C.c_int), ("has_sched", C.c_int),
                 ("mask_digest", C.c_ulonglong), ("profile_digest", C.c_ulonglong), ("sched_digest", C.c_ulonglong),
-                ("collision_param", C.c_double * 2), ("walls", C.c_double * 4)]
+                ("collision_param", C.c_double * 2), ("walls", C.c_double * 4), ("has_ports", C.c_int), ("ports", C.c_double * 4)]
 
 
-CKPT_HEAD_MAX = 176                                            # LBM_CKPT_HEAD_MAX
+CKPT_HEAD_MAX = 184                                            # LBM_CKPT_HEAD_MAX
 
 _lib = None
 
@@ -102,6 +102,9 @@ def lib():
         L.lbm_set_wall.argtypes = [vp, C.c_int, C.c_int, C.c_double]
         L.lbm_get_wall.argtypes = [vp, C.c_int, C.POINTER(C.c_int), dp]
         L.lbm_debug_wall_rule.argtypes = [C.c_int, C.c_int, C.c_double, C.c_int, dp, dp]
+        L.lbm_set_port.argtypes = [vp, C.c_int, C.c_int, C.c_double]
+        L.lbm_get_port.argtypes = [vp, C.c_int, C.POINTER(C.c_int), dp]
+        L.lbm_debug_port_rule.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, dp, dp, dp, dp]
         L.lbm_set_inlet_schedule.argtypes = [vp, dp, C.c_int, C.c_int]
         L.lbm_inlet_schedule_length.argtypes = [vp]
         L.lbm_get_inlet_scale.argtypes = [vp, C.c_int, dp]
@@ -422,6 +425,55 @@ def debug_wall_rule(side, kind, velocity, f9, precision="f64"):
     return out
 
 
+PORT_SIDES = {"west": 0, "east": 1}                            # LBM_PORT_WEST / LBM_PORT_EAST
+PORT_KINDS = {"velocity": 0, "pressure": 1}                    # LBM_PORT_VELOCITY / LBM_PORT_PRESSURE
+_PORT_NAMES = {v: k for k, v in PORT_KINDS.items()}
+PORT_DEFAULTS = ((0, 0.0), (1, 1.0))                           # west (velocity, 0), east (pressure, 1): the reference's pair
+
+
+def _port_code(table, what, v):
+    """A side / kind given by name or by its LBM_PORT_* number -> the number (numbers pass through: the library checks their range)."""
+    if isinstance(v, str):
+        if v not in table:
+            raise ValueError(f"unknown port {what} {v!r}: one of {sorted(table)}")
+        return table[v]
+    return int(v)
+
+
+def _port_pair(ports):
+    """The ports= keyword as ((west kind, west value), (east kind, east value)): a pair (west, east) with west "velocity" or
+    ("pressure", rho) and east ("pressure", rho) or ("velocity", u); None in either place: that port's default."""
+    west, east = ports
+
+    def one(p, default, is_west):
+        if p is None:
+            return default
+        if isinstance(p, str):             # the bare name: the west velocity port alone, which is given no value here
+            if p != "velocity" or not is_west:
+                raise ValueError(f'a port is "velocity" (west only), ("pressure", rho) or ("velocity", u) (east only), not {p!r}'
+                                 f' in the {"west" if is_west else "east"} place')
+            return PORT_KINDS["velocity"], 0.0
+        kind, v = p
+        return _port_code(PORT_KINDS, "kind", kind), float(v)
+    return one(west, PORT_DEFAULTS[0], True), one(east, PORT_DEFAULTS[1], False)
+
+
+def debug_port_rule(side, kind, value, f9, u_in=0.0, precision="f64"):
+    """lbm_debug_port_rule (no device): the kernels' port rule on ONE cell. f9: the nine populations after the pull and the wall rule; they
+    are cast to the element type, the rule of port `side` ("west" / "east") with `kind` ("velocity" / "pressure") and `value` is applied
+    (a west velocity port is given u_in), and (the nine results, rho, u) come back as float64."""
+    a = np.ascontiguousarray(f9, dtype=np.float64)
+    if a.shape != (9,):
+        raise ValueError(f"a cell has nine populations, not shape {a.shape}")
+    out = np.empty(9, dtype=np.float64)
+    rho, u = C.c_double(), C.c_double()
+    rc = lib().lbm_debug_port_rule(_port_code(PORT_SIDES, "side", side), _port_code(PORT_KINDS, "kind", kind), float(value), float(u_in),
+                                   {"f64": 0, "f32": 1}[precision], _dp(a), _dp(out), C.byref(rho), C.byref(u))
+    if rc < 0:
+        raise LbmError(f"lbm_hip error {rc}: {lib().lbm_last_error().decode()}")
+    return out, rho.value, u.value
+
+
 def _dp(a):
     return a.ctypes.data_as(C.POINTER(C.c_double)) if a is not None else None
 
@@ -460,12 +512,15 @@ class Context:
     entries are "no-slip", "free-slip" or ("moving", u_w) with the wall's tangential velocity u_w. inlet_schedule: optional table of
     scale factors of the inflow, one per iteration (lbm_set_inlet_schedule): a table holds its last entry for ever, a pair
     (table, "repeat") is periodic (see cosine_ramp, sine_pulse). forcing: optional pair (fx, fy), a uniform driving force density in
-    lattice units on every fluid cell (lbm_set_forcing, Guo's scheme on BGK); (0, 0) / None: none; not with smagorinsky or trt_magic."""
+    lattice units on every fluid cell (lbm_set_forcing, Guo's scheme on BGK); (0, 0) / None: none; not with smagorinsky or trt_magic.
+    ports: optional pair (west, east) of the two open ends (lbm_set_port) in place of the velocity inlet and the pressure outlet with
+    rho = 1: west "velocity" or ("pressure", rho), east ("pressure", rho) or ("velocity", u); None in either place: that port's default.
+    A west pressure port takes neither inlet_profile nor inlet_schedule (initialise() fails)."""
 
     def __init__(self, nx, ny, tau=0.6, inlet_velocity=0.01333, cylinder_x=0.2, cylinder_y=0.5,
                  cylinder_radius=0.05, y_start=0, local_ny=0, precision="f64", device=0, force_log_capacity=0,
                  options=None, solid=None, inlet_profile=None, smagorinsky=None, bodies=None, frames=None, trt_magic=None,
-                 probes=None, probe_capacity=None, walls=None, inlet_schedule=None, forcing=None):
+                 probes=None, probe_capacity=None, walls=None, inlet_schedule=None, forcing=None, ports=None):
         if solid is not None and bodies is not None:
             raise LbmError("solid= and bodies= exclude each other: the body labels are the geometry (solid where nonzero)")
         self.L = lib()
@@ -500,6 +555,9 @@ class Context:
             self.set_inlet_schedule(*_schedule(inlet_schedule))
         if forcing is not None:
             self.set_forcing(*forcing)
+        if ports is not None:
+            for side, (kind, v) in zip(("west", "east"), _port_pair(ports)):
+                self.set_port(side, kind, v)
 
     def _chk(self, rc):
         if rc < 0:
@@ -607,6 +665,22 @@ class Context:
         v = C.c_double()
         self._chk(self.L.lbm_get_inlet_scale(self.h, int(t), C.byref(v)))
         return v.value
+
+    def set_port(self, side, kind, value=0.0):
+        """lbm_set_port: side "west" (column 0) / "east" (column nx - 1); kind "velocity" / "pressure" with the density of a pressure
+        port or the velocity of the east velocity port (0 for the west velocity port, which takes inlet_velocity, the profile and the
+        schedule); before initialise()."""
+        self._chk(self.L.lbm_set_port(self.h, _port_code(PORT_SIDES, "side", side), _port_code(PORT_KINDS, "kind", kind), float(value)))
+
+    def get_port(self, side):
+        """(kind name, value) of one port (lbm_get_port)."""
+        k, v = C.c_int(), C.c_double()
+        self._chk(self.L.lbm_get_port(self.h, _port_code(PORT_SIDES, "side", side), C.byref(k), C.byref(v)))
+        return _PORT_NAMES[k.value], v.value
+
+    def ports(self):
+        """((west kind, value), (east kind, value)) as set; (("velocity", 0.0), ("pressure", 1.0)) on a fresh context."""
+        return self.get_port("west"), self.get_port("east")
 
     def walls(self):
         """((south kind, velocity), (north kind, velocity)) as set; (("no-slip", 0.0), ("no-slip", 0.0)) on a fresh context."""
@@ -840,11 +914,12 @@ class Group:
     solid: optional global (ny, nx) obstacle mask, inlet_profile: optional global [ny] inlet velocities, smagorinsky: optional LES
     constant Cs, trt_magic: optional TRT magic parameter, bodies: optional global (ny, nx) body numbers (in place of solid), frames: optional frame stride k, probes / probe_capacity: optional probe points (global coordinates), walls: optional kinds of the
     bottom and top walls (as Context takes them), inlet_schedule: optional scale factors of the inflow per iteration (likewise), forcing:
-    optional driving force (fx, fy); all given to every member."""
+    optional driving force (fx, fy), ports: optional pair (west, east) of the two open ends (as Context takes them); all given to every
+    member."""
 
     def __init__(self, nx, ny, bounds, devices=None, transport="peer", options=None, solid=None, inlet_profile=None, smagorinsky=None,
                  bodies=None, frames=None, trt_magic=None, probes=None, probe_capacity=None, walls=None, inlet_schedule=None, forcing=None,
-                 **kw):
+                 ports=None, **kw):
         from .strips import partition_rows
         if isinstance(bounds, int):
             bounds = partition_rows(ny, bounds)
@@ -852,7 +927,8 @@ class Group:
         self.nx, self.ny = nx, ny
         self.ctxs = [Context(nx, ny, y_start=y0, local_ny=n, device=d, options=options, solid=solid, inlet_profile=inlet_profile,
                              smagorinsky=smagorinsky, bodies=bodies, frames=frames, trt_magic=trt_magic, probes=probes,
-                             probe_capacity=probe_capacity, walls=walls, inlet_schedule=inlet_schedule, forcing=forcing, **kw)
+                             probe_capacity=probe_capacity, walls=walls, inlet_schedule=inlet_schedule, forcing=forcing, ports=ports,
+                             **kw)
                      for (y0, n), d in zip(bounds, devices)]
         self.L = lib()
         self._arr = (C.c_void_p * len(self.ctxs))(*[c.h for c in self.ctxs])

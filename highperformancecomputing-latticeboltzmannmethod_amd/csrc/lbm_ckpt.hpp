@@ -16,6 +16,8 @@
 //                bit 4 (16)  4 doubles south kind, south velocity, north kind, north velocity; where a wall is not no-slip: lbm_set_wall
 //                bit 5 (32)  1 word    the inlet schedule's digest            lbm_set_inlet_schedule
 //                bit 6 (64)  2 doubles the force {fx, fy}                     lbm_set_forcing
+//                bit 7 (128) unassigned: a head that announces it is not a checkpoint
+//                bit 8 (256) 4 doubles west kind, west value, east kind, east value; where a port is off its default: lbm_set_port
 //              (the bits and sizes of the collision parameters are those of collision_models, lbm_plan.hpp; a context has one model)
 //        then  the post-collision populations P_{steps_done} of the strip's interior, [9][local_ny][nx] in the element type
 // "LBMCKPT2" is the fixed header, the mask's digest (no flags) and the populations; "LBMCKPT1" the fixed header and the populations.
@@ -26,13 +28,14 @@
 // low and the high half of each velocity's bit pattern}; schedule {mode, n, the halves of each factor}.
 // A context loads only a file that announces exactly the fields it has, with equal values (doubles compared as numbers) and an equal
 // fixed header but for steps_done. The refusal names the first difference in this order: the collision models from the last row of
-// collision_models to the first (forcing, TRT, Smagorinsky), the walls, the inlet profile, the inlet schedule, the mask, the header.
+// collision_models to the first (forcing, TRT, Smagorinsky), the walls, the ports, the inlet profile, the inlet schedule, the mask, the header.
 #pragma once
 #include <algorithm>
 #include <array>
 #include <cstdarg>
 #include <cstddef>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <iterator>
 #include <string>
@@ -134,8 +137,25 @@ inline std::string walls_refusal(const CkptField&, CkptRefusal r, const lbm_ckpt
     return ckpt_text("for different walls: south kind %g u = %.17g, north kind %g u = %.17g; this context has south kind %d u = %.17g, north kind %d u = %.17g",
                      w[0], w[1], w[2], w[3], (int)m[0], m[1], (int)m[2], m[3]);
 }
+// (a port's value with the fewest digits that read back exactly: 0.99, not 0.98999999999999999)
+inline std::string shortest_text(double v) {
+    char b[64];
+    for (int digits = 1; digits <= 17; ++digits) {
+        snprintf(b, sizeof(b), "%.*g", digits, v);
+        if (strtod(b, nullptr) == v) break;
+    }
+    return b;
+}
+inline std::string ports_text(const double* p) {
+    return ckpt_text("ports west kind %g value %s, east kind %g value %s", p[0], shortest_text(p[1]).c_str(), p[2], shortest_text(p[3]).c_str());
+}
+inline std::string ports_refusal(const CkptField&, CkptRefusal r, const lbm_ckpt_head& file, const lbm_ckpt_head& here) {
+    if (r == CkptRefusal::file_lacks) return "with the default ports; this context has " + ports_text(here.ports);
+    if (r == CkptRefusal::context_lacks) return "with " + ports_text(file.ports) + "; this context has the default ports";
+    return "with " + ports_text(file.ports) + "; this context has " + ports_text(here.ports);
+}
 
-// ---- the table: the four fields of the setters, and one per collision model that has a parameter ----
+// ---- the table: the five fields of the setters, and one per collision model that has a parameter ----
 constexpr int CKPT_MODELS = (int)std::size(collision_models);
 constexpr int ckpt_model_fields() {
     int n = 0;
@@ -143,13 +163,14 @@ constexpr int ckpt_model_fields() {
     return n;
 }
 constexpr auto make_ckpt_fields(bool by_rank) {
-    std::array<CkptField, 4 + ckpt_model_fields()> t{{
-        {1, 1, &lbm_ckpt_head::has_mask, 1, offsetof(lbm_ckpt_head, mask_digest), false, CKPT_MODELS + 2, digest_refusal, "obstacle mask"},
-        {2, 1, &lbm_ckpt_head::has_profile, 1, offsetof(lbm_ckpt_head, profile_digest), false, CKPT_MODELS, digest_refusal, "inlet profile"},
+    std::array<CkptField, 5 + ckpt_model_fields()> t{{
+        {1, 1, &lbm_ckpt_head::has_mask, 1, offsetof(lbm_ckpt_head, mask_digest), false, CKPT_MODELS + 3, digest_refusal, "obstacle mask"},
+        {2, 1, &lbm_ckpt_head::has_profile, 1, offsetof(lbm_ckpt_head, profile_digest), false, CKPT_MODELS + 1, digest_refusal, "inlet profile"},
         {16, 4, &lbm_ckpt_head::has_walls, 1, offsetof(lbm_ckpt_head, walls), true, CKPT_MODELS - 1, walls_refusal, "walls"},
-        {32, 1, &lbm_ckpt_head::has_sched, 1, offsetof(lbm_ckpt_head, sched_digest), false, CKPT_MODELS + 1, digest_refusal, "inlet schedule"},
+        {32, 1, &lbm_ckpt_head::has_sched, 1, offsetof(lbm_ckpt_head, sched_digest), false, CKPT_MODELS + 2, digest_refusal, "inlet schedule"},
+        {256, 4, &lbm_ckpt_head::has_ports, 1, offsetof(lbm_ckpt_head, ports), true, CKPT_MODELS, ports_refusal, "ports"},
     }};
-    int k = 4;
+    int k = 5;
     for (int i = 0; i < CKPT_MODELS; ++i) {
         const CollisionModel& m = collision_models[i];
         if (m.ckpt_bit) t[k++] = {m.ckpt_bit, m.nparam, &lbm_ckpt_head::collision, m.base, offsetof(lbm_ckpt_head, collision_param), true, CKPT_MODELS - 1 - i, param_refusal, m.param};
@@ -163,14 +184,15 @@ constexpr auto ckpt_refusal_order = make_ckpt_fields(true);    // in the order o
 constexpr int CKPT_FIXED = 64;      // the bytes of the fixed header behind the magic: the head's leading members as they stand
 static_assert(offsetof(lbm_ckpt_head, has_mask) == CKPT_FIXED && offsetof(lbm_ckpt_head, tau) == 24, "the fixed header is written as it lies in lbm_ckpt_head");
 constexpr int ckpt_head_max() {
-    int n = 8 + CKPT_FIXED + 8;
+    int n = 8 + CKPT_FIXED + 8, model = 0;
     unsigned long long seen = 0;
     for (const CkptField& f : ckpt_fields) {
         if (!f.bit || (seen & f.bit)) return -1;       // (every field has a bit of its own)
         seen |= f.bit;
-        n += 8 * f.words;
+        if (f.key == &lbm_ckpt_head::collision) model = f.words > model ? f.words : model;      // (a head has one collision model: the longest)
+        else n += 8 * f.words;
     }
-    return n;
+    return n + 8 * model;
 }
 static_assert(ckpt_head_max() > 0 && ckpt_head_max() <= LBM_CKPT_HEAD_MAX, "LBM_CKPT_HEAD_MAX (include/lbm_hip.h) holds every head");
 

@@ -351,6 +351,12 @@ struct lbm_ctx {
     int wall_kind[2] = {0, 0};
     double wall_u[2] = {0.0, 0.0};
     bool has_walls() const { return wall_kind[0] != 0 || wall_kind[1] != 0; }
+    // The two ports (lbm_set_port), [0] west (column 0) and [1] east (column nx - 1): kind (lbm_kernels.hpp PortKind) and the value given,
+    // a density for a pressure port, a velocity for the east velocity port, 0 for the west velocity port (which takes inlet_velocity,
+    // the profile and the schedule). The reference's pair is the default. Every strip of a run carries both.
+    int port_kind[2] = {0, 1};
+    double port_value[2] = {0.0, 1.0};
+    bool has_ports() const { return port_kind[0] != 0 || port_kind[1] != 1 || port_value[1] != 1.0; }
     // options
     int alternate = 1;   // walk the rows bottom-up / top-down on alternate steps (Infinity Cache reuse)
     int use_nt = 0;      // non-temporal stores in the step kernel

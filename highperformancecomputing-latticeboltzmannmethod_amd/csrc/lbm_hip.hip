@@ -152,6 +152,8 @@ lbm_ckpt_head ckpt_head_of(const lbm_ctx* c) {
     h.has_walls = c->has_walls();
     h.walls[0] = (double)c->wall_kind[0]; h.walls[1] = c->wall_u[0]; h.walls[2] = (double)c->wall_kind[1]; h.walls[3] = c->wall_u[1];
     h.has_sched = c->has_sched(); h.sched_digest = c->sched_digest;
+    h.has_ports = c->has_ports();
+    h.ports[0] = (double)c->port_kind[0]; h.ports[1] = c->port_value[0]; h.ports[2] = (double)c->port_kind[1]; h.ports[3] = c->port_value[1];
     return h;
 }
 // lbm_load_state and lbm_debug_ckpt_load: the head in the first n bytes of `path` against the loading context's: the bytes it takes and
@@ -219,6 +221,35 @@ void debug_wall_rule(int side, int kind, double velocity, const double* in9, dou
     wall_rule<T>(f, side == LBM_WALL_SOUTH, side == LBM_WALL_NORTH, side == LBM_WALL_SOUTH ? wall_pack(kind, 0) : wall_pack(0, kind),
                  wall_ks<T>(kind, velocity, kind, velocity));
     for (int i = 0; i < Q; ++i) out9[i] = (double)f[i];
+}
+}  // namespace
+
+// ---- the two ports (lbm_set_port) ----
+namespace {
+// the argument checks shared by lbm_set_port and lbm_debug_port_rule; the text names the offender
+int check_port(const char* who, int side, int kind, double value) {
+    if (side != LBM_PORT_WEST && side != LBM_PORT_EAST) return fail(LBM_ERR_ARG, "%s: side = %d (0 west or 1 east only)", who, side);
+    if (kind != LBM_PORT_VELOCITY && kind != LBM_PORT_PRESSURE) return fail(LBM_ERR_ARG, "%s: kind = %d (0 velocity or 1 pressure only)", who, kind);
+    if (!std::isfinite(value)) return fail(LBM_ERR_ARG, "%s: value = %g (finite values only)", who, value);
+    if (kind == LBM_PORT_PRESSURE && value <= 0.0) return fail(LBM_ERR_ARG, "%s: pressure = %g (a density above 0 only)", who, value);
+    if (kind == LBM_PORT_VELOCITY && side == LBM_PORT_EAST && std::fabs(value) >= 1.0)
+        return fail(LBM_ERR_ARG, "%s: east velocity = %g (magnitude below 1 only)", who, value);
+    if (kind == LBM_PORT_VELOCITY && side == LBM_PORT_WEST && value != 0.0)
+        return fail(LBM_ERR_ARG, "%s: value = %g with a west velocity port (it takes inlet_velocity, the inlet profile and the inlet schedule; 0 only)", who, value);
+    return LBM_OK;
+}
+template <typename T>
+void debug_port_rule(int side, int kind, double value, double u_in, const double* in9, double* out9, double* rho_out, double* u_out) {
+    T f[Q];
+    for (int i = 0; i < Q; ++i) f[i] = (T)in9[i];
+    const bool west = side == LBM_PORT_WEST;
+    const T u_west = (T)u_in;
+    T rho = T(0), u = T(0);
+    port_rule<T>(f, west, !west, west ? port_pack(kind, PORT_PRESSURE) : port_pack(PORT_VELOCITY, kind), port_ks<T>(value, west ? PORT_PRESSURE : kind, value),
+                 [&]() { return u_west; }, rho, u);
+    for (int i = 0; i < Q; ++i) out9[i] = (double)f[i];
+    if (rho_out) *rho_out = (double)rho;
+    if (u_out) *u_out = (double)u;
 }
 }  // namespace
 
@@ -400,6 +431,11 @@ int lbm_initialise(lbm_ctx* c, int* solid_count_out) {
     if (!c) return fail(LBM_ERR_ARG, "null context");
     lbm_trace("initialise", "ctx %p %dx%d rows %d..%d begin", (void*)c, c->nx, c->p.ny, c->p.y_start, c->p.y_start + c->nyl);
     if (int rc = refuse_deep(c, c->collision, c->deep, true)) return rc;
+    // a west pressure port solves for the velocity: it takes none (the three settings are known only here)
+    if (c->port_kind[0] == LBM_PORT_PRESSURE && c->has_profile)
+        return fail(LBM_ERR_ARG, "lbm_initialise: an inlet profile (lbm_set_inlet_profile) with a west pressure port (lbm_set_port): a pressure port takes no inlet velocity");
+    if (c->port_kind[0] == LBM_PORT_PRESSURE && c->has_sched())
+        return fail(LBM_ERR_ARG, "lbm_initialise: an inlet schedule (lbm_set_inlet_schedule) with a west pressure port (lbm_set_port): a pressure port takes no inlet velocity");
     HIPCHK(hipSetDevice(c->device));
     if (c->has_sched()) { if (int rc = prepare_schedule(c)) return rc; }
     { int wr = wait_stream(c, c->stream, "compute stream (lbm_initialise)"); if (wr) return wr; }        // (re-)initialisation starts from quiet streams
@@ -867,6 +903,23 @@ int lbm_get_wall(const lbm_ctx* c, int side, int* kind, double* velocity) {
     return LBM_OK;
 }
 
+int lbm_set_port(lbm_ctx* c, int side, int kind, double value) {
+    if (!c) return fail(LBM_ERR_ARG, "lbm_set_port: null context");
+    if (c->initialised) return fail(LBM_ERR_ARG, "lbm_set_port must be called before lbm_initialise");
+    if (int rc = check_port("lbm_set_port", side, kind, value)) return rc;
+    c->port_kind[side] = kind;
+    c->port_value[side] = value;
+    return LBM_OK;
+}
+
+int lbm_get_port(const lbm_ctx* c, int side, int* kind, double* value) {
+    if (!c) return fail(LBM_ERR_ARG, "lbm_get_port: null context");
+    if (side != LBM_PORT_WEST && side != LBM_PORT_EAST) return fail(LBM_ERR_ARG, "lbm_get_port: side = %d (0 west or 1 east only)", side);
+    if (kind) *kind = c->port_kind[side];
+    if (value) *value = c->port_value[side];
+    return LBM_OK;
+}
+
 int lbm_set_inlet_schedule(lbm_ctx* c, const double* s, int n, int mode) {
     if (!c) return fail(LBM_ERR_ARG, "lbm_set_inlet_schedule: null context");
     if (c->initialised) return fail(LBM_ERR_ARG, "lbm_set_inlet_schedule must be called before lbm_initialise");
@@ -1321,6 +1374,17 @@ int lbm_debug_wall_rule(int side, int kind, double velocity, int precision, cons
     if (int rc = check_wall("lbm_debug_wall_rule", side, kind, velocity)) return rc;
     if (precision == LBM_PRECISION_F32) debug_wall_rule<float>(side, kind, velocity, f_in9, f_out9);
     else debug_wall_rule<double>(side, kind, velocity, f_in9, f_out9);
+    return LBM_OK;
+}
+
+/* TEST HOOK (no device needed): port_rule (lbm_kernels.hpp), the function the kernels call, on one cell in the element type of `precision`. */
+int lbm_debug_port_rule(int side, int kind, double value, double u_in, int precision, const double* f_in9, double* f_out9, double* rho_out, double* u_out) {
+    if (!f_in9 || !f_out9) return fail(LBM_ERR_ARG, "lbm_debug_port_rule: null pointer");
+    if (precision != LBM_PRECISION_F64 && precision != LBM_PRECISION_F32) return fail(LBM_ERR_ARG, "lbm_debug_port_rule: precision = %d", precision);
+    if (int rc = check_port("lbm_debug_port_rule", side, kind, value)) return rc;
+    if (!std::isfinite(u_in) || std::fabs(u_in) >= 1.0) return fail(LBM_ERR_ARG, "lbm_debug_port_rule: u_in = %g (finite values of magnitude below 1 only)", u_in);
+    if (precision == LBM_PRECISION_F32) debug_port_rule<float>(side, kind, value, u_in, f_in9, f_out9, rho_out, u_out);
+    else debug_port_rule<double>(side, kind, value, u_in, f_in9, f_out9, rho_out, u_out);
     return LBM_OK;
 }
 

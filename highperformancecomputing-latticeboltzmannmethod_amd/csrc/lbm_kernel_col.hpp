@@ -180,7 +180,7 @@ __global__ void __launch_bounds__(NW * 64, (col_min_waves<T, NW, AR>())) k_stepc
                     }
                 }
             }
-            if (bx == 0 && lane < R) {
+            if (bx == 0 && lane < R && !(a.walls & PORT_WEST_PRESSURE)) {       // (a west pressure port reads no inlet velocity: port_rule)
                 const int yg = a.y_start + Yr + ry0 + lane;
                 u_sh[w][lane] = (yg >= 0 && yg < a.ny_glob) ? a.u_row[yg] : T(0);
             }

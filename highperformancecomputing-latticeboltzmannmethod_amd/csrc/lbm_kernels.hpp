@@ -108,6 +108,26 @@ inline WallK<T> wall_ks(int south, double u_south, int north, double u_north) {
     return k;
 }
 
+// The two ports (lbm_set_port, include/lbm_hip.h LBM_PORT_*): the west one is column 0, the east one column nx - 1; each is a Zou-He
+// rule with the velocity given and the density solved for, or the density given and the velocity solved for. The two kinds ride in the
+// spare bits of the word that carries the walls (wall_pack above uses bits 0-3): bit 4 set = the west port is a PRESSURE port, bit 5
+// set = the east port is a VELOCITY port, so the reference's pair (velocity inlet, pressure outlet) is 0 in both.
+enum PortKind { PORT_VELOCITY = 0, PORT_PRESSURE = 1 };
+constexpr int PORT_WEST_PRESSURE = 16, PORT_EAST_VELOCITY = 32;
+__host__ __device__ constexpr int port_pack(int west_kind, int east_kind) {
+    return (west_kind == PORT_PRESSURE ? PORT_WEST_PRESSURE : 0) | (east_kind == PORT_VELOCITY ? PORT_EAST_VELOCITY : 0);
+}
+// What the two ports are given, formed on the host in double and cast once: the west port's density (read by a pressure port only; a
+// velocity port takes its velocity per row and iteration from u_row and the schedule) and the east port's density or velocity.
+// east_den is what the east rule divides S by: the density of a pressure port, 1 + u of a velocity port — that ONE addition in the
+// element type, the operation the table writes, done here once instead of by every thread of the column.
+template <typename T> struct PortK { T west, east, east_den; };
+template <typename T>
+inline PortK<T> port_ks(double west_value, int east_kind, double east_value) {
+    const T e = (T)east_value;
+    return PortK<T>{(T)west_value, e, east_kind == PORT_VELOCITY ? T(1.0) + e : e};
+}
+
 
 template <typename T>
 struct KArgs {
@@ -119,8 +139,11 @@ struct KArgs {
     // fields across the two by their alignment, up to 64 bytes. Four values behind `sched` part the two blocks and 26 earlier
     // instantiations came out with other scalar spills or vector register counts; with every field moved by 64 bytes, K2Extra's
     // included, each of them keeps its loads and its register allocation (profiles/forcing/README.md).
+    // The values of the two ports (lbm_set_port; the kinds ride in `walls`) stand in what was padding of this block, for the same
+    // reason: no field of KArgs or K2Extra moves. Launch-uniform: read inside the inlet / outlet branches of apply_bcs only.
     T frc_gx, frc_gy, frc_hx, frc_hy;
-    char frc_pad[64 - 4 * sizeof(T)];
+    PortK<T> pk;
+    char frc_pad[64 - 7 * sizeof(T)];
     const T* src;      // plane 0 of the buffer read  (P_t)
     T* dst;            // plane 0 of the buffer written (P_{t+1})
     long plane;        // elements per plane
@@ -155,7 +178,8 @@ struct KArgs {
     union { T les_c; T trt_wb; };
     // The two physical walls (lbm_set_wall), appended for the same reason: wall_pack of the two kinds, and what each wall adds to and
     // subtracts from its diagonal populations (wall_ks: k = u_w / 6 of a moving wall, formed on the host in double; the identity
-    // operands otherwise). Launch-uniform: read inside the bottom / top branches of apply_bcs only.
+    // operands otherwise). Launch-uniform: read inside the bottom / top branches of apply_bcs only. Bits 4 and 5 of `walls` are the
+    // kinds of the two ports (port_pack), read inside the inlet / outlet branches only.
     int walls;
     WallK<T> wk;
     // The inlet schedule (lbm_set_inlet_schedule), appended likewise: the device block {int n; int mode; T s[n]} (inlet_sched_at), nullptr
@@ -249,32 +273,58 @@ __host__ __device__ __forceinline__ void wall_rule(T (&f)[Q], bool bottom, bool 
     }
 }
 
+// The port rule of ONE fluid cell of column 0 (west) and / or column nx - 1 (east), after the pull and the wall rule: Zou and He's
+// closure on the reference's expressions (:181-206, :212-235) with ONE of (rho, u) given and the other solved for.
+//   west  S = f0 + f2 + f4 + 2 (f3 + f6 + f7)   VELOCITY: u = inlet_u(), rho = S / (1 - u)     PRESSURE: rho = pk.west, u = 1 - S / rho
+//   east  S = f0 + f2 + f4 + 2 (f1 + f5 + f8)   PRESSURE: rho = pk.east, u = -1 + S / rho      VELOCITY: u = pk.east,  rho = S / (1 + u)
+// and the three unknown populations from (rho, u) as the reference writes them. Every operation is one IEEE operation in the element
+// type in the order written (the library is built without contraction), so strict and contracted arithmetic apply the same bits. The
+// reference's pair is (VELOCITY, PRESSURE 1): S / 1 and (2/3) * 1 * u change no bit, so the default is no special case.
+// The kinds (bits of `walls`, port_pack) and the two values are launch-uniform; the branch on the kind sits inside the one-column branch.
+// `inlet_u` gives the west velocity of the cell's row at the iteration served and is called for a west VELOCITY port only: u_row[yg],
+// times the schedule's factor where there is one, ONE multiplication rounded before its uses. A schedule scales nothing else.
+// rho_bc / u_bc: (rho, u) of the rule applied, the east one where both ran (nx == 1), for the snapshot; untouched off the ports.
+// __host__ too: lbm_debug_port_rule applies this very function on the CPU.
+template <typename T, typename U>
+__host__ __device__ __forceinline__ void port_rule(T (&f)[Q], bool west, bool east, int walls, const PortK<T>& pk, U&& inlet_u,
+                                                   T& rho_bc, T& u_bc) {
+    if (west) {
+        const T S = f[0] + f[2] + f[4] + T(2.0) * (f[3] + f[6] + f[7]);
+        // (one division for both kinds: by the density given, or by 1 - u)
+        const bool pressure = walls & PORT_WEST_PRESSURE;
+        T rho = pk.west, u = T(0.0), den = pk.west;
+        if (!pressure) { u = inlet_u(); den = T(1.0) - u; }
+        const T q = S / den;
+        if (pressure) u = T(1.0) - q; else rho = q;
+        f[1] = f[3] + T(2.0 / 3.0) * rho * u;
+        f[5] = f[7] - T(0.5) * (f[2] - f[4]) + T(1.0 / 6.0) * rho * u;
+        f[8] = f[6] + T(0.5) * (f[2] - f[4]) + T(1.0 / 6.0) * rho * u;
+        rho_bc = rho; u_bc = u;
+    }
+    if (east) {
+        const T S = f[0] + f[2] + f[4] + T(2.0) * (f[1] + f[5] + f[8]);
+        // (one division for both kinds: by the density given, or by 1 + u, which port_ks has formed: pk.east_den)
+        const bool velocity = walls & PORT_EAST_VELOCITY;
+        const T q = S / pk.east_den;
+        const T rho = velocity ? q : pk.east, u = velocity ? pk.east : T(-1.0) + q;
+        f[3] = f[1] - T(2.0 / 3.0) * rho * u;
+        f[6] = f[8] - T(0.5) * (f[2] - f[4]) - T(1.0 / 6.0) * rho * u;
+        f[7] = f[5] + T(0.5) * (f[2] - f[4]) - T(1.0 / 6.0) * rho * u;
+        rho_bc = rho; u_bc = u;
+    }
+}
+
 // apply_boundary_conditions on the pulled populations of ONE cell, in the reference's sequential loop order
 // bottom -> top -> inlet -> outlet (LBMSolver.h:152-236). Solid cells are skipped by every one
-// of those loops. Returns nothing; rho_bc/u_out are exposed for the macro snapshot kernel.
+// of those loops. Returns nothing; rho_bc/u_bc are exposed for the macro snapshot kernel.
 // The inlet velocity of global row yg is u_row[yg] (KArgs::u_row): loaded inside the inlet branch only, so no cell off column 0
-// carries its address or value. The two walls are wall_rule above: the one statement of it, for the step kernels and the snapshot.
-// `inlet_u` gives the inlet velocity of the cell's row at the iteration served and is called inside the inlet branch only: u_row[yg],
-// times the schedule's factor where there is one — ONE IEEE multiplication in the element type, rounded before the two uses below (the
-// library is built without contraction), so strict and contracted arithmetic apply the same bits here.
+// carries its address or value. The two walls are wall_rule above, the two open ends port_rule: the one statement of each, for the
+// step kernels and the snapshot.
 template <typename T, typename U>
 __device__ __forceinline__ void apply_bcs(T (&f)[Q], bool bottom, bool top, bool inlet, bool outlet, U&& inlet_u,
-                                          int walls, const WallK<T>& wk, T& rho_bc, T& u_out) {
+                                          int walls, const WallK<T>& wk, const PortK<T>& pk, T& rho_bc, T& u_bc) {
     wall_rule(f, bottom, top, walls, wk);
-    if (inlet) {                                                              // :181-206 (Zou-He velocity)
-        const T u_in = inlet_u();
-        rho_bc = (f[0] + f[2] + f[4] + T(2.0) * (f[3] + f[6] + f[7])) / (T(1.0) - u_in);
-        f[1] = f[3] + T(2.0 / 3.0) * rho_bc * u_in;
-        f[5] = f[7] - T(0.5) * (f[2] - f[4]) + T(1.0 / 6.0) * rho_bc * u_in;
-        f[8] = f[6] + T(0.5) * (f[2] - f[4]) + T(1.0 / 6.0) * rho_bc * u_in;
-    }
-    if (outlet) {                                                             // :212-235 (Zou-He pressure, rho=1)
-        const T rho_out = T(1.0);
-        u_out = T(-1.0) + (f[0] + f[2] + f[4] + T(2.0) * (f[1] + f[5] + f[8])) / rho_out;
-        f[3] = f[1] - T(2.0 / 3.0) * rho_out * u_out;
-        f[6] = f[8] - T(0.5) * (f[2] - f[4]) - T(1.0 / 6.0) * rho_out * u_out;
-        f[7] = f[5] + T(0.5) * (f[2] - f[4]) - T(1.0 / 6.0) * rho_out * u_out;
-    }
+    port_rule(f, inlet, outlet, walls, pk, inlet_u, rho_bc, u_bc);
 }
 // apply_bcs at global cell (x, yg) for the step kernels, at level `lvl` (0-based) of the launch: iteration *t_base + t + lvl, the number
 // the first-unstable bookkeeping forms. The device word is read under the schedule's test only — a captured graph carries a fixed `t` and
@@ -285,12 +335,12 @@ __device__ __forceinline__ void apply_bcs(T (&f)[Q], bool bottom, bool top, bool
 // from level to level, and stays here).
 template <typename T, typename U>
 __device__ __forceinline__ void bcs_at_with(const KArgs<T>& a, T (&f)[Q], int x, int yg, int lvl, U&& row_u) {
-    T rho_bc, u_out;
+    T rho_bc, u_bc;
     apply_bcs(f, yg == 0, yg == a.ny_glob - 1, x == 0, x == a.nx - 1, [&]() {
         T u = row_u();
         if (a.sched) u = u * inlet_sched_at<T>(a.sched, *a.t_base + a.t + lvl);
         return u;
-    }, a.walls, a.wk, rho_bc, u_out);
+    }, a.walls, a.wk, a.pk, rho_bc, u_bc);
 }
 template <typename T>
 __device__ __forceinline__ void bcs_at(const KArgs<T>& a, T (&f)[Q], int x, int yg, int lvl) {
@@ -1133,9 +1183,9 @@ __global__ void __launch_bounds__(256) k_init(const InitArgs<T> p) {
 // Macroscopic snapshot from the buffer `old` = P_t that the last step kernel READ:
 //   fluid interior : moments of P_t at the cell. collision conserves rho and rho*u, so these equal the
 //                    pre-collision moments the reference stored at LBMSolver.h:112-114 to round-off (~1e-16).
-//   inlet/outlet   : (rho_bc, u_in, 0) / (1, u_out, 0) of apply_boundary_conditions of iteration t,
-//                    recomputed exactly as the step kernel did (pull from P_t + wall BC + Zou-He); u_in is the row's
-//                    value (u_row), also in the initial snapshot.
+//   inlet/outlet   : (rho, u, 0) of the port's rule (port_rule) of iteration t — (rho_bc, u_in, 0) / (1, u_out, 0) with the
+//                    reference's ports — recomputed exactly as the step kernel did (pull from P_t + wall BC + Zou-He); the
+//                    initial snapshot has the row's value (u_row) and rho = 1 there.
 //   solid          : (1, 0, 0) (rho never rewritten after init, u zeroed at LBMSolver.h:260-261).
 template <typename T>
 struct MacroArgs {
@@ -1151,7 +1201,8 @@ struct MacroArgs {
                                            // (lbm_set_inlet_schedule); 1 without a schedule: x * 1 changes no bit, so no branch
     T frc_hx, frc_hy;                      // a context with a driving force (lbm_set_forcing): h = F/2, as KArgs carries it, which the fluid cells'
     int forced;                            // velocity takes off the momentum of the populations read (macro_moments) where `forced` is set
-    char frc_pad[64 - 2 * sizeof(T) - sizeof(int)];   // (64 bytes in all: what follows this struct in FrameArgs, ProbeArgs, StatsArgs keeps its alignment)
+    PortK<T> pk;                           // the values of the two ports, as KArgs carries them (their kinds ride in `walls`), in what was padding
+    char frc_pad[64 - 6 * sizeof(T)];      // (64 bytes in all with `forced` and its alignment: what follows this struct in FrameArgs, ProbeArgs, StatsArgs keeps its place)
 };
 
 // the moments of the nine populations of a fluid cell, in the element type: rho and u = (sum c_i f_i) / rho (one definition for
@@ -1187,11 +1238,10 @@ __device__ __forceinline__ void macro_cell(const MacroArgs<T>& p, int x, int y, 
         T f[Q];
 #pragma unroll
         for (int i = 0; i < Q; ++i) f[i] = p.old[(long)i * p.plane + c - (long)cy(i) * p.pitch - cx(i)];
-        T rho_bc = T(1), u_out = T(0);
-        apply_bcs(f, yg == 0, yg == p.ny_glob - 1, x == 0, x == p.nx - 1, [&]() { return p.u_row[yg] * p.in_scale; }, p.walls, p.wk, rho_bc, u_out);
-        // the outlet loop runs after the inlet loop (only matters for nx == 1)
-        if (x == p.nx - 1) { r = 1.0; vx = (double)u_out; vy = 0.0; }
-        else { r = (double)rho_bc; vx = (double)(p.u_row[yg] * p.in_scale); vy = 0.0; }
+        T rho_bc = T(1), u_bc = T(0);
+        apply_bcs(f, yg == 0, yg == p.ny_glob - 1, x == 0, x == p.nx - 1, [&]() { return p.u_row[yg] * p.in_scale; }, p.walls, p.wk, p.pk, rho_bc, u_bc);
+        // (rho, u) of the port's rule: the given one as cast, the other as solved; the east rule runs after the west one (only matters for nx == 1)
+        r = (double)rho_bc; vx = (double)u_bc; vy = 0.0;
     } else {
         T f[Q];
 #pragma unroll

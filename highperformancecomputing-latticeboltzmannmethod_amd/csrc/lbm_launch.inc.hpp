@@ -1,11 +1,13 @@
 // csrc/lbm_launch.inc.hpp — kernel arguments, layouts and the launchers of every step-kernel family (single iteration, fused tiles, deep LDS tiles, registers), forces
 // (part of the one host translation unit lbm_hip.hip, which includes it in this place; round 4 split a 2 100-line file by concern)
 
-// The two walls as every argument block carries them (KArgs, MacroArgs): the packed kinds and the operands of wall_ks.
+// The two walls as every argument block carries them (KArgs, MacroArgs): the packed kinds and the operands of wall_ks. The two ports
+// (lbm_set_port) ride with them: their kinds in the spare bits of the same word (port_pack), their values cast once (port_ks).
 template <typename T, typename A>
 void fill_walls(const lbm_ctx* c, A& a) {
-    a.walls = wall_pack(c->wall_kind[0], c->wall_kind[1]);
+    a.walls = wall_pack(c->wall_kind[0], c->wall_kind[1]) | port_pack(c->port_kind[0], c->port_kind[1]);
     a.wk = wall_ks<T>(c->wall_kind[0], c->wall_u[0], c->wall_kind[1], c->wall_u[1]);
+    a.pk = port_ks<T>(c->port_value[0], c->port_kind[1], c->port_value[1]);
 }
 
 // The driving force (lbm_set_forcing) as the argument blocks carry it: h = F/2 (KArgs and MacroArgs) and g = (1 - wp/2) F with wp = 1/tau

@@ -58,6 +58,8 @@ public:
             if (p.forced()) check(lbm_set_forcing(c, p.forcing_x, p.forcing_y), "lbm_set_forcing");   // (every strip the same force)
             if (p.walled())      // every strip carries both walls; only the strips that hold row 0 / ny - 1 use them
                 for (int side = 0; side < 2; ++side) check(lbm_set_wall(c, side, p.wall_kind[side], p.wall_velocity[side]), "lbm_set_wall");
+            if (p.ported())      // every strip carries both ports
+                for (int side = 0; side < 2; ++side) check(lbm_set_port(c, side, p.port_kind[side], p.port_value[side]), "lbm_set_port");
             y += n;
         }
         check(lbm_group_link(group(), num_strips(), opt.rccl ? 1 : 0), "lbm_group_link");

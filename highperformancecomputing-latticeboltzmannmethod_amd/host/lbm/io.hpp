@@ -313,6 +313,10 @@ private:
             f.put("wall_south,"); f.put(p.wall_text(0).c_str()); f.put("\n");
             f.put("wall_north,"); f.put(p.wall_text(1).c_str()); f.put("\n");
         }
+        if (p.ported()) {                                                                                  // (runs with a port off its default only, likewise)
+            f.put("inlet,"); f.put(p.port_text(0).c_str()); f.put("\n");
+            f.put("outlet,"); f.put(p.port_text(1).c_str()); f.put("\n");
+        }
         if (p.scheduled()) { f.put("inlet_schedule,"); f.put(p.inlet_schedule_spec.c_str()); f.put("\n"); }   // (runs with an inlet schedule only)
         if (p.forced()) {                                                                                  // (runs with a driving force only; the last lines)
             f.put("forcing_x,"); f.put(SimulationParams::shortest_text(p.forcing_x).c_str()); f.put("\n");

@@ -80,6 +80,12 @@ struct SimulationParams {
     // (lbm_set_wall). Both no-slip: everything the run prints and writes is the reference's.
     int wall_kind[2] = {0, 0};
     double wall_velocity[2] = {0.0, 0.0};
+    // the two open ends (lbm_solver --inlet / --outlet; not in the reference, whose pair is a velocity inlet and a pressure outlet
+    // with rho = 1): [0] west (column 0), [1] east (column nx - 1); kind 0 velocity, 1 pressure, with the density of a pressure port
+    // or the velocity of the east velocity port beside it (lbm_set_port). The defaults: everything the run prints and writes is the
+    // reference's.
+    int port_kind[2] = {0, 1};
+    double port_value[2] = {0.0, 1.0};
 
     double nu() const { return (tau - 0.5) / 3.0; }
     bool masked() const { return !obstacle_mask.empty(); }
@@ -95,7 +101,9 @@ struct SimulationParams {
     bool probes() const { return !probe_xy.empty(); }
     int probe_count() const { return (int)(probe_xy.size() / 2); }
     bool walled() const { return wall_kind[0] != 0 || wall_kind[1] != 0; }
-    // a number with the fewest digits that read back exactly
+    bool ported() const { return port_kind[0] != 0 || port_kind[1] != 1 || port_value[1] != 1.0; }
+    // a number with the fewest digits that read back exactly (csrc/lbm_ckpt.hpp holds a copy for the ports in a checkpoint's refusal: the
+    // library does not include this layer; the two must stay alike, so that a port reads the same in simulation_params.csv and there)
     static std::string shortest_text(double v) {
         char b[64];
         for (int digits = 1; digits <= 17; ++digits) {
@@ -149,6 +157,27 @@ struct SimulationParams {
         if (end == num || *end != '\0') throw bad("has no wall velocity");
         if (!std::isfinite(u) || std::fabs(u) >= 1.0) throw bad("has a wall velocity that is not finite or not below 1 in magnitude");
         wall_kind[side] = 2; wall_velocity[side] = u;
+    }
+    // a port as the command line names it: "velocity" (west), "velocity:U" (east) or "pressure:RHO"
+    std::string port_text(int side) const {
+        if (port_kind[side] == 1) return "pressure:" + shortest_text(port_value[side]);
+        return side == 0 ? "velocity" : "velocity:" + shortest_text(port_value[side]);
+    }
+    // KIND of --inlet (side 0: velocity | pressure:RHO) / --outlet (side 1: pressure:RHO | velocity:U) with a finite RHO > 0 and a
+    // finite |U| < 1 (std::invalid_argument with the one-line message otherwise)
+    void set_port(int side, const std::string& option, const std::string& text) {
+        const char* forms = side == 0 ? " (velocity or pressure:RHO with RHO > 0)" : " (pressure:RHO with RHO > 0 or velocity:U with |U| < 1)";
+        const auto bad = [&](const char* why) { return std::invalid_argument(option + ": '" + text + "' " + why + forms); };
+        if (side == 0 && text == "velocity") { port_kind[0] = 0; port_value[0] = 0.0; return; }
+        const bool pressure = text.rfind("pressure:", 0) == 0, velocity = side == 1 && text.rfind("velocity:", 0) == 0;
+        if (!pressure && !velocity) throw bad("is not a port kind");
+        const char* num = text.c_str() + 9;
+        char* end = nullptr;
+        const double v = std::strtod(num, &end);
+        if (end == num || *end != '\0' || std::isspace((unsigned char)*num)) throw bad(pressure ? "has no density" : "has no velocity");
+        if (pressure && !(std::isfinite(v) && v > 0.0)) throw bad("has a density that is not finite or not above 0");
+        if (velocity && !(std::isfinite(v) && std::fabs(v) < 1.0)) throw bad("has a velocity that is not finite or not below 1 in magnitude");
+        port_kind[side] = pressure ? 1 : 0; port_value[side] = v;
     }
     double reynolds() const {
         if (masked()) return inlet_velocity * mask_frontal_height / nu();

@@ -25,6 +25,7 @@ static void usage() {
               "           [--inlet-profile parabolic|FILE] [--print-inlet-profile] [--smagorinsky CS] [--trt-magic LAMBDA]\n"
               "           [--forcing FX,FY]\n"
               "           [--stats-start N] [--wall-south KIND] [--wall-north KIND] [--walls KIND]\n"
+              "           [--inlet velocity|pressure:RHO] [--outlet pressure:RHO|velocity:U]\n"
               "           [--frame-stride K] [--probes FILE] [--probe-line x0 y0 x1 y1 n]\n"
               "           [--inlet-ramp N | --inlet-pulse A:P | --inlet-schedule FILE [--inlet-schedule-repeat]] [--print-inlet-schedule]\n"
               "Defaults are the reference's SimulationParams (LBMConfig.h:37-51). --reynolds sets the inlet velocity\n"
@@ -66,6 +67,14 @@ static void usage() {
               "bounce-back) | free-slip (specular reflection: no boundary layer, for unconfined flow past a body) | moving:U (a wall\n"
               "sliding at the tangential velocity U, |U| < 1: Couette flow, a lid, a moving ground). --walls KIND sets both. The\n"
               "on-node scheme does not make ux on a moving wall's row equal U, and the wall's density is taken as 1.\n"
+              "--inlet velocity|pressure:RHO / --outlet pressure:RHO|velocity:U: the two open ends, column 0 and column nx-1. The\n"
+              "defaults are the reference's: a Zou-He velocity inlet (--inlet-velocity, --inlet-profile, the inlet schedules) and a Zou-He\n"
+              "pressure outlet with RHO = 1. --inlet pressure:RHO gives the inlet's density (RHO > 0) and solves for its velocity;\n"
+              "--outlet velocity:U gives the outlet's velocity (|U| < 1, positive leaves the domain: suction, a piston) and solves for\n"
+              "its density. A channel driven from rest by a density difference: --inlet-velocity 0 --inlet pressure:1.005 --outlet\n"
+              "pressure:0.995. A pressure inlet takes no --inlet-profile and no inlet schedule; Reynolds number and Cd / Cl keep\n"
+              "referring to --inlet-velocity. The ports do not know about --forcing, and the on-node walls exchange mass with the fluid\n"
+              "wherever the density is not 1, so the flux of a pressure-driven channel is not constant along x.\n"
               "--stats-start N: time-averaged statistics from step N on, sampled on the device every --output-frequency steps;\n"
               "the run ends with mean_fields.vtk and mean_fields.csv (means of rho, ux, uy and the Reynolds stresses). With\n"
               "--checkpoint / --restart the sums travel beside the checkpoint as FILE.stats. --no-final suppresses the two\n"
@@ -140,6 +149,14 @@ int main(int argc, char** argv) {
                 const std::string kind = val();
                 if (k != "--wall-north") params.set_wall(0, k, kind);
                 if (k != "--wall-south") params.set_wall(1, k, kind);
+            } catch (const std::exception& e) {
+                std::fprintf(stderr, "%s\n", e.what());
+                return 2;
+            }
+        }
+        else if (k == "--inlet" || k == "--outlet") {   // checked here: no device is touched before a bad value exits
+            try {
+                params.set_port(k == "--inlet" ? 0 : 1, k, val());
             } catch (const std::exception& e) {
                 std::fprintf(stderr, "%s\n", e.what());
                 return 2;
@@ -307,6 +324,11 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "%s\n", e.what());
             return 2;
         }
+    }
+    if (params.port_kind[0] == 1 && (!params.inlet_profile_spec.empty() || params.scheduled())) {   // a pressure inlet solves for its velocity
+        std::fprintf(stderr, "--inlet pressure:RHO cannot be combined with %s: a pressure inlet takes no inlet velocity\n",
+                     !params.inlet_profile_spec.empty() ? "--inlet-profile" : schedule_option.c_str());
+        return 2;
     }
     if (print_profile) {
         if (!params.profiled()) { std::fprintf(stderr, "--print-inlet-profile needs --inlet-profile\n"); return 2; }

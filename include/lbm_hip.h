@@ -388,6 +388,45 @@ int  lbm_get_forcing(const lbm_ctx* c, double* fx, double* fy);
 int  lbm_set_wall(lbm_ctx* c, int side, int kind, double velocity);
 /* The wall of `side` as set (kind 0, velocity 0 on a fresh context); either pointer may be NULL. LBM_ERR_ARG: null context, side outside 0..1. */
 int  lbm_get_wall(const lbm_ctx* c, int side, int* kind, double* velocity);
+/* The two ports: generalises the two open ends of the channel (LBMSolver.h:181-235), a Zou-He velocity inlet on column 0 and a Zou-He
+ * pressure outlet with rho = 1 on column nx - 1, to a KIND and a VALUE per end. The west port is column 0, the east port column
+ * nx - 1. On a fluid cell of the port's column, after the pull and after the wall rule, in the unchanged order bottom -> top -> west ->
+ * east:
+ *     west   S = f0 + f2 + f4 + 2 (f3 + f6 + f7)
+ *       LBM_PORT_VELOCITY 0   u = u[y] * s(t) (inlet_velocity / lbm_set_inlet_profile / lbm_set_inlet_schedule), rho = S / (1 - u)  (the default)
+ *       LBM_PORT_PRESSURE 1   rho = value, u = 1 - S / rho
+ *       then f1 = f3 + (2/3) rho u;  f5 = f7 - 0.5 (f2 - f4) + (1/6) rho u;  f8 = f6 + 0.5 (f2 - f4) + (1/6) rho u
+ *     east   S = f0 + f2 + f4 + 2 (f1 + f5 + f8)
+ *       LBM_PORT_PRESSURE 1   rho = value, u = -1 + S / rho                                                     (the default, with value 1)
+ *       LBM_PORT_VELOCITY 0   u = value,   rho = S / (1 + u)
+ *       then f3 = f1 - (2/3) rho u;  f6 = f8 - 0.5 (f2 - f4) - (1/6) rho u;  f7 = f5 + 0.5 (f2 - f4) - (1/6) rho u
+ * The value is cast once to the element type; every operation is one IEEE operation in that type in the order written, (2/3) * rho * u
+ * from left to right, so strict and contracted arithmetic (option "arith") apply the same bits in the port rule. With the defaults, west
+ * (VELOCITY, 0) and east (PRESSURE, 1.0), S / 1 and 1 * u change no bit: every result, kernel name, checkpoint byte and dry-run record
+ * is what it was without this call. Flow driven by a density difference is (PRESSURE, rho_w) and (PRESSURE, rho_e) with
+ * inlet_velocity = 0; suction or a piston is an east VELOCITY port (u > 0 leaves the domain).
+ * Everything else stays the reference's: solid cells of a port column are skipped; with nx == 1 the west rule runs first, then the east
+ * rule on the same cell; the initial state is unchanged (interior cells start at f_eq(1, (u[y] s(0), 0)) of inlet_velocity, profile and
+ * schedule), and so are the ghost frame, the reference velocity of Cd / Cl (inlet_velocity), the forces, the stability scan, the halo
+ * exchange and the dry-run choreography: the ports change no launch and no row range. The snapshot - lbm_get_macros, statistics, frames,
+ * probes - reports (rho, u, 0) of the rule on a port column, through the same function: the given one as cast, the other as solved; so
+ * does the f_current of lbm_get_populations. A schedule scales the west velocity only, never a pressure or the east velocity.
+ * Documented, not corrected: the rules do not know about a driving force (lbm_set_forcing), like the reference's pair; and they are not
+ * mass-tight at the reference's walls: the on-node walls exchange mass with the fluid wherever rho is not 1, so the flux of a
+ * pressure-driven channel is not constant along x.
+ * Call after lbm_create and before lbm_initialise, like lbm_set_wall: the plan is measured with the ports set. Every strip of a run is
+ * given the same two ports. A west PRESSURE port takes no inlet velocity: lbm_initialise fails with LBM_ERR_ARG, naming the offender, if
+ * an inlet profile or an inlet schedule is set beside it. Checkpoints carry both ports where either is off its default (lbm_save_state:
+ * magic "LBMCKPT3", flag bit 8) and load only into a context with equal ports.
+ * LBM_ERR_ARG (the text names the offender): a null context, an initialised context, side outside 0..1, kind outside 0..1, a value
+ * that is not finite, a pressure <= 0, an east velocity with |u| >= 1, a nonzero value with west VELOCITY. */
+#define LBM_PORT_WEST 0      /* column 0 */
+#define LBM_PORT_EAST 1      /* column nx - 1 */
+#define LBM_PORT_VELOCITY 0
+#define LBM_PORT_PRESSURE 1
+int  lbm_set_port(lbm_ctx* c, int side, int kind, double value);
+/* The port of `side` as set (west: kind 0, value 0; east: kind 1, value 1 on a fresh context); either pointer may be NULL. LBM_ERR_ARG: null context, side outside 0..1. */
+int  lbm_get_port(const lbm_ctx* c, int side, int* kind, double* value);
 
 /* ---- strip halo exchange (replaces Grid::exchange_ghost_cells, LBMGrid.h:249-283) ----
  * Device path: RCCL send/recv of the LBM_HALO_ROWS edge rows per face (one contiguous run in the row-interleaved
@@ -483,9 +522,9 @@ int  lbm_halo_import(lbm_ctx* c, const double* south_in, const double* north_in)
 /* Checkpoint / restart (the reference has none): the strip's post-collision populations and the
  * iteration counter. lbm_load_state needs an initialised context created with the same parameters; the macro /
  * population snapshots become available again after the next lbm_step. A file written with an obstacle mask, an inlet
- * profile, a Smagorinsky constant, a TRT magic parameter, a force (lbm_set_forcing), a wall that is not no-slip (lbm_set_wall) or an
- * inlet schedule (lbm_set_inlet_schedule) loads only into a context with the same mask, profile, constant, parameter, force, walls and
- * schedule (the failure names which one differs). The file format, and the order in which differences are named: the comment at the
+ * profile, a Smagorinsky constant, a TRT magic parameter, a force (lbm_set_forcing), a wall that is not no-slip (lbm_set_wall), an
+ * inlet schedule (lbm_set_inlet_schedule) or a port off its default (lbm_set_port) loads only into a context with the same mask,
+ * profile, constant, parameter, force, walls, schedule and ports (the failure names which one differs). The file format, and the order in which differences are named: the comment at the
  * head of csrc/lbm_ckpt.hpp. */
 int  lbm_save_state(lbm_ctx* c, const char* path);
 int  lbm_load_state(lbm_ctx* c, const char* path);
@@ -566,6 +605,14 @@ int lbm_debug_strict_div2(const double* a1, const double* a2, const double* b, i
  * the nine results are widened into f_out9. The argument errors of lbm_set_wall, and LBM_ERR_ARG for a null pointer or an unknown
  * precision. Replaces nothing in the reference (its rule is LBMSolver.h:155-176, kind 0). */
 int lbm_debug_wall_rule(int side, int kind, double velocity, int precision, const double* f_in9, double* f_out9);
+/* Test hook, callable without a device: the port rule of lbm_set_port on ONE cell - the inline function every step kernel and the
+ * snapshot call (csrc/lbm_kernels.hpp port_rule), compiled for the host. f_in9 = the cell's nine populations after the pull and the wall
+ * rule; they are cast to the element type of `precision`, the rule of port `side` with `kind` and `value` is applied as on a fluid cell
+ * of that port's column, and the nine results are widened into f_out9, (rho, u) of the rule into *rho_out and *u_out (nullable). u_in:
+ * the velocity a west VELOCITY port is given (|u_in| < 1; read by that port only). The argument errors of lbm_set_port, and LBM_ERR_ARG
+ * for a null pointer, an unknown precision or such a u_in. Replaces nothing in the reference (its rules are LBMSolver.h:181-235). */
+int lbm_debug_port_rule(int side, int kind, double value, double u_in, int precision, const double* f_in9, double* f_out9, double* rho_out,
+                        double* u_out);
 /* Test hook, callable without a device: the factor the schedule {s, n, mode} of lbm_set_inlet_schedule gives each of the nt iterations
  * t[i] >= 0, out[i] = (double)(T)s(t[i]) in the element type of `precision` — through the index function the step kernels and the
  * snapshot call (csrc/lbm_kernels.hpp inlet_sched_index), compiled for the host. The argument errors of lbm_set_inlet_schedule, and
@@ -573,7 +620,8 @@ int lbm_debug_wall_rule(int side, int kind, double velocity, int precision, cons
 int lbm_debug_inlet_scale(const double* s, int n, int mode, int precision, const int* t, int nt, double* out);
 /* What the head of a checkpoint says about a run (csrc/lbm_ckpt.hpp, which also describes the file): the fixed header, then for each
  * optional field whether the run has it and its value. has_*: 0 or 1; collision: 0, or the setter's model as lbm_ctx holds it (2 Smagorinsky,
- * 4 TRT, 8 forcing) with collision_param = {Cs}, {magic} or {fx, fy}; walls = {south kind, south velocity, north kind, north velocity}. */
+ * 4 TRT, 8 forcing) with collision_param = {Cs}, {magic} or {fx, fy}; walls = {south kind, south velocity, north kind, north velocity};
+ * ports = {west kind, west value, east kind, east value} (has_ports: either port is off its default). */
 typedef struct lbm_ckpt_head {
     int nx, ny, y_start, local_ny, precision, steps_done;
     double tau, inlet_velocity, cylinder_x, cylinder_y, cylinder_radius;
@@ -581,8 +629,10 @@ typedef struct lbm_ckpt_head {
     unsigned long long mask_digest, profile_digest, sched_digest;
     double collision_param[2];
     double walls[4];
+    int has_ports;
+    double ports[4];
 } lbm_ckpt_head;
-#define LBM_CKPT_HEAD_MAX 176   /* bytes: no head is longer */
+#define LBM_CKPT_HEAD_MAX 184   /* bytes: no head is longer (every field present, the collision model with two parameters) */
 /* Test hook, callable without a device: the head lbm_save_state writes for a context that *h describes, through the function it calls,
  * into out (cap >= LBM_CKPT_HEAD_MAX); returns its length. Where mask ([h->ny][h->nx] bytes), profile (h->ny doubles) or sched (sched_n
  * doubles, sched_mode) is not NULL, that field is marked present and its digest is formed as lbm_set_solid_mask, lbm_set_inlet_profile,
