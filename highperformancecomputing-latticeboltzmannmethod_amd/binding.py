@@ -35,7 +35,8 @@ class CkptHead(C.Structure):
                 ("cylinder_radius", C.c_double),
                 ("has_mask", C.c_int), ("has_profile", C.c_int), ("collision", C.c_int), ("has_walls", C.c_int), ("has_sched", C.c_int),
                 ("mask_digest", C.c_ulonglong), ("profile_digest", C.c_ulonglong), ("sched_digest", C.c_ulonglong),
-                ("collision_param", C.c_double * 2), ("walls", C.c_double * 4), ("has_ports", C.c_int), ("ports", C.c_double * 4)]
+                ("collision_param", C.c_double * 2), ("walls", C.c_double * 4), ("has_ports", C.c_int), ("ports", C.c_double * 4),
+                ("has_periodic_y", C.c_int)]
 
 
 CKPT_HEAD_MAX = 184                                            # LBM_CKPT_HEAD_MAX
@@ -104,6 +105,8 @@ def lib():
         L.lbm_debug_wall_rule.argtypes = [C.c_int, C.c_int, C.c_double, C.c_int, dp, dp]
         L.lbm_set_port.argtypes = [vp, C.c_int, C.c_int, C.c_double]
         L.lbm_get_port.argtypes = [vp, C.c_int, C.POINTER(C.c_int), dp]
+        L.lbm_set_periodic_y.argtypes = [vp, C.c_int]
+        L.lbm_get_periodic_y.argtypes = [vp]
         L.lbm_debug_port_rule.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, dp, dp, dp, dp]
         L.lbm_set_inlet_schedule.argtypes = [vp, dp, C.c_int, C.c_int]
         L.lbm_inlet_schedule_length.argtypes = [vp]
@@ -515,12 +518,14 @@ class Context:
     lattice units on every fluid cell (lbm_set_forcing, Guo's scheme on BGK); (0, 0) / None: none; not with smagorinsky or trt_magic.
     ports: optional pair (west, east) of the two open ends (lbm_set_port) in place of the velocity inlet and the pressure outlet with
     rho = 1: west "velocity" or ("pressure", rho), east ("pressure", rho) or ("velocity", u); None in either place: that port's default.
-    A west pressure port takes neither inlet_profile nor inlet_schedule (initialise() fails)."""
+    A west pressure port takes neither inlet_profile nor inlet_schedule (initialise() fails). periodic_y: True makes the top and bottom
+    boundaries periodic (lbm_set_periodic_y): row -1 is row ny - 1, no wall rule runs; not with walls other than no-slip, nor with bodies
+    that touch row 0 or ny - 1 (initialise() fails)."""
 
     def __init__(self, nx, ny, tau=0.6, inlet_velocity=0.01333, cylinder_x=0.2, cylinder_y=0.5,
                  cylinder_radius=0.05, y_start=0, local_ny=0, precision="f64", device=0, force_log_capacity=0,
                  options=None, solid=None, inlet_profile=None, smagorinsky=None, bodies=None, frames=None, trt_magic=None,
-                 probes=None, probe_capacity=None, walls=None, inlet_schedule=None, forcing=None, ports=None):
+                 probes=None, probe_capacity=None, walls=None, inlet_schedule=None, forcing=None, ports=None, periodic_y=False):
         if solid is not None and bodies is not None:
             raise LbmError("solid= and bodies= exclude each other: the body labels are the geometry (solid where nonzero)")
         self.L = lib()
@@ -558,6 +563,8 @@ class Context:
         if ports is not None:
             for side, (kind, v) in zip(("west", "east"), _port_pair(ports)):
                 self.set_port(side, kind, v)
+        if periodic_y:
+            self.set_periodic_y(True)
 
     def _chk(self, rc):
         if rc < 0:
@@ -677,6 +684,14 @@ class Context:
         k, v = C.c_int(), C.c_double()
         self._chk(self.L.lbm_get_port(self.h, _port_code(PORT_SIDES, "side", side), C.byref(k), C.byref(v)))
         return _PORT_NAMES[k.value], v.value
+
+    def set_periodic_y(self, on=True):
+        """lbm_set_periodic_y: periodic top and bottom boundaries on / off; before initialise()."""
+        self._chk(self.L.lbm_set_periodic_y(self.h, 1 if on is True else 0 if on is False else int(on)))
+
+    def periodic_y(self):
+        """True on a context with periodic top and bottom boundaries (lbm_get_periodic_y)."""
+        return bool(self.L.lbm_get_periodic_y(self.h))
 
     def ports(self):
         """((west kind, value), (east kind, value)) as set; (("velocity", 0.0), ("pressure", 1.0)) on a fresh context."""
@@ -914,12 +929,12 @@ class Group:
     solid: optional global (ny, nx) obstacle mask, inlet_profile: optional global [ny] inlet velocities, smagorinsky: optional LES
     constant Cs, trt_magic: optional TRT magic parameter, bodies: optional global (ny, nx) body numbers (in place of solid), frames: optional frame stride k, probes / probe_capacity: optional probe points (global coordinates), walls: optional kinds of the
     bottom and top walls (as Context takes them), inlet_schedule: optional scale factors of the inflow per iteration (likewise), forcing:
-    optional driving force (fx, fy), ports: optional pair (west, east) of the two open ends (as Context takes them); all given to every
-    member."""
+    optional driving force (fx, fy), ports: optional pair (west, east) of the two open ends (as Context takes them), periodic_y: True joins strip
+    n - 1 to strip 0 (periodic top and bottom, as Context takes it); all given to every member."""
 
     def __init__(self, nx, ny, bounds, devices=None, transport="peer", options=None, solid=None, inlet_profile=None, smagorinsky=None,
                  bodies=None, frames=None, trt_magic=None, probes=None, probe_capacity=None, walls=None, inlet_schedule=None, forcing=None,
-                 ports=None, **kw):
+                 ports=None, periodic_y=False, **kw):
         from .strips import partition_rows
         if isinstance(bounds, int):
             bounds = partition_rows(ny, bounds)
@@ -928,7 +943,7 @@ class Group:
         self.ctxs = [Context(nx, ny, y_start=y0, local_ny=n, device=d, options=options, solid=solid, inlet_profile=inlet_profile,
                              smagorinsky=smagorinsky, bodies=bodies, frames=frames, trt_magic=trt_magic, probes=probes,
                              probe_capacity=probe_capacity, walls=walls, inlet_schedule=inlet_schedule, forcing=forcing, ports=ports,
-                             **kw)
+                             periodic_y=periodic_y, **kw)
                      for (y0, n), d in zip(bounds, devices)]
         self.L = lib()
         self._arr = (C.c_void_p * len(self.ctxs))(*[c.h for c in self.ctxs])

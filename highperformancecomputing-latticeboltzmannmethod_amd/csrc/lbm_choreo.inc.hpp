@@ -158,6 +158,8 @@ inline std::string choreo_op_text(const ChoreoOp& o, int idx) {
                       o.w1[1] > o.w0[1] ? (" + [" + std::to_string(o.w0[1]) + "," + std::to_string(o.w1[1]) + ")").c_str() : "");
     else if (o.kind == ChoreoOp::RECORD || o.kind == ChoreoOp::WAIT) n += snprintf(b + n, sizeof(b) - n, " %s of strip %d", evs[o.ev], o.ev_strip);
     else if (o.kind == ChoreoOp::COPY) n += snprintf(b + n, sizeof(b) - n, " buf %d: rows [%d,%d) of strip %d -> rows [%d,%d)", o.buf, o.r0, o.r1, o.r_strip, o.w0[0], o.w1[0]);
+    else if (o.kind == ChoreoOp::SEND && o.ring) n += snprintf(b + n, sizeof(b) - n, " buf %d rows [%d,%d) to strip %d", o.buf, o.r0, o.r1, o.r_strip);
+    else if (o.kind == ChoreoOp::RECV && o.ring) n += snprintf(b + n, sizeof(b) - n, " buf %d rows [%d,%d) <- rows [%d,%d) of strip %d", o.buf, o.w0[0], o.w1[0], o.r0, o.r1, o.r_strip);
     else if (o.kind == ChoreoOp::SEND) n += snprintf(b + n, sizeof(b) - n, " buf %d rows [%d,%d)", o.buf, o.r0, o.r1);
     else if (o.kind == ChoreoOp::RECV) n += snprintf(b + n, sizeof(b) - n, " buf %d rows [%d,%d)", o.buf, o.w0[0], o.w1[0]);
     else if (o.is_sample()) n += snprintf(b + n, sizeof(b) - n, " t=%d reads buf %d rows [%d,%d)%s", o.t, o.buf, o.r0, o.r1, o.sample().writes);

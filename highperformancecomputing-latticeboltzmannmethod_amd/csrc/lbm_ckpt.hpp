@@ -18,6 +18,7 @@
 //                bit 6 (64)  2 doubles the force {fx, fy}                     lbm_set_forcing
 //                bit 7 (128) unassigned: a head that announces it is not a checkpoint
 //                bit 8 (256) 4 doubles west kind, west value, east kind, east value; where a port is off its default: lbm_set_port
+//                bit 9 (512) nothing   periodic y (the flag is the field)       lbm_set_periodic_y
 //              (the bits and sizes of the collision parameters are those of collision_models, lbm_plan.hpp; a context has one model)
 //        then  the post-collision populations P_{steps_done} of the strip's interior, [9][local_ny][nx] in the element type
 // "LBMCKPT2" is the fixed header, the mask's digest (no flags) and the populations; "LBMCKPT1" the fixed header and the populations.
@@ -28,7 +29,7 @@
 // low and the high half of each velocity's bit pattern}; schedule {mode, n, the halves of each factor}.
 // A context loads only a file that announces exactly the fields it has, with equal values (doubles compared as numbers) and an equal
 // fixed header but for steps_done. The refusal names the first difference in this order: the collision models from the last row of
-// collision_models to the first (forcing, TRT, Smagorinsky), the walls, the ports, the inlet profile, the inlet schedule, the mask, the header.
+// collision_models to the first (forcing, TRT, Smagorinsky), the walls, periodic y, the ports, the inlet profile, the inlet schedule, the mask, the header.
 #pragma once
 #include <algorithm>
 #include <array>
@@ -155,7 +156,11 @@ inline std::string ports_refusal(const CkptField&, CkptRefusal r, const lbm_ckpt
     return "with " + ports_text(file.ports) + "; this context has " + ports_text(here.ports);
 }
 
-// ---- the table: the five fields of the setters, and one per collision model that has a parameter ----
+inline std::string periodic_refusal(const CkptField&, CkptRefusal r, const lbm_ckpt_head&, const lbm_ckpt_head&) {
+    return r == CkptRefusal::file_lacks ? "without periodic y (two walls); this context has periodic y" : "with periodic y; this context has two walls";
+}
+
+// ---- the table: the six fields of the setters, and one per collision model that has a parameter ----
 constexpr int CKPT_MODELS = (int)std::size(collision_models);
 constexpr int ckpt_model_fields() {
     int n = 0;
@@ -163,14 +168,15 @@ constexpr int ckpt_model_fields() {
     return n;
 }
 constexpr auto make_ckpt_fields(bool by_rank) {
-    std::array<CkptField, 5 + ckpt_model_fields()> t{{
-        {1, 1, &lbm_ckpt_head::has_mask, 1, offsetof(lbm_ckpt_head, mask_digest), false, CKPT_MODELS + 3, digest_refusal, "obstacle mask"},
-        {2, 1, &lbm_ckpt_head::has_profile, 1, offsetof(lbm_ckpt_head, profile_digest), false, CKPT_MODELS + 1, digest_refusal, "inlet profile"},
+    std::array<CkptField, 6 + ckpt_model_fields()> t{{
+        {1, 1, &lbm_ckpt_head::has_mask, 1, offsetof(lbm_ckpt_head, mask_digest), false, CKPT_MODELS + 4, digest_refusal, "obstacle mask"},
+        {2, 1, &lbm_ckpt_head::has_profile, 1, offsetof(lbm_ckpt_head, profile_digest), false, CKPT_MODELS + 2, digest_refusal, "inlet profile"},
         {16, 4, &lbm_ckpt_head::has_walls, 1, offsetof(lbm_ckpt_head, walls), true, CKPT_MODELS - 1, walls_refusal, "walls"},
-        {32, 1, &lbm_ckpt_head::has_sched, 1, offsetof(lbm_ckpt_head, sched_digest), false, CKPT_MODELS + 2, digest_refusal, "inlet schedule"},
-        {256, 4, &lbm_ckpt_head::has_ports, 1, offsetof(lbm_ckpt_head, ports), true, CKPT_MODELS, ports_refusal, "ports"},
+        {32, 1, &lbm_ckpt_head::has_sched, 1, offsetof(lbm_ckpt_head, sched_digest), false, CKPT_MODELS + 3, digest_refusal, "inlet schedule"},
+        {256, 4, &lbm_ckpt_head::has_ports, 1, offsetof(lbm_ckpt_head, ports), true, CKPT_MODELS + 1, ports_refusal, "ports"},
+        {512, 0, &lbm_ckpt_head::has_periodic_y, 1, 0, false, CKPT_MODELS, periodic_refusal, "periodic y"},
     }};
-    int k = 5;
+    int k = 6;
     for (int i = 0; i < CKPT_MODELS; ++i) {
         const CollisionModel& m = collision_models[i];
         if (m.ckpt_bit) t[k++] = {m.ckpt_bit, m.nparam, &lbm_ckpt_head::collision, m.base, offsetof(lbm_ckpt_head, collision_param), true, CKPT_MODELS - 1 - i, param_refusal, m.param};

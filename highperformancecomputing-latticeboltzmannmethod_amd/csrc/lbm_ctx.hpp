@@ -204,6 +204,7 @@ struct ChoreoOp {
     int t = 0, depth = 0;           // KERNEL: first iteration and iterations; a sample: the iteration
     int w0[2] = {0, 0}, w1[2] = {0, 0};   // rows written, [w0, w1) in local rows (ghost rows: < 0 or >= nyl); KERNEL: two ranges
     int r0 = 0, r1 = 0, r_strip = -1;     // COPY / SEND / a sample: rows read and whose (RECV: where the data comes from; -1: another process)
+    bool ring = false;                    // SEND / RECV of a periodic group (lbm_set_periodic_y): the dump states the pairing (the peer, and whose rows arrive)
     // The samples of an output point (sample_outputs, lbm_launch.inc.hpp), one row per kind from FORCES on: each reads rows
     // [lo, nyl + hi) of its own strip's P_t on the compute stream and writes memory of its own, named in the dump.
     struct Sample { int lo, hi; const char* writes; };
@@ -376,6 +377,14 @@ struct lbm_ctx {
     int num_cus = 256;   // compute units of the device (what counts as a small grid: one round of blocks)
     int loopback = 0;    // TEST ONLY: the strip is its own north and south neighbour (exercises the overlap choreography):
                          // 1 = device copies, 2 = RCCL send/recv to self on a one-rank communicator
+    // Periodic top and bottom (lbm_set_periodic_y): the lattice is the ny rows repeated for ever. Both faces of the strip are live, no wall
+    // rule runs, and every kernel sees the strip PERIODIC_PAD rows up in a lattice of ny + 2 PERIODIC_PAD rows (row_offset / rows_glob,
+    // lbm_launch.inc.hpp), with the row tables and the geometry window built to match at lbm_initialise (prepare_periodic, lbm_hip.hip)
+    // from what the user set: user_mask keeps the rows of the user's mask that the wrapped window holds (lbm_geom.hpp wrapped_rows), pmask
+    // is the window the kernels read.
+    int periodic_y = 0;
+    std::vector<unsigned char> user_mask;
+    HostMask pmask;
     int deep_halo = 1;       // strips: 1 = one exchange of six rows per TWO launches of up to three iterations (the first launch of a pair is
                              // extended); deep plans exchange after every launch. 2 = deep plans too: twelve rows per two launches of up to six
     int halo_trim = 0;       // strips: 1 = an exchange carries only the sub-rows the receiver's launches read (9 hr - 9 of the 9 hr sub-rows of a
@@ -395,6 +404,7 @@ struct lbm_ctx {
     bool depth_rel_measured = false;
     int timing = 0;
     int overlap = 1;
+    bool layout_pinned = false;   // "layout" set through lbm_set_option (a periodic context refuses a pinned planar layout)
     bool overlap_pinned = false, deep_pinned = false;   // set through lbm_set_option: the strip tuner leaves them alone
     int skip_exchange = 0;   // DIAGNOSTIC: issue every launch but no halo traffic (times the compute side of a strip run; results invalid)
     char sched_desc[800] = "";
@@ -408,6 +418,8 @@ struct lbm_ctx {
     // in-process group of strips (lbm_group_link): neighbours, transport (0 peer copies, 1 RCCL), size
     lbm_ctx* nb_south = nullptr;
     lbm_ctx* nb_north = nullptr;
+    lbm_ctx* ring_south = nullptr;   // strip 0: strip n-1; strip n-1's ring_north: strip 0 — neighbours where the group is periodic in y
+    lbm_ctx* ring_north = nullptr;
     int group_transport = 0, group_n = 1, group_k = 0;
     int group_threads = 1;   // a group is driven by one host thread per strip (0: the calling thread issues for every strip)
     long wait_timeout_ms = 0;    // bound of the host-side waits (0: LBM_WAIT_TIMEOUT_MS or five minutes); option "wait_timeout_ms"

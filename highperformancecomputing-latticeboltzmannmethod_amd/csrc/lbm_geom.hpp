@@ -60,6 +60,50 @@ inline HostMask pack_mask(const unsigned char* mask, int nx, int ny, int y_start
     return h;
 }
 
+// Periodic y (lbm_set_periodic_y): the window of a strip whose kernels count rows from `pad` rows below the lattice (lbm_launch.inc.hpp
+// row_offset): rows y_start + pad - GR .. y_start + pad + local_ny + GR - 1 in that count, ALL of them (no clipping: every one is a
+// row of the repeated lattice), row r of the count being S(x, (r - pad) mod ny). `solid(x, w, y)` answers for window row w, which is
+// lattice row y: the user's mask (kept by window row, wrapped_rows below) or the disc test. The bounding box is that of the WINDOW, in
+// the same count (the force box: the images across the seam belong to it); no digest (a checkpoint describes what the user set).
+template <typename Solid>
+inline HostMask pack_mask_periodic(Solid&& solid, int nx, int ny, int y_start, int local_ny, int pad) {
+    HostMask h;
+    h.y0 = y_start + pad - GR;
+    h.rows = local_ny + 2 * GR;
+    h.words = (nx + 63) / 64;
+    h.nbx = (nx + 7) / 8;
+    h.nby = (h.rows + 7) / 8;
+    h.bits.assign((size_t)h.rows * h.words, 0ull);
+    std::vector<int> blocks((size_t)h.nby * h.nbx, 0);
+    h.bx0 = nx; h.by0 = h.y0 + h.rows;
+    for (int r = 0; r < h.rows; ++r) {
+        const int y = ((h.y0 + r - pad) % ny + ny) % ny;
+        for (int x = 0; x < nx; ++x)
+            if (solid(x, r, y)) {
+                h.bits[(size_t)r * h.words + (x >> 6)] |= 1ull << (x & 63);
+                blocks[(size_t)(r >> 3) * h.nbx + (x >> 3)] += 1;
+                h.bx0 = x < h.bx0 ? x : h.bx0; h.bx1 = x > h.bx1 ? x : h.bx1;
+                h.by0 = h.y0 + r < h.by0 ? h.y0 + r : h.by0; h.by1 = h.y0 + r > h.by1 ? h.y0 + r : h.by1;
+            }
+    }
+    const int W = h.nbx + 1;
+    h.sat.assign((size_t)(h.nby + 1) * W, 0);
+    for (int b = 0; b < h.nby; ++b)
+        for (int c = 0; c < h.nbx; ++c)
+            h.sat[(size_t)(b + 1) * W + c + 1] = blocks[(size_t)b * h.nbx + c] + h.sat[(size_t)b * W + c + 1] +
+                                                 h.sat[(size_t)(b + 1) * W + c] - h.sat[(size_t)b * W + c];
+    if (h.bx1 < 0) { h.bx0 = 0; h.by0 = 0; }
+    return h;
+}
+
+// ... and the rows of a global [ny][nx] mask that window holds, [local_ny + 2 GR][nx], wrapped: what a context keeps of the user's mask
+// in case it is made periodic (the setters may come in either order)
+inline std::vector<unsigned char> wrapped_rows(const unsigned char* mask, int nx, int ny, int y_start, int local_ny) {
+    std::vector<unsigned char> w((size_t)(local_ny + 2 * GR) * nx);
+    for (int r = 0; r < local_ny + 2 * GR; ++r) memcpy(&w[(size_t)r * nx], mask + (size_t)(((y_start - GR + r) % ny + ny) % ny) * nx, (size_t)nx);
+    return w;
+}
+
 // Per-body force reporting (lbm_set_body_labels): what k_forces_bodies reads for ONE strip of a global [ny][nx] label array
 // (0 fluid, k = 1..255 a solid cell of body k; B = the largest label present, a label nobody carries is a body without cells).
 //   lab    [(local_ny + 2)][nx]: the strip's rows and one ghost row per face, zeros beyond the domain

@@ -93,6 +93,15 @@ int upload_feqrow(lbm_ctx* c, const double* u, int ny) {
     return upload_rows(c, c->d_feqrow, feqrow.data(), feqrow.size());
 }
 
+// v[0 .. ny) by global row -> the table the kernels index by the rows they count: v itself, or — periodic y — rows_glob entries,
+// entry r = v[(r - PERIODIC_PAD) mod ny]
+std::vector<double> table_rows(const lbm_ctx* c, const double* v) {
+    const int ny = c->p.ny, n = rows_glob(c), off = row_offset(c);
+    std::vector<double> t((size_t)n);
+    for (int r = 0; r < n; ++r) t[(size_t)r] = v[(size_t)(((r - off) % ny + ny) % ny)];
+    return t;
+}
+
 // ---- the inlet schedule (lbm_set_inlet_schedule) ----
 // the argument checks shared by lbm_set_inlet_schedule and lbm_debug_inlet_scale; the text names the offender
 int check_schedule(const char* who, const double* s, int n, int mode) {
@@ -132,9 +141,69 @@ int prepare_schedule(lbm_ctx* c) {
     }
     std::vector<double> u0((size_t)ny);
     for (int y = 0; y < ny; ++y) u0[(size_t)y] = c->h_urow[(size_t)y] * c->sched[0];
-    if (int rc = upload_feqrow(c, u0.data(), ny)) return rc;
-    if (!c->d_urow0) HIPCHK(hipMalloc(&c->d_urow0, (size_t)ny * c->esize));
-    return upload_rows(c, c->d_urow0, u0.data(), u0.size());
+    const std::vector<double> t0 = table_rows(c, u0.data());
+    if (int rc = upload_feqrow(c, t0.data(), (int)t0.size())) return rc;
+    if (c->d_urow0) { HIPCHK(hipFree(c->d_urow0)); c->d_urow0 = nullptr; }
+    HIPCHK(hipMalloc(&c->d_urow0, t0.size() * c->esize));
+    return upload_rows(c, c->d_urow0, t0.data(), t0.size());
+}
+
+// ---- periodic y (lbm_set_periodic_y): what lbm_initialise builds for the rows the kernels count (lbm_launch.inc.hpp row_offset) ----
+// The refusals only lbm_initialise can make, each naming the offender.
+int refuse_periodic(const lbm_ctx* c) {
+    if (c->has_walls())
+        return fail(LBM_ERR_ARG, "lbm_initialise: a %s south wall and a %s north wall (lbm_set_wall) beside periodic y (lbm_set_periodic_y): no wall rule runs on a periodic lattice",
+                    wall_kind_name(c->wall_kind[0]), wall_kind_name(c->wall_kind[1]));
+    if (c->body_n > 0 && (c->hmask.by0 == 0 || c->hmask.by1 == c->p.ny - 1))
+        return fail(LBM_ERR_ARG, "lbm_initialise: body labels (lbm_set_body_labels) with a labelled cell on row %d beside periodic y: a body's box is clipped at the domain, "
+                                 "its links across the seam would be missed", c->hmask.by0 == 0 ? 0 : c->p.ny - 1);
+    if (c->comm && c->nranks > 1 && c->group_n <= 1)
+        return fail(LBM_ERR_ARG, "lbm_initialise: a communicator of %d ranks (lbm_comm_init) beside periodic y: rings of processes are not built", c->nranks);
+    if (c->layout_pinned && c->layout == 0) return fail(LBM_ERR_ARG, "lbm_initialise: option layout = 0 (planar) beside periodic y: a periodic context is a strip, row-interleaved only");
+    if (c->split_pinned && c->split) return fail(LBM_ERR_ARG, "lbm_initialise: option split = %d beside periodic y: row-range launches exist for a whole domain only", c->split);
+    if (c->loopback) return fail(LBM_ERR_ARG, "lbm_initialise: option loopback = %d (a test transport, with walls) beside periodic y", c->loopback);
+    if (c->nyl < 2 * HR1) return fail(LBM_ERR_ARG, "lbm_initialise: a strip of %d rows beside periodic y: a strip with neighbours needs at least %d rows", c->nyl, 2 * HR1);
+    return LBM_OK;
+}
+// The device copies of a packed mask's bitmap and coarse table (owned by the context from the moment they exist: lbm_destroy frees them)
+// in place of the ones it had, and the partial sums of the force kernel's chunks: what lbm_set_solid_mask and prepare_periodic upload.
+int upload_mask(lbm_ctx* c, const HostMask& h) {
+    if (c->mview.bits) { HIPCHK(hipFree((void*)c->mview.bits)); c->mview.bits = nullptr; }
+    if (c->mview.sat) { HIPCHK(hipFree((void*)c->mview.sat)); c->mview.sat = nullptr; }
+    if (c->d_fpart) { HIPCHK(hipFree(c->d_fpart)); c->d_fpart = nullptr; }
+    c->mview = h.view();
+    c->mview.bits = nullptr; c->mview.sat = nullptr;
+    unsigned long long* dbits = nullptr;
+    int* dsat = nullptr;
+    HIPCHK(hipMalloc(&dbits, std::max<size_t>(1, h.bits.size()) * sizeof(unsigned long long)));
+    c->mview.bits = dbits;
+    HIPCHK(hipMalloc(&dsat, h.sat.size() * sizeof(int)));
+    c->mview.sat = dsat;
+    HIPCHK(hipMemcpy(dbits, h.bits.data(), h.bits.size() * sizeof(unsigned long long), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dsat, h.sat.data(), h.sat.size() * sizeof(int), hipMemcpyHostToDevice));
+    c->fpart_chunks = (int)(((long)c->nx * c->nyl + FORCE_CHUNK - 1) / FORCE_CHUNK);
+    HIPCHK(hipMalloc(&c->d_fpart, 2 * sizeof(double) * (size_t)std::max(1, c->fpart_chunks)));
+    return LBM_OK;
+}
+// The row tables with PERIODIC_PAD wrapped rows each side, and the wrapped window of the geometry — the user's mask, or the disc
+// rasterised by the disc test, so that its image across the seam exists — in place of what the setters uploaded.
+int prepare_periodic(lbm_ctx* c) {
+    const std::vector<double> t = table_rows(c, c->h_urow.data());
+    if (c->d_urow) { HIPCHK(hipFree(c->d_urow)); c->d_urow = nullptr; }
+    HIPCHK(hipMalloc(&c->d_urow, t.size() * c->esize));
+    if (int rc = upload_rows(c, c->d_urow, t.data(), t.size())) return rc;
+    if (c->has_profile && !c->has_sched()) { if (int rc = upload_feqrow(c, t.data(), (int)t.size())) return rc; }
+    const int nx = c->nx, ny = c->p.ny;
+    const double r2 = (double)(c->cyl_r * c->cyl_r);
+    auto solid = [&](int x, int w, int y) {
+        if (c->has_mask) return c->user_mask[(size_t)w * nx + x] != 0;
+        const double dx = x - c->cyl_x, dy = y - c->cyl_y;      // (the test of lbm_get_solid and is_solid_cell)
+        return dx * dx + dy * dy <= r2;
+    };
+    HostMask h = pack_mask_periodic(solid, nx, ny, c->p.y_start, c->nyl, PERIODIC_PAD);
+    if (int rc = upload_mask(c, h)) return rc;
+    c->pmask = std::move(h);
+    return LBM_OK;
 }
 }  // namespace
 
@@ -154,6 +223,7 @@ lbm_ckpt_head ckpt_head_of(const lbm_ctx* c) {
     h.has_sched = c->has_sched(); h.sched_digest = c->sched_digest;
     h.has_ports = c->has_ports();
     h.ports[0] = (double)c->port_kind[0]; h.ports[1] = c->port_value[0]; h.ports[2] = (double)c->port_kind[1]; h.ports[3] = c->port_value[1];
+    h.has_periodic_y = c->periodic_y;
     return h;
 }
 // lbm_load_state and lbm_debug_ckpt_load: the head in the first n bytes of `path` against the loading context's: the bytes it takes and
@@ -365,8 +435,8 @@ void lbm_destroy(lbm_ctx* c) {
     if (!leak && c->stream && wait_stream(c, c->stream, "compute stream (lbm_destroy)") == LBM_ERR_TIMEOUT) leak = true;
     if (!leak && c->comm_stream && wait_stream(c, c->comm_stream, "exchange stream (lbm_destroy)") == LBM_ERR_TIMEOUT) leak = true;
     if (!leak && c->split_stream && wait_stream(c, c->split_stream, "second compute stream (lbm_destroy)") == LBM_ERR_TIMEOUT) leak = true;
-    for (lbm_ctx* nb : {c->nb_south, c->nb_north}) {  // a destroyed member leaves its group
-        if (!nb) continue;
+    for (lbm_ctx* nb : {c->nb_south, c->nb_north, c->ring_south, c->ring_north}) {  // a destroyed member leaves its group
+        if (!nb || nb == c) continue;
         // the neighbour's exchange stream may still hold a pull (hipMemcpyPeerAsync) that READS this member's edge rows, and
         // freeing a buffer only waits for work of this member's own device: drain the neighbour's streams first
         (void)hipSetDevice(nb->device);
@@ -374,12 +444,14 @@ void lbm_destroy(lbm_ctx* c) {
         if (!leak && nb->stream && wait_stream(nb, nb->stream, "a neighbour's compute stream (lbm_destroy)") == LBM_ERR_TIMEOUT) leak = true;
         if (nb->nb_south == c) nb->nb_south = nullptr;
         if (nb->nb_north == c) nb->nb_north = nullptr;
+        if (nb->ring_south == c) nb->ring_south = nullptr;
+        if (nb->ring_north == c) nb->ring_north = nullptr;
     }
     (void)hipSetDevice(c->device);
     if (leak) {
         fprintf(stderr, "lbm_destroy: context %p left allocated (%s)\n", (void*)c, g_err);
         lbm_trace("destroy", "ctx %p LEAKED: %s", (void*)c, g_err);
-        c->nb_south = c->nb_north = nullptr;
+        c->nb_south = c->nb_north = c->ring_south = c->ring_north = nullptr;
         return;
     }
     // (a graph that captured RCCL operations holds the communicator: ncclCommDestroy waits for it to go away first)
@@ -406,7 +478,7 @@ namespace {
 // May this context run deep shape `deep` under collision model `collision` (deep_refusal, lbm_plan.hpp)? `settled`: its arithmetic mode
 // and its extent count too (lbm_initialise: the arithmetic and the strip options may follow `deep`).
 int refuse_deep(const lbm_ctx* c, int collision, int deep, bool settled) {
-    const bool whole = !((c->comm && c->nranks > 1) || c->group_n > 1 || c->loopback || c->nyl != c->p.ny);
+    const bool whole = !((c->comm && c->nranks > 1) || c->group_n > 1 || c->loopback || c->periodic_y || c->nyl != c->p.ny);
     const std::string why = deep_refusal(deep, (int)c->esize, collision_model(collision), settled, c->arith == AR_CONTRACTED, whole);
     return why.empty() ? LBM_OK : fail(LBM_ERR_ARG, "%s", why.c_str());
 }
@@ -436,7 +508,9 @@ int lbm_initialise(lbm_ctx* c, int* solid_count_out) {
         return fail(LBM_ERR_ARG, "lbm_initialise: an inlet profile (lbm_set_inlet_profile) with a west pressure port (lbm_set_port): a pressure port takes no inlet velocity");
     if (c->port_kind[0] == LBM_PORT_PRESSURE && c->has_sched())
         return fail(LBM_ERR_ARG, "lbm_initialise: an inlet schedule (lbm_set_inlet_schedule) with a west pressure port (lbm_set_port): a pressure port takes no inlet velocity");
+    if (c->periodic_y) { if (int rc = refuse_periodic(c)) return rc; }
     HIPCHK(hipSetDevice(c->device));
+    if (c->periodic_y) { if (int rc = prepare_periodic(c)) return rc; }
     if (c->has_sched()) { if (int rc = prepare_schedule(c)) return rc; }
     { int wr = wait_stream(c, c->stream, "compute stream (lbm_initialise)"); if (wr) return wr; }        // (re-)initialisation starts from quiet streams
     { int wr = wait_stream(c, c->comm_stream, "exchange stream (lbm_initialise)"); if (wr) return wr; }
@@ -754,7 +828,7 @@ int lbm_set_f_current(lbm_ctx* c, const double* aos) {
     HIPCHK(hipStreamSynchronize(c->comm_stream));
     int rc = DISPATCH(c, do_set_f_current<double>(c, aos), do_set_f_current<float>(c, aos));
     if (rc) return rc;
-    if ((c->comm || c->loopback) && c->group_n <= 1)   // (a group: lbm_group_refresh_halos once every member is set)
+    if ((c->comm || self_wrap(c)) && c->group_n <= 1)   // (a group: lbm_group_refresh_halos once every member is set)
         rc = DISPATCH(c, exchange_rccl<double>(c, c->cur, c->stream), exchange_rccl<float>(c, c->cur, c->stream));
     return rc;
 }
@@ -790,24 +864,10 @@ int lbm_set_solid_mask(lbm_ctx* c, const unsigned char* mask, int nx, int ny) {
         c->body_n = c->body_chunks = 0;
         c->body_log.release();
     }
-    if (c->mview.bits) { HIPCHK(hipFree((void*)c->mview.bits)); c->mview.bits = nullptr; }
-    if (c->mview.sat) { HIPCHK(hipFree((void*)c->mview.sat)); c->mview.sat = nullptr; }
-    if (c->d_fpart) { HIPCHK(hipFree(c->d_fpart)); c->d_fpart = nullptr; }
     c->has_mask = false;
-    // device copies of the bitmap and the coarse table (owned by the context from the moment they exist: lbm_destroy frees them)
-    c->mview = h.view();
-    c->mview.bits = nullptr; c->mview.sat = nullptr;
-    unsigned long long* dbits = nullptr;
-    int* dsat = nullptr;
-    HIPCHK(hipMalloc(&dbits, std::max<size_t>(1, h.bits.size()) * sizeof(unsigned long long)));
-    c->mview.bits = dbits;
-    HIPCHK(hipMalloc(&dsat, h.sat.size() * sizeof(int)));
-    c->mview.sat = dsat;
-    HIPCHK(hipMemcpy(dbits, h.bits.data(), h.bits.size() * sizeof(unsigned long long), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dsat, h.sat.data(), h.sat.size() * sizeof(int), hipMemcpyHostToDevice));
-    c->fpart_chunks = (int)(((long)c->nx * c->nyl + FORCE_CHUNK - 1) / FORCE_CHUNK);
-    HIPCHK(hipMalloc(&c->d_fpart, 2 * sizeof(double) * (size_t)std::max(1, c->fpart_chunks)));
+    if (int rc = upload_mask(c, h)) return rc;
     c->hmask = std::move(h);
+    c->user_mask = wrapped_rows(mask, nx, ny, c->p.y_start, c->nyl);      // (periodic y: lbm_initialise builds the wrapped window from them)
     c->has_mask = true;
     return LBM_OK;
 }
@@ -919,6 +979,16 @@ int lbm_get_port(const lbm_ctx* c, int side, int* kind, double* value) {
     if (value) *value = c->port_value[side];
     return LBM_OK;
 }
+
+int lbm_set_periodic_y(lbm_ctx* c, int on) {
+    if (!c) return fail(LBM_ERR_ARG, "lbm_set_periodic_y: null context");
+    if (c->initialised) return fail(LBM_ERR_ARG, "lbm_set_periodic_y must be called before lbm_initialise");
+    if (on != 0 && on != 1) return fail(LBM_ERR_ARG, "lbm_set_periodic_y: on = %d (0 or 1 only)", on);
+    c->periodic_y = on;
+    return LBM_OK;
+}
+
+int lbm_get_periodic_y(const lbm_ctx* c) { return c ? c->periodic_y : 0; }
 
 int lbm_set_inlet_schedule(lbm_ctx* c, const double* s, int n, int mode) {
     if (!c) return fail(LBM_ERR_ARG, "lbm_set_inlet_schedule: null context");
@@ -1041,7 +1111,7 @@ int lbm_group_link(lbm_ctx** cs, int n, int transport) {
         for (int k = 0; k < n; ++k) {
             lbm_ctx* c = cs[k];
             HIPCHK(hipSetDevice(c->device));
-            for (lbm_ctx* nb : {k > 0 ? cs[k - 1] : nullptr, k + 1 < n ? cs[k + 1] : nullptr}) {
+            for (lbm_ctx* nb : {k > 0 ? cs[k - 1] : nullptr, k + 1 < n ? cs[k + 1] : nullptr, (c->periodic_y && (k == 0 || k + 1 == n)) ? cs[k == 0 ? n - 1 : 0] : nullptr}) {
                 if (!nb || nb->device == c->device) continue;
                 int can = 0;
                 HIPCHK(hipDeviceCanAccessPeer(&can, c->device, nb->device));
@@ -1063,6 +1133,8 @@ int lbm_group_link(lbm_ctx** cs, int n, int transport) {
     for (int k = 0; k < n; ++k) {
         cs[k]->nb_south = k > 0 ? cs[k - 1] : nullptr;
         cs[k]->nb_north = k + 1 < n ? cs[k + 1] : nullptr;
+        cs[k]->ring_south = k == 0 ? cs[n - 1] : nullptr;      // (neighbours where the group is periodic in y: south_of / north_of)
+        cs[k]->ring_north = k + 1 == n ? cs[0] : nullptr;
         cs[k]->group_transport = transport;
         cs[k]->group_n = n;
         cs[k]->group_k = k;
@@ -1075,6 +1147,8 @@ int lbm_group_initialise(lbm_ctx** cs, int n, int* solid_total) {
     int rc = check_group(cs, n, true);
     if (rc) return rc;
     int total = 0;
+    for (int k = 0; k < n; ++k)
+        if (cs[k]->periodic_y != cs[0]->periodic_y) return fail(LBM_ERR_ARG, "strip %d and strip 0 of the group differ in periodic y (lbm_set_periodic_y): set it on every strip", k);
     for (int k = 0; k < n; ++k) {
         int sc = 0;
         rc = lbm_initialise(cs[k], &sc);
@@ -1106,6 +1180,7 @@ int lbm_group_refresh_halos(lbm_ctx** cs, int n) {
 
 int lbm_halo_export(lbm_ctx* c, double* south_out, double* north_out) {
     if (!c || !c->initialised) return fail(LBM_ERR_ARG, "context not initialised");
+    if (c->periodic_y) return fail(LBM_ERR_ARG, "lbm_halo_export: a periodic context (lbm_set_periodic_y) exchanges on the device only");
     HIPCHK(hipSetDevice(c->device));
     { int jr = join_comm(c); if (jr) return jr; }
     return DISPATCH(c, do_halo_export<double>(c, south_out, north_out), do_halo_export<float>(c, south_out, north_out));
@@ -1113,6 +1188,7 @@ int lbm_halo_export(lbm_ctx* c, double* south_out, double* north_out) {
 
 int lbm_halo_import(lbm_ctx* c, const double* south_in, const double* north_in) {
     if (!c || !c->initialised) return fail(LBM_ERR_ARG, "context not initialised");
+    if (c->periodic_y) return fail(LBM_ERR_ARG, "lbm_halo_import: a periodic context (lbm_set_periodic_y) exchanges on the device only");
     HIPCHK(hipSetDevice(c->device));
     { int jr = join_comm(c); if (jr) return jr; }
     return DISPATCH(c, do_halo_import<double>(c, south_in, north_in), do_halo_import<float>(c, south_in, north_in));
@@ -1158,7 +1234,7 @@ int lbm_load_state(lbm_ctx* c, const char* path) {
     c->force_log.ix.reset(); c->body_log.ix.reset();
     c->last_was_pair = false;
     c->mid_pair = false;
-    if ((c->comm || c->loopback) && c->group_n <= 1)   // (a group: lbm_group_refresh_halos once every member is restored)
+    if ((c->comm || self_wrap(c)) && c->group_n <= 1)   // (a group: lbm_group_refresh_halos once every member is restored)
         rc = DISPATCH(c, exchange_rccl<double>(c, c->cur, c->stream), exchange_rccl<float>(c, c->cur, c->stream));
     return rc;
 }
@@ -1188,7 +1264,11 @@ int lbm_set_option(lbm_ctx* c, const char* key, long value) {
         return fail(LBM_ERR_ARG, "option %s must be set before lbm_initialise", key);
     if (k == "timing") c->timing = (int)value;
     else if (k == "alternate") c->alternate = (int)value;
-    else if (k == "layout") c->layout = (int)value ? 1 : 0;
+    else if (k == "layout") { c->layout = (int)value ? 1 : 0; c->layout_pinned = true; }
+    else if (k == "periodic_y") {   // lbm_set_periodic_y by its key (the dry runs take options only)
+        if (value != 0 && value != 1) return fail(LBM_ERR_ARG, "lbm_set_periodic_y: on = %ld (0 or 1 only)", value);
+        return lbm_set_periodic_y(c, (int)value);
+    }
     else if (k == "nt") c->use_nt = (int)value ? 1 : 0;
     else if (k == "ntl") c->use_ntl = (int)value ? 1 : 0;
     else if (k == "fuse") { if (value < 1 || value > 4) return fail(LBM_ERR_ARG, "fuse must be 1, 2, 3 or 4 (4: tile kernel, no strip faces)"); c->fuse = (int)value; c->deep = 0; }
@@ -1526,6 +1606,7 @@ int lbm_debug_choreography(int nx, int ny, const int* bounds2, int nstrips, int 
             c->nranks = 1 + (s_face ? 1 : 0) + (n_face ? 1 : 0);
             c->rank = s_face ? 1 : 0;
         } else if (transport == 3) c->loopback = 1;
+        if (c->periodic_y && transport >= 2) { cleanup(); return fail(LBM_ERR_ARG, "periodic_y=1 goes with transports 0 and 1 (a ring of strips; one strip: a periodic context on its own)"); }
         if (int rc = refuse_deep(c, c->collision, c->deep, true)) { cleanup(); return rc; }       // (as lbm_initialise does)
         c->initialised = true;
         c->cur = 1;
@@ -1538,6 +1619,11 @@ int lbm_debug_choreography(int nx, int ny, const int* bounds2, int nstrips, int 
         for (int k = 0; k < nstrips; ++k) {
             cs[(size_t)k]->nb_south = k > 0 ? cs[(size_t)k - 1] : nullptr;
             cs[(size_t)k]->nb_north = k + 1 < nstrips ? cs[(size_t)k + 1] : nullptr;
+            if (nstrips > 1) {      // (periodic_y=1: the ring; one strip is a periodic context on its own)
+                cs[(size_t)k]->ring_south = k == 0 ? cs[(size_t)nstrips - 1] : nullptr;
+                cs[(size_t)k]->ring_north = k + 1 == nstrips ? cs[0] : nullptr;
+            }
+            if (cs[(size_t)k]->periodic_y != cs[0]->periodic_y || (cs[0]->periodic_y && cs[(size_t)k]->nyl < 2 * HR1)) { cleanup(); return fail(LBM_ERR_ARG, "periodic y: every strip alike, and at least %d rows each", 2 * HR1); }
             cs[(size_t)k]->group_transport = transport; cs[(size_t)k]->group_n = nstrips; cs[(size_t)k]->group_threads = 0;
             const int expect = k == 0 ? 0 : cs[(size_t)k - 1]->p.y_start + cs[(size_t)k - 1]->nyl;
             if (cs[(size_t)k]->p.y_start != expect || (k + 1 == nstrips && expect + cs[(size_t)k]->nyl != ny)) { cleanup(); return fail(LBM_ERR_ARG, "the strips must cover the lattice bottom to top"); }
@@ -1599,6 +1685,7 @@ int lbm_debug_p2p_matching(int nx, int ny, const int* bounds2, int nranks, int p
         if (c->nyl < 1 || c->p.y_start != expect || (k + 1 == nranks && expect + c->nyl != ny)) { cleanup(); return fail(LBM_ERR_ARG, "the strips must cover the lattice bottom to top"); }
         int rc = apply(c, options);
         if (!rc && k == 1) rc = apply(c, options_rank1);
+        if (!rc && c->periodic_y) rc = fail(LBM_ERR_ARG, "lbm_debug_p2p_matching: periodic_y=1 (rings of processes are not built: lbm_initialise refuses them)");
         if (rc) { cleanup(); return rc; }
         c->layout = 1; configure_layout(c, 1);
         if (c->deep) c->fuse = deep_depth(c->deep);

@@ -1,6 +1,21 @@
 // csrc/lbm_launch.inc.hpp — kernel arguments, layouts and the launchers of every step-kernel family (single iteration, fused tiles, deep LDS tiles, registers), forces
 // (part of the one host translation unit lbm_hip.hip, which includes it in this place; round 4 split a 2 100-line file by concern)
 
+// Periodic y (lbm_set_periodic_y) through the kernels' arguments: a periodic context's launches and samplers see the strip
+// PERIODIC_PAD rows up (y_start + row_offset) in a lattice of rows_glob = ny + 2 PERIODIC_PAD rows — a strip in the middle of a taller
+// lattice, which is the path every plan runs on an interior strip: no row is the domain's edge, so no wall rule, no one-sided
+// difference and no clamp fires, and every row a launch or a sampler reaches (twelve halo rows; the frame's second ghost row lies within
+// them) is a row of the lattice. The tables indexed by the global row (u_row, d_urow0, d_feqrow: rows_glob entries) and the geometry
+// window (lbm_ctx::pmask) are filled from y mod ny to match (prepare_periodic, lbm_hip.hip). Walled: offset 0, ny rows, as ever.
+constexpr int PERIODIC_PAD = 16;
+static_assert(PERIODIC_PAD > GR + 1, "the offset covers the deepest reach of a launch and the lean test of a tile at the strip's first row");
+inline int row_offset(const lbm_ctx* c) { return c->periodic_y ? PERIODIC_PAD : 0; }
+inline int rows_glob(const lbm_ctx* c) { return c->p.ny + 2 * row_offset(c); }
+inline int row_start(const lbm_ctx* c) { return c->p.y_start + row_offset(c); }
+// the geometry the kernels read through MaskView: the user's mask, or — periodic y — the wrapped window of mask or disc
+inline bool geom_masked(const lbm_ctx* c) { return c->has_mask || c->periodic_y; }
+inline const HostMask& geom_mask(const lbm_ctx* c) { return c->periodic_y ? c->pmask : c->hmask; }
+
 // The two walls as every argument block carries them (KArgs, MacroArgs): the packed kinds and the operands of wall_ks. The two ports
 // (lbm_set_port) ride with them: their kinds in the spare bits of the same word (port_pack), their values cast once (port_ks).
 template <typename T, typename A>
@@ -47,12 +62,12 @@ KArgs<T> make_kargs(const lbm_ctx* c, int src, int dst, int t) {
     a.xoff = c->xoff;
     a.nx = c->nx;
     a.ny_loc = c->nyl;
-    a.ny_glob = c->p.ny;
-    a.y_start = c->p.y_start;
+    a.ny_glob = rows_glob(c);
+    a.y_start = row_start(c);
     a.cyl_x = c->cyl_x;
     a.cyl_y = c->cyl_y;
     a.cyl_r2 = (double)(c->cyl_r * c->cyl_r);
-    if (c->has_mask) a.mv = c->mview;
+    if (geom_masked(c)) a.mv = c->mview;
     a.tau_inv = (T)(1.0 / c->p.tau);
     a.u_row = static_cast<const T*>(c->d_urow);
     a.unstable_t = c->d_unstable;
@@ -175,9 +190,9 @@ MacroArgs<T> make_macro_args(const lbm_ctx* c, const void* src, int t) {
     MacroArgs<T> m;
     m.old = static_cast<const T*>(src);
     m.plane = (long)c->plane; m.pitch = c->pitch; m.xoff = c->xoff;
-    m.nx = c->nx; m.ny_loc = c->nyl; m.ny_glob = c->p.ny; m.y_start = c->p.y_start;
+    m.nx = c->nx; m.ny_loc = c->nyl; m.ny_glob = rows_glob(c); m.y_start = row_start(c);
     m.cyl_x = c->cyl_x; m.cyl_y = c->cyl_y; m.cyl_r2 = (double)(c->cyl_r * c->cyl_r);
-    if (c->has_mask) m.mv = c->mview;
+    if (geom_masked(c)) m.mv = c->mview;
     m.u_row = static_cast<const T*>(c->d_urow);
     fill_walls<T>(c, m);
     m.in_scale = inlet_scale<T>(c, t);
@@ -217,16 +232,16 @@ int launch_forces(lbm_ctx* c, double* out, int t) {
     ForceArgs<T> f;
     f.cur = static_cast<const T*>(c->buf[c->cur]);
     f.plane = (long)c->plane; f.pitch = c->pitch; f.xoff = c->xoff;
-    f.nx = c->nx; f.ny_loc = c->nyl; f.ny_glob = c->p.ny; f.y_start = c->p.y_start;
+    f.nx = c->nx; f.ny_loc = c->nyl; f.ny_glob = rows_glob(c); f.y_start = row_start(c);
     f.cyl_x = c->cyl_x; f.cyl_y = c->cyl_y; f.cyl_r = c->cyl_r; f.cyl_r2 = (double)(c->cyl_r * c->cyl_r);
     f.out = out; f.t = t; f.part = c->d_fpart;
-    if (c->has_mask) {   // the mask's bounding box + 1 cell, within this strip's rows; large boxes in fixed chunks (k_forces)
-        const HostMask& h = c->hmask;
+    if (geom_masked(c)) {   // the mask's bounding box + 1 cell, within this strip's rows; large boxes in fixed chunks (k_forces)
+        const HostMask& h = geom_mask(c);    // (periodic y: the box of the wrapped window, in the rows the kernels count)
         f.mv = c->mview;
         f.x0 = std::max(0, h.bx0 - 1);
         f.x1 = std::min(c->nx - 1, h.bx1 + 1);
-        f.y0 = std::max(0, h.by0 - 1 - c->p.y_start);
-        f.y1 = std::min(c->nyl - 1, h.by1 + 1 - c->p.y_start);
+        f.y0 = std::max(0, h.by0 - 1 - row_start(c));
+        f.y1 = std::min(c->nyl - 1, h.by1 + 1 - row_start(c));
         if (h.bx1 < h.bx0) f.x1 = f.x0 - 1;    // no solid cell: no link
         const long ncell = (f.x1 >= f.x0 && f.y1 >= f.y0) ? (long)(f.x1 - f.x0 + 1) * (f.y1 - f.y0 + 1) : 0;
         const int nchunks = (int)std::max(1L, (ncell + FORCE_CHUNK - 1) / FORCE_CHUNK);

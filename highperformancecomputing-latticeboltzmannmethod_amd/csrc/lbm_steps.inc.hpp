@@ -124,7 +124,7 @@ int do_steps(lbm_ctx** cs, int n, int nsteps, int of) {
         if (c->steps_done != cs[0]->steps_done) return fail(LBM_ERR_ARG, "the strips of a group are at different iterations");
     }
     lbm_ctx* c0 = cs[0];
-    const bool transport = n > 1 || (c0->comm && c0->nranks > 1) || c0->loopback;   // a device transport is attached
+    const bool transport = n > 1 || (c0->comm && c0->nranks > 1) || self_wrap(c0);   // a device transport is attached
     int launches = 0;
     std::vector<Launch> L((size_t)n);
     if (n > 1 && c0->group_threads && c0->pool) {

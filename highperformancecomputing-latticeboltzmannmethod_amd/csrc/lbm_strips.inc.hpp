@@ -9,7 +9,14 @@
 // FaceSpans is the single place the offsets and the count are computed; every transport below uses it.
 // rows per face and exchange / rows of each internal face the first launch of a pair recomputes: six and three, or — a deep plan
 // with "deep_halo" 2 — twelve and six
-inline bool device_transport(const lbm_ctx* c) { return c->group_n > 1 || (c->comm && c->nranks > 1) || c->loopback; }
+// The strip is its own north and south neighbour: the test option "loopback" (1 device copies, 2 RCCL to itself) with its walls, or a
+// periodic context on its own (lbm_set_periodic_y; a group of one included), which wraps through the device copies.
+inline int self_wrap(const lbm_ctx* c) { return c->loopback ? c->loopback : (c->periodic_y && c->group_n <= 1) ? 1 : 0; }
+// The neighbours of a member of a group: the strips below and above, and — periodic y — the ring: strip n-1 below strip 0, strip 0 above
+// strip n-1 (with two strips both neighbours are the same peer).
+inline lbm_ctx* south_of(const lbm_ctx* c) { return c->nb_south ? c->nb_south : c->periodic_y ? c->ring_south : nullptr; }
+inline lbm_ctx* north_of(const lbm_ctx* c) { return c->nb_north ? c->nb_north : c->periodic_y ? c->ring_north : nullptr; }
+inline bool device_transport(const lbm_ctx* c) { return c->group_n > 1 || (c->comm && c->nranks > 1) || self_wrap(c); }
 inline bool deep_pairs(const lbm_ctx* c) { return c->deep && deep_depth(c->deep) <= HR1 && c->deep_halo == 2 && device_transport(c); }
 // (a deep LDS shape of seven / eight iterations per launch refreshes seven / eight: the frame holds twelve)
 inline int halo_rows(const lbm_ctx* c) {
@@ -109,14 +116,14 @@ int exchange_rccl(lbm_ctx* c, int dst, hipStream_t s) {
     const FaceSpans f = face_spans(c);
     if (c->rec) {       // dry run: one rank of a multi-process run (its neighbours are other processes), or the device-copy loopback
         const int hr = halo_rows(c);
-        if (c->loopback) {
+        if (self_wrap(c)) {
             rec_xfer(c, ChoreoOp::COPY, s, dst, f.ghost_s, f.top_rows, hr, c);
             rec_xfer(c, ChoreoOp::COPY, s, dst, f.ghost_n, f.bot_rows, hr, c);
         } else if (c->nranks > 1) {
             if (c->rank + 1 < c->nranks) { rec_xfer(c, ChoreoOp::SEND, s, dst, -1, f.top_rows, hr, nullptr); rec_xfer(c, ChoreoOp::RECV, s, dst, f.ghost_n, -1, hr, nullptr); }
             if (c->rank > 0) { rec_xfer(c, ChoreoOp::SEND, s, dst, -1, f.bot_rows, hr, nullptr); rec_xfer(c, ChoreoOp::RECV, s, dst, f.ghost_s, -1, hr, nullptr); }
         }
-        if (c->loopback || c->nranks <= 1) return LBM_OK;
+        if (self_wrap(c) || c->nranks <= 1) return LBM_OK;
         // (a rank of a multi-process run: the posting loops below run too — dry: what they would hand to RCCL goes to the transcript)
     }
     T* b = static_cast<T*>(c->buf[dst]);
@@ -126,9 +133,9 @@ int exchange_rccl(lbm_ctx* c, int dst, hipStream_t s) {
     const size_t sub = (size_t)c->pitch0;                        // elements of one sub-row
     // my top rows and my south ghost rows are "south blocks" (below the strip they border), my bottom rows and north ghost rows are not
     const FaceRuns south_runs = face_runs(hr, trim, true), north_runs = face_runs(hr, trim, false);
-    if (c->loopback) {   // test transports: my own edge rows become my ghost rows
-        if (c->layout != 1) return fail(LBM_ERR_COMM, "loopback requires the row-interleaved layout");
-        if (c->loopback == 2) {   // ... through RCCL itself: a one-rank communicator sending to / receiving from rank 0
+    if (self_wrap(c)) {   // my own edge rows become my ghost rows: the test transports, and the wrap of a periodic context on its own
+        if (c->layout != 1) return fail(LBM_ERR_COMM, "%s requires the row-interleaved layout", c->loopback ? "loopback" : "periodic y");
+        if (self_wrap(c) == 2) {   // ... through RCCL itself: a one-rank communicator sending to / receiving from rank 0
             if (!c->comm) return fail(LBM_ERR_COMM, "loopback=2 needs lbm_comm_init(c, 0, 1, id)");
             NCCLCHK(ncclGroupStart());        // self send/recv pairs match in posting order
             for (int k = 0; k < south_runs.n; ++k) {
@@ -201,14 +208,50 @@ int pull_halos(lbm_ctx** cs, int n, int k, int dst) {
         }
         return LBM_OK;
     };
-    if (k > 0) { int rc = pull(cs[k - 1], face_spans(cs[k - 1]).top_rows, f.ghost_s, true); if (rc) return rc; }
-    if (k + 1 < n) { int rc = pull(cs[k + 1], face_spans(cs[k + 1]).bot_rows, f.ghost_n, false); if (rc) return rc; }
+    // (periodic y: the ring — strip n-1's top rows are strip 0's south ghost rows, strip 0's bottom rows strip n-1's north ones)
+    lbm_ctx* south = k > 0 ? cs[k - 1] : c->periodic_y ? cs[n - 1] : nullptr;
+    lbm_ctx* north = k + 1 < n ? cs[k + 1] : c->periodic_y ? cs[0] : nullptr;
+    if (south) { int rc = pull(south, face_spans(south).top_rows, f.ghost_s, true); if (rc) return rc; }
+    if (north) { int rc = pull(north, face_spans(north).bot_rows, f.ghost_n, false); if (rc) return rc; }
     return LBM_OK;
 }
 
 template <typename T>
 int exchange_group(lbm_ctx** cs, int n, int dst) {
     if (n < 2 || cs[0]->skip_exchange) return LBM_OK;
+    if (cs[0]->group_transport == 1 && cs[0]->periodic_y) {
+        // Periodic y, the ring: every member talks to both neighbours, and with two members both are the SAME peer. RCCL pairs the k-th
+        // send to a peer with that peer's k-th receive from the sender, so the order is explicit: all northward messages of every member
+        // first (my top rows to the strip above, which receives them in its SOUTH ghost rows), then all southward ones (my bottom rows to
+        // the strip below, into its NORTH ghost rows). The dry run records the same pairing.
+        const ncclDataType_t dt = sizeof(T) == 8 ? ncclDouble : ncclFloat;
+        const bool dry = cs[0]->rec != nullptr;
+        if (!dry) NCCLCHK(ncclGroupStart());
+        for (int phase = 0; phase < 2; ++phase)
+            for (int k = 0; k < n; ++k) {
+                lbm_ctx* c = cs[k];
+                const int to = phase == 0 ? (k + 1) % n : (k + n - 1) % n, from = phase == 0 ? (k + n - 1) % n : (k + 1) % n;
+                const FaceSpans f = face_spans(c);
+                const long mine = phase == 0 ? f.top_rows : f.bot_rows, ghost = phase == 0 ? f.ghost_s : f.ghost_n;
+                hipStream_t s = exchange_stream(c);
+                if (dry) {
+                    const FaceSpans ff = face_spans(cs[from]);
+                    rec_xfer(c, ChoreoOp::SEND, s, dst, -1, mine, halo_rows(c), nullptr);
+                    c->rec->ops.back().ring = true; c->rec->ops.back().r_strip = to;      // (a SEND reads its own rows: here r_strip names the peer)
+                    rec_xfer(c, ChoreoOp::RECV, s, dst, ghost, phase == 0 ? ff.top_rows : ff.bot_rows, halo_rows(c), cs[from]);
+                    c->rec->ops.back().ring = true;
+                    continue;
+                }
+                T* b = static_cast<T*>(c->buf[dst]);
+                const size_t sub = (size_t)c->pitch0;
+                // (a sender's top rows and a receiver's south ghost rows are "south blocks": both sides walk the same runs)
+                const FaceRuns r = face_runs(halo_rows(c), c->halo_trim != 0, phase == 0);
+                for (int q = 0; q < r.n; ++q) NCCLCHK(ncclSend(b + mine + r.off[q] * sub, r.cnt[q] * sub, dt, to, c->comm, s));
+                for (int q = 0; q < r.n; ++q) NCCLCHK(ncclRecv(b + ghost + r.off[q] * sub, r.cnt[q] * sub, dt, from, c->comm, s));
+            }
+        if (!dry) NCCLCHK(ncclGroupEnd());
+        return LBM_OK;
+    }
     if (cs[0]->group_transport == 1 && cs[0]->rec) {      // dry run: every member's sends (reads) and receives (writes) on its exchange stream
         for (int k = 0; k < n; ++k) {
             lbm_ctx* c = cs[k];
@@ -274,8 +317,8 @@ enum { KIND_LOCAL = 0, KIND_EXTENDED = 1, KIND_EXCHANGE = 2 };
 struct Launch { int depth, kind, src, dst, t; };
 
 inline int join_comm(lbm_ctx* c);
-inline bool face_south(const lbm_ctx* c) { return c->p.y_start > 0 || c->loopback; }
-inline bool face_north(const lbm_ctx* c) { return c->p.y_start + c->nyl < c->p.ny || c->loopback; }
+inline bool face_south(const lbm_ctx* c) { return c->p.y_start > 0 || c->loopback || c->periodic_y; }
+inline bool face_north(const lbm_ctx* c) { return c->p.y_start + c->nyl < c->p.ny || c->loopback || c->periodic_y; }
 
 template <typename T>
 int launch_depth(const lbm_ctx* c, const KArgs<T>& a, int depth, hipStream_t s) {
@@ -536,7 +579,7 @@ int issue_before(lbm_ctx* c, const Launch& L) {
     hipStream_t es = exchange_stream(c);
     auto wait_for_neighbour_pulls = [&](hipStream_t s) -> int {   // group / peer: my edge rows of buf[dst] may still be being read
         if (c->debug_skip_pull_wait) return LBM_OK;               // (TEST ONLY: the dry-run checker must name the race this leaves)
-        for (lbm_ctx* nb : {c->nb_south, c->nb_north})
+        for (lbm_ctx* nb : {south_of(c), north_of(c)})      // (periodic y: the wrapped neighbour too)
             if (nb && c->group_transport == 0 && nb->comm_issued) QCHK(q_wait(c, s, nb, nb->ev_comm));
         return LBM_OK;
     };
@@ -638,9 +681,9 @@ int init_state(lbm_ctx* c) {
     ia.a = static_cast<T*>(c->buf[0]);
     ia.b = static_cast<T*>(c->buf[1]);
     ia.plane = (long)c->plane; ia.pitch = c->pitch; ia.xoff = c->xoff;
-    ia.nx = c->nx; ia.ny_loc = c->nyl; ia.ny_glob = c->p.ny; ia.y_start = c->p.y_start;
+    ia.nx = c->nx; ia.ny_loc = c->nyl; ia.ny_glob = rows_glob(c); ia.y_start = row_start(c);
     ia.cyl_x = c->cyl_x; ia.cyl_y = c->cyl_y; ia.cyl_r2 = (double)(c->cyl_r * c->cyl_r);
-    if (c->has_mask) ia.mv = c->mview;
+    if (geom_masked(c)) ia.mv = c->mview;
     for (int i = 0; i < Q; ++i) ia.feq_in[i] = (T)c->feq_in[i];
     ia.feq_row = (c->has_profile || c->has_sched()) ? static_cast<const T*>(c->d_feqrow) : nullptr;
     ia.solid_count = c->d_solid_count;

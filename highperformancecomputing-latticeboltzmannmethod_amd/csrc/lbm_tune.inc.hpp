@@ -53,7 +53,7 @@ int time_plan(lbm_ctx* c, float* ms_out, int window = 36) {
 
 template <typename T>
 int choose_plan(lbm_ctx* c) {
-    const bool strips = (c->comm && c->nranks > 1) || c->group_n > 1 || c->loopback;
+    const bool strips = (c->comm && c->nranks > 1) || c->group_n > 1 || self_wrap(c);      // (a periodic context is a strip with two faces)
     const Plan fixed = {(strips || c->loopback) ? 1 : c->layout, c->use_nt, c->alternate, c->fuse, c->pair_ty, c->xcd,
                         "fixed by options", c->deep, c->use_ntl};
     const bool p2 = pair_possible(c);
@@ -414,7 +414,7 @@ int do_initialise(lbm_ctx* c) {
     HIPCHK(hipMemcpyAsync(c->d_unstable, &big, sizeof(int), hipMemcpyHostToDevice, c->stream));
     rc = init_state<T>(c);
     if (rc) return rc;
-    if ((c->comm || c->loopback) && c->group_n <= 1) {   // (a group exchanges once all members are initialised)
+    if ((c->comm || self_wrap(c)) && c->group_n <= 1) {   // (a group exchanges once all members are initialised)
         rc = exchange_rccl<T>(c, c->cur, c->stream);
         if (rc) return rc;
         rc = tune_strip_schedule<T>(c);

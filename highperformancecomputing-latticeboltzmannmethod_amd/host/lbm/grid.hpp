@@ -60,6 +60,7 @@ public:
                 for (int side = 0; side < 2; ++side) check(lbm_set_wall(c, side, p.wall_kind[side], p.wall_velocity[side]), "lbm_set_wall");
             if (p.ported())      // every strip carries both ports
                 for (int side = 0; side < 2; ++side) check(lbm_set_port(c, side, p.port_kind[side], p.port_value[side]), "lbm_set_port");
+            if (p.periodic_y) check(lbm_set_periodic_y(c, 1), "lbm_set_periodic_y");   // (every strip: the group joins strip n-1 to strip 0)
             y += n;
         }
         check(lbm_group_link(group(), num_strips(), opt.rccl ? 1 : 0), "lbm_group_link");

@@ -322,6 +322,7 @@ private:
             f.put("forcing_x,"); f.put(SimulationParams::shortest_text(p.forcing_x).c_str()); f.put("\n");
             f.put("forcing_y,"); f.put(SimulationParams::shortest_text(p.forcing_y).c_str()); f.put("\n");
         }
+        if (p.periodic_y) f.put("periodic_y,1\n");                                                          // (periodic runs only; behind every other line)
         std::printf("  simulation_params.csv written\n");
     }
     // calculate_time_averaged_drag (LBMIO.h:367-413): statistics of the CSV values (8 decimals) for timestep > 1000.

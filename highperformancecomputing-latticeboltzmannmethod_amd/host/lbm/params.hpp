@@ -86,6 +86,10 @@ struct SimulationParams {
     // reference's.
     int port_kind[2] = {0, 1};
     double port_value[2] = {0.0, 1.0};
+    // periodic top and bottom boundaries (lbm_solver --periodic-y; not in the reference, whose rows 0 and ny - 1 are walls): row -1 is
+    // row ny - 1 and row ny is row 0, for the populations, the geometry and the inlet profile; no wall rule runs (lbm_set_periodic_y).
+    // Off: everything the run prints and writes is the reference's.
+    bool periodic_y = false;
 
     double nu() const { return (tau - 0.5) / 3.0; }
     bool masked() const { return !obstacle_mask.empty(); }

@@ -59,6 +59,8 @@ public:
             std::printf("  Walls: south %s, north %s\n", params_.wall_banner(0).c_str(), params_.wall_banner(1).c_str());
         if (!opt_.quiet && params_.ported())
             std::printf("  Ports: inlet %s, outlet %s\n", params_.port_text(0).c_str(), params_.port_text(1).c_str());
+        if (!opt_.quiet && params_.periodic_y)
+            std::printf("  Top and bottom: periodic (row -1 is row %d; no wall rule runs)\n", params_.ny - 1);
         if (!opt_.quiet && params_.masked()) {
             std::printf("  Obstacle: %s %s, frontal height D=%d cells\n  Solid cells: %d\n  Plan: %s\n", params_.bodied() ? "bodies" : "mask",
                         params_.bodied() ? params_.obstacle_bodies_file.c_str() : params_.obstacle_mask_file.c_str(),

@@ -75,6 +75,10 @@ static void usage() {
               "pressure:0.995. A pressure inlet takes no --inlet-profile and no inlet schedule; Reynolds number and Cd / Cl keep\n"
               "referring to --inlet-velocity. The ports do not know about --forcing, and the on-node walls exchange mass with the fluid\n"
               "wherever the density is not 1, so the flux of a pressure-driven channel is not constant along x.\n"
+              "--periodic-y: periodic top and bottom boundaries in place of the two walls: row -1 is row ny-1 and row ny is row 0, for the\n"
+              "flow, the obstacle (a body may lie across the seam) and --inlet-profile; no wall rule runs. For a cascade or an infinite row\n"
+              "of bodies, a wake without blockage, a shear layer, a cross-stream --forcing. Also with --gpus N / --strips N (every strip at\n"
+              "least 12 rows). Not with a wall KIND other than no-slip, and not with --obstacle-bodies that touch row 0 or row ny-1.\n"
               "--stats-start N: time-averaged statistics from step N on, sampled on the device every --output-frequency steps;\n"
               "the run ends with mean_fields.vtk and mean_fields.csv (means of rho, ux, uy and the Reynolds stresses). With\n"
               "--checkpoint / --restart the sums travel beside the checkpoint as FILE.stats. --no-final suppresses the two\n"
@@ -144,6 +148,7 @@ int main(int argc, char** argv) {
         else if (k == "--trt-magic") trt_magic = val();
         else if (k == "--forcing") forcing = val();
         else if (k == "--stats-start") stats_start = val();
+        else if (k == "--periodic-y") params.periodic_y = true;
         else if (k == "--wall-south" || k == "--wall-north" || k == "--walls") {   // checked here: no device is touched before a bad value exits
             try {
                 const std::string kind = val();
@@ -314,6 +319,26 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "%s\n", e.what());
             return 2;
         }
+    }
+    if (params.periodic_y) {   // checked before any device is touched: what lbm_initialise would refuse
+        if (params.walled()) {
+            std::fprintf(stderr, "--periodic-y cannot be combined with a %s wall (--wall-south / --wall-north / --walls): no wall rule runs on a periodic lattice\n",
+                         params.wall_text(params.wall_kind[0] != 0 ? 0 : 1).c_str());
+            return 2;
+        }
+        const int nstrips = std::min(params.ny, opt.strips > 0 ? opt.strips : std::max(1, opt.gpus));
+        if (params.ny / std::max(1, nstrips) < 12) {
+            std::fprintf(stderr, "--periodic-y: %d rows in %d strip(s): every strip needs at least 12 rows\n", params.ny, nstrips);
+            return 2;
+        }
+        if (params.bodied())
+            for (int row : {0, params.ny - 1})
+                for (int x = 0; x < params.nx; ++x)
+                    if (params.obstacle_mask[(size_t)row * params.nx + x]) {
+                        std::fprintf(stderr, "--periodic-y: --obstacle-bodies has a labelled cell on row %d: a body's links across the seam would be missed (keep bodies off rows 0 and %d, or use --obstacle-mask)\n",
+                                     row, params.ny - 1);
+                        return 2;
+                    }
     }
     if (reynolds > 0.0 && params.masked()) params.inlet_velocity = reynolds * params.nu() / params.mask_frontal_height;
     else if (reynolds > 0.0) params.inlet_velocity = reynolds * params.nu() / (2.0 * params.cylinder_radius * params.ny);

@@ -428,6 +428,32 @@ int  lbm_set_port(lbm_ctx* c, int side, int kind, double value);
 /* The port of `side` as set (west: kind 0, value 0; east: kind 1, value 1 on a fresh context); either pointer may be NULL. LBM_ERR_ARG: null context, side outside 0..1. */
 int  lbm_get_port(const lbm_ctx* c, int side, int* kind, double* value);
 
+/* ---- periodic top and bottom boundaries (periodic y) ----
+ * on = 1: the lattice is the ny rows repeated for ever. Row -1 is row ny - 1 and row ny is row 0, for the populations, for the geometry
+ * - solid(x, y) = S(x, y mod ny) with S what lbm_get_solid returns, disc or mask - and for the inlet profile, u[y mod ny]. No wall rule
+ * runs anywhere: a fluid cell of row 0 or ny - 1 takes its nine pulls, then the port rules if it lies on column 0 or nx - 1 (west, then
+ * east, as ever). Everything else is the reference's: solid cells, the stability scan, the initial state, zeros in the E/W ghost columns
+ * (those of the wrapped rows included). Forces cross the seam: a fluid cell (x, y) whose neighbour (x + cx, (y + cy) mod ny) is solid
+ * contributes 2 c_i f_i, to the strip that owns the fluid cell. Snapshots (macros, statistics, probes) are per cell what they were;
+ * frames take the central difference for d/dy on rows 0 and ny - 1, with the wrapped neighbour (the x edges keep the one-sided form).
+ * Probe coordinates stay 0 <= py <= ny - 1: there is no interpolation across the seam.
+ * A periodic context is a strip with two live faces: it uses the row-interleaved layout and the strip plans, and wraps through device
+ * copies of its own edge rows into its own ghost rows after every launch (the halo exchange of a strip, with itself as both
+ * neighbours). In a group (lbm_group_link) strip 0 and strip n - 1 become neighbours on either transport. It is never a whole domain
+ * for the plans: pinning "split", a whole-domain-only shape ("deep" 10, 11: the fp64 64x40 regions) or "layout" 0 makes lbm_initialise fail with
+ * LBM_ERR_ARG, naming the option. ny >= 2 * LBM_HALO_ROWS, like any strip with neighbours.
+ * lbm_initialise also refuses, naming the offender: a wall that is not no-slip (lbm_set_wall) beside periodic y; body labels
+ * (lbm_set_body_labels) with a labelled cell on row 0 or ny - 1 (the per-body boxes are clipped at the domain, so such a body's links
+ * across the seam would be missed; bodies away from the seam work); a communicator of more than one rank (lbm_comm_init: rings of
+ * processes are not built). lbm_halo_export / lbm_halo_import refuse a periodic context. Checkpoints carry the setting (lbm_save_state:
+ * magic "LBMCKPT3", flag bit 9, no payload) and load only into a context with the same setting.
+ * Without the call, or with on = 0, every result, kernel name, plan candidate, checkpoint byte and dry-run record is what it was.
+ * lbm_set_option(c, "periodic_y", on) is the same call. Call after lbm_create and before lbm_initialise.
+ * LBM_ERR_ARG (the text names the offender): a null context, an initialised context, on outside 0..1. */
+int  lbm_set_periodic_y(lbm_ctx* c, int on);
+/* 1 on a periodic context, else 0; 0 for a null context. */
+int  lbm_get_periodic_y(const lbm_ctx* c);
+
 /* ---- strip halo exchange (replaces Grid::exchange_ghost_cells, LBMGrid.h:249-283) ----
  * Device path: RCCL send/recv of the LBM_HALO_ROWS edge rows per face (one contiguous run in the row-interleaved
  * layout) once per launch of up to six iterations (or 2 x LBM_HALO_ROWS rows once per two such launches: option "deep_halo" 2,
@@ -621,7 +647,7 @@ int lbm_debug_inlet_scale(const double* s, int n, int mode, int precision, const
 /* What the head of a checkpoint says about a run (csrc/lbm_ckpt.hpp, which also describes the file): the fixed header, then for each
  * optional field whether the run has it and its value. has_*: 0 or 1; collision: 0, or the setter's model as lbm_ctx holds it (2 Smagorinsky,
  * 4 TRT, 8 forcing) with collision_param = {Cs}, {magic} or {fx, fy}; walls = {south kind, south velocity, north kind, north velocity};
- * ports = {west kind, west value, east kind, east value} (has_ports: either port is off its default). */
+ * ports = {west kind, west value, east kind, east value} (has_ports: either port is off its default); has_periodic_y: lbm_set_periodic_y. */
 typedef struct lbm_ckpt_head {
     int nx, ny, y_start, local_ny, precision, steps_done;
     double tau, inlet_velocity, cylinder_x, cylinder_y, cylinder_radius;
@@ -631,6 +657,7 @@ typedef struct lbm_ckpt_head {
     double walls[4];
     int has_ports;
     double ports[4];
+    int has_periodic_y;
 } lbm_ckpt_head;
 #define LBM_CKPT_HEAD_MAX 184   /* bytes: no head is longer (every field present, the collision model with two parameters) */
 /* Test hook, callable without a device: the head lbm_save_state writes for a context that *h describes, through the function it calls,
