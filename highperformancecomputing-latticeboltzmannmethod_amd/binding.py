@@ -100,6 +100,8 @@ def lib():
         L.lbm_set_trt.argtypes = [vp, C.c_double]
         L.lbm_set_forcing.argtypes = [vp, C.c_double, C.c_double]
         L.lbm_get_forcing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.lbm_set_mrt.argtypes = [vp, C.c_double, C.c_double]
+        L.lbm_get_mrt.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.lbm_set_wall.argtypes = [vp, C.c_int, C.c_int, C.c_double]
         L.lbm_get_wall.argtypes = [vp, C.c_int, C.POINTER(C.c_int), dp]
         L.lbm_debug_wall_rule.argtypes = [C.c_int, C.c_int, C.c_double, C.c_int, dp, dp]
@@ -516,6 +518,9 @@ class Context:
     scale factors of the inflow, one per iteration (lbm_set_inlet_schedule): a table holds its last entry for ever, a pair
     (table, "repeat") is periodic (see cosine_ramp, sine_pulse). forcing: optional pair (fx, fy), a uniform driving force density in
     lattice units on every fluid cell (lbm_set_forcing, Guo's scheme on BGK); (0, 0) / None: none; not with smagorinsky or trt_magic.
+    mrt: optional pair (bulk_rate, magic) of a multiple-relaxation-time collision (lbm_set_mrt): TRT with that magic parameter whose
+    bulk rate, in (0, 2), is free of tau (1/tau: TRT; lower: more bulk viscosity); bulk_rate 0 / None: BGK; not with smagorinsky,
+    trt_magic or forcing.
     ports: optional pair (west, east) of the two open ends (lbm_set_port) in place of the velocity inlet and the pressure outlet with
     rho = 1: west "velocity" or ("pressure", rho), east ("pressure", rho) or ("velocity", u); None in either place: that port's default.
     A west pressure port takes neither inlet_profile nor inlet_schedule (initialise() fails). periodic_y: True makes the top and bottom
@@ -525,7 +530,7 @@ class Context:
     def __init__(self, nx, ny, tau=0.6, inlet_velocity=0.01333, cylinder_x=0.2, cylinder_y=0.5,
                  cylinder_radius=0.05, y_start=0, local_ny=0, precision="f64", device=0, force_log_capacity=0,
                  options=None, solid=None, inlet_profile=None, smagorinsky=None, bodies=None, frames=None, trt_magic=None,
-                 probes=None, probe_capacity=None, walls=None, inlet_schedule=None, forcing=None, ports=None, periodic_y=False):
+                 probes=None, probe_capacity=None, walls=None, inlet_schedule=None, forcing=None, ports=None, periodic_y=False, mrt=None):
         if solid is not None and bodies is not None:
             raise LbmError("solid= and bodies= exclude each other: the body labels are the geometry (solid where nonzero)")
         self.L = lib()
@@ -560,6 +565,8 @@ class Context:
             self.set_inlet_schedule(*_schedule(inlet_schedule))
         if forcing is not None:
             self.set_forcing(*forcing)
+        if mrt is not None:
+            self.set_mrt(*mrt)
         if ports is not None:
             for side, (kind, v) in zip(("west", "east"), _port_pair(ports)):
                 self.set_port(side, kind, v)
@@ -639,6 +646,17 @@ class Context:
     def set_forcing(self, fx, fy):
         """lbm_set_forcing: the uniform driving force density (fx, fy), each of magnitude below 1 ((0, 0): none); before initialise()."""
         self._chk(self.L.lbm_set_forcing(self.h, float(fx), float(fy)))
+
+    def set_mrt(self, bulk_rate, magic):
+        """lbm_set_mrt: the bulk rate in (0, 2) and the magic parameter in (0, 1] of the MRT collision (bulk_rate 0: plain BGK); before
+        initialise()."""
+        self._chk(self.L.lbm_set_mrt(self.h, float(bulk_rate), float(magic)))
+
+    def mrt(self):
+        """(bulk_rate, magic) as set (lbm_get_mrt); (0.0, 0.0) without MRT."""
+        sb, magic = C.c_double(), C.c_double()
+        self._chk(self.L.lbm_get_mrt(self.h, C.byref(sb), C.byref(magic)))
+        return sb.value, magic.value
 
     def forcing(self):
         """(fx, fy) as set (lbm_get_forcing); (0.0, 0.0) without a force."""
@@ -929,12 +947,12 @@ class Group:
     solid: optional global (ny, nx) obstacle mask, inlet_profile: optional global [ny] inlet velocities, smagorinsky: optional LES
     constant Cs, trt_magic: optional TRT magic parameter, bodies: optional global (ny, nx) body numbers (in place of solid), frames: optional frame stride k, probes / probe_capacity: optional probe points (global coordinates), walls: optional kinds of the
     bottom and top walls (as Context takes them), inlet_schedule: optional scale factors of the inflow per iteration (likewise), forcing:
-    optional driving force (fx, fy), ports: optional pair (west, east) of the two open ends (as Context takes them), periodic_y: True joins strip
+    optional driving force (fx, fy), mrt: optional MRT pair (bulk_rate, magic), ports: optional pair (west, east) of the two open ends (as Context takes them), periodic_y: True joins strip
     n - 1 to strip 0 (periodic top and bottom, as Context takes it); all given to every member."""
 
     def __init__(self, nx, ny, bounds, devices=None, transport="peer", options=None, solid=None, inlet_profile=None, smagorinsky=None,
                  bodies=None, frames=None, trt_magic=None, probes=None, probe_capacity=None, walls=None, inlet_schedule=None, forcing=None,
-                 ports=None, periodic_y=False, **kw):
+                 ports=None, periodic_y=False, mrt=None, **kw):
         from .strips import partition_rows
         if isinstance(bounds, int):
             bounds = partition_rows(ny, bounds)
@@ -943,7 +961,7 @@ class Group:
         self.ctxs = [Context(nx, ny, y_start=y0, local_ny=n, device=d, options=options, solid=solid, inlet_profile=inlet_profile,
                              smagorinsky=smagorinsky, bodies=bodies, frames=frames, trt_magic=trt_magic, probes=probes,
                              probe_capacity=probe_capacity, walls=walls, inlet_schedule=inlet_schedule, forcing=forcing, ports=ports,
-                             periodic_y=periodic_y, **kw)
+                             periodic_y=periodic_y, mrt=mrt, **kw)
                      for (y0, n), d in zip(bounds, devices)]
         self.L = lib()
         self._arr = (C.c_void_p * len(self.ctxs))(*[c.h for c in self.ctxs])

@@ -43,7 +43,8 @@ def embedded_id(path=LIB):
 
 
 # the collision models (csrc/lbm_plan.hpp collision_models) as (Arith base, `park`: the fp64 64x40 regions are built for it): BGK,
-# Smagorinsky (LES), two relaxation times (TRT), BGK under a driving force (lbm_set_forcing)
+# Smagorinsky (LES), two relaxation times (TRT), BGK under a driving force (lbm_set_forcing). Models that have objects of their own only:
+# the MRT kernels (lbm_set_mrt, base 16; no 64x40 regions) share TRT's pair code and are instantiated in TRT's objects (the row's `unit`)
 COLLISION_MODELS = ((0, True), (2, True), (4, True), (8, True))
 COLLISION_BASES = tuple(base for base, _ in COLLISION_MODELS)
 

@@ -25,6 +25,11 @@ bool launch_col(const KArgs<T>& a, const K2Extra<T>& e, int depth, bool nt, hipS
 #if defined(LBM_COL_T) && defined(LBM_AR_BASE)
 LBM_COL_INST(LBM_COL_T, RK_STD, LBM_AR_BASE);
 LBM_COL_INST(LBM_COL_T, RK_STD, LBM_AR_BASE | 1);
+#if LBM_AR_BASE == 4      // TRT's objects hold the model that rides with it (collision_models: unit), MRT
+static_assert(LBM_AR_BASE == AR_STRICT_TRT && collision_model(AR_STRICT_MRT).unit == AR_STRICT_TRT);
+LBM_COL_INST(LBM_COL_T, RK_STD, AR_STRICT_MRT);
+LBM_COL_INST(LBM_COL_T, RK_STD, AR_STRICT_MRT | 1);
+#endif
 #elif defined(LBM_COL_TALL)
 LBM_COL_INST(float, RK_TALL, AR_STRICT | LBM_COL_TALL);
 #elif defined(LBM_COL_PARK)

@@ -946,6 +946,26 @@ int lbm_get_forcing(const lbm_ctx* c, double* fx, double* fy) {
     return LBM_OK;
 }
 
+int lbm_set_mrt(lbm_ctx* c, double bulk_rate, double magic) {
+    if (!c) return fail(LBM_ERR_ARG, "lbm_set_mrt: null context");
+    if (c->initialised) return fail(LBM_ERR_ARG, "lbm_set_mrt must be called before lbm_initialise");
+    if (!std::isfinite(bulk_rate) || bulk_rate < 0.0 || bulk_rate >= 2.0)
+        return fail(LBM_ERR_ARG, "lbm_set_mrt: bulk rate = %g (0, or finite values in (0, 2) only)", bulk_rate);
+    if (!std::isfinite(magic)) return fail(LBM_ERR_ARG, "lbm_set_mrt: magic parameter = %g (finite values only)", magic);
+    if (bulk_rate == 0.0) return set_collision(c, AR_STRICT_MRT, 0.0, "lbm_set_mrt:", true, 0.0);
+    if (!(magic > 0.0) || magic > 1.0) return fail(LBM_ERR_ARG, "lbm_set_mrt: magic parameter = %g (finite values in (0, 1] only)", magic);
+    if (!(c->p.tau > 0.5)) return fail(LBM_ERR_ARG, "lbm_set_mrt: tau = %g (the MRT rates need tau > 0.5)", c->p.tau);
+    return set_collision(c, AR_STRICT_MRT, bulk_rate, "lbm_set_mrt: (bulk rate, magic) =", true, magic);
+}
+
+int lbm_get_mrt(const lbm_ctx* c, double* bulk_rate, double* magic) {
+    if (!c) return fail(LBM_ERR_ARG, "lbm_get_mrt: null context");
+    const bool on = c->collision == AR_STRICT_MRT;
+    if (bulk_rate) *bulk_rate = on ? c->collision_param : 0.0;
+    if (magic) *magic = on ? c->collision_param2 : 0.0;
+    return LBM_OK;
+}
+
 int lbm_set_wall(lbm_ctx* c, int side, int kind, double velocity) {
     if (!c) return fail(LBM_ERR_ARG, "lbm_set_wall: null context");
     if (c->initialised) return fail(LBM_ERR_ARG, "lbm_set_wall must be called before lbm_initialise");
@@ -1401,7 +1421,7 @@ int lbm_debug_body_chunks(const unsigned char* labels, int nx, int ny, int y_sta
 
 /* TEST HOOK (no device needed): the candidates lbm_initialise would time for a whole-domain context of this grid, one per line:
  * "name|lbm_set_option pairs|dominant kernel|iterations per launch". arith: 0 / 1, 2 / 3 for a Smagorinsky (LES) context, 4 / 5 for a TRT one,
- * 8 / 9 for one with a driving force (lbm_set_forcing). */
+ * 8 / 9 for one with a driving force (lbm_set_forcing), 16 / 17 for an MRT one (lbm_set_mrt). */
 int lbm_debug_plan_candidates(int nx, int ny, int precision, int arith, int num_cus, char* out, int cap) {
     if (!out || cap < 1 || nx < 1 || ny < 1) return fail(LBM_ERR_ARG, "bad argument");
     PlanQuery q;
@@ -1654,6 +1674,46 @@ int lbm_debug_choreography(int nx, int ny, const int* bounds2, int nstrips, int 
     const int nbad = (int)chk.bad.size();
     cleanup();
     return nbad;
+}
+
+/* TEST HOOK (no device needed): the collision models' setters on a context no device knows: see include/lbm_hip.h. */
+int lbm_debug_collision_setters(double tau, int precision, const char* options, const int* setter, const double* v1, const double* v2, int n,
+                                int* rc, char* texts, int cap, double* collision3) {
+    if (!setter || !v1 || !v2 || n < 0 || !rc || !texts || cap < 1 || !collision3) return fail(LBM_ERR_ARG, "lbm_debug_collision_setters: null argument");
+    lbm_ctx* c = choreo_fake_ctx(64, 64, 0, 64, precision, 0);
+    c->p.tau = tau;
+    for (const char* q = options ? options : ""; *q;) {        // "key=value key=value"
+        while (*q == ' ') ++q;
+        const char* eq = strchr(q, '=');
+        if (!eq) break;
+        const std::string key(q, eq);
+        char* end = nullptr;
+        const long v = strtol(eq + 1, &end, 10);
+        if (int orc = lbm_set_option(c, key.c_str(), v)) { delete c; return orc; }
+        q = end;
+    }
+    std::string text;
+    int bad = LBM_OK;
+    for (int k = 0; k < n && !bad; ++k) {
+        switch (setter[k]) {
+            case 0: rc[k] = lbm_set_smagorinsky(c, v1[k]); break;
+            case 1: rc[k] = lbm_set_trt(c, v1[k]); break;
+            case 2: rc[k] = lbm_set_forcing(c, v1[k], v2[k]); break;
+            case 3: rc[k] = lbm_set_mrt(c, v1[k], v2[k]); break;
+            case 4: c->initialised = true; rc[k] = LBM_OK; break;
+            case 5: rc[k] = refuse_deep(c, c->collision, c->deep, true); break;
+            default: bad = LBM_ERR_ARG; continue;
+        }
+        if (rc[k]) text += lbm_last_error();
+        text += "\n";
+    }
+    collision3[0] = c->collision;
+    (void)lbm_get_mrt(c, &collision3[1], &collision3[2]);
+    delete c;
+    if (bad) return fail(LBM_ERR_ARG, "lbm_debug_collision_setters: setter 0..5 only");
+    if ((int)text.size() + 1 > cap) return fail(LBM_ERR_ARG, "lbm_debug_collision_setters: buffer too small (%zu bytes needed)", text.size() + 1);
+    memcpy(texts, text.c_str(), text.size() + 1);
+    return LBM_OK;
 }
 
 /* TEST HOOK (no device needed): every rank of a multi-process strip run issues its launch groups DRY (as lbm_debug_choreography does for one

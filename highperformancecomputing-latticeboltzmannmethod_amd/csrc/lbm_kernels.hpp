@@ -176,6 +176,9 @@ struct KArgs {
     union { T les_tau; T trt_wm; };
     union { T les_tau2; T trt_wa; };
     union { T les_c; T trt_wb; };
+    // An MRT context (lbm_set_mrt; never LES, TRT or forcing as well) carries wm in trt_wm as TRT does, the folded rates of its contracted
+    // arithmetic in trt_wa / trt_wb, all three as TRT does, and the bulk rate sb and the folded (sb - wp)/(4 wp) in frc_gx / frc_gy of the block at the
+    // front, which only a forced context reads otherwise: no field moves or is added.
     // The two physical walls (lbm_set_wall), appended for the same reason: wall_pack of the two kinds, and what each wall adds to and
     // subtracts from its diagonal populations (wall_ks: k = u_w / 6 of a moving wall, formed on the host in double; the identity
     // operands otherwise). Launch-uniform: read inside the bottom / top branches of apply_bcs only. Bits 4 and 5 of `walls` are the
@@ -363,12 +366,17 @@ __device__ __forceinline__ void bcs_at(const KArgs<T>& a, T (&f)[Q], int x, int 
 //                 taken at u = (sum c f + F/2) / rho and the source S_i = (1 - 1/(2 tau)) w_i [3 (c_i - u) + 9 (c_i.u) c_i] . F is added
 //                 to the relaxed populations. Separate instantiations for the same reason. Forcing excludes LES and TRT: there are no
 //                 values 10 to 13.
+//   AR_STRICT_MRT / AR_CONTRACTED_MRT  the same two arithmetic modes with the multiple-relaxation-time operator (lbm_set_mrt): TRT's even
+//                 and odd parts of each pair, with the even parts of the two axis pairs (and of the two diagonal pairs) split into their
+//                 half sum, relaxed with the launch-uniform bulk rate sb like the rest population, and their half difference, relaxed
+//                 with 1/tau. Separate instantiations for the same reason. MRT excludes LES, TRT and forcing: of 16 to 31 there are 16, 17.
 enum Arith { AR_STRICT = 0, AR_CONTRACTED = 1, AR_STRICT_LES = 2, AR_CONTRACTED_LES = 3, AR_STRICT_TRT = 4, AR_CONTRACTED_TRT = 5,
-             AR_STRICT_FORCED = 8, AR_CONTRACTED_FORCED = 9 };
+             AR_STRICT_FORCED = 8, AR_CONTRACTED_FORCED = 9, AR_STRICT_MRT = 16, AR_CONTRACTED_MRT = 17 };
 constexpr bool ar_contracted(int ar) { return (ar & 1) != 0; }
 constexpr bool ar_les(int ar) { return (ar & 2) != 0; }
 constexpr bool ar_trt(int ar) { return (ar & 4) != 0; }
 constexpr bool ar_forced(int ar) { return (ar & 8) != 0; }
+constexpr bool ar_mrt(int ar) { return (ar & 16) != 0; }
 constexpr int ar_of(bool contracted, bool les, bool trt = false) { return (contracted ? 1 : 0) | (les ? 2 : 0) | (trt ? 4 : 0); }
 
 __device__ __forceinline__ double fma_t(double a, double b, double c) { return __builtin_fma(a, b, c); }
@@ -474,8 +482,10 @@ __device__ __forceinline__ T les_tau_inv_strict(const T (&f)[Q], T rho, T ux, T 
 // relaxation rate of the cell comes from les_tau / les_tau2 / les_c (KArgs); BGK modes never read those three. TRT modes: tau_inv
 // relaxes the even part of each opposite pair (and the rest population), `les_tau` carries the rate of the odd part, wm = 1/tau_minus, and les_tau2 / les_c the folded rates (wp + wm)/2, (wp - wm)/2.
 // FORCED modes: tau_inv is BGK's, and the four values carry gx, gy, hx, hy (KArgs::frc_*): g = (1 - wp/2) F, h = F/2.
+// MRT modes: tau_inv is wp, `les_tau` carries wm as in TRT, les_tau2 / les_c TRT's folded rates, frc_hy the bulk
+// rate sb and mrt_cb the folded (sb - wp)/(4 wp).
 template <typename T, int AR = AR_STRICT>
-__device__ __forceinline__ void bgk_collide(T (&f)[Q], T tau_inv, T les_tau = T(0), T les_tau2 = T(0), T les_c = T(0), T frc_hy = T(0)) {
+__device__ __forceinline__ void bgk_collide(T (&f)[Q], T tau_inv, T les_tau = T(0), T les_tau2 = T(0), T les_c = T(0), T frc_hy = T(0), T mrt_cb = T(0)) {
     T rho = T(0), ux = T(0), uy = T(0);
     if constexpr (ar_contracted(AR)) {
         // moments as short trees over opposite pairs (depth 4 / 3 instead of chains of 9 / 6 dependent additions)
@@ -484,6 +494,8 @@ __device__ __forceinline__ void bgk_collide(T (&f)[Q], T tau_inv, T les_tau = T(
         rho = ((f[0] + a13) + (a24 + a57)) + a68;
         ux = (d13 + d57) - d68;
         uy = (d24 + d57) + d68;
+        T mrt_sa = T(0), mrt_sd = T(0);       // MRT: the sums of the axis and of the diagonal populations, while the pair sums are at hand
+        if constexpr (ar_mrt(AR) && sizeof(T) == 8) { mrt_sa = a13 + a24; mrt_sd = a57 + a68; }
         if constexpr (ar_forced(AR)) { ux = ux + les_c; uy = uy + frc_hy; }      // Guo: the momenta take h = F/2, so v below is 3u of the forced velocity
         // v = 3u. 1 + 3cu + 4.5cu^2 - 1.5u^2 = base + cv*(1 + 0.5cv) with cv = c.v and base = 1 - v^2/6: the inner bracket
         // is one FMA with INLINE constants (0.5, 1.0). gfx950 VALU instructions take one SGPR/literal operand at most, so
@@ -502,27 +514,68 @@ __device__ __forceinline__ void bgk_collide(T (&f)[Q], T tau_inv, T les_tau = T(
         }
         const T base = fma_t(T(-1.0 / 6.0), fma_t(vx, vx, vy * vy), T(1.0));
         const T wr0 = wgt<T>(0) * rho, wr1 = wgt<T>(1) * rho, wr5 = wgt<T>(5) * rho;
-        if constexpr (ar_trt(AR)) {
+        if constexpr (ar_trt(AR) || ar_mrt(AR)) {
             // f_i' = f_i + wa (feq_i - f_i) + wb (feq_ib - f_ib) with wa = (wp + wm)/2, wb = (wp - wm)/2: BGK's residuals of the two
             // directions (c.v changes its sign for the opposite one), then two FMAs each, in place. Two temporaries beyond BGK's.
+            // MRT is TRT plus the same g = (sb - wp)/4 S on the four populations of a group (the axis pairs; the diagonal pairs), S the sum
+            // of the group's four residuals (-4 ta, -4 td), with the rest population relaxed by sb. Since wa + wb = wp, raising the
+            // equilibrium's `base` of a group by g / (wp w rho) adds exactly g to each of its populations: a group runs TRT's pair code
+            // on a base of its own, and nothing but that base is alive beyond TRT's values. With t = 1 - base = |v|^2 / 6, 4 w5 = w1 and
+            // kb = (sb - wp) / (4 wp) folded on the host:  base_axes = base + kb ((4 + 2 t) - 9 (f1 + f2 + f3 + f4) / rho),
+            // base_diagonals = base + 4 kb ((1 + 2 t) - 9 (f5 + f6 + f7 + f8) / rho), in inline constants only (a VALU instruction reads
+            // one scalar register or literal at most). That is the fp64 form; fp32 adds g itself (below).
             const T wa = les_tau2, wb = les_c;
-            f[0] = fma_t(tau_inv, fma_t(wr0, base, -f[0]), f[0]);
-            auto pair = [&](int i, int ib, T cv, T wr) {     // i: the direction whose c.v is `cv`; ib: its opposite
-                const T ri = fma_t(wr, fma_t(cv, fma_t(cv, T(0.5), T(1.0)), base), -f[i]);
-                const T rb = fma_t(wr, fma_t(cv, fma_t(cv, T(0.5), T(-1.0)), base), -f[ib]);
+            f[0] = fma_t(ar_mrt(AR) ? frc_hy : tau_inv, fma_t(wr0, base, -f[0]), f[0]);
+            auto pair = [&](int i, int ib, T cv, T wr, T b, T g = T(0)) {     // i: the direction whose c.v is `cv`; ib: its opposite; b: the base
+                const T ri = fma_t(wr, fma_t(cv, fma_t(cv, T(0.5), T(1.0)), b), -f[i]);
+                const T rb = fma_t(wr, fma_t(cv, fma_t(cv, T(0.5), T(-1.0)), b), -f[ib]);
+                if constexpr (ar_mrt(AR) && sizeof(T) == 4) { f[i] += g; f[ib] += g; }
                 f[i] = fma_t(wa, ri, fma_t(wb, rb, f[i]));
                 f[ib] = fma_t(wa, rb, fma_t(wb, ri, f[ib]));
             };
             // One pair after the other: an empty asm statement that "rewrites" a finished pair together with the next pair's inputs keeps
             // the compiler from starting the next pair's residuals early (it would hold all eight and spill in the fp64 register kernel).
             auto then = [&](int i, int ib, int j, int jb) { asm volatile("" : "+v"(f[i]), "+v"(f[ib]), "+v"(f[j]), "+v"(f[jb])); };
-            pair(5, 7, vx + vy, wr5);
+            if constexpr (ar_mrt(AR) && sizeof(T) == 4) {
+                // fp32: the shift of the base costs the register kernel a wave of occupancy (84 to 86 VGPRs where 80 are the limit); g
+                // itself, formed in front of its group from the populations the group is about to replace and added to them, does not
+                auto group = [&](int i, int ib, int j, int jb, T k) {
+                    const T sum = ((f[i] + f[ib]) + f[j]) + f[jb];
+                    return mrt_cb * (tau_inv * fma_t(wr1, fma_t(T(2.0), T(1.0) - base, k), -sum));
+                };
+                T g = group(5, 7, 8, 6, T(1.0));
+                pair(5, 7, vx + vy, wr5, base, g);
+                then(5, 7, 8, 6);
+                pair(8, 6, vx - vy, wr5, base, g);
+                then(8, 6, 1, 3);
+                g = group(1, 3, 2, 4, T(4.0));
+                pair(1, 3, vx, wr1, base, g);
+                then(1, 3, 2, 4);
+                pair(2, 4, vy, wr1, base, g);
+                return;
+            }
+            if constexpr (ar_mrt(AR)) {
+                const T t2 = T(2.0) * (T(1.0) - base);
+                auto nine_over_rho = [&](T sum) { const T x = sum * inv3; return fma_t(T(2.0), x, x); };
+                T ba = fma_t(mrt_cb, (t2 + T(4.0)) - nine_over_rho(mrt_sa), base);
+                T bd = fma_t(mrt_cb, T(4.0) * ((t2 + T(1.0)) - nine_over_rho(mrt_sd)), base);
+                asm volatile("" : "+v"(ba), "+v"(bd));
+                pair(5, 7, vx + vy, wr5, bd);
+                then(5, 7, 8, 6);
+                pair(8, 6, vx - vy, wr5, bd);
+                then(8, 6, 1, 3);
+                pair(1, 3, vx, wr1, ba);
+                then(1, 3, 2, 4);
+                pair(2, 4, vy, wr1, ba);
+                return;
+            }
+            pair(5, 7, vx + vy, wr5, base);
             then(5, 7, 8, 6);
-            pair(8, 6, vx - vy, wr5);
+            pair(8, 6, vx - vy, wr5, base);
             then(8, 6, 1, 3);
-            pair(1, 3, vx, wr1);
+            pair(1, 3, vx, wr1, base);
             then(1, 3, 2, 4);
-            pair(2, 4, vy, wr1);
+            pair(2, 4, vy, wr1, base);
             return;
         }
 #pragma unroll
@@ -584,9 +637,30 @@ __device__ __forceinline__ void bgk_collide(T (&f)[Q], T tau_inv, T les_tau = T(
         const T feq = wr * bracket;
         fi = fi - tau_inv * (fi - feq);
     };
-    relax(f[0], wr0, (T(1.0) + T(0.0)) - c15);      // cu = 0: 1.0 + 3.0*0 + 4.5*0*0 = 1.0 exactly
+    if constexpr (ar_mrt(AR)) { const T feq0 = wr0 * ((T(1.0) + T(0.0)) - c15); f[0] = f[0] - frc_hy * (f[0] - feq0); }     // the rest population: the bulk rate
+    else relax(f[0], wr0, (T(1.0) + T(0.0)) - c15);      // cu = 0: 1.0 + 3.0*0 + 4.5*0*0 = 1.0 exactly
+    T mrt_np = T(0), mrt_wmn = T(0);      // MRT: the even part and the relaxed odd part of a group's first pair, kept for its second
     auto pair = [&](int i, int ib, T cu, T wr) {     // i: the direction whose c.u is `cu`; ib: its opposite
         const T t3 = T(3.0) * cu, t45 = (T(4.5) * cu) * cu;
+        if constexpr (ar_mrt(AR)) {
+            // MRT (tests/mrt_reference.py mrt_collide, operation by operation): TRT's np, nm of the pair; the first pair (1,3 / 5,7) of a
+            // group leaves them, the second (2,4 / 8,6; `jj`, `jb`: the first pair's directions) forms the group's half sum t and half
+            // difference d of the even parts, relaxes t with the bulk rate sb and d with wp, and finishes all four populations
+            const T feq = wr * (((T(1.0) + t3) + t45) - c15), feqb = wr * (((T(1.0) - t3) + t45) - c15);
+            const T np = T(0.5) * ((f[i] + f[ib]) - (feq + feqb));
+            const T nm = T(0.5) * ((f[i] - f[ib]) - (feq - feqb));
+            const T wmn = les_tau * nm;
+            if (i == 1 || i == 5) { mrt_np = np; mrt_wmn = wmn; return; }
+            const int jj = i == 2 ? 1 : 5, jb = i == 2 ? 3 : 7;
+            const T tr = T(0.5) * (mrt_np + np), dv = T(0.5) * (mrt_np - np);
+            const T st = frc_hy * tr, wd = tau_inv * dv;
+            const T ep = st + wd, eq = st - wd;
+            f[jj] = (f[jj] - ep) - mrt_wmn;
+            f[jb] = (f[jb] - ep) + mrt_wmn;
+            f[i] = (f[i] - eq) - wmn;
+            f[ib] = (f[ib] - eq) + wmn;
+            return;
+        }
         if constexpr (ar_trt(AR)) {
             // TRT (tests/test_gpu_trt.py trt_collide, operation by operation): the same two feq, then the even (np) and odd (nm)
             // non-equilibrium parts of the pair, relaxed with wp = 1/tau and wm = 1/tau_minus
@@ -626,12 +700,15 @@ __device__ __forceinline__ void bgk_collide(T (&f)[Q], T tau_inv, T les_tau = T(
 }
 
 // The collision of the step kernels: BGK with the global 1/tau, (LES modes) the Smagorinsky rate of each cell, or (TRT modes) 1/tau
-// for the even and trt_wm for the odd part of each pair (contracted: the two folded into trt_wa, trt_wb)
+// for the even and trt_wm for the odd part of each pair (contracted: the two folded into trt_wa, trt_wb), or (MRT modes) TRT's parts with
+// the trace of the even parts relaxed at the bulk rate (KArgs: the TRT slots and frc_gx, frc_gy)
 template <typename T, int AR>
 __device__ __forceinline__ void collide(T (&f)[Q], const KArgs<T>& a) {
     static_assert(!(ar_les(AR) && ar_trt(AR)), "TRT and LES exclude each other");
     static_assert(!(ar_forced(AR) && (ar_les(AR) || ar_trt(AR))), "forcing excludes LES and TRT");
-    if constexpr (ar_forced(AR)) bgk_collide<T, AR>(f, a.tau_inv, a.frc_gx, a.frc_gy, a.frc_hx, a.frc_hy);
+    static_assert(!(ar_mrt(AR) && (ar_les(AR) || ar_trt(AR) || ar_forced(AR))), "MRT excludes LES, TRT and forcing");
+    if constexpr (ar_mrt(AR)) bgk_collide<T, AR>(f, a.tau_inv, a.trt_wm, a.trt_wa, a.trt_wb, a.frc_gx, a.frc_gy);
+    else if constexpr (ar_forced(AR)) bgk_collide<T, AR>(f, a.tau_inv, a.frc_gx, a.frc_gy, a.frc_hx, a.frc_hy);
     else if constexpr (ar_trt(AR)) bgk_collide<T, AR>(f, a.tau_inv, a.trt_wm, a.trt_wa, a.trt_wb);
     else if constexpr (ar_les(AR)) bgk_collide<T, AR>(f, T(0), a.les_tau, a.les_tau2, a.les_c);
     else bgk_collide<T, AR>(f, a.tau_inv);

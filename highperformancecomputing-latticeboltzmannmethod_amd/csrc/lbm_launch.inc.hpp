@@ -83,9 +83,12 @@ KArgs<T> make_kargs(const lbm_ctx* c, int src, int dst, int t) {
     a.les_tau2 = (T)(c->p.tau * c->p.tau);
     a.les_c = (T)(18.0 * std::sqrt(2.0) * (cs * cs));
     // a TRT context: the rate of the odd parts, 1/tau_minus with (tau - 1/2)(tau_minus - 1/2) = magic, in that slot
-    // (and the two folded rates of the contracted arithmetic in the other two)
-    if (c->collision == AR_STRICT_TRT) {
-        const double wp = 1.0 / c->p.tau, wm = 1.0 / (0.5 + c->collision_param / (c->p.tau - 0.5));
+    // (and the two folded rates of the contracted arithmetic in the other two). An MRT context (never TRT or forced as well): the same
+    // three from its magic parameter, collision_param2; its bulk rate sb = collision_param and the folded (sb - wp)/(4 wp) of the contracted
+    // arithmetic take the first two slots of the forcing block (below, behind fill_forcing)
+    if (c->collision == AR_STRICT_TRT || c->collision == AR_STRICT_MRT) {
+        const double magic = c->collision == AR_STRICT_MRT ? c->collision_param2 : c->collision_param;
+        const double wp = 1.0 / c->p.tau, wm = 1.0 / (0.5 + magic / (c->p.tau - 0.5));
         a.trt_wm = (T)wm;
         a.trt_wa = (T)(0.5 * (wp + wm));
         a.trt_wb = (T)(0.5 * (wp - wm));
@@ -93,6 +96,10 @@ KArgs<T> make_kargs(const lbm_ctx* c, int src, int dst, int t) {
     fill_walls<T>(c, a);
     a.sched = static_cast<const int*>(c->d_sched);
     fill_forcing<T>(c, a);
+    if (c->collision == AR_STRICT_MRT) {
+        a.frc_gx = (T)c->collision_param;
+        a.frc_gy = (T)(0.25 * (c->collision_param * c->p.tau - 1.0));
+    }
     return a;
 }
 

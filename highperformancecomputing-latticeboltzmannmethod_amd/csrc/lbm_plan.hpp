@@ -31,15 +31,23 @@ constexpr bool PARK_LES = true, PARK_TRT = true;
 // per SIMD like BGK's 120 (profiles/forcing/README.md). Like LES and TRT it has no tall fp32 regions: their
 // two objects are BGK's alone (lbm_col.hip -DLBM_COL_TALL), so no forced instantiation of them exists to meet the bar.
 constexpr bool PARK_FORCED = true;
+// The MRT collision (lbm_set_mrt): its contracted kernels take all 128 VGPRs on the 64x32 regions of fp64 (no scratch, BGK's four waves
+// per SIMD); on the tall fp64 regions they spilled 7 to 9 VGPRs into 24 bytes of scratch per lane when they were built, so the row
+// withholds them (profiles/mrt/README.md). No tall fp32 regions, like every model but BGK.
+constexpr bool PARK_MRT = false;
 // `nparam`: the doubles of the model's parameter (the force has two components; lbm_ctx::collision_param, collision_param2). A model whose
 // ckpt_bit lies above the bits of the walls and the inlet schedule stands behind them in a checkpoint, as its bit says
 // (lbm_ckpt.hpp makes one row of its field table from each model that has a bit).
-struct CollisionModel { int base; const char* noun; bool tall, park; unsigned long long ckpt_bit; const char *param, *value, *none; int nparam = 1; };
+// `unit`: the base of the model in whose objects the model's kernels are instantiated (build.py builds one set of objects per unit;
+// lbm_step_k.hip and lbm_col.hip instantiate a unit's riders beside it); -1: its own. MRT shares TRT's pair code and rides in TRT's objects.
+struct CollisionModel { int base; const char* noun; bool tall, park; unsigned long long ckpt_bit; const char *param, *value, *none; int nparam = 1; int unit = -1; };
 constexpr CollisionModel collision_models[] = {
     {AR_STRICT, "BGK", true, true, 0, "", "", ""},
     {AR_STRICT_LES, "Smagorinsky (LES)", false, PARK_LES, 4, "Smagorinsky constant", "Cs = ", " (BGK)"},
     {AR_STRICT_TRT, "two-relaxation-time (TRT)", false, PARK_TRT, 8, "TRT magic parameter", "", ""},
     {AR_STRICT_FORCED, "forced BGK (Guo forcing)", false, PARK_FORCED, 64, "forcing", "F = ", "", 2},
+    {.base = AR_STRICT_MRT, .noun = "multiple-relaxation-time (MRT)", .tall = false, .park = PARK_MRT, .ckpt_bit = 1024, .param = "MRT parameters",
+     .value = "(bulk rate, magic) = ", .none = "", .nparam = 2, .unit = AR_STRICT_TRT},
 };
 // the row of an Arith value, strict or contracted
 constexpr const CollisionModel& collision_model(int arith) {
@@ -235,7 +243,7 @@ inline std::vector<Plan> plan_candidates(const PlanQuery& q, const Plan& fixed) 
 }
 
 // the dominant kernel of a plan, as rocprofv3 names it (minus "lbmk::" and blanks)
-// (arith: the kernels' Arith value, 0..5, 8, 9; the region shapes follow its strict / contracted half; the store policy is the row's)
+// (arith: the kernels' Arith value, 0..5, 8, 9, 16, 17; the region shapes follow its strict / contracted half; the store policy is the row's)
 inline std::string plan_kernel_name(int fuse, int deep, int pair_ty, int nt, int arith, int esize) {
     char name[96];
     const char* t = esize == 4 ? "float" : "double";

@@ -4,7 +4,7 @@
 #include "lbm_launch_k.hpp"
 
 #ifndef LBM_AR_BASE
-#error "compile with -DLBM_AR_BASE=<Arith base of a collision model: 0, 2, 4 or 8>"
+#error "compile with -DLBM_AR_BASE=<Arith base of a collision model that has objects of its own: 0, 2, 4 or 8>"
 #endif
 
 namespace lbmk {
@@ -58,12 +58,17 @@ void launch_tile(const KArgs<T>& a, const K2Extra<T>& e, int depth, int ty, bool
 #undef LBM_KT
 }
 
-#define LBM_STEP_K_INST(T_) \
-    template void launch_site<T_, LBM_AR_BASE>(const KArgs<T_>&, int, bool, bool, hipStream_t); \
-    template bool launch_deep<T_, LBM_AR_BASE>(const KArgs<T_>&, const K2Extra<T_>&, int, bool, hipStream_t); \
-    template void launch_tile<T_, LBM_AR_BASE>(const KArgs<T_>&, const K2Extra<T_>&, int, int, bool, hipStream_t);
-LBM_STEP_K_INST(double)
-LBM_STEP_K_INST(float)
+#define LBM_STEP_K_INST(T_, ARB_) \
+    template void launch_site<T_, ARB_>(const KArgs<T_>&, int, bool, bool, hipStream_t); \
+    template bool launch_deep<T_, ARB_>(const KArgs<T_>&, const K2Extra<T_>&, int, bool, hipStream_t); \
+    template void launch_tile<T_, ARB_>(const KArgs<T_>&, const K2Extra<T_>&, int, int, bool, hipStream_t);
+LBM_STEP_K_INST(double, LBM_AR_BASE)
+LBM_STEP_K_INST(float, LBM_AR_BASE)
+#if LBM_AR_BASE == 4      // TRT's objects hold the model that rides with it (collision_models: unit), MRT
+static_assert(LBM_AR_BASE == AR_STRICT_TRT && collision_model(AR_STRICT_MRT).unit == AR_STRICT_TRT);
+LBM_STEP_K_INST(double, AR_STRICT_MRT)
+LBM_STEP_K_INST(float, AR_STRICT_MRT)
+#endif
 #undef LBM_STEP_K_INST
 
 }  // namespace lbmk

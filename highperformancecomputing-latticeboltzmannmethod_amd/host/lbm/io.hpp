@@ -322,6 +322,10 @@ private:
             f.put("forcing_x,"); f.put(SimulationParams::shortest_text(p.forcing_x).c_str()); f.put("\n");
             f.put("forcing_y,"); f.put(SimulationParams::shortest_text(p.forcing_y).c_str()); f.put("\n");
         }
+        if (p.mrt()) {                                                                                     // (MRT runs only, likewise)
+            f.put("mrt_bulk_rate,"); f.put(SimulationParams::shortest_text(p.mrt_bulk_rate).c_str()); f.put("\n");
+            f.put("mrt_magic,"); f.put(SimulationParams::shortest_text(p.mrt_magic).c_str()); f.put("\n");
+        }
         if (p.periodic_y) f.put("periodic_y,1\n");                                                          // (periodic runs only; behind every other line)
         std::printf("  simulation_params.csv written\n");
     }

@@ -64,6 +64,10 @@ struct SimulationParams {
     // Uniform driving force (lbm_solver --forcing FX,FY; not in the reference): a constant force density in lattice units on every
     // fluid cell, Guo's scheme on the BGK collision (lbm_set_forcing). (0, 0) = none. Never together with smagorinsky_cs or trt_magic.
     double forcing_x = 0.0, forcing_y = 0.0;
+    // Multiple-relaxation-time collision (lbm_solver --mrt BULK,MAGIC; not in the reference): TRT with the magic parameter MAGIC whose
+    // bulk rate BULK, in (0, 2), is free of tau (lbm_set_mrt). Bulk rate 0 = plain BGK. Never together with smagorinsky_cs, trt_magic
+    // or a force. tau keeps setting the shear viscosity.
+    double mrt_bulk_rate = 0.0, mrt_magic = 0.0;
     // time-averaged statistics (lbm_solver --stats-start; not in the reference): the first step sampled, -1 = off. Samples are taken on
     // the device at the output_frequency cadence (lbm_stats_begin); the run ends with mean_fields.vtk / mean_fields.csv.
     int stats_start = -1;
@@ -100,6 +104,7 @@ struct SimulationParams {
     bool les() const { return smagorinsky_cs > 0.0; }
     bool trt() const { return trt_magic > 0.0; }
     bool forced() const { return forcing_x != 0.0 || forcing_y != 0.0; }
+    bool mrt() const { return mrt_bulk_rate != 0.0; }
     bool stats() const { return stats_start >= 0; }
     bool frames() const { return frame_stride > 0; }
     bool probes() const { return !probe_xy.empty(); }
@@ -135,6 +140,26 @@ struct SimulationParams {
             if (!std::isfinite(v[k]) || std::fabs(v[k]) >= 1.0) throw bad("has a component that is not finite or not below 1 in magnitude");
         }
         forcing_x = v[0]; forcing_y = v[1];
+    }
+    // BULK,MAGIC of --mrt: one token, two numbers each parsed whole, BULK 0 or in (0, 2), MAGIC in (0, 1] beside a nonzero BULK
+    // (std::invalid_argument with the one-line message otherwise)
+    void set_mrt(const std::string& text) {
+        const auto bad = [&](const char* why) {
+            return std::invalid_argument("--mrt: '" + text + "' " + why + " (BULK,MAGIC: the bulk rate, 0 or in (0, 2), and the magic parameter in (0, 1])");
+        };
+        const size_t comma = text.find(',');
+        if (comma == std::string::npos || text.find(',', comma + 1) != std::string::npos) throw bad("is not a pair BULK,MAGIC");
+        const std::string part[2] = {text.substr(0, comma), text.substr(comma + 1)};
+        double v[2];
+        for (int k = 0; k < 2; ++k) {
+            char* end = nullptr;
+            v[k] = std::strtod(part[k].c_str(), &end);
+            if (part[k].empty() || std::isspace((unsigned char)part[k][0]) || end == part[k].c_str() || *end != '\0') throw bad(k ? "has no number MAGIC" : "has no number BULK");
+            if (!std::isfinite(v[k])) throw bad("has a number that is not finite");
+        }
+        if (v[0] < 0.0 || v[0] >= 2.0) throw bad("has a bulk rate outside (0, 2)");
+        if (v[0] != 0.0 && (!(v[1] > 0.0) || v[1] > 1.0)) throw bad("has a magic parameter outside (0, 1]");
+        mrt_bulk_rate = v[0]; mrt_magic = v[0] != 0.0 ? v[1] : 0.0;
     }
     // a wall as the command line names it: "no-slip", "free-slip" or "moving:U"
     std::string wall_text(int side) const {

@@ -55,6 +55,9 @@ public:
         if (!opt_.quiet && params_.forced())
             std::printf("  driving force (Guo): Fx = %s, Fy = %s\n", SimulationParams::shortest_text(params_.forcing_x).c_str(),
                         SimulationParams::shortest_text(params_.forcing_y).c_str());
+        if (!opt_.quiet && params_.mrt())
+            std::printf("  Collision: MRT collision, bulk rate = %s, magic = %s (the trace of the stress relaxes with the bulk rate; tau sets the shear viscosity)\n",
+                        SimulationParams::shortest_text(params_.mrt_bulk_rate).c_str(), SimulationParams::shortest_text(params_.mrt_magic).c_str());
         if (!opt_.quiet && params_.walled())
             std::printf("  Walls: south %s, north %s\n", params_.wall_banner(0).c_str(), params_.wall_banner(1).c_str());
         if (!opt_.quiet && params_.ported())

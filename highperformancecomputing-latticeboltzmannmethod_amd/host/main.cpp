@@ -23,7 +23,7 @@ static void usage() {
               "           [--gpus N] [--strips N] [--rccl]\n"
               "           [--checkpoint FILE] [--restart FILE] [--obstacle-mask FILE.pgm] [--obstacle-bodies FILE.pgm]\n"
               "           [--inlet-profile parabolic|FILE] [--print-inlet-profile] [--smagorinsky CS] [--trt-magic LAMBDA]\n"
-              "           [--forcing FX,FY]\n"
+              "           [--forcing FX,FY] [--mrt BULK,MAGIC]\n"
               "           [--stats-start N] [--wall-south KIND] [--wall-north KIND] [--walls KIND]\n"
               "           [--inlet velocity|pressure:RHO] [--outlet pressure:RHO|velocity:U]\n"
               "           [--frame-stride K] [--probes FILE] [--probe-line x0 y0 x1 y1 n]\n"
@@ -63,6 +63,11 @@ static void usage() {
               "force. Guo's scheme on the BGK collision: the velocity of the equilibrium and of every output is (sum c f + F/2) / rho.\n"
               "A channel of H rows between the walls carries the parabola of peak u_max under FX = 8 nu u_max / H^2. The inlet, the outlet\n"
               "and the walls do not know about the force. Cannot be combined with --smagorinsky or --trt-magic.\n"
+              "--mrt BULK,MAGIC: multiple-relaxation-time (MRT) collision (one token): TRT with magic parameter MAGIC in (0, 1] whose bulk\n"
+              "rate BULK in (0, 2) is free of tau. The trace of the stress (the energy moments) relaxes with BULK, so the bulk viscosity\n"
+              "grows with 1/BULK - 1/2 and pressure waves of an impulsive start die out; the shear viscosity stays (tau - 0.5) / 3.\n"
+              "BULK = 1/tau is --trt-magic MAGIC; BULK 0: plain BGK. Needs tau > 0.5; cannot be combined with --smagorinsky, --trt-magic\n"
+              "or --forcing.\n"
               "--wall-south KIND / --wall-north KIND: the bottom (row 0) / top (row ny-1) wall, KIND = no-slip (the default: on-node\n"
               "bounce-back) | free-slip (specular reflection: no boundary layer, for unconfined flow past a body) | moving:U (a wall\n"
               "sliding at the tangential velocity U, |U| < 1: Couette flow, a lid, a moving ground). --walls KIND sets both. The\n"
@@ -105,6 +110,7 @@ int main(int argc, char** argv) {
     const char* smagorinsky = nullptr;
     const char* trt_magic = nullptr;
     const char* forcing = nullptr;
+    const char* mrt = nullptr;
     const char* stats_start = nullptr;
     const char* frame_stride = nullptr;
     std::vector<LBM::ProbePoint> probe_points;
@@ -147,6 +153,7 @@ int main(int argc, char** argv) {
         else if (k == "--smagorinsky") smagorinsky = val();
         else if (k == "--trt-magic") trt_magic = val();
         else if (k == "--forcing") forcing = val();
+        else if (k == "--mrt") mrt = val();
         else if (k == "--stats-start") stats_start = val();
         else if (k == "--periodic-y") params.periodic_y = true;
         else if (k == "--wall-south" || k == "--wall-north" || k == "--walls") {   // checked here: no device is touched before a bad value exits
@@ -238,6 +245,27 @@ int main(int argc, char** argv) {
         }
         if (params.forced() && (params.smagorinsky_cs > 0.0 || params.trt_magic > 0.0)) {
             std::fprintf(stderr, "--forcing cannot be combined with %s (one collision model at a time)\n", params.smagorinsky_cs > 0.0 ? "--smagorinsky" : "--trt-magic");
+            return 2;
+        }
+    }
+    if (mrt) {           // likewise: BULK,MAGIC parsed whole, a tau the rates are defined for, and no second collision model (in the words of
+                         // the library's setters, set_collision in csrc/lbm_hip.hip, which a context would meet after a device is open)
+        try {
+            params.set_mrt(mrt);
+        } catch (const std::exception& e) {
+            std::fprintf(stderr, "%s\n", e.what());
+            return 2;
+        }
+        if (params.mrt() && !(params.tau > 0.5)) {
+            std::fprintf(stderr, "--mrt: tau = %g (the MRT rates need tau > 0.5)\n", params.tau);
+            return 2;
+        }
+        char other[160] = "";
+        if (params.smagorinsky_cs > 0.0) std::snprintf(other, sizeof(other), "Smagorinsky constant Cs = %g", params.smagorinsky_cs);
+        else if (params.trt_magic > 0.0) std::snprintf(other, sizeof(other), "TRT magic parameter %g", params.trt_magic);
+        else if (params.forced()) std::snprintf(other, sizeof(other), "forcing F = (%g, %g)", params.forcing_x, params.forcing_y);
+        if (params.mrt() && other[0]) {
+            std::fprintf(stderr, "--mrt: (bulk rate, magic) = (%g, %g) on a context with %s (the two collisions cannot be combined)\n", params.mrt_bulk_rate, params.mrt_magic, other);
             return 2;
         }
     }

@@ -354,6 +354,37 @@ int  lbm_set_trt(lbm_ctx* c, double magic);
 int  lbm_set_forcing(lbm_ctx* c, double fx, double fy);
 /* The force as set, (0, 0) on a context without one; either pointer may be NULL. LBM_ERR_ARG: null context. */
 int  lbm_get_forcing(const lbm_ctx* c, double* fx, double* fy);
+/* The collision: replaces the BGK operator by a multiple-relaxation-time one (MRT: Lallemand and Luo 2000, d'Humieres 2002) whose bulk
+ * rate `bulk_rate` = sb is free of tau, in the pair form of lbm_set_trt plus that one rate. With feq as BGK forms it, n0 = f0 - feq0 and,
+ * per opposite pair p = (i, ib) of (1,3), (2,4), (5,7), (8,6), TRT's even and odd non-equilibrium parts np_p, nm_p:
+ *     ta = (np_13 + np_24) / 2,  da = (np_13 - np_24) / 2       (axis pairs: trace and deviator)
+ *     td = (np_57 + np_86) / 2,  dd = (np_57 - np_86) / 2       (diagonal pairs)
+ *     f0' = f0 - sb n0
+ *     f1' = f1 - (sb ta + wp da) - wm nm_13,  f3' = f3 - (sb ta + wp da) + wm nm_13
+ *     f2' = f2 - (sb ta - wp da) - wm nm_24,  f4' = f4 - (sb ta - wp da) + wm nm_24
+ *     f5' = f5 - (sb td + wp dd) - wm nm_57,  f7' = f7 - (sb td + wp dd) + wm nm_57
+ *     f8' = f8 - (sb td - wp dd) - wm nm_86,  f6' = f6 - (sb td - wp dd) + wm nm_86
+ *     wp = 1 / tau,  wm = 1 / (1/2 + magic / (tau - 1/2)).
+ * In moment space (rho, e, eps, jx, qx, jy, qy, pxx, pxy) this is the Lallemand-Luo operator with the rates (0, sb, sb, 0, wm, 0, wm, wp,
+ * wp): the shear viscosity stays (tau - 1/2) / 3, the bulk viscosity grows with 1/sb - 1/2, and mass and momentum are conserved, so the
+ * snapshot (lbm_get_macros, statistics, frames, probes) needs no correction. sb = 1/tau is TRT with the same magic up to rounding, and
+ * magic = (tau - 1/2)^2 besides is BGK up to rounding. The host forms sb, wp, wm in double and casts each once to the element type.
+ * Strict arithmetic (option arith=0) evaluates, one IEEE operation at a time with no contraction: rho, ux, uy and the feq_i as BGK forms
+ * them; f0' = f0 - sb (f0 - feq0); per pair np = 0.5 ((f_i + f_ib) - (feq_i + feq_ib)), nm = 0.5 ((f_i - f_ib) - (feq_i - feq_ib)),
+ * o = wm nm; per group (p, q) of pairs, (13, 24) and (57, 86): t = 0.5 (np_p + np_q), d = 0.5 (np_p - np_q), a = sb t, b = wp d,
+ * e_p = a + b, e_q = a - b; then f_i' = (f_i - e_p) - o_p, f_ib' = (f_ib - e_p) + o_p for pair p and the same with e_q, o_q for pair q.
+ * Contracted arithmetic (arith=1) is TRT's FMA chain on an equilibrium whose velocity-free term is shifted, for the axis pairs and for the diagonal pairs, so that each population takes (sb - wp)/4 times the sum of its group's residuals. About a
+ * dozen operations per cell more than TRT, no extra memory traffic. Every strip of a run is given the same pair.
+ * Call after lbm_create and before lbm_initialise, like lbm_set_trt: the plan is then measured on the MRT kernels (Arith values 16 / 17;
+ * no fp32 deep=8 plan: pinning it fails). bulk_rate == 0 clears the model: the BGK kernels, and every result, kernel name and checkpoint
+ * byte as without the call (magic is then ignored, if finite). Checkpoints carry the pair (lbm_save_state: magic word "LBMCKPT3", flag
+ * bit 10) and load only into a context with an equal one.
+ * LBM_ERR_ARG (the text names the offender): a null context, an initialised context, a value that is not finite, a nonzero bulk_rate
+ * outside (0, 2), magic outside (0, 1] with a nonzero bulk_rate, a context whose tau <= 0.5, or a context with a Smagorinsky constant,
+ * a TRT magic parameter or a force — and any of those setters on a context with MRT: the collisions cannot be combined. */
+int  lbm_set_mrt(lbm_ctx* c, double bulk_rate, double magic);
+/* The pair as set, (0, 0) on a context without MRT; either pointer may be NULL. LBM_ERR_ARG: null context. */
+int  lbm_get_mrt(const lbm_ctx* c, double* bulk_rate, double* magic);
 /* The two walls: generalises the on-node bounce-back of the bottom and top rows (LBMSolver.h:155-176), a stationary no-slip wall, to a
  * KIND and a tangential VELOCITY per wall. The south wall is global row 0, the north wall global row ny - 1. On a fluid cell of the
  * wall's row, after the pull:
@@ -548,7 +579,7 @@ int  lbm_halo_import(lbm_ctx* c, const double* south_in, const double* north_in)
 /* Checkpoint / restart (the reference has none): the strip's post-collision populations and the
  * iteration counter. lbm_load_state needs an initialised context created with the same parameters; the macro /
  * population snapshots become available again after the next lbm_step. A file written with an obstacle mask, an inlet
- * profile, a Smagorinsky constant, a TRT magic parameter, a force (lbm_set_forcing), a wall that is not no-slip (lbm_set_wall), an
+ * profile, a Smagorinsky constant, a TRT magic parameter, a force (lbm_set_forcing), an MRT pair (lbm_set_mrt), a wall that is not no-slip (lbm_set_wall), an
  * inlet schedule (lbm_set_inlet_schedule) or a port off its default (lbm_set_port) loads only into a context with the same mask,
  * profile, constant, parameter, force, walls, schedule and ports (the failure names which one differs). The file format, and the order in which differences are named: the comment at the
  * head of csrc/lbm_ckpt.hpp. */
@@ -689,6 +720,14 @@ int lbm_debug_ring(int capacity, const int* ops, int nops, int* out3);
 /* Test hook, callable without a device: the candidate plans lbm_initialise would time on a whole-domain context of this grid
  * (csrc/lbm_plan.hpp), one per line: "name|lbm_set_option pairs|dominant kernel|iterations per launch". */
 int lbm_debug_plan_candidates(int nx, int ny, int precision, int arith, int num_cus, char* out, int cap);
+/* Test hook, callable without a device: the setters of the collision models on a context that is never initialised on a device (64 x 64
+ * cells, the given tau and precision, `options` = "key=value ..." as for lbm_set_option applied first). Call k is setter[k] with
+ * (v1[k], v2[k]): 0 lbm_set_smagorinsky(v1), 1 lbm_set_trt(v1), 2 lbm_set_forcing(v1, v2), 3 lbm_set_mrt(v1, v2), 4 marks the context
+ * initialised (as lbm_initialise leaves it), 5 lbm_initialise's refusal of a pinned deep shape. rc[k] receives each return value, `texts`
+ * one line per call: the error text of a failed call, empty for LBM_OK. collision3 receives {lbm_ctx::collision, and what lbm_get_mrt
+ * reports}. LBM_ERR_ARG: a null pointer, an unknown setter, a bad option, a buffer too small. */
+int lbm_debug_collision_setters(double tau, int precision, const char* options, const int* setter, const double* v1, const double* v2, int n,
+                                int* rc, char* texts, int cap, double* collision3);
 /* Test hook, callable without a device: the table behind option "deep" (csrc/lbm_plan.hpp deep_shapes, region_kinds), one line per id,
  * precision and arithmetic mode that exists: "id|f64 or f32|strict or contracted|lds or registers|iterations per launch|width|height of
  * the tile or region|rows per thread|waves|offered depths|restrictions". An offered depth of a register shape reads
