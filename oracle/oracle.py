@@ -107,6 +107,7 @@ class Oracle:
             pass
 
     # phases
+    def initialise(self): self.L.lbmo_initialise(self.h)       # (again: after a write to `solid`)
     def collide(self): self.L.lbmo_collide(self.h)
     def exchange_physical(self): self.L.lbmo_exchange_physical(self.h)
     def stream(self): self.L.lbmo_stream(self.h)

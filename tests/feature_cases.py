@@ -145,6 +145,12 @@ def reference_of(case):
     return read_only(oracle_run(case.nx, case.ny, steps_of(case), case.of, **physics_kw(case)))
 
 
+@functools.lru_cache(maxsize=None)
+def reference32_of(case):
+    """reference_of in float32 (tests/numpy_oracle.py): what an fp32 context in strict arithmetic must equal bit for bit."""
+    return read_only(oracle_run(case.nx, case.ny, steps_of(case), case.of, dtype=np.float32, **physics_kw(case)))
+
+
 def _wall(rng):
     kind = int(rng.integers(0, 3))
     u_w = round(float(rng.uniform(-0.06, 0.06)), 4)

@@ -16,7 +16,9 @@ def forcing_constants(tau, force):
 
 def guo_source(r, ux, uy, gx, gy):
     """The nine source terms S_i = w_i ((3 cg - u3) + (9 cu) cg), u3 = 3 (ux gx + uy gy), with cu and cg per opposite pair; the
-    opposite direction negates 3 cg and keeps the product."""
+    opposite direction negates 3 cg and keeps the product. gx, gy: the host's doubles, cast once to the cells' element type, in which
+    gx + gy and gx - gy of the diagonal pairs are formed (lbm_kernels.hpp bgk_collide, the ar_forced phase: both are T there)."""
+    gx, gy = r.dtype.type(gx), r.dtype.type(gy)
     u3 = 3.0 * (ux * gx + uy * gy)
     s = [None] * 9
     s[0] = W[0] * (0.0 - u3)

@@ -7,10 +7,9 @@ import functools
 
 import numpy as np
 
-from oracle.oracle import Oracle, make_params
 from tests.ports_reference import DEFAULT_PORTS, VELOCITY, port_of, port_rule
 from tests.ports_reference import boundaries as walled_boundaries
-from tests.reference import CX, CY, HOLD, NOSLIP, OPP, Run, feq_rows, link_forces, sched_index
+from tests.reference import CX, CY, NOSLIP, OPP, close_run, link_forces, open_run
 
 
 def periodic_boundaries(o, solid, u, ports):
@@ -42,33 +41,19 @@ def periodic_link_forces(f_next, solid):
         xs, xd = (slice(CX[i], None), slice(0, nx - CX[i])) if CX[i] >= 0 else (slice(0, nx + CX[i]), slice(-CX[i], None))
         nb[:, xd] = rolled[:, xs]
         sel = nb & ~solid
-        s = float(np.sum(f[..., i][sel]))
+        s = float(np.sum(f[..., i][sel].astype(np.float64)))      # (k_forces widens each population and sums in double)
         fx += 2.0 * CX[i] * s
         fy += 2.0 * CY[i] * s
     return fx, fy
 
 
 def periodic_run(nx, ny, steps, of, *, periodic=True, ports=DEFAULT_PORTS, mask=None, u=None, walls=(NOSLIP, NOSLIP), schedule=None,
-                 collide=None, keep_f_current=False, **params):
+                 collide=None, keep_f_current=False, dtype=np.float64, backend=None, **params):
     """oracle_run (ports_run) on a lattice that is periodic in y; the keywords are theirs. `walls` counts with periodic=False only."""
     if isinstance(walls, str):
         walls = (walls, walls)
     ports = (port_of(ports[0], DEFAULT_PORTS[0]), port_of(ports[1], DEFAULT_PORTS[1]))
-    o = Oracle(make_params(nx, ny, **params))
-    if mask is not None:
-        o.solid[:] = mask
-    o.L.lbmo_initialise(o.h)
-    solid = o.solid.astype(bool).copy()
-    fluid = ~solid
-    u_rows = np.full(ny, o.p.inlet_velocity, dtype=np.float64) if u is None else np.asarray(u, dtype=np.float64)
-    s, mode = (None, HOLD) if schedule is None else (np.asarray(schedule[0], dtype=np.float64), schedule[1])
-    if u is not None or s is not None:
-        u0 = u_rows if s is None else u_rows * s[0]
-        fr = feq_rows(u0)
-        for arr in (o.f_current, o.f_next):
-            inner = arr[1:-1, 1:-1]
-            inner[fluid] = np.broadcast_to(fr[:, None, :], (ny, nx, 9))[fluid]
-        o.ux[fluid] = np.broadcast_to(u0[:, None], (ny, nx))[fluid]
+    o, solid, u_at = open_run(nx, ny, dtype, backend, mask, u, schedule, **params)
     tau = o.p.tau
     forces, bad, tmax = [], -1, None
     for t in range(steps):
@@ -83,7 +68,7 @@ def periodic_run(nx, ny, steps, of, *, periodic=True, ports=DEFAULT_PORTS, mask=
                 o.set_ghost_row(0, o.edge_row(1))
                 o.set_ghost_row(1, o.edge_row(0))
             o.stream()
-            u_t = u_rows if s is None else u_rows * s[sched_index(t, len(s), mode)]
+            u_t = u_at(t)
             if periodic:
                 periodic_boundaries(o, solid, u_t, ports)
             else:
@@ -91,10 +76,7 @@ def periodic_run(nx, ny, steps, of, *, periodic=True, ports=DEFAULT_PORTS, mask=
         if not o.stable():
             bad = t
             break
-    out = Run(o.f_next.copy(), o.rho.copy(), o.ux.copy(), o.uy.copy(), forces, bad, o.solid_count(), tmax)
-    fcur = o.f_current.copy()
-    o.close()
-    return (out, fcur) if keep_f_current else out
+    return close_run(o, solid, forces, bad, tmax, collide, keep_f_current)
 
 
 # ---- the inputs of the periodic tests: 200x72, tau 0.6, 60 iterations ----------------------------------------------------------------

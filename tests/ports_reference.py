@@ -4,8 +4,7 @@ around it. numpy, fp64, IEEE, one operation per operation of the table in the or
 With the default ports it is oracle_run to the bit (tests/test_ports_cpu.py)."""
 import numpy as np
 
-from oracle.oracle import Oracle, make_params
-from tests.reference import HOLD, NOSLIP, OPP, Run, feq_rows, link_forces, sched_index, wall_kind_k, wall_rule
+from tests.reference import NOSLIP, OPP, close_run, link_forces, open_run, wall_kind_k, wall_rule
 
 VELOCITY, PRESSURE = "velocity", "pressure"
 DEFAULT_PORTS = (VELOCITY, (PRESSURE, 1.0))
@@ -44,6 +43,7 @@ def port_rule(f, side, kind, given):
         f[:, 3] = f[:, 1] - (2.0 / 3.0) * rho * u
         f[:, 6] = f[:, 8] - 0.5 * (f[:, 2] - f[:, 4]) - (1.0 / 6.0) * rho * u
         f[:, 7] = f[:, 5] + 0.5 * (f[:, 2] - f[:, 4]) - (1.0 / 6.0) * rho * u
+    assert rho.dtype == u.dtype == f.dtype, "the port rule left " + str(f.dtype)      # (the caller's assignments would cast silently)
     return rho, u
 
 
@@ -70,27 +70,13 @@ def boundaries(o, solid, walls, u, ports):
 
 
 def ports_run(nx, ny, steps, of, *, ports=DEFAULT_PORTS, mask=None, u=None, walls=(NOSLIP, NOSLIP), schedule=None, collide=None,
-              keep_f_current=False, **params):
+              keep_f_current=False, dtype=np.float64, backend=None, **params):
     """tests/reference.py oracle_run with ports = (west, east): west "velocity" or ("pressure", rho), east ("pressure", rho) or
     ("velocity", u), None in either place the default. The initial state stays oracle_run's. Returns a Run."""
     if isinstance(walls, str):
         walls = (walls, walls)
     ports = (port_of(ports[0], DEFAULT_PORTS[0]), port_of(ports[1], DEFAULT_PORTS[1]))
-    o = Oracle(make_params(nx, ny, **params))
-    if mask is not None:
-        o.solid[:] = mask
-    o.L.lbmo_initialise(o.h)
-    solid = o.solid.astype(bool).copy()
-    fluid = ~solid
-    u_rows = np.full(ny, o.p.inlet_velocity, dtype=np.float64) if u is None else np.asarray(u, dtype=np.float64)
-    s, mode = (None, HOLD) if schedule is None else (np.asarray(schedule[0], dtype=np.float64), schedule[1])
-    if u is not None or s is not None:
-        u0 = u_rows if s is None else u_rows * s[0]
-        fr = feq_rows(u0)
-        for arr in (o.f_current, o.f_next):
-            inner = arr[1:-1, 1:-1]
-            inner[fluid] = np.broadcast_to(fr[:, None, :], (ny, nx, 9))[fluid]
-        o.ux[fluid] = np.broadcast_to(u0[:, None], (ny, nx))[fluid]
+    o, solid, u_at = open_run(nx, ny, dtype, backend, mask, u, schedule, **params)
     tau = o.p.tau
     forces, bad, tmax = [], -1, None
     for t in range(steps):
@@ -102,14 +88,11 @@ def ports_run(nx, ny, steps, of, *, ports=DEFAULT_PORTS, mask=None, u=None, wall
                 forces.append((t,) + link_forces(o.f_next, solid))
             o.exchange_physical()
             o.stream()
-            boundaries(o, solid, walls, u_rows if s is None else u_rows * s[sched_index(t, len(s), mode)], ports)
+            boundaries(o, solid, walls, u_at(t), ports)
         if not o.stable():
             bad = t
             break
-    out = Run(o.f_next.copy(), o.rho.copy(), o.ux.copy(), o.uy.copy(), forces, bad, o.solid_count(), tmax)
-    fcur = o.f_current.copy()
-    o.close()
-    return (out, fcur) if keep_f_current else out
+    return close_run(o, solid, forces, bad, tmax, collide, keep_f_current)
 
 
 # ---- the pressure-driven channel of the physics checks (tests/test_ports_cpu.py, tests/test_gpu_ports.py) -----------------------------

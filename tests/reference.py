@@ -3,14 +3,22 @@
 The C oracle's arrays are writable views, so its loop taken step by step, with a numpy collision operator in place of o.collide()
 and a numpy restatement of ALL of lbmo_boundaries (oracle/lbm_oracle.c) in place of o.boundaries(), is the reference of every feature
 the oracle itself does not have: obstacle masks, inlet profiles and schedules, the wall kinds, the collision operators, and any
-combination of them. Everything here is fp64, IEEE, in the operation order the library's strict arithmetic evaluates: strict plans
-must match it bit for bit. tests/test_reference_cpu.py pins the loop and the shared pieces to the unmodified oracle."""
+combination of them. Everything here is IEEE, in the operation order the library's strict arithmetic evaluates: strict plans must
+match it bit for bit. tests/test_reference_cpu.py pins the loop and the shared pieces to the unmodified oracle.
+
+dtype=np.float64 (the default) runs on the C oracle. dtype=np.float32 runs the same loop on tests/numpy_oracle.py NumpyOracle, whose
+arrays are float32: every operation below is then one IEEE float32 operation, a Python float that meets an array is rounded to float32
+first (the library's T(constant), or its host value formed in double and cast once), and what the library forms in the element type
+on the device (the inlet velocity of a row times the schedule's factor, g_x + g_y of the driving force) is formed from float32 values
+here. The strict fp32 plans must match such a run bit for bit (tests/test_gpu_f32_oracle.py); tests/test_f32_reference_cpu.py pins
+NumpyOracle in float64 to the C oracle."""
 import collections
 import math
 
 import numpy as np
 
 from oracle.oracle import Oracle, make_params
+from tests.numpy_oracle import NumpyOracle
 
 CX = [0, 1, 0, -1, 0, 1, -1, -1, 1]
 CY = [0, 0, 1, 0, -1, 1, 1, -1, -1]
@@ -39,7 +47,9 @@ def feq(i, r, vx, vy, usq):
 
 
 def write_back(o, fluid, out, r, vx, vy):
-    """f_next on the interior's fluid cells, and rho / ux / uy recorded as the oracle does."""
+    """f_next on the interior's fluid cells, and rho / ux / uy recorded as the oracle does. (An assignment into the oracle's arrays
+    would cast silently: an operator that left the oracle's element type on the way is stopped here.)"""
+    assert all(v.dtype == o.f_next.dtype for v in list(out) + [r, vx, vy]), "the collision operator left " + str(o.f_next.dtype)
     inner = o.f_next[1:-1, 1:-1]
     for i in range(9):
         col = inner[:, :, i]
@@ -116,7 +126,7 @@ def link_forces(f_next, solid):
         xs, xd = (slice(CX[i], None), slice(0, nx - CX[i])) if CX[i] >= 0 else (slice(0, nx + CX[i]), slice(-CX[i], None))
         nb[yd, xd] = solid[ys, xs]
         sel = nb & ~solid
-        s = float(np.sum(f[..., i][sel]))
+        s = float(np.sum(f[..., i][sel].astype(np.float64)))      # (k_forces widens each population and sums in double)
         fx += 2.0 * CX[i] * s
         fy += 2.0 * CY[i] * s
     return fx, fy
@@ -191,6 +201,7 @@ def boundaries(o, solid, walls, u):
     f[:, 5] = f[:, 7] - 0.5 * (f[:, 2] - f[:, 4]) + (1.0 / 6.0) * rho_bc * ur
     f[:, 8] = f[:, 6] + 0.5 * (f[:, 2] - f[:, 4]) + (1.0 / 6.0) * rho_bc * ur
     fc[rows + 1, 1, :] = f
+    assert rho_bc.dtype == ur.dtype == fc.dtype, "the inlet left " + str(fc.dtype)      # (the assignments would cast silently)
     o.rho[rows, 0] = rho_bc; o.ux[rows, 0] = ur; o.uy[rows, 0] = 0.0
     # outlet: fluid cells of column nx - 1, Zou-He pressure with rho = 1
     rows = np.nonzero(fluid[:, nx - 1])[0]
@@ -209,23 +220,22 @@ def boundaries(o, solid, walls, u):
 
 
 # ---- the loop -------------------------------------------------------------------------------------------------------------------
-Run = collections.namedtuple("Run", "f_next rho ux uy forces first_unstable solid_count tau_max")
+Run = collections.namedtuple("Run", "f_next rho ux uy forces first_unstable solid_count tau_max solid forced", defaults=(None, None))
 
 
-def oracle_run(nx, ny, steps, of, *, mask=None, u=None, walls=(NOSLIP, NOSLIP), schedule=None, collide=None, keep_f_current=False,
-               **params):
-    """The stepwise oracle: on `mask` (None: the analytic disc of `params`); with the inlet of row y at iteration t at u[y] (None: the
-    uniform inlet_velocity of `params`) times, under schedule = (s, HOLD or REPEAT), s[sched_index(t)] — one IEEE multiplication in
-    double, formed before `boundaries` uses it; between walls = (south, north), each "no-slip", "free-slip" or ("moving", u_w), one
-    string meaning both; and with collide(o, tau) in place of its own o.collide() (None: plain BGK). forces are [(t, fx, fy)] by
-    link_forces; tau_max is the largest value the operator returned, None if it returns none. Returns a Run (and, with
-    keep_f_current, f_current beside it)."""
-    if isinstance(walls, str):
-        walls = (walls, walls)
-    o = Oracle(make_params(nx, ny, **params))
+def open_run(nx, ny, dtype, backend, mask, u, schedule, **params):
+    """What the reference loops (oracle_run, ports_run, periodic_run) share in front of their iterations: the oracle on `mask` in its
+    initial state, and the inlet. Returns (o, solid, u_at): o the C oracle (dtype float64) or a NumpyOracle (any other dtype; backend
+    "numpy": float64 too); u_at(t) the inlet velocity of every row at iteration t, in dtype.
+    As the library forms them: the profile and the schedule's factors are each cast to dtype (upload_rows, upload_schedule) and their
+    product is ONE multiplication in dtype (lbm_kernels.hpp bcs_at_with, macro_cell); the initial state under a profile or a schedule
+    is f_eq(1, (u[y] * s[0], 0)) with the product and the equilibrium formed in double and cast once (prepare_schedule, upload_feqrow)."""
+    dtype = np.dtype(dtype)
+    p = make_params(nx, ny, **params)
+    o = Oracle(p) if (dtype == np.float64 and backend != "numpy") else NumpyOracle(p, dtype)
     if mask is not None:
         o.solid[:] = mask
-    o.L.lbmo_initialise(o.h)
+    o.initialise()
     solid = o.solid.astype(bool).copy()
     fluid = ~solid
     u_rows = np.full(ny, o.p.inlet_velocity, dtype=np.float64) if u is None else np.asarray(u, dtype=np.float64)
@@ -237,6 +247,34 @@ def oracle_run(nx, ny, steps, of, *, mask=None, u=None, walls=(NOSLIP, NOSLIP), 
             inner = arr[1:-1, 1:-1]
             inner[fluid] = np.broadcast_to(fr[:, None, :], (ny, nx, 9))[fluid]
         o.ux[fluid] = np.broadcast_to(u0[:, None], (ny, nx))[fluid]
+    u_t = u_rows.astype(dtype)
+    s_t = None if s is None else s.astype(dtype)
+
+    def u_at(t):
+        return u_t if s_t is None else u_t * s_t[sched_index(t, len(s_t), mode)]
+    return o, solid, u_at
+
+
+def close_run(o, solid, forces, bad, tmax, collide, keep_f_current):
+    """The Run of a finished loop (and, with keep_f_current, f_current beside it); closes the oracle."""
+    force = getattr(collide, "keywords", {}).get("force")           # (a guo_collide partial: what `snapshot` takes off the momentum)
+    out = Run(o.f_next.copy(), o.rho.copy(), o.ux.copy(), o.uy.copy(), forces, bad, o.solid_count(), tmax, solid, force)
+    fcur = o.f_current.copy()
+    o.close()
+    return (out, fcur) if keep_f_current else out
+
+
+def oracle_run(nx, ny, steps, of, *, mask=None, u=None, walls=(NOSLIP, NOSLIP), schedule=None, collide=None, keep_f_current=False,
+               dtype=np.float64, backend=None, **params):
+    """The stepwise oracle: on `mask` (None: the analytic disc of `params`); with the inlet of row y at iteration t at u[y] (None: the
+    uniform inlet_velocity of `params`) times, under schedule = (s, HOLD or REPEAT), s[sched_index(t)] — one IEEE multiplication in
+    dtype, formed before `boundaries` uses it; between walls = (south, north), each "no-slip", "free-slip" or ("moving", u_w), one
+    string meaning both; and with collide(o, tau) in place of its own o.collide() (None: plain BGK). forces are [(t, fx, fy)] by
+    link_forces; tau_max is the largest value the operator returned, None if it returns none. dtype, backend: see open_run. Returns a
+    Run (and, with keep_f_current, f_current beside it)."""
+    if isinstance(walls, str):
+        walls = (walls, walls)
+    o, solid, u_at = open_run(nx, ny, dtype, backend, mask, u, schedule, **params)
     tau = o.p.tau
     forces, bad, tmax = [], -1, None
     for t in range(steps):
@@ -248,13 +286,40 @@ def oracle_run(nx, ny, steps, of, *, mask=None, u=None, walls=(NOSLIP, NOSLIP), 
                 forces.append((t,) + link_forces(o.f_next, solid))
             o.exchange_physical()
             o.stream()
-            boundaries(o, solid, walls, u_rows if s is None else u_rows * s[sched_index(t, len(s), mode)])
+            boundaries(o, solid, walls, u_at(t))
         if not o.stable():
             bad = t
             break
-    out = Run(o.f_next.copy(), o.rho.copy(), o.ux.copy(), o.uy.copy(), forces, bad, o.solid_count(), tmax)
-    fcur = o.f_current.copy()
-    o.close()
-    return (out, fcur) if keep_f_current else out
+    return close_run(o, solid, forces, bad, tmax, collide, keep_f_current)
 
 
+# ---- the macro snapshot ----------------------------------------------------------------------------------------------------------
+def snapshot(run):
+    """(rho, ux, uy) of ctx.macros() after the run's iterations, restated from the run's arrays in the run's dtype (lbm_kernels.hpp
+    macro_cell; csrc/lbm_steps.inc.hpp do_macros: it reads the buffer the last step kernel READ, which is the run's f_next, and
+    describes the run's last iteration):
+      * a fluid cell off the two port columns: the moments of its nine populations of f_next in the element type, i ascending, then
+        the two divisions; under a driving force h = F/2, cast once, is taken off each momentum before its division (macro_moments);
+      * a fluid cell of column 0 or nx - 1: (rho, u, 0) of the port's rule on the populations pulled from f_next behind the wall rule,
+        which is what `boundaries` recorded in rho / ux / uy at the last iteration, operation for operation: taken from there;
+      * a solid cell: (1, 0, 0), which rho / ux / uy hold too.
+    The oracle's rho / ux / uy of the other fluid cells are moments of f_current, another set of populations with the same sums up to
+    rounding: close to the snapshot, not equal to it."""
+    assert run.first_unstable == -1 and run.solid is not None
+    rho, ux, uy = run.rho.copy(), run.ux.copy(), run.uy.copy()
+    ny, nx = run.solid.shape
+    if nx > 2:
+        sel = ~run.solid[:, 1:-1]
+        f = [run.f_next[1:-1, 2:-2, i][sel] for i in range(9)]
+        r = np.zeros_like(f[0]); sx = np.zeros_like(f[0]); sy = np.zeros_like(f[0])
+        for i in range(9):
+            r = r + f[i]
+            sx = sx + float(CX[i]) * f[i]
+            sy = sy + float(CY[i]) * f[i]
+        if run.forced is not None:
+            sx = sx - 0.5 * float(run.forced[0])
+            sy = sy - 0.5 * float(run.forced[1])
+        for a, v in ((rho, r), (ux, sx / r), (uy, sy / r)):
+            inner = a[:, 1:-1]
+            inner[sel] = v
+    return rho, ux, uy

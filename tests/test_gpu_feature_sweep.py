@@ -6,16 +6,21 @@ sequences, strips of odd heights and checkpoints on grids narrower than a tile, 
 columns, and the register kernel's LEAN path (interior tiles: almost every tile of a real grid) is held to the reference for every model.
 
 fp64: against tests/reference.py oracle_run with the model's operator, at the bars of helpers.assert_matches_reference: strict plans
-f_next bit for bit and rho within 1e-14, contracted ones within 1e-10, force rows within 1e-10. fp32 has no oracle: bit for bit against
-the same context stepped at one iteration per launch in the same arithmetic, as tests/test_gpu_random.py does. Every run must name the
-kernel of its model and arithmetic mode, so no case can pass on another model's kernel."""
+f_next bit for bit and rho within 1e-14, contracted ones within 1e-10, force rows within 1e-10. fp32: bit for bit against the same
+context stepped at one iteration per launch in the same arithmetic, as tests/test_gpu_random.py does, and those single iterations
+against the reference: in strict arithmetic bit for bit against the same loop in float32 (feature_cases.reference32_of: f_next, the
+macro snapshot, the first unstable iteration), in contracted arithmetic against the fp64 reference within four float32 floors of the case
+(tests/f32_oracle_cases.py contracted_problems). Every run must name the kernel of its model and arithmetic mode, so no case can pass
+on another model's kernel."""
 import functools
 
 import numpy as np
 import pytest
 
+from tests import f32_oracle_cases as oc
 from tests import feature_cases as fc
 from tests.helpers import PLANS, U_BAR_ABS, assert_forces_match, assert_matches_reference, lbm_gpu, record, where  # noqa: F401
+from tests.reference import snapshot
 
 pytestmark = pytest.mark.gpu
 
@@ -101,6 +106,24 @@ def run_fp32_case(lbm, case):
         r_bad = one.first_unstable_step()
         if r_bad == -1:
             r_fn, r_macros, r_log = one.populations("f_next"), one.macros(), one.drain_force_log()
+    # the single iterations themselves against the reference: what every plan is held to below is then held to ground truth
+    if not fc.contracted(case.plan):
+        ref = fc.reference32_of(case)
+        assert count == ref.solid_count and r_bad == ref.first_unstable, (count, ref.solid_count, r_bad, ref.first_unstable)
+        if r_bad == -1:
+            want = ref.f_next.astype(np.float64)
+            assert np.array_equal(r_fn, want), "the single iterations' f_next is not the float32 reference's bit for bit: " + where(r_fn, want)
+            for got, want in zip(r_macros, snapshot(ref)):
+                assert np.array_equal(got, want.astype(np.float64)), "the single iterations' macros are not the float32 reference's snapshot"
+            assert_forces_match(r_log, ref.forces, "single iterations")
+    elif fc.reference_of(case).first_unstable == -1:
+        ref = fc.reference_of(case)
+        assert count == ref.solid_count and r_bad == -1, (count, ref.solid_count, r_bad)
+        err, floor = oc.errors(r_fn, r_macros, ref), oc.floors_of_runs(fc.reference32_of(case), ref)
+        record("f32_oracle_sweep_contracted", case=case.k, model=case.model, steps=fc.steps_of(case), err_f=err[0], err_rho=err[1], err_u=err[2],
+               floor_f=floor[0], floor_rho=floor[1], floor_u=floor[2])
+        bad = oc.contracted_problems(err, floor)
+        assert not bad, "the single iterations against the float64 reference: " + "; ".join(bad)
     with make(lbm, case) as ctx:
         assert ctx.initialise() == count
         for n in fc.issued_calls(case):

@@ -10,7 +10,7 @@ at EVERY position of a horizontal, a vertical and a diagonal line that cross sev
 outside a strip's window included), the smallest analytic discs (radius 0, 1, 2 cells: the disc branch of tile_near_solid) on the
 same lines, and single cells in the corners, next to them and on the four boundaries.
 
-References: the CPU oracle on the same mask (strict plans bit for bit, contracted ones within 1e-10); fp32, which has no oracle, is
+References: the CPU oracle on the same mask (strict plans bit for bit, contracted ones within 1e-10); fp32 (tests/test_gpu_f32_oracle.py holds it to a float32 reference) is
 held bit for bit to one k_step_site launch per iteration in the same arithmetic, as tests/test_gpu_random.py does.
 A failing item reports every position that failed, so that the distance to the nearest tile origin / face names the short level.
 

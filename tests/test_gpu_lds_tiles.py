@@ -14,7 +14,7 @@ names the plan, not the launches: no kernel but the plan's own fuses more than f
 that segment contain one.
 
 fp64 against the stepwise oracle at the bars of tests/helpers.py assert_matches_reference (strict: f_next bit for bit, rho within
-1e-14; contracted: 1e-10); fp32, which has no oracle, bit for bit against the same context stepped one iteration per launch."""
+1e-14; contracted: 1e-10); fp32 (held to a float32 reference in tests/test_gpu_f32_oracle.py) bit for bit against the same context stepped one iteration per launch."""
 import functools
 
 import numpy as np
