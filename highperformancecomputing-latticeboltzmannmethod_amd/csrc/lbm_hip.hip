@@ -1402,6 +1402,53 @@ int lbm_debug_geometry(const unsigned char* mask, int nx, int ny, int y_start, i
     return LBM_OK;
 }
 
+/* TEST HOOK (no device needed): the per-wave verdict of k_stepc_col (lbm_kernels.hpp wave_plain, the function the kernel's branch calls)
+ * for one wave of one tile of one launch of a context that is described, not created: see include/lbm_hip.h. The arguments the kernel
+ * would receive are formed as make_kargs, launch_fused_rows and band_origin form them. */
+int lbm_debug_wave_plain(int nx, int ny, int y_start, int local_ny, int precision, int arith, int periodic_y, const unsigned char* mask,
+                         const double* cylinder3, int deep, int depth, int y_lo, int y_cnt, int bx, int by, int wave, int* dims4) {
+    if (nx < 1 || ny < 1 || y_start < 0 || local_ny < 1 || y_start + local_ny > ny) return fail(LBM_ERR_ARG, "lbm_debug_wave_plain: strip [%d,%d) outside [0,%d)", y_start, y_start + local_ny, ny);
+    if (precision != LBM_PRECISION_F64 && precision != LBM_PRECISION_F32) return fail(LBM_ERR_ARG, "lbm_debug_wave_plain: bad precision %d", precision);
+    if ((arith != 0 && arith != 1) || (periodic_y != 0 && periodic_y != 1)) return fail(LBM_ERR_ARG, "lbm_debug_wave_plain: arith and periodic_y are 0 or 1");
+    const RegionKind* kind = deep_kind(deep);
+    if (!kind) return fail(LBM_ERR_ARG, "lbm_debug_wave_plain: deep %d is no register shape", deep);
+    const RowsWaves rw = col_rw(*kind, precision == LBM_PRECISION_F32 ? 4 : 8, arith != 0);
+    if (!rw.rows) return fail(LBM_ERR_ARG, "lbm_debug_wave_plain: deep %d (%s regions) is not built for this precision and arithmetic", deep, kind->name);
+    if (!col_depth(*kind, depth)) return fail(LBM_ERR_ARG, "lbm_debug_wave_plain: %s regions offer no launch of %d iterations", kind->name, depth);
+    if (y_cnt <= 0) { y_lo = 0; y_cnt = local_ny; }
+    const int HW = depth - 1, OW = col_tile_w(depth), OH = col_tile_h(depth, rw);
+    const int nbx = (nx + OW - 1) / OW, nby = (y_cnt + OH - 1) / OH;
+    if (bx < 0 || bx >= nbx || by < 0 || by >= nby || wave < 0 || wave >= rw.waves)
+        return fail(LBM_ERR_ARG, "lbm_debug_wave_plain: tile (%d, %d) of %d x %d, wave %d of %d", bx, by, nbx, nby, wave, rw.waves);
+    lbm_ctx* c = choreo_fake_ctx(nx, ny, y_start, local_ny, precision, 0);      // (row-interleaved, as every deep plan is)
+    c->periodic_y = periodic_y;
+    if (cylinder3) { c->cyl_x = (int)(cylinder3[0] * nx); c->cyl_y = (int)(cylinder3[1] * ny); c->cyl_r = (int)(cylinder3[2] * ny); }
+    KArgs<double> a{};
+    a.nx = nx; a.ny_loc = local_ny; a.ny_glob = rows_glob(c); a.y_start = row_start(c);
+    a.cyl_x = c->cyl_x; a.cyl_y = c->cyl_y; a.cyl_r2 = (double)(c->cyl_r * c->cyl_r);
+    a.y_lo = y_lo; a.y_cnt = y_cnt;
+    HostMask h;
+    if (periodic_y) {       // (prepare_periodic: the wrapped window of the mask or of the disc)
+        const double r2 = a.cyl_r2;
+        h = pack_mask_periodic([&](int x, int, int y) {
+            if (mask) return mask[(size_t)y * nx + x] != 0;
+            const double dx = x - c->cyl_x, dy = y - c->cyl_y;
+            return dx * dx + dy * dy <= r2;
+        }, nx, ny, y_start, local_ny, PERIODIC_PAD);
+    } else if (mask) h = pack_mask(mask, nx, ny, y_start, local_ny);
+    if (periodic_y || mask) a.mv = h.view();
+    const bool small = buffer_small(c);
+    delete c;
+    const int y_end = y_lo + y_cnt, Xo = bx * OW, Yo = y_lo + by * OH;               // (band_origin, first range)
+    const bool near = tile_near_solid(a, Xo, Yo, OW, OH, HW);
+    if (dims4) {
+        const int yg0 = a.y_start + Yo;
+        const bool lean = !near && Xo >= HW + 1 && Xo + OW + HW <= nx - 1 && yg0 >= HW + 1 && yg0 + OH + HW <= a.ny_glob - 1 && Yo + OH <= y_end && small;   // (TileFrame::lean)
+        dims4[0] = rw.rows; dims4[1] = rw.waves; dims4[2] = lean ? 1 : 0; dims4[3] = near ? 1 : 0;
+    }
+    return wave_plain(nx, a.ny_glob, a.y_start, Xo, Yo, y_end, OW, OH, HW, near, small, wave * rw.rows, rw.rows) ? 1 : 0;
+}
+
 /* TEST HOOK (no device needed): what lbm_set_body_labels uploads for the strip [y_start, y_start + local_ny) (csrc/lbm_geom.hpp pack_bodies). */
 int lbm_debug_body_chunks(const unsigned char* labels, int nx, int ny, int y_start, int local_ny, int* boxes4, int boxes_cap,
                           long* chunks3, int chunks_cap, int* nchunks_out) {

@@ -44,6 +44,26 @@
 // Ghost rows (general path): a top row outside the domain takes its ghost values at level 1, is skipped at levels 2..D and is read at
 // every one of them, from both parities of xbuf: level 1 writes its three into both. pbuf keeps its other six untouched.
 // A lane that reads a pad column of pbuf (lane 0 at x-1, lane 63 at x+1) is outside every window from level 2 on, as for xbuf.
+// Mixed blocks. The path is chosen per WAVE: a block that is not lean (a wall tile, a partial band, a strip's edge) still sends down the
+// lean path every wave for which wave_plain (lbm_kernels.hpp) holds — all its rows plain interior fluid at every level, loaded at level 1,
+// counted and stored as the general path would. In a top wall tile of seven iterations on 64x40 that is four of eight waves, in a bottom
+// one six; the general path is 2.85 times the lean path's instructions per level. Why the two paths may share a block:
+//   barriers  both run exactly one __syncthreads per level 2..D and none elsewhere (the early return is for the whole block), and the
+//             hardware barrier counts the waves of the workgroup that arrive, at whichever instruction each of them does
+//   xbuf      both write slots [L&1][w][3..5] (and [0..2], unparked) in front of barrier L and read [L&1][w-1][0..2] / [w+1][3..5] behind
+//             it, under the same window test (the general path's additional `rin` is true for a plain wave's rows), so a wave cannot tell
+//             which path its neighbour took; the reuse argument above speaks of levels and barriers only and holds as it stands
+//   pbuf      a wave touches its own slot only
+//   ghost rows (parked form) a general wave's level 1 parks its top row's north-going three into BOTH parities, a lean wave into parity 0
+//             only. The second write is for a top row that no later level updates because it lies outside the domain; a plain wave has no
+//             such row, and its top row is covered by "Skipped top rows". The general wave's extra write into xbuf[1][w][0..2] is read by
+//             wave w+1 at level 3 at the earliest and overwritten before by w's own level 2 where that level updates the row: as in a
+//             block that is general throughout
+//   u_sh      written and read by general waves of tile column 0 only; no wave of that column is plain
+//   counting  level 1 counts every lane of every row on the lean path and `col_in` lanes of loaded rows on the general path; levels 2..D
+//             count `lane_ok` against `lane_ok && col_in && y <= y_end + HW - L`; the stores add `col_in && y < y_end && !solid`:
+//             wave_plain is true only where each pair agrees for all the wave's rows
+// A lean tile's waves never evaluate a different instruction stream than before: the verdict is one more scalar test in front of it.
 #pragma once
 #include "lbm_kernels.hpp"
 
@@ -74,8 +94,11 @@ template <int NW> constexpr int col_waves_per_simd() { return NW == 12 ? 6 : NW 
 // ... per instantiation: the fp32 contracted TRT kernels of eight waves run THREE blocks per CU (six waves per SIMD, 80 VGPRs; 74 when they
 // were written). With the bound of four the allocator takes what it likes below 128, and the seven-iteration one came out at 82 once
 // KArgs carried the walls: two blocks per CU, 237 -> 208 GLUPS at 4096x1024 (profiles/walls/README.md). Said here, it stays at six.
+// The fp32 contracted MRT kernels likewise: 76-80 VGPRs before the per-wave verdict; with it and the bound of four the five-iteration
+// ones took 82 (five waves per SIMD instead of six). Under the bound of six: 78 / 76 / 78 at five / six / seven iterations, no scratch
+// (profiles/boundary_waves/kernel_resources.txt).
 template <typename T, int NW, int AR> constexpr int col_min_waves() {
-    return (sizeof(T) == 4 && NW == 8 && AR == AR_CONTRACTED_TRT) ? 6 : col_waves_per_simd<NW>();
+    return (sizeof(T) == 4 && NW == 8 && (AR == AR_CONTRACTED_TRT || AR == AR_CONTRACTED_MRT)) ? 6 : col_waves_per_simd<NW>();
 }
 
 // Tile walk: blocks are dealt round-robin over the 8 XCDs (each with its own 4 MiB L2) in index order; here every XCD walks
@@ -320,7 +343,8 @@ __global__ void __launch_bounds__(NW * 64, (col_min_waves<T, NW, AR>())) k_stepc
         };
         [&]<int... Ls>(std::integer_sequence<int, Ls...>) { (level.template operator()<Ls + 2>(), ...); }(std::make_integer_sequence<int, D - 1>{});
     };
-    if (fr.lean) run.template operator()<true>();
+    // (wave-uniform: header, "Mixed blocks")
+    if (fr.lean || wave_plain(a.nx, a.ny_glob, a.y_start, Xo, Yo, y_end, OW, OH, HW, fr.near_solid, e.small != 0, ry0, R)) run.template operator()<true>();
     else run.template operator()<false>();
 }
 

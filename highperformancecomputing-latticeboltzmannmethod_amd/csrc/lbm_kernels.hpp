@@ -226,8 +226,9 @@ __device__ __forceinline__ bool solid_at(const A& a, int x, int yg) {
 // Block-uniform test: can any cell of the tile [X0, X0+TX) x [Y0, Y0+TY) grown by `ring` cells be solid? Disc: bounding
 // boxes in integer cells (cyl_r2 = r*r exactly, so r is recovered by an exact sqrt of a perfect square). Mask: the coarse table
 // with the box rounded outward to 8x8 blocks. Both exact or conservative: false only where no cell of the box is solid.
+// __host__ too: lbm_debug_wave_plain asks it on the CPU.
 template <typename T>
-__device__ __forceinline__ bool tile_near_solid(const KArgs<T>& a, int X0, int Y0, int TX, int TY, int ring) {
+__host__ __device__ __forceinline__ bool tile_near_solid(const KArgs<T>& a, int X0, int Y0, int TX, int TY, int ring) {
     const int yg0 = a.y_start + Y0;
     if (a.mv.bits) return mask_box_any(a.mv, X0 - ring, X0 + TX - 1 + ring, yg0 - ring, yg0 + TY - 1 + ring);
     const int r = (int)sqrt(a.cyl_r2) + 1;
@@ -926,6 +927,41 @@ struct TileFrame {
         if (nt) store<true>(f, voff, soff); else store<false>(f, voff, soff);
     }
 };
+
+// The verdict of ONE WAVE of k_stepc_col in a block that is not lean (TileFrame::lean is one verdict for the whole block, and a tile
+// whose rings touch a wall row fails it for all its waves, those included whose rows are plain interior fluid at every level). The wave
+// holds the R region rows from ry0 of the tile whose outputs are the OW x OH cells at local (Xo, Yo) with HW = D - 1 rings; its band ends
+// at y_end. True when every test the general path makes on these rows and on the tile's columns, at every level 1..D, comes out as it
+// does for a plain fluid cell, so that the lean path reads, counts and stores for this wave exactly what the general path would:
+//   columns  the x-conditions of `lean`: no lane lacks a column, none is the inlet or the outlet column
+//   geometry the tile is not near a solid cell (the general path's `sbits` stay 0, its selects change nothing)
+//   small    the lean path addresses the buffers with 32-bit byte offsets
+//   rows     all R rows lie in [1, ny_glob - 2]: inside the domain (`rin`), off both wall rows. A strip's face and a periodic lattice
+//            (a strip PERIODIC_PAD rows up in a taller lattice) reach a wave through these row numbers and through y_end alone
+//   load     level 1 loads all R rows (`rld`: y <= y_end + HW - 1)
+//   count    levels 2..D count a row inside the level's window (L - 1 <= ry <= H - L) where y <= y_end + HW - L; the lean path counts
+//            every row of the window. ry + L over the levels that hold ry is at most min(ry + D, 2 ry + 1, H), which grows with ry, so
+//            the wave's last row decides (the rows no level >= 2 holds, ry = 0 and ry = H - 1, are never the binding ones: R >= 2)
+//   store    the lean path stores the wave's rows of [Yo, Yo + OH); the general path those below y_end as well: the same rows
+// A full band (Yo + OH <= y_end) passes load, count and store for every wave; the partial top band of a whole domain passes them for
+// every wave whose rows end below the wall row (y_end = ny_glob there); other partial bands are decided by the same three tests.
+// Every term is conservative or exact: false wherever a test of the general path could come out otherwise. The kernel's branch and
+// lbm_debug_wave_plain (and through it the tests) call this function. Two restatements exist and must follow it: tools/prof_phases.py
+// classifies recorded waves with a copy in Python, and lbm_debug_wave_plain restates TileFrame::lean for the block verdict it reports.
+__host__ __device__ inline bool wave_plain(int nx, int ny_glob, int y_start, int Xo, int Yo, int y_end, int OW, int OH, int HW,
+                                           bool near_solid, bool small, int ry0, int R) {
+    const int D = HW + 1, H = OH + 2 * HW;
+    const int ya = Yo - HW + ry0, yb = ya + R - 1, ryb = ry0 + R - 1;            // first / last local row, last region row
+    int top = ryb + D;                                                        // max (ry + L) over the levels that hold the last row
+    if (2 * ryb + 1 < top) top = 2 * ryb + 1;
+    if (H < top) top = H;
+    const int last_out = yb < Yo + OH - 1 ? yb : Yo + OH - 1;                 // the last row the lean path stores, if it stores any
+    return !near_solid && small && Xo >= HW + 1 && Xo + OW + HW <= nx - 1 &&
+           y_start + ya >= 1 && y_start + yb <= ny_glob - 2 &&
+           yb <= y_end + HW - 1 &&
+           top <= y_end - Yo + 2 * HW &&
+           (ya >= Yo + OH || last_out < y_end);
+}
 
 // The frame of the LDS tile kernels: tile (bx, by) of TX x TY outputs, grid = tiles x bands. Workgroups are dealt round-robin
 // over the 8 XCDs (each with its own L2); with e.xcd the linear block id is remapped so that every XCD walks one contiguous run

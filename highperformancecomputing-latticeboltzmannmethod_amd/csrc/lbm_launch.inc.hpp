@@ -147,6 +147,8 @@ inline int deep_rows(const lbm_ctx* c, int id, int depth) {
     const RegionKind* k = deep_kind(id);
     return k ? col_tile_h(depth, col_rw(*k, (int)c->esize, c->arith != 0)) : deep_shape(id)->tile_h;
 }
+// K2Extra::small: the lean paths may address the buffer with 32-bit byte offsets (+ one row of slack). Also asked by lbm_debug_wave_plain.
+inline bool buffer_small(const lbm_ctx* c) { return (c->total + (size_t)c->pitch) * c->esize + 1024 < (size_t(1) << 32); }
 // A fused kernel over the local rows [a.y_lo, a.y_lo + a.y_cnt): iterations a.t .. a.t + depth - 1 (depth 2..8). LBM_ERR_ARG, and
 // nothing queued: a deep launch of a depth the shape's row does not list (plan_launch reads the same row: it asks for none).
 template <typename T>
@@ -154,7 +156,7 @@ int launch_fused_rows(const lbm_ctx* c, const KArgs<T>& a, int depth, hipStream_
     const int shape = c->deep;
     K2Extra<T> e;
     e.feq_in = static_cast<const T*>(c->d_feq);
-    e.small = ((c->total + (size_t)c->pitch) * c->esize + 1024 < (size_t(1) << 32)) ? 1 : 0;   // 32-bit byte offsets (+ one row of slack)
+    e.small = buffer_small(c) ? 1 : 0;
     e.xcd = c->xcd;
     e.nt = c->use_nt;
     e.ntl = c->use_ntl;

@@ -776,6 +776,18 @@ int lbm_debug_p2p_matching(int nx, int ny, const int* bounds2, int nranks, int p
  * "any solid cell in the box" for boxes4[k] = {x0, x1, y0, y1} (global, inclusive), answered from the coarse table. */
 int lbm_debug_geometry(const unsigned char* mask, int nx, int ny, int y_start, int local_ny, int* dims9, unsigned long long* bits, long bits_cap,
                        int* sat, long sat_cap, const int* boxes4, int nbox, int* near_out);
+/* Test hook, callable without a device: the verdict the register kernel k_stepc_col reaches for ONE WAVE of a tile that is not lean as
+ * a whole — may the wave run the lean path although its block does not (csrc/lbm_kernels.hpp wave_plain, the very function the kernel's
+ * branch calls, compiled for the host)? The context is described: the strip [y_start, y_start + local_ny) of an nx x ny lattice in
+ * `precision` with arithmetic `arith` (0 strict, 1 contracted), periodic_y as lbm_set_periodic_y, `mask` as lbm_set_solid_mask takes it
+ * (NULL: the disc of cylinder3 = {x / nx, y / ny, radius / ny}; NULL: 0.2, 0.5, 0.05). The launch: `depth` iterations on the regions of
+ * shape `deep` (option "deep": a register shape) over the local rows [y_lo, y_lo + y_cnt) (y_cnt <= 0: the whole strip; a range launch
+ * of option "split" or an edge band otherwise). The wave: `wave` of tile column bx, band by of that range. Returns 1 (plain), 0, or
+ * LBM_ERR_ARG. dims4 (nullable) = {rows per thread, waves per block, the block's own lean verdict, its near-solid verdict}. Walls, ports
+ * and inlet profiles need no argument: they act on rows 0 and ny - 1 and on columns 0 and nx - 1, which no plain wave holds.
+ * No reference counterpart. */
+int lbm_debug_wave_plain(int nx, int ny, int y_start, int local_ny, int precision, int arith, int periodic_y, const unsigned char* mask,
+                         const double* cylinder3, int deep, int depth, int y_lo, int y_cnt, int bx, int by, int wave, int* dims4);
 /* Test hook, callable without a device: what lbm_set_body_labels derives from a global [ny][nx] label array for the strip
  * [y_start, y_start + local_ny) (csrc/lbm_geom.hpp pack_bodies). Returns B (or < 0). boxes4 (nullable, boxes_cap entries of four ints) =
  * B x {x0, x1, y0, y1}: body k's bounding box dilated by one cell, clipped to the domain and to the strip's rows, inclusive, y in LOCAL

@@ -69,6 +69,8 @@ struct Lattice {
         a.cyl_x = (int)(0.2 * nx); a.cyl_y = (int)(0.5 * ny);
         const int r = (int)(0.05 * ny); a.cyl_r2 = (double)(r * r);
         a.tau_inv = (T)(1.0 / 0.6); a.u_row = d_urow; a.unstable_t = d_unst; a.t = depth_t; a.t_base = d_zero;
+        a.walls = wall_pack(WALL_NOSLIP, WALL_NOSLIP) | port_pack(PORT_VELOCITY, PORT_PRESSURE);       // the reference's walls and ports
+        a.wk = wall_ks<T>(WALL_NOSLIP, 0.0, WALL_NOSLIP, 0.0); a.pk = port_ks<T>(1.0, PORT_PRESSURE, 1.0);
         return a;
     }
     K2Extra<T> extra() { K2Extra<T> e; e.feq_in = d_feq; e.xcd = 1; e.nt = 1; e.ntl = g_ntl; e.small = (total * sizeof(T) + 4096 < (size_t(1) << 32)) ? 1 : 0; return e; }

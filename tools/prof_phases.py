@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Reads the in-kernel phase records written by `tools/colbench_prof --prof DIR` (lbm_kernel_col.hpp, LBM_COL_PROF) and
 prints, per kernel variant: the clock calibration, the distribution of every phase over the blocks (load issue -> level 1
-done, then one entry per level / step), how many blocks a CU holds at once and how their phases overlap.
+done, then one entry per level / step), how many blocks a CU holds at once and how their phases overlap; block lifetimes for three
+tile classes (lean, wall, other general: tile_classes), inside wall tiles the level times of the waves the per-wave verdict sends down
+the lean path against the others, and per XCD the end of its last block.
+A record is ONE whole-domain launch (y_start = 0, y_end = ny): colbench issues no row-range launches and the record is indexed by the
+tile index within a launch, so the per-XCD end times of each range kernel of a `split` launch are not reported here
+(profiles/boundary_waves/README.md §3 says what that would take).
 usage: tools/prof_phases.py DIR [--cu N]"""
 import csv, glob, os, sys
 import numpy as np
@@ -16,9 +21,12 @@ def load(path):
     return head, launch_us, cols, data
 
 def tile_classes(head, blocks):
-    """Of every block index (the tile index the kernel records): True where the tile takes the lean path. The predicate is
-    TileFrame::lean (csrc/lbm_kernels.hpp) on the lattice tools/colbench.hip builds: one whole-domain launch of the fp64 register kernel,
-    the disc at (0.2 nx, 0.5 ny) with radius 0.05 ny. None where the header names no register kernel."""
+    """Of every block index (the tile index the kernel records): its class and, for a wall tile, which of its waves are plain.
+    Classes: "lean" (TileFrame::lean, csrc/lbm_kernels.hpp), "wall" (not lean only because its rings touch a wall row or its band is
+    partial: a middle tile column, no solid cell near — the tiles whose plain waves take the lean path, wave_plain), "other" (tile
+    columns 0 and last, tiles near the disc). The predicates are those of csrc/lbm_kernels.hpp on the lattice tools/colbench.hip builds:
+    one whole-domain launch of the fp64 register kernel, the disc at (0.2 nx, 0.5 ny) with radius 0.05 ny. None where the header names
+    no register kernel. Returns ({block: class}, {block: [plain per wave]}, NW)."""
     import re
     m = re.search(r"col R=(\d+) NW=(\d+) D=(\d+) (..) (alt)? *p\d+ (\d+)x(\d+) ", head)
     if not m:
@@ -26,19 +34,28 @@ def tile_classes(head, blocks):
     R, NW, D = int(m.group(1)), int(m.group(2)), int(m.group(3))
     nx, ny = int(m.group(6)), int(m.group(7))
     HW = D - 1
-    OW, OH = 64 - 2 * HW, R * NW - 2 * HW
+    OW, OH, H = 64 - 2 * HW, R * NW - 2 * HW, R * NW
     nbx, nby = -(-nx // OW), -(-ny // OH)
     cx, cy, r = int(0.2 * nx), int(0.5 * ny), int(0.05 * ny) + 1
     pitch0 = -(-(16 + nx + 1) // 16) * 16                       # (Lattice<double>: 128-byte sub-rows, twelve ghost rows on each side)
     small = 9 * pitch0 * (ny + 24) * 8 + 4096 < 2 ** 32
-    out = {}
+    cls, plain = {}, {}
     for b in blocks:
         by, bx = divmod(int(b), nbx)
         X0, Y0 = bx * OW, by * OH
         near = X0 - HW <= cx + r and X0 + OW - 1 + HW >= cx - r and Y0 - HW <= cy + r and Y0 + OH - 1 + HW >= cy - r
-        out[b] = (not near and X0 >= HW + 1 and X0 + OW + HW <= nx - 1 and Y0 >= HW + 1 and Y0 + OH + HW <= ny - 1
-                  and Y0 + OH <= ny and small and by < nby)
-    return out
+        xok = X0 >= HW + 1 and X0 + OW + HW <= nx - 1
+        lean = (not near and xok and Y0 >= HW + 1 and Y0 + OH + HW <= ny - 1 and Y0 + OH <= ny and small and by < nby)
+        cls[b] = "lean" if lean else ("wall" if (xok and not near and small) else "other")
+        if cls[b] == "wall":           # wave_plain, y_start = 0, y_end = ny_glob = ny
+            out = []
+            for w in range(NW):
+                ya = Y0 - HW + w * R
+                yb, ryb = ya + R - 1, w * R + R - 1
+                top = min(ryb + D, 2 * ryb + 1, H)
+                out.append(ya >= 1 and yb <= ny - 2 and yb <= ny + HW - 1 and top <= ny - Y0 + 2 * HW and (ya >= Y0 + OH or min(yb, Y0 + OH - 1) < ny))
+            plain[b] = out
+    return cls, plain, NW
 
 def describe(path, show_cu=None):
     head, launch_us, cols, d = load(path)
@@ -85,22 +102,42 @@ def describe(path, show_cu=None):
     life = last - first
     print(f"   block lifetime us: median {np.median(life):.2f}, p10 {np.percentile(life,10):.2f}, p90 {np.percentile(life,90):.2f}; "
           f"first starts: {np.sort(first)[:3].round(2)}, last start {first.max():.2f}, last end {last.max():.2f}")
-    # block lifetime by tile class (first mark of wave 0 -> last mark of any wave of the block), lean against general
-    lean = tile_classes(head, blocks)
+    # block lifetime by tile class (first mark of any wave -> last mark of any wave of the block): lean, wall, other general
+    tc = tile_classes(head, blocks)
+    lean = None
     allfirst = np.where(used, t, np.inf).min(axis=1); alllast = np.where(used, t, -np.inf).max(axis=1)
-    if lean is not None:
+    if tc is not None:
+        cls, plain, _ = tc
+        lean = {b: cls[b] == "lean" for b in blocks}
         bl = np.array([bix[b] for b in d[:, 0].tolist()])
         bfirst = np.full(len(blocks), np.inf); blast = np.full(len(blocks), -np.inf)
         np.minimum.at(bfirst, bl, allfirst); np.maximum.at(blast, bl, alllast)
         blife = blast - bfirst
-        is_lean = np.array([lean[b] for b in blocks])
-        for name, sel in (("lean", is_lean), ("general", ~is_lean)):
+        kind = np.array([cls[b] for b in blocks])
+        is_lean = kind == "lean"
+        for name, sel in (("lean", is_lean), ("general", ~is_lean), ("wall", kind == "wall"), ("other", kind == "other")):
             if sel.sum():
                 v = blife[sel]
                 print(f"   {name:7s} blocks: {int(sel.sum()):5d}, lifetime us (all waves): median {np.median(v):.2f}, p10 {np.percentile(v,10):.2f}, "
                       f"p90 {np.percentile(v,90):.2f}")
-        if is_lean.sum() and (~is_lean).sum():
-            print(f"   general / lean median lifetime: {np.median(blife[~is_lean]) / np.median(blife[is_lean]):.3f}")
+        if is_lean.sum():
+            for name, sel in (("general", ~is_lean), ("wall", kind == "wall"), ("other", kind == "other")):
+                if sel.sum():
+                    print(f"   {name} / lean median lifetime: {np.median(blife[sel]) / np.median(blife[is_lean]):.3f}")
+        # inside wall tiles: the time of every level (mark k-1 -> k) of the waves wave_plain passes against the waves it does not
+        rows_wall = np.array([cls[b] == "wall" for b in d[:, 0].tolist()])
+        if rows_wall.any():
+            wp = np.array([cls[b] == "wall" and plain[b][int(w)] for b, w in zip(d[:, 0].tolist(), d[:, 1].tolist())])
+            print(f"   wall tiles: {int((rows_wall & wp).sum())} plain wave records, {int((rows_wall & ~wp).sum())} general; level times us, median (p90), "
+                  "plain | general, and the waves of lean tiles beside them:")
+            rows_lean = np.array([lean[b] for b in d[:, 0].tolist()])
+            for k in range(1, nmarks):
+                def stat(sel):
+                    ok = sel & used[:, k] & used[:, k - 1]
+                    if not ok.any(): return "      -      "
+                    v = t[ok, k] - t[ok, k - 1]
+                    return f"{np.median(v):6.2f} ({np.percentile(v, 90):6.2f})"
+                print(f"     {k:3d}: {stat(rows_wall & wp)} | {stat(rows_wall & ~wp)} | lean {stat(rows_lean)}")
     # per XCD: when its last block ends, relative to the launch's end (the last mark of all)
     xall = d[:, 2] & 0xf
     end = alllast.max(); start = allfirst.min()
