@@ -102,6 +102,10 @@ def lib():
         L.lbm_get_forcing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.lbm_set_mrt.argtypes = [vp, C.c_double, C.c_double]
         L.lbm_get_mrt.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.lbm_set_sponge.argtypes = [vp, C.c_int, C.c_double]
+        L.lbm_get_sponge.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_double)]
+        L.lbm_get_sponge_rate.argtypes = [vp, C.c_int, C.POINTER(C.c_double)]
+        L.lbm_debug_sponge_rates.argtypes = [C.c_int, C.c_double, C.c_int, C.c_int, C.c_double, dp, dp]
         L.lbm_set_wall.argtypes = [vp, C.c_int, C.c_int, C.c_double]
         L.lbm_get_wall.argtypes = [vp, C.c_int, C.POINTER(C.c_int), dp]
         L.lbm_debug_wall_rule.argtypes = [C.c_int, C.c_int, C.c_double, C.c_int, dp, dp]
@@ -359,6 +363,33 @@ def sine_pulse(amplitude, period):
     return 1.0 + float(amplitude) * np.sin(2.0 * np.pi * k / period)
 
 
+def sponge_tau(nx, tau, width, tau_end):
+    """The relaxation time of every column under lbm_set_sponge(width, tau_end), float64 [nx], operation by operation as the library forms
+    it: tau up to column x0 = nx - 1 - width, then tau + (tau_end - tau) * (s * s) with s = (x - x0) / width. The kernels relax column x
+    with the rate (1 / sponge_tau)[x] cast once to their element type (Context.sponge_rate). width 0: tau everywhere."""
+    nx, width, tau, tau_end = int(nx), int(width), float(tau), float(tau_end)
+    if nx < 1 or width < 0 or width > nx - 1:
+        raise ValueError("a sponge of %d columns does not fit %d columns (0 .. nx - 1; column 0 keeps tau)" % (width, nx))
+    t = np.full(nx, tau, dtype=np.float64)
+    if width > 0:
+        x0 = nx - 1 - width
+        s = np.arange(1, width + 1, dtype=np.float64) / np.float64(width)
+        t[x0 + 1:] = tau + (tau_end - tau) * (s * s)
+    return t
+
+
+def debug_sponge_rates(nx, tau, precision, width, tau_end):
+    """lbm_debug_sponge_rates (no device): lbm_set_sponge on a context of nx columns, then what lbm_get_sponge and lbm_get_sponge_rate
+    report: ((width, tau_end), float64 [nx] rates). precision: "f64" / "f32". Raises LbmError with the setter's text if it refuses."""
+    pair, rates = np.zeros(2, dtype=np.float64), np.zeros(int(nx), dtype=np.float64)
+    dp = C.POINTER(C.c_double)
+    rc = lib().lbm_debug_sponge_rates(int(nx), float(tau), 1 if precision in ("f32", 1) else 0, int(width), float(tau_end),
+                                      pair.ctypes.data_as(dp), rates.ctypes.data_as(dp))
+    if rc != 0:
+        raise LbmError(lib().lbm_last_error().decode())
+    return (int(pair[0]), float(pair[1])), rates
+
+
 def _schedule(spec):
     """The inlet_schedule= keyword as (float64 table, mode number): a table (hold) or a pair (table, "hold" | "repeat" | 0 | 1)."""
     mode = 0
@@ -521,6 +552,9 @@ class Context:
     mrt: optional pair (bulk_rate, magic) of a multiple-relaxation-time collision (lbm_set_mrt): TRT with that magic parameter whose
     bulk rate, in (0, 2), is free of tau (1/tau: TRT; lower: more bulk viscosity); bulk_rate 0 / None: BGK; not with smagorinsky,
     trt_magic or forcing.
+    sponge: optional pair (width, tau_end) of an outlet sponge zone (lbm_set_sponge): over the last `width` columns the relaxation time
+    rises from tau to tau_end (sponge_tau), so that what reaches the east port is diffused before it reflects; width 0 / None: none; not
+    with smagorinsky, trt_magic, forcing or mrt.
     ports: optional pair (west, east) of the two open ends (lbm_set_port) in place of the velocity inlet and the pressure outlet with
     rho = 1: west "velocity" or ("pressure", rho), east ("pressure", rho) or ("velocity", u); None in either place: that port's default.
     A west pressure port takes neither inlet_profile nor inlet_schedule (initialise() fails). periodic_y: True makes the top and bottom
@@ -530,7 +564,8 @@ class Context:
     def __init__(self, nx, ny, tau=0.6, inlet_velocity=0.01333, cylinder_x=0.2, cylinder_y=0.5,
                  cylinder_radius=0.05, y_start=0, local_ny=0, precision="f64", device=0, force_log_capacity=0,
                  options=None, solid=None, inlet_profile=None, smagorinsky=None, bodies=None, frames=None, trt_magic=None,
-                 probes=None, probe_capacity=None, walls=None, inlet_schedule=None, forcing=None, ports=None, periodic_y=False, mrt=None):
+                 probes=None, probe_capacity=None, walls=None, inlet_schedule=None, forcing=None, ports=None, periodic_y=False, mrt=None,
+                 sponge=None):
         if solid is not None and bodies is not None:
             raise LbmError("solid= and bodies= exclude each other: the body labels are the geometry (solid where nonzero)")
         self.L = lib()
@@ -567,6 +602,8 @@ class Context:
             self.set_forcing(*forcing)
         if mrt is not None:
             self.set_mrt(*mrt)
+        if sponge is not None:
+            self.set_sponge(*sponge)
         if ports is not None:
             for side, (kind, v) in zip(("west", "east"), _port_pair(ports)):
                 self.set_port(side, kind, v)
@@ -657,6 +694,23 @@ class Context:
         sb, magic = C.c_double(), C.c_double()
         self._chk(self.L.lbm_get_mrt(self.h, C.byref(sb), C.byref(magic)))
         return sb.value, magic.value
+
+    def set_sponge(self, width, tau_end):
+        """lbm_set_sponge: the outlet sponge zone, `width` columns in 0 .. nx - 1 (0: none) over which the relaxation time rises to tau_end
+        > 0.5; before initialise()."""
+        self._chk(self.L.lbm_set_sponge(self.h, int(width), float(tau_end)))
+
+    def sponge(self):
+        """(width, tau_end) as set (lbm_get_sponge); (0, 0.0) without a sponge."""
+        width, tau_end = C.c_int(), C.c_double()
+        self._chk(self.L.lbm_get_sponge(self.h, C.byref(width), C.byref(tau_end)))
+        return width.value, tau_end.value
+
+    def sponge_rate(self, x):
+        """The rate column x relaxes with, as the kernels see it (lbm_get_sponge_rate): float(T(1 / tau_x)); BGK's 1 / tau without a sponge."""
+        wp = C.c_double()
+        self._chk(self.L.lbm_get_sponge_rate(self.h, int(x), C.byref(wp)))
+        return wp.value
 
     def forcing(self):
         """(fx, fy) as set (lbm_get_forcing); (0.0, 0.0) without a force."""
@@ -947,12 +1001,12 @@ class Group:
     solid: optional global (ny, nx) obstacle mask, inlet_profile: optional global [ny] inlet velocities, smagorinsky: optional LES
     constant Cs, trt_magic: optional TRT magic parameter, bodies: optional global (ny, nx) body numbers (in place of solid), frames: optional frame stride k, probes / probe_capacity: optional probe points (global coordinates), walls: optional kinds of the
     bottom and top walls (as Context takes them), inlet_schedule: optional scale factors of the inflow per iteration (likewise), forcing:
-    optional driving force (fx, fy), mrt: optional MRT pair (bulk_rate, magic), ports: optional pair (west, east) of the two open ends (as Context takes them), periodic_y: True joins strip
+    optional driving force (fx, fy), mrt: optional MRT pair (bulk_rate, magic), sponge: optional outlet sponge (width, tau_end), ports: optional pair (west, east) of the two open ends (as Context takes them), periodic_y: True joins strip
     n - 1 to strip 0 (periodic top and bottom, as Context takes it); all given to every member."""
 
     def __init__(self, nx, ny, bounds, devices=None, transport="peer", options=None, solid=None, inlet_profile=None, smagorinsky=None,
                  bodies=None, frames=None, trt_magic=None, probes=None, probe_capacity=None, walls=None, inlet_schedule=None, forcing=None,
-                 ports=None, periodic_y=False, mrt=None, **kw):
+                 ports=None, periodic_y=False, mrt=None, sponge=None, **kw):
         from .strips import partition_rows
         if isinstance(bounds, int):
             bounds = partition_rows(ny, bounds)
@@ -961,7 +1015,7 @@ class Group:
         self.ctxs = [Context(nx, ny, y_start=y0, local_ny=n, device=d, options=options, solid=solid, inlet_profile=inlet_profile,
                              smagorinsky=smagorinsky, bodies=bodies, frames=frames, trt_magic=trt_magic, probes=probes,
                              probe_capacity=probe_capacity, walls=walls, inlet_schedule=inlet_schedule, forcing=forcing, ports=ports,
-                             periodic_y=periodic_y, mrt=mrt, **kw)
+                             periodic_y=periodic_y, mrt=mrt, sponge=sponge, **kw)
                      for (y0, n), d in zip(bounds, devices)]
         self.L = lib()
         self._arr = (C.c_void_p * len(self.ctxs))(*[c.h for c in self.ctxs])

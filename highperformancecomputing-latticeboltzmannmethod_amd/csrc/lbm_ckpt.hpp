@@ -20,6 +20,7 @@
 //                bit 8 (256) 4 doubles west kind, west value, east kind, east value; where a port is off its default: lbm_set_port
 //                bit 9 (512) nothing   periodic y (the flag is the field)       lbm_set_periodic_y
 //                bit 10 (1024) 2 doubles the MRT pair {bulk rate, magic}          lbm_set_mrt
+//                bit 11 (2048) 2 doubles the outlet sponge {width, tau_end}       lbm_set_sponge
 //              (the bits and sizes of the collision parameters are those of collision_models, lbm_plan.hpp; a context has one model)
 //        then  the post-collision populations P_{steps_done} of the strip's interior, [9][local_ny][nx] in the element type
 // "LBMCKPT2" is the fixed header, the mask's digest (no flags) and the populations; "LBMCKPT1" the fixed header and the populations.
@@ -30,7 +31,7 @@
 // low and the high half of each velocity's bit pattern}; schedule {mode, n, the halves of each factor}.
 // A context loads only a file that announces exactly the fields it has, with equal values (doubles compared as numbers) and an equal
 // fixed header but for steps_done. The refusal names the first difference in this order: the collision models from the last row of
-// collision_models to the first (MRT, forcing, TRT, Smagorinsky), the walls, periodic y, the ports, the inlet profile, the inlet schedule, the mask, the header.
+// collision_models to the first (sponge, MRT, forcing, TRT, Smagorinsky), the walls, periodic y, the ports, the inlet profile, the inlet schedule, the mask, the header.
 #pragma once
 #include <algorithm>
 #include <array>

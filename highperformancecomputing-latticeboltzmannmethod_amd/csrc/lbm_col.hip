@@ -30,6 +30,11 @@ static_assert(LBM_AR_BASE == AR_STRICT_TRT && collision_model(AR_STRICT_MRT).uni
 LBM_COL_INST(LBM_COL_T, RK_STD, AR_STRICT_MRT);
 LBM_COL_INST(LBM_COL_T, RK_STD, AR_STRICT_MRT | 1);
 #endif
+#if LBM_AR_BASE == 0      // ... and BGK's the outlet sponge
+static_assert(LBM_AR_BASE == AR_STRICT && collision_model(AR_STRICT_SPONGE).unit == AR_STRICT);
+LBM_COL_INST(LBM_COL_T, RK_STD, AR_STRICT_SPONGE);
+LBM_COL_INST(LBM_COL_T, RK_STD, AR_STRICT_SPONGE | 1);
+#endif
 #elif defined(LBM_COL_TALL)
 LBM_COL_INST(float, RK_TALL, AR_STRICT | LBM_COL_TALL);
 #elif defined(LBM_COL_PARK)

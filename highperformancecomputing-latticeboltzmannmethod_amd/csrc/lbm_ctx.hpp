@@ -344,6 +344,9 @@ struct lbm_ctx {
     int sched_mode = 0;
     unsigned long long sched_digest = 0;
     void* d_sched = nullptr;
+    // The outlet sponge (lbm_set_sponge): the rate of every column, (T)(1 / tau_x), nx elements, uploaded by lbm_initialise on a sponge
+    // context (KArgs::wp_x; nullptr on every other). Strips cut rows: every strip holds the whole table.
+    void* d_wpx = nullptr;
     void* d_urow0 = nullptr;
     std::vector<double> h_urow;
     bool has_sched() const { return !sched.empty(); }
@@ -370,10 +373,10 @@ struct lbm_ctx {
     int arith = 0;       // collision arithmetic: 0 strict IEEE op-by-op (bit-identical to the oracle), 1 contracted (FMA +
                          // one reciprocal, as the reference's -ffast-math -mfma build permits); see lbm_kernels.hpp Arith
     int collision = 0;   // the collision model, the `base` of its row in collision_models (lbm_plan.hpp): 0 BGK, AR_STRICT_LES (lbm_set_smagorinsky),
-                         // AR_STRICT_TRT (lbm_set_trt), AR_STRICT_FORCED (lbm_set_forcing), AR_STRICT_MRT (lbm_set_mrt); collision | arith is the Arith value of every step kernel
+                         // AR_STRICT_TRT (lbm_set_trt), AR_STRICT_FORCED (lbm_set_forcing), AR_STRICT_MRT (lbm_set_mrt), AR_STRICT_SPONGE (lbm_set_sponge); collision | arith is the Arith value of every step kernel
                          // the context launches
-    double collision_param = 0.0;   // ... and the model's parameter: Cs > 0, the magic parameter > 0, Fx of the driving force, MRT's bulk rate; BGK: 0
-    double collision_param2 = 0.0;  // ... and its second one where the model has two (collision_models: nparam): Fy, MRT's magic parameter
+    double collision_param = 0.0;   // ... and the model's parameter: Cs > 0, the magic parameter > 0, Fx of the driving force, MRT's bulk rate, the sponge's width; BGK: 0
+    double collision_param2 = 0.0;  // ... and its second one where the model has two (collision_models: nparam): Fy, MRT's magic parameter, the sponge's tau_end
     int num_cus = 256;   // compute units of the device (what counts as a small grid: one round of blocks)
     int loopback = 0;    // TEST ONLY: the strip is its own north and south neighbour (exercises the overlap choreography):
                          // 1 = device copies, 2 = RCCL send/recv to self on a one-rank communicator

@@ -460,7 +460,7 @@ void lbm_destroy(lbm_ctx* c) {
     c->pool.reset();
     void* ptrs[] = {c->buf[0], c->buf[1], c->scratch, c->d_macro, c->d_maxbits, c->d_unstable, c->d_tbase, c->d_solid_count, c->d_feq,
                     c->d_force_now, c->force_log.d, c->d_halo, c->d_red, (void*)c->mview.bits, (void*)c->mview.sat, c->d_fpart,
-                    c->d_urow, c->d_feqrow, c->d_sched, c->d_urow0, c->d_stats, c->d_labels, c->d_body_box, c->d_body_chunks, c->d_body_first, c->d_body_part,
+                    c->d_urow, c->d_feqrow, c->d_sched, c->d_wpx, c->d_urow0, c->d_stats, c->d_labels, c->d_body_box, c->d_body_chunks, c->d_body_first, c->d_body_part,
                     c->d_body_now, c->body_log.d, c->frames.d, c->d_probe_table, c->probes.d};
     for (void* q : ptrs)
         if (q) (void)hipFree(q);
@@ -497,6 +497,36 @@ int set_collision(lbm_ctx* c, int base, double value, const char* what, bool tal
     else if (c->collision == base) { c->collision = AR_STRICT; c->collision_param = 0.0; c->collision_param2 = 0.0; }
     return LBM_OK;
 }
+// ---- the outlet sponge (lbm_set_sponge) ----
+// The relaxation time of column x: tau up to x0 = nx - 1 - width, then tau + (tau_end - tau) s^2 with s = (x - x0) / width, every
+// operation in double and in this order (no contraction: the Python sponge_tau forms the same bits).
+double sponge_tau_at(int nx, double tau, int width, double tau_end, int x) {
+#pragma clang fp contract(off)
+    const int x0 = nx - 1 - width;
+    if (width <= 0 || x <= x0) return tau;
+    const double s = (double)(x - x0) / (double)width;
+    const double s2 = s * s;
+    const double rise = (tau_end - tau) * s2;
+    return tau + rise;
+}
+double sponge_tau_of(const lbm_ctx* c, int x) {
+    const bool on = c->collision == AR_STRICT_SPONGE;
+    return sponge_tau_at(c->nx, c->p.tau, on ? (int)c->collision_param : 0, c->collision_param2, x);
+}
+// the rate of column x as the kernels see it, (double)(T)(1 / tau_x)
+double sponge_rate_at(const lbm_ctx* c, int x) {
+    const double wp = 1.0 / sponge_tau_of(c, x);
+    return c->esize == 4 ? (double)(float)wp : wp;
+}
+// lbm_initialise on a sponge context: the table KArgs::wp_x of all nx columns, cast once; no table on any other context
+int upload_sponge(lbm_ctx* c) {
+    if (c->d_wpx) { HIPCHK(hipFree(c->d_wpx)); c->d_wpx = nullptr; }
+    if (c->collision != AR_STRICT_SPONGE) return LBM_OK;
+    std::vector<double> wp((size_t)c->nx);
+    for (int x = 0; x < c->nx; ++x) wp[(size_t)x] = 1.0 / sponge_tau_of(c, x);
+    HIPCHK(hipMalloc(&c->d_wpx, wp.size() * c->esize));
+    return upload_rows(c, c->d_wpx, wp.data(), wp.size());
+}
 }  // namespace
 
 int lbm_initialise(lbm_ctx* c, int* solid_count_out) {
@@ -512,7 +542,8 @@ int lbm_initialise(lbm_ctx* c, int* solid_count_out) {
     HIPCHK(hipSetDevice(c->device));
     if (c->periodic_y) { if (int rc = prepare_periodic(c)) return rc; }
     if (c->has_sched()) { if (int rc = prepare_schedule(c)) return rc; }
-    { int wr = wait_stream(c, c->stream, "compute stream (lbm_initialise)"); if (wr) return wr; }        // (re-)initialisation starts from quiet streams
+    { int wr = wait_stream(c, c->stream, "compute stream (lbm_initialise)"); if (wr) return wr; }
+    if (int rc = upload_sponge(c)) return rc;       // (behind the wait: a launch in flight may read the table this replaces)        // (re-)initialisation starts from quiet streams
     { int wr = wait_stream(c, c->comm_stream, "exchange stream (lbm_initialise)"); if (wr) return wr; }
     { int wr = wait_stream(c, c->split_stream, "second compute stream (lbm_initialise)"); if (wr) return wr; }
     c->split_i = 0;
@@ -966,6 +997,33 @@ int lbm_get_mrt(const lbm_ctx* c, double* bulk_rate, double* magic) {
     return LBM_OK;
 }
 
+int lbm_set_sponge(lbm_ctx* c, int width, double tau_end) {
+    if (!c) return fail(LBM_ERR_ARG, "lbm_set_sponge: null context");
+    if (c->initialised) return fail(LBM_ERR_ARG, "lbm_set_sponge must be called before lbm_initialise");
+    if (width < 0 || width > c->nx - 1)
+        return fail(LBM_ERR_ARG, "lbm_set_sponge: width = %d (0 .. nx - 1 = %d only: column 0 keeps tau)", width, c->nx - 1);
+    if (width == 0) return set_collision(c, AR_STRICT_SPONGE, 0.0, "lbm_set_sponge:", true, 0.0);
+    if (!std::isfinite(tau_end) || !(tau_end > 0.5)) return fail(LBM_ERR_ARG, "lbm_set_sponge: tau_end = %g (finite values above 0.5 only)", tau_end);
+    if (!(c->p.tau > 0.5)) return fail(LBM_ERR_ARG, "lbm_set_sponge: tau = %g (the sponge's rates need tau > 0.5)", c->p.tau);
+    return set_collision(c, AR_STRICT_SPONGE, (double)width, "lbm_set_sponge: (width, tau_end) =", true, tau_end);
+}
+
+int lbm_get_sponge(const lbm_ctx* c, int* width, double* tau_end) {
+    if (!c) return fail(LBM_ERR_ARG, "lbm_get_sponge: null context");
+    const bool on = c->collision == AR_STRICT_SPONGE;
+    if (width) *width = on ? (int)c->collision_param : 0;
+    if (tau_end) *tau_end = on ? c->collision_param2 : 0.0;
+    return LBM_OK;
+}
+
+int lbm_get_sponge_rate(const lbm_ctx* c, int x, double* wp_out) {
+    if (!c) return fail(LBM_ERR_ARG, "lbm_get_sponge_rate: null context");
+    if (!wp_out) return fail(LBM_ERR_ARG, "lbm_get_sponge_rate: null pointer");
+    if (x < 0 || x >= c->nx) return fail(LBM_ERR_ARG, "lbm_get_sponge_rate: x = %d (columns 0 .. %d only)", x, c->nx - 1);
+    *wp_out = sponge_rate_at(c, x);
+    return LBM_OK;
+}
+
 int lbm_set_wall(lbm_ctx* c, int side, int kind, double velocity) {
     if (!c) return fail(LBM_ERR_ARG, "lbm_set_wall: null context");
     if (c->initialised) return fail(LBM_ERR_ARG, "lbm_set_wall must be called before lbm_initialise");
@@ -1289,6 +1347,10 @@ int lbm_set_option(lbm_ctx* c, const char* key, long value) {
         if (value != 0 && value != 1) return fail(LBM_ERR_ARG, "lbm_set_periodic_y: on = %ld (0 or 1 only)", value);
         return lbm_set_periodic_y(c, (int)value);
     }
+    else if (k == "sponge") {       // lbm_set_sponge by its key, width `value` with tau_end 1.5 (the dry runs take options only)
+        if (value < INT_MIN || value > INT_MAX) return fail(LBM_ERR_ARG, "sponge must be a width that an int holds");
+        return lbm_set_sponge(c, (int)value, 1.5);
+    }
     else if (k == "nt") c->use_nt = (int)value ? 1 : 0;
     else if (k == "ntl") c->use_ntl = (int)value ? 1 : 0;
     else if (k == "fuse") { if (value < 1 || value > 4) return fail(LBM_ERR_ARG, "fuse must be 1, 2, 3 or 4 (4: tile kernel, no strip faces)"); c->fuse = (int)value; c->deep = 0; }
@@ -1468,7 +1530,8 @@ int lbm_debug_body_chunks(const unsigned char* labels, int nx, int ny, int y_sta
 
 /* TEST HOOK (no device needed): the candidates lbm_initialise would time for a whole-domain context of this grid, one per line:
  * "name|lbm_set_option pairs|dominant kernel|iterations per launch". arith: 0 / 1, 2 / 3 for a Smagorinsky (LES) context, 4 / 5 for a TRT one,
- * 8 / 9 for one with a driving force (lbm_set_forcing), 16 / 17 for an MRT one (lbm_set_mrt). */
+ * 8 / 9 for one with a driving force (lbm_set_forcing), 16 / 17 for an MRT one (lbm_set_mrt), 32 / 33 for one with an outlet sponge
+ * (lbm_set_sponge). */
 int lbm_debug_plan_candidates(int nx, int ny, int precision, int arith, int num_cus, char* out, int cap) {
     if (!out || cap < 1 || nx < 1 || ny < 1) return fail(LBM_ERR_ARG, "bad argument");
     PlanQuery q;
@@ -1749,6 +1812,7 @@ int lbm_debug_collision_setters(double tau, int precision, const char* options, 
             case 3: rc[k] = lbm_set_mrt(c, v1[k], v2[k]); break;
             case 4: c->initialised = true; rc[k] = LBM_OK; break;
             case 5: rc[k] = refuse_deep(c, c->collision, c->deep, true); break;
+            case 6: rc[k] = lbm_set_sponge(c, (int)v1[k], v2[k]); break;
             default: bad = LBM_ERR_ARG; continue;
         }
         if (rc[k]) text += lbm_last_error();
@@ -1757,10 +1821,25 @@ int lbm_debug_collision_setters(double tau, int precision, const char* options, 
     collision3[0] = c->collision;
     (void)lbm_get_mrt(c, &collision3[1], &collision3[2]);
     delete c;
-    if (bad) return fail(LBM_ERR_ARG, "lbm_debug_collision_setters: setter 0..5 only");
+    if (bad) return fail(LBM_ERR_ARG, "lbm_debug_collision_setters: setter 0..6 only");
     if ((int)text.size() + 1 > cap) return fail(LBM_ERR_ARG, "lbm_debug_collision_setters: buffer too small (%zu bytes needed)", text.size() + 1);
     memcpy(texts, text.c_str(), text.size() + 1);
     return LBM_OK;
+}
+
+/* TEST HOOK (no device needed): lbm_set_sponge on a context no device knows, and the rate of every column: see include/lbm_hip.h. */
+int lbm_debug_sponge_rates(int nx, double tau, int precision, int width, double tau_end, double* pair2, double* rates) {
+    if (!pair2 || !rates || nx < 1) return fail(LBM_ERR_ARG, "lbm_debug_sponge_rates: null pointer or nx < 1");
+    lbm_ctx* c = choreo_fake_ctx(nx, 64, 0, 64, precision, 0);
+    c->p.tau = tau;
+    const int rc = lbm_set_sponge(c, width, tau_end);
+    const std::string text = rc ? lbm_last_error() : "";
+    int w = 0;
+    (void)lbm_get_sponge(c, &w, &pair2[1]);
+    pair2[0] = w;
+    for (int x = 0; x < nx; ++x) (void)lbm_get_sponge_rate(c, x, &rates[x]);
+    delete c;
+    return rc ? fail(rc, "%s", text.c_str()) : LBM_OK;
 }
 
 /* TEST HOOK (no device needed): every rank of a multi-process strip run issues its launch groups DRY (as lbm_debug_choreography does for one

@@ -167,6 +167,9 @@ __global__ void __launch_bounds__(NW * 64, (col_min_waves<T, NW, AR>())) k_stepc
         // level 1 of the parked form takes the top row first and parks it: the other rows' collisions then run over R - 1 rows of state
         auto first_top = [](int jj) { return PARK ? (jj == 0 ? R - 1 : jj - 1) : jj; };
         const bool col_in = (x >= 0 && x < a.nx);
+        // (sponge kernels) the rate of the thread's column, the same at every level: one load per launch, on both paths. A lane without a
+        // column takes the nearest column's (column_rate clamps the index into the table); nothing it computes is counted or stored
+        const T wpx = column_rate<T, AR>(a, x);
         // bit j: the thread's cell of row j is solid. The thread <-> cell map is fixed for all D levels, so the geometry is looked
         // up once, here, and serves every level and the store predicate (block-uniform branch: only tiles near a solid cell)
         unsigned sbits = 0;
@@ -223,7 +226,7 @@ __global__ void __launch_bounds__(NW * 64, (col_min_waves<T, NW, AR>())) k_stepc
             for (int jj = 0; jj < R; ++jj) {
                 const int j = first_top(jj);
                 bad |= any_unstable(g[j]);
-                collide<T, AR>(g[j], a);
+                collide<T, AR>(g[j], a, wpx);
                 if constexpr (PARK) if (jj == 0) park(g[j], 0);
             }
         } else {
@@ -270,7 +273,7 @@ __global__ void __launch_bounds__(NW * 64, (col_min_waves<T, NW, AR>())) k_stepc
                 const int j = first_top(jj);
                 const int yg = a.y_start + Yr + ry0 + j;
                 if ((rld >> j) & 1u) {
-                    cell_update_with<T, AR, true>(a, g[j], x, yg, 0, (sbits >> j) & 1u, fr.near_solid, col_in, bad, [&]() { return u_sh[w][j]; });
+                    cell_update_with<T, AR, true>(a, g[j], x, yg, 0, (sbits >> j) & 1u, fr.near_solid, col_in, bad, wpx, [&]() { return u_sh[w][j]; });
 #pragma unroll
                     for (int i = 0; i < Q; ++i) g[j][i] = col_in ? g[j][i] : T(0);
                 }
@@ -316,11 +319,11 @@ __global__ void __launch_bounds__(NW * 64, (col_min_waves<T, NW, AR>())) k_stepc
                 bool store = L == D && lane >= HW && lane < 64 - HW && ry >= HW && ry < H - HW;
                 if (LEAN) {
                     badl |= unstable_if(f, valid);
-                    collide<T, AR>(f, a);
+                    collide<T, AR>(f, a, wpx);
                 } else {
                     // (a lane without a column: as at level 1 — not counted, not stored, its zeros back)
                     cell_update_with<T, AR, true>(a, f, x, yg, L - 1, (sbits >> j) & 1u, fr.near_solid,
-                                                  valid && col_in && y <= y_end + HW - L, badl, [&]() { return u_sh[w][j]; });
+                                                  valid && col_in && y <= y_end + HW - L, badl, wpx, [&]() { return u_sh[w][j]; });
 #pragma unroll
                     for (int i = 0; i < Q; ++i) f[i] = col_in ? f[i] : T(0);
                     store = store && col_in && y < y_end && !((sbits >> j) & 1u);

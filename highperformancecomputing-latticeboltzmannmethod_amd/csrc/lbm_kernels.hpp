@@ -41,6 +41,7 @@
 //     store P_{t+1}
 // Algorithmic traffic: 9 loads + 9 stores per lattice update = 144 B (fp64) / 72 B (fp32). HBM-bound; no MFMA.
 #pragma once
+#include <cstddef>
 #include <utility>
 #include <hip/hip_runtime.h>
 
@@ -129,6 +130,9 @@ inline PortK<T> port_ks(double west_value, int east_kind, double east_value) {
 }
 
 
+template <int N> struct KPad { char b[N]; };
+template <> struct KPad<0> {};
+
 template <typename T>
 struct KArgs {
     // The uniform driving force (lbm_set_forcing; Guo, Zheng and Shi 2002): g = (1 - 1/(2 tau)) F, the factor of the source term, and
@@ -141,9 +145,13 @@ struct KArgs {
     // included, each of them keeps its loads and its register allocation (profiles/forcing/README.md).
     // The values of the two ports (lbm_set_port; the kinds ride in `walls`) stand in what was padding of this block, for the same
     // reason: no field of KArgs or K2Extra moves. Launch-uniform: read inside the inlet / outlet branches of apply_bcs only.
+    // The outlet sponge's table (lbm_set_sponge) takes the last eight bytes of the block, which were padding too: 1/tau_x of every column of
+    // the domain, nx elements, each formed on the host in double and cast once; nullptr on every other context. Read only by the sponge
+    // instantiations (AR_STRICT_SPONGE / AR_CONTRACTED_SPONGE), through column_rate.
     T frc_gx, frc_gy, frc_hx, frc_hy;
     PortK<T> pk;
-    char frc_pad[64 - 7 * sizeof(T)];
+    [[no_unique_address]] KPad<56 - 7 * sizeof(T)> frc_pad;
+    const T* wp_x;
     const T* src;      // plane 0 of the buffer read  (P_t)
     T* dst;            // plane 0 of the buffer written (P_{t+1})
     long plane;        // elements per plane
@@ -189,6 +197,8 @@ struct KArgs {
     // without one. Launch-uniform: tested and read inside the inlet branch of apply_bcs only.
     const int* sched;
 };
+static_assert(offsetof(KArgs<double>, wp_x) == 56 && offsetof(KArgs<double>, src) == 64 && offsetof(KArgs<float>, wp_x) == 56 &&
+              offsetof(KArgs<float>, src) == 64, "the block in front of KArgs is 64 bytes, the sponge's table its last eight");
 
 // Row handled by blockIdx.y. Blocks are dispatched roughly in index order; walking the rows in the opposite
 // direction on every other step makes a step start on the rows the previous step wrote last, which are the
@@ -371,13 +381,18 @@ __device__ __forceinline__ void bcs_at(const KArgs<T>& a, T (&f)[Q], int x, int 
 //                 and odd parts of each pair, with the even parts of the two axis pairs (and of the two diagonal pairs) split into their
 //                 half sum, relaxed with the launch-uniform bulk rate sb like the rest population, and their half difference, relaxed
 //                 with 1/tau. Separate instantiations for the same reason. MRT excludes LES, TRT and forcing: of 16 to 31 there are 16, 17.
+//   AR_STRICT_SPONGE / AR_CONTRACTED_SPONGE  BGK's two arithmetic modes, operation for operation, with the rate of the cell's COLUMN
+//                 (lbm_set_sponge: KArgs::wp_x, column_rate) in place of the global 1/tau. Separate instantiations for the same reason.
+//                 The sponge excludes LES, TRT, forcing and MRT: of 32 to 63 there are 32, 33.
 enum Arith { AR_STRICT = 0, AR_CONTRACTED = 1, AR_STRICT_LES = 2, AR_CONTRACTED_LES = 3, AR_STRICT_TRT = 4, AR_CONTRACTED_TRT = 5,
-             AR_STRICT_FORCED = 8, AR_CONTRACTED_FORCED = 9, AR_STRICT_MRT = 16, AR_CONTRACTED_MRT = 17 };
+             AR_STRICT_FORCED = 8, AR_CONTRACTED_FORCED = 9, AR_STRICT_MRT = 16, AR_CONTRACTED_MRT = 17, AR_STRICT_SPONGE = 32,
+             AR_CONTRACTED_SPONGE = 33 };
 constexpr bool ar_contracted(int ar) { return (ar & 1) != 0; }
 constexpr bool ar_les(int ar) { return (ar & 2) != 0; }
 constexpr bool ar_trt(int ar) { return (ar & 4) != 0; }
 constexpr bool ar_forced(int ar) { return (ar & 8) != 0; }
 constexpr bool ar_mrt(int ar) { return (ar & 16) != 0; }
+constexpr bool ar_sponge(int ar) { return (ar & 32) != 0; }
 constexpr int ar_of(bool contracted, bool les, bool trt = false) { return (contracted ? 1 : 0) | (les ? 2 : 0) | (trt ? 4 : 0); }
 
 __device__ __forceinline__ double fma_t(double a, double b, double c) { return __builtin_fma(a, b, c); }
@@ -703,12 +718,24 @@ __device__ __forceinline__ void bgk_collide(T (&f)[Q], T tau_inv, T les_tau = T(
 // The collision of the step kernels: BGK with the global 1/tau, (LES modes) the Smagorinsky rate of each cell, or (TRT modes) 1/tau
 // for the even and trt_wm for the odd part of each pair (contracted: the two folded into trt_wa, trt_wb), or (MRT modes) TRT's parts with
 // the trace of the even parts relaxed at the bulk rate (KArgs: the TRT slots and frc_gx, frc_gy)
+// The rate of column x on a sponge context (the sponge modes only; every other mode gets a zero that nothing reads). The index is
+// clamped into the table: the lanes and region cells that have no column (x < 0, x >= nx: a region's overhang, a ragged nx, nx < 64)
+// compute on zeros or garbage that is never stored, with the rate of the nearest column, and read nothing outside [0, nx).
 template <typename T, int AR>
-__device__ __forceinline__ void collide(T (&f)[Q], const KArgs<T>& a) {
+__device__ __forceinline__ T column_rate(const KArgs<T>& a, int x) {
+    if constexpr (ar_sponge(AR)) return a.wp_x[x < 0 ? 0 : (x < a.nx ? x : a.nx - 1)];
+    else return T(0);
+}
+
+// ... `wpx`: column_rate of the cell's column (read by the sponge modes only)
+template <typename T, int AR>
+__device__ __forceinline__ void collide(T (&f)[Q], const KArgs<T>& a, T wpx) {
     static_assert(!(ar_les(AR) && ar_trt(AR)), "TRT and LES exclude each other");
     static_assert(!(ar_forced(AR) && (ar_les(AR) || ar_trt(AR))), "forcing excludes LES and TRT");
     static_assert(!(ar_mrt(AR) && (ar_les(AR) || ar_trt(AR) || ar_forced(AR))), "MRT excludes LES, TRT and forcing");
-    if constexpr (ar_mrt(AR)) bgk_collide<T, AR>(f, a.tau_inv, a.trt_wm, a.trt_wa, a.trt_wb, a.frc_gx, a.frc_gy);
+    static_assert(!(ar_sponge(AR) && (AR & 30) != 0), "the sponge excludes LES, TRT, forcing and MRT");
+    if constexpr (ar_sponge(AR)) bgk_collide<T, AR>(f, wpx);
+    else if constexpr (ar_mrt(AR)) bgk_collide<T, AR>(f, a.tau_inv, a.trt_wm, a.trt_wa, a.trt_wb, a.frc_gx, a.frc_gy);
     else if constexpr (ar_forced(AR)) bgk_collide<T, AR>(f, a.tau_inv, a.frc_gx, a.frc_gy, a.frc_hx, a.frc_hy);
     else if constexpr (ar_trt(AR)) bgk_collide<T, AR>(f, a.tau_inv, a.trt_wm, a.trt_wa, a.trt_wb);
     else if constexpr (ar_les(AR)) bgk_collide<T, AR>(f, T(0), a.les_tau, a.les_tau2, a.les_c);
@@ -785,7 +812,7 @@ __global__ void __launch_bounds__(256) k_step_site(const KArgs<T> a) {
         }
     } else {
         if (solid) return;   // collision skips solid cells: they keep w_i for ever (LBMSolver.h:92, N4)
-        collide<T, AR>(f, a);
+        collide<T, AR>(f, a, column_rate<T, AR>(a, x));
     }
 #pragma unroll
     for (int i = 0; i < Q; ++i) {
@@ -819,14 +846,15 @@ template <typename T> struct K2Extra {
 // One general cell of level lvl + 1 (any cell of a non-LEAN path): BCs of that level's iteration unless solid, the stability test where `count`, the
 // collision; a solid cell keeps w_i (its collision result is discarded). `near_solid` is block-uniform: tiles far from every
 // solid cell skip the select. BRANCH_FREE: the stability test is unstable_if (k_stepc_col, whose garbage cells are masked).
-// cell_update_with: the same with the row's inlet velocity from `row_u` (bcs_at_with).
+// cell_update_with: the same with the row's inlet velocity from `row_u` (bcs_at_with) and the column's rate `wpx` (column_rate; x may
+// lie outside the domain here).
 template <typename T, int AR, bool BRANCH_FREE = false, typename U>
 __device__ __forceinline__ void cell_update_with(const KArgs<T>& a, T (&f)[Q], int x, int yg, int lvl, bool solid, bool near_solid,
-                                                 bool count, bool& bad, U&& row_u) {
+                                                 bool count, bool& bad, T wpx, U&& row_u) {
     if (!solid) bcs_at_with(a, f, x, yg, lvl, row_u);
     if (BRANCH_FREE) bad |= unstable_if(f, count);
     else if (count) bad |= any_unstable(f);
-    collide<T, AR>(f, a);
+    collide<T, AR>(f, a, wpx);
     if (near_solid) {
 #pragma unroll
         for (int i = 0; i < Q; ++i) f[i] = solid ? wgt<T>(i) : f[i];
@@ -835,7 +863,7 @@ __device__ __forceinline__ void cell_update_with(const KArgs<T>& a, T (&f)[Q], i
 template <typename T, int AR, bool BRANCH_FREE = false>
 __device__ __forceinline__ void cell_update_as(const KArgs<T>& a, T (&f)[Q], int x, int yg, int lvl, bool solid, bool near_solid,
                                                bool count, bool& bad) {
-    cell_update_with<T, AR, BRANCH_FREE>(a, f, x, yg, lvl, solid, near_solid, count, bad, [&]() { return a.u_row[yg]; });
+    cell_update_with<T, AR, BRANCH_FREE>(a, f, x, yg, lvl, solid, near_solid, count, bad, column_rate<T, AR>(a, x), [&]() { return a.u_row[yg]; });
 }
 // ... with the geometry looked up here (block-uniform branch: only tiles near a solid cell)
 template <typename T, int AR>
@@ -852,7 +880,7 @@ __device__ __forceinline__ bool cell_update_last(const KArgs<T>& a, T (&f)[Q], i
     if (!solid) bcs_at(a, f, x, yg, lvl);
     bad |= any_unstable(f);
     if (solid) return false;
-    collide<T, AR>(f, a);
+    collide<T, AR>(f, a, column_rate<T, AR>(a, x));
     return true;
 }
 
@@ -1114,7 +1142,7 @@ __device__ __forceinline__ void step_tile(const KArgs<T>& a, const K2Extra<T>& e
             if (LEAN) {
                 fr.load(f, fr.at(ry, rx), fr.src_off(a, Y0 - HW, X0 - HW));
                 bad |= any_unstable(f);
-                collide<T, AR>(f, a);
+                collide<T, AR>(f, a, column_rate<T, AR>(a, X0 + rx - HW));
             } else {
                 const int x = X0 + rx - HW, y = Y0 + ry - HW;
                 const int yg = a.y_start + y;
@@ -1175,7 +1203,7 @@ __device__ __forceinline__ void step_tile(const KArgs<T>& a, const K2Extra<T>& e
                         for (int i = 0; i < Q; ++i) f[i] = g[k][i];
                     }
                     badl |= any_unstable(f);
-                    collide<T, AR>(f, a);
+                    collide<T, AR>(f, a, column_rate<T, AR>(a, X0 + rx - HW));
                 } else {
                     const int x = X0 + rx - HW, y = Y0 + ry - HW;
                     const int yg = a.y_start + y;
@@ -1209,7 +1237,7 @@ __device__ __forceinline__ void step_tile(const KArgs<T>& a, const K2Extra<T>& e
             for (int i = 0; i < Q; ++i) f[i] = lds[i][ly + HW - cy(i)][lx + HW - cx(i)];
             if (LEAN) {
                 bad |= any_unstable(f);
-                collide<T, AR>(f, a);
+                collide<T, AR>(f, a, column_rate<T, AR>(a, x));
                 fr.store(f, fr.at(ly, lx), fr.dst_off(a, Y0, X0), e.nt != 0);
             } else if (cell_update_last<T, AR>(a, f, x, a.y_start + y, D - 1, fr.near_solid, bad)) store_cell(a, f, x, y, e.nt != 0);
         }

@@ -100,6 +100,7 @@ KArgs<T> make_kargs(const lbm_ctx* c, int src, int dst, int t) {
         a.frc_gx = (T)c->collision_param;
         a.frc_gy = (T)(0.25 * (c->collision_param * c->p.tau - 1.0));
     }
+    a.wp_x = static_cast<const T*>(c->d_wpx);       // (lbm_initialise: upload_sponge; nullptr without a sponge)
     return a;
 }
 

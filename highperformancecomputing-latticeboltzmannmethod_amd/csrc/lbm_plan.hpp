@@ -35,12 +35,26 @@ constexpr bool PARK_FORCED = true;
 // per SIMD); on the tall fp64 regions they spilled 7 to 9 VGPRs into 24 bytes of scratch per lane when they were built, so the row
 // withholds them (profiles/mrt/README.md). No tall fp32 regions, like every model but BGK.
 constexpr bool PARK_MRT = false;
+// The outlet sponge (lbm_set_sponge): BGK with the rate of the cell's column. Its row starts as MRT's did, with neither kind of tall
+// region: the fp64 64x40 instantiations have not been built and read for scratch, so the row withholds them (profiles/sponge/README.md).
+constexpr bool PARK_SPONGE = false;
 // `nparam`: the doubles of the model's parameter (the force has two components; lbm_ctx::collision_param, collision_param2). A model whose
 // ckpt_bit lies above the bits of the walls and the inlet schedule stands behind them in a checkpoint, as its bit says
 // (lbm_ckpt.hpp makes one row of its field table from each model that has a bit).
 // `unit`: the base of the model in whose objects the model's kernels are instantiated (build.py builds one set of objects per unit;
-// lbm_step_k.hip and lbm_col.hip instantiate a unit's riders beside it); -1: its own. MRT shares TRT's pair code and rides in TRT's objects.
+// lbm_step_k.hip and lbm_col.hip instantiate a unit's riders beside it); -1: its own. MRT shares TRT's pair code and rides in TRT's objects,
+// the outlet sponge is BGK's code with another rate and rides in BGK's.
 struct CollisionModel { int base; const char* noun; bool tall, park; unsigned long long ckpt_bit; const char *param, *value, *none; int nparam = 1; int unit = -1; };
+// (the sponge's row, member by member: the width is carried as a double in front of tau_end)
+constexpr CollisionModel sponge_model() {
+    CollisionModel m{};
+    m.base = AR_STRICT_SPONGE; m.noun = "outlet sponge";
+    m.tall = false; m.park = PARK_SPONGE;
+    m.ckpt_bit = 2048;
+    m.param = "sponge"; m.value = "(width, tau_end) = "; m.none = "";
+    m.nparam = 2; m.unit = AR_STRICT;
+    return m;
+}
 constexpr CollisionModel collision_models[] = {
     {AR_STRICT, "BGK", true, true, 0, "", "", ""},
     {AR_STRICT_LES, "Smagorinsky (LES)", false, PARK_LES, 4, "Smagorinsky constant", "Cs = ", " (BGK)"},
@@ -48,6 +62,7 @@ constexpr CollisionModel collision_models[] = {
     {AR_STRICT_FORCED, "forced BGK (Guo forcing)", false, PARK_FORCED, 64, "forcing", "F = ", "", 2},
     {.base = AR_STRICT_MRT, .noun = "multiple-relaxation-time (MRT)", .tall = false, .park = PARK_MRT, .ckpt_bit = 1024, .param = "MRT parameters",
      .value = "(bulk rate, magic) = ", .none = "", .nparam = 2, .unit = AR_STRICT_TRT},
+    sponge_model(),
 };
 // the row of an Arith value, strict or contracted
 constexpr const CollisionModel& collision_model(int arith) {
@@ -243,7 +258,7 @@ inline std::vector<Plan> plan_candidates(const PlanQuery& q, const Plan& fixed) 
 }
 
 // the dominant kernel of a plan, as rocprofv3 names it (minus "lbmk::" and blanks)
-// (arith: the kernels' Arith value, 0..5, 8, 9, 16, 17; the region shapes follow its strict / contracted half; the store policy is the row's)
+// (arith: the kernels' Arith value, 0..5, 8, 9, 16, 17, 32, 33; the region shapes follow its strict / contracted half; the store policy is the row's)
 inline std::string plan_kernel_name(int fuse, int deep, int pair_ty, int nt, int arith, int esize) {
     char name[96];
     const char* t = esize == 4 ? "float" : "double";

@@ -69,6 +69,11 @@ static_assert(LBM_AR_BASE == AR_STRICT_TRT && collision_model(AR_STRICT_MRT).uni
 LBM_STEP_K_INST(double, AR_STRICT_MRT)
 LBM_STEP_K_INST(float, AR_STRICT_MRT)
 #endif
+#if LBM_AR_BASE == 0      // ... and BGK's the outlet sponge
+static_assert(LBM_AR_BASE == AR_STRICT && collision_model(AR_STRICT_SPONGE).unit == AR_STRICT);
+LBM_STEP_K_INST(double, AR_STRICT_SPONGE)
+LBM_STEP_K_INST(float, AR_STRICT_SPONGE)
+#endif
 #undef LBM_STEP_K_INST
 
 }  // namespace lbmk

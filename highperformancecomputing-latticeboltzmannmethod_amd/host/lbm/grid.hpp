@@ -57,6 +57,7 @@ public:
             if (p.trt()) check(lbm_set_trt(c, p.trt_magic), "lbm_set_trt");
             if (p.forced()) check(lbm_set_forcing(c, p.forcing_x, p.forcing_y), "lbm_set_forcing");   // (every strip the same force)
             if (p.mrt()) check(lbm_set_mrt(c, p.mrt_bulk_rate, p.mrt_magic), "lbm_set_mrt");
+            if (p.sponge()) check(lbm_set_sponge(c, p.sponge_width, p.sponge_tau_end), "lbm_set_sponge");   // (every strip the same pair: strips cut rows)
             if (p.walled())      // every strip carries both walls; only the strips that hold row 0 / ny - 1 use them
                 for (int side = 0; side < 2; ++side) check(lbm_set_wall(c, side, p.wall_kind[side], p.wall_velocity[side]), "lbm_set_wall");
             if (p.ported())      // every strip carries both ports

@@ -326,6 +326,10 @@ private:
             f.put("mrt_bulk_rate,"); f.put(SimulationParams::shortest_text(p.mrt_bulk_rate).c_str()); f.put("\n");
             f.put("mrt_magic,"); f.put(SimulationParams::shortest_text(p.mrt_magic).c_str()); f.put("\n");
         }
+        if (p.sponge()) {                                                                                  // (sponge runs only, likewise)
+            f.put("sponge_width,"); f.put(std::to_string(p.sponge_width).c_str()); f.put("\n");
+            f.put("sponge_tau_end,"); f.put(SimulationParams::shortest_text(p.sponge_tau_end).c_str()); f.put("\n");
+        }
         if (p.periodic_y) f.put("periodic_y,1\n");                                                          // (periodic runs only; behind every other line)
         std::printf("  simulation_params.csv written\n");
     }

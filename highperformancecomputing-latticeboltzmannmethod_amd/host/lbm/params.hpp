@@ -68,6 +68,10 @@ struct SimulationParams {
     // bulk rate BULK, in (0, 2), is free of tau (lbm_set_mrt). Bulk rate 0 = plain BGK. Never together with smagorinsky_cs, trt_magic
     // or a force. tau keeps setting the shear viscosity.
     double mrt_bulk_rate = 0.0, mrt_magic = 0.0;
+    // Outlet sponge zone (lbm_solver --sponge WIDTH:TAU_END; not in the reference): over the last WIDTH columns the relaxation time rises
+    // from tau to TAU_END (lbm_set_sponge). Width 0 = none. Never together with smagorinsky_cs, trt_magic, a force or MRT.
+    int sponge_width = 0;
+    double sponge_tau_end = 0.0;
     // time-averaged statistics (lbm_solver --stats-start; not in the reference): the first step sampled, -1 = off. Samples are taken on
     // the device at the output_frequency cadence (lbm_stats_begin); the run ends with mean_fields.vtk / mean_fields.csv.
     int stats_start = -1;
@@ -105,6 +109,7 @@ struct SimulationParams {
     bool trt() const { return trt_magic > 0.0; }
     bool forced() const { return forcing_x != 0.0 || forcing_y != 0.0; }
     bool mrt() const { return mrt_bulk_rate != 0.0; }
+    bool sponge() const { return sponge_width > 0; }
     bool stats() const { return stats_start >= 0; }
     bool frames() const { return frame_stride > 0; }
     bool probes() const { return !probe_xy.empty(); }
@@ -160,6 +165,24 @@ struct SimulationParams {
         if (v[0] < 0.0 || v[0] >= 2.0) throw bad("has a bulk rate outside (0, 2)");
         if (v[0] != 0.0 && (!(v[1] > 0.0) || v[1] > 1.0)) throw bad("has a magic parameter outside (0, 1]");
         mrt_bulk_rate = v[0]; mrt_magic = v[0] != 0.0 ? v[1] : 0.0;
+    }
+    // WIDTH:TAU_END of --sponge: one token, a whole number >= 0 and a number parsed whole, TAU_END finite and above 0.5 beside a nonzero
+    // WIDTH (std::invalid_argument with the one-line message otherwise; the grid's bound on WIDTH is the caller's to check)
+    void set_sponge(const std::string& text) {
+        const auto bad = [&](const char* why) {
+            return std::invalid_argument("--sponge: '" + text + "' " + why + " (WIDTH:TAU_END: the columns of the zone, 0 .. nx - 1, and the relaxation time at the outlet, above 0.5)");
+        };
+        const size_t colon = text.find(':');
+        if (colon == std::string::npos || text.find(':', colon + 1) != std::string::npos) throw bad("is not a pair WIDTH:TAU_END");
+        const std::string part[2] = {text.substr(0, colon), text.substr(colon + 1)};
+        char* end = nullptr;
+        const long w = std::strtol(part[0].c_str(), &end, 10);
+        if (part[0].empty() || std::isspace((unsigned char)part[0][0]) || end == part[0].c_str() || *end != '\0') throw bad("has no whole number WIDTH");
+        if (w < 0 || w > 2147483647L) throw bad("has a width below 0 or beyond any grid");
+        const double t = std::strtod(part[1].c_str(), &end);
+        if (part[1].empty() || std::isspace((unsigned char)part[1][0]) || end == part[1].c_str() || *end != '\0') throw bad("has no number TAU_END");
+        if (w != 0 && (!std::isfinite(t) || !(t > 0.5))) throw bad("has a TAU_END that is not a finite number above 0.5");
+        sponge_width = (int)w; sponge_tau_end = w != 0 ? t : 0.0;
     }
     // a wall as the command line names it: "no-slip", "free-slip" or "moving:U"
     std::string wall_text(int side) const {

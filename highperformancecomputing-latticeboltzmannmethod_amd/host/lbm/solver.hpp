@@ -58,6 +58,9 @@ public:
         if (!opt_.quiet && params_.mrt())
             std::printf("  Collision: MRT collision, bulk rate = %s, magic = %s (the trace of the stress relaxes with the bulk rate; tau sets the shear viscosity)\n",
                         SimulationParams::shortest_text(params_.mrt_bulk_rate).c_str(), SimulationParams::shortest_text(params_.mrt_magic).c_str());
+        if (!opt_.quiet && params_.sponge())
+            std::printf("  Outlet sponge: the last %d columns, tau rising to %s at the outlet (the viscosity there is (tau_x - 0.5) / 3)\n", params_.sponge_width,
+                        SimulationParams::shortest_text(params_.sponge_tau_end).c_str());
         if (!opt_.quiet && params_.walled())
             std::printf("  Walls: south %s, north %s\n", params_.wall_banner(0).c_str(), params_.wall_banner(1).c_str());
         if (!opt_.quiet && params_.ported())

@@ -23,7 +23,7 @@ static void usage() {
               "           [--gpus N] [--strips N] [--rccl]\n"
               "           [--checkpoint FILE] [--restart FILE] [--obstacle-mask FILE.pgm] [--obstacle-bodies FILE.pgm]\n"
               "           [--inlet-profile parabolic|FILE] [--print-inlet-profile] [--smagorinsky CS] [--trt-magic LAMBDA]\n"
-              "           [--forcing FX,FY] [--mrt BULK,MAGIC]\n"
+              "           [--forcing FX,FY] [--mrt BULK,MAGIC] [--sponge WIDTH:TAU_END]\n"
               "           [--stats-start N] [--wall-south KIND] [--wall-north KIND] [--walls KIND]\n"
               "           [--inlet velocity|pressure:RHO] [--outlet pressure:RHO|velocity:U]\n"
               "           [--frame-stride K] [--probes FILE] [--probe-line x0 y0 x1 y1 n]\n"
@@ -68,6 +68,11 @@ static void usage() {
               "grows with 1/BULK - 1/2 and pressure waves of an impulsive start die out; the shear viscosity stays (tau - 0.5) / 3.\n"
               "BULK = 1/tau is --trt-magic MAGIC; BULK 0: plain BGK. Needs tau > 0.5; cannot be combined with --smagorinsky, --trt-magic\n"
               "or --forcing.\n"
+              "--sponge WIDTH:TAU_END: outlet sponge zone (one token): over the last WIDTH columns (1 .. nx-1) the relaxation time rises\n"
+              "smoothly from tau to TAU_END > 0.5, tau_x = tau + (TAU_END - tau) s^2 with s the fraction of the zone behind the column, so\n"
+              "that vortices and pressure waves are diffused before they meet the outlet, which reflects them. The viscosity inside the\n"
+              "zone is (tau_x - 0.5) / 3: results taken there are not those of the fluid. WIDTH 0: none. Needs tau > 0.5; cannot be\n"
+              "combined with --smagorinsky, --trt-magic, --forcing or --mrt.\n"
               "--wall-south KIND / --wall-north KIND: the bottom (row 0) / top (row ny-1) wall, KIND = no-slip (the default: on-node\n"
               "bounce-back) | free-slip (specular reflection: no boundary layer, for unconfined flow past a body) | moving:U (a wall\n"
               "sliding at the tangential velocity U, |U| < 1: Couette flow, a lid, a moving ground). --walls KIND sets both. The\n"
@@ -111,6 +116,7 @@ int main(int argc, char** argv) {
     const char* trt_magic = nullptr;
     const char* forcing = nullptr;
     const char* mrt = nullptr;
+    const char* sponge = nullptr;
     const char* stats_start = nullptr;
     const char* frame_stride = nullptr;
     std::vector<LBM::ProbePoint> probe_points;
@@ -154,6 +160,7 @@ int main(int argc, char** argv) {
         else if (k == "--trt-magic") trt_magic = val();
         else if (k == "--forcing") forcing = val();
         else if (k == "--mrt") mrt = val();
+        else if (k == "--sponge") sponge = val();
         else if (k == "--stats-start") stats_start = val();
         else if (k == "--periodic-y") params.periodic_y = true;
         else if (k == "--wall-south" || k == "--wall-north" || k == "--walls") {   // checked here: no device is touched before a bad value exits
@@ -266,6 +273,32 @@ int main(int argc, char** argv) {
         else if (params.forced()) std::snprintf(other, sizeof(other), "forcing F = (%g, %g)", params.forcing_x, params.forcing_y);
         if (params.mrt() && other[0]) {
             std::fprintf(stderr, "--mrt: (bulk rate, magic) = (%g, %g) on a context with %s (the two collisions cannot be combined)\n", params.mrt_bulk_rate, params.mrt_magic, other);
+            return 2;
+        }
+    }
+    if (sponge) {        // likewise: WIDTH:TAU_END parsed whole, a width the grid holds, a tau the rates are defined for, and no second
+                         // collision model (in the words of the library's setters)
+        try {
+            params.set_sponge(sponge);
+        } catch (const std::exception& e) {
+            std::fprintf(stderr, "%s\n", e.what());
+            return 2;
+        }
+        if (params.sponge_width > params.nx - 1) {
+            std::fprintf(stderr, "--sponge: width = %d (0 .. nx - 1 = %d only: column 0 keeps tau)\n", params.sponge_width, params.nx - 1);
+            return 2;
+        }
+        if (params.sponge() && !(params.tau > 0.5)) {
+            std::fprintf(stderr, "--sponge: tau = %g (the sponge's rates need tau > 0.5)\n", params.tau);
+            return 2;
+        }
+        char other[160] = "";
+        if (params.smagorinsky_cs > 0.0) std::snprintf(other, sizeof(other), "Smagorinsky constant Cs = %g", params.smagorinsky_cs);
+        else if (params.trt_magic > 0.0) std::snprintf(other, sizeof(other), "TRT magic parameter %g", params.trt_magic);
+        else if (params.forced()) std::snprintf(other, sizeof(other), "forcing F = (%g, %g)", params.forcing_x, params.forcing_y);
+        else if (params.mrt()) std::snprintf(other, sizeof(other), "MRT parameters (bulk rate, magic) = (%g, %g)", params.mrt_bulk_rate, params.mrt_magic);
+        if (params.sponge() && other[0]) {
+            std::fprintf(stderr, "--sponge: (width, tau_end) = (%d, %g) on a context with %s (the two collisions cannot be combined)\n", params.sponge_width, params.sponge_tau_end, other);
             return 2;
         }
     }

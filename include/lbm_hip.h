@@ -385,6 +385,34 @@ int  lbm_get_forcing(const lbm_ctx* c, double* fx, double* fy);
 int  lbm_set_mrt(lbm_ctx* c, double bulk_rate, double magic);
 /* The pair as set, (0, 0) on a context without MRT; either pointer may be NULL. LBM_ERR_ARG: null context. */
 int  lbm_get_mrt(const lbm_ctx* c, double* bulk_rate, double* magic);
+/* The collision: an outlet sponge zone (a viscosity sponge) in front of the east port. Over the last `width` columns the relaxation time
+ * rises smoothly from tau to `tau_end`, so that vortices and pressure waves are diffused before they meet the port, which reflects them.
+ * With x0 = nx - 1 - width:
+ *     column x <= x0:  tau_x = tau                                       (its rate is the very bits BGK's 1/tau holds)
+ *     column x >  x0:  tau_x = tau + (tau_end - tau) * (s * s),  s = (double)(x - x0) / (double)width
+ * formed on the host in double, in exactly that order; the kernels read the table wp_x[x] = (T)(1.0 / tau_x), cast once to the element
+ * type, nx elements. The collision is BGK's with 1/tau replaced by wp_x of the cell's column: strict arithmetic (option arith=0)
+ * evaluates f_i - wp_x (f_i - feq_i) operation by operation as BGK does, contracted arithmetic (arith=1) BGK's FMA chain with that rate.
+ * Every cell that collides takes its column's rate, the port columns and the wall rows included; solid cells are skipped as ever. BGK
+ * conserves mass and momentum at any rate, so the snapshot (lbm_get_macros, statistics, frames, probes) needs no correction. The ports
+ * and the walls do not know about the sponge, and the viscosity inside the zone is (tau_x - 1/2) / 3: results taken there are not those
+ * of the fluid. The register kernel reads its column's rate once per launch; no extra memory traffic per cell.
+ * Call after lbm_create and before lbm_initialise, like lbm_set_mrt: the plan is then measured on the sponge kernels (Arith values
+ * 32 / 33; neither the fp32 64x48 nor the fp64 64x40 regions: pinning them fails). width == 0 clears the model: the BGK kernels, and every
+ * result, kernel name, plan candidate and checkpoint byte as without the call (tau_end is then ignored). Every strip of a run is given
+ * the same pair; strips cut rows, so every strip holds the whole table. Forces, the stability scan, the halo exchange and every launch
+ * and row range are those of BGK. Checkpoints carry the pair (lbm_save_state: magic word "LBMCKPT3", flag bit 11) and load only into a
+ * context with an equal one.
+ * LBM_ERR_ARG (the text names the offender): a null context, an initialised context, width < 0 or width > nx - 1 (column 0 keeps tau),
+ * with a nonzero width a tau_end that is not finite or is <= 0.5 or a context whose tau <= 0.5, or a context with a Smagorinsky
+ * constant, a TRT magic parameter, a force or MRT — and any of those setters on a context with a sponge: the collisions cannot be
+ * combined. */
+int  lbm_set_sponge(lbm_ctx* c, int width, double tau_end);
+/* The pair as set, (0, 0) on a context without a sponge; either pointer may be NULL. LBM_ERR_ARG: null context. */
+int  lbm_get_sponge(const lbm_ctx* c, int* width, double* tau_end);
+/* The rate column x relaxes with, as the kernels see it: (double)(T)(1 / tau_x); BGK's (double)(T)(1 / tau) without a sponge.
+ * LBM_ERR_ARG: a null context or pointer, x outside 0 .. nx - 1. */
+int  lbm_get_sponge_rate(const lbm_ctx* c, int x, double* wp_out);
 /* The two walls: generalises the on-node bounce-back of the bottom and top rows (LBMSolver.h:155-176), a stationary no-slip wall, to a
  * KIND and a tangential VELOCITY per wall. The south wall is global row 0, the north wall global row ny - 1. On a fluid cell of the
  * wall's row, after the pull:
@@ -579,7 +607,7 @@ int  lbm_halo_import(lbm_ctx* c, const double* south_in, const double* north_in)
 /* Checkpoint / restart (the reference has none): the strip's post-collision populations and the
  * iteration counter. lbm_load_state needs an initialised context created with the same parameters; the macro /
  * population snapshots become available again after the next lbm_step. A file written with an obstacle mask, an inlet
- * profile, a Smagorinsky constant, a TRT magic parameter, a force (lbm_set_forcing), an MRT pair (lbm_set_mrt), a wall that is not no-slip (lbm_set_wall), an
+ * profile, a Smagorinsky constant, a TRT magic parameter, a force (lbm_set_forcing), an MRT pair (lbm_set_mrt), an outlet sponge (lbm_set_sponge), a wall that is not no-slip (lbm_set_wall), an
  * inlet schedule (lbm_set_inlet_schedule) or a port off its default (lbm_set_port) loads only into a context with the same mask,
  * profile, constant, parameter, force, walls, schedule and ports (the failure names which one differs). The file format, and the order in which differences are named: the comment at the
  * head of csrc/lbm_ckpt.hpp. */
@@ -628,6 +656,8 @@ int  lbm_load_state(lbm_ctx* c, const char* path);
  *                 probes from lbm_probes_begin and ignores the key)
  *   "bodies" 1    lbm_debug_choreography only: the dry run records a per-body force sample behind every force kernel (a real context
  *                 gets its bodies from lbm_set_body_labels and ignores the key)
+ *   "sponge" W    lbm_set_sponge(c, W, 1.5) by its key, for the dry runs, which take options only (lbm_debug_choreography); a run calls
+ *                 lbm_set_sponge with a tau_end of its own
  *   "timing" 1    record HIP events around each lbm_step call (lbm_last_step_kernel_ms). */
 int  lbm_set_option(lbm_ctx* c, const char* key, long value);
 /* Average device time per step-kernel launch (ms) measured with HIP events on the context's stream around
@@ -723,11 +753,16 @@ int lbm_debug_plan_candidates(int nx, int ny, int precision, int arith, int num_
 /* Test hook, callable without a device: the setters of the collision models on a context that is never initialised on a device (64 x 64
  * cells, the given tau and precision, `options` = "key=value ..." as for lbm_set_option applied first). Call k is setter[k] with
  * (v1[k], v2[k]): 0 lbm_set_smagorinsky(v1), 1 lbm_set_trt(v1), 2 lbm_set_forcing(v1, v2), 3 lbm_set_mrt(v1, v2), 4 marks the context
- * initialised (as lbm_initialise leaves it), 5 lbm_initialise's refusal of a pinned deep shape. rc[k] receives each return value, `texts`
+ * initialised (as lbm_initialise leaves it), 5 lbm_initialise's refusal of a pinned deep shape, 6 lbm_set_sponge((int)v1, v2). rc[k] receives each return value, `texts`
  * one line per call: the error text of a failed call, empty for LBM_OK. collision3 receives {lbm_ctx::collision, and what lbm_get_mrt
  * reports}. LBM_ERR_ARG: a null pointer, an unknown setter, a bad option, a buffer too small. */
 int lbm_debug_collision_setters(double tau, int precision, const char* options, const int* setter, const double* v1, const double* v2, int n,
                                 int* rc, char* texts, int cap, double* collision3);
+/* Test hook, callable without a device: lbm_set_sponge(width, tau_end) on a context of nx columns that is never initialised on a device
+ * (the given tau and precision), then lbm_get_sponge into pair2 = {width, tau_end} and lbm_get_sponge_rate of every column into
+ * rates[nx]. Returns what lbm_set_sponge returned (its text: lbm_last_error); the getters run either way. LBM_ERR_ARG besides: a null
+ * pointer, nx < 1. */
+int lbm_debug_sponge_rates(int nx, double tau, int precision, int width, double tau_end, double* pair2, double* rates);
 /* Test hook, callable without a device: the table behind option "deep" (csrc/lbm_plan.hpp deep_shapes, region_kinds), one line per id,
  * precision and arithmetic mode that exists: "id|f64 or f32|strict or contracted|lds or registers|iterations per launch|width|height of
  * the tile or region|rows per thread|waves|offered depths|restrictions". An offered depth of a register shape reads
