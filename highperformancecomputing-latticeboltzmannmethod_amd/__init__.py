@@ -8,6 +8,6 @@ numerics of its own and fails loudly if the HIP library is missing.
 """
 from .binding import (LbmError, Params, Context, Group, lib, lib_path, device_count, build_id, runtime_versions, device_memory,
                       debug_geometry, debug_body_chunks, debug_ring, debug_gather, debug_wall_rule, debug_port_rule, parabolic_profile, scale_inlet_profile,
-                      debug_inlet_scale, cosine_ramp, sine_pulse, sponge_tau, debug_sponge_rates, CkptHead, debug_ckpt_save, debug_ckpt_load)  # noqa: F401
+                      debug_inlet_scale, cosine_ramp, sine_pulse, sponge_tau, debug_sponge_rates, debug_collision_args, CkptHead, debug_ckpt_save, debug_ckpt_load)  # noqa: F401
 from .build import build_all, source_id, embedded_id  # noqa: F401
 from .strips import partition_rows, GlooHalo  # noqa: F401

@@ -106,6 +106,7 @@ def lib():
         L.lbm_get_sponge.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_double)]
         L.lbm_get_sponge_rate.argtypes = [vp, C.c_int, C.POINTER(C.c_double)]
         L.lbm_debug_sponge_rates.argtypes = [C.c_int, C.c_double, C.c_int, C.c_int, C.c_double, dp, dp]
+        L.lbm_debug_collision_args.argtypes = [C.c_double, C.c_int, C.c_int, C.c_double, C.c_double, dp, C.c_int]
         L.lbm_set_wall.argtypes = [vp, C.c_int, C.c_int, C.c_double]
         L.lbm_get_wall.argtypes = [vp, C.c_int, C.POINTER(C.c_int), dp]
         L.lbm_debug_wall_rule.argtypes = [C.c_int, C.c_int, C.c_double, C.c_int, dp, dp]
@@ -388,6 +389,19 @@ def debug_sponge_rates(nx, tau, precision, width, tau_end):
     if rc != 0:
         raise LbmError(lib().lbm_last_error().decode())
     return (int(pair[0]), float(pair[1])), rates
+
+
+def debug_collision_args(tau, precision, setter, v1=0.0, v2=0.0):
+    """lbm_debug_collision_args (no device): the launch-uniform values of one collision model as a launch carries them. setter: -1 plain
+    BGK, 0 lbm_set_smagorinsky(v1), 1 lbm_set_trt(v1), 2 lbm_set_forcing(v1, v2), 3 lbm_set_mrt(v1, v2), 6 lbm_set_sponge(int(v1), v2).
+    Returns (named values in the model's order, the seven shared slots), both float64 arrays. precision: "f64" / "f32". Raises
+    LbmError with the setter's text if it refuses."""
+    out = np.zeros(16, dtype=np.float64)
+    n = lib().lbm_debug_collision_args(float(tau), 1 if precision in ("f32", 1) else 0, int(setter), float(v1), float(v2),
+                                       out.ctypes.data_as(C.POINTER(C.c_double)), len(out))
+    if n < 0:
+        raise LbmError(lib().lbm_last_error().decode())
+    return out[:n].copy(), out[n:n + 7].copy()
 
 
 def _schedule(spec):

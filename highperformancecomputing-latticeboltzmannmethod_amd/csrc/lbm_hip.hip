@@ -1827,6 +1827,45 @@ int lbm_debug_collision_setters(double tau, int precision, const char* options, 
     return LBM_OK;
 }
 
+/* TEST HOOK (no device needed): the launch-uniform values of one collision model as make_kargs stores them and the slot map reads them
+ * back: see include/lbm_hip.h. */
+int lbm_debug_collision_args(double tau, int precision, int setter, double v1, double v2, double* out, int cap) {
+    if (!out || cap < 0) return fail(LBM_ERR_ARG, "lbm_debug_collision_args: null pointer or negative capacity");
+    lbm_ctx* c = choreo_fake_ctx(64, 64, 0, 64, precision, 0);
+    c->p.tau = tau;
+    int rc = LBM_OK;
+    switch (setter) {
+        case -1: break;
+        case 0: rc = lbm_set_smagorinsky(c, v1); break;
+        case 1: rc = lbm_set_trt(c, v1); break;
+        case 2: rc = lbm_set_forcing(c, v1, v2); break;
+        case 3: rc = lbm_set_mrt(c, v1, v2); break;
+        case 6: rc = lbm_set_sponge(c, (int)v1, v2); break;
+        default: rc = fail(LBM_ERR_ARG, "lbm_debug_collision_args: setter -1, 0, 1, 2, 3 or 6 only");
+    }
+    auto read = [&](auto element) -> int {      // (a generic lambda: this part of the file has C linkage)
+        using T = decltype(element);
+        const KArgs<T> a = make_kargs<T>(c, 0, 1, 0);
+        std::vector<double> v;
+        switch (c->collision) {
+            case AR_STRICT: { const BgkK<T> k = bgk_k(a); v = {(double)k.wp}; break; }
+            case AR_STRICT_LES: { const LesK<T> k = les_k(a); v = {(double)k.tau, (double)k.tau2, (double)k.c}; break; }
+            case AR_STRICT_TRT: { const TrtK<T> k = trt_k(a); v = {(double)k.wp, (double)k.wm, (double)k.wa, (double)k.wb}; break; }
+            case AR_STRICT_FORCED: { const ForcedK<T> k = forced_k(a); v = {(double)k.wp, (double)k.gx, (double)k.gy, (double)k.hx, (double)k.hy}; break; }
+            case AR_STRICT_MRT: { const MrtK<T> k = mrt_k(a); v = {(double)k.wp, (double)k.wm, (double)k.wa, (double)k.wb, (double)k.sb, (double)k.kb}; break; }
+            default: break;      // the outlet sponge: nothing launch-uniform beyond its table
+        }
+        const int named = (int)v.size();
+        for (T raw : shared_collision_slots(a)) v.push_back((double)raw);
+        if ((int)v.size() > cap) return fail(LBM_ERR_ARG, "lbm_debug_collision_args: %zu values, room for %d", v.size(), cap);
+        std::copy(v.begin(), v.end(), out);
+        return named;
+    };
+    if (rc == LBM_OK) rc = precision == LBM_PRECISION_F32 ? read(float{}) : read(double{});
+    delete c;
+    return rc;
+}
+
 /* TEST HOOK (no device needed): lbm_set_sponge on a context no device knows, and the rate of every column: see include/lbm_hip.h. */
 int lbm_debug_sponge_rates(int nx, double tau, int precision, int width, double tau_end, double* pair2, double* rates) {
     if (!pair2 || !rates || nx < 1) return fail(LBM_ERR_ARG, "lbm_debug_sponge_rates: null pointer or nx < 1");

@@ -32,12 +32,14 @@
 // k_step3_tile, k_step4_tile and k_stepd_tile are one body (step_tile) at depth 3, 4 and 6..8.
 // Arithmetic modes of the collision (enum Arith): strict IEEE operation by operation (bit-identical to the CPU oracle)
 // or FMA-contracted with one reciprocal (what the reference's -ffast-math -mfma build permits; <= 1e-10).
+// The collision itself is lbm_collision.hpp, included below: one operator per model and arithmetic mode, each model's launch-uniform
+// values under their own names with the one map of those names to the slots of KArgs, and collide(), which picks by Arith.
 //
 // Step kernel K_t (one iteration = one loop body of Solver::run, LBMSolver.h:49-60):
 //     pull from P_t        == exchange_ghost_cells + streaming_step        (LBMGrid.h:249, LBMSolver.h:128-145)
 //     wall / inlet / outlet== apply_boundary_conditions, sequential order  (LBMSolver.h:147-236)
 //     stability test       == Grid::check_stability                        (LBMGrid.h:285-317)
-//     moments + BGK        == collision_step of iteration t+1              (LBMSolver.h:84-126)
+//     moments + collide()  == collision_step of iteration t+1              (LBMSolver.h:84-126)
 //     store P_{t+1}
 // Algorithmic traffic: 9 loads + 9 stores per lattice update = 144 B (fp64) / 72 B (fp32). HBM-bound; no MFMA.
 #pragma once
@@ -135,10 +137,9 @@ template <> struct KPad<0> {};
 
 template <typename T>
 struct KArgs {
-    // The uniform driving force (lbm_set_forcing; Guo, Zheng and Shi 2002): g = (1 - 1/(2 tau)) F, the factor of the source term, and
-    // h = F/2, what the velocity of the equilibrium adds to the momentum, each formed on the host in double and cast once. Read only by
-    // the forced instantiations (AR_STRICT_FORCED / AR_CONTRACTED_FORCED): a slot of their own, four values where the union below has
-    // three. A block of exactly 64 bytes IN FRONT of everything else, not behind it like the additions below: the fused kernels' second
+    // Four of the slots that carry the collision models' launch-uniform values (tau_inv and the three unions below are the others; which
+    // model's value stands in which slot is written once, in the slot map of lbm_collision.hpp, and no other code names them): four
+    // values where the unions have three. A block of exactly 64 bytes IN FRONT of everything else, not behind it like the additions below: the fused kernels' second
     // argument block (K2Extra) follows this struct in the kernel-argument segment, and the compiler merges the scalar loads of adjacent
     // fields across the two by their alignment, up to 64 bytes. Four values behind `sched` part the two blocks and 26 earlier
     // instantiations came out with other scalar spills or vector register counts; with every field moved by 64 bytes, K2Extra's
@@ -163,7 +164,7 @@ struct KArgs {
     int cyl_x, cyl_y;  // LBMConfig.h:61-63 (integer cells)
     double cyl_r2;     // (double)(r*r), LBMGrid.h:169
     MaskView mv;       // user-defined geometry (lbm_set_solid_mask); mv.bits == nullptr: the disc above
-    T tau_inv;         // 1/tau, LBMSolver.h:85
+    T tau_inv;         // 1/tau, LBMSolver.h:85 (a slot of the collision models' values: lbm_collision.hpp)
     const T* u_row;    // inlet velocity of global row yg at u_row[yg], every row of the domain: inlet_velocity on every row, or the
                        // profile of lbm_set_inlet_profile. Read on the inlet column (x == 0) only, inside apply_bcs
     int* unstable_t;   // device word: first unstable iteration (INT_MAX if none)
@@ -175,18 +176,12 @@ struct KArgs {
     int y_lo2, y_cnt2; // optional second range [y_lo2, y_lo2 + y_cnt2) of the same launch (both edge bands of a strip
                        // in one grid); y_cnt2 == 0: none
     int reverse;       // 1: blockIdx.y walks the rows top-down (alternated per launch by the host, see row_of_block)
-    // Smagorinsky LES (lbm_set_smagorinsky): tau, tau*tau and C = 18*sqrt(2)*Cs^2, computed on the host in double. Read only by the
-    // LES instantiations (AR_STRICT_LES / AR_CONTRACTED_LES); appended so that the fields BGK kernels read keep their offsets.
-    // A TRT context (lbm_set_trt; never LES as well) carries its second rate wm = 1/tau_minus in the first of the three slots instead,
-    // and the folded rates of the contracted arithmetic, (wp + wm)/2 and (wp - wm)/2, in the other two (formed on the host: a uniform
-    // value formed by the kernel would sit in vector registers). The struct, and with it every BGK and LES kernel, keeps its size
-    // and offsets.
+    // Three more slots of the collision models' values (lbm_collision.hpp: the slot map), appended so that the fields BGK kernels read
+    // keep their offsets, and shared by the models that came later (a context has one model), so that the struct, and with it every
+    // earlier kernel, keeps its size and offsets. The names are those of the first two models that used them.
     union { T les_tau; T trt_wm; };
     union { T les_tau2; T trt_wa; };
     union { T les_c; T trt_wb; };
-    // An MRT context (lbm_set_mrt; never LES, TRT or forcing as well) carries wm in trt_wm as TRT does, the folded rates of its contracted
-    // arithmetic in trt_wa / trt_wb, all three as TRT does, and the bulk rate sb and the folded (sb - wp)/(4 wp) in frc_gx / frc_gy of the block at the
-    // front, which only a forced context reads otherwise: no field moves or is added.
     // The two physical walls (lbm_set_wall), appended for the same reason: wall_pack of the two kinds, and what each wall adds to and
     // subtracts from its diagonal populations (wall_ks: k = u_w / 6 of a moving wall, formed on the host in double; the identity
     // operands otherwise). Launch-uniform: read inside the bottom / top branches of apply_bcs only. Bits 4 and 5 of `walls` are the
@@ -199,6 +194,16 @@ struct KArgs {
 };
 static_assert(offsetof(KArgs<double>, wp_x) == 56 && offsetof(KArgs<double>, src) == 64 && offsetof(KArgs<float>, wp_x) == 56 &&
               offsetof(KArgs<float>, src) == 64, "the block in front of KArgs is 64 bytes, the sponge's table its last eight");
+// ... and the slots of the collision models' launch-uniform values (lbm_collision.hpp maps each model's names to them): the offsets are
+// what keeps every kernel at its scalar loads and register counts (profiles/forcing/README.md)
+template <typename T> constexpr bool collision_slots_at(size_t tau_inv, size_t u0) {
+    return offsetof(KArgs<T>, frc_gx) == 0 && offsetof(KArgs<T>, frc_gy) == sizeof(T) && offsetof(KArgs<T>, frc_hx) == 2 * sizeof(T) &&
+           offsetof(KArgs<T>, frc_hy) == 3 * sizeof(T) && offsetof(KArgs<T>, tau_inv) == tau_inv && offsetof(KArgs<T>, les_tau) == u0 &&
+           offsetof(KArgs<T>, trt_wm) == u0 && offsetof(KArgs<T>, les_tau2) == u0 + sizeof(T) && offsetof(KArgs<T>, trt_wa) == u0 + sizeof(T) &&
+           offsetof(KArgs<T>, les_c) == u0 + 2 * sizeof(T) && offsetof(KArgs<T>, trt_wb) == u0 + 2 * sizeof(T);
+}
+static_assert(collision_slots_at<double>(168, 232) && collision_slots_at<float>(168, 228) && sizeof(KArgs<double>) == 304 &&
+              sizeof(KArgs<float>) == 272, "the collision models' slots and the size of KArgs stay as they are");
 
 // Row handled by blockIdx.y. Blocks are dispatched roughly in index order; walking the rows in the opposite
 // direction on every other step makes a step start on the rows the previous step wrote last, which are the
@@ -361,64 +366,10 @@ __device__ __forceinline__ void bcs_at(const KArgs<T>& a, T (&f)[Q], int x, int 
     bcs_at_with(a, f, x, yg, lvl, [&]() { return a.u_row[yg]; });
 }
 
-// Arithmetic of the collision (the only place the two modes differ):
-//   AR_STRICT     the reference's expression tree evaluated operation by operation in IEEE arithmetic, no contraction,
-//                 two IEEE divisions: bit-identical to the strict CPU oracle (library default, parity tests).
-//   AR_CONTRACTED the same formulas as fused multiply-adds with ONE reciprocal of rho (two Newton steps on v_rcp): what the
-//                 reference's own build flags permit its compiler to do (CMakeLists.txt:21-22: -ffast-math -mfma). 70
-//                 instead of 150 floating-point instructions per cell; rho/u stay within 1e-10 of the reference (tests).
-//   AR_STRICT_LES / AR_CONTRACTED_LES  the same two arithmetic modes with the Smagorinsky relaxation time of each cell (les_tau_inv)
-//                 in place of the global 1/tau. Separate instantiations, never a runtime branch: a kernel's VGPR count is the maximum
-//                 over its paths, and the BGK kernels have no headroom.
-//   AR_STRICT_TRT / AR_CONTRACTED_TRT  the same two arithmetic modes with the two-relaxation-time operator (lbm_set_trt): the even
-//                 part of each opposite pair relaxes with 1/tau, the odd part with the launch-uniform second rate trt_wm. Separate
-//                 instantiations for the same reason. TRT and LES exclude each other: there are no values 6 and 7.
-//   AR_STRICT_FORCED / AR_CONTRACTED_FORCED  BGK under a uniform force density F (lbm_set_forcing), Guo's scheme: the equilibrium is
-//                 taken at u = (sum c f + F/2) / rho and the source S_i = (1 - 1/(2 tau)) w_i [3 (c_i - u) + 9 (c_i.u) c_i] . F is added
-//                 to the relaxed populations. Separate instantiations for the same reason. Forcing excludes LES and TRT: there are no
-//                 values 10 to 13.
-//   AR_STRICT_MRT / AR_CONTRACTED_MRT  the same two arithmetic modes with the multiple-relaxation-time operator (lbm_set_mrt): TRT's even
-//                 and odd parts of each pair, with the even parts of the two axis pairs (and of the two diagonal pairs) split into their
-//                 half sum, relaxed with the launch-uniform bulk rate sb like the rest population, and their half difference, relaxed
-//                 with 1/tau. Separate instantiations for the same reason. MRT excludes LES, TRT and forcing: of 16 to 31 there are 16, 17.
-//   AR_STRICT_SPONGE / AR_CONTRACTED_SPONGE  BGK's two arithmetic modes, operation for operation, with the rate of the cell's COLUMN
-//                 (lbm_set_sponge: KArgs::wp_x, column_rate) in place of the global 1/tau. Separate instantiations for the same reason.
-//                 The sponge excludes LES, TRT, forcing and MRT: of 32 to 63 there are 32, 33.
-enum Arith { AR_STRICT = 0, AR_CONTRACTED = 1, AR_STRICT_LES = 2, AR_CONTRACTED_LES = 3, AR_STRICT_TRT = 4, AR_CONTRACTED_TRT = 5,
-             AR_STRICT_FORCED = 8, AR_CONTRACTED_FORCED = 9, AR_STRICT_MRT = 16, AR_CONTRACTED_MRT = 17, AR_STRICT_SPONGE = 32,
-             AR_CONTRACTED_SPONGE = 33 };
-constexpr bool ar_contracted(int ar) { return (ar & 1) != 0; }
-constexpr bool ar_les(int ar) { return (ar & 2) != 0; }
-constexpr bool ar_trt(int ar) { return (ar & 4) != 0; }
-constexpr bool ar_forced(int ar) { return (ar & 8) != 0; }
-constexpr bool ar_mrt(int ar) { return (ar & 16) != 0; }
-constexpr bool ar_sponge(int ar) { return (ar & 32) != 0; }
-constexpr int ar_of(bool contracted, bool les, bool trt = false) { return (contracted ? 1 : 0) | (les ? 2 : 0) | (trt ? 4 : 0); }
-
-__device__ __forceinline__ double fma_t(double a, double b, double c) { return __builtin_fma(a, b, c); }
-__device__ __forceinline__ float fma_t(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-__device__ __forceinline__ double recip_t(double d) {      // 1/d to an ulp: v_rcp_f64 + two Newton steps
-    double r = __builtin_amdgcn_rcp(d);
-    r = fma_t(fma_t(-d, r, 1.0), r, r);
-    r = fma_t(fma_t(-d, r, 1.0), r, r);
-    return r;
-}
-__device__ __forceinline__ float recip_t(float d) {        // v_rcp_f32 (1 ulp) + one Newton step
-    float r = __builtin_amdgcn_rcpf(d);
-    return fma_t(fma_t(-d, r, 1.0f), r, r);
-}
-__device__ __forceinline__ double sqrt_t(double v) { return __builtin_sqrt(v); }   // correctly rounded (rsq + refinement + scaling)
-__device__ __forceinline__ float sqrt_t(float v) { return __builtin_sqrtf(v); }
-// contracted arithmetic (LES): v_rsq_f64 and one Goldschmidt step, to about an ulp, for ~5 instead of ~17 instructions and fewer live
-// registers (the fp64 register kernel has four spare VGPRs). Values below 1e-300, zero included, are raised to it first (rsq(0) is
-// inf): a square root of 1e-150 instead of 0 beside tau^2 >= 0.25 changes nothing. fp32: v_sqrt_f32 (1 ulp).
-__device__ __forceinline__ double sqrt_c(double v) {
-    v = __builtin_fmax(v, 1e-300);
-    const double y = __builtin_amdgcn_rsq(v);
-    const double s = v * y;
-    return fma_t(s, fma_t(-s, 0.5 * y, 0.5), s);
-}
-__device__ __forceinline__ float sqrt_c(float v) { return __builtin_amdgcn_sqrtf(v); }
+// The collision: the Arith enum, the operators of every model, the map of their launch-uniform values to the slots of KArgs, collide().
+}  // namespace lbmk
+#include "lbm_collision.hpp"
+namespace lbmk {
 
 // Buffer-descriptor access for the block-uniform "lean" paths: address = descriptor base + SGPR offset + ONE 32-bit VGPR
 // offset, so the nine populations of a cell cost nine scalar adds and no vector address arithmetic at all (a global_load
@@ -439,307 +390,6 @@ template <bool NT> __device__ __forceinline__ void buf_store(double v, __amdgpu_
 }
 template <bool NT> __device__ __forceinline__ void buf_store(float v, __amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, voff, soff, NT ? 2 : 0);
-}
-
-// ux /= rho; uy /= rho (LBMSolver.h:108-109) in strict mode: two correctly rounded IEEE divisions by the SAME denominator.
-// hipcc expands an fp64 division into v_div_scale x2, v_rcp_f64, two Newton steps on the reciprocal (four FMAs), q = a*r,
-// rem = fma(-b, q, a), v_div_fmas (= fma(rem, r, q) unless the operands were scaled) and v_div_fixup (special values) — twice,
-// because the scaling instruction takes the numerator too. For operands in the normal range (rho ~ 1, |rho u| < 1: nothing is
-// scaled, nothing is special) the reciprocal chain depends on the denominator only, so the two divisions share it: the same
-// operations on the same values in the same order => the same bits as the compiler's two expansions and as the oracle's divsd
-// (every strict parity test holds the populations to np.array_equal), for 13 instead of ~26 instructions and a dozen fewer live
-// registers. (A run that blows up is flagged by |f| > 1e5 long before rho or rho*u leave the range where no scaling happens.)
-// RANGE of the bit-identity (tests/test_gpu_thin_spots.py::test_strict_div2_equals_ieee_division_in_its_range holds it on 4 M random
-// operands through lbm_debug_strict_div2): denominators in [2^-20, 2^20], numerators 0 or of magnitude in [2^-400, 2^400] —
-// populations of a stable run live in [1e-3, 1e1]. Outside it the chain is NOT an IEEE division: a -0 numerator gives +0 (the sign
-// of a zero velocity is erased by the equilibrium's bracket and compares equal in every accessor), denormal quotients and
-// exponent gaps beyond the fp64 range are not rescaled, rho == 0 gives NaN where IEEE gives +-inf (both flagged unstable).
-__device__ __forceinline__ void strict_div2(double& a1, double& a2, double b) {
-    double r = __builtin_amdgcn_rcp(b);
-    double e = __builtin_fma(-b, r, 1.0);
-    r = __builtin_fma(r, e, r);
-    e = __builtin_fma(-b, r, 1.0);
-    r = __builtin_fma(r, e, r);
-    double q = a1 * r;
-    a1 = __builtin_fma(__builtin_fma(-b, q, a1), r, q);
-    q = a2 * r;
-    a2 = __builtin_fma(__builtin_fma(-b, q, a2), r, q);
-}
-__device__ __forceinline__ void strict_div2(float& a1, float& a2, float b) { a1 /= b; a2 /= b; }
-// test kernel (lbm_debug_strict_div2): strict_div2 beside the compiler's own IEEE divisions, element by element
-template <int UNUSED = 0>      // (a template: the header is included by three translation units)
-__global__ void k_debug_strict_div2(const double* a1, const double* a2, const double* b, int n, double* q1, double* q2, double* r1, double* r2) {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n) return;
-    double x = a1[k], y = a2[k];
-    strict_div2(x, y, b[k]);
-    q1[k] = x; q2[k] = y;
-    r1[k] = a1[k] / b[k]; r2[k] = a2[k] / b[k];
-}   // (fp32 has no oracle to be bit-equal to: plain divisions)
-
-// Smagorinsky relaxation rate of one cell, 1/tau_eff with tau_eff = (tau + sqrt(tau^2 + C*|Pi_neq|/rho))/2: the closed form of
-// tau = tau0 + 3 Cs^2 |S|, |S| = sqrt(2 S:S), for cs^2 = 1/3 and dx = dt = 1, where Pi_neq is the non-equilibrium momentum flux of
-// the post-BC populations. STRICT: the operation tree of the issue's reference operator (tests/test_gpu_les.py les_collide) in IEEE
-// arithmetic with correctly rounded square roots and divisions, on ux, uy already divided by rho — bit-identical to numpy.
-template <typename T>
-__device__ __forceinline__ T les_tau_inv_strict(const T (&f)[Q], T rho, T ux, T uy, T tau, T tau2, T c) {
-    const T sxx = ((((f[1] + f[3]) + f[5]) + f[6]) + f[7]) + f[8];
-    const T syy = ((((f[2] + f[4]) + f[5]) + f[6]) + f[7]) + f[8];
-    const T sxy = ((f[5] - f[6]) + f[7]) - f[8];
-    const T pxx = (sxx - rho * (ux * ux)) - rho * T(1.0 / 3.0);
-    const T pyy = (syy - rho * (uy * uy)) - rho * T(1.0 / 3.0);
-    const T pxy = sxy - rho * (ux * uy);
-    const T qn = sqrt_t((pxx * pxx + pyy * pyy) + T(2.0) * (pxy * pxy));
-    const T tau_eff = T(0.5) * (tau + sqrt_t(tau2 + c * (qn / rho)));
-    return T(1.0) / tau_eff;
-}
-
-// collision_step for one cell, LBMSolver.h:101-123 (moments i = 0..8 ascending from 0, N7). LES modes: tau_inv is ignored and the
-// relaxation rate of the cell comes from les_tau / les_tau2 / les_c (KArgs); BGK modes never read those three. TRT modes: tau_inv
-// relaxes the even part of each opposite pair (and the rest population), `les_tau` carries the rate of the odd part, wm = 1/tau_minus, and les_tau2 / les_c the folded rates (wp + wm)/2, (wp - wm)/2.
-// FORCED modes: tau_inv is BGK's, and the four values carry gx, gy, hx, hy (KArgs::frc_*): g = (1 - wp/2) F, h = F/2.
-// MRT modes: tau_inv is wp, `les_tau` carries wm as in TRT, les_tau2 / les_c TRT's folded rates, frc_hy the bulk
-// rate sb and mrt_cb the folded (sb - wp)/(4 wp).
-template <typename T, int AR = AR_STRICT>
-__device__ __forceinline__ void bgk_collide(T (&f)[Q], T tau_inv, T les_tau = T(0), T les_tau2 = T(0), T les_c = T(0), T frc_hy = T(0), T mrt_cb = T(0)) {
-    T rho = T(0), ux = T(0), uy = T(0);
-    if constexpr (ar_contracted(AR)) {
-        // moments as short trees over opposite pairs (depth 4 / 3 instead of chains of 9 / 6 dependent additions)
-        const T a13 = f[1] + f[3], a24 = f[2] + f[4], a57 = f[5] + f[7], a68 = f[6] + f[8];
-        const T d13 = f[1] - f[3], d24 = f[2] - f[4], d57 = f[5] - f[7], d68 = f[6] - f[8];
-        rho = ((f[0] + a13) + (a24 + a57)) + a68;
-        ux = (d13 + d57) - d68;
-        uy = (d24 + d57) + d68;
-        T mrt_sa = T(0), mrt_sd = T(0);       // MRT: the sums of the axis and of the diagonal populations, while the pair sums are at hand
-        if constexpr (ar_mrt(AR) && sizeof(T) == 8) { mrt_sa = a13 + a24; mrt_sd = a57 + a68; }
-        if constexpr (ar_forced(AR)) { ux = ux + les_c; uy = uy + frc_hy; }      // Guo: the momenta take h = F/2, so v below is 3u of the forced velocity
-        // v = 3u. 1 + 3cu + 4.5cu^2 - 1.5u^2 = base + cv*(1 + 0.5cv) with cv = c.v and base = 1 - v^2/6: the inner bracket
-        // is one FMA with INLINE constants (0.5, 1.0). gfx950 VALU instructions take one SGPR/literal operand at most, so
-        // fma(4.5, cu, 3.0) cost two v_mov per direction to build the 3.0 — 16 of ~100 vector instructions per cell.
-        const T rinv = recip_t(rho);
-        const T inv3 = rinv * T(3.0);
-        const T vx = ux * inv3, vy = uy * inv3;
-        if constexpr (ar_les(AR)) {
-            // the same operator with FMAs on the momenta (ux, uy here are rho*u): Pi_neq = S - j j / rho - rho/3 I
-            const T sxx = (a13 + a57) + a68, syy = (a24 + a57) + a68, sxy = a57 - a68;
-            const T jxr = ux * rinv;
-            const T third = rho * T(-1.0 / 3.0);
-            const T pxx = fma_t(-jxr, ux, sxx + third), pyy = fma_t(-uy * rinv, uy, syy + third), pxy = fma_t(-jxr, uy, sxy);
-            const T qn = sqrt_c(fma_t(pxx, pxx, fma_t(pyy, pyy, T(2.0) * (pxy * pxy))));
-            tau_inv = T(2.0) * recip_t(les_tau + sqrt_c(fma_t(les_c, qn * rinv, les_tau2)));
-        }
-        const T base = fma_t(T(-1.0 / 6.0), fma_t(vx, vx, vy * vy), T(1.0));
-        const T wr0 = wgt<T>(0) * rho, wr1 = wgt<T>(1) * rho, wr5 = wgt<T>(5) * rho;
-        if constexpr (ar_trt(AR) || ar_mrt(AR)) {
-            // f_i' = f_i + wa (feq_i - f_i) + wb (feq_ib - f_ib) with wa = (wp + wm)/2, wb = (wp - wm)/2: BGK's residuals of the two
-            // directions (c.v changes its sign for the opposite one), then two FMAs each, in place. Two temporaries beyond BGK's.
-            // MRT is TRT plus the same g = (sb - wp)/4 S on the four populations of a group (the axis pairs; the diagonal pairs), S the sum
-            // of the group's four residuals (-4 ta, -4 td), with the rest population relaxed by sb. Since wa + wb = wp, raising the
-            // equilibrium's `base` of a group by g / (wp w rho) adds exactly g to each of its populations: a group runs TRT's pair code
-            // on a base of its own, and nothing but that base is alive beyond TRT's values. With t = 1 - base = |v|^2 / 6, 4 w5 = w1 and
-            // kb = (sb - wp) / (4 wp) folded on the host:  base_axes = base + kb ((4 + 2 t) - 9 (f1 + f2 + f3 + f4) / rho),
-            // base_diagonals = base + 4 kb ((1 + 2 t) - 9 (f5 + f6 + f7 + f8) / rho), in inline constants only (a VALU instruction reads
-            // one scalar register or literal at most). That is the fp64 form; fp32 adds g itself (below).
-            const T wa = les_tau2, wb = les_c;
-            f[0] = fma_t(ar_mrt(AR) ? frc_hy : tau_inv, fma_t(wr0, base, -f[0]), f[0]);
-            auto pair = [&](int i, int ib, T cv, T wr, T b, T g = T(0)) {     // i: the direction whose c.v is `cv`; ib: its opposite; b: the base
-                const T ri = fma_t(wr, fma_t(cv, fma_t(cv, T(0.5), T(1.0)), b), -f[i]);
-                const T rb = fma_t(wr, fma_t(cv, fma_t(cv, T(0.5), T(-1.0)), b), -f[ib]);
-                if constexpr (ar_mrt(AR) && sizeof(T) == 4) { f[i] += g; f[ib] += g; }
-                f[i] = fma_t(wa, ri, fma_t(wb, rb, f[i]));
-                f[ib] = fma_t(wa, rb, fma_t(wb, ri, f[ib]));
-            };
-            // One pair after the other: an empty asm statement that "rewrites" a finished pair together with the next pair's inputs keeps
-            // the compiler from starting the next pair's residuals early (it would hold all eight and spill in the fp64 register kernel).
-            auto then = [&](int i, int ib, int j, int jb) { asm volatile("" : "+v"(f[i]), "+v"(f[ib]), "+v"(f[j]), "+v"(f[jb])); };
-            if constexpr (ar_mrt(AR) && sizeof(T) == 4) {
-                // fp32: the shift of the base costs the register kernel a wave of occupancy (84 to 86 VGPRs where 80 are the limit); g
-                // itself, formed in front of its group from the populations the group is about to replace and added to them, does not
-                auto group = [&](int i, int ib, int j, int jb, T k) {
-                    const T sum = ((f[i] + f[ib]) + f[j]) + f[jb];
-                    return mrt_cb * (tau_inv * fma_t(wr1, fma_t(T(2.0), T(1.0) - base, k), -sum));
-                };
-                T g = group(5, 7, 8, 6, T(1.0));
-                pair(5, 7, vx + vy, wr5, base, g);
-                then(5, 7, 8, 6);
-                pair(8, 6, vx - vy, wr5, base, g);
-                then(8, 6, 1, 3);
-                g = group(1, 3, 2, 4, T(4.0));
-                pair(1, 3, vx, wr1, base, g);
-                then(1, 3, 2, 4);
-                pair(2, 4, vy, wr1, base, g);
-                return;
-            }
-            if constexpr (ar_mrt(AR)) {
-                const T t2 = T(2.0) * (T(1.0) - base);
-                auto nine_over_rho = [&](T sum) { const T x = sum * inv3; return fma_t(T(2.0), x, x); };
-                T ba = fma_t(mrt_cb, (t2 + T(4.0)) - nine_over_rho(mrt_sa), base);
-                T bd = fma_t(mrt_cb, T(4.0) * ((t2 + T(1.0)) - nine_over_rho(mrt_sd)), base);
-                asm volatile("" : "+v"(ba), "+v"(bd));
-                pair(5, 7, vx + vy, wr5, bd);
-                then(5, 7, 8, 6);
-                pair(8, 6, vx - vy, wr5, bd);
-                then(8, 6, 1, 3);
-                pair(1, 3, vx, wr1, ba);
-                then(1, 3, 2, 4);
-                pair(2, 4, vy, wr1, ba);
-                return;
-            }
-            pair(5, 7, vx + vy, wr5, base);
-            then(5, 7, 8, 6);
-            pair(8, 6, vx - vy, wr5, base);
-            then(8, 6, 1, 3);
-            pair(1, 3, vx, wr1, base);
-            then(1, 3, 2, 4);
-            pair(2, 4, vy, wr1, base);
-            return;
-        }
-#pragma unroll
-        for (int i = 0; i < Q; ++i) {
-            T cv;
-            if (cx(i) == 0 && cy(i) == 0) cv = T(0);
-            else if (cy(i) == 0) cv = T(cx(i)) * vx;
-            else if (cx(i) == 0) cv = T(cy(i)) * vy;
-            else cv = T(cx(i)) * vx + T(cy(i)) * vy;
-            const T t = (i == 0) ? base : fma_t(cv, fma_t(cv, T(0.5), T(1.0)), base);
-            const T wr = i == 0 ? wr0 : (i < 5 ? wr1 : wr5);
-            f[i] = fma_t(tau_inv, fma_t(wr, t, -f[i]), f[i]);     // f - (f - feq)/tau = f + (feq - f)/tau
-        }
-        if constexpr (ar_forced(AR)) {
-            // Guo's source, added once BGK's chain above has finished. With cg = c_i.g and cv = c_i.v:
-            //     S_i = w_i (3 cg - 3 u.g + 9 (c_i.u) cg) = 3 w_i ((cg cv - u.g) + cg),   the opposite direction 3 w_i ((cg cv - u.g) - cg)
-            // so a pair shares m = cg cv - u.g, and gx, gy enter as scalar operands only (no uniform value is formed in a vector register).
-            // A phase of its own behind an empty asm statement that "rewrites" its inputs: base and the three w rho are dead by now and
-            // u.g is not yet alive, so the kernel holds no more values at once than BGK's does (folded into the relaxation, the
-            // register kernels of fp64 spilled: profiles/forcing/README.md).
-            const T gx = les_tau, gy = les_tau2;
-            T sx = vx, sy = vy;
-            asm volatile("" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]), "+v"(f[4]), "+v"(f[5]), "+v"(f[6]), "+v"(f[7]), "+v"(f[8]), "+v"(sx), "+v"(sy));
-            const T ug = fma_t(sx, gx, sy * gy) * T(1.0 / 3.0);      // u.g
-            f[0] = fma_t(T(-4.0 / 3.0), ug, f[0]);                  // S_0 = -3 w_0 u.g
-            auto source = [&](int i, int ib, T w3, T mi, T mb) {     // mi = m + cg, mb = m - cg; w3 = 3 w_i
-                f[i] = fma_t(w3, mi, f[i]);
-                f[ib] = fma_t(w3, mb, f[ib]);
-            };
-            {   const T m = fma_t(gx, sx, -ug); source(1, 3, T(1.0 / 3.0), m + gx, m - gx); }
-            {   const T m = fma_t(gy, sy, -ug); source(2, 4, T(1.0 / 3.0), m + gy, m - gy); }
-            {   const T cv = sx + sy, m = fma_t(gx, cv, fma_t(gy, cv, -ug)); source(5, 7, T(1.0 / 12.0), (m + gx) + gy, (m - gx) - gy); }
-            {   const T cv = sx - sy, m = fma_t(gx, cv, fma_t(-gy, cv, -ug)); source(8, 6, T(1.0 / 12.0), (m + gx) - gy, (m - gx) + gy); }
-        }
-        return;
-    }
-#pragma unroll
-    for (int i = 0; i < Q; ++i) {
-        rho += f[i];
-        if (cx(i) != 0) ux += T(cx(i)) * f[i];
-        if (cy(i) != 0) uy += T(cy(i)) * f[i];
-    }
-    if constexpr (ar_forced(AR)) { ux = ux + les_c; uy = uy + frc_hy; }      // Guo: the momenta take h = F/2 before the divisions
-    strict_div2(ux, uy, rho);
-    if constexpr (ar_les(AR)) tau_inv = les_tau_inv_strict(f, rho, ux, uy, les_tau, les_tau2, les_c);
-    const T usq = ux * ux + uy * uy;
-    // feq_i = w_i*rho*(1.0 + 3.0*cu + 4.5*cu*cu - 1.5*usq), cu = c_ix*ux + c_iy*uy with integer c (LBMSolver.h:119-121), evaluated
-    // operation by operation in the reference's order: ((1.0 + 3.0*cu) + (4.5*cu)*cu) - 1.5*usq. Shared WITHOUT changing a bit:
-    //  * where a component of c_i is 0 its product is an exact signed zero and the sum equals the other term bit for bit, except
-    //    for the sign of a zero result — which the bracket erases (1 + 3*(+-0) = 1, 4.5*(+-0)^2 = +0);
-    //  * opposite directions have cu of equal magnitude and opposite sign EXACTLY (negation is exact and rounding is symmetric:
-    //    (-1)*ux + (-1)*uy == -(ux + uy)), hence 3.0*cu flips its sign exactly and (4.5*cu)*cu is the same number: one cu, one
-    //    3*cu and one 4.5*cu*cu per PAIR, and 1.0 + (-t) is the subtraction 1.0 - t;
-    //  * 1.5*usq and the three w*rho are common to all directions.
-    // 112 instead of ~137 fp64 operations per cell (round 4); the populations stay np.array_equal to the oracle in every test.
-    const T c15 = T(1.5) * usq;
-    const T wr0 = wgt<T>(0) * rho, wr1 = wgt<T>(1) * rho, wr5 = wgt<T>(5) * rho;
-    auto relax = [&](T& fi, T wr, T bracket) {
-        const T feq = wr * bracket;
-        fi = fi - tau_inv * (fi - feq);
-    };
-    if constexpr (ar_mrt(AR)) { const T feq0 = wr0 * ((T(1.0) + T(0.0)) - c15); f[0] = f[0] - frc_hy * (f[0] - feq0); }     // the rest population: the bulk rate
-    else relax(f[0], wr0, (T(1.0) + T(0.0)) - c15);      // cu = 0: 1.0 + 3.0*0 + 4.5*0*0 = 1.0 exactly
-    T mrt_np = T(0), mrt_wmn = T(0);      // MRT: the even part and the relaxed odd part of a group's first pair, kept for its second
-    auto pair = [&](int i, int ib, T cu, T wr) {     // i: the direction whose c.u is `cu`; ib: its opposite
-        const T t3 = T(3.0) * cu, t45 = (T(4.5) * cu) * cu;
-        if constexpr (ar_mrt(AR)) {
-            // MRT (tests/mrt_reference.py mrt_collide, operation by operation): TRT's np, nm of the pair; the first pair (1,3 / 5,7) of a
-            // group leaves them, the second (2,4 / 8,6; `jj`, `jb`: the first pair's directions) forms the group's half sum t and half
-            // difference d of the even parts, relaxes t with the bulk rate sb and d with wp, and finishes all four populations
-            const T feq = wr * (((T(1.0) + t3) + t45) - c15), feqb = wr * (((T(1.0) - t3) + t45) - c15);
-            const T np = T(0.5) * ((f[i] + f[ib]) - (feq + feqb));
-            const T nm = T(0.5) * ((f[i] - f[ib]) - (feq - feqb));
-            const T wmn = les_tau * nm;
-            if (i == 1 || i == 5) { mrt_np = np; mrt_wmn = wmn; return; }
-            const int jj = i == 2 ? 1 : 5, jb = i == 2 ? 3 : 7;
-            const T tr = T(0.5) * (mrt_np + np), dv = T(0.5) * (mrt_np - np);
-            const T st = frc_hy * tr, wd = tau_inv * dv;
-            const T ep = st + wd, eq = st - wd;
-            f[jj] = (f[jj] - ep) - mrt_wmn;
-            f[jb] = (f[jb] - ep) + mrt_wmn;
-            f[i] = (f[i] - eq) - wmn;
-            f[ib] = (f[ib] - eq) + wmn;
-            return;
-        }
-        if constexpr (ar_trt(AR)) {
-            // TRT (tests/test_gpu_trt.py trt_collide, operation by operation): the same two feq, then the even (np) and odd (nm)
-            // non-equilibrium parts of the pair, relaxed with wp = 1/tau and wm = 1/tau_minus
-            const T feq = wr * (((T(1.0) + t3) + t45) - c15), feqb = wr * (((T(1.0) - t3) + t45) - c15);
-            const T np = T(0.5) * ((f[i] + f[ib]) - (feq + feqb));
-            const T nm = T(0.5) * ((f[i] - f[ib]) - (feq - feqb));
-            const T wpn = tau_inv * np, wmn = les_tau * nm;
-            f[i] = (f[i] - wpn) - wmn;
-            f[ib] = (f[ib] - wpn) + wmn;
-            return;
-        }
-        relax(f[i], wr, ((T(1.0) + t3) + t45) - c15);
-        relax(f[ib], wr, ((T(1.0) - t3) + t45) - c15);
-    };
-    pair(1, 3, ux, wr1);              // c1 = (1,0),  c3 = (-1,0)
-    pair(2, 4, uy, wr1);              // c2 = (0,1),  c4 = (0,-1)
-    pair(5, 7, ux + uy, wr5);         // c5 = (1,1),  c7 = (-1,-1)
-    pair(8, 6, ux - uy, wr5);         // c8 = (1,-1), c6 = (-1,1): 1*ux + (-1)*uy == ux - uy
-    if constexpr (ar_forced(AR)) {
-        // Guo's source (tests/forcing_reference.py guo_collide, operation by operation), added to BGK's relaxed populations:
-        //     S_i = w_i * ((3 cg - u3) + (9 cu) cg),  u3 = 3 (ux gx + uy gy),  cg = c_i.g; the opposite direction negates 3 cg and keeps the product.
-        // A phase of its own behind an empty asm statement, as in the contracted branch: what the relaxation held is dead by now.
-        const T gx = les_tau, gy = les_tau2;
-        asm volatile("" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]), "+v"(f[4]), "+v"(f[5]), "+v"(f[6]), "+v"(f[7]), "+v"(f[8]), "+v"(ux), "+v"(uy));
-        const T u3 = T(3.0) * (ux * gx + uy * gy);
-        f[0] = f[0] + wgt<T>(0) * (T(0.0) - u3);
-        auto source = [&](int i, int ib, T cu, T cg, T w) {
-            const T sa = T(3.0) * cg, sb = (T(9.0) * cu) * cg;
-            f[i] = f[i] + w * ((sa - u3) + sb);
-            f[ib] = f[ib] + w * (((-sa) - u3) + sb);
-        };
-        source(1, 3, ux, gx, wgt<T>(1));
-        source(2, 4, uy, gy, wgt<T>(1));
-        source(5, 7, ux + uy, gx + gy, wgt<T>(5));
-        source(8, 6, ux - uy, gx - gy, wgt<T>(5));
-    }
-}
-
-// The collision of the step kernels: BGK with the global 1/tau, (LES modes) the Smagorinsky rate of each cell, or (TRT modes) 1/tau
-// for the even and trt_wm for the odd part of each pair (contracted: the two folded into trt_wa, trt_wb), or (MRT modes) TRT's parts with
-// the trace of the even parts relaxed at the bulk rate (KArgs: the TRT slots and frc_gx, frc_gy)
-// The rate of column x on a sponge context (the sponge modes only; every other mode gets a zero that nothing reads). The index is
-// clamped into the table: the lanes and region cells that have no column (x < 0, x >= nx: a region's overhang, a ragged nx, nx < 64)
-// compute on zeros or garbage that is never stored, with the rate of the nearest column, and read nothing outside [0, nx).
-template <typename T, int AR>
-__device__ __forceinline__ T column_rate(const KArgs<T>& a, int x) {
-    if constexpr (ar_sponge(AR)) return a.wp_x[x < 0 ? 0 : (x < a.nx ? x : a.nx - 1)];
-    else return T(0);
-}
-
-// ... `wpx`: column_rate of the cell's column (read by the sponge modes only)
-template <typename T, int AR>
-__device__ __forceinline__ void collide(T (&f)[Q], const KArgs<T>& a, T wpx) {
-    static_assert(!(ar_les(AR) && ar_trt(AR)), "TRT and LES exclude each other");
-    static_assert(!(ar_forced(AR) && (ar_les(AR) || ar_trt(AR))), "forcing excludes LES and TRT");
-    static_assert(!(ar_mrt(AR) && (ar_les(AR) || ar_trt(AR) || ar_forced(AR))), "MRT excludes LES, TRT and forcing");
-    static_assert(!(ar_sponge(AR) && (AR & 30) != 0), "the sponge excludes LES, TRT, forcing and MRT");
-    if constexpr (ar_sponge(AR)) bgk_collide<T, AR>(f, wpx);
-    else if constexpr (ar_mrt(AR)) bgk_collide<T, AR>(f, a.tau_inv, a.trt_wm, a.trt_wa, a.trt_wb, a.frc_gx, a.frc_gy);
-    else if constexpr (ar_forced(AR)) bgk_collide<T, AR>(f, a.tau_inv, a.frc_gx, a.frc_gy, a.frc_hx, a.frc_hy);
-    else if constexpr (ar_trt(AR)) bgk_collide<T, AR>(f, a.tau_inv, a.trt_wm, a.trt_wa, a.trt_wb);
-    else if constexpr (ar_les(AR)) bgk_collide<T, AR>(f, T(0), a.les_tau, a.les_tau2, a.les_c);
-    else bgk_collide<T, AR>(f, a.tau_inv);
 }
 
 // Grid::check_stability on one cell's populations: NaN, Inf, > 1e5, < -1e5 (LBMGrid.h:296-307); 1e5 is exact in fp32 too,

@@ -25,24 +25,21 @@ void fill_walls(const lbm_ctx* c, A& a) {
     a.pk = port_ks<T>(c->port_value[0], c->port_kind[1], c->port_value[1]);
 }
 
-// The driving force (lbm_set_forcing) as the argument blocks carry it: h = F/2 (KArgs and MacroArgs) and g = (1 - wp/2) F with wp = 1/tau
-// as tau_inv is formed (KArgs), each formed in double and cast once. Zeros on every other context, whose kernels never read them.
-struct ForcingK { double gx, gy, hx, hy; };
-inline ForcingK forcing_ks(const lbm_ctx* c) {
-    if (c->collision != AR_STRICT_FORCED) return {0.0, 0.0, 0.0, 0.0};
-    const double wp = 1.0 / c->p.tau, k = 1.0 - 0.5 * wp;
-    return {k * c->collision_param, k * c->collision_param2, 0.5 * c->collision_param, 0.5 * c->collision_param2};
-}
+// The launch-uniform values of the context's collision model in the slots of KArgs: the model's values formed from tau and its
+// parameters (*_values) and stored through the slot map (put), both lbm_collision.hpp. Every slot the model does not own is zero; no
+// kernel of the model reads it. The outlet sponge owns none: its rates are the table wp_x.
 template <typename T>
-void fill_forcing(const lbm_ctx* c, KArgs<T>& a) {
-    const ForcingK k = forcing_ks(c);
-    a.frc_gx = (T)k.gx; a.frc_gy = (T)k.gy; a.frc_hx = (T)k.hx; a.frc_hy = (T)k.hy;
-}
-template <typename T>
-void fill_forcing(const lbm_ctx* c, MacroArgs<T>& m) {
-    const ForcingK k = forcing_ks(c);
-    m.forced = c->collision == AR_STRICT_FORCED ? 1 : 0;
-    m.frc_hx = (T)k.hx; m.frc_hy = (T)k.hy;
+void fill_collision(const lbm_ctx* c, KArgs<T>& a) {
+    const double tau = c->p.tau, p1 = c->collision_param, p2 = c->collision_param2;
+    clear_collision_slots(a);
+    switch (c->collision) {
+        case AR_STRICT: put(a, bgk_values<T>(tau)); break;
+        case AR_STRICT_LES: put(a, les_values<T>(tau, p1)); break;
+        case AR_STRICT_TRT: put(a, trt_values<T>(tau, p1)); break;
+        case AR_STRICT_FORCED: put(a, forced_values<T>(tau, p1, p2)); break;
+        case AR_STRICT_MRT: put(a, mrt_values<T>(tau, p1, p2)); break;
+        default: break;
+    }
 }
 
 // The inlet schedule's factor of iteration t in the element type, (T)s(t); 1 without a schedule (or before iteration 0).
@@ -68,7 +65,6 @@ KArgs<T> make_kargs(const lbm_ctx* c, int src, int dst, int t) {
     a.cyl_y = c->cyl_y;
     a.cyl_r2 = (double)(c->cyl_r * c->cyl_r);
     if (geom_masked(c)) a.mv = c->mview;
-    a.tau_inv = (T)(1.0 / c->p.tau);
     a.u_row = static_cast<const T*>(c->d_urow);
     a.unstable_t = c->d_unstable;
     a.t = t - c->tbase_host;
@@ -78,28 +74,9 @@ KArgs<T> make_kargs(const lbm_ctx* c, int src, int dst, int t) {
     a.y_lo2 = 0;
     a.y_cnt2 = 0;
     a.reverse = 0;
-    const double cs = c->collision == AR_STRICT_LES ? c->collision_param : 0.0;
-    a.les_tau = (T)c->p.tau;           // the Smagorinsky constants (read by LES instantiations only): tau, tau^2, 18 sqrt(2) Cs^2, in double
-    a.les_tau2 = (T)(c->p.tau * c->p.tau);
-    a.les_c = (T)(18.0 * std::sqrt(2.0) * (cs * cs));
-    // a TRT context: the rate of the odd parts, 1/tau_minus with (tau - 1/2)(tau_minus - 1/2) = magic, in that slot
-    // (and the two folded rates of the contracted arithmetic in the other two). An MRT context (never TRT or forced as well): the same
-    // three from its magic parameter, collision_param2; its bulk rate sb = collision_param and the folded (sb - wp)/(4 wp) of the contracted
-    // arithmetic take the first two slots of the forcing block (below, behind fill_forcing)
-    if (c->collision == AR_STRICT_TRT || c->collision == AR_STRICT_MRT) {
-        const double magic = c->collision == AR_STRICT_MRT ? c->collision_param2 : c->collision_param;
-        const double wp = 1.0 / c->p.tau, wm = 1.0 / (0.5 + magic / (c->p.tau - 0.5));
-        a.trt_wm = (T)wm;
-        a.trt_wa = (T)(0.5 * (wp + wm));
-        a.trt_wb = (T)(0.5 * (wp - wm));
-    }
+    fill_collision<T>(c, a);
     fill_walls<T>(c, a);
     a.sched = static_cast<const int*>(c->d_sched);
-    fill_forcing<T>(c, a);
-    if (c->collision == AR_STRICT_MRT) {
-        a.frc_gx = (T)c->collision_param;
-        a.frc_gy = (T)(0.25 * (c->collision_param * c->p.tau - 1.0));
-    }
     a.wp_x = static_cast<const T*>(c->d_wpx);       // (lbm_initialise: upload_sponge; nullptr without a sponge)
     return a;
 }
@@ -206,7 +183,9 @@ MacroArgs<T> make_macro_args(const lbm_ctx* c, const void* src, int t) {
     m.u_row = static_cast<const T*>(c->d_urow);
     fill_walls<T>(c, m);
     m.in_scale = inlet_scale<T>(c, t);
-    fill_forcing<T>(c, m);
+    m.forced = c->collision == AR_STRICT_FORCED ? 1 : 0;      // h = F/2 of the forced model's values; zeros, unread, on every other context
+    const ForcedK<T> fk = m.forced ? forced_values<T>(c->p.tau, c->collision_param, c->collision_param2) : ForcedK<T>{};
+    m.frc_hx = fk.hx; m.frc_hy = fk.hy;
     m.initial = 0;
     m.rho = m.ux = m.uy = nullptr; m.max_usq_bits = nullptr;
     return m;

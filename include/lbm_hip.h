@@ -758,6 +758,14 @@ int lbm_debug_plan_candidates(int nx, int ny, int precision, int arith, int num_
  * reports}. LBM_ERR_ARG: a null pointer, an unknown setter, a bad option, a buffer too small. */
 int lbm_debug_collision_setters(double tau, int precision, const char* options, const int* setter, const double* v1, const double* v2, int n,
                                 int* rc, char* texts, int cap, double* collision3);
+/* Test hook, callable without a device: what the step kernels of one collision model are handed per launch. On the context of
+ * lbm_debug_collision_setters (the given tau and precision) the one setter is applied with (v1, v2), numbered as there: 0, 1, 2, 3, 6,
+ * or -1 for plain BGK; the kernel arguments are filled as for a launch, and the model's values are read back by the code the kernels
+ * read them with. out receives them as doubles in the order BGK {wp}, Smagorinsky {tau, tau^2, C}, TRT {wp, wm, wa, wb}, forcing
+ * {wp, gx, gy, hx, hy}, MRT {wp, wm, wa, wb, sb, kb}, sponge {}, and behind them the raw content of the seven slots the models share:
+ * the four of the forcing block, then the three behind them. Returns the number of named values (the seven follow), or what the setter
+ * returned; LBM_ERR_ARG besides: a null pointer, an unknown setter, cap below the count. */
+int lbm_debug_collision_args(double tau, int precision, int setter, double v1, double v2, double* out, int cap);
 /* Test hook, callable without a device: lbm_set_sponge(width, tau_end) on a context of nx columns that is never initialised on a device
  * (the given tau and precision), then lbm_get_sponge into pair2 = {width, tau_end} and lbm_get_sponge_rate of every column into
  * rates[nx]. Returns what lbm_set_sponge returned (its text: lbm_last_error); the getters run either way. LBM_ERR_ARG besides: a null
